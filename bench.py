@@ -2,7 +2,7 @@
 """bench.py — INT8 images/sec of the BASELINE.json graphs on N MI355X GPUs.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c4|c5|c2] [--scaling weak|strong]
-                    [--batch B | --global-batch B] [--inflight P]
+                    [--batch B | --global-batch B] [--inflight P] [--dump-outputs DIR] [--full [--layer-table]]
 
 Default (what the driver runs): config C3 = MobileNetV1-INT8 full graph, batch 128 per GPU (BASELINE.json metric).
   c4 = ResNet50-INT8 batch 256, c5 = MobileNetV2-INT8 global batch 1024 split over the GPUs (strong scaling),
@@ -22,8 +22,16 @@ ONE global batch and scatters the shards (sharding.shard_range); every step each
 the layer loop) and the [rows, 1000] probabilities are all-gathered asynchronously, overlapping the next steps.
 weak: global batch = --batch x N; strong: global batch fixed (--global-batch).
 
-The JSON line carries `roofline` for the dominant kernel family (launch time measured live with HIP events on the launch
-stream) and `cpu_baseline` (oracle port of the reference algorithm on the host cores, bounded sample; rank 0, N = 1).
+A plain run does only what the headline needs: set up, warm up (W steps), time ONE window of exactly K steps, write the
+last step's outputs if --dump-outputs is given, print the JSON line.  `--full` adds everything else, as before: the median
+of 5 windows of K steps (unless --windows says otherwise), the oracle self-check of the last step, `single_stream` (the
+same steps strictly serial), `roofline` for the dominant kernel family (launch time measured live with HIP events on the
+launch stream) with `roofline_by_family` / `kernels` (and --layer-table), `cpu_baseline` (oracle port of the reference
+algorithm on the host cores, bounded sample; rank 0, N = 1) and, for N > 1 weak scaling, the `strong` point.
+
+--dump-outputs DIR: what the timed path computed in its last step (the [images, classes] probabilities; c2: the conv's
+int8 output), as DIR/<variable>.npy in float32; over the size budget a fixed, seeded sample of its rows.  Weights and
+inputs come from fixed seeds, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import importlib
@@ -65,17 +73,28 @@ def parse(argv=None):
     ap.add_argument("--batch", type=int, default=None, help="images per GPU and step (weak scaling); default: the config's")
     ap.add_argument("--scaling", choices=["weak", "strong"], default=None)
     ap.add_argument("--global-batch", type=int, default=None, help="strong scaling: images per step over all GPUs")
-    ap.add_argument("--windows", type=int, default=5, help="timed windows of --steps steps each, back to back; the median is reported")
+    ap.add_argument("--windows", type=int, default=None,
+                    help="timed windows of --steps steps each, back to back; the median is reported (default 1, 5 with --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the self-check, single_stream, roofline / per-kernel table, cpu_baseline and (N > 1) the strong point")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--no-selfcheck", action="store_true", help="skip the oracle comparison of the last step's output")
-    ap.add_argument("--layer-table", action="store_true", help="print the per-instruction timing table to stderr")
+    ap.add_argument("--layer-table", action="store_true", help="print the per-instruction timing table to stderr (implies --full)")
     ap.add_argument("--inflight", type=int, default=4,
                     help="predictors per GPU, each on its own host thread + HIP stream, each running WHOLE steps; the steps "
                          "are dealt round-robin, so --inflight steps are in flight at once (the reference's "
                          "one-predictor-per-thread serving model, cxx_api.h:103-137). 1 = strictly serial steps.")
     ap.add_argument("--res", type=int, default=224, help=argparse.SUPPRESS)  # tests only
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    args.full = args.full or args.layer_table
+    if args.windows is None:
+        args.windows = 5 if args.full else 1
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 # =====================================================================================================================
@@ -146,6 +165,7 @@ def spawn_ranks(args):
 # =====================================================================================================================
 class HipEngine:
     def __init__(self, torch, lite, wl, local_rank, dev, net, rows, image, cfg):
+        import numpy as np
         self.torch = torch
         self.stream = torch.cuda.Stream(dev)
         self.pred = lite.Predictor(local_rank, stream=self.stream.cuda_stream)
@@ -156,12 +176,12 @@ class HipEngine:
             p = o["pad"]
             self.pred.add_conv("conv2d", "xd", o["name"], o["w"], o["bias"], (o["stride"],) * 2, (p, p, p, p), (1, 1), 1, o["act"],
                                0.0, float(o["in_scale"]), o["w_scale"], float(o["out_scale"]), True)
-            self.out_var, self.plan = o["name"], None
+            self.out_var, self.plan, self.out_dtype = o["name"], None, np.int8
         else:
             wl.emit_graph(self.pred, net, rows, fuse_dwpw={"0": False, "1": True}.get(os.environ.get("PLHIP_BENCH_FUSE_DWPW", ""), None))
             self.plan = self.pred.graph_plan()
             self.pred.graph_lower()
-            self.out_var = net["output"]
+            self.out_var, self.out_dtype = net["output"], np.float32
         self.pred.set_input("image", image)
         self.pred.run(skip_io_copy=False)  # uploads the feed; PrepareForRun (weight pack, scale fold) everywhere
         self.pred.sync()
@@ -175,6 +195,10 @@ class HipEngine:
 
     def stage(self, dst, nbytes):
         self.pred.copy_var_to_device(self.out_var, dst.data_ptr(), nbytes)
+
+    def output(self):
+        """What this predictor's last step left in its output variable (a caller's result; synchronises)."""
+        return self.pred.get_var(self.out_var, self.out_dtype, max_bytes=1 << 30)
 
     def record(self):
         ev = self.torch.cuda.Event()
@@ -203,6 +227,9 @@ class DryEngine:
 
     def stage(self, dst, nbytes):
         dst[:self.fake.shape[0]].copy_(self.fake)
+
+    def output(self):
+        return self.fake.numpy()
 
     def record(self):
         return None
@@ -331,6 +358,26 @@ def oracle_selfcheck(np, pred, net, cfg, images, out_var):
     return {"ok": bad == 0 and out_var in checked, "images": n, "variables_checked": len(checked), "output": checked.get(out_var), "mismatches": bad}
 
 
+DUMP_BUDGET_BYTES = 60 << 20  # --dump-outputs: at most this much in all (float32)
+
+
+def dump_outputs(np, out_dir, arrays):
+    """--dump-outputs: every array as out_dir/<name>.npy in float32.  An array over what is left of the budget is written as
+    a fixed, seeded sample of its rows (sorted, the same rows in every run), so that two builds compare output for output."""
+    os.makedirs(out_dir, exist_ok=True)
+    left = DUMP_BUDGET_BYTES
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.nbytes > left:
+            if a.ndim == 0 or a[0].nbytes > left:
+                a = a.reshape(-1)
+            keep = min(a.shape[0], max(1, left // max(1, a[0].nbytes)))
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], size=keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        left -= a.nbytes
+        sys.stderr.write("bench.py: wrote %s/%s.npy %s float32\n" % (out_dir, name, list(a.shape)))
+
+
 def main():
     args = parse()
     wd = os.environ.get("PLHIP_BENCH_WATCHDOG")  # seconds: dump every thread's Python stack and exit if still running by then
@@ -398,10 +445,11 @@ def main():
         if dist.get_world_size() != args.gpus:
             raise SystemExit("only %d of %d ranks joined" % (dist.get_world_size(), args.gpus))
 
-    def run_case(scaling, global_batch_arg, per_gpu_arg, details):
+    def run_case(scaling, global_batch_arg, per_gpu_arg, details, dump_dir=None):
         """One timed case: build the predictors for this split, warm up, time `windows` x `steps` steps, tear down.
-        details: also the serial rate, the per-kernel table / roofline, the oracle self-check and the CPU baseline (headline
-        case only; the extra strong-scaling point of a multi-GPU run carries its rate alone)."""
+        details (--full, headline case only): also the serial rate, the per-kernel table / roofline, the oracle self-check and
+        the CPU baseline (the extra strong-scaling point of a multi-GPU run carries its rate alone).
+        dump_dir: write the last timed step's outputs there (--dump-outputs)."""
         # ---- work split ----
         per_gpu = per_gpu_arg or cfg["batch"]
         if scaling == "strong":
@@ -578,9 +626,9 @@ def main():
         if stagger_env is None and P > 1 and args.warmup >= P and not dry:
             # (the warm-up's own time may include first-touch costs: its estimate is capped low; later windows measure)
             stagger[0] = min((time.perf_counter() - tw) / args.warmup / P, 0.0002)
-        # EXACTLY args.steps steps per timed window, barrier + synchronize on both sides (the contract); the window is repeated
-        # back to back and the MEDIAN window is reported: a single 20-step window is ~9 ms here and moved the figure by 3-7 %
-        # from run to run.  min / median / max over the windows are in the line.
+        # EXACTLY args.steps steps per timed window, barrier + synchronize on both sides (the contract).  A plain run times one
+        # window; --windows (5 by default with --full) repeats it back to back and reports the MEDIAN window: a single 20-step
+        # window is ~9 ms and moved the figure by 3-7 % from run to run.  min / median / max over the windows are in the line.
         wins = []
         for _ in range(max(1, args.windows)):
             sync_all()
@@ -598,8 +646,10 @@ def main():
         elapsed = float(np.median(wins))
 
         # ---- outside the timed region: the gathered result of the last step is complete and in rank-major image order ----
+        gathered_out = None
         if use_dist and last_gather[0] is not None:
             g_ = last_gather[0].float().cpu().numpy().reshape(world, max_rows, classes)
+            blks = []
             for r in range(world):
                 l_, h_ = sharding.shard_range(global_batch, r, world)
                 blk = g_[r, :h_ - l_]
@@ -607,6 +657,19 @@ def main():
                     assert np.array_equal(blk[:, 0], np.arange(l_, h_, dtype=np.float32)), "gathered rows out of order"
                 else:
                     assert np.all(np.isfinite(blk)) and np.allclose(blk.sum(-1), 1.0, rtol=1e-3), "gathered probabilities are not distributions"
+                blks.append(blk)
+            gathered_out = np.concatenate(blks)
+
+        # ---- --dump-outputs, before anything is re-run: what a caller receives from the last timed step (N > 1: the gathered
+        # global batch; one rank: the output of the predictor that ran that step) ----
+        if dump_dir and rank == 0:
+            if use_dist:
+                out = gathered_out
+            else:
+                out = engines[(args.steps - 1) % P].output()
+                if cfg["model"] != "conv":
+                    out = out.reshape(rows, classes)
+            dump_outputs(np, dump_dir, {net["output"]: out})
 
         # ---- self-check, outside the timed region and BEFORE anything is re-run: what the last timed step of EVERY predictor
         # left in its variables for the first two images of this rank's shard must equal the oracle's result for the same bytes
@@ -740,11 +803,11 @@ def main():
                     roof=roof, fam_out=fam_out, selfcheck=selfcheck, cpu=cpu, net=net)
 
     head_scaling = args.scaling or cfg.get("scaling", "weak")
-    case = run_case(head_scaling, args.global_batch, args.batch, True)
+    case = run_case(head_scaling, args.global_batch, args.batch, args.full, args.dump_outputs)
     # a multi-GPU run of the default (weak: fixed images per GPU) config also times the STRONG point the north star names: one
     # large batch (1024 images) split over the GPUs; it goes into the line as `strong`, the headline stays as configured
     strong = None
-    if world > 1 and head_scaling == "weak" and args.scaling is None and cfg["model"] != "conv":
+    if args.full and world > 1 and head_scaling == "weak" and args.scaling is None and cfg["model"] != "conv":
         sc_ = run_case("strong", args.global_batch or 1024, None, False)
         strong = {"global_batch": sc_["global_batch"], "images_per_gpu": sc_["rows"], "value": round(sc_["global_batch"] * args.steps / sc_["elapsed"], 1),
                   "unit": "img/s", "ms_per_step": round(1e3 * sc_["elapsed"] / args.steps, 4), "scaling": "strong",
@@ -768,15 +831,17 @@ def main():
                        "parallelism": "batch split x%d (shard_range), RCCL network broadcast + input scatter at init, "
                                       "asynchronous all_gather of the probabilities per step" % world},
             "ms_per_step_note": "elapsed / steps with %d steps in flight: an aggregate issue interval, not a step latency "
-                                "(see single_stream)" % P,
+                                "(see single_stream, with --full)" % P,
             "whole_graph_TOP/s": round(val * ops_per_img / 1e12, 2),
             "whole_graph_frac_of_i8_mfma_peak": round(val * ops_per_img / 1e12 / MFMA_I8_PEAK_TOPS, 4),
             "windows": {"count": len(wins), "steps_each": args.steps,
                         "ms_per_step_min_median_max": [round(1e3 * min(wins) / args.steps, 4), round(1e3 * elapsed / args.steps, 4),
                                                        round(1e3 * max(wins) / args.steps, 4)]},
-            "selfcheck": selfcheck, "strong": strong,
-            "debug_knobs": dict(getattr(sys.modules.get("paddle_lite_amd.capi"), "KNOBS_SET", {})), "single_stream": serial, "roofline": roof, "roofline_by_family": by_family(fam_out), "kernels": fam_out, "cpu_baseline": cpu,
+            "debug_knobs": dict(getattr(sys.modules.get("paddle_lite_amd.capi"), "KNOBS_SET", {})),
         }
+        if args.full:
+            line.update({"selfcheck": selfcheck, "strong": strong, "single_stream": serial, "roofline": roof,
+                         "roofline_by_family": by_family(fam_out), "kernels": fam_out, "cpu_baseline": cpu})
         real_stdout.write(json.dumps(line) + "\n")
         real_stdout.flush()
     if use_dist:

@@ -14,6 +14,8 @@ Provenance of each array in a fixture:
                           tests/test_oracle.py asserts.
 The reference has no committed golden vectors for the int8 path, hence this script.
 """
+import hashlib
+import json
 import os
 import sys
 
@@ -113,8 +115,60 @@ def make_calib(seed):
     np.savez_compressed(os.path.join(HERE, "calib.npz"), x=x, scale=scale, q=q, deq=xf, seed=np.int32(seed))
 
 
+def reference_grid_cases():
+    """The random grid over which tests/test_oracle.py compares the oracle with the reference's conv_basic / basic_gemm, in
+    order: ("conv", shape, x, w) and ("gemm", None, a, b), seeded inputs (conv grid of conv_int8_compute_test.cc:676-731:
+    random k / stride / pad / dilation / group; GEMM grid gemm_int8_compute_test.cc:350-357, subset)."""
+    rng = np.random.default_rng(11)
+    for cin, cout, g in ((1, 1, 1), (17, 8, 1), (8, 8, 2), (6, 6, 6)):
+        for kh, kw in ((1, 1), (2, 3), (3, 3), (1, 2)):
+            for st in (1, 2):
+                for pads in ((0, 0, 0, 0), (1, 2, 0, 1), (2, 2, 2, 2)):
+                    for dl in (1, 2):
+                        for h in (1, 3, 5, 19):
+                            s = plref.shape(2, cin, h, h, cout, kh, kw, pads, (st, st), (dl, dl), g)
+                            oh, ow = plref.out_dims(s)
+                            if oh < 1 or ow < 1:
+                                continue
+                            x = rng.integers(-127, 128, (2, cin, h, h)).astype(np.int8)
+                            w = rng.integers(-127, 128, (cout, cin // g, kh, kw)).astype(np.int8)
+                            yield "conv", s, x, w
+    for m in (1, 3, 33, 38):
+        for n in (1, 13, 141):
+            for k in (1, 3, 59, 67):
+                a = rng.integers(-127, 128, (m, k)).astype(np.int8)
+                b = rng.integers(-127, 128, (k, n)).astype(np.int8)
+                yield "gemm", None, a, b
+
+
+def digest(*arrays):
+    """sha256 (16 hex digits) over dtype, shape and bytes of each array."""
+    h = hashlib.sha256()
+    for a in arrays:
+        h.update(("%s%s" % (a.dtype, a.shape)).encode())
+        h.update(np.ascontiguousarray(a).tobytes())
+    return h.hexdigest()[:16]
+
+
+def make_reference_grid():
+    """reference_grid.json: per case of reference_grid_cases() the digest of the inputs and of the REFERENCE's accumulators
+    on them (recorded results), so that the oracle is held to the reference bit for bit where oracle/_ref is not built."""
+    cases = []
+    for kind, s, a, b in reference_grid_cases():
+        acc = plref.ref_conv_acc(s, a, b) if kind == "conv" else plref.ref_gemm_acc(a, b)
+        cases.append([kind, digest(a, b), digest(acc)])
+    with open(os.path.join(HERE, "reference_grid.json"), "w") as f:
+        json.dump({"what": "[kind, digest(inputs), digest(reference accumulators)] per case of make_golden.reference_grid_cases()",
+                   "cases": cases}, f, indent=0)
+        f.write("\n")
+    return len(cases)
+
+
 if __name__ == "__main__":
     assert plref.ref_lib() is not None, "build oracle/_ref first (make -C oracle ref)"
+    if sys.argv[1:] == ["--reference-grid-only"]:
+        sys.exit(print("reference grid cases:", make_reference_grid()))
+    print("reference grid cases:", make_reference_grid())
     tot = 0
     for i, (name, spec) in enumerate(sorted(CONV_CASES.items())):
         tot += make_conv(name, spec, 1000 + i)

@@ -20,13 +20,13 @@ def _run(args, extra_env=None, timeout=300):
 
 
 def test_gpus_2_spawns_two_ranks_weak():
-    rc, out, err = _run(["--gpus", "2", "--steps", "7", "--warmup", "3", "--inflight", "2", "--batch", "5", "--res", "32"])
+    rc, out, err = _run(["--gpus", "2", "--steps", "7", "--warmup", "3", "--inflight", "2", "--batch", "5", "--res", "32", "--full"])
     assert rc == 0, err[-3000:]
     line = json.loads([l for l in out.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 2 and line["scaling"] == "weak" and line["config"]["global_batch"] == 10
     assert line["steps"] == 7 and line["data"] == "dryrun-no-compute" and line["value"] > 0
     assert line["metric"] == "INT8 images/sec MobileNetV1 224x224"
-    # the default (weak) multi-GPU run also carries the strong-scaling point: one large batch split over the ranks
+    # the default (weak) multi-GPU run with --full also carries the strong-scaling point: one large batch split over the ranks
     st = line["strong"]
     assert st and st["scaling"] == "strong" and st["global_batch"] == 1024 and st["images_per_gpu"] == 512 and st["value"] > 0
 
@@ -34,7 +34,7 @@ def test_gpus_2_spawns_two_ranks_weak():
 def test_strong_scaling_ragged_global_batch_three_ranks():
     # 7 images over 3 ranks -> shards of 3, 2, 2 rows: padded staging slots, rank-major order checked inside bench.py
     rc, out, err = _run(["--gpus", "3", "--steps", "9", "--warmup", "2", "--inflight", "3", "--scaling", "strong",
-                         "--global-batch", "7", "--config", "c5", "--res", "32"])
+                         "--global-batch", "7", "--config", "c5", "--res", "32", "--full"])
     assert rc == 0, err[-3000:]
     line = json.loads([l for l in out.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 3 and line["scaling"] == "strong" and line["config"]["global_batch"] == 7 and line["strong"] is None
@@ -73,13 +73,59 @@ def test_world_size_mismatch_is_an_error():
 
 
 def test_single_process_line_shape():
-    rc, out, err = _run(["--steps", "3", "--warmup", "1", "--batch", "4", "--res", "32"])
+    rc, out, err = _run(["--steps", "3", "--warmup", "1", "--batch", "4", "--res", "32", "--full"])
     assert rc == 0, err[-3000:]
     line = json.loads(out.strip().splitlines()[-1])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert k in line
     assert line["n_gpus"] == 1 and line["config"]["name"] == "c3"
+    assert line["windows"]["count"] == 5 and line["windows"]["steps_each"] == 3
+
+
+def test_plain_run_times_exactly_steps_and_carries_the_headline_only():
+    """Without --full: one timed window of exactly --steps steps, the headline fields, none of the --full extras."""
+    rc, out, err = _run(["--gpus", "1", "--steps", "6", "--warmup", "2", "--batch", "4", "--res", "32"])
+    assert rc == 0, err[-3000:]
+    lines = [l for l in out.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup"):
+        assert k in line
+    assert line["steps"] == 6 and line["warmup"] == 2 and line["ms_per_step"] > 0
+    assert line["windows"]["count"] == 1 and line["windows"]["steps_each"] == 6
+    assert line["metric"] == "INT8 images/sec MobileNetV1 224x224" and line["unit"] == "img/s" and line["higher_is_better"] is True
+    for k in ("selfcheck", "single_stream", "roofline", "roofline_by_family", "kernels", "cpu_baseline", "strong"):
+        assert k not in line
+
+
+def test_dump_outputs_writes_the_last_step_result(tmp_path):
+    """--dump-outputs DIR: the last timed step's probabilities as float32 .npy (the stand-in's first column is the image index),
+    one rank and the gathered result of two ranks."""
+    import numpy as np
+    d1, d2 = tmp_path / "one", tmp_path / "two"
+    rc, out, err = _run(["--steps", "5", "--warmup", "1", "--batch", "4", "--res", "32", "--dump-outputs", str(d1)])
+    assert rc == 0, err[-3000:]
+    a = np.load(d1 / "prob.npy")
+    assert a.dtype == np.float32 and a.shape == (4, 1000) and a[:, 0].tolist() == [0, 1, 2, 3]
+    rc, out, err = _run(["--gpus", "2", "--steps", "5", "--warmup", "1", "--batch", "3", "--res", "32", "--dump-outputs", str(d2)])
+    assert rc == 0, err[-3000:]
+    b = np.load(d2 / "prob.npy")
+    assert b.dtype == np.float32 and b.shape == (6, 1000) and b[:, 0].tolist() == list(range(6))
+
+
+def test_dump_outputs_samples_rows_over_the_budget(tmp_path, monkeypatch):
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 10 * 4 * 8)
+    a = np.arange(100 * 8, dtype=np.int32).reshape(100, 8)
+    bench.dump_outputs(np, str(tmp_path / "a"), {"y": a})
+    bench.dump_outputs(np, str(tmp_path / "b"), {"y": a})
+    s1, s2 = np.load(tmp_path / "a" / "y.npy"), np.load(tmp_path / "b" / "y.npy")
+    assert s1.dtype == np.float32 and s1.shape == (10, 8) and np.array_equal(s1, s2)   # the same rows every time
+    rows = s1[:, 0] / 8
+    assert np.all(np.diff(rows) > 0) and np.array_equal(s1, a[rows.astype(int)].astype(np.float32))
 
 
 def test_a_rank_dying_before_the_rendezvous_ends_the_launch_quickly():

@@ -1,11 +1,12 @@
 """CPU: pin the oracle (oracle/plref.c) against the golden vectors minted from the reference's own
-scalar oracle, and (in the authoring container) against the reference header compiled in place."""
+scalar oracle and the digests of its results over a random grid, and (where oracle/_ref is built) against the
+reference header compiled in place."""
 import os
 
 import numpy as np
 import pytest
 
-from conftest import golden_files, load_golden
+from conftest import GOLDEN, golden_files, load_golden
 
 CONV = golden_files("conv_")
 GEMM = golden_files("gemm_")
@@ -75,31 +76,25 @@ def test_fc_and_calib_golden(plref):
 
 
 def test_oracle_vs_reference_header_in_place(plref):
-    """Authoring container only: the reference's conv_basic / basic_gemm compiled from /root/reference."""
-    if plref.ref_lib() is None:
-        pytest.skip("oracle/_ref not built (reference tree absent)")
-    rng = np.random.default_rng(11)
-    # grid borrowed from conv_int8_compute_test.cc:676-731 (random k/stride/pad/dilation/group)
-    for cin, cout, g in ((1, 1, 1), (17, 8, 1), (8, 8, 2), (6, 6, 6)):
-        for kh, kw in ((1, 1), (2, 3), (3, 3), (1, 2)):
-            for st in (1, 2):
-                for pads in ((0, 0, 0, 0), (1, 2, 0, 1), (2, 2, 2, 2)):
-                    for dl in (1, 2):
-                        for h in (1, 3, 5, 19):
-                            s = plref.shape(2, cin, h, h, cout, kh, kw, pads, (st, st), (dl, dl), g)
-                            oh, ow = plref.out_dims(s)
-                            if oh < 1 or ow < 1:
-                                continue
-                            x = rng.integers(-127, 128, (2, cin, h, h)).astype(np.int8)
-                            w = rng.integers(-127, 128, (cout, cin // g, kh, kw)).astype(np.int8)
-                            assert np.array_equal(plref.conv2d_acc(s, x, w), plref.ref_conv_acc(s, x, w))
-    # GEMM grid gemm_int8_compute_test.cc:350-357 (subset)
-    for m in (1, 3, 33, 38):
-        for n in (1, 13, 141):
-            for k in (1, 3, 59, 67):
-                a = rng.integers(-127, 128, (m, k)).astype(np.int8)
-                b = rng.integers(-127, 128, (k, n)).astype(np.int8)
-                assert np.array_equal(plref.gemm_acc(a, b), plref.ref_gemm_acc(a, b))
+    """The reference's conv_basic / basic_gemm over a random grid (tests/golden/make_golden.py: reference_grid_cases): the
+    oracle's accumulators against the digests of the reference's, recorded on the same seeded inputs
+    (tests/golden/reference_grid.json), and against the reference header compiled in place (oracle/_ref) where it is built."""
+    import importlib.util
+    import json
+    spec = importlib.util.spec_from_file_location("make_golden", os.path.join(GOLDEN, "make_golden.py"))
+    mg = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mg)
+    recorded = json.load(open(os.path.join(GOLDEN, "reference_grid.json")))["cases"]
+    live = plref.ref_lib() is not None
+    n = 0
+    for i, (kind, s, a, b) in enumerate(mg.reference_grid_cases()):
+        assert [kind, mg.digest(a, b)] == recorded[i][:2], "case %d: the seeded inputs differ from the recorded grid" % i
+        ours = plref.conv2d_acc(s, a, b) if kind == "conv" else plref.gemm_acc(a, b)
+        assert mg.digest(ours) == recorded[i][2], "case %d: %s accumulators differ from the reference's" % (i, kind)
+        if live:
+            assert np.array_equal(ours, plref.ref_conv_acc(s, a, b) if kind == "conv" else plref.ref_gemm_acc(a, b))
+        n += 1
+    assert n == len(recorded) == 720
 
 
 def test_im2col_layout(plref):

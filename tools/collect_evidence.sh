@@ -16,7 +16,7 @@ mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 if [ "$PART" != "2" ]; then
 SQ="SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU"
-B="--no-cpu-baseline --no-selfcheck --windows 1"
+B="--full --no-cpu-baseline --no-selfcheck --windows 1"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/stats_default -o p --output-format csv -- python $R/bench.py $B --steps 30 > $O/bench_under_rocprof_default.json 2> $O/stats_default.err || exit 1
 echo "stats default done"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/stats_serial -o p --output-format csv -- python $R/bench.py $B --inflight 1 --steps 30 > $O/bench_under_rocprof_serial.json 2> $O/stats_serial.err || exit 1
@@ -64,14 +64,14 @@ done
 PLHIP_FUSED_SMALL=2 timeout -k 10 200 python tools/opbench.py fused 2>&1 | cut -c1-110 | grep "fused\|2-krn" > $O/opbench_fused_small_two_blocks.txt || exit 1
 [ -x tools/_probe_coexec ] && ./tools/_probe_coexec > $O/probe_coexec.txt 2>&1
 [ -x tools/_probe_rtz ] && ./tools/_probe_rtz > $O/probe_cvt_rtz.txt 2>&1
-PLHIP_FUSED_STREAM=0 PLHIP_FUSED_SMALL=0 timeout -k 10 200 python bench.py --no-cpu-baseline > $O/bench_stream_off.json 2>/dev/null || exit 1
-PLHIP_FUSED_STREAM=0 PLHIP_FUSED_SMALL=0 timeout -k 10 200 python bench.py --no-cpu-baseline --inflight 1 > $O/bench_stream_off_inflight1.json 2>/dev/null || exit 1
-PLHIP_FUSED_STREAM=2 PLHIP_FUSED_SMALL=0 timeout -k 10 200 python bench.py --no-cpu-baseline > $O/bench_stride1_only.json 2>/dev/null || exit 1
-PLHIP_FUSED_SMALL=0 timeout -k 10 200 python bench.py --no-cpu-baseline > $O/bench_small_off.json 2>/dev/null || exit 1
-PLHIP_FUSED_SMALL=2 timeout -k 10 200 python bench.py --no-cpu-baseline > $O/bench_small_two_blocks.json 2>/dev/null || exit 1
-PLHIP_BENCH_FUSE_DWPW=1 timeout -k 10 200 python bench.py --no-cpu-baseline > $O/bench_no_pool_tail.json 2>/dev/null || exit 1
-PLHIP_BENCH_FUSE_DWPW=0 timeout -k 10 200 python bench.py --no-cpu-baseline > $O/bench_dwpw_off.json 2>/dev/null || exit 1
-PLHIP_BENCH_FUSE_DWPW=0 timeout -k 10 200 python bench.py --no-cpu-baseline --inflight 1 > $O/bench_dwpw_off_inflight1.json 2>/dev/null || exit 1
+PLHIP_FUSED_STREAM=0 PLHIP_FUSED_SMALL=0 timeout -k 10 200 python bench.py --full --no-cpu-baseline > $O/bench_stream_off.json 2>/dev/null || exit 1
+PLHIP_FUSED_STREAM=0 PLHIP_FUSED_SMALL=0 timeout -k 10 200 python bench.py --full --no-cpu-baseline --inflight 1 > $O/bench_stream_off_inflight1.json 2>/dev/null || exit 1
+PLHIP_FUSED_STREAM=2 PLHIP_FUSED_SMALL=0 timeout -k 10 200 python bench.py --full --no-cpu-baseline > $O/bench_stride1_only.json 2>/dev/null || exit 1
+PLHIP_FUSED_SMALL=0 timeout -k 10 200 python bench.py --full --no-cpu-baseline > $O/bench_small_off.json 2>/dev/null || exit 1
+PLHIP_FUSED_SMALL=2 timeout -k 10 200 python bench.py --full --no-cpu-baseline > $O/bench_small_two_blocks.json 2>/dev/null || exit 1
+PLHIP_BENCH_FUSE_DWPW=1 timeout -k 10 200 python bench.py --full --no-cpu-baseline > $O/bench_no_pool_tail.json 2>/dev/null || exit 1
+PLHIP_BENCH_FUSE_DWPW=0 timeout -k 10 200 python bench.py --full --no-cpu-baseline > $O/bench_dwpw_off.json 2>/dev/null || exit 1
+PLHIP_BENCH_FUSE_DWPW=0 timeout -k 10 200 python bench.py --full --no-cpu-baseline --inflight 1 > $O/bench_dwpw_off_inflight1.json 2>/dev/null || exit 1
 timeout -k 10 200 python tools/opbench.py all --batch 256 2>&1 | cut -c1-110 | grep -v "fused\|2-krn" > $O/opbench_b256.txt || exit 1
 PLHIP_GEMM_WIDE=0 timeout -k 10 200 python tools/opbench.py pw 2>&1 | cut -c1-110 > $O/opbench_pw_wide_off.txt || exit 1
 for l in pw8 pw6 pw13; do PLHIP_GEMM_DEBUG=32 timeout -k 10 100 python tools/wide_timeline.py $l > $O/wide_timeline_$l.txt 2>&1 || exit 1; done
@@ -92,15 +92,15 @@ PLHIP_PATCH_DEBUG=32 timeout -k 10 100 python tools/patch_timeline.py --n 256 --
 PLHIP_PATCH_DEBUG=32 timeout -k 10 100 python tools/patch_timeline.py --n 256 --cin 128 --cout 128 --hw 56 --stride 2 > $O/patch_timeline_res3a_s2.txt 2>&1 || exit 1
 PLHIP_PATCH_DEBUG=32 timeout -k 10 100 python tools/patch_timeline.py --n 256 --cin 512 --cout 512 --hw 14 --stride 2 > $O/patch_timeline_res5a_s2.txt 2>&1 || exit 1
 echo "tables done"
-timeout -k 10 400 python bench.py --layer-table > $O/bench.json 2> $O/layer_table.txt || exit 1
-timeout -k 10 200 python bench.py --no-cpu-baseline --inflight 1 > $O/bench_inflight1.json 2>/dev/null || exit 1
-timeout -k 10 200 python bench.py --steps 20 --warmup 5 > $O/bench_driver_form.json 2>/dev/null || exit 1
+timeout -k 10 400 python bench.py --full --layer-table > $O/bench.json 2> $O/layer_table.txt || exit 1
+timeout -k 10 200 python bench.py --full --no-cpu-baseline --inflight 1 > $O/bench_inflight1.json 2>/dev/null || exit 1
+timeout -k 10 200 python bench.py --full --steps 20 --warmup 5 > $O/bench_driver_form.json 2>/dev/null || exit 1
 echo "c3 done"
 # the other BASELINE configs (whole graphs, their own batch), with their cpu_baseline legs and per-instruction tables
-timeout -k 10 400 python bench.py --config c4 --layer-table > $O/bench_c4.json 2> $O/layer_table_c4.txt || exit 1
-timeout -k 10 400 python bench.py --config c5 --layer-table > $O/bench_c5.json 2> $O/layer_table_c5.txt || exit 1
-timeout -k 10 300 python bench.py --config c2 > $O/bench_c2.json 2>/dev/null || exit 1
+timeout -k 10 400 python bench.py --full --config c4 --layer-table > $O/bench_c4.json 2> $O/layer_table_c4.txt || exit 1
+timeout -k 10 400 python bench.py --full --config c5 --layer-table > $O/bench_c5.json 2> $O/layer_table_c5.txt || exit 1
+timeout -k 10 300 python bench.py --full --config c2 > $O/bench_c2.json 2>/dev/null || exit 1
 # the N > 1 data path on one GPU: one rank, RCCL broadcast / scatter / per-step all_gather
-PLHIP_BENCH_FORCE_DIST=1 PLHIP_BENCH_WATCHDOG=200 timeout -k 10 300 python bench.py --no-cpu-baseline > $O/bench_force_dist.json 2> $O/force_dist.err || { echo "force_dist rc=$?"; tail -30 $O/force_dist.err; exit 1; }
+PLHIP_BENCH_FORCE_DIST=1 PLHIP_BENCH_WATCHDOG=200 timeout -k 10 300 python bench.py --full --no-cpu-baseline > $O/bench_force_dist.json 2> $O/force_dist.err || { echo "force_dist rc=$?"; tail -30 $O/force_dist.err; exit 1; }
 timeout -k 10 100 python tools/c2bench.py > $O/c2bench.txt 2>&1 || exit 1
 tail -c 400 $O/bench.json
