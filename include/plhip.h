@@ -166,6 +166,27 @@ plhip_status plhip_dwpw_fused_int8(plhip_ctx* ctx, const plhip_conv_desc* dw, co
                                    const float* pw_scale, const float* pw_bias, int pw_act, float pw_alpha, void* y,
                                    plhip_out_kind out);
 
+/* ---- fused depthwise 3x3 [int8_out] -> 1x1 conv with the conv's graph tail (fusion G, graph-level fusion) ----
+ * Replaces the instruction pair  depthwise_conv2d[int8_out] ; conv2d 1x1 s1 p0 g1 [+ residual add + calib]  of the MobileNetV2
+ * blocks when the depthwise output has no other consumer.  Bit-identical to plhip_depthwise_conv_int8 (PLHIP_OUT_I8) followed by
+ * plhip_conv2d_int8 (no tail) or plhip_conv2d_int8_fused (tail); the int8 intermediate never leaves the CU.
+ * dw: the depthwise conv; dw_scale / dw_bias its folded int8-out scale / bias.  pw_cout, pw_w_packed (plhip_pack_conv_weights of
+ * the 1x1 conv [n, C, oh, ow] -> pw_cout), pw_scale / pw_bias, pw_act / pw_alpha describe the 1x1 conv; y: [n, pw_cout, oh, ow]
+ * of kind `out`.  The tail (residual, residual_relu, y_i8, calib_scale) has plhip_conv2d_int8_fused's meaning and needs
+ * PLHIP_OUT_F32; y may then be NULL when y_i8 is set.
+ * Envelope, all at run time: depthwise 3x3, channel multiplier 1 (groups == cin == cout), dilation 1, stride 1 or 2 (the same
+ * in both directions), each padding 0 or 1, activation none / relu / relu6 / leaky; any n, h, w >= 1; cin % 16 == 0 and
+ * cin <= 1024; pw_cout % 8 == 0 and pw_cout <= 1024; every element offset of the input and of the output below 2^31; out
+ * PLHIP_OUT_I32_ACC, PLHIP_OUT_F32 or PLHIP_OUT_I8, and a tail only with PLHIP_OUT_F32.  Outside it the call returns
+ * PLHIP_ERR_UNSUPPORTED and launches nothing; plhip_dw_conv1x1_fused_supported (host logic, no device query) answers the
+ * same question up front (has_tail: 1 when a residual or a calib copy is requested). */
+int plhip_dw_conv1x1_fused_supported(const plhip_conv_desc* dw, int pw_cout, plhip_out_kind out, int has_tail);
+plhip_status plhip_dw_conv1x1_fused_int8(plhip_ctx* ctx, const plhip_conv_desc* dw, const int8_t* x,
+                                         const int8_t* dw_w_oihw, const float* dw_scale, const float* dw_bias, int pw_cout,
+                                         const void* pw_w_packed, const float* pw_scale, const float* pw_bias, int pw_act,
+                                         float pw_alpha, void* y, plhip_out_kind out, const float* residual,
+                                         int residual_relu, int8_t* y_i8, float calib_scale);
+
 /* ---- fc ----
  * Replaces: FcCompute<kInt8,*>::Run (lite/kernels/arm/fc_compute.cc:229-344) -> gemm_s8 / gemv_int8
  * (lite/backends/arm/math/gemm_s8.cc:23-47, gemv_arm_int8.cc:701-760).
@@ -222,7 +243,8 @@ plhip_status plhip_selftest(plhip_ctx* ctx);
 
 /* ---- diagnostics (no effect on results): switches of the shipped library are set HERE, never through the environment,
  * so that a stray variable cannot change which kernel a benchmark measures.  Keys: the A/B knobs of DESIGN.md 3.6 without
- * their former PLHIP_ prefix ("GEMM_WIDE", "CONV_PATCH", "DW_STAGE", "GEMM_DEBUG", ...), "fused_exp", and "fused_stamps" (1 = the fused
+ * their former PLHIP_ prefix ("GEMM_WIDE", "CONV_PATCH", "DW_STAGE", "GEMM_DEBUG", ...; "DWCONV_FUSED" = 0: plhip_dw_conv1x1_fused_supported refuses every shape, so callers
+ * run the two instructions), "fused_exp", and "fused_stamps" (1 = the fused
  * depthwise -> pointwise kernel records its in-kernel timeline, read back with plhip_debug_read_fw_stamps:
  * [tile][wave][16] shader-clock stamps).  Returns 0, or -1 for an unknown key. ---- */
 int plhip_debug_set(const char* key, int value);

@@ -23,7 +23,7 @@ EXPORTS = [
     "plhip_memcpy_d2h", "plhip_memcpy_d2d", "plhip_memset", "plhip_stream_sync", "plhip_event_create",
     "plhip_event_record", "plhip_event_elapsed_ms", "plhip_event_destroy",
     "plhip_conv_packed_weight_bytes", "plhip_pack_conv_weights", "plhip_conv_workspace_bytes",
-    "plhip_conv2d_int8", "plhip_conv2d_int8_fused", "plhip_conv_impl_name", "plhip_depthwise_conv_int8", "plhip_dwpw_fused_int8", "plhip_dwpw_fused_supported", "plhip_graph_begin", "plhip_graph_end", "plhip_graph_launch", "plhip_graph_destroy",
+    "plhip_conv2d_int8", "plhip_conv2d_int8_fused", "plhip_conv_impl_name", "plhip_depthwise_conv_int8", "plhip_dwpw_fused_int8", "plhip_dwpw_fused_supported", "plhip_dw_conv1x1_fused_int8", "plhip_dw_conv1x1_fused_supported", "plhip_graph_begin", "plhip_graph_end", "plhip_graph_launch", "plhip_graph_destroy",
     "plhip_fc_packed_weight_bytes", "plhip_pack_fc_weights", "plhip_fc_int8",
     "plhip_calib_f32_to_i8", "plhip_calib_i8_to_f32", "plhip_global_avg_pool_f32", "plhip_softmax_f32",
     "plhip_pool2d_f32", "plhip_pool2d_max_i8", "plhip_elementwise_add_f32", "plhip_selftest",
@@ -74,7 +74,8 @@ _lib = None
 # bench.py prints the dict in its JSON line, so a measurement taken with a knob says so.
 KNOBS = ("STEM_MFMA", "CONV_PATCH", "CONV_PATCH_S2", "PATCH_DEBUG", "PATCH_DELAY", "STEM7", "DW_STAGE", "DW_STAGE_NP2", "DW_FASTV",
          "DW5_DIRECT", "DW_RS1", "DW_RS2", "GEMM_VARIANT", "GEMM_AREG", "GEMM_MA", "GEMM_DEBUG", "SUBSAMPLE_1X1", "GEMM_TR", "TR_DELAY",
-         "TR_CFG", "GEMM_WIDE", "WIDE_NTT", "FC_MFMA", "IMPLICIT_GEMM", "FUSED_STREAM", "FUSED_SMALL")
+         "TR_CFG", "GEMM_WIDE", "WIDE_NTT", "FC_MFMA", "IMPLICIT_GEMM", "FUSED_STREAM", "FUSED_SMALL",
+         "DWCONV_FUSED")
 KNOBS_SET = {}
 
 
@@ -133,6 +134,10 @@ def load():
     L.plhip_dwpw_fused_int8.argtypes = [vp, C.POINTER(ConvDesc), vp, vp, vp, vp, i32, vp, vp, vp, i32, f32, vp, i32]
     L.plhip_dwpw_fused_supported.argtypes = [C.POINTER(ConvDesc), i32, i32]
     L.plhip_dwpw_fused_supported.restype = i32
+    L.plhip_dw_conv1x1_fused_int8.argtypes = [vp, C.POINTER(ConvDesc), vp, vp, vp, vp, i32, vp, vp, vp, i32, f32, vp, i32,
+                                              vp, i32, vp, f32]
+    L.plhip_dw_conv1x1_fused_supported.argtypes = [C.POINTER(ConvDesc), i32, i32, i32]
+    L.plhip_dw_conv1x1_fused_supported.restype = i32
     L.plhip_fc_packed_weight_bytes.argtypes = [i32, i32]
     L.plhip_fc_packed_weight_bytes.restype = sz
     L.plhip_pack_fc_weights.argtypes = [vp, i32, i32, vp, vp]
@@ -300,6 +305,40 @@ class Context:
                 ([dbp] if b_pw is not None else []):
             self.free(p)
         return y
+
+    def dw_conv1x1_fused(self, d_dw, x, w_dw, s_dw, b_dw, w_pw, s_pw, b_pw, pw_act, pw_alpha, out_kind,
+                         residual=None, residual_relu=0, calib_scale=None, want_y=True):
+        """Fused depthwise 3x3 -> 1x1 conv with the conv's graph tail (plhip_dw_conv1x1_fused_int8) on host arrays:
+        returns (y or None, y_i8 or None); y is of `out_kind`, y_i8 the calib copy when calib_scale is given."""
+        oh, ow = out_hw(d_dw)
+        cout = w_pw.shape[0]
+        shape = (d_dw.n, cout, oh, ow)
+        d_pw = conv_desc(d_dw.n, d_dw.cin, oh, ow, cout, 1, 1, act=pw_act, alpha=pw_alpha)
+        dx = self.to_device(np.ascontiguousarray(x, np.int8))
+        dwd = self.to_device(np.ascontiguousarray(w_dw, np.int8))
+        dsd = self.to_device(np.ascontiguousarray(s_dw, np.float32))
+        dbd = self.to_device(np.ascontiguousarray(b_dw, np.float32)) if b_dw is not None else C.c_void_p()
+        dwp_raw = self.to_device(np.ascontiguousarray(w_pw, np.int8))
+        dwp = self.malloc(self.L.plhip_conv_packed_weight_bytes(C.byref(d_pw)))
+        self.check(self.L.plhip_pack_conv_weights(self.h, C.byref(d_pw), dwp_raw, dwp), "pack")
+        dsp = self.to_device(np.ascontiguousarray(s_pw, np.float32)) if s_pw is not None else C.c_void_p()
+        dbp = self.to_device(np.ascontiguousarray(b_pw, np.float32)) if b_pw is not None else C.c_void_p()
+        dr = self.to_device(np.ascontiguousarray(residual, np.float32)) if residual is not None else C.c_void_p()
+        n_out = int(np.prod(shape))
+        esz = 1 if out_kind == OUT_I8 else 4
+        dy = self.malloc(n_out * esz) if want_y else C.c_void_p()
+        dyq = self.malloc(n_out) if calib_scale is not None else C.c_void_p()
+        self.check(self.L.plhip_dw_conv1x1_fused_int8(self.h, C.byref(d_dw), dx, dwd, dsd, dbd, cout, dwp, dsp, dbp, pw_act,
+                                                      pw_alpha, dy, out_kind, dr, int(residual_relu), dyq,
+                                                      float(calib_scale) if calib_scale is not None else 0.0),
+                   "dw_conv1x1_fused")
+        y = self.to_host(dy, shape, _OUT_DTYPE[out_kind]) if want_y else None
+        yq = self.to_host(dyq, shape, np.int8) if calib_scale is not None else None
+        for p in [dx, dwd, dsd, dwp_raw, dwp] + ([dy] if want_y else []) + ([dyq] if calib_scale is not None else []) + \
+                ([dbd] if b_dw is not None else []) + ([dsp] if s_pw is not None else []) + ([dbp] if b_pw is not None else []) + \
+                ([dr] if residual is not None else []):
+            self.free(p)
+        return y, yq
 
     def fc(self, x, w, scale, bias, relu, out_kind):
         x = np.ascontiguousarray(x, np.int8)

@@ -782,6 +782,83 @@ plhip_status plhip_dwpw_fused_int8(plhip_ctx* ctx, const plhip_conv_desc* dw, co
   return PLHIP_OK;
 }
 
+// ------------------------------------------------------------------ fused depthwise -> 1x1 conv with the conv's tail (fusion G)
+// geometry + launch plan; false: outside the kernel's envelope (the caller runs the two instructions).  Host logic only.
+static bool dw_conv1x1_plan(const plhip_conv_desc* dw, int pw_cout, plhip_out_kind out, int has_tail, plhip::DwConvArgs* a,
+                            const char** why) {
+  ConvGeom g;
+  *why = "bad depthwise descriptor";
+  if (!dw || !conv_geom(dw, &g)) return false;
+  *why = "output kind";
+  if (out != PLHIP_OUT_I32_ACC && out != PLHIP_OUT_F32 && out != PLHIP_OUT_I8) return false;
+  *why = "a graph tail needs fp32 output";
+  if (has_tail && out != PLHIP_OUT_F32) return false;
+  *why = "first conv must be a 3x3 depthwise conv, channel multiplier 1, dilation 1, stride 1 | 2, paddings 0 | 1";
+  if (dw->groups != dw->cin || dw->cin != dw->cout || dw->kh != 3 || dw->kw != 3 || dw->dil[0] != 1 || dw->dil[1] != 1 ||
+      dw->stride[0] != dw->stride[1] || (dw->stride[0] != 1 && dw->stride[0] != 2))
+    return false;
+  for (int i = 0; i < 4; ++i)
+    if (dw->pad[i] != 0 && dw->pad[i] != 1) return false;
+  *why = "unsupported depthwise activation";
+  if (dw->act != PLHIP_ACT_NONE && dw->act != PLHIP_ACT_RELU && dw->act != PLHIP_ACT_RELU6 && dw->act != PLHIP_ACT_LEAKY_RELU)
+    return false;
+  memset(a, 0, sizeof(*a));
+  a->dw_act = dw->act;
+  a->dw_alpha = dw->act_alpha;
+  a->n = dw->n; a->C = dw->cin; a->h = dw->h; a->w = dw->w; a->oh = g.oh; a->ow = g.ow;
+  a->pt = dw->pad[0]; a->pl = dw->pad[2]; a->stride = dw->stride[0];
+  a->M = pw_cout;
+  *why = "fused depthwise -> 1x1 kernel switched off (diagnostics knob DWCONV_FUSED = 0)";
+  if (!plhip::knob("DWCONV_FUSED", 1)) return false;
+  *why = "shape outside the fused kernel (C % 16, C <= 1024, M % 8, M <= 1024, 32-bit element offsets)";
+  return plhip::dw_conv1x1_plan(a);
+}
+
+int plhip_dw_conv1x1_fused_supported(const plhip_conv_desc* dw, int pw_cout, plhip_out_kind out, int has_tail) {
+  plhip::DwConvArgs a;
+  const char* why;
+  return dw_conv1x1_plan(dw, pw_cout, out, has_tail, &a, &why) ? 1 : 0;
+}
+
+plhip_status plhip_dw_conv1x1_fused_int8(plhip_ctx* ctx, const plhip_conv_desc* dw, const int8_t* x, const int8_t* dw_w_oihw,
+                                         const float* dw_scale, const float* dw_bias, int pw_cout, const void* pw_w_packed,
+                                         const float* pw_scale, const float* pw_bias, int pw_act, float pw_alpha, void* y,
+                                         plhip_out_kind out, const float* residual, int residual_relu, int8_t* y_i8,
+                                         float calib_scale) {
+  const int has_tail = residual || y_i8;
+  if (!ctx || !dw || !x || !dw_w_oihw || !dw_scale || !pw_w_packed || (!y && !y_i8) || pw_cout < 1)
+    return fail(ctx, PLHIP_ERR_INVALID, "plhip_dw_conv1x1_fused_int8: null / bad argument");
+  if (out != PLHIP_OUT_I32_ACC && out != PLHIP_OUT_F32 && out != PLHIP_OUT_I8)
+    return fail(ctx, PLHIP_ERR_INVALID, "plhip_dw_conv1x1_fused_int8: bad out kind");
+  if (out != PLHIP_OUT_I32_ACC && !pw_scale) return fail(ctx, PLHIP_ERR_INVALID, "plhip_dw_conv1x1_fused_int8: pw_scale required");
+  if (pw_act != PLHIP_ACT_NONE && pw_act != PLHIP_ACT_RELU && pw_act != PLHIP_ACT_RELU6 && pw_act != PLHIP_ACT_LEAKY_RELU)
+    return fail(ctx, PLHIP_ERR_UNSUPPORTED, "plhip_dw_conv1x1_fused_int8: unsupported 1x1 activation");
+  plhip::DwConvArgs a;
+  const char* why;
+  if (!dw_conv1x1_plan(dw, pw_cout, out, has_tail, &a, &why)) return fail(ctx, PLHIP_ERR_UNSUPPORTED, "plhip_dw_conv1x1_fused_int8: %s", why);
+  if (!y && out != PLHIP_OUT_F32) return fail(ctx, PLHIP_ERR_INVALID, "plhip_dw_conv1x1_fused_int8: y required");
+  if (y_i8 && !(calib_scale > 0.f)) return fail(ctx, PLHIP_ERR_INVALID, "plhip_dw_conv1x1_fused_int8: calib scale must be > 0");
+  if (residual_relu && !residual) return fail(ctx, PLHIP_ERR_INVALID, "plhip_dw_conv1x1_fused_int8: residual_relu without a residual");
+  if (!aligned(pw_w_packed, 16)) return fail(ctx, PLHIP_ERR_INVALID, "plhip_dw_conv1x1_fused_int8: packed weights must be 16-byte aligned");
+  a.x = x;
+  a.dw_w = dw_w_oihw;
+  a.dw_scale = dw_scale;
+  a.dw_bias = dw_bias;
+  a.wp = (const int8_t*)pw_w_packed;
+  a.y = y;
+  a.scale = pw_scale;
+  a.bias = pw_bias;
+  a.act = pw_act;
+  a.alpha = pw_alpha;
+  a.res = residual;
+  a.res_relu = residual_relu;
+  a.y2 = y_i8;
+  a.inv_scale2 = y_i8 ? 1.f / calib_scale : 0.f;  // type_trans.cc:45
+  plhip::launch_dw_conv1x1(a, (int)out, ctx->stream);
+  LAUNCHCHK(ctx, "dw_conv1x1_fused");
+  return PLHIP_OK;
+}
+
 // ------------------------------------------------------------------ fc
 size_t plhip_fc_packed_weight_bytes(int k, int n) {
   if (k < 1 || n < 1) return 0;
@@ -963,7 +1040,7 @@ Knob g_knobs[] = {
     {"STEM7", 0, false}, {"DW_STAGE", 0, false}, {"DW_STAGE_NP2", 0, false}, {"DW_FASTV", 0, false}, {"DW5_DIRECT", 0, false},
     {"DW_RS1", 0, false}, {"DW_RS2", 0, false}, {"GEMM_VARIANT", 0, false}, {"GEMM_AREG", 0, false}, {"GEMM_MA", 0, false},
     {"GEMM_DEBUG", 0, false}, {"SUBSAMPLE_1X1", 0, false}, {"GEMM_TR", 0, false}, {"TR_DELAY", 0, false}, {"TR_CFG", 0, false},
-    {"GEMM_WIDE", 0, false}, {"WIDE_NTT", 0, false}, {"FC_MFMA", 0, false}, {"IMPLICIT_GEMM", 0, false}, {"FUSED_STREAM", 0, false}, {"FUSED_SMALL", 0, false}};
+    {"GEMM_WIDE", 0, false}, {"WIDE_NTT", 0, false}, {"FC_MFMA", 0, false}, {"IMPLICIT_GEMM", 0, false}, {"FUSED_STREAM", 0, false}, {"FUSED_SMALL", 0, false}, {"DWCONV_FUSED", 0, false}};
 }  // namespace
 int knob(const char* name, int dflt) {
   for (const Knob& k : g_knobs)

@@ -178,6 +178,39 @@ int debug_read_fw_stamps(void* dst, size_t bytes);
 int debug_read_fs_stamps(void* dst, size_t bytes);  // the streaming kernel's
 int debug_read_f7_stamps(void* dst, size_t bytes);  // the small-plane kernel's
 
+// fused depthwise 3x3 (int8 out) -> 1x1 conv with the conv's graph tail (fused_dwconv_i8.hip, fusion G)
+struct DwConvArgs {
+  const int8_t* x;        // [n, C, h, w]
+  const int8_t* dw_w;     // [C, 1, 3, 3]
+  const float* dw_scale;  // folded depthwise scale / bias (int8-out folding), per channel
+  const float* dw_bias;   // or nullptr
+  int dw_act;
+  float dw_alpha;
+  int n, C, h, w, oh, ow, pt, pl, stride;
+  int M;                  // 1x1 conv output channels
+  const int8_t* wp;       // its weights as plhip_pack_conv_weights packs them: [MT32][KS][64][16]
+  void* y;                // [n, M, oh, ow] of the output kind (fp32: may be nullptr when y2 is set)
+  const float* scale;     // [M] folded scale (unused for I32)
+  const float* bias;      // [M] or nullptr
+  int act;
+  float alpha;
+  const float* res;       // fp32 tail, as GemmArgs: residual (+ relu), calib copy y2 = round_sat_i8(v * inv_scale2)
+  int res_relu;
+  int8_t* y2;
+  float inv_scale2;
+  // launch plan (dw_conv1x1_plan): K-steps of 32 channels; 32-row m tiles in all / per block (grid.y = m groups); tile = TR
+  // output rows x CW columns of one image (CW = ow, or 128-column segments of wider rows) = NT 32-pixel n tiles; tiles per
+  // image (tr_tiles x cw_tiles); staged input rows IR of WP bytes (LDS column = input column - CW-segment start + 4); stage
+  // units per row (dwords when w % 4 == 0, else bytes) and rows per wave pass; accumulators per wave; LDS bytes
+  int KS, mt32, mtpb, mgroups, TR, CW, NT, tr_tiles, cw_tiles, tpi, IR, WP, dword_stage, wu, rpp, nacc;
+  unsigned ir_m, owq_m, tr_m, cw_m, tpi_m, ctl_m;  // fastdiv_u31 (magic, shift) for IR, CW / 4 quads, TR, CW, tpi, cw_tiles
+  int ir_s, owq_s, tr_s, cw_s, tpi_s, ctl_s;
+  size_t lds;
+};
+// fills the plan from (n, C, h, w, oh, ow, stride, M); false = shape outside the kernel's envelope
+bool dw_conv1x1_plan(DwConvArgs* a);
+void launch_dw_conv1x1(const DwConvArgs& a, int out, hipStream_t s);
+
 int launch_gemm_i8(const GemmArgs& g, int ma, int out, bool vec_store, bool aligned_loads, hipStream_t s);  // 0 or -3
 // second-generation ring kernel (gemm_tr_i8.hip); false = shape outside it, the caller falls back
 bool launch_gemm_tr(const GemmArgs& g, int out, hipStream_t s);

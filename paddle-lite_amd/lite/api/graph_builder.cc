@@ -180,7 +180,7 @@ void GraphBuilder::FuseSteps(std::vector<Step>* steps_io) {
   // only where the fused kernel takes the pair, which needs the depthwise conv's input shape: propagated from the feeds through
   // conv / calib / elementwise ops (anything else: shape unknown, no fusion)
   std::map<std::string, std::vector<int64_t>> shape;
-  if (fuse_dwpw_ == 2) {
+  if (fuse_dwpw_ == 2 || fuse_dwconv_) {
     for (auto& f : feeds_) shape[f.name] = f.dims;
     for (size_t i = 0; i < st.size(); ++i) {
       if (dead[i]) continue;
@@ -302,6 +302,65 @@ void GraphBuilder::FuseSteps(std::vector<Step>* steps_io) {
       dead[i] = true;
     }
   }
+  // (G, opt-in) a depthwise_conv2d[int8_out] whose only reader is a 1x1 conv that D left alone — because it carries a fused tail
+  // (residual add, calib copy, dropped fp32 output) or because D's kernels do not take the shape — takes that conv over with
+  // its tail, where plhip_dw_conv1x1_fused_supported takes the propagated shapes: MobileNetV2's blocks
+  if (fuse_dwconv_) {
+    for (size_t i = 0; i < st.size(); ++i) {
+      if (dead[i] || st[i].kind != "op" || ops_[st[i].op].type != "depthwise_conv2d" || !st[i].int8_out || st[i].pw_op >= 0) continue;
+      if (uses(st[i].out) != 1) continue;
+      const GraphOp& dwo = ops_[st[i].op];
+      if (dwo.w_dims.size() != 4 || dwo.w_dims[1] != 1 || dwo.w_dims[0] != dwo.conv.groups) continue;
+      int j = -1;
+      for (size_t t = 0; t < st.size(); ++t)
+        if (!dead[t] && st[t].kind == "op" && !st[t].op_inputs.empty() && st[t].op_inputs[0] == st[i].out) j = static_cast<int>(t);
+      if (j < 0 || st[j].op_inputs.size() != 1) continue;
+      const GraphOp& c = ops_[st[j].op];
+      if (c.type != "conv2d" || !c.enable_int8 || c.w_dims.size() != 4 || c.w_dims[2] != 1 || c.w_dims[3] != 1 || c.conv.groups != 1 ||
+          c.conv.strides != std::vector<int>({1, 1}) || c.conv.dilations != std::vector<int>({1, 1}) || st[j].pool_int8 ||
+          st[j].in_calib_scale > 0.f)
+        continue;
+      bool pad0 = true;
+      for (int v : c.conv.paddings) pad0 = pad0 && v == 0;
+      if (!pad0) continue;
+      // the one instruction runs where the depthwise conv ran: the residual operand must exist by then
+      if (!st[j].res.empty()) {
+        bool late = false;
+        for (int t = static_cast<int>(i) + 1; t < j; ++t)
+          if (!dead[t] && (st[t].out == st[j].res || st[t].calib_out == st[j].res)) late = true;
+        if (late) continue;
+      }
+      auto it = st[i].op_inputs.empty() ? shape.end() : shape.find(st[i].op_inputs[0]);
+      const std::vector<int> dpd = pad4(dwo.conv.paddings);
+      if (it == shape.end() || it->second.size() != 4 || dpd.size() != 4 || dwo.conv.strides.size() != 2 ||
+          dwo.conv.dilations.size() != 2 || !dwo.conv.padding_algorithm.empty())
+        continue;
+      plhip_conv_desc d;
+      memset(&d, 0, sizeof(d));
+      d.n = static_cast<int>(it->second[0]); d.cin = static_cast<int>(it->second[1]);
+      d.h = static_cast<int>(it->second[2]); d.w = static_cast<int>(it->second[3]);
+      d.cout = static_cast<int>(dwo.w_dims[0]); d.kh = static_cast<int>(dwo.w_dims[2]); d.kw = static_cast<int>(dwo.w_dims[3]);
+      for (int q = 0; q < 4; ++q) d.pad[q] = dpd[q];
+      d.stride[0] = dwo.conv.strides[0]; d.stride[1] = dwo.conv.strides[1];
+      d.dil[0] = dwo.conv.dilations[0]; d.dil[1] = dwo.conv.dilations[1];
+      d.groups = dwo.conv.groups;
+      const int has_tail = !st[j].res.empty() || !st[j].calib_out.empty();
+      if (!plhip_dw_conv1x1_fused_supported(&d, static_cast<int>(c.w_dims[0]), st[j].int8_out ? PLHIP_OUT_I8 : PLHIP_OUT_F32, has_tail))
+        continue;
+      st[i].pw_op = st[j].op;
+      st[i].pw_tail = true;
+      st[i].pw_int8_out = st[j].int8_out;
+      st[i].pw_out_scale = st[j].out_scale;
+      st[i].via = st[i].out;
+      st[i].out = st[j].out;
+      st[i].res = st[j].res;
+      st[i].res_relu = st[j].res_relu;
+      st[i].calib_out = st[j].calib_out;
+      st[i].calib_scale = st[j].calib_scale;
+      st[i].drop_f32 = st[j].drop_f32;
+      dead[j] = true;
+    }
+  }
   std::vector<Step> kept;
   for (size_t i = 0; i < st.size(); ++i)
     if (!dead[i]) kept.push_back(st[i]);
@@ -335,6 +394,13 @@ std::vector<std::string> GraphBuilder::Plan() {
         snprintf(buf, sizeof buf, " in_scale=%.9g", s.in_calib_scale);
         l += " +calib_in=" + s.via_in + buf;
       }
+      if (s.pw_tail) {  // (G): the 1x1 conv taken over, then its own fields as its unfused line had them
+        l += std::string(" +conv1x1=conv2d/") + (s.pw_int8_out ? "int8_out" : "fp32_out") + " via=" + s.via;
+        if (s.pw_int8_out) {
+          snprintf(buf, sizeof buf, " oscale=%.9g", s.pw_out_scale);
+          l += buf;
+        }
+      }
       if (!s.res.empty()) l += std::string(" +add=") + s.res + (s.res_relu ? " +relu" : "");
       if (!s.calib_out.empty()) {
         snprintf(buf, sizeof buf, " scale=%.9g", s.calib_scale);
@@ -342,7 +408,7 @@ std::vector<std::string> GraphBuilder::Plan() {
       }
       if (s.drop_f32) l += " -f32";
       if (s.pool_int8) l += " int8";
-      if (s.pw_op >= 0) {
+      if (s.pw_op >= 0 && !s.pw_tail) {
         l += std::string(" +pw=conv2d/") + (s.pw_int8_out ? "int8_out" : "fp32_out") + " via=" + s.via;
         if (s.pw_int8_out) {
           snprintf(buf, sizeof buf, " pw_oscale=%.9g", s.pw_out_scale);
@@ -402,6 +468,7 @@ std::vector<std::string> GraphBuilder::Lower(HipPredictor* pred) {
           a.pw_act = c.conv.act;
           a.pw_act_coef = c.conv.act_coef;
           a.pw_pool = s.pw_pool;
+          a.pw_tail = s.pw_tail;
         }
         pred->AddConv(op.type, s.op_inputs[0], s.out, op.w.data(), op.w_dims, op.has_bias ? op.bias.data() : nullptr, a);
       } else if (op.type == "fc") {

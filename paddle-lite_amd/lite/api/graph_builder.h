@@ -59,6 +59,11 @@ class GraphBuilder {
   // takes every eligible pair over (shapes outside the kernel run as two launches inside the one instruction), false = off.
   void set_fuse_dwpw(bool on) { fuse_dwpw_ = on ? 1 : 0; }
   void set_fuse_dwpw_mode(int mode) { fuse_dwpw_ = mode; }
+  //   (G) depthwise_conv2d[int8_out] -> conv2d 1x1 (stride 1, no padding, groups 1) WITH the 1x1 conv's fused tail (residual add,
+  // calib copy, dropped fp32 output), sole consumer  => ONE instruction, one launch of plhip_dw_conv1x1_fused_int8.  Opt-in
+  // (default off): runs with set_fuse(true) only, after D / E / F, on the pairs D left alone, where
+  // plhip_dw_conv1x1_fused_supported takes the shapes propagated from the feeds.  MobileNetV2's 17 block pairs.
+  void set_fuse_dwconv(bool on) { fuse_dwconv_ = on; }
   GraphOp& Add(const std::string& type, const std::vector<std::string>& inputs, const std::string& output);
   // Emits the program into `pred`; returns the host-side names of the fetched variables ("<name>/host").
   std::vector<std::string> Lower(HipPredictor* pred);
@@ -89,6 +94,7 @@ class GraphBuilder {
     std::string via;          // name the depthwise result would have had
     bool pw_pool{false};      // ... and that conv's sole consumer, a global average pool2d, too (E): `out` is the pool's output
     std::string via_pw;       // name the 1x1 conv's result would have had
+    bool pw_tail{false};      // fusion G: pw_op is the 1x1 consumer with its tail (res / calib_out / drop_f32 are then its own)
     float in_calib_scale{0.f};  // conv that took the calib[fp32_to_int8] in front of it over (F): its input is the calib's fp32 input
     std::string via_in;       // name the calib's int8 result would have had
   };
@@ -101,6 +107,7 @@ class GraphBuilder {
   };
   bool fuse_{true};
   int fuse_dwpw_{2};
+  bool fuse_dwconv_{false};
   std::vector<FeedDesc> feeds_;
   std::vector<std::string> fetches_;
   std::vector<GraphOp> ops_;

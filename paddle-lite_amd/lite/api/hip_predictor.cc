@@ -102,13 +102,13 @@ void HipPredictor::AddConv(const std::string& op_type, const std::string& in, co
     if (a.act == 4) p.activation_param.Leaky_relu_alpha = a.act_coef;
   }
   if (!a.residual.empty()) {
-    CHECK(!a.int8_out) << "the fused residual add belongs to the fp32_out kernel";
+    CHECK(!a.int8_out || (a.pw_tail && !a.pw_int8_out)) << "the fused residual add belongs to the fp32_out kernel";
     p.fuse_residual_connection = true;
     p.residualData = Var(a.residual);
     fz.fuse_residual_relu = a.residual_relu;
   }
   if (!a.calib_out.empty()) {
-    CHECK(!a.int8_out) << "the fused calib belongs to the fp32_out kernel";
+    CHECK(!a.int8_out || (a.pw_tail && !a.pw_int8_out)) << "the fused calib belongs to the fp32_out kernel";
     fz.calib_output = Var(a.calib_out);
     fz.calib_output->set_precision(PRECISION(kInt8));
     fz.calib_scale = a.calib_scale;
@@ -131,6 +131,7 @@ void HipPredictor::AddConv(const std::string& op_type, const std::string& in, co
       if (a.pw_act == 4) fz.pw_activation_param.Leaky_relu_alpha = a.pw_act_coef;
     }
     p.output->set_precision(a.pw_int8_out ? PRECISION(kInt8) : PRECISION(kFloat));
+    fz.pw_tail = a.pw_tail;
     if (a.pw_pool) {
       CHECK(!a.pw_int8_out) << "the fused global average pool reads the 1x1 conv's fp32 output";
       fz.pw_global_avg_pool = true;

@@ -57,6 +57,9 @@ int pllite_graph_fetch(pllite_predictor* p, const char* name);
 int pllite_graph_set_fuse(pllite_predictor* p, int on);
 // opt-in: depthwise_conv2d[int8_out] -> sole consumer conv2d 1x1 as ONE instruction (GraphBuilder::set_fuse_dwpw)
 int pllite_graph_set_fuse_dwpw(pllite_predictor* p, int on);
+// opt-in (default off): fusion G, depthwise_conv2d[int8_out] -> sole consumer conv2d 1x1 WITH its fused tail as ONE
+// instruction (GraphBuilder::set_fuse_dwconv)
+int pllite_graph_set_fuse_dwconv(pllite_predictor* p, int on);
 /* '\n'-separated plan (GraphBuilder::Plan) — needs no device. */
 int pllite_graph_plan(pllite_predictor* p, char* buf, int cap);
 /* Emit the program into the predictor; '\n'-separated host names of the fetched variables in buf. */

@@ -111,8 +111,14 @@ void ConvCompute<Ptype, OutType>::ReInitWhenNeeded() {
     pw_desc_.h = (desc_.h + desc_.pad[0] + desc_.pad[1] - (desc_.dil[0] * (desc_.kh - 1) + 1)) / desc_.stride[0] + 1;
     pw_desc_.w = (desc_.w + desc_.pad[2] + desc_.pad[3] - (desc_.dil[1] * (desc_.kw - 1) + 1)) / desc_.stride[1] + 1;
     const bool gap = fusion_.pw_global_avg_pool;
-    pw_fused_ = plhip_dwpw_fused_supported(&desc_, pw_desc_.cout, gap ? PLHIP_OUT_F32_GAP : (fusion_.pw_int8_out ? PLHIP_OUT_I8 : PLHIP_OUT_F32)) != 0;
-    kernel_func_name_ = pw_fused_ ? "conv_depthwise_3x3_pointwise_1x1_fused_int8_hip" : "conv_depthwise_int8_hip+conv1x1s1_gemm_int8_mfma32x32x32";
+    if (fusion_.pw_tail) {  // fusion G: the 1x1 conv keeps its graph tail
+      const int has_tail = param.fuse_residual_connection || fusion_.calib_output != nullptr;
+      pw_fused_ = plhip_dw_conv1x1_fused_supported(&desc_, pw_desc_.cout, fusion_.pw_int8_out ? PLHIP_OUT_I8 : PLHIP_OUT_F32, has_tail) != 0;
+      kernel_func_name_ = pw_fused_ ? "conv_depthwise_3x3_conv1x1_fused_int8_hip" : "conv_depthwise_int8_hip+conv1x1_tail_gemm_int8_hip";
+    } else {
+      pw_fused_ = plhip_dwpw_fused_supported(&desc_, pw_desc_.cout, gap ? PLHIP_OUT_F32_GAP : (fusion_.pw_int8_out ? PLHIP_OUT_I8 : PLHIP_OUT_F32)) != 0;
+      kernel_func_name_ = pw_fused_ ? "conv_depthwise_3x3_pointwise_1x1_fused_int8_hip" : "conv_depthwise_int8_hip+conv1x1s1_gemm_int8_mfma32x32x32";
+    }
     if (gap) kernel_func_name_ += "+pooling_global_avg";
   }
   last_shape_ = param.x->dims();
@@ -300,6 +306,41 @@ void ConvCompute<Ptype, OutType>::Run() {
     HIP_CALL(ctx.ctx(), plhip_conv2d_int8_fused(ctx.ctx(), &desc_, x, weights_.raw_data(), sc, bi,
                                                 fusion_.drop_fp32_output ? nullptr : static_cast<float*>(y), res,
                                                 fusion_.fuse_residual_relu ? 1 : 0, q, fusion_.calib_scale, ws, workspace_bytes_));
+  } else if (is_depthwise_ && has_pw_ && fusion_.pw_tail) {
+    // fusion G: `output` is the 1x1 conv's tensor; its tail (residual, calib copy, dropped fp32 output) as in the branch above
+    const bool f32 = !fusion_.pw_int8_out;
+    void* yo = f32 ? (fusion_.drop_fp32_output ? nullptr : static_cast<void*>(param.output->template mutable_data<float>(TARGET(kHIP))))
+                   : static_cast<void*>(param.output->template mutable_data<int8_t>(TARGET(kHIP)));
+    const float* res = nullptr;
+    if (param.fuse_residual_connection) {
+      CHECK(f32 && param.residualData && param.residualData->target() == TARGET(kHIP)) << "fused residual operand must live on the device";
+      CHECK(param.residualData->dims() == param.output->dims()) << "fused residual operand must have the output's shape";
+      res = param.residualData->template data<float>();
+    }
+    int8_t* q = nullptr;
+    if (fusion_.calib_output) {
+      CHECK(f32) << "the fused calib reads the 1x1 conv's fp32 output";
+      fusion_.calib_output->Resize(param.output->dims());
+      q = fusion_.calib_output->template mutable_data<int8_t>(TARGET(kHIP));
+    }
+    const float* psc = pw_scale_.data<float>();
+    const float* pbi = pw_has_bias_ ? pw_bias_.data<float>() : nullptr;
+    const plhip_out_kind ko = f32 ? PLHIP_OUT_F32 : PLHIP_OUT_I8;
+    if (pw_fused_) {
+      HIP_CALL(ctx.ctx(), plhip_dw_conv1x1_fused_int8(ctx.ctx(), &desc_, x, weights_.data<int8_t>(), sc, bi, pw_desc_.cout,
+                                                      pw_weights_.raw_data(), psc, pbi, pw_desc_.act, pw_desc_.act_alpha, yo, ko, res,
+                                                      fusion_.fuse_residual_relu ? 1 : 0, q, fusion_.calib_scale));
+    } else {  // shape outside the fused kernel: the two instructions, the depthwise result in a private tensor
+      mid_.Resize({desc_.n, desc_.cout, pw_desc_.h, pw_desc_.w});
+      int8_t* mid = mid_.mutable_data<int8_t>(TARGET(kHIP));
+      HIP_CALL(ctx.ctx(), plhip_depthwise_conv_int8(ctx.ctx(), &desc_, x, weights_.data<int8_t>(), sc, bi, mid, PLHIP_OUT_I8));
+      if (res || q) {
+        HIP_CALL(ctx.ctx(), plhip_conv2d_int8_fused(ctx.ctx(), &pw_desc_, mid, pw_weights_.raw_data(), psc, pbi, static_cast<float*>(yo), res,
+                                                    fusion_.fuse_residual_relu ? 1 : 0, q, fusion_.calib_scale, nullptr, 0));
+      } else {
+        HIP_CALL(ctx.ctx(), plhip_conv2d_int8(ctx.ctx(), &pw_desc_, mid, pw_weights_.raw_data(), psc, pbi, yo, ko, nullptr, 0));
+      }
+    }
   } else if (is_depthwise_ && has_pw_) {
     // `output` is the pointwise conv's tensor (HipConvFusion::pw_*); y above was allocated as int8: redo it for fp32
     void* yo = fusion_.pw_int8_out ? static_cast<void*>(param.output->template mutable_data<int8_t>(TARGET(kHIP)))

@@ -56,6 +56,7 @@ def load():
     L.pllite_graph_fetch.argtypes = [vp, cs]
     L.pllite_graph_set_fuse.argtypes = [vp, i32]
     L.pllite_graph_set_fuse_dwpw.argtypes = [vp, i32]
+    L.pllite_graph_set_fuse_dwconv.argtypes = [vp, i32]
     L.pllite_graph_plan.argtypes = [vp, cs, i32]
     L.pllite_graph_lower.argtypes = [vp, cs, i32]
     L.pllite_load_model.argtypes = [vp, vp, i64, i32]
@@ -200,6 +201,11 @@ class Predictor:
         """Opt-in: a depthwise conv [int8_out] takes its sole 1x1 consumer over (one instruction, one launch where the
         shape fits the fused kernel)."""
         self._ck(self.L.pllite_graph_set_fuse_dwpw(self.h, int(on)))
+
+    def graph_set_fuse_dwconv(self, on):
+        """Opt-in (default off), fusion G: a depthwise conv [int8_out] takes its sole 1x1 consumer over together with that
+        conv's fused tail (residual add, calib copy), one launch of plhip_dw_conv1x1_fused_int8 where the shape fits."""
+        self._ck(self.L.pllite_graph_set_fuse_dwconv(self.h, int(on)))
 
     def graph_fetch(self, name):
         self._ck(self.L.pllite_graph_fetch(self.h, name.encode()))

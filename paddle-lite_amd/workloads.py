@@ -270,15 +270,19 @@ def net_stats(net):
     return macs
 
 
-def emit_graph(pred, net, batch, fuse=True, fuse_dwpw=None):
+def emit_graph(pred, net, batch, fuse=True, fuse_dwpw=None, fuse_dwconv=None):
     """Feed the op list to the predictor's graph mode and lower it.  Returns the host name of the output variable.
     fuse=False: the reference program instruction for instruction (no kHIP graph-level fusion).
     fuse_dwpw: None = the builder's default (depthwise -> pointwise pairs the fused kernel takes become one instruction),
-    True = every eligible pair (shapes outside the kernel run as two launches inside the instruction), False = none."""
+    True = every eligible pair (shapes outside the kernel run as two launches inside the instruction), False = none.
+    fuse_dwconv: None = the builder's default (off); True = fusion G, a depthwise conv takes its 1x1 consumer over together with
+    that conv's fused tail (MobileNetV2's blocks), False = off."""
     from . import liteapi
     pred.graph_set_fuse(fuse)
     if fuse_dwpw is not None:
         pred.graph_set_fuse_dwpw(fuse_dwpw)
+    if fuse_dwconv is not None:
+        pred.graph_set_fuse_dwconv(fuse_dwconv)
     c, h, w = net["input_shape"]
     pred.graph_feed(net["input"], (batch, c, h, w), liteapi.PREC_FLOAT)
     for o in net["ops"]:
