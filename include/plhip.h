@@ -241,16 +241,12 @@ plhip_status plhip_elementwise_add_f32(plhip_ctx* ctx, const float* x, const flo
  * Runs a tiny known-answer GEMM through the MFMA path; returns PLHIP_OK iff bit-exact. ---- */
 plhip_status plhip_selftest(plhip_ctx* ctx);
 
-/* ---- diagnostics (no effect on results): switches of the shipped library are set HERE, never through the environment,
- * so that a stray variable cannot change which kernel a benchmark measures.  Keys: the A/B knobs of DESIGN.md 3.6 without
- * their former PLHIP_ prefix ("GEMM_WIDE", "CONV_PATCH", "DW_STAGE", "GEMM_DEBUG", ...; "DWCONV_FUSED" = 0: plhip_dw_conv1x1_fused_supported refuses every shape, so callers
- * run the two instructions), "fused_exp", and "fused_stamps" (1 = the fused
- * depthwise -> pointwise kernel records its in-kernel timeline, read back with plhip_debug_read_fw_stamps:
- * [tile][wave][16] shader-clock stamps).  Returns 0, or -1 for an unknown key. ---- */
+/* ---- diagnostics: switches of the shipped library are set HERE, never through the environment, so that a stray variable
+ * cannot change which kernel a benchmark measures.  Keys: the A/B knobs of DESIGN.md 3.6 without their former PLHIP_ prefix
+ * ("GEMM_WIDE", "CONV_PATCH", "DW_STAGE", ...).  Each selects one of several kernels or tiles that compute the same result;
+ * "DWCONV_FUSED" = 0: plhip_dw_conv1x1_fused_supported refuses every shape, so callers run the two instructions.  A
+ * `make EXPERIMENTS=1` build also accepts "STAMPS" (in-kernel timelines).  Returns 0, or -1 for an unknown key. ---- */
 int plhip_debug_set(const char* key, int value);
-int plhip_debug_read_fw_stamps(void* dst_host, size_t bytes);
-int plhip_debug_read_fs_stamps(void* dst_host, size_t bytes); /* the streaming fused kernel: [tile < 2048][wave 4][8] */
-int plhip_debug_read_f7_stamps(void* dst_host, size_t bytes); /* the small-plane fused kernel: [block < 1024][wave 8][8] */
 
 #ifdef __cplusplus
 }

@@ -27,7 +27,7 @@ EXPORTS = [
     "plhip_fc_packed_weight_bytes", "plhip_pack_fc_weights", "plhip_fc_int8",
     "plhip_calib_f32_to_i8", "plhip_calib_i8_to_f32", "plhip_global_avg_pool_f32", "plhip_softmax_f32",
     "plhip_pool2d_f32", "plhip_pool2d_max_i8", "plhip_elementwise_add_f32", "plhip_selftest",
-    "plhip_debug_set", "plhip_debug_read_fw_stamps", "plhip_debug_read_fs_stamps", "plhip_debug_read_f7_stamps", "plhip_conv2d_calib_supported", "plhip_conv2d_calib_int8",
+    "plhip_debug_set", "plhip_conv2d_calib_supported", "plhip_conv2d_calib_int8",
 ]
 
 
@@ -71,11 +71,11 @@ class PlhipError(RuntimeError):
 _lib = None
 # Diagnostic knobs this PROCESS set through plhip_debug_set (the library itself never reads the environment).  The binding
 # forwards PLHIP_<KNOB>=<int> variables of the A/B scripts (tools/*.sh) explicitly and records them here;
-# bench.py prints the dict in its JSON line, so a measurement taken with a knob says so.
-KNOBS = ("STEM_MFMA", "CONV_PATCH", "CONV_PATCH_S2", "PATCH_DEBUG", "PATCH_DELAY", "STEM7", "DW_STAGE", "DW_STAGE_NP2", "DW_FASTV",
-         "DW5_DIRECT", "DW_RS1", "DW_RS2", "GEMM_VARIANT", "GEMM_AREG", "GEMM_MA", "GEMM_DEBUG", "SUBSAMPLE_1X1", "GEMM_TR", "TR_DELAY",
-         "TR_CFG", "GEMM_WIDE", "WIDE_NTT", "FC_MFMA", "IMPLICIT_GEMM", "FUSED_STREAM", "FUSED_SMALL",
-         "DWCONV_FUSED")
+# bench.py prints the dict in its JSON line, so a measurement taken with a knob says so.  The same keys, in the same order, as
+# the library's knob table (plhip_capi.hip); STAMPS exists in a `make EXPERIMENTS=1` build only, a default one refuses it.
+KNOBS = ("STEM_MFMA", "CONV_PATCH", "CONV_PATCH_S2", "STEM7", "DW_STAGE", "DW_STAGE_NP2", "DW_FASTV", "DW5_DIRECT", "DW_RS1",
+         "DW_RS2", "GEMM_VARIANT", "GEMM_AREG", "GEMM_MA", "SUBSAMPLE_1X1", "GEMM_TR", "TR_CFG", "GEMM_WIDE", "WIDE_NTT", "FC_MFMA",
+         "IMPLICIT_GEMM", "FUSED_STREAM", "FUSED_SMALL", "DWCONV_FUSED", "STAMPS")
 KNOBS_SET = {}
 
 
@@ -152,6 +152,22 @@ def load():
     L.plhip_selftest.argtypes = [vp]
     _lib = L
     return L
+
+
+def read_stamps(family, shape):
+    """The in-kernel timeline of the last stamping launch of a kernel family ("gemm", "tr", "wide", "patch", "fw", "fs",
+    "f7") as a uint64 array of `shape`.  Needs a `make EXPERIMENTS=1` library and PLHIP_STAMPS=1."""
+    L = load()
+    if not hasattr(L, "plhip_debug_read_stamps"):
+        raise PlhipError("this library has no timeline stamps: rebuild with `make -C paddle-lite_amd/csrc clean && "
+                         "make -C paddle-lite_amd/csrc EXPERIMENTS=1`")
+    if not KNOBS_SET.get("STAMPS"):
+        raise PlhipError("run with PLHIP_STAMPS=1")
+    L.plhip_debug_read_stamps.argtypes = [C.c_char_p, C.c_void_p, C.c_size_t]
+    buf = np.zeros(shape, np.uint64)
+    if L.plhip_debug_read_stamps(family.encode(), buf.ctypes.data, buf.nbytes) != 0:
+        raise PlhipError("no %s stamps: no launch of that kernel family since PLHIP_STAMPS=1" % family)
+    return buf
 
 
 class Context:

@@ -35,18 +35,6 @@
 
 namespace plhip {
 
-__device__ unsigned long long g_patch_stamps[512 * 8 * PATCH_STAMP_SLOTS];
-static unsigned long long* patch_stamps_ptr() {
-  static unsigned long long* p = nullptr;
-  if (!p) (void)hipGetSymbolAddress((void**)&p, HIP_SYMBOL(g_patch_stamps));
-  return p;
-}
-int debug_read_patch_stamps(void* dst, size_t bytes) {
-  const size_t cap = sizeof(unsigned long long) * 512 * 8 * PATCH_STAMP_SLOTS;
-  if (bytes > cap) bytes = cap;
-  return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_patch_stamps), bytes, 0, hipMemcpyDeviceToHost);
-}
-
 static int patch_env() {  // PLHIP_CONV_PATCH=0: the ring-kernel implicit GEMM instead (A/B runs)
   const int v = knob("CONV_PATCH", 1);
   return v;
@@ -323,11 +311,7 @@ static inline void magic_u31(long d, unsigned& m, int& sh, bool general_pow2 = f
 }
 
 void launch_conv_patch(PatchArgs a, int out, hipStream_t s) {
-      // its OWN variable (diagnostics only): 1 = no epilogue (timing experiments), 32 = timeline stamps.  (PLHIP_GEMM_DEBUG
-    // also re-routes the GEMM kernels of the other layers, e.g. 7-wide implicit-GEMM rows onto a kernel that cannot run them.)
-  const int dbg_env = knob("PATCH_DEBUG", 0);
-  a.dbg = dbg_env;
-  a.stamps = (a.dbg & 32) ? patch_stamps_ptr() : nullptr;
+  PLHIP_SET_STAMPS(a, "patch", sizeof(unsigned long long) * 512 * 8 * PATCH_STAMP_SLOTS);
   a.NCH = a.C / 32;
   a.HWY = a.OH * a.OW;
   a.y_bstride = (size_t)a.M * a.HWY;
@@ -366,8 +350,6 @@ void launch_conv_patch(PatchArgs a, int out, hipStream_t s) {
   a.rounds = (a.T8 + NH * nq - 1) / (NH * nq);
   nq = (a.T8 + NH * a.rounds - 1) / (NH * a.rounds);  // the fewest blocks that need no more rounds
   a.NQ = nq;
-  const int delay_env = knob("PATCH_DELAY", 0);  // s_sleep units (64 clocks) the second block of a CU starts late
-  a.delay = delay_env;
   magic_u31(a.PWp, a.pw_m, a.pw_s, true);
   magic_u31(a.TPI, a.tpi_m, a.tpi_s);
   magic_u31(a.pitch, a.pitch_m, a.pitch_s);

@@ -15,6 +15,8 @@ namespace plhip {
 
 constexpr int PATCH_NTW = 7;           // 32-pixel n tiles per wave and tile
 constexpr int PATCH_SP = 144;          // staging row pitch of the int8 epilogue: 128 bytes + 16
+// timeline stamps (EXPERIMENTS=1 builds, plhip_device.h): per wave in static LDS, flushed to the "patch" stamp buffer
+// [block < 512][wave 8][PATCH_STAMP_SLOTS] at the end (tools/patch_timeline.py)
 constexpr int PATCH_STAMP_SLOTS = 32;
 
 template <int I, int N, class F>
@@ -24,11 +26,6 @@ __device__ __forceinline__ void patch_static_for(F&& f) {
     patch_static_for<I + 1, N>(std::forward<F>(f));
   }
 }
-
-#define PLHIP_PATCH_STAMP(i)                                               \
-  do {                                                                     \
-    if (diag && lane == 0) lstamp[i] = __builtin_amdgcn_s_memtime();       \
-  } while (0)
 
 // NH halves of 4 waves per block, WMH x WNH waves per half: a half owns its own stream of pixel tiles.  NH = 1: 4-wave
 // blocks, TWO per CU, each with its own ring and its own barriers: the blocks drift apart, so that one's epilogue (VALU,
@@ -72,24 +69,23 @@ __global__ __launch_bounds__(256 * NH, 2) void conv_patch_i8_kernel(PatchArgs a)
   PLHIP_PRELOAD(a.NCH); PLHIP_PRELOAD(a.pitch); PLHIP_PRELOAD(a.pps); PLHIP_PRELOAD(a.TPI); PLHIP_PRELOAD(a.T); PLHIP_PRELOAD(a.T8);
   PLHIP_PRELOAD(a.MB); PLHIP_PRELOAD(a.NQ); PLHIP_PRELOAD(a.rounds); PLHIP_PRELOAD(a.HWY); PLHIP_PRELOAD(a.y_bstride);
   PLHIP_PRELOAD(a.act); PLHIP_PRELOAD(a.alpha); PLHIP_PRELOAD(a.pw_m); PLHIP_PRELOAD(a.pw_s); PLHIP_PRELOAD(a.tpi_m);
-  PLHIP_PRELOAD(a.tpi_s); PLHIP_PRELOAD(a.pitch_m); PLHIP_PRELOAD(a.pitch_s); PLHIP_PRELOAD(a.dbg); PLHIP_PRELOAD(a.res);
+  PLHIP_PRELOAD(a.tpi_s); PLHIP_PRELOAD(a.pitch_m); PLHIP_PRELOAD(a.pitch_s); PLHIP_PRELOAD(a.res);
   PLHIP_PRELOAD(a.glob); PLHIP_PRELOAD(a.nimg); PLHIP_PRELOAD(a.IMGP); PLHIP_PRELOAD(a.imgp_m); PLHIP_PRELOAD(a.imgp_s); PLHIP_PRELOAD(a.hwy_m); PLHIP_PRELOAD(a.hwy_s);
-  PLHIP_PRELOAD(a.y2); PLHIP_PRELOAD(a.inv_scale2); PLHIP_PRELOAD(a.res_relu); PLHIP_PRELOAD(a.stamps); PLHIP_PRELOAD(a.delay);
+  PLHIP_PRELOAD(a.y2); PLHIP_PRELOAD(a.inv_scale2); PLHIP_PRELOAD(a.res_relu);
   extern __shared__ __attribute__((aligned(16))) uint8_t ring[];        // NSLOT x [half 0: 32 x pitch][half 1][weights]
   __shared__ __attribute__((aligned(16))) uint8_t stg_all[NW * 32 * PATCH_SP];  // int8 epilogue staging, one image per wave
-  __shared__ unsigned long long stamp_all[NW * PATCH_STAMP_SLOTS];
+  __shared__ unsigned long long stamp_all[kStamps ? NW * PATCH_STAMP_SLOTS : 1];  // (unused and not allocated without stamps)
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int half = NH == 2 ? wave >> 2 : 0, wq = wave & 3;
   const int wm = wq % WMH, wn = wq / WMH;  // wave-uniform
   const int c = lane & 31, h = lane >> 5;
-  const bool diag = (a.dbg & 32) != 0;
+  unsigned long long* const gstamp = PLHIP_STAMPS_OF(a);
+  const bool diag = kStamps && gstamp;
   unsigned long long* lstamp = stamp_all + wave * PATCH_STAMP_SLOTS;
-  if (diag && lane == 0) {
-    lstamp[0] = __builtin_amdgcn_s_memrealtime();
-    lstamp[1] = __builtin_amdgcn_s_memtime();
-    lstamp[2] = (unsigned long long)__builtin_amdgcn_s_getreg(63492) | ((unsigned long long)__builtin_amdgcn_s_getreg(63508) << 32);
-  }
+  PLHIP_STAMP_REAL(0);
+  PLHIP_STAMP(1);
+  PLHIP_STAMP_CLOCK(2, (unsigned long long)__builtin_amdgcn_s_getreg(63492) | ((unsigned long long)__builtin_amdgcn_s_getreg(63508) << 32));
 
   // ---- block -> (XCD, M block, n-block slot); stream of a half = 2 nq + half inside the XCD's contiguous tile range
   const int bx = blockIdx.x & 7, bq = blockIdx.x >> 3;
@@ -340,7 +336,7 @@ __global__ __launch_bounds__(256 * NH, 2) void conv_patch_i8_kernel(PatchArgs a)
           }
         });
         const int len = d_b - d_a;  // <= 128
-        if (diag && nepi == 0 && lane == 0) lstamp[18 + 2 * gi] = __builtin_amdgcn_s_memtime();  // group staged
+        if (nepi == 0) PLHIP_STAMP(18 + 2 * gi);  // group staged
         v4i rv[4];
         asm volatile("ds_read_b128 %0, %1" : "=v"(rv[0]) : "v"(rrow) : "memory");
         asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(rv[1]) : "v"(rrow), "n"(8 * PATCH_SP) : "memory");
@@ -406,7 +402,7 @@ __global__ __launch_bounds__(256 * NH, 2) void conv_patch_i8_kernel(PatchArgs a)
           }
         }
         }
-        if (diag && nepi == 0 && lane == 0) lstamp[19 + 2 * gi] = __builtin_amdgcn_s_memtime();  // group's stores issued
+        if (nepi == 0) PLHIP_STAMP(19 + 2 * gi);  // group's stores issued
       });
     } else {
       // 32-bit outputs: register group gq of n tile t = 4 consecutive pixels 32t + 8gq + 4h (inside one row: PWp % 4 == 0);
@@ -515,7 +511,7 @@ __global__ __launch_bounds__(256 * NH, 2) void conv_patch_i8_kernel(PatchArgs a)
       if constexpr (STAT) asm volatile("" : "+v"(w[3 * Q]), "+v"(w[3 * Q + 1]), "+v"(w[3 * Q + 2]));
     }
     __builtin_amdgcn_s_barrier();  // ... everyone's have, and nobody reads the previous step's slot any more
-    if (diag && nstep < 6 && lane == 0) lstamp[5 + nstep] = __builtin_amdgcn_s_memtime();
+    if (nstep < 6) PLHIP_STAMP(5 + nstep);
     // The slot of the step before is free now: the DMA of the slot D steps ahead goes into it, ONE PIECE BEHIND EVERY FOURTH
     // MFMA.  (All pieces at the top of the step, from all waves at once, is a burst of 24-40 KiB into an address path that
     // takes ~58 B/clk: every wave sat ~700 cycles in the issue with the matrix pipe idle, and the time of the data movement
@@ -585,16 +581,13 @@ __global__ __launch_bounds__(256 * NH, 2) void conv_patch_i8_kernel(PatchArgs a)
 #undef PLHIP_PATCH_READ
       static_assert(IEV * (NPI - 1) + 1 < NM, "every piece has its MFMA");
     }
-    if (diag && nstep < 6 && lane == 0) lstamp[11 + nstep] = __builtin_amdgcn_s_memtime();
+    if (nstep < 6) PLHIP_STAMP(11 + nstep);
     ++nstep;
     slot = slot + 1 == NSLOT ? 0 : slot + 1;
   };
 
   // ---- prologue: the slots of the first D steps; register-resident weights: the three fragments of step p right behind
   // slab p, the rest behind slab D - 1: step 0 starts when a quarter of the prologue's bytes has arrived
-  if (NH == 1 && a.delay > 0 && 2 * blockIdx.x >= gridDim.x) {  // the CU's second block starts late (see the template comment)
-    for (int i = 0; i < a.delay; i += 100) __builtin_amdgcn_s_sleep(100);
-  }
   cursor_tiles(0);
   patch_static_for<0, D>([&](auto p_c) __attribute__((always_inline)) {
     constexpr int pp = decltype(p_c)::value;
@@ -607,7 +600,7 @@ __global__ __launch_bounds__(256 * NH, 2) void conv_patch_i8_kernel(PatchArgs a)
     }
   });
   if constexpr (STAT) patch_static_for<3 * D, 18>([&](auto i_c) __attribute__((always_inline)) { load_w(i_c); });
-  PLHIP_PATCH_STAMP(3);
+  PLHIP_STAMP(3);
 
   using std::integral_constant;
   int nstamp = 22;  // 5-10: barrier of step i passed, 11-16: its MFMAs issued, 18-21: first epilogue, 22..: end of round k
@@ -645,7 +638,11 @@ __global__ __launch_bounds__(256 * NH, 2) void conv_patch_i8_kernel(PatchArgs a)
         }
       }
     }
-    if (live && !(a.dbg & 1)) {  // (PLHIP_PATCH_DEBUG & 1: no epilogue; timing experiments)
+    // every fragment read of the tile has landed before the epilogue takes registers for its own values: the reads are inline
+    // asm that the compiler's wait-count pass does not see, and without the stamps this point used to carry, the epilogue's
+    // address arithmetic of the stride-2 form was allocated onto the destinations of the last ones (tools/check_wide_isa.py)
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    if (live) {
       // (opaque copies: the address arithmetic of the epilogue must not be hoisted above the K loop, where its lane masks
       // and offsets would sit in registers for the whole tile)
       int be = b, pe = p0, me = mt;
@@ -657,18 +654,15 @@ __global__ __launch_bounds__(256 * NH, 2) void conv_patch_i8_kernel(PatchArgs a)
       ++nepi;
     }
     if (nstamp < PATCH_STAMP_SLOTS - 3) {
-      PLHIP_PATCH_STAMP(nstamp);
+      PLHIP_STAMP(nstamp);
       ++nstamp;
     }
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the surplus DMA pieces must land before the LDS is released
   if (diag) {  // wave-uniform
-    if (lane == 0) {
-      lstamp[PATCH_STAMP_SLOTS - 2] = __builtin_amdgcn_s_memtime();
-      lstamp[PATCH_STAMP_SLOTS - 1] = __builtin_amdgcn_s_memrealtime();
-    }
-    if (a.stamps && blockIdx.x < 512 && lane < PATCH_STAMP_SLOTS)
-      a.stamps[((size_t)blockIdx.x * 8 + wave) * PATCH_STAMP_SLOTS + lane] = lstamp[lane];
+    PLHIP_STAMP(PATCH_STAMP_SLOTS - 2);
+    PLHIP_STAMP_REAL(PATCH_STAMP_SLOTS - 1);
+    if (blockIdx.x < 512 && lane < PATCH_STAMP_SLOTS) gstamp[((size_t)blockIdx.x * 8 + wave) * PATCH_STAMP_SLOTS + lane] = lstamp[lane];
   }
 }
 

@@ -38,23 +38,11 @@ constexpr int FW_NT = 4;       // 32-pixel n tiles per tile (2 rows of pitch 16 
 constexpr int FW_SP = 112;     // staging pitch of a channel row (98 bytes used)
 constexpr int FW_KSTEP = 4096; // LDS bytes of one K-step of the activation image: [kg 4][k%8 8][chunk slot 8][16 B]
 
-// ---- diagnostic timeline (plhip_debug_set("fused_stamps", 1); never set in production): s_memtime per wave at the phase
-// boundaries, read back by plhip_debug_read_fw_stamps (tools/fused_timeline.py).  Slots: 0 realtime start, 1 entry, 2 operands
-// of round 0 requested, 3 round 0 produced, 4 + 2 (r - 1) round r done, 5 + 2 (r - 1) behind its barrier (r < 5), 12 last
-// K-steps multiplied, 13 requantised + staged, 14 stores issued, 15 stores acknowledged
+// timeline stamps (EXPERIMENTS=1 builds, plhip_device.h): per wave of the first 1024 tiles at the phase boundaries, straight
+// into the "fw" stamp buffer [tile][wave 8][FW_STAMP_SLOTS] (tools/fused_timeline.py).  Slots: 0 realtime start, 1 entry,
+// 2 operands of round 0 requested, 3 round 0 produced, 4 + 2 (r - 1) round r done, 5 + 2 (r - 1) behind its barrier (r < 5),
+// 12 last K-steps multiplied, 13 requantised + staged, 14 stores issued, 15 stores acknowledged
 constexpr int FW_STAMP_SLOTS = 16;
-__device__ unsigned long long g_fw_stamps[1024 * 8 * FW_STAMP_SLOTS];
-static int g_fw_debug = 0;
-void debug_set_fused(int v) { g_fw_debug = v; }  // bit 5: stamps; bits 0-1: timing experiments
-int debug_read_fw_stamps(void* dst, size_t bytes) {
-  if (bytes > sizeof(g_fw_stamps)) bytes = sizeof(g_fw_stamps);
-  if (hipDeviceSynchronize() != hipSuccess) return -1;
-  return hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_fw_stamps), bytes) == hipSuccess ? 0 : -1;
-}
-#define PLHIP_FW_STAMP(i)                                                                                   \
-  do {                                                                                                      \
-    if (diag && lane == 0) g_fw_stamps[((size_t)vb * 8 + wave) * FW_STAMP_SLOTS + (i)] = __builtin_amdgcn_s_memtime(); \
-  } while (0)
 
 // 8 bytes of an input row: scalar base + the lane's 32-bit offset (>= 0) + a compile-time row distance (the immediate of
 // the load: no address arithmetic per row)
@@ -65,9 +53,7 @@ __device__ __forceinline__ void fw_load_row(const int8_t* __restrict__ xs, uint3
 
 // MTW: 32-row m tiles per wave (M = 256 MTW).  OUT: output kind.  DWNN / PWNN: the depthwise / pointwise activation is
 // relu or relu6 (the packed non-negative requantisation); else none / leaky (leaky with slope 1 for none: exact).
-// EXP (timing experiments only, results are wrong): 1 = no MFMAs in the produce + consume rounds, 2 = no depthwise arithmetic there,
-// 3 = no input-row fetches there (the arithmetic runs on stale rows), 4 = no weight fetches there
-template <int MTW, int OUT, bool DWNN, bool PWNN, int EXP = 0, int ORDER_T = 1, int NEWQ = 1>
+template <int MTW, int OUT, bool DWNN, bool PWNN>
 __global__ __launch_bounds__(512, 2) void fused_dwpw14_kernel(FusedArgs a) {
   const GemmArgs& g = a.pw;
   PLHIP_PRELOAD(a.x); PLHIP_PRELOAD(a.dw_w); PLHIP_PRELOAD(a.dw_scale); PLHIP_PRELOAD(a.dw_bias); PLHIP_PRELOAD(a.dw_act);
@@ -81,17 +67,11 @@ __global__ __launch_bounds__(512, 2) void fused_dwpw14_kernel(FusedArgs a) {
   const unsigned vb = (blockIdx.x & 7) * per + (blockIdx.x >> 3);
   if (vb >= nb) return;  // block-uniform
   const int b = (int)(vb >> 1), hf = (int)(vb & 1);
-  const bool diag = (g.dbg & 32) != 0 && vb < 1024;
-#ifdef PLHIP_FW_AGPR
-  // accumulators in AGPRs (this file is built WITHOUT -amdgpu-mfma-vgpr-form): naming one AGPR makes the compiler keep the
-  // accumulator file for the MFMA results, whose reads / writes then do not compete with the VALU for the VGPR ports
-  {
-    int agpr_hint;
-    asm volatile("; keep AGPRs %0" : "=a"(agpr_hint));
-  }
-#endif
-  if (diag && lane == 0) g_fw_stamps[((size_t)vb * 8 + wave) * FW_STAMP_SLOTS] = __builtin_amdgcn_s_memrealtime();
-  PLHIP_FW_STAMP(1);
+  unsigned long long* const gstamp = PLHIP_STAMPS_OF(g);
+  const bool diag = kStamps && gstamp && vb < 1024;
+  unsigned long long* const lstamp = diag ? gstamp + ((size_t)vb * 8 + wave) * FW_STAMP_SLOTS : nullptr;
+  PLHIP_STAMP_REAL(0);
+  PLHIP_STAMP(1);
   const int KS = g.KS, C = a.C, R = KS >> 2;  // rounds of 128 channels (K % 128 == 0: fused_dwpw_plan)
   const int c = lane & 31, h = lane >> 5;
 
@@ -181,14 +161,14 @@ __global__ __launch_bounds__(512, 2) void fused_dwpw14_kernel(FusedArgs a) {
   // into the same registers behind their last use.  CONSUME: K-steps 4 rc .. 4 rc + 3 (W) multiplied, the next four fetched.
   // The MFMAs are dealt over the 9 row chunks of the task so that every chunk carries VALU and matrix work side by side.
   using std::integral_constant;
-  // ORDER: 1 (default) = TAPS FIRST: the 9 row chunks' window cuts and v_dot4 taps with no MFMA between them, then the 7
+  // A producing round is TAPS FIRST: the 9 row chunks' window cuts and v_dot4 taps with no MFMA between them, then the 7
   // requantisation slices with the round's MFMAs dealt over them.  v_dot4_i32_i8 runs on the matrix pipe: beside an MFMA it
   // waits for it (tools/probe_coexec.hip: one wave's MFMA + 8 fma take 51 cycles, MFMA + 8 dot4 90; a dot4-only wave beside an
-  // MFMA-only wave runs at 9.5 cycles per dot4), while cvt / fma / min / perm overlap with it.  0 = everything dealt over the
-  // row chunks (the first form: rounds took MFMA time + VALU time, profiles/r04_fused_timeline_order0.txt).
-  auto round = [&](auto produce_c, auto consume_c, auto order_c, int rp, int rc) __attribute__((always_inline)) {
+  // MFMA-only wave runs at 9.5 cycles per dot4), while cvt / fma / min / perm overlap with it.  (Dealing everything over the
+  // row chunks instead made rounds take MFMA time + VALU time, profiles/r04_fused_timeline_order0.txt.)  The consume-only
+  // last round deals its MFMAs over the 9 row chunks' proportions.
+  auto round = [&](auto produce_c, auto consume_c, int rp, int rc) __attribute__((always_inline)) {
     constexpr bool PRODUCE = decltype(produce_c)::value, CONSUME = decltype(consume_c)::value;
-    constexpr int ORDER = decltype(order_c)::value;
     // next task (clamped: the last round fetches its own operands again, unused)
     const int rn = rp + 1 < R ? rp + 1 : rp;
     const int nch = 128 * rn + 16 * wave + chl;
@@ -222,7 +202,7 @@ __global__ __launch_bounds__(512, 2) void fused_dwpw14_kernel(FusedArgs a) {
       acc[n][m] = __builtin_amdgcn_mfma_i32_32x32x32_i8(av, W[j][m], acc[n][m], 0, 0, 0);
       if constexpr (n == FW_NT - 1 && m == MTW - 1) {  // K-step j done: its registers take K-step j of the next round
         const int ksn = 4 * (rc + 1) + j;
-        if constexpr (!(EXP == 4 && PRODUCE)) fetch_w(j, ksn < KS ? ksn : KS - 1);
+        fetch_w(j, ksn < KS ? ksn : KS - 1);
       }
     };
     auto mfmas = [&](auto self, auto i_c, auto end_c) __attribute__((always_inline)) -> void {
@@ -256,7 +236,7 @@ __global__ __launch_bounds__(512, 2) void fused_dwpw14_kernel(FusedArgs a) {
                                : __builtin_amdgcn_sdot4((int)win[jj], (int)(t == 8 ? wr2b : wr[r]), dacc[o][jj], false);
       }
       // the next task's row t into the registers just consumed
-      if constexpr (!(EXP == 3 && CONSUME)) load_row(integral_constant<int, t>{}, noff, in[t]);
+      load_row(integral_constant<int, t>{}, noff, in[t]);
       if constexpr (t == 2) {
         const int8_t* wp = a.dw_w + (size_t)nch * 9;
         uint32_t w0, w1, w2;
@@ -273,32 +253,26 @@ __global__ __launch_bounds__(512, 2) void fused_dwpw14_kernel(FusedArgs a) {
     };
     auto finish = [&](auto o_c) __attribute__((always_inline)) {  // output row o is complete: requantise, into the image
       constexpr int o = decltype(o_c)::value;
-      const uint32_t pk = DWNN ? (NEWQ ? requant4_nn_rtz(dacc[o], dsc, dbi, dw_hi2, a.ones) : dw_requant4<ACT_RELU6>(dacc[o], dsc, dbi, 0.f, 0.f, dw_hi2, a.ones))
-                               : dw_requant4<ACT_LEAKY>(dacc[o], dsc, dbi, dw_leak, -254.f, 254.f);
+      const uint32_t pk = DWNN ? requant4_nn_rtz(dacc[o], dsc, dbi, dw_hi2, a.ones) : dw_requant4<ACT_LEAKY>(dacc[o], dsc, dbi, dw_leak, -254.f, 254.f);
       *reinterpret_cast<uint32_t*>(fw_lds + (wb ^ (uint32_t)(o << 4))) = pk;
     };
-    constexpr bool DO_P = PRODUCE && !(EXP == 2 && CONSUME), DO_C = CONSUME && !(EXP == 1 && PRODUCE);
-    auto chunk = [&](auto t_c) __attribute__((always_inline)) {  // ORDER 0: row chunk t with its share of the MFMAs
+    auto chunk = [&](auto t_c) __attribute__((always_inline)) {  // consume-only round: row chunk t's share of the MFMAs
       constexpr int t = decltype(t_c)::value;
-      if constexpr (DO_C) mfmas(mfmas, integral_constant<int, mstart(t)>{}, integral_constant<int, mstart(t + 1)>{});
-      if constexpr (DO_P) {
-        taps(t_c);
-        if constexpr (t >= 2) finish(integral_constant<int, t - 2>{});
-      }
+      mfmas(mfmas, integral_constant<int, mstart(t)>{}, integral_constant<int, mstart(t + 1)>{});
       __builtin_amdgcn_sched_barrier(0);
     };
-    // first MFMA of requantisation slice o (o = 7: end), ORDER 1
+    // first MFMA of requantisation slice o (o = 7: end)
     constexpr auto m1start = [](int o) {
       constexpr int cum[8] = {0, 5, 10, 14, 19, 23, 28, 32};
       return cum[o] * NM / 32;
     };
-    auto slice = [&](auto o_c) __attribute__((always_inline)) {  // ORDER 1: requantisation slice o with its share of the MFMAs
+    auto slice = [&](auto o_c) __attribute__((always_inline)) {  // requantisation slice o with its share of the MFMAs
       constexpr int o = decltype(o_c)::value;
-      if constexpr (DO_C) mfmas(mfmas, integral_constant<int, m1start(o)>{}, integral_constant<int, m1start(o + 1)>{});
-      if constexpr (DO_P) finish(o_c);
+      if constexpr (CONSUME) mfmas(mfmas, integral_constant<int, m1start(o)>{}, integral_constant<int, m1start(o + 1)>{});
+      finish(o_c);
       __builtin_amdgcn_sched_barrier(0);
     };
-    if constexpr (ORDER == 0 || !DO_P) {
+    if constexpr (!PRODUCE) {
       chunk(integral_constant<int, 0>{});
       chunk(integral_constant<int, 1>{});
       chunk(integral_constant<int, 2>{});
@@ -327,7 +301,7 @@ __global__ __launch_bounds__(512, 2) void fused_dwpw14_kernel(FusedArgs a) {
       slice(integral_constant<int, 5>{});
       slice(integral_constant<int, 6>{});
     }
-    if constexpr (PRODUCE && !(EXP == 2 && CONSUME)) {
+    if constexpr (PRODUCE) {
       wr[0] = nwr[0];
       wr[1] = nwr[1];
       wr[2] = nwr[2];
@@ -341,18 +315,17 @@ __global__ __launch_bounds__(512, 2) void fused_dwpw14_kernel(FusedArgs a) {
   fetch_w(1, 1 < KS ? 1 : KS - 1);
   fetch_w(2, 2 < KS ? 2 : KS - 1);
   fetch_w(3, 3 < KS ? 3 : KS - 1);
-  PLHIP_FW_STAMP(2);
-  using OD = integral_constant<int, ORDER_T>;
-  round(std::true_type{}, std::false_type{}, OD{}, 0, 0);
+  PLHIP_STAMP(2);
+  round(std::true_type{}, std::false_type{}, 0, 0);
   xoff += (R > 1 ? 1 : 0) * 128 * 196;
-  PLHIP_FW_STAMP(3);
+  PLHIP_STAMP(3);
   __syncthreads();
   for (int r = 1; r < R; ++r) {
-    round(std::true_type{}, std::true_type{}, OD{}, r, r - 1);
+    round(std::true_type{}, std::true_type{}, r, r - 1);
     xoff += (r + 1 < R ? 1 : 0) * 128 * 196;
-    if (r < 5) PLHIP_FW_STAMP(4 + 2 * (r - 1));
+    if (r < 5) PLHIP_STAMP(4 + 2 * (r - 1));
     __syncthreads();
-    if (r < 5) PLHIP_FW_STAMP(5 + 2 * (r - 1));
+    if (r < 5) PLHIP_STAMP(5 + 2 * (r - 1));
   }
   float psc[MTW], pbi[MTW];  // pointwise scale / bias of this lane's channels: fetched under the last round's MFMAs
 #pragma unroll
@@ -404,8 +377,7 @@ __global__ __launch_bounds__(512, 2) void fused_dwpw14_kernel(FusedArgs a) {
         for (int gq = 0; gq < 4; ++gq) {
           if (n == FW_NT - 1 && gq >= 2) continue;  // row 7 of the tile does not exist
           int v[4] = {acc[n][m][4 * gq], acc[n][m][4 * gq + 1], acc[n][m][4 * gq + 2], acc[n][m][4 * gq + 3]};
-          edw[gq] = PWNN ? (NEWQ ? requant4_nn_rtz(v, s2, b2, hi2, a.ones) : dw_requant4<ACT_RELU6>(v, s2, b2, 0.f, 0.f, hi2, a.ones))
-                         : dw_requant4<ACT_LEAKY>(v, s2, b2, leak, -254.f, 254.f);
+          edw[gq] = PWNN ? requant4_nn_rtz(v, s2, b2, hi2, a.ones) : dw_requant4<ACT_LEAKY>(v, s2, b2, leak, -254.f, 254.f);
         }
         // half exchange: every lane gets the 16 pixels of ONE output row of its channel (h = 0: row 2 n, h = 1: row 2 n + 1)
         auto s02 = __builtin_amdgcn_permlane32_swap(edw[0], edw[2], false, false);
@@ -440,9 +412,9 @@ __global__ __launch_bounds__(512, 2) void fused_dwpw14_kernel(FusedArgs a) {
     mfma_tile(I3{});
     epi_tile(I2{});
     __builtin_amdgcn_sched_barrier(0);
-    PLHIP_FW_STAMP(12);
+    PLHIP_STAMP(12);
     epi_tile(I3{});
-    PLHIP_FW_STAMP(13);
+    PLHIP_STAMP(13);
     // copy-out: lane -> (row lane >> 3 of a group of 8, 16-byte piece lane & 7); a channel row is 98 contiguous bytes
     const int piece = lane & 7, rsub = lane >> 3;
     int8_t* ybase = reinterpret_cast<int8_t*>(g.y) + ((size_t)b * g.M + mt0 * 32) * 196 + 98 * hf + piece * 16;
@@ -458,8 +430,8 @@ __global__ __launch_bounds__(512, 2) void fused_dwpw14_kernel(FusedArgs a) {
       }
     }
   } else {
-    round(std::false_type{}, std::true_type{}, OD{}, R, R - 1);
-    PLHIP_FW_STAMP(12);
+    round(std::false_type{}, std::true_type{}, R, R - 1);
+    PLHIP_STAMP(12);
     const float fcap = g.act == ACT_RELU6 ? g.alpha : __builtin_huge_valf();
     const float flo = (g.act == ACT_RELU || g.act == ACT_RELU6) ? 0.f : -__builtin_huge_valf();
 #pragma unroll
@@ -503,10 +475,10 @@ __global__ __launch_bounds__(512, 2) void fused_dwpw14_kernel(FusedArgs a) {
       }
     }
   }
-  PLHIP_FW_STAMP(14);
+  PLHIP_STAMP(14);
   if (diag) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    PLHIP_FW_STAMP(15);
+    PLHIP_STAMP(15);
   }
 }
 
@@ -551,47 +523,7 @@ static void launch_fused_t(const FusedArgs& a, hipStream_t s) {
     (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);           \
     hipLaunchKernelGGL(kfn, dim3(blocks), dim3(512), lds, s, a);                                                 \
   } while (0)
-  if (OUT == OUT_I8 && MTW == 2 && dwnn && pwnn && (a.pw.dbg & 12)) {
-    if ((a.pw.dbg & 12) == 4) {
-      auto kfn = fused_dwpw14_kernel<MTW, OUT, true, true, 0, 0, 1>;
-      (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      hipLaunchKernelGGL(kfn, dim3(blocks), dim3(512), lds, s, a);
-    } else if ((a.pw.dbg & 12) == 8) {
-      auto kfn = fused_dwpw14_kernel<MTW, OUT, true, true, 0, 1, 0>;
-      (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      hipLaunchKernelGGL(kfn, dim3(blocks), dim3(512), lds, s, a);
-    } else {
-      auto kfn = fused_dwpw14_kernel<MTW, OUT, true, true, 0, 0, 0>;
-      (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      hipLaunchKernelGGL(kfn, dim3(blocks), dim3(512), lds, s, a);
-    }
-    return;
-  }
-  if (OUT == OUT_I8 && MTW == 2 && dwnn && pwnn && (a.pw.dbg & 3) == 3) {
-    if (a.pw.dbg & 16) {
-      auto kfn = fused_dwpw14_kernel<MTW, OUT, true, true, 4>;
-      (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      hipLaunchKernelGGL(kfn, dim3(blocks), dim3(512), lds, s, a);
-    } else {
-      auto kfn = fused_dwpw14_kernel<MTW, OUT, true, true, 3>;
-      (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      hipLaunchKernelGGL(kfn, dim3(blocks), dim3(512), lds, s, a);
-    }
-    return;
-  }
-  if (OUT == OUT_I8 && MTW == 2 && dwnn && pwnn && (a.pw.dbg & 3)) {  // timing experiments (plhip_debug_set("fused_exp", 1 | 2))
-    if (a.pw.dbg & 1) {
-      auto kfn = fused_dwpw14_kernel<MTW, OUT, true, true, 1>;
-      (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      hipLaunchKernelGGL(kfn, dim3(blocks), dim3(512), lds, s, a);
-    } else {
-      auto kfn = fused_dwpw14_kernel<MTW, OUT, true, true, 2>;
-      (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      hipLaunchKernelGGL(kfn, dim3(blocks), dim3(512), lds, s, a);
-    }
-    return;
-  }
-  if (OUT == OUT_I8) {
+  if constexpr (OUT == OUT_I8) {
     if (dwnn && pwnn) PLHIP_FW_LAUNCH(true, true);
     else if (dwnn) PLHIP_FW_LAUNCH(true, false);
     else if (pwnn) PLHIP_FW_LAUNCH(false, true);
@@ -606,7 +538,6 @@ static void launch_fused_t(const FusedArgs& a, hipStream_t s) {
 // `a` must have passed fused_dwpw_plan with the same `out`.
 void launch_fused_dwpw(const FusedArgs& a_in, int out, hipStream_t s) {
   FusedArgs a = a_in;
-  a.pw.dbg = g_fw_debug;
   if (a.stream == 2) {
     launch_fused_small(a, out, s);
     return;
@@ -615,6 +546,7 @@ void launch_fused_dwpw(const FusedArgs& a_in, int out, hipStream_t s) {
     launch_fused_stream(a, out, s);
     return;
   }
+  PLHIP_SET_STAMPS(a.pw, "fw", sizeof(unsigned long long) * 1024 * 8 * FW_STAMP_SLOTS);
   if (a.pw.M == 512) {
     if (out == OUT_I32) launch_fused_t<2, OUT_I32>(a, s);
     else if (out == OUT_F32) launch_fused_t<2, OUT_F32>(a, s);

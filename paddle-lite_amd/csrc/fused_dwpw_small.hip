@@ -34,18 +34,9 @@ typedef float v2f_s __attribute__((ext_vector_type(2)));
 constexpr int F7_PITCH = 96;   // bytes per channel row of the image: 64 slots + pad
 constexpr int F7_WAVES = 8;
 
-// diagnostic timeline (plhip_debug_set("fused_stamps", 1)): per wave of the first 1024 blocks: 0 realtime, 1 entry, 2 first operands
-// requested, 3 parameters staged (behind the first barrier), 4 produced, 5 behind the barrier, 6 multiplied, 7 realtime end
-__device__ unsigned long long g_f7_stamps[1024 * F7_WAVES * 8];
-int debug_read_f7_stamps(void* dst, size_t bytes) {
-  if (bytes > sizeof(g_f7_stamps)) bytes = sizeof(g_f7_stamps);
-  if (hipDeviceSynchronize() != hipSuccess) return -1;
-  return hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_f7_stamps), bytes) == hipSuccess ? 0 : -1;
-}
-#define PLHIP_F7_STAMP(i)                                                                                                 \
-  do {                                                                                                                    \
-    if (diag && lane == 0) g_f7_stamps[((size_t)vb * F7_WAVES + wave) * 8 + (i)] = __builtin_amdgcn_s_memtime();          \
-  } while (0)
+// timeline stamps (EXPERIMENTS=1 builds, plhip_device.h): per wave of the first 1024 blocks, straight into the "f7" stamp
+// buffer [block][wave 8][8]: 0 realtime, 1 entry, 2 first operands requested, 3 parameters staged (behind the first barrier),
+// 4 produced, 5 behind the barrier, 6 multiplied, 7 realtime end
 
 // K, M: channels in / out; S: depthwise stride (input plane 7 S x 7 S); MB: blocks per image along M; PD: iterations in flight
 template <int K, int M, int S, int MB, int PD, int OUT, bool DWNN, bool PWNN>
@@ -69,9 +60,11 @@ __global__ __launch_bounds__(512, K >= 1024 ? 1 : 2) void fused_dwpw7_kernel(Fus
   if (vb >= nb) return;  // block-uniform
   const int b = (int)(vb / (unsigned)MB), mb = (int)(vb - (unsigned)b * MB);
   const int c = lane & 31, h = lane >> 5;
-  const bool diag = (g.dbg & 32) != 0 && vb < 1024;
-  if (diag && lane == 0) g_f7_stamps[((size_t)vb * F7_WAVES + wave) * 8] = __builtin_amdgcn_s_memrealtime();
-  PLHIP_F7_STAMP(1);
+  unsigned long long* const gstamp = PLHIP_STAMPS_OF(g);
+  const bool diag = kStamps && gstamp && vb < 1024;
+  unsigned long long* const lstamp = diag ? gstamp + ((size_t)vb * F7_WAVES + wave) * 8 : nullptr;
+  PLHIP_STAMP_REAL(0);
+  PLHIP_STAMP(1);
 
   // ------------------------------------------------------------------ produce
   const float dw_hi2 = a.dw_act == ACT_RELU6 ? fminf(a.dw_alpha + a.dw_alpha, 254.f) : 254.f;
@@ -175,7 +168,7 @@ __global__ __launch_bounds__(512, K >= 1024 ? 1 : 2) void fused_dwpw7_kernel(Fus
     }
   };
   prime(prime, integral_constant<int, 0>{});
-  PLHIP_F7_STAMP(2);
+  PLHIP_STAMP(2);
   // ---- the consumer's first operands, requested here so that they arrive under the depthwise arithmetic
   const int mt0 = mb * MTB + wave * MW;
   const uint32_t trb = (uint32_t)(((h * 2) * 8 + ((lane & 15) >> 1)) * F7_PITCH + ((lane >> 4) & 1) * 16 + (lane & 1) * 8);
@@ -215,7 +208,7 @@ __global__ __launch_bounds__(512, K >= 1024 ? 1 : 2) void fused_dwpw7_kernel(Fus
     o[4] = __float_as_uint(bi + bi);
   }
   __syncthreads();  // the parameters are in LDS (the row fetches above are in flight meanwhile)
-  PLHIP_F7_STAMP(3);
+  PLHIP_STAMP(3);
   auto steps = [&](auto self, auto it_c) __attribute__((always_inline)) -> void {
     constexpr int it = decltype(it_c)::value;
     if constexpr (it < NIT) {
@@ -225,9 +218,9 @@ __global__ __launch_bounds__(512, K >= 1024 ? 1 : 2) void fused_dwpw7_kernel(Fus
     }
   };
   steps(steps, integral_constant<int, 0>{});
-  PLHIP_F7_STAMP(4);
+  PLHIP_STAMP(4);
   __syncthreads();
-  PLHIP_F7_STAMP(5);
+  PLHIP_STAMP(5);
 
   // ------------------------------------------------------------------ consume
   v16i acc[2][MW];
@@ -260,7 +253,7 @@ __global__ __launch_bounds__(512, K >= 1024 ? 1 : 2) void fused_dwpw7_kernel(Fus
 #pragma unroll 2
   for (int ks = WD; ks < KS; ks += WD) group(ks, integral_constant<bool, false>{});
 
-  PLHIP_F7_STAMP(6);
+  PLHIP_STAMP(6);
   if (OUT != OUT_I8 && OUT != OUT_GAP) __syncthreads();  // the image is dead: its LDS becomes the output staging of the 4-byte forms
   // ------------------------------------------------------------------ epilogue
   // accumulator register r of n tile n: slot 32 n + 8 (r >> 2) + 4 h + (r & 3) = (row slot >> 3, column slot & 7); lane (c, h)
@@ -366,7 +359,7 @@ __global__ __launch_bounds__(512, K >= 1024 ? 1 : 2) void fused_dwpw7_kernel(Fus
       }
     }
   }
-  if (diag && lane == 0) g_f7_stamps[((size_t)vb * F7_WAVES + wave) * 8 + 7] = __builtin_amdgcn_s_memrealtime();
+  PLHIP_STAMP_REAL(7);
 }
 
 // shapes: 7 x 7 output planes, 3x3, pad 1: (stride 2, 512 -> 1024) and (stride 1, 1024 -> 1024): MobileNetV1's last two pairs
@@ -405,7 +398,9 @@ static void launch_small_o(const FusedArgs& a, int out, hipStream_t s) {
   else launch_small_t<K, M, S, MB, PD, OUT_I8>(a, s);
 }
 
-void launch_fused_small(const FusedArgs& a, int out, hipStream_t s) {
+void launch_fused_small(const FusedArgs& a_in, int out, hipStream_t s) {
+  FusedArgs a = a_in;
+  PLHIP_SET_STAMPS(a.pw, "f7", sizeof(unsigned long long) * 1024 * F7_WAVES * 8);
   // blocks per image along M: 1 (default) = no duplicated work, half the CUs at batch 128: what several predictors in flight
   // prefer (c3: 379 k img/s against 370 k / 370 k with two blocks / the two kernels; one step in flight 300 k / 308 k / 291 k);
   // 2 (knob FUSED_SMALL = 2) = every CU gets a block, the depthwise stage computed twice: best alone

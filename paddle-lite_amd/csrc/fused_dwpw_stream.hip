@@ -36,19 +36,10 @@ typedef float v2f __attribute__((ext_vector_type(2)));
 // pitch / 4 = 8 (mod 16): 160 / 288 / 544
 constexpr int fs_pitch(int tp) { return tp == 128 ? 160 : (tp == 224 ? 288 : 544); }
 
-// diagnostic timeline (plhip_debug_set("fused_stamps", 1)): per wave of the first 2048 tiles: 0 realtime, 1 entry, 2 operands of
-// the first PD iterations requested, 3 produced, 4 behind the barrier, 5 multiplied, 6 stores issued, 7 realtime end
+// timeline stamps (EXPERIMENTS=1 builds, plhip_device.h): per wave of the first 2048 tiles, straight into the "fs" stamp
+// buffer [tile][wave 4][FS_STAMP_SLOTS]: 0 realtime, 1 entry, 2 operands of the first PD iterations requested, 3 produced,
+// 4 behind the barrier, 5 multiplied, 6 stores issued, 7 realtime end
 constexpr int FS_STAMP_SLOTS = 8;
-__device__ unsigned long long g_fs_stamps[2048 * 4 * FS_STAMP_SLOTS];
-int debug_read_fs_stamps(void* dst, size_t bytes) {
-  if (bytes > sizeof(g_fs_stamps)) bytes = sizeof(g_fs_stamps);
-  if (hipDeviceSynchronize() != hipSuccess) return -1;
-  return hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_fs_stamps), bytes) == hipSuccess ? 0 : -1;
-}
-#define PLHIP_FS_STAMP(i)                                                                                                  \
-  do {                                                                                                                     \
-    if (diag && lane == 0) g_fs_stamps[((size_t)vb * 4 + wave) * FS_STAMP_SLOTS + (i)] = __builtin_amdgcn_s_memtime();    \
-  } while (0)
 
 // W: plane width; K, M: channels in / out; RS: output rows per strip (TR = 224 / W rows per tile, TR % RS == 0); PD: iterations
 // of operands in flight
@@ -90,9 +81,11 @@ __global__ __launch_bounds__(256, M / MP >= 256 ? 2 : 3) void fused_dwpw_stream_
   const int H = a.oh, TPI = g.NT;  // output rows; tiles per image (launcher)
   const int b = (int)(vb / (unsigned)TPI), ti = (int)(vb - (unsigned)b * TPI), tr0 = ti * TR;
   const int c = lane & 31, h = lane >> 5;
-  const bool diag = (g.dbg & 32) != 0 && vb < 2048;
-  if (diag && lane == 0) g_fs_stamps[((size_t)vb * 4 + wave) * FS_STAMP_SLOTS] = __builtin_amdgcn_s_memrealtime();
-  PLHIP_FS_STAMP(1);
+  unsigned long long* const gstamp = PLHIP_STAMPS_OF(g);
+  const bool diag = kStamps && gstamp && vb < 2048;
+  unsigned long long* const lstamp = diag ? gstamp + ((size_t)vb * 4 + wave) * FS_STAMP_SLOTS : nullptr;
+  PLHIP_STAMP_REAL(0);
+  PLHIP_STAMP(1);
 
   // ------------------------------------------------------------------ produce
   const int gl = lane / QW, q = lane - gl * QW;  // group inside the iteration, column quad
@@ -246,7 +239,7 @@ __global__ __launch_bounds__(256, M / MP >= 256 ? 2 : 3) void fused_dwpw_stream_
     }
   };
   prime(prime, integral_constant<int, 0>{});
-  PLHIP_FS_STAMP(2);
+  PLHIP_STAMP(2);
   // ---- the consumer's first operands, requested here so that they arrive under the depthwise arithmetic
   // wave -> (m split, n split): per pass m tiles [(mp MSPLIT + ms) MW, + MW), n tiles [ns NW, min(FS_NT, ns NW + NW))
   const int ms = wave % MSPLIT, ns = wave / MSPLIT;
@@ -297,9 +290,9 @@ __global__ __launch_bounds__(256, M / MP >= 256 ? 2 : 3) void fused_dwpw_stream_
     }
   };
   steps(steps, integral_constant<int, 0>{});
-  PLHIP_FS_STAMP(3);
+  PLHIP_STAMP(3);
   __syncthreads();
-  PLHIP_FS_STAMP(4);
+  PLHIP_STAMP(4);
 
   // ------------------------------------------------------------------ consume, MP passes over the output channels
   const int vrows = H - tr0 < TR ? H - tr0 : TR;  // valid rows of this tile
@@ -337,7 +330,7 @@ __global__ __launch_bounds__(256, M / MP >= 256 ? 2 : 3) void fused_dwpw_stream_
           }
         }
       }
-      if constexpr (mp == MP - 1) PLHIP_FS_STAMP(5);
+      if constexpr (mp == MP - 1) PLHIP_STAMP(5);
       // the next pass's first operands arrive under this pass's epilogue (every slot of the ring is free by now)
       if constexpr (mp + 1 < MP) pass_operands(integral_constant<int, mp + 1>{});
       // ---------------------------------------------------------------- epilogue
@@ -427,8 +420,8 @@ __global__ __launch_bounds__(256, M / MP >= 256 ? 2 : 3) void fused_dwpw_stream_
     }
   };
   pass(pass, integral_constant<int, 0>{});
-  PLHIP_FS_STAMP(6);
-  if (diag && lane == 0) g_fs_stamps[((size_t)vb * 4 + wave) * FS_STAMP_SLOTS + 7] = __builtin_amdgcn_s_memrealtime();
+  PLHIP_STAMP(6);
+  PLHIP_STAMP_REAL(7);
 }
 
 // shapes of the streaming kernel: (W, K, M) = (112, 32, 64), (56, 128, 128), (28, 256, 256): MobileNetV1's stride-1 pairs on
@@ -473,7 +466,9 @@ static void launch_stream_o(const FusedArgs& a, int out, hipStream_t s) {
   else launch_stream_t<W, K, M, TP, RS, PD, S, MP, OUT_I8>(a, s);
 }
 
-void launch_fused_stream(const FusedArgs& a, int out, hipStream_t s) {
+void launch_fused_stream(const FusedArgs& a_in, int out, hipStream_t s) {
+  FusedArgs a = a_in;
+  PLHIP_SET_STAMPS(a.pw, "fs", sizeof(unsigned long long) * 2048 * 4 * FS_STAMP_SLOTS);
   // 112-wide: 4-row tiles of 448 pixels (2-row tiles fetched and cut every input row twice: 61 us, the two kernels 56)
   if (a.stride == 2 && a.ow == 14) launch_stream_o<14, 256, 512, 128, 7, 2, 2, 2>(a, out, s);  // half images, M in two passes
   else if (a.stride == 2 && a.ow == 56) launch_stream_o<56, 64, 128, 224, 4, 2, 2>(a, out, s);

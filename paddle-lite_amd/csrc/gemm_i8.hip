@@ -20,12 +20,11 @@
 //     with, for i = 0..3, column n = 4c+i, k = 16h..16h+15.  MFMA i therefore computes columns
 //     {4c+i}, so each lane finishes with 4 CONSECUTIVE n for every output row and the int8 result is
 //     stored as one dword per row (32 lanes x 4 B = 128 contiguous bytes of an NCHW row);
-//   * four kernels share this scheme and differ in how B reaches the registers:
+//   * three kernels share this scheme and differ in how B reaches the registers:
 //       gemm_i8_nchw_kernel  private tiles, no LDS, no barrier (M <= 64 or one K-step: purely streaming layers);
 //       gemm_i8_lds_kernel   4 waves split M and share B through LDS in fragment order (register-staged loads);
 //       gemm_i8_dma_kernel   LDS-DMA ring (16-byte pieces, counted vmcnt, one barrier per K-step), A through LDS or
-//                            (NG > 0) straight into a register ring; also the implicit-GEMM route of dense k x k convs;
-//       gemm_i8_ws_kernel    wave-specialised experiment (opt-in).
+//                            (NG > 0) straight into a register ring; also the implicit-GEMM route of dense k x k convs.
 //     All of them map block b to the (b % 8)-th eighth of the N tiles (XCD-contiguous work, xcd_tile_map).
 // The MFMA's k-slot <-> (lane>>5, byte) map never matters: A and B use the same one.
 #include <stdlib.h>
@@ -84,7 +83,7 @@ __global__ __launch_bounds__(256, 2) void gemm_i8_nchw_kernel(GemmArgs g) {
   PLHIP_PRELOAD(g.wp); PLHIP_PRELOAD(g.x); PLHIP_PRELOAD(g.y); PLHIP_PRELOAD(g.scale); PLHIP_PRELOAD(g.bias);
   PLHIP_PRELOAD(g.M); PLHIP_PRELOAD(g.K); PLHIP_PRELOAD(g.KS); PLHIP_PRELOAD(g.HWX); PLHIP_PRELOAD(g.HWY); PLHIP_PRELOAD(g.XP);
   PLHIP_PRELOAD(g.NB); PLHIP_PRELOAD(g.x_bstride); PLHIP_PRELOAD(g.y_bstride); PLHIP_PRELOAD(g.MT); PLHIP_PRELOAD(g.NT);
-  PLHIP_PRELOAD(g.act); PLHIP_PRELOAD(g.alpha); PLHIP_PRELOAD(g.dbg);
+  PLHIP_PRELOAD(g.act); PLHIP_PRELOAD(g.alpha);
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // wave-uniform for the compiler too
   const uint32_t wid = blockIdx.x * 4u + (uint32_t)wave;  // MT * NT < 2^31 (launcher)
@@ -138,11 +137,11 @@ __global__ __launch_bounds__(256, 2) void gemm_i8_nchw_kernel(GemmArgs g) {
       for (int i = 0; i < 4; ++i)
         acc[a][i] = __builtin_amdgcn_mfma_i32_32x32x32_i8(ac[a], bf[i], FIRST ? zero : acc[a][i], 0, 0, 0);
   };
-  kbody(0, std::integral_constant<bool, true>{});  // (PLHIP_GEMM_DEBUG bit 1 cannot skip the first step any more)
-  for (int ks = 1; ks < ((g.dbg & 2) ? 0 : g.KS); ++ks) kbody(ks, std::integral_constant<bool, false>{});
+  kbody(0, std::integral_constant<bool, true>{});
+  for (int ks = 1; ks < g.KS; ++ks) kbody(ks, std::integral_constant<bool, false>{});
 
   if (OUT != OUT_I32) store_scale_bias<MA, OUT>(lsb, lane, my_s, my_b);
-  if (!nvalid || (g.dbg & 1)) return;
+  if (!nvalid) return;
   if (OUT == OUT_I32) {
     gemm_epilogue<MA, OUT, VEC_STORE, MFULL, ACT_NONE>(g, acc, mt, h, b, hw, lsb, g.HWY - hw);
     return;
@@ -169,7 +168,7 @@ __global__ __launch_bounds__(256, 2) void gemm_i8_lds_kernel(GemmArgs g) {
   PLHIP_PRELOAD(g.wp); PLHIP_PRELOAD(g.x); PLHIP_PRELOAD(g.y); PLHIP_PRELOAD(g.scale); PLHIP_PRELOAD(g.bias);
   PLHIP_PRELOAD(g.M); PLHIP_PRELOAD(g.K); PLHIP_PRELOAD(g.KS); PLHIP_PRELOAD(g.HWX); PLHIP_PRELOAD(g.HWY); PLHIP_PRELOAD(g.XP);
   PLHIP_PRELOAD(g.NB); PLHIP_PRELOAD(g.x_bstride); PLHIP_PRELOAD(g.y_bstride); PLHIP_PRELOAD(g.MT); PLHIP_PRELOAD(g.NT);
-  PLHIP_PRELOAD(g.act); PLHIP_PRELOAD(g.alpha); PLHIP_PRELOAD(g.dbg);
+  PLHIP_PRELOAD(g.act); PLHIP_PRELOAD(g.alpha);
   __shared__ __attribute__((aligned(16))) v4i bs[2][4][4][64];  // [buf][kstep][i][lane] : 32 KiB
   __shared__ __attribute__((aligned(16))) float lsb_all[4][2 * MA * 32];
   const int lane = threadIdx.x & 63;
@@ -240,7 +239,7 @@ __global__ __launch_bounds__(256, 2) void gemm_i8_lds_kernel(GemmArgs g) {
   if (wave < KS) stage_write(0);
   __syncthreads();
 
-  for (int s = 0; s < ((g.dbg & 2) ? 0 : S); ++s) {
+  for (int s = 0; s < S; ++s) {
     const int buf = s & 1;
     const int ks0 = 4 * s;
     const bool more = s + 1 < S;
@@ -263,7 +262,7 @@ __global__ __launch_bounds__(256, 2) void gemm_i8_lds_kernel(GemmArgs g) {
   }
 
   if (OUT != OUT_I32) store_scale_bias<MA, OUT>(lsb, lane, my_s, my_b);
-  if (!nvalid || !mactive || (g.dbg & 1)) return;
+  if (!nvalid || !mactive) return;
   if (OUT == OUT_I32) {
     gemm_epilogue<MA, OUT, VEC_STORE, MFULL, ACT_NONE>(g, acc, mt, h, b, hw, lsb, g.HWY - hw);
     return;
@@ -277,14 +276,10 @@ __global__ __launch_bounds__(256, 2) void gemm_i8_lds_kernel(GemmArgs g) {
 }
 
 // =====================================================================================================================
-// ---- diagnostic timeline (PLHIP_GEMM_DEBUG & 32; never set in production): per-wave s_memtime stamps of the LDS-DMA
-// kernel, kept in LDS during the run and flushed to this buffer at the end (plhip_debug_read_stamps reads it).
+// timeline stamps of the LDS-DMA kernel (EXPERIMENTS=1 builds, plhip_device.h): per wave, kept in LDS during the run and
+// flushed to the "gemm" stamp buffer [block < 1024][wave 4][STAMP_SLOTS] at the end (tools/gemm_timeline.py)
 constexpr int STAMP_SLOTS = 32;
-__device__ unsigned long long g_stamps[1024 * 4 * STAMP_SLOTS];
-#define PLHIP_STAMP(i)                                                                        \
-  do {                                                                                        \
-    if (diag && lane == 0) lstamp[i] = __builtin_amdgcn_s_memtime();                          \
-  } while (0)
+constexpr size_t STAMP_LDS = kStamps ? 4 * STAMP_SLOTS * 8 : 0;
 
 // LDS-DMA ring variant (the fast path for MFMA-heavy layers: M >= 256-ish, K >= 128, 4-byte aligned rows).
 // PMC on the register-staged kernel showed MFMA busy ~13 % per wave and one full memory latency per stage: register
@@ -319,7 +314,7 @@ __global__ __launch_bounds__(256, GD_D <= 4 ? 2 : 1) void gemm_i8_dma_kernel(Gem
   PLHIP_PRELOAD(g.wp); PLHIP_PRELOAD(g.x); PLHIP_PRELOAD(g.y); PLHIP_PRELOAD(g.scale); PLHIP_PRELOAD(g.bias);
   PLHIP_PRELOAD(g.M); PLHIP_PRELOAD(g.K); PLHIP_PRELOAD(g.KS); PLHIP_PRELOAD(g.HWX); PLHIP_PRELOAD(g.HWY); PLHIP_PRELOAD(g.XP);
   PLHIP_PRELOAD(g.NB); PLHIP_PRELOAD(g.x_bstride); PLHIP_PRELOAD(g.y_bstride); PLHIP_PRELOAD(g.MT); PLHIP_PRELOAD(g.NT);
-  PLHIP_PRELOAD(g.act); PLHIP_PRELOAD(g.alpha); PLHIP_PRELOAD(g.dbg);
+  PLHIP_PRELOAD(g.act); PLHIP_PRELOAD(g.alpha);
   PLHIP_PRELOAD(g.im_kw); PLHIP_PRELOAD(g.im_khkw); PLHIP_PRELOAD(g.im_c); PLHIP_PRELOAD(g.im_ph); PLHIP_PRELOAD(g.im_pw); PLHIP_PRELOAD(g.im_oh);
   constexpr int GD_NS = GD_D + 1;
   constexpr int SLOT = AREG ? 4096 : 4096 + 4 * MA * 1024;
@@ -386,13 +381,12 @@ __global__ __launch_bounds__(256, GD_D <= 4 ? 2 : 1) void gemm_i8_dma_kernel(Gem
   const int8_t* ab = g.wp + (size_t)mtc * MA * g.KS * 1024 + lane * 16;
   const int KS = g.KS;
   float* lsb = reinterpret_cast<float*>(ring + GD_NS * SLOT) + wave * 2 * MA * 32;
-  const bool diag = (g.dbg & 32) != 0;
+  unsigned long long* const gstamp = PLHIP_STAMPS_OF(g);
+  const bool diag = kStamps && gstamp;
   unsigned long long* lstamp = reinterpret_cast<unsigned long long*>(ring + GD_NS * SLOT + 4 * 2 * MA * 32 * 4) + wave * STAMP_SLOTS;
-  if (diag && lane == 0) {
-    lstamp[0] = __builtin_amdgcn_s_memrealtime();
-    lstamp[1] = __builtin_amdgcn_s_memtime();
-    lstamp[2] = (unsigned long long)__builtin_amdgcn_s_getreg(63492) | ((unsigned long long)__builtin_amdgcn_s_getreg(63508) << 32);
-  }
+  PLHIP_STAMP_REAL(0);
+  PLHIP_STAMP(1);
+  PLHIP_STAMP_CLOCK(2, (unsigned long long)__builtin_amdgcn_s_getreg(63492) | ((unsigned long long)__builtin_amdgcn_s_getreg(63508) << 32));
 
   auto issue = [&](int ks, int slot) {
     uint8_t* sb = ring + slot * SLOT;
@@ -510,16 +504,11 @@ __global__ __launch_bounds__(256, GD_D <= 4 ? 2 : 1) void gemm_i8_dma_kernel(Gem
     constexpr bool ISSUE = decltype(issue_c)::value;
     constexpr bool NEXT = decltype(next_c)::value;
     if (ks < STAMP_SLOTS - 8) PLHIP_STAMP(4 + ks);
-    const bool sub = diag && (g.dbg & 64) && ks == 6;  // sub-stamps of one steady-state K-step (they perturb it: the
-                                                        // s_memtime results force lgkmcnt(0), i.e. wait for the LDS reads)
     if (NEXT) {
       wait_vmcnt<YOUNGER * PER>();
-      if (sub && lane == 0) lstamp[20] = __builtin_amdgcn_s_memtime();
       __builtin_amdgcn_s_barrier();  // K-step ks+1 complete for everyone; nobody reads K-step ks-1's slot any more
-      if (sub && lane == 0) lstamp[21] = __builtin_amdgcn_s_memtime();
       read_slot(rslot, raw, af_nxt);
       rslot = rslot + 1 == GD_NS ? 0 : rslot + 1;
-      if (sub && lane == 0) lstamp[22] = __builtin_amdgcn_s_memtime();
     }
     if (ISSUE) {
       issue(ks + AHEAD, islot);
@@ -547,7 +536,6 @@ __global__ __launch_bounds__(256, GD_D <= 4 ? 2 : 1) void gemm_i8_dma_kernel(Gem
       __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
       __builtin_amdgcn_sched_group_barrier(0x002, (32 + NM - LEAD - 1) / (NM - LEAD), 0);
     }
-    if (sub && lane == 0) lstamp[23] = __builtin_amdgcn_s_memtime();
     // AREG: the fragments of K-step ks+AHEAD replace the ones just consumed.  At the END of the step: an asm statement
     // closes the scheduling region, and the MFMA / v_perm interleave above must stay in one region.
     if (AREG && ISSUE) load_a_regs(ks + AHEAD, aring[RI]);
@@ -565,50 +553,46 @@ __global__ __launch_bounds__(256, GD_D <= 4 ? 2 : 1) void gemm_i8_dma_kernel(Gem
   typedef integral_constant<bool, false> F_;
   if (AREG) {
     // unrolled by the ring size: K-step ks uses aring[ks % 4]; KS == 4 * NG, so the last group is the peeled tail
-    if (!(g.dbg & 2)) {
-      int ks = 0;
-      // (the very first step multiplies into a zero addend: FIRST)
-      if (NG > 1) {
-        step(0, integral_constant<int, 2>{}, T_{}, T_{}, integral_constant<int, 0>{}, T_{});
-        step(1, integral_constant<int, 2>{}, T_{}, T_{}, integral_constant<int, 1>{}, F_{});
-        step(2, integral_constant<int, 2>{}, T_{}, T_{}, integral_constant<int, 2>{}, F_{});
-        step(3, integral_constant<int, 2>{}, T_{}, T_{}, integral_constant<int, 3>{}, F_{});
-        ks = 4;
-      }
-#pragma unroll
-      for (int gi = 1; gi + 1 < NG; ++gi, ks += 4) {
-        step(ks, integral_constant<int, 2>{}, T_{}, T_{}, integral_constant<int, 0>{}, F_{});
-        step(ks + 1, integral_constant<int, 2>{}, T_{}, T_{}, integral_constant<int, 1>{}, F_{});
-        step(ks + 2, integral_constant<int, 2>{}, T_{}, T_{}, integral_constant<int, 2>{}, F_{});
-        step(ks + 3, integral_constant<int, 2>{}, T_{}, T_{}, integral_constant<int, 3>{}, F_{});
-      }
-      if (NG > 1) step(ks, integral_constant<int, 2>{}, F_{}, T_{}, integral_constant<int, 0>{}, F_{});
-      else step(ks, integral_constant<int, 2>{}, F_{}, T_{}, integral_constant<int, 0>{}, T_{});
-      step(ks + 1, integral_constant<int, 1>{}, F_{}, T_{}, integral_constant<int, 1>{}, F_{});
-      step(ks + 2, integral_constant<int, 0>{}, F_{}, T_{}, integral_constant<int, 2>{}, F_{});
-      step(ks + 3, integral_constant<int, 0>{}, F_{}, F_{}, integral_constant<int, 3>{}, F_{});
+    int ks = 0;
+    // (the very first step multiplies into a zero addend: FIRST)
+    if (NG > 1) {
+      step(0, integral_constant<int, 2>{}, T_{}, T_{}, integral_constant<int, 0>{}, T_{});
+      step(1, integral_constant<int, 2>{}, T_{}, T_{}, integral_constant<int, 1>{}, F_{});
+      step(2, integral_constant<int, 2>{}, T_{}, T_{}, integral_constant<int, 2>{}, F_{});
+      step(3, integral_constant<int, 2>{}, T_{}, T_{}, integral_constant<int, 3>{}, F_{});
+      ks = 4;
     }
+#pragma unroll
+    for (int gi = 1; gi + 1 < NG; ++gi, ks += 4) {
+      step(ks, integral_constant<int, 2>{}, T_{}, T_{}, integral_constant<int, 0>{}, F_{});
+      step(ks + 1, integral_constant<int, 2>{}, T_{}, T_{}, integral_constant<int, 1>{}, F_{});
+      step(ks + 2, integral_constant<int, 2>{}, T_{}, T_{}, integral_constant<int, 2>{}, F_{});
+      step(ks + 3, integral_constant<int, 2>{}, T_{}, T_{}, integral_constant<int, 3>{}, F_{});
+    }
+    if (NG > 1) step(ks, integral_constant<int, 2>{}, F_{}, T_{}, integral_constant<int, 0>{}, F_{});
+    else step(ks, integral_constant<int, 2>{}, F_{}, T_{}, integral_constant<int, 0>{}, T_{});
+    step(ks + 1, integral_constant<int, 1>{}, F_{}, T_{}, integral_constant<int, 1>{}, F_{});
+    step(ks + 2, integral_constant<int, 0>{}, F_{}, T_{}, integral_constant<int, 2>{}, F_{});
+    step(ks + 3, integral_constant<int, 0>{}, F_{}, F_{}, integral_constant<int, 3>{}, F_{});
   } else {
-    const int kmain = (g.dbg & 2) ? 0 : KS - AHEAD;
+    const int kmain = KS - AHEAD;
     for (int ks = 0; ks < kmain; ++ks) step(ks, integral_constant<int, AHEAD - 2>{}, T_{}, T_{}, integral_constant<int, 0>{}, F_{});
-    if (!(g.dbg & 2)) {
-      // peeled tail: K-steps KS-AHEAD .. KS-1, nothing left to issue, the in-flight count shrinks
-      static_assert(AHEAD >= 2 && AHEAD <= 8, "tail is written for 2..8 K-steps ahead");
-      int ks = KS - AHEAD;
+    // peeled tail: K-steps KS-AHEAD .. KS-1, nothing left to issue, the in-flight count shrinks
+    static_assert(AHEAD >= 2 && AHEAD <= 8, "tail is written for 2..8 K-steps ahead");
+    int ks = KS - AHEAD;
 #define PLHIP_TAIL(T)                                                                                                    \
   if (AHEAD - 1 > T) {                                                                                                   \
     step(ks, integral_constant<int, (AHEAD - 2 - T > 0 ? AHEAD - 2 - T : 0)>{}, F_{}, T_{}, integral_constant<int, 0>{}, F_{}); \
     ++ks;                                                                                                                \
   }
-      PLHIP_TAIL(0) PLHIP_TAIL(1) PLHIP_TAIL(2) PLHIP_TAIL(3) PLHIP_TAIL(4) PLHIP_TAIL(5) PLHIP_TAIL(6)
+    PLHIP_TAIL(0) PLHIP_TAIL(1) PLHIP_TAIL(2) PLHIP_TAIL(3) PLHIP_TAIL(4) PLHIP_TAIL(5) PLHIP_TAIL(6)
 #undef PLHIP_TAIL
-      step(ks, integral_constant<int, 0>{}, F_{}, F_{}, integral_constant<int, 0>{}, F_{});
-    }
+    step(ks, integral_constant<int, 0>{}, F_{}, F_{}, integral_constant<int, 0>{}, F_{});
   }
 
   if (OUT != OUT_I32) store_scale_bias<MA, OUT>(lsb, lane, my_s, my_b);
   PLHIP_STAMP(STAMP_SLOTS - 4);
-  if (nvalid && mactive && !(g.dbg & 1)) {
+  if (nvalid && mactive) {
     if (OUT == OUT_I32) {
       gemm_epilogue<MA, OUT, VEC_STORE, MFULL, ACT_NONE>(g, acc, mt, h, b, hw, lsb, g.HWY - hw, skip);
     } else {
@@ -623,187 +607,12 @@ __global__ __launch_bounds__(256, GD_D <= 4 ? 2 : 1) void gemm_i8_dma_kernel(Gem
   if (diag) {  // wave-uniform
     PLHIP_STAMP(STAMP_SLOTS - 3);  // epilogue instructions issued
     wait_vmcnt<0>();
-    if (lane == 0) {
-      lstamp[STAMP_SLOTS - 2] = __builtin_amdgcn_s_memtime();  // stores acknowledged
-      lstamp[STAMP_SLOTS - 1] = __builtin_amdgcn_s_memrealtime();
-    }
-    if (blockIdx.x < 1024 && lane < STAMP_SLOTS) g_stamps[((size_t)blockIdx.x * 4 + wave) * STAMP_SLOTS + lane] = lstamp[lane];
+    PLHIP_STAMP(STAMP_SLOTS - 2);  // stores acknowledged
+    PLHIP_STAMP_REAL(STAMP_SLOTS - 1);
+    if (blockIdx.x < 1024 && lane < STAMP_SLOTS) gstamp[((size_t)blockIdx.x * 4 + wave) * STAMP_SLOTS + lane] = lstamp[lane];
   }
 }
 
-// =====================================================================================================================
-// Wave-specialised variant (producer / consumer) for the MFMA-heavy layers.
-// PMC + ablation on the ring kernel: per K-step every wave ran the chain  barrier -> 18 LDS reads -> 32 v_perm -> 8 MFMA,
-// and with <= 2 waves per SIMD nothing overlapped it (MFMA busy 13 %); a deeper ring changed nothing.  Here the roles are
-// split so that the matrix pipes only ever see ds_read_b128 + MFMA:
-//   * waves 4,5 = PRODUCERS.  Producer p owns k-rows {8p..8p+7, 16+8p..16+8p+7} of every K-step: it fetches them by
-//     LDS-DMA into a PRIVATE ring (5 K-steps in flight, counted vmcnt, no cross-wave dependency on raw data), reads
-//     them back, transposes (16 v_perm) and writes its 8-byte half of the four B fragments into the shared, double
-//     buffered fragment area;
-//   * waves 0-3 = CONSUMERS (64 x 128 outputs each): 4 ds_read_b128 for B, A fragments straight from L2 through a
-//     4-deep register ring (their only vector-memory traffic, so the in-order vmcnt never couples to anything slow),
-//     8 MFMAs per K-step;
-//   * one s_barrier per K-step hands fragment buffer (ks+1)&1 to the consumers and buffer ks&1 back to the producers.
-#ifdef PLHIP_EXPERIMENTS  // make EXPERIMENTS=1 (PLHIP_GEMM_VARIANT=5): slower than the ring kernel, kept as a record
-#define WS_D 5   // K-steps a producer keeps in flight
-#define WS_NS 6  // slots of its private raw ring
-
-template <int OUT, bool VEC_STORE, bool MFULL>
-__global__ __launch_bounds__(384, 2) void gemm_i8_ws_kernel(GemmArgs g) {
-  constexpr int MA = 2;
-  // ONE LDS object: [2 fragment buffers x 4 KiB][2 producers x WS_NS x 2 KiB raw rings][4 consumers x scale/bias]
-  __shared__ __attribute__((aligned(16))) uint8_t sm[2 * 4096 + 2 * WS_NS * 2048 + 4 * 2 * MA * 32 * 4];
-  typedef __attribute__((address_space(3))) void* lds_ptr;
-  typedef const __attribute__((address_space(1))) void* glb_ptr;
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int mtb_n = (g.MT + 3) >> 2;
-  int mtb, nt;
-  xcd_tile_map(blockIdx.x, mtb_n, g.NT, mtb, nt);
-  if (nt >= g.NT) return;  // block-uniform
-  const int c = lane & 31, h = lane >> 5;
-  const int ntot = g.NB * g.HWX;
-  int n4 = nt * 128 + 4 * c;
-  const bool nvalid = n4 < ntot;
-  if (!nvalid) n4 = 0;
-  const int b = n4 / g.HWX;
-  const int hw = n4 - b * g.HWX;
-  const int KS = g.KS;
-  v4i* frags = reinterpret_cast<v4i*>(sm);  // [buf][i][lane]
-
-  if (wave >= 4) {
-    // ------------------------------------------------------------------ producer
-    const int p = wave - 4;
-    uint8_t* ring = sm + 2 * 4096 + p * WS_NS * 2048;
-    const int8_t* xb = g.x + (size_t)b * g.x_bstride + hw;
-    auto issue = [&](int ks, int slot) {
-      uint8_t* sb = ring + slot * 2048;
-#pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        const int lrow = 2 * q;                                   // local rows lrow, lrow+1 (lanes 0-31 / 32-63)
-        const int krow = (q < 4 ? 8 * p : 16 + 8 * p) + 2 * (q & 3);  // k-row inside the K-step
-        int k = ks * 32 + krow + h;
-        k = k < g.K ? k : g.K - 1;
-        __builtin_amdgcn_global_load_lds((glb_ptr)(xb + (size_t)k * g.XP), (lds_ptr)(sb + lrow * 128), 4, 0, 0);
-      }
-    };
-    auto transpose_to = [&](int slot, int buf) {
-      const uint8_t* sb = ring + slot * 2048;
-      uint32_t raw[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) raw[j] = *reinterpret_cast<const uint32_t*>(sb + (8 * h + j) * 128 + 4 * c);  // k = 16h + 8p + j
-      uint32_t o[2][4];
-      transpose4x4_b8(raw[0], raw[1], raw[2], raw[3], o[0][0], o[0][1], o[0][2], o[0][3]);
-      transpose4x4_b8(raw[4], raw[5], raw[6], raw[7], o[1][0], o[1][1], o[1][2], o[1][3]);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {  // dwords 2p, 2p+1 of lane's 16-byte entry of fragment i
-        uint2 v = make_uint2(o[0][i], o[1][i]);
-        *reinterpret_cast<uint2*>(reinterpret_cast<uint8_t*>(frags + (buf * 4 + i) * 64 + lane) + 8 * p) = v;
-      }
-    };
-    auto wait_landed = [&](int younger) {
-      switch (younger) {
-        case 0: wait_vmcnt<0>(); break;
-        case 1: wait_vmcnt<8>(); break;
-        case 2: wait_vmcnt<16>(); break;
-        case 3: wait_vmcnt<24>(); break;
-        default: wait_vmcnt<32>(); break;
-      }
-    };
-#pragma unroll
-    for (int t = 0; t < WS_D; ++t)
-      if (t < KS) issue(t, t);
-    {
-      const int last = WS_D - 1 < KS - 1 ? WS_D - 1 : KS - 1;
-      wait_landed(last);
-      transpose_to(0, 0);
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    int islot = WS_D % WS_NS, rslot = 1;
-    const int KSP = (KS + 3) & ~3;  // same number of hand-over barriers as the consumers
-    for (int ks = 0; ks < KSP; ++ks) {
-      if (ks + WS_D < KS) issue(ks + WS_D, islot);
-      islot = islot + 1 == WS_NS ? 0 : islot + 1;
-      if (ks + 1 < KS && !(g.dbg & 16)) {
-        const int last = ks + WS_D < KS - 1 ? ks + WS_D : KS - 1;
-        wait_landed(last - (ks + 1));
-        transpose_to(rslot, (ks + 1) & 1);
-        rslot = rslot + 1 == WS_NS ? 0 : rslot + 1;
-      }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-    }
-    return;
-  }
-
-  // -------------------------------------------------------------------- consumer
-  const int mt = mtb * 4 + wave;
-  const bool mactive = mt < g.MT;
-  const int mtc = mactive ? mt : g.MT - 1;
-  float* lsb = reinterpret_cast<float*>(sm + 2 * 4096 + 2 * WS_NS * 2048) + wave * 2 * MA * 32;
-  v16i acc[MA][4];
-#pragma unroll
-  for (int a = 0; a < MA; ++a)
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[a][i][r] = 0;
-  v4i a0[MA], a1[MA], a2[MA], a3[MA];
-  auto load_a_c = [&](int ks, v4i (&af)[MA]) {
-    if ((g.dbg & 8) && ks > 1) return;  // timing experiment: no A traffic inside the loop
-    load_a<MA>(g.wp, mtc, KS, ks < KS ? ks : KS - 1, lane, af);
-  };
-  load_a_c(0, a0);
-  load_a_c(1, a1);
-  float my_s = 1.f, my_b = 0.f;
-  if (OUT != OUT_I32) load_scale_bias<MA>(g, mtc, lane, my_s, my_b);
-  auto kstep = [&](int buf, const v4i (&af)[MA]) {
-    v4i bf[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) bf[i] = frags[(buf * 4 + i) * 64 + lane];
-#pragma unroll
-    for (int a = 0; a < MA; ++a)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) acc[a][i] = __builtin_amdgcn_mfma_i32_32x32x32_i8(af[a], bf[i], acc[a][i], 0, 0, 0);
-  };
-  __builtin_amdgcn_s_barrier();  // fragment buffer 0 is ready
-  // K loop unrolled by 4 so that the A ring uses static register names; every K-step ends with the hand-over barrier.
-  // Both roles run KSP = roundup(KS, 4) rounds (the surplus ones are empty) so that the barrier counts always match.
-  const int KSP = (KS + 3) & ~3;
-  for (int ks0 = 0; ks0 < KSP; ks0 += 4) {
-    load_a_c(ks0 + 2, a2);
-    kstep(0, a0);  // ks0 < KS always
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    load_a_c(ks0 + 3, a3);
-    if (ks0 + 1 < KS) kstep(1, a1);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    load_a_c(ks0 + 4, a0);
-    if (ks0 + 2 < KS) kstep(0, a2);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    load_a_c(ks0 + 5, a1);
-    if (ks0 + 3 < KS) kstep(1, a3);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-  }
-  if (OUT != OUT_I32) store_scale_bias<MA, OUT>(lsb, lane, my_s, my_b);
-  if (!nvalid || !mactive || (g.dbg & 1)) return;
-  if (OUT == OUT_I32) {
-    gemm_epilogue<MA, OUT, VEC_STORE, MFULL, ACT_NONE>(g, acc, mt, h, b, hw, lsb, g.HWY - hw);
-    return;
-  }
-  switch (g.act) {
-    case ACT_RELU: gemm_epilogue<MA, OUT, VEC_STORE, MFULL, ACT_RELU>(g, acc, mt, h, b, hw, lsb, g.HWY - hw); break;
-    case ACT_RELU6: gemm_epilogue<MA, OUT, VEC_STORE, MFULL, ACT_RELU6>(g, acc, mt, h, b, hw, lsb, g.HWY - hw); break;
-    case ACT_LEAKY: gemm_epilogue<MA, OUT, VEC_STORE, MFULL, ACT_LEAKY>(g, acc, mt, h, b, hw, lsb, g.HWY - hw); break;
-    default: gemm_epilogue<MA, OUT, VEC_STORE, MFULL, ACT_NONE>(g, acc, mt, h, b, hw, lsb, g.HWY - hw); break;
-  }
-}
-
-#endif  // PLHIP_EXPERIMENTS
 
 // ---- weight pre-pack: [G][Mg][Kg] row-major (OIHW flattened) -> [G][MT32][KS][64 lanes][16 B] ----
 // lane (r = lane&31, h = lane>>5), byte j  <-  W[g][mt32*32 + r][ks*32 + 16h + j]   (0 outside).
@@ -873,12 +682,7 @@ __global__ __launch_bounds__(256) void im2col_i8_kernel(Im2colArgs a) {
 }
 
 // ---- host-side launchers (called from plhip_capi.hip) ----
-int debug_read_stamps(void* dst, size_t bytes) {
-  if (bytes > sizeof(unsigned long long) * 1024 * 4 * STAMP_SLOTS) bytes = sizeof(unsigned long long) * 1024 * 4 * STAMP_SLOTS;
-  return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_stamps), bytes, 0, hipMemcpyDeviceToHost);
-}
-
-static int gemm_variant() {  // PLHIP_GEMM_VARIANT: 0 auto, 1 private-tile kernel, 2 register-staged LDS kernel, 3 LDS-DMA ring, 5 wave-specialised
+static int gemm_variant() {  // PLHIP_GEMM_VARIANT: 0 auto, 1 private-tile kernel, 2 register-staged LDS kernel, 3 LDS-DMA ring
   const int v = knob("GEMM_VARIANT", 0);
   return v;
 }
@@ -888,19 +692,6 @@ static void launch_gemm_t(const GemmArgs& g_in, bool vec_store, bool aligned, hi
   GemmArgs g = g_in;
   const bool mfull = g.M % (32 * MA) == 0;
   const int var = gemm_variant();
-#ifdef PLHIP_EXPERIMENTS
-  const bool use_ws = MA == 2 && aligned && var == 5 && g.im_kw == 0;  // experiment, opt-in: slower than the ring
-  if (use_ws) {
-    const unsigned blocks = (unsigned)(((g.MT + 3) / 4) * (long)((g.NT + 7) / 8 * 8));
-    if (vec_store && mfull)
-      hipLaunchKernelGGL((gemm_i8_ws_kernel<OUT, true, true>), dim3(blocks), dim3(384), 0, s, g);
-    else if (vec_store)
-      hipLaunchKernelGGL((gemm_i8_ws_kernel<OUT, true, false>), dim3(blocks), dim3(384), 0, s, g);
-    else
-      hipLaunchKernelGGL((gemm_i8_ws_kernel<OUT, false, false>), dim3(blocks), dim3(384), 0, s, g);
-    return;
-  }
-#endif
   // (32-row wave tiles with a short K -- e.g. 128->128 at 56x56 -- run faster on the register-staged kernel: 24.8 vs 26.6 us)
   const bool use_dma = g.im_kw > 0 ||  // the implicit-GEMM route exists only in the ring kernel (conv_geom checked the shape)
                        (g.HWX >= 16 && g.KS >= 4 && (var == 3 || (var == 0 && g.MT >= 4 && (MA == 2 || g.KS >= 8))));
@@ -909,12 +700,13 @@ static void launch_gemm_t(const GemmArgs& g_in, bool vec_store, bool aligned, hi
     // for the dword kernels; this kernel moves END-aligned 16-byte pieces and must know the TRUE row length, or the last
     // piece of a row reaches HWX - XP bytes into the next row -- and past the end of the tensor on its last row
     if (g.im_kw == 0 && g.XP > 0 && g.XP < g.HWX) g.HWX = g.XP;
+    PLHIP_SET_STAMPS(g, "gemm", sizeof(unsigned long long) * 1024 * 4 * STAMP_SLOTS);
     g.NT = (int)(((long)g.NB * ((g.HWX + 15) & ~15) + 127) / 128);  // 16-byte padded column space of this kernel
     const unsigned blocks = (unsigned)(((g.MT + 3) / 4) * (long)((g.NT + 7) / 8 * 8));
     const int areg_env = knob("GEMM_AREG", 1);
     const int ng = (areg_env && (g.KS & 3) == 0 && mfull && MA == 2) ? g.KS >> 2 : 0;
     const bool areg = ng == 1 || ng == 2 || ng == 4 || ng == 8;  // K = 128 / 256 / 512 / 1024
-    const size_t lds = (size_t)(4 + 1) * (areg ? 4096 : 4096 + 4 * MA * 1024) + 4 * 2 * MA * 32 * 4 + 4 * STAMP_SLOTS * 8;
+    const size_t lds = (size_t)(4 + 1) * (areg ? 4096 : 4096 + 4 * MA * 1024) + 4 * 2 * MA * 32 * 4 + STAMP_LDS;
 #define PLHIP_LAUNCH_DMA2(VS, MF, NGV)                                                                            \
   do {                                                                                                            \
     auto kfn = gemm_i8_dma_kernel<MA, OUT, VS, MF, 4, NGV>;                                                       \
@@ -972,8 +764,6 @@ int launch_gemm_i8(const GemmArgs& g_in, int ma, int out, bool vec_store, bool a
   // (32-row wave tiles): do so for M <= 128, where 64-row tiles would leave waves of the 4-wave block without work.
   const int ma_env = knob("GEMM_MA", 0);
   GemmArgs g = g_in;
-  const int dbg_env = knob("GEMM_DEBUG", 0);
-  g.dbg = dbg_env;
   // The transposed-read ring kernel (gemm_tr_i8.hip) is the implicit-GEMM engine (any M > 32, rows down to 7 columns).
   // For plain 1x1 / im2col GEMMs it is opt-in (PLHIP_GEMM_TR=2): measured on MobileNetV1's pointwise layers it ties
   // the first-generation ring kernel at batch 128 and loses at batch 256 (both are bound by the
@@ -981,15 +771,13 @@ int launch_gemm_i8(const GemmArgs& g_in, int ma, int out, bool vec_store, bool a
   // It moves END-aligned 16-byte pieces and must know the TRUE row length of a dense slab (HW = 49).
   // Third generation (gemm_wide_i8.hip): plain 1x1 GEMMs with M >= 256 and K in {128, 256, 512, 1024}: one 256 x (128..256)
   // tile per CU, the weight panel read once per CU, every operand byte in flight before the first MFMA.
-  if (g.im_kw == 0 && gemm_variant() == 0 && (dbg_env & ~32) == 0) {
+  if (g.im_kw == 0 && gemm_variant() == 0) {
     GemmArgs t = g;
     if (t.XP > 0 && t.XP < t.HWX) t.HWX = t.XP;  // the TRUE row length of a dense slab
     if (launch_gemm_wide(t, out, s)) return 0;
   }
-  // (stride-2 / short-row implicit GEMMs exist on the transposed-read kernel ONLY: the timing bits of PLHIP_GEMM_DEBUG must
-  // not send them to a first-generation kernel, which would read outside its operands: a GPU memory fault, seen once)
   const bool tr_only = g.im_kw > 0 && (g.im_s == 2 || g.HWX < 16);
-  if (g.M > 32 && (g.im_kw > 0 || (gemm_variant() == 0 && gemm_tr_enabled() >= 2)) && ((dbg_env & ~96) == 0 || tr_only)) {
+  if (g.M > 32 && (g.im_kw > 0 || (gemm_variant() == 0 && gemm_tr_enabled() >= 2))) {
     GemmArgs t = g;
     if (t.im_kw == 0 && t.XP > 0 && t.XP < t.HWX) t.HWX = t.XP;
     if (launch_gemm_tr(t, out, s)) return 0;

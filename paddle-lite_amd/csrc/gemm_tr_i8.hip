@@ -34,14 +34,10 @@
 
 namespace plhip {
 
-// ---- diagnostic timeline (PLHIP_GEMM_DEBUG & 32; never set in production): per-wave s_memtime stamps kept in LDS during
-// the run and flushed to this buffer at the end (plhip_debug_read_stamps reads it; tools/gemm_timeline.py --tr)
+// timeline stamps (EXPERIMENTS=1 builds, plhip_device.h): per wave, kept in LDS during the run and flushed to the "tr"
+// stamp buffer [block < 1024][wave 8][TR_STAMP_SLOTS] at the end (tools/gemm_timeline.py --tr)
 constexpr int TR_STAMP_SLOTS = 32;
-__device__ unsigned long long g_tr_stamps[1024 * 8 * TR_STAMP_SLOTS];
-#define PLHIP_TR_STAMP(i)                                                 \
-  do {                                                                    \
-    if (diag && lane == 0) lstamp[i] = __builtin_amdgcn_s_memtime();      \
-  } while (0)
+constexpr size_t TR_STAMP_LDS = kStamps ? 8 * TR_STAMP_SLOTS * 8 : 0;
 
 // WN x WM waves; every wave owns 128 (n) x 64 (m) outputs = 4 x 2 MFMA tiles.  D K-steps in flight, D + 1 ring slots.
 template <int WN, int WM, int OUT, int D, bool IM>
@@ -55,7 +51,7 @@ __global__ __launch_bounds__(64 * WN * WM, 2) void gemm_i8_tr_kernel(GemmArgs g)
   PLHIP_PRELOAD(g.wp); PLHIP_PRELOAD(g.x); PLHIP_PRELOAD(g.y); PLHIP_PRELOAD(g.scale); PLHIP_PRELOAD(g.bias);
   PLHIP_PRELOAD(g.M); PLHIP_PRELOAD(g.K); PLHIP_PRELOAD(g.KS); PLHIP_PRELOAD(g.HWX); PLHIP_PRELOAD(g.HWY); PLHIP_PRELOAD(g.XP);
   PLHIP_PRELOAD(g.NB); PLHIP_PRELOAD(g.x_bstride); PLHIP_PRELOAD(g.y_bstride); PLHIP_PRELOAD(g.MT); PLHIP_PRELOAD(g.NT);
-  PLHIP_PRELOAD(g.act); PLHIP_PRELOAD(g.alpha); PLHIP_PRELOAD(g.dbg);
+  PLHIP_PRELOAD(g.act); PLHIP_PRELOAD(g.alpha);
   PLHIP_PRELOAD(g.im_kw); PLHIP_PRELOAD(g.im_khkw); PLHIP_PRELOAD(g.im_c); PLHIP_PRELOAD(g.im_ph); PLHIP_PRELOAD(g.im_pw); PLHIP_PRELOAD(g.im_oh); PLHIP_PRELOAD(g.im_s);
   extern __shared__ __attribute__((aligned(16))) uint8_t ring[];  // NS * SLOT, ONE LDS object
   const int lane = threadIdx.x & 63;
@@ -64,21 +60,15 @@ __global__ __launch_bounds__(64 * WN * WM, 2) void gemm_i8_tr_kernel(GemmArgs g)
   int mb, nb;
   tr_xcd_tile_map(blockIdx.x, g.MT, g.NT, mb, nb);  // g.MT = blocks along M, g.NT = blocks along N (set by the launcher)
   if (nb >= g.NT) return;                            // block-uniform (grid padded to 8 N blocks)
-  // experiment (PLHIP_TR_DELAY, units of 64 clocks): the second block of a CU starts late, so that its K loop runs
-  // beside the first block's epilogue (VALU + stores) instead of beside its K loop
-  if ((g.dbg >> 8) > 0 && blockIdx.x >= 256) {
-    for (int i = 0; i < (g.dbg >> 8); i += 100) __builtin_amdgcn_s_sleep(100);
-  }
   const int c = lane & 31, h = lane >> 5;
   const int KS = g.KS;
   const int MT32 = (g.M + 31) >> 5;
-  const bool diag = (g.dbg & 32) != 0;
+  unsigned long long* const gstamp = PLHIP_STAMPS_OF(g);
+  const bool diag = kStamps && gstamp;
   unsigned long long* lstamp = reinterpret_cast<unsigned long long*>(ring + NS * SLOT) + wave * TR_STAMP_SLOTS;
-  if (diag && lane == 0) {
-    lstamp[0] = __builtin_amdgcn_s_memrealtime();
-    lstamp[1] = __builtin_amdgcn_s_memtime();
-    lstamp[2] = (unsigned long long)__builtin_amdgcn_s_getreg(63492) | ((unsigned long long)__builtin_amdgcn_s_getreg(63508) << 32);
-  }
+  PLHIP_STAMP_REAL(0);
+  PLHIP_STAMP(1);
+  PLHIP_STAMP_CLOCK(2, (unsigned long long)__builtin_amdgcn_s_getreg(63492) | ((unsigned long long)__builtin_amdgcn_s_getreg(63508) << 32));
   constexpr bool implicit = IM;  // implicit GEMM on the zero-padded input copy (g.im_kw > 0)
 
   // ---- column space (gemm_i8_dma_kernel): every image's HWX columns padded to HWP = roundup(HWX, 16); the last
@@ -211,7 +201,7 @@ __global__ __launch_bounds__(64 * WN * WM, 2) void gemm_i8_tr_kernel(GemmArgs g)
   // ---- pipeline (the launcher guarantees KS >= D) ----
 #pragma unroll
   for (int p = 0; p < D; ++p) issue(p, p);
-  PLHIP_TR_STAMP(3);
+  PLHIP_STAMP(3);
   v16i acc[4][2];
 #pragma unroll
   for (int t = 0; t < 4; ++t)
@@ -226,21 +216,16 @@ __global__ __launch_bounds__(64 * WN * WM, 2) void gemm_i8_tr_kernel(GemmArgs g)
     constexpr int YOUNGER = decltype(younger_c)::value;
     constexpr bool ISSUE = decltype(issue_c)::value;
     constexpr bool NEXT = decltype(next_c)::value;
-    if (ks < TR_STAMP_SLOTS - 9) PLHIP_TR_STAMP(5 + ks);
-    const bool sub = diag && (g.dbg & 64) && ks == 6;  // sub-stamps of one steady-state K-step (they perturb it)
+    if (ks < TR_STAMP_SLOTS - 9) PLHIP_STAMP(5 + ks);
     if (NEXT) {
       tr_wait_vmcnt<YOUNGER * PW>();   // my pieces of K-step ks+1 have landed
-      if (sub && lane == 0) lstamp[22] = __builtin_amdgcn_s_memtime();
       __builtin_amdgcn_s_barrier();     // ... everyone's have; nobody reads K-step ks-1's slot any more
-      if (sub && lane == 0) lstamp[23] = __builtin_amdgcn_s_memtime();
       read_slot(rslot, nxt);
       rslot = rslot + 1 == NS ? 0 : rslot + 1;
-      if (sub && lane == 0) lstamp[24] = __builtin_amdgcn_s_memtime();
     }
     if (ISSUE) {
       issue(ks + D, islot);
       islot = islot + 1 == NS ? 0 : islot + 1;
-      if (sub && lane == 0) lstamp[25] = __builtin_amdgcn_s_memtime();
     }
 #pragma unroll
     for (int u = 0; u < 2; ++u)
@@ -249,7 +234,6 @@ __global__ __launch_bounds__(64 * WN * WM, 2) void gemm_i8_tr_kernel(GemmArgs g)
         const v4i a = {cur.lo[t][0], cur.lo[t][1], cur.hi[t][0], cur.hi[t][1]};
         acc[t][u] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, cur.w[u], acc[t][u], 0, 0, 0);
       }
-    if (sub && lane == 0) lstamp[21] = __builtin_amdgcn_s_memtime();
     if (NEXT) wait_frags(nxt);
   };
   using std::integral_constant;
@@ -263,7 +247,7 @@ __global__ __launch_bounds__(64 * WN * WM, 2) void gemm_i8_tr_kernel(GemmArgs g)
     const int S = KS - D;
     tr_wait_vmcnt<(D - 1) * PW>();
     __builtin_amdgcn_s_barrier();
-    PLHIP_TR_STAMP(4);
+    PLHIP_STAMP(4);
     int ks = 0;
     if (S & 1) {
       read_slot(0, fs[1]);
@@ -290,7 +274,7 @@ __global__ __launch_bounds__(64 * WN * WM, 2) void gemm_i8_tr_kernel(GemmArgs g)
     }
   }
 
-  PLHIP_TR_STAMP(TR_STAMP_SLOTS - 4);
+  PLHIP_STAMP(TR_STAMP_SLOTS - 4);
   // ---- epilogue: lane (c, h) owns channel rows mrow[0], mrow[1]; per n tile t, register r <-> n = 32t + 8(r>>2) + 4h + (r&3)
   const int Jb = nb * (BN / 16) + wn * 8;  // first chunk of this wave's 128 columns
   if (OUT == OUT_I8) {
@@ -299,7 +283,7 @@ __global__ __launch_bounds__(64 * WN * WM, 2) void gemm_i8_tr_kernel(GemmArgs g)
     // Storing straight from the MFMA layout (one channel row per lane, 32 bytes contiguous per row and instruction)
     // ran at 7 B/clk/CU: 9.0k of the launch's 25k cycles on the 512->512 14x14 layer.
     __builtin_amdgcn_s_barrier();  // every wave has finished reading the ring: it becomes staging space
-    PLHIP_TR_STAMP(TR_STAMP_SLOTS - 6);
+    PLHIP_STAMP(TR_STAMP_SLOTS - 6);
     uint8_t* stg = ring + wave * (64 * 144);
     if (g.y2) {  // kernel-uniform: calib-only tail of an fp32-output conv (launch_gemm_tr): the int8 tensor is g.y2
       tr_stage_i8_calib(acc, sc, bi, g.act, g.alpha, g.inv_scale2, stg, c, h);
@@ -311,7 +295,7 @@ __global__ __launch_bounds__(64 * WN * WM, 2) void gemm_i8_tr_kernel(GemmArgs g)
         default: tr_stage_i8<ACT_NONE>(acc, sc, bi, g.alpha, stg, c, h); break;
       }
     }
-    PLHIP_TR_STAMP(TR_STAMP_SLOTS - 5);  // requantised + staged
+    PLHIP_STAMP(TR_STAMP_SLOTS - 5);  // requantised + staged
     // this lane's 16-column chunk (the same for all 8 store rounds) and its first row
     const int J = Jb + (lane & 7);
     int b = J / CPI;
@@ -430,20 +414,12 @@ __global__ __launch_bounds__(64 * WN * WM, 2) void gemm_i8_tr_kernel(GemmArgs g)
     }
   }
   if (diag) {  // wave-uniform
-    PLHIP_TR_STAMP(TR_STAMP_SLOTS - 3);  // epilogue instructions issued
+    PLHIP_STAMP(TR_STAMP_SLOTS - 3);  // epilogue instructions issued
     tr_wait_vmcnt<0>();
-    if (lane == 0) {
-      lstamp[TR_STAMP_SLOTS - 2] = __builtin_amdgcn_s_memtime();  // stores acknowledged
-      lstamp[TR_STAMP_SLOTS - 1] = __builtin_amdgcn_s_memrealtime();
-    }
-    if (blockIdx.x < 1024 && lane < TR_STAMP_SLOTS)
-      g_tr_stamps[((size_t)blockIdx.x * 8 + wave) * TR_STAMP_SLOTS + lane] = lstamp[lane];
+    PLHIP_STAMP(TR_STAMP_SLOTS - 2);  // stores acknowledged
+    PLHIP_STAMP_REAL(TR_STAMP_SLOTS - 1);
+    if (blockIdx.x < 1024 && lane < TR_STAMP_SLOTS) gstamp[((size_t)blockIdx.x * 8 + wave) * TR_STAMP_SLOTS + lane] = lstamp[lane];
   }
-}
-
-int debug_read_tr_stamps(void* dst, size_t bytes) {
-  if (bytes > sizeof(unsigned long long) * 1024 * 8 * TR_STAMP_SLOTS) bytes = sizeof(unsigned long long) * 1024 * 8 * TR_STAMP_SLOTS;
-  return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_tr_stamps), bytes, 0, hipMemcpyDeviceToHost);
 }
 
 int gemm_tr_enabled() {  // PLHIP_GEMM_TR=0: first-generation kernels only (A/B runs)
@@ -461,7 +437,7 @@ static void launch_tr_cfg2(GemmArgs g, hipStream_t s) {
   g.NT = (int)(((long)g.NB * HWP + BN - 1) / BN);  // blocks along N
   g.MT = (g.M + BM - 1) / BM;                      // blocks along M
   const unsigned blocks = (unsigned)((long)g.MT * ((g.NT + 7) / 8 * 8));
-  const size_t lds = (size_t)(D + 1) * (BN * 32 + BM * 32) + 8 * TR_STAMP_SLOTS * 8;
+  const size_t lds = (size_t)(D + 1) * (BN * 32 + BM * 32) + TR_STAMP_LDS;
   auto kfn = gemm_i8_tr_kernel<WN, WM, OUT, D, IM>;
   // per DEVICE and called from several predictor threads: set on every launch (a process-wide flag was wrong on a second GPU)
   (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -478,10 +454,7 @@ static void launch_tr_cfg(const GemmArgs& g, hipStream_t s) {
 // length of the im2col buffer / OW (implicit GEMM); KS >= 4, HWX >= 16.
 bool launch_gemm_tr(const GemmArgs& g_in, int out, hipStream_t s) {
   GemmArgs g = g_in;
-  {
-    const int delay_env = knob("TR_DELAY", 0);
-    g.dbg = (g.dbg & 0xff) | (delay_env << 8);
-  }
+  PLHIP_SET_STAMPS(g, "tr", sizeof(unsigned long long) * 1024 * 8 * TR_STAMP_SLOTS);
   // rows shorter than 16 bytes: only on the padded copy of the implicit route (a 16-byte piece may run past the row)
   if (!gemm_tr_enabled() || g.KS < 4 || (g.HWX < 16 && g.im_kw == 0)) return false;
   if ((long)g.NB * ((g.HWX + 15) & ~15) >= ((long)1 << 31) - 1024) return false;

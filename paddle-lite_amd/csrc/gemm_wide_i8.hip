@@ -30,20 +30,6 @@
 
 namespace plhip {
 
-// ---- diagnostic timeline (PLHIP_GEMM_DEBUG & 32; never set in production): the kernels write here through GemmArgs::stamps
-__device__ unsigned long long g_wide_stamps[512 * 8 * WIDE_STAMP_SLOTS];
-unsigned long long* wide_stamps_ptr() {
-  static unsigned long long* p = nullptr;
-  if (!p) (void)hipGetSymbolAddress((void**)&p, HIP_SYMBOL(g_wide_stamps));
-  return p;
-}
-
-int debug_read_wide_stamps(void* dst, size_t bytes) {
-  const size_t cap = sizeof(unsigned long long) * 512 * 8 * WIDE_STAMP_SLOTS;
-  if (bytes > cap) bytes = cap;
-  return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_wide_stamps), bytes, 0, hipMemcpyDeviceToHost);
-}
-
 static int g_wide_ntt_override = -1;  // tests / A-B runs: plhip_debug_wide_ntt (-1 = PLHIP_WIDE_NTT or automatic)
 void debug_set_wide_ntt(int v) { g_wide_ntt_override = v; }
 
@@ -74,7 +60,7 @@ int gemm_wide_ntt(const GemmArgs& g) {
     if (force && ntt != force) continue;
     {  // the activation tile + the staging images must fit the LDS (wide_lds_bytes)
       const int c1 = 2 * ntt > 8 ? 2 * ntt - 8 : 0;
-      if ((long)g.KS * 4 * (1024 + c1 * 128) + 8 * 32 * 48 + 8 * WIDE_STAMP_SLOTS * 8 > 160 * 1024) continue;
+      if ((long)g.KS * 4 * (1024 + c1 * 128) + 8 * 32 * 48 + WIDE_STAMP_LDS > 160 * 1024) continue;
     }
     const long nblocks = (chunks + 2 * ntt - 1) / (2 * ntt);
     const long blocks = nblocks * mblocks;
@@ -98,7 +84,7 @@ bool launch_gemm_wide(const GemmArgs& g_in, int out, hipStream_t s) {
   const int ntt = gemm_wide_ntt(g_in);
   if (!ntt) return false;
   GemmArgs g = g_in;
-  g.stamps = (g.dbg & 32) ? wide_stamps_ptr() : nullptr;
+  PLHIP_SET_STAMPS(g, "wide", sizeof(unsigned long long) * 512 * 8 * WIDE_STAMP_SLOTS);
   if (ntt == 4) launch_wide_n4(g, out, s);
   else if (g.KS == 32) return false;
   else if (ntt == 7) launch_wide_n7(g, out, s);

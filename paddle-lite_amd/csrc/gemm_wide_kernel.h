@@ -13,11 +13,10 @@
 
 namespace plhip {
 
+// timeline stamps (EXPERIMENTS=1 builds, plhip_device.h): per wave, kept in LDS behind the staging images and flushed to the
+// "wide" stamp buffer [block < 512][wave 8][WIDE_STAMP_SLOTS] at the end (tools/wide_timeline.py)
 constexpr int WIDE_STAMP_SLOTS = 48;  // 0-9 phases, 10 + ks: top of K-step ks (behind its barrier)
-#define PLHIP_WIDE_STAMP(i)                                                \
-  do {                                                                     \
-    if (diag && lane == 0) lstamp[i] = __builtin_amdgcn_s_memtime();       \
-  } while (0)
+constexpr int WIDE_STAMP_LDS = kStamps ? 8 * WIDE_STAMP_SLOTS * 8 : 0;
 
 // NTT 32-column n tiles per block (4, 7, 8), KS K-steps of 32 (K = 32 KS exactly); A0 K-steps are issued before the loop and
 // R more inside every K-step until all KS are in flight (issuing everything first cost 4.4 k cycles in front of the first
@@ -85,7 +84,7 @@ __global__ __launch_bounds__(512, 2) void gemm_i8_wide_kernel(GemmArgs g) {
   PLHIP_PRELOAD(g.wp); PLHIP_PRELOAD(g.x); PLHIP_PRELOAD(g.y); PLHIP_PRELOAD(g.scale); PLHIP_PRELOAD(g.bias);
   PLHIP_PRELOAD(g.M); PLHIP_PRELOAD(g.HWX); PLHIP_PRELOAD(g.HWY); PLHIP_PRELOAD(g.XP); PLHIP_PRELOAD(g.NB);
   PLHIP_PRELOAD(g.x_bstride); PLHIP_PRELOAD(g.y_bstride); PLHIP_PRELOAD(g.MT); PLHIP_PRELOAD(g.NT);
-  PLHIP_PRELOAD(g.act); PLHIP_PRELOAD(g.alpha); PLHIP_PRELOAD(g.dbg); PLHIP_PRELOAD(g.cpi_m); PLHIP_PRELOAD(g.cpi_s);
+  PLHIP_PRELOAD(g.act); PLHIP_PRELOAD(g.alpha); PLHIP_PRELOAD(g.cpi_m); PLHIP_PRELOAD(g.cpi_s);
   extern __shared__ __attribute__((aligned(16))) uint8_t ring[];  // [tile: TILE_BYTES][8 staging images][stamps]
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -93,13 +92,12 @@ __global__ __launch_bounds__(512, 2) void gemm_i8_wide_kernel(GemmArgs g) {
   tr_xcd_tile_map(blockIdx.x, g.MT, g.NT, mb, nb);  // g.MT / g.NT = blocks along M / N (launcher)
   if (nb >= g.NT) return;                            // block-uniform (grid padded to 8 N blocks)
   const int c = lane & 31, h = lane >> 5;
-  const bool diag = (g.dbg & 32) != 0;
+  unsigned long long* const gstamp = PLHIP_STAMPS_OF(g);
+  const bool diag = kStamps && gstamp;
   unsigned long long* lstamp = reinterpret_cast<unsigned long long*>(ring + TILE_BYTES + 8 * 32 * SP) + wave * WIDE_STAMP_SLOTS;
-  if (diag && lane == 0) {
-    lstamp[0] = __builtin_amdgcn_s_memrealtime();
-    lstamp[1] = __builtin_amdgcn_s_memtime();
-    lstamp[2] = (unsigned long long)__builtin_amdgcn_s_getreg(63492) | ((unsigned long long)__builtin_amdgcn_s_getreg(63508) << 32);
-  }
+  PLHIP_STAMP_REAL(0);
+  PLHIP_STAMP(1);
+  PLHIP_STAMP_CLOCK(2, (unsigned long long)__builtin_amdgcn_s_getreg(63492) | ((unsigned long long)__builtin_amdgcn_s_getreg(63508) << 32));
 
   // ---- column space: every image's HWX columns padded to HWP = roundup(HWX, 16); the last chunk of an image is
   // END-aligned (source columns HWX-16 .. HWX-1): its leading 16 - HWX%16 columns repeat the previous chunk's last ones.
@@ -170,7 +168,7 @@ __global__ __launch_bounds__(512, 2) void gemm_i8_wide_kernel(GemmArgs g) {
   };
 #pragma unroll
   for (int ks = 0; ks < A0; ++ks) issue(ks);
-  PLHIP_WIDE_STAMP(3);
+  PLHIP_STAMP(3);
 
   // ---- transposed-read addresses: tile t <-> chunk pair (2t, 2t+1); lane 2q'+p of a 16-lane group -> row q', sub-chunk
   // p; 16-lane group parity -> chunk parity; k half h -> kg {2h, 2h+1}
@@ -210,7 +208,7 @@ __global__ __launch_bounds__(512, 2) void gemm_i8_wide_kernel(GemmArgs g) {
   // memory and no barrier.
   asm volatile("s_waitcnt vmcnt(%1)" : "+v"(w[0]) : "n"(2 * (A0 - 1)) : "memory");
   __builtin_amdgcn_s_barrier();
-  PLHIP_WIDE_STAMP(4);
+  PLHIP_STAMP(4);
   {
     auto kstep = [&](auto self, auto ks_c) __attribute__((always_inline)) -> void {
       constexpr int ks = decltype(ks_c)::value;
@@ -238,7 +236,7 @@ __global__ __launch_bounds__(512, 2) void gemm_i8_wide_kernel(GemmArgs g) {
           for (int i = S1; i < KS; ++i) asm volatile("" : "+v"(w[i]));  // no use of a later fragment above this wait
           __builtin_amdgcn_s_barrier();
         }
-        if constexpr (ks < 20) PLHIP_WIDE_STAMP(10 + ks);
+        if constexpr (ks < 20) PLHIP_STAMP(10 + ks);
         auto mm = [&](auto mself, auto t_c) __attribute__((always_inline)) -> void {
           constexpr int t = decltype(t_c)::value;
           if constexpr (t < TK) {
@@ -262,7 +260,7 @@ __global__ __launch_bounds__(512, 2) void gemm_i8_wide_kernel(GemmArgs g) {
     kstep(kstep, integral_constant<int, 0>{});
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (the last counted wait already was vmcnt(0))
-  PLHIP_WIDE_STAMP(5);
+  PLHIP_STAMP(5);
 
   // ---------------------------------------------------------------------------------------------------------------
   // phase 2: the flat MFMA sequence i = t * NG + j (tile t, K-step S1 + j); fragments two MFMAs ahead in a ring of 3 sets;
@@ -356,23 +354,20 @@ __global__ __launch_bounds__(512, 2) void gemm_i8_wide_kernel(GemmArgs g) {
         if constexpr (i + 2 < Q) PLHIP_WIDE_READ(p2ks(i + 2), p2tile(i + 2), (i + 2) % 3);
         runslices(runslices, integral_constant<int, cursor(i)>{}, integral_constant<int, cursor(i + 1)>{});
         __builtin_amdgcn_sched_barrier(0);
-        if constexpr (j == KS - 1 && t < 16) PLHIP_WIDE_STAMP(30 + t);
+        if constexpr (j == KS - 1 && t < 16) PLHIP_STAMP(30 + t);
         self(self, integral_constant<int, i + 1>{});
       }
     };
     mm2(mm2, integral_constant<int, 0>{});
-    PLHIP_WIDE_STAMP(7);
+    PLHIP_STAMP(7);
     runslices(runslices, integral_constant<int, cursor(Q)>{}, integral_constant<int, 16 * NTT>{});  // what is left: the last tile at least
   }
 #undef PLHIP_WIDE_READ
   if (diag) {  // wave-uniform
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (lane == 0) {
-      lstamp[8] = __builtin_amdgcn_s_memtime();  // stores acknowledged
-      lstamp[9] = __builtin_amdgcn_s_memrealtime();
-    }
-    if (g.stamps && blockIdx.x < 512 && lane < WIDE_STAMP_SLOTS)
-      g.stamps[((size_t)blockIdx.x * 8 + wave) * WIDE_STAMP_SLOTS + lane] = lstamp[lane];
+    PLHIP_STAMP(8);  // stores acknowledged
+    PLHIP_STAMP_REAL(9);
+    if (blockIdx.x < 512 && lane < WIDE_STAMP_SLOTS) gstamp[((size_t)blockIdx.x * 8 + wave) * WIDE_STAMP_SLOTS + lane] = lstamp[lane];
   }
 }
 
@@ -393,14 +388,14 @@ static inline void launch_wide_t(GemmArgs g, hipStream_t s) {
   constexpr int A0 = 4, R = 2;
   constexpr int C1 = 2 * NTT > 8 ? 2 * NTT - 8 : 0, KSTEP = 4 * (1024 + C1 * 128);
   constexpr int LDS_MAIN = KS * KSTEP + 8 * 32 * 48;
-  static_assert(LDS_MAIN + 8 * WIDE_STAMP_SLOTS * 8 <= 160 * 1024, "LDS");
+  static_assert(LDS_MAIN + WIDE_STAMP_LDS <= 160 * 1024, "LDS");
   const int CPI = (g.HWX + 15) >> 4;
   const long chunks = (long)g.NB * CPI;
   g.NT = (int)((chunks + 2 * NTT - 1) / (2 * NTT));
   g.MT = (g.M + 255) / 256;
   cpi_magic(CPI, g.cpi_m, g.cpi_s);
   const unsigned blocks = (unsigned)((long)g.MT * ((g.NT + 7) / 8 * 8));
-  const size_t lds = (size_t)LDS_MAIN + 8 * WIDE_STAMP_SLOTS * 8;
+  const size_t lds = (size_t)LDS_MAIN + WIDE_STAMP_LDS;
   const bool nonneg = g.act == ACT_RELU || g.act == ACT_RELU6;
   if (OUT == OUT_I8 && !nonneg) {
     auto kfn = gemm_i8_wide_kernel<NTT, KS, OUT, A0, R, false>;

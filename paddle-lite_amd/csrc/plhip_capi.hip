@@ -998,49 +998,24 @@ plhip_status plhip_selftest(plhip_ctx* ctx) {
 
 }  // extern "C"
 
-// Diagnostic only (not part of include/plhip.h): timeline stamps of the last PLHIP_GEMM_DEBUG=32 GEMM launch.
-namespace plhip {
-int debug_read_stamps(void* dst, size_t bytes);
-int debug_read_tr_stamps(void* dst, size_t bytes);
-}
-extern "C" int plhip_debug_read_wide_stamps(void* dst_host, size_t bytes) {
-  if (!dst_host) return -1;
-  return plhip::debug_read_wide_stamps(dst_host, bytes);
-}
 // tests / A-B runs: force the wide-tile GEMM's n tiles per block (4, 7, 8), 0 = automatic choice, -1 = environment
-extern "C" int plhip_debug_read_patch_stamps(void* dst_host, size_t bytes) {
-  if (!dst_host) return -1;
-  return plhip::debug_read_patch_stamps(dst_host, bytes);
-}
 extern "C" void plhip_debug_wide_ntt(int v) { plhip::debug_set_wide_ntt(v); }
-extern "C" int plhip_debug_read_tr_stamps(void* dst_host, size_t bytes) {
-  (void)hipDeviceSynchronize();
-  return plhip::debug_read_tr_stamps(dst_host, bytes);
-}
-extern "C" int plhip_debug_read_fw_stamps(void* dst_host, size_t bytes) {
-  if (!dst_host) return -1;
-  return plhip::debug_read_fw_stamps(dst_host, bytes);
-}
-extern "C" int plhip_debug_read_fs_stamps(void* dst_host, size_t bytes) {
-  if (!dst_host) return -1;
-  return plhip::debug_read_fs_stamps(dst_host, bytes);
-}
-extern "C" int plhip_debug_read_f7_stamps(void* dst_host, size_t bytes) {
-  if (!dst_host) return -1;
-  return plhip::debug_read_f7_stamps(dst_host, bytes);
-}
 // Diagnostics switches of the shipped library (declared in include/plhip.h).  NOTHING in the library reads the environment:
-// the A/B and timing knobs the kernels' launchers consult (plhip::knob) live in this table and change only
-// through plhip_debug_set; an unknown key is refused.  "fused_stamps" / "fused_exp": the fused kernel's timeline / timing experiments.
+// the A/B knobs the kernels' launchers consult (plhip::knob) live in this table and change only through
+// plhip_debug_set; an unknown key is refused.  "STAMPS" (timeline stamps) exists in a `make EXPERIMENTS=1` build only.
 namespace plhip {
 namespace {
 struct Knob { const char* name; int value; bool set; };
 Knob g_knobs[] = {
-    {"STEM_MFMA", 0, false}, {"CONV_PATCH", 0, false}, {"CONV_PATCH_S2", 0, false}, {"PATCH_DEBUG", 0, false}, {"PATCH_DELAY", 0, false},
+    {"STEM_MFMA", 0, false}, {"CONV_PATCH", 0, false}, {"CONV_PATCH_S2", 0, false},
     {"STEM7", 0, false}, {"DW_STAGE", 0, false}, {"DW_STAGE_NP2", 0, false}, {"DW_FASTV", 0, false}, {"DW5_DIRECT", 0, false},
     {"DW_RS1", 0, false}, {"DW_RS2", 0, false}, {"GEMM_VARIANT", 0, false}, {"GEMM_AREG", 0, false}, {"GEMM_MA", 0, false},
-    {"GEMM_DEBUG", 0, false}, {"SUBSAMPLE_1X1", 0, false}, {"GEMM_TR", 0, false}, {"TR_DELAY", 0, false}, {"TR_CFG", 0, false},
-    {"GEMM_WIDE", 0, false}, {"WIDE_NTT", 0, false}, {"FC_MFMA", 0, false}, {"IMPLICIT_GEMM", 0, false}, {"FUSED_STREAM", 0, false}, {"FUSED_SMALL", 0, false}, {"DWCONV_FUSED", 0, false}};
+    {"SUBSAMPLE_1X1", 0, false}, {"GEMM_TR", 0, false}, {"TR_CFG", 0, false},
+    {"GEMM_WIDE", 0, false}, {"WIDE_NTT", 0, false}, {"FC_MFMA", 0, false}, {"IMPLICIT_GEMM", 0, false}, {"FUSED_STREAM", 0, false}, {"FUSED_SMALL", 0, false}, {"DWCONV_FUSED", 0, false},
+#ifdef PLHIP_EXPERIMENTS
+    {"STAMPS", 0, false},
+#endif
+};
 }  // namespace
 int knob(const char* name, int dflt) {
   for (const Knob& k : g_knobs)
@@ -1052,12 +1027,38 @@ extern "C" int plhip_debug_set(const char* key, int value) {
   if (!key) return -1;
   for (plhip::Knob& k : plhip::g_knobs)
     if (!strcmp(k.name, key)) { k.value = value; k.set = true; return 0; }
-  static int fused_bits = 0;
-  if (!strcmp(key, "fused_stamps")) { fused_bits = (fused_bits & ~32) | (value ? 32 : 0); plhip::debug_set_fused(fused_bits); return 0; }
-  if (!strcmp(key, "fused_exp")) { fused_bits = (fused_bits & ~31) | (value & 31); plhip::debug_set_fused(fused_bits); return 0; }  // timing experiments, wrong results
   return -1;
 }
-extern "C" int plhip_debug_read_stamps(void* dst_host, size_t bytes) {
-  (void)hipDeviceSynchronize();
-  return plhip::debug_read_stamps(dst_host, bytes);
+
+#ifdef PLHIP_EXPERIMENTS
+// Timeline stamp buffers, one per kernel family, allocated on the first launch that stamps.  Not part of
+// include/plhip.h: the timeline tools (tools/*_timeline.py) read them with plhip_debug_read_stamps after the launch.
+namespace plhip {
+namespace {
+struct StampBuf { const char* family; unsigned long long* p; size_t bytes; };
+StampBuf g_stamp_bufs[] = {{"gemm", nullptr, 0}, {"tr", nullptr, 0}, {"wide", nullptr, 0}, {"patch", nullptr, 0},
+                           {"fw", nullptr, 0}, {"fs", nullptr, 0}, {"f7", nullptr, 0}};
+StampBuf* find_stamp_buf(const char* family) {
+  for (StampBuf& b : g_stamp_bufs)
+    if (!strcmp(b.family, family)) return &b;
+  return nullptr;
 }
+}  // namespace
+unsigned long long* stamp_buffer(const char* family, size_t bytes) {
+  if (!knob("STAMPS", 0)) return nullptr;
+  StampBuf* b = find_stamp_buf(family);
+  if (!b->p && hipMalloc((void**)&b->p, bytes) == hipSuccess) {
+    b->bytes = bytes;
+    (void)hipMemset(b->p, 0, bytes);
+  }
+  return b->p;
+}
+}  // namespace plhip
+// the stamps of the last stamping launch of `family` ("gemm", "tr", "wide", "patch", "fw", "fs", "f7"): 0, or -1 when that
+// family has not stamped yet
+extern "C" int plhip_debug_read_stamps(const char* family, void* dst_host, size_t bytes) {
+  plhip::StampBuf* b = family && dst_host ? plhip::find_stamp_buf(family) : nullptr;
+  if (!b || !b->p || hipDeviceSynchronize() != hipSuccess) return -1;
+  return hipMemcpy(dst_host, b->p, bytes < b->bytes ? bytes : b->bytes, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1;
+}
+#endif

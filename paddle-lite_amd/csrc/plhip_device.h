@@ -104,4 +104,22 @@ __device__ __forceinline__ void transpose4x4_b8(uint32_t r0, uint32_t r1, uint32
 // the entry block, so all fields arrive with one batch of s_load.
 #define PLHIP_PRELOAD(x) asm volatile("" ::"s"(x))
 
+// ---- timeline stamps: built only by `make EXPERIMENTS=1`, where plhip_debug_set("STAMPS", 1) hands each
+// launch a stamp buffer (GemmArgs / PatchArgs::stamps).  A kernel sets `diag` from PLHIP_STAMPS_OF(args) and points `lstamp`
+// at its wave's slots; PLHIP_STAMP(i) then writes the shader clock (PLHIP_STAMP_REAL: the constant-rate clock) into slot i
+// from lane 0.  In a default build kStamps is false, the fields do not exist, and no stamp code or stamp LDS is compiled.
+#ifdef PLHIP_EXPERIMENTS
+constexpr bool kStamps = true;
+#define PLHIP_STAMPS_OF(args) ((args).stamps)
+#else
+constexpr bool kStamps = false;
+#define PLHIP_STAMPS_OF(args) ((unsigned long long*)nullptr)
+#endif
+#define PLHIP_STAMP_CLOCK(i, clock)                          \
+  do {                                                       \
+    if (::plhip::kStamps && diag && lane == 0) lstamp[i] = clock; \
+  } while (0)
+#define PLHIP_STAMP(i) PLHIP_STAMP_CLOCK(i, __builtin_amdgcn_s_memtime())
+#define PLHIP_STAMP_REAL(i) PLHIP_STAMP_CLOCK(i, __builtin_amdgcn_s_memrealtime())
+
 }  // namespace plhip

@@ -6,9 +6,17 @@
 
 namespace plhip {
 
-// A/B and timing knobs of the launchers: name -> value set through plhip_debug_set (include/plhip.h), else the
+// A/B knobs of the launchers: name -> value set through plhip_debug_set (include/plhip.h), else the
 // default.  The library never reads the environment.
 int knob(const char* name, int dflt);
+#ifdef PLHIP_EXPERIMENTS
+// timeline stamps (plhip_device.h): the stamp buffer of `family` ("gemm", "tr", "wide", "patch", "fw", "fs", "f7"), allocated
+// on first use with `bytes`, when plhip_debug_set("STAMPS", 1) is in force; else nullptr
+unsigned long long* stamp_buffer(const char* family, size_t bytes);
+#define PLHIP_SET_STAMPS(args, family, bytes) ((args).stamps = ::plhip::stamp_buffer(family, bytes))
+#else
+#define PLHIP_SET_STAMPS(args, family, bytes) ((void)0)
+#endif
 
 struct GemmArgs {
   const int8_t* wp;    // packed weights of this group: [MT32][KS][64][16]
@@ -25,7 +33,6 @@ struct GemmArgs {
   int MT, NT;          // wave tiles along M (32*MA rows) and N (128 columns)
   int act;
   float alpha;
-  int dbg;             // PLHIP_GEMM_DEBUG (timing experiments only): 1 = skip the epilogue, 2 = skip the K loop
   // fused graph tail of an fp32-output conv (OUT_F32 only; all optional, zero = plain conv):
   //   v = act(fma(acc, s, b));  if (res) v = v + res[same offset];  if (res_relu) v = max(v, 0);
   //   if (y) y = v;  if (y2) y2 = round_sat_i8(v * inv_scale2)          (calib, type_trans.cc:45,183-184)
@@ -46,7 +53,9 @@ struct GemmArgs {
   // wide-tile kernel (gemm_wide_i8.hip): fastdiv_u31's (magic, shift) for the chunks per image, set by its launcher
   unsigned cpi_m;
   int cpi_s;
-  unsigned long long* stamps;  // its diagnostic timeline buffer (PLHIP_GEMM_DEBUG & 32) or nullptr
+#ifdef PLHIP_EXPERIMENTS
+  unsigned long long* stamps;  // timeline stamp buffer of the launch, or nullptr
+#endif
 };
 
 struct PadArgs {
@@ -88,14 +97,14 @@ struct PatchArgs {
   int res_relu;
   int8_t* y2;
   float inv_scale2;
-  int dbg;
   // global mode (planes smaller than a tile: 7-wide): the padded copy is [c][image][PH][PWp], p runs over all images
   int s2;              // 3x3 stride 2 as a 2x2 conv over phase planes: C = 4 Cin, the slabs are walked with 2 taps per side
   int glob, nimg, IMGP;  // nimg = the real image count; IMGP = PH * PWp pixels per image (PLANE is then the CHANNEL stride B * IMGP, B = 1, TPI = T)
   unsigned imgp_m, hwy_m;
   int imgp_s, hwy_s;
-  int delay;           // NH = 1: s_sleep units the second block of a CU starts late (experiments)
-  unsigned long long* stamps;
+#ifdef PLHIP_EXPERIMENTS
+  unsigned long long* stamps;  // as GemmArgs::stamps
+#endif
 };
 // row pitch of the padded copy for (w, pl, pr), 0 = outside the route
 int conv_patch_row_pitch(int w, int pl, int pr);
@@ -114,7 +123,6 @@ bool conv_patch_s2_supported(int cin, int cout, int kh, int kw, int sh, int sw, 
 size_t conv_patch_s2_packed_bytes(int cin, int cout);
 void launch_pack_conv_patch_s2(const int8_t* w_oihw, int8_t* wp, int cin, int cout, hipStream_t s);
 void launch_pad_phase8(PadArgs a, hipStream_t s);
-int debug_read_patch_stamps(void* dst, size_t bytes);
 
 struct Im2colArgs {
   const int8_t* x;
@@ -173,10 +181,6 @@ bool fused_stream_supported(const FusedArgs& a);   // fused_dwpw_stream.hip: the
 void launch_fused_stream(const FusedArgs& a, int out, hipStream_t s);
 bool fused_small_supported(const FusedArgs& a);    // fused_dwpw_small.hip: the 7 x 7 planes (512 -> 1024 stride 2, 1024 -> 1024)
 void launch_fused_small(const FusedArgs& a, int out, hipStream_t s);
-void debug_set_fused(int v);                        // bit 5 (32): timeline stamps
-int debug_read_fw_stamps(void* dst, size_t bytes);
-int debug_read_fs_stamps(void* dst, size_t bytes);  // the streaming kernel's
-int debug_read_f7_stamps(void* dst, size_t bytes);  // the small-plane kernel's
 
 // fused depthwise 3x3 (int8 out) -> 1x1 conv with the conv's graph tail (fused_dwconv_i8.hip, fusion G)
 struct DwConvArgs {
@@ -218,7 +222,6 @@ int gemm_tr_enabled();
 // third-generation kernel: one wide tile per CU (gemm_wide_i8.hip); false = shape outside it, the caller falls back
 bool launch_gemm_wide(const GemmArgs& g, int out, hipStream_t s);
 int gemm_wide_ntt(const GemmArgs& g);  // n tiles per block it would use, 0 = not taken
-int debug_read_wide_stamps(void* dst, size_t bytes);
 void debug_set_wide_ntt(int v);
 void launch_wide_n4(const GemmArgs& g, int out, hipStream_t s);  // per-tile translation units (gemm_wide_n*.hip)
 void launch_wide_n7(const GemmArgs& g, int out, hipStream_t s);

@@ -18,6 +18,21 @@ def test_library_exports_every_declared_symbol(pkg):
         assert hasattr(lib, name), name
 
 
+def test_removed_and_experiment_only_knobs_are_refused(pkg):
+    """The timing experiments are gone (their keys are unknown), and a default build refuses the stamp knob too."""
+    lib = pkg.capi.load()
+    for key in (b"fused_exp", b"fused_stamps", b"GEMM_DEBUG", b"PATCH_DEBUG", b"TR_DELAY", b"PATCH_DELAY", b"STAMPS"):
+        assert lib.plhip_debug_set(key, 0) == -1, key
+    assert not hasattr(lib, "plhip_debug_read_stamps")
+
+
+def test_binding_knobs_match_the_library_table(pkg):
+    """capi.KNOBS forwards exactly the keys of the knob table in plhip_capi.hip, in its order."""
+    src = open(os.path.join(ROOT, "paddle-lite_amd", "csrc", "plhip_capi.hip")).read()
+    table = re.search(r"Knob g_knobs\[\] = \{(.*?)\n\};", src, re.S).group(1)
+    assert list(pkg.capi.KNOBS) == re.findall(r'\{"(\w+)", 0, false\}', table)
+
+
 def test_no_device_is_an_error_not_a_fallback(pkg):
     lib = pkg.capi.load()
     if lib.plhip_device_count() > 0:

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Runs the fused depthwise -> pointwise op N times (for rocprofv3 passes).  Usage: python tools/fused_run.py [--exp E] [--reps N]"""
+"""Runs the fused depthwise -> pointwise op N times (for rocprofv3 passes).  Usage: python tools/fused_run.py [--reps N]"""
 import argparse
 import ctypes as C
 import os
@@ -14,7 +14,6 @@ import __graft_entry__ as ge  # noqa: E402
 pkg = ge.import_package()
 capi = pkg.capi
 ap = argparse.ArgumentParser()
-ap.add_argument("--exp", type=int, default=0)
 ap.add_argument("--reps", type=int, default=20)
 ap.add_argument("--batch", type=int, default=128)
 ap.add_argument("--c", type=int, default=512)
@@ -40,8 +39,6 @@ with capi.Context(0) as ctx:
     ctx.check(L.plhip_pack_conv_weights(ctx.h, C.byref(dp), dwr, dwp), "pack")
     dsp = ctx.to_device(np.full(m, 1e-4, np.float32))
     dy = ctx.malloc(B * m * oh * oh)
-    if args.exp:
-        assert L.plhip_debug_set(b"fused_exp", args.exp) == 0
     for _ in range(args.reps):
         ctx.check(L.plhip_dwpw_fused_int8(ctx.h, C.byref(d), dx, dwd, dsd, None, m, dwp, dsp, None, capi.ACT_RELU, 0.0, dy, capi.OUT_I8), "fused")
     ctx.sync()

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Timeline of one fused depthwise -> pointwise launch from in-kernel s_memtime stamps (plhip_debug_set("fused_stamps", 1)).
-Usage: python tools/fused_timeline.py [--batch 128] [--c 512] [--m 512]"""
+"""Timeline of one fused depthwise -> pointwise launch from in-kernel s_memtime stamps (a `make EXPERIMENTS=1` build).
+Usage: PLHIP_STAMPS=1 python tools/fused_timeline.py [--batch 128] [--c 512] [--m 512]"""
 import argparse
 import ctypes as C
 import os
@@ -23,14 +23,11 @@ def main():
     ap.add_argument("--batch", type=int, default=128)
     ap.add_argument("--c", type=int, default=512)
     ap.add_argument("--m", type=int, default=512)
-    ap.add_argument("--exp", type=int, default=0, help="timing experiment: 1 = rounds without MFMAs, 2 = rounds without depthwise arithmetic")
     args = ap.parse_args()
     B, c, m = args.batch, args.c, args.m
     rng = np.random.default_rng(0)
     with capi.Context(0) as ctx:
         L = ctx.L
-        L.plhip_debug_set.argtypes = [C.c_char_p, C.c_int]
-        L.plhip_debug_read_fw_stamps.argtypes = [C.c_void_p, C.c_size_t]
         d = capi.conv_desc(B, c, 14, 14, c, 3, 3, (1, 1, 1, 1), (1, 1), (1, 1), c, capi.ACT_RELU, 0.0)
         dp = capi.conv_desc(B, c, 14, 14, m, 1, 1, act=capi.ACT_RELU)
         dx = ctx.to_device(rng.integers(-127, 128, (B, c, 14, 14), dtype=np.int8))
@@ -42,20 +39,11 @@ def main():
         dsp = ctx.to_device(np.full(m, 1e-4, np.float32))
         dy = ctx.malloc(B * m * 196)
         fn = lambda: ctx.check(L.plhip_dwpw_fused_int8(ctx.h, C.byref(d), dx, dwd, dsd, None, m, dwp, dsp, None, capi.ACT_RELU, 0.0, dy, capi.OUT_I8), "fused")
-        for _ in range(5):
-            fn()
-        ctx.sync()
-        assert L.plhip_debug_set(b"fused_stamps", 1) == 0
-        if args.exp:
-            assert L.plhip_debug_set(b"fused_exp", args.exp) == 0
-        for _ in range(3):
+        for _ in range(8):  # warm clocks and caches; the stamps of the last launch stay
             fn()
         ctx.sync()
         nt = min(2 * B, 1024)
-        st = np.zeros((nt, 8, 16), np.uint64)
-        assert L.plhip_debug_read_fw_stamps(st.ctypes.data_as(C.c_void_p), st.nbytes) == 0
-        L.plhip_debug_set(b"fused_stamps", 0)
-        L.plhip_debug_set(b"fused_exp", 0)
+        st = capi.read_stamps("fw", (nt, 8, 16))
     R = c // 128
     rel = st[:, :, 1:].astype(np.int64) - st[:, :, 1:2].astype(np.int64)  # cycles since the wave's entry
     rt = st[:, :, 0].astype(np.int64)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Timeline of one LDS-DMA GEMM launch from in-kernel s_memtime stamps (diagnostic build path PLHIP_GEMM_DEBUG=32).
-Usage: PLHIP_GEMM_DEBUG=32 python tools/gemm_timeline.py [layer=pw8] [--batch 128]
+"""Timeline of one LDS-DMA GEMM launch from in-kernel s_memtime stamps (a `make EXPERIMENTS=1` build).
+Usage: PLHIP_STAMPS=1 python tools/gemm_timeline.py [layer=pw8] [--batch 128]
 Prints, per phase, the median / p10 / p90 over waves, and the block start-time spread (dispatch ramp)."""
 import argparse
 import ctypes as C
@@ -31,7 +31,6 @@ def main():
     if args.conv:
         args.tr = True
     WPB = 8 if args.tr else 4
-    assert int(os.environ.get("PLHIP_GEMM_DEBUG", "0")) & 32, "run with PLHIP_GEMM_DEBUG=32 (or 33, 34 ...)"
     rng = np.random.default_rng(0)
     B = args.batch
     with capi.Context(0) as ctx:
@@ -61,12 +60,7 @@ def main():
             ctx.sync()
             hwp = (ho * ho + 15) // 16 * 16
             nblk = 1024 if args.conv else min(1024, ((cout + 255) // 256) * ((B * hwp + 127) // 128 + 7) // 8 * 8)
-            buf = np.zeros(1024 * WPB * SLOTS, np.uint64)
-            rd = L.plhip_debug_read_tr_stamps if args.tr else L.plhip_debug_read_stamps
-            rd.argtypes = [C.c_void_p, C.c_size_t]
-            rc = rd(buf.ctypes.data, buf.nbytes)
-            assert rc == 0, rc
-            st = buf.reshape(1024, WPB, SLOTS)[:nblk].astype(np.int64)
+            st = capi.read_stamps("tr" if args.tr else "gemm", (1024, WPB, SLOTS))[:nblk].astype(np.int64)
             live = st[:, :, 1] != 0
             st = st[live[:, 0]]
             print("blocks with stamps:", st.shape[0], "of", nblk)
@@ -97,19 +91,6 @@ def main():
                 for i in range(min(ks, SLOTS - 8) - 1):
                     show("K-step %d" % i, t[:, 5 + i] - t[:, 4 + i])
                 lastk = 4 + min(ks, SLOTS - 8) - 1
-            if args.tr and int(os.environ.get("PLHIP_GEMM_DEBUG", "0")) & 64:
-                show("  K-step 6: top -> vmcnt wait done", t[:, 22] - t[:, 11])
-                show("  K-step 6: barrier", t[:, 23] - t[:, 22])
-                show("  K-step 6: 10 LDS reads issued", t[:, 24] - t[:, 23])
-                show("  K-step 6: DMA pieces issued", t[:, 25] - t[:, 24])
-                show("  K-step 6: 8 MFMAs issued", t[:, 21] - t[:, 25])
-                show("  K-step 6: -> next top (lgkmcnt wait)", t[:, 12] - t[:, 21])
-            elif int(os.environ.get("PLHIP_GEMM_DEBUG", "0")) & 64:
-                show("  K-step 6: top -> vmcnt wait done", t[:, 20] - t[:, 10])
-                show("  K-step 6: barrier", t[:, 21] - t[:, 20])
-                show("  K-step 6: LDS reads issued + returned", t[:, 22] - t[:, 21])
-                show("  K-step 6: DMA issue + MFMAs + perms", t[:, 23] - t[:, 22])
-                show("  K-step 6: end -> next top", t[:, 11] - t[:, 23])
             show("last K-step -> loop end", t[:, SLOTS - 4] - t[:, lastk])
             show("whole loop", t[:, SLOTS - 4] - t[:, 4])
             if args.tr:

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Timeline of one patch-kernel launch (conv_patch_i8.hip) from in-kernel s_memtime stamps (PLHIP_PATCH_DEBUG=32).
-Usage: PLHIP_PATCH_DEBUG=32 python tools/patch_timeline.py [--n 32 --cin 64 --cout 128 --hw 56]"""
+"""Timeline of one patch-kernel launch (conv_patch_i8.hip) from in-kernel s_memtime stamps (a `make EXPERIMENTS=1` build).
+Usage: PLHIP_STAMPS=1 python tools/patch_timeline.py [--n 32 --cin 64 --cout 128 --hw 56]"""
 import argparse
 import ctypes as C
 import os
@@ -25,7 +25,6 @@ def main():
     ap.add_argument("--hw", type=int, default=56)
     ap.add_argument("--stride", type=int, default=1, help="2: the phase-plane form (6 steps of 2 / 1 tap rows per 32 channels)")
     a = ap.parse_args()
-    assert int(os.environ.get("PLHIP_PATCH_DEBUG", "0")) & 32, "run with PLHIP_PATCH_DEBUG=32"
     rng = np.random.default_rng(0)
     n, cin, cout, hw = a.n, a.cin, a.cout, a.hw
     with capi.Context(0) as ctx:
@@ -44,11 +43,7 @@ def main():
         for _ in range(20):
             ctx.check(L.plhip_conv2d_int8(ctx.h, C.byref(d), dx, dwp, ds, db, dy, capi.OUT_I8, dws, wsb), "conv")
         ctx.sync()
-        buf = np.zeros(NBLK * WPB * SLOTS, np.uint64)
-        rd = L.plhip_debug_read_patch_stamps
-        rd.argtypes = [C.c_void_p, C.c_size_t]
-        assert rd(buf.ctypes.data, buf.nbytes) == 0
-        st = buf.reshape(NBLK, WPB, SLOTS).astype(np.int64)
+        st = capi.read_stamps("patch", (NBLK, WPB, SLOTS)).astype(np.int64)
         st = st[st[:, 0, 1] != 0]
         print("%s n%d %d->%d @%d: blocks with stamps: %d" % (L.plhip_conv_impl_name(C.byref(d)).decode(), n, cin, cout, hw, st.shape[0]))
         rt0, rt1 = st[:, 0, 0], st[:, :, 31].max(axis=1)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Timeline of the streaming fused depthwise -> pointwise kernel (fused_dwpw_stream.hip) from in-kernel stamps.
-Usage: python tools/stream_timeline.py [--c 128 --m 128 --hw 56] [--stride 1] [--batch 128] [--f32]
+"""Timeline of the streaming fused depthwise -> pointwise kernel (fused_dwpw_stream.hip) from in-kernel stamps
+(a `make EXPERIMENTS=1` build).  Usage: PLHIP_STAMPS=1 python tools/stream_timeline.py [--c 128 --m 128 --hw 56] [--stride 1] [--batch 128] [--f32]
 (7 x 7 output planes: the small-plane kernel, fused_dwpw_small.hip)"""
 import argparse
 import ctypes as C
@@ -30,8 +30,6 @@ okind = capi.OUT_F32 if args.f32 else capi.OUT_I8
 rng = np.random.default_rng(0)
 with capi.Context(0) as ctx:
     L = ctx.L
-    L.plhip_debug_read_fs_stamps.argtypes = [C.c_void_p, C.c_size_t]
-    L.plhip_debug_read_f7_stamps.argtypes = [C.c_void_p, C.c_size_t]
     d = capi.conv_desc(B, c, hw, hw, c, 3, 3, (1, 1, 1, 1), (st_, st_), (1, 1), c, capi.ACT_RELU, 0.0)
     dp = capi.conv_desc(B, c, oh, oh, m, 1, 1, act=capi.ACT_RELU)
     dx = ctx.to_device(rng.integers(-127, 128, (B, c, hw, hw), dtype=np.int8))
@@ -43,20 +41,10 @@ with capi.Context(0) as ctx:
     dsp = ctx.to_device(np.full(m, 1e-4, np.float32))
     dy = ctx.malloc(B * m * oh * oh * 4)
     fn = lambda: ctx.check(L.plhip_dwpw_fused_int8(ctx.h, C.byref(d), dx, dwd, dsd, None, m, dwp, dsp, None, capi.ACT_RELU, 0.0, dy, okind), "fused")
-    for _ in range(5):
+    for _ in range(7):  # warm clocks and caches; the stamps of the last launch stay
         fn()
     ctx.sync()
-    assert L.plhip_debug_set(b"fused_stamps", 1) == 0
-    for _ in range(2):
-        fn()
-    ctx.sync()
-    if small:
-        st = np.zeros((1024, 8, 8), np.uint64)
-        assert L.plhip_debug_read_f7_stamps(st.ctypes.data_as(C.c_void_p), st.nbytes) == 0
-    else:
-        st = np.zeros((2048, 4, 8), np.uint64)
-        assert L.plhip_debug_read_fs_stamps(st.ctypes.data_as(C.c_void_p), st.nbytes) == 0
-    L.plhip_debug_set(b"fused_stamps", 0)
+    st = capi.read_stamps("f7", (1024, 8, 8)) if small else capi.read_stamps("fs", (2048, 4, 8))
 if small:
     nt = min(1024, 2 * B)
     names = ["entry", "first operands requested", "parameters staged", "produced", "behind the barrier", "multiplied"]

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Timeline of one wide-tile GEMM launch (gemm_wide_i8.hip) from in-kernel s_memtime stamps (PLHIP_GEMM_DEBUG=32).
-Usage: PLHIP_GEMM_DEBUG=32 python tools/wide_timeline.py [layer=pw8] [--batch 128]"""
+"""Timeline of one wide-tile GEMM launch (gemm_wide_i8.hip) from in-kernel s_memtime stamps (a `make EXPERIMENTS=1` build).
+Usage: PLHIP_STAMPS=1 python tools/wide_timeline.py [layer=pw8] [--batch 128]"""
 import argparse
 import ctypes as C
 import os
@@ -25,7 +25,6 @@ def main():
     ap.add_argument("layer", nargs="?", default="pw8")
     ap.add_argument("--batch", type=int, default=128)
     args = ap.parse_args()
-    assert int(os.environ.get("PLHIP_GEMM_DEBUG", "0")) & 32, "run with PLHIP_GEMM_DEBUG=32"
     rng = np.random.default_rng(0)
     B = args.batch
     with capi.Context(0) as ctx:
@@ -46,11 +45,7 @@ def main():
             for _ in range(20):  # warm clocks and caches; the stamps of the last launch stay
                 ctx.check(L.plhip_conv2d_int8(ctx.h, C.byref(d), dx, dwp, ds, db, dy, (capi.OUT_F32 if name == "pw14" else capi.OUT_I8), None, 0), "conv")
             ctx.sync()
-            buf = np.zeros(NBLK * WPB * SLOTS, np.uint64)
-            rd = L.plhip_debug_read_wide_stamps
-            rd.argtypes = [C.c_void_p, C.c_size_t]
-            assert rd(buf.ctypes.data, buf.nbytes) == 0
-            st = buf.reshape(NBLK, WPB, SLOTS).astype(np.int64)
+            st = capi.read_stamps("wide", (NBLK, WPB, SLOTS)).astype(np.int64)
             st = st[st[:, 0, 1] != 0]
             print("blocks with stamps:", st.shape[0])
             ks = cin // 32
