@@ -141,6 +141,35 @@ int plhip_conv2d_calib_supported(const plhip_conv_desc* d);
 plhip_status plhip_conv2d_calib_int8(plhip_ctx* ctx, const plhip_conv_desc* d, const float* x_f32, float calib_scale,
                                      const void* w_packed, const float* scale, const float* bias, void* y, plhip_out_kind out);
 
+/* ---- uint8 image input (ImagePreprocess::image_to_tensor on the device) ----
+ * Replaces ImagePreprocess::image_to_tensor (lite/utils/cv/paddle_image_preprocess.cc:143-172 -> Image2Tensor::choose,
+ * lite/utils/cv/image2tensor.cc), the host step that turns a decoded image into the fp32 NCHW input tensor:
+ *   y[b][c][h][w] = (float(src[((b * h + h) * w + w) * cs + c]) - means[c]) * scales[c]
+ * two fp32 roundings (a subtract, then a multiply: image2tensor.cc:481-488, 549-563).  src is the interleaved image [n, h, w, cs],
+ * cs = 4 (RGBA / BGRA, the 4th byte dropped), 3 (RGB / BGR) or 1 (GRAY); the output has 3 channels (1 for GRAY), channel c = byte c
+ * of the pixel in the image's own order (no swap), and means / scales are indexed by that byte.  The int8 form quantises every value
+ * exactly as plhip_calib_f32_to_i8 does (bit-identical to the two calls).  Any n, h, w >= 1; 16-byte aligned pointers and
+ * h * w % 16 == 0 take the vector path, anything else a scalar one.  The descriptor is passed by pointer and read at the call:
+ * the launches stay capture-safe. */
+typedef enum { PLHIP_IMG_RGBA = 0, PLHIP_IMG_BGRA = 1, PLHIP_IMG_RGB = 2, PLHIP_IMG_BGR = 3, PLHIP_IMG_GRAY = 4 } plhip_image_format; /* == cv::ImageFormat */
+typedef struct {
+  int n, h, w;
+  int format; /* plhip_image_format */
+  float means[3];
+  float scales[3];
+} plhip_image_desc;
+plhip_status plhip_image_to_tensor_f32(plhip_ctx* ctx, const plhip_image_desc* img, const uint8_t* src, float* y);
+plhip_status plhip_image_to_tensor_i8(plhip_ctx* ctx, const plhip_image_desc* img, const uint8_t* src, int8_t* y, float calib_scale);
+/* image_to_tensor + calib[fp32_to_int8](calib_scale) + conv2d 3x3 s2 in one launch: plhip_conv2d_calib_int8 with the uint8 image as
+ * its source (conv_stem_u8in.hip), bit-identical to plhip_image_to_tensor_i8 followed by plhip_conv2d_int8.  Envelope: that of
+ * plhip_conv2d_calib_supported, plus d->cin == the image's output channels and d->n, h, w == the image's.  Rows that start off a
+ * dword (w * cs % 4 != 0) cannot occur inside it: w % 4 == 0 is part of that envelope.  src 4-byte aligned, w_packed 16, y 4
+ * elements.  plhip_conv2d_image_supported: host logic only, 1 where the fused kernel takes the pair. */
+int plhip_conv2d_image_supported(const plhip_conv_desc* d, const plhip_image_desc* img);
+plhip_status plhip_conv2d_image_int8(plhip_ctx* ctx, const plhip_conv_desc* d, const plhip_image_desc* img, const uint8_t* src,
+                                     float calib_scale, const void* w_packed, const float* scale, const float* bias, void* y,
+                                     plhip_out_kind out);
+
 /* ---- depthwise conv (groups == cin == cout) ----
  * Replaces: DepthwiseConv<kInt8,*>::Run (lite/kernels/arm/conv_depthwise.cc:357-446) ->
  * conv_depthwise_3x3_int8_{fp32,int8} / conv_depthwise_5x5_int8_{fp32,int8}

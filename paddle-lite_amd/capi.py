@@ -28,7 +28,13 @@ EXPORTS = [
     "plhip_calib_f32_to_i8", "plhip_calib_i8_to_f32", "plhip_global_avg_pool_f32", "plhip_softmax_f32",
     "plhip_pool2d_f32", "plhip_pool2d_max_i8", "plhip_elementwise_add_f32", "plhip_selftest",
     "plhip_debug_set", "plhip_conv2d_calib_supported", "plhip_conv2d_calib_int8",
+    "plhip_image_to_tensor_f32", "plhip_image_to_tensor_i8", "plhip_conv2d_image_supported", "plhip_conv2d_image_int8",
 ]
+
+# plhip_image_format == cv::ImageFormat (lite/utils/cv/paddle_image_preprocess.h)
+IMG_RGBA, IMG_BGRA, IMG_RGB, IMG_BGR, IMG_GRAY = 0, 1, 2, 3, 4
+IMG_BYTES = {IMG_RGBA: 4, IMG_BGRA: 4, IMG_RGB: 3, IMG_BGR: 3, IMG_GRAY: 1}      # bytes a pixel of the interleaved image has
+IMG_CHANNELS = {IMG_RGBA: 3, IMG_BGRA: 3, IMG_RGB: 3, IMG_BGR: 3, IMG_GRAY: 1}   # channels of the NCHW tensor made from it
 
 
 class ConvDesc(C.Structure):
@@ -42,6 +48,21 @@ class PoolDesc(C.Structure):
     _fields_ = [("planes", C.c_int), ("h", C.c_int), ("w", C.c_int), ("oh", C.c_int), ("ow", C.c_int),
                 ("kh", C.c_int), ("kw", C.c_int), ("pad", C.c_int * 4), ("stride", C.c_int * 2),
                 ("is_max", C.c_int), ("exclusive", C.c_int)]
+
+
+class ImageDesc(C.Structure):
+    _fields_ = [("n", C.c_int), ("h", C.c_int), ("w", C.c_int), ("format", C.c_int),
+                ("means", C.c_float * 3), ("scales", C.c_float * 3)]
+
+
+def image_desc(n, h, w, fmt, means, scales):
+    """plhip_image_desc; means / scales: one value per source byte of a pixel (the first only for GRAY)."""
+    d = ImageDesc()
+    d.n, d.h, d.w, d.format = n, h, w, fmt
+    m, s = list(means) + [0.0] * (3 - len(means)), list(scales) + [0.0] * (3 - len(scales))
+    d.means[:] = [float(v) for v in m[:3]]
+    d.scales[:] = [float(v) for v in s[:3]]
+    return d
 
 
 def conv_desc(n, cin, h, w, cout, kh, kw, pad=(0, 0, 0, 0), stride=(1, 1), dil=(1, 1), groups=1,
@@ -128,6 +149,11 @@ def load():
     L.plhip_conv2d_int8_fused.argtypes = [vp, C.POINTER(ConvDesc), vp, vp, vp, vp, vp, vp, i32, vp, f32, vp, sz]
     L.plhip_conv2d_calib_supported.argtypes = [C.POINTER(ConvDesc)]
     L.plhip_conv2d_calib_int8.argtypes = [vp, C.POINTER(ConvDesc), vp, f32, vp, vp, vp, vp, i32]
+    L.plhip_image_to_tensor_f32.argtypes = [vp, C.POINTER(ImageDesc), vp, vp]
+    L.plhip_image_to_tensor_i8.argtypes = [vp, C.POINTER(ImageDesc), vp, vp, f32]
+    L.plhip_conv2d_image_supported.argtypes = [C.POINTER(ConvDesc), C.POINTER(ImageDesc)]
+    L.plhip_conv2d_image_supported.restype = i32
+    L.plhip_conv2d_image_int8.argtypes = [vp, C.POINTER(ConvDesc), C.POINTER(ImageDesc), vp, f32, vp, vp, vp, vp, i32]
     L.plhip_conv_impl_name.argtypes = [C.POINTER(ConvDesc)]
     L.plhip_conv_impl_name.restype = C.c_char_p
     L.plhip_depthwise_conv_int8.argtypes = [vp, C.POINTER(ConvDesc), vp, vp, vp, vp, vp, i32]
@@ -268,6 +294,40 @@ class Context:
         dwp = self.malloc(self.L.plhip_conv_packed_weight_bytes(C.byref(d)))
         self.check(self.L.plhip_pack_conv_weights(self.h, C.byref(d), dw, dwp), "pack")
         self.check(self.L.plhip_conv2d_calib_int8(self.h, C.byref(d), dx, calib_scale, dwp, ds, db, dy, out_kind), "conv2d_calib")
+        y = self.to_host(dy, (d.n, d.cout, oh, ow), _OUT_DTYPE[out_kind])
+        for p in [dx, dw, dy, dwp] + ([ds] if scale is not None else []) + ([db] if bias is not None else []):
+            self.free(p)
+        return y
+
+    def image_to_tensor(self, img, src_u8, calib_scale=None):
+        """plhip_image_to_tensor_f32 (calib_scale None) or _i8 on a host uint8 image [n, h, w, cs]: the NCHW tensor."""
+        src = np.ascontiguousarray(src_u8, np.uint8)
+        shape = (img.n, IMG_CHANNELS[img.format], img.h, img.w)
+        cnt = int(np.prod(shape))
+        dx = self.to_device(src)
+        if calib_scale is None:
+            dy = self.malloc(cnt * 4)
+            self.check(self.L.plhip_image_to_tensor_f32(self.h, C.byref(img), dx, dy), "image_to_tensor_f32")
+            y = self.to_host(dy, shape, np.float32)
+        else:
+            dy = self.malloc(cnt)
+            self.check(self.L.plhip_image_to_tensor_i8(self.h, C.byref(img), dx, dy, float(calib_scale)), "image_to_tensor_i8")
+            y = self.to_host(dy, shape, np.int8)
+        self.free(dx), self.free(dy)
+        return y
+
+    def conv2d_image(self, d, img, src_u8, calib_scale, w, scale, bias, out_kind):
+        """plhip_conv2d_image_int8 on host arrays: image_to_tensor + calib[fp32_to_int8](calib_scale) + conv2d in one launch."""
+        oh, ow = out_hw(d)
+        dx = self.to_device(np.ascontiguousarray(src_u8, np.uint8))
+        dw = self.to_device(np.ascontiguousarray(w, np.int8))
+        ds = self.to_device(np.ascontiguousarray(scale, np.float32)) if scale is not None else C.c_void_p()
+        db = self.to_device(np.ascontiguousarray(bias, np.float32)) if bias is not None else C.c_void_p()
+        dy = self.malloc(d.n * d.cout * oh * ow * (1 if out_kind == OUT_I8 else 4))
+        dwp = self.malloc(self.L.plhip_conv_packed_weight_bytes(C.byref(d)))
+        self.check(self.L.plhip_pack_conv_weights(self.h, C.byref(d), dw, dwp), "pack")
+        self.check(self.L.plhip_conv2d_image_int8(self.h, C.byref(d), C.byref(img), dx, float(calib_scale), dwp, ds, db, dy, out_kind),
+                   "conv2d_image")
         y = self.to_host(dy, (d.n, d.cout, oh, ow), _OUT_DTYPE[out_kind])
         for p in [dx, dw, dy, dwp] + ([ds] if scale is not None else []) + ([db] if bias is not None else []):
             self.free(p)

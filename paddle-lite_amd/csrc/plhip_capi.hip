@@ -645,6 +645,74 @@ plhip_status plhip_conv2d_calib_int8(plhip_ctx* ctx, const plhip_conv_desc* d, c
   return PLHIP_OK;
 }
 
+// ------------------------------------------------------------------ uint8 image input
+// ImagePreprocess::image_to_tensor (paddle_image_preprocess.cc:143-172 -> Image2Tensor::choose, image2tensor.cc:85-128): which
+// formats exist and how many bytes a pixel has / how many channels come out
+static bool image_args(const plhip_image_desc* img, const uint8_t* src, plhip::ImageArgs* a) {
+  if (!img || img->n < 1 || img->h < 1 || img->w < 1 || img->format < PLHIP_IMG_RGBA || img->format > PLHIP_IMG_GRAY) return false;
+  a->src = src;
+  a->n = img->n; a->h = img->h; a->w = img->w;
+  a->cs = img->format == PLHIP_IMG_GRAY ? 1 : (img->format == PLHIP_IMG_RGB || img->format == PLHIP_IMG_BGR) ? 3 : 4;
+  a->c = img->format == PLHIP_IMG_GRAY ? 1 : 3;
+  for (int i = 0; i < 3; ++i) {
+    a->mean[i] = img->means[i];
+    a->scale[i] = img->scales[i];
+  }
+  return true;
+}
+
+plhip_status plhip_image_to_tensor_f32(plhip_ctx* ctx, const plhip_image_desc* img, const uint8_t* src, float* y) {
+  plhip::ImageArgs a;
+  if (!ctx || !src || !y) return fail(ctx, PLHIP_ERR_INVALID, "plhip_image_to_tensor_f32: null argument");
+  if (!image_args(img, src, &a)) return fail(ctx, PLHIP_ERR_INVALID, "plhip_image_to_tensor_f32: bad image descriptor");
+  plhip::launch_image_to_tensor_f32(a, y, ctx->stream);
+  LAUNCHCHK(ctx, "image_to_tensor_f32");
+  return PLHIP_OK;
+}
+
+plhip_status plhip_image_to_tensor_i8(plhip_ctx* ctx, const plhip_image_desc* img, const uint8_t* src, int8_t* y, float calib_scale) {
+  plhip::ImageArgs a;
+  if (!ctx || !src || !y || !(calib_scale > 0.f)) return fail(ctx, PLHIP_ERR_INVALID, "plhip_image_to_tensor_i8: null / bad argument");
+  if (!image_args(img, src, &a)) return fail(ctx, PLHIP_ERR_INVALID, "plhip_image_to_tensor_i8: bad image descriptor");
+  plhip::launch_image_to_tensor_i8(a, y, calib_scale, ctx->stream);
+  LAUNCHCHK(ctx, "image_to_tensor_i8");
+  return PLHIP_OK;
+}
+
+int plhip_conv2d_image_supported(const plhip_conv_desc* d, const plhip_image_desc* img) {
+  plhip::DirectS2Args a;
+  plhip::ImageArgs im;
+  return calib_conv_args(d, &a) && image_args(img, nullptr, &im) && plhip::conv3x3s2_u8in_supported(a, im) ? 1 : 0;
+}
+
+plhip_status plhip_conv2d_image_int8(plhip_ctx* ctx, const plhip_conv_desc* d, const plhip_image_desc* img, const uint8_t* src,
+                                     float calib_scale, const void* w_packed, const float* scale, const float* bias, void* y,
+                                     plhip_out_kind out) {
+  if (!ctx || !src || !w_packed || !y || !(calib_scale > 0.f)) return fail(ctx, PLHIP_ERR_INVALID, "plhip_conv2d_image_int8: null / bad argument");
+  if (out != PLHIP_OUT_I32_ACC && out != PLHIP_OUT_F32 && out != PLHIP_OUT_I8)
+    return fail(ctx, PLHIP_ERR_INVALID, "plhip_conv2d_image_int8: bad out kind");
+  if (out != PLHIP_OUT_I32_ACC && !scale) return fail(ctx, PLHIP_ERR_INVALID, "plhip_conv2d_image_int8: scale required");
+  if (d && d->act != PLHIP_ACT_NONE && d->act != PLHIP_ACT_RELU && d->act != PLHIP_ACT_RELU6 && d->act != PLHIP_ACT_LEAKY_RELU)
+    return fail(ctx, PLHIP_ERR_UNSUPPORTED, "plhip_conv2d_image_int8: unsupported activation");
+  plhip::DirectS2Args a;
+  plhip::ImageArgs im;
+  if (!image_args(img, src, &im)) return fail(ctx, PLHIP_ERR_INVALID, "plhip_conv2d_image_int8: bad image descriptor");
+  if (!calib_conv_args(d, &a) || !plhip::conv3x3s2_u8in_supported(a, im))
+    return fail(ctx, PLHIP_ERR_UNSUPPORTED, "plhip_conv2d_image_int8: shape outside the fused stem");
+  const size_t esz = out == PLHIP_OUT_I8 ? 1 : 4;
+  if (!aligned(src, 4) || !aligned(y, 4 * esz) || !aligned(w_packed, 16))
+    return fail(ctx, PLHIP_ERR_INVALID, "plhip_conv2d_image_int8: src must be 4-byte aligned, w_packed 16, y 4 elements");
+  a.x_inv_scale = 1.f / calib_scale;  // type_trans.cc:45
+  a.wp = (const uint32_t*)w_packed;
+  a.y = y;
+  a.scale = scale;
+  a.bias = bias;
+  const int8_t* afrag = reinterpret_cast<const int8_t*>(w_packed) + plhip::conv3x3s2_dot4_bytes(d->cin, d->cout);
+  plhip::launch_conv3x3s2_u8in(a, im, afrag, (int)out, ctx->stream);
+  LAUNCHCHK(ctx, "conv3x3s2_u8in");
+  return PLHIP_OK;
+}
+
 // ------------------------------------------------------------------ depthwise
 plhip_status plhip_depthwise_conv_int8(plhip_ctx* ctx, const plhip_conv_desc* d, const int8_t* x, const int8_t* w_oihw,
                                        const float* scale, const float* bias, void* y, plhip_out_kind out) {

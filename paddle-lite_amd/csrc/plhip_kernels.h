@@ -263,6 +263,18 @@ size_t conv3x3s2_dot4_bytes(int cin, int cout);              // offset of the MF
 bool conv3x3s2_f32in_supported(const DirectS2Args& a);      // conv_stem_f32in.hip: calib[fp32_to_int8] + this conv in one launch
 void launch_conv3x3s2_f32in(const DirectS2Args& a, const int8_t* afrag, int out, hipStream_t s);
 
+// uint8 interleaved image [n, h, w, cs] (cs 1 / 3 / 4) -> c = (cs == 1 ? 1 : 3) normalised channels (image_to_tensor.hip)
+struct ImageArgs {
+  const uint8_t* src;
+  int n, h, w, cs, c;
+  float mean[3], scale[3];  // indexed by the source byte of the pixel (image2tensor.cc:279-284)
+};
+void launch_image_to_tensor_f32(const ImageArgs& a, float* y, hipStream_t s);
+void launch_image_to_tensor_i8(const ImageArgs& a, int8_t* y, float calib_scale, hipStream_t s);
+// conv_stem_u8in.hip: image_to_tensor + calib[fp32_to_int8] + the 3x3 stride-2 stem in one launch; a.x_inv_scale = 1 / calib scale
+bool conv3x3s2_u8in_supported(const DirectS2Args& a, const ImageArgs& im);
+void launch_conv3x3s2_u8in(const DirectS2Args& a, const ImageArgs& im, const int8_t* afrag, int out, hipStream_t s);
+
 size_t fc_packed_bytes(int k, int n);
 void launch_pack_fc(const int8_t* w_kn, int8_t* wp, int k, int n, hipStream_t s);
 void launch_fc(const int8_t* x, const int8_t* wp, const float* scale, const float* bias, void* y, int m, int k, int n,

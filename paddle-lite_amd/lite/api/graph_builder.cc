@@ -4,6 +4,7 @@
 #include <string.h>
 
 #include "lite/core/mir/fusion/hip_conv_tail_matcher.h"
+#include "lite/kernels/hip/image_to_tensor.h"
 #include "plhip.h"
 
 #include <cstdio>
@@ -14,6 +15,22 @@ namespace lite {
 
 void GraphBuilder::Feed(const std::string& name, const std::vector<int64_t>& dims, PrecisionType prec) {
   feeds_.push_back({name, dims, prec});
+}
+
+void GraphBuilder::FeedImage(const std::string& name, int n, int h, int w, int format, const float* means, const float* scales) {
+  CHECK(format >= PLHIP_IMG_RGBA && format <= PLHIP_IMG_GRAY) << "FeedImage: unsupported image format " << format;
+  CHECK(n > 0 && h > 0 && w > 0) << "FeedImage: bad image size";
+  FeedDesc f;
+  f.name = name;
+  f.dims = {n, operators::ImageChannels(format), h, w};
+  f.prec = PRECISION(kFloat);
+  f.image_format = format;
+  f.image_dims = {n, h, w, operators::ImagePixelBytes(format)};
+  for (int i = 0; i < 3; ++i) {
+    f.means[i] = means[i];
+    f.scales[i] = scales[i];
+  }
+  feeds_.push_back(f);
 }
 
 GraphOp& GraphBuilder::Add(const std::string& type, const std::vector<std::string>& inputs, const std::string& output) {
@@ -60,17 +77,26 @@ std::vector<GraphBuilder::Step> GraphBuilder::Schedule() {
   std::map<std::string, PrecisionType> prec;   // precision of every device variable
   std::map<std::string, std::string> cast_of;  // type_precision_cast_pass's cast_nodes
   std::vector<Step> steps;
-  for (auto& f : feeds_) {
+  for (size_t k = 0; k < feeds_.size(); ++k) {
+    const FeedDesc& f = feeds_[k];
     Step s;
     s.kind = "io_copy_h2d";
     s.in = f.name;
     s.out = f.name + "/target_trans";
     steps.push_back(s);
     prec[f.name] = f.prec;
+    if (f.image_format >= 0) {  // FeedImage: the bytes on the device become the fp32 NCHW tensor the ops name
+      Step t;
+      t.kind = "image_to_tensor";
+      t.in = s.out;
+      t.out = f.name + "/tensor";
+      t.image_feed = static_cast<int>(k);
+      steps.push_back(t);
+    }
   }
   auto dev_name = [&](const std::string& v) {
     for (auto& f : feeds_)
-      if (f.name == v) return v + "/target_trans";
+      if (f.name == v) return v + (f.image_format >= 0 ? "/tensor" : "/target_trans");
     return v;
   };
   for (size_t i = 0; i < ops_.size(); ++i) {
@@ -175,6 +201,63 @@ void GraphBuilder::FuseSteps(std::vector<Step>* steps_io) {
       st[i].drop_f32 = t.drop_f32;
       st[i].pool_int8 = t.pool_int8;
     }
+  }
+  // (H) an image feed's image_to_tensor whose only reader is a calib[fp32_to_int8]: (H1) where that calib's only reader is a conv2d
+  // plhip_conv2d_image_supported takes (the 3x3 stride-2 stem), the conv takes both over and reads the uint8 image itself (the fp32
+  // and the int8 image are never written); (H2) otherwise the calib folds into image_to_tensor (its int8 form).  Before F, which
+  // would otherwise take the calib alone.
+  for (size_t i = 0; i < st.size(); ++i) {
+    if (dead[i] || st[i].kind != "image_to_tensor" || uses(st[i].out) != 1) continue;
+    int k = -1;
+    for (size_t t = 0; t < st.size(); ++t)
+      if (!dead[t] && st[t].kind == "calib_f2i" && st[t].in == st[i].out) k = static_cast<int>(t);
+    if (k < 0) continue;
+    const FeedDesc& f = feeds_[st[i].image_feed];
+    if (uses(st[k].out) == 1) {
+      int j = -1;
+      for (size_t t = 0; t < st.size(); ++t)
+        if (!dead[t] && st[t].kind == "op" && !st[t].op_inputs.empty() && st[t].op_inputs[0] == st[k].out) j = static_cast<int>(t);
+      bool take = j >= 0;
+      if (take) {
+        const GraphOp& c = ops_[st[j].op];
+        const std::vector<int> cpd = pad4(c.conv.paddings);
+        take = c.type == "conv2d" && c.enable_int8 && c.w_dims.size() == 4 && cpd.size() == 4 && c.conv.strides.size() == 2 &&
+               c.conv.dilations.size() == 2 && c.conv.padding_algorithm.empty() && st[j].res.empty() && st[j].calib_out.empty() &&
+               st[j].pw_op < 0;
+        if (take) {
+          plhip_conv_desc d;
+          memset(&d, 0, sizeof(d));
+          d.n = static_cast<int>(f.dims[0]); d.cin = static_cast<int>(f.dims[1]);
+          d.h = static_cast<int>(f.dims[2]); d.w = static_cast<int>(f.dims[3]);
+          d.cout = static_cast<int>(c.w_dims[0]); d.kh = static_cast<int>(c.w_dims[2]); d.kw = static_cast<int>(c.w_dims[3]);
+          for (int q = 0; q < 4; ++q) d.pad[q] = cpd[q];
+          d.stride[0] = c.conv.strides[0]; d.stride[1] = c.conv.strides[1];
+          d.dil[0] = c.conv.dilations[0]; d.dil[1] = c.conv.dilations[1];
+          d.groups = c.conv.groups;
+          plhip_image_desc img;
+          memset(&img, 0, sizeof(img));
+          img.n = d.n; img.h = d.h; img.w = d.w;
+          img.format = f.image_format;
+          for (int q = 0; q < 3; ++q) {
+            img.means[q] = f.means[q];
+            img.scales[q] = f.scales[q];
+          }
+          take = plhip_conv2d_image_supported(&d, &img) != 0;
+        }
+      }
+      if (take) {  // (H1)
+        st[j].in_calib_scale = st[k].scale;
+        st[j].via_in = st[k].out;
+        st[j].op_inputs[0] = st[i].in;
+        st[j].image_feed = st[i].image_feed;
+        dead[i] = dead[k] = true;
+        continue;
+      }
+    }
+    st[i].out = st[k].out;  // (H2)
+    st[i].scale = st[k].scale;
+    st[i].image_int8 = true;
+    dead[k] = true;
   }
   // (D) depthwise_conv2d[int8_out] whose only consumer is a plain 1x1 conv (no tail of its own) takes it over.  Mode 2 (default):
   // only where the fused kernel takes the pair, which needs the depthwise conv's input shape: propagated from the feeds through
@@ -390,7 +473,11 @@ std::vector<std::string> GraphBuilder::Plan() {
         snprintf(buf, sizeof buf, " oscale=%.9g", s.out_scale);
         l += buf;
       }
-      if (s.in_calib_scale > 0.f) {
+      if (s.image_feed >= 0) {  // (H1): image_to_tensor + calib taken over, the conv reads the uint8 image
+        const FeedDesc& f = feeds_[s.image_feed];
+        snprintf(buf, sizeof buf, " in_scale=%.9g", s.in_calib_scale);
+        l += " +image_in=" + f.name + " fmt=" + operators::ImageFormatName(f.image_format) + buf;
+      } else if (s.in_calib_scale > 0.f) {
         snprintf(buf, sizeof buf, " in_scale=%.9g", s.in_calib_scale);
         l += " +calib_in=" + s.via_in + buf;
       }
@@ -416,6 +503,13 @@ std::vector<std::string> GraphBuilder::Plan() {
         }
         if (s.pw_pool) l += " +pool=avg/global pw_out=" + s.via_pw;
       }
+    } else if (s.kind == "image_to_tensor") {
+      l = std::string("image_to_tensor/") + (s.image_int8 ? "int8" : "fp32") + " in=" + s.in + " out=" + s.out + " fmt=" +
+          operators::ImageFormatName(feeds_[s.image_feed].image_format);
+      if (s.image_int8) {
+        snprintf(buf, sizeof buf, " scale=%.9g", s.scale);
+        l += buf;
+      }
     } else {
       l = s.kind == "io_copy_h2d" ? "io_copy/host_to_device"
           : s.kind == "io_copy_d2h" ? "io_copy/device_to_host"
@@ -432,7 +526,10 @@ std::vector<std::string> GraphBuilder::Plan() {
 }
 
 std::vector<std::string> GraphBuilder::Lower(HipPredictor* pred) {
-  for (auto& f : feeds_) pred->AddFeed(f.name, f.dims, f.prec);
+  for (auto& f : feeds_) {
+    if (f.image_format >= 0) pred->AddFeed(f.name, f.image_dims, PRECISION(kUInt8));
+    else pred->AddFeed(f.name, f.dims, f.prec);
+  }
   std::vector<std::string> outs;
   auto steps = Schedule();
   if (fuse_) FuseSteps(&steps);
@@ -444,6 +541,9 @@ std::vector<std::string> GraphBuilder::Lower(HipPredictor* pred) {
       outs.push_back(s.out);
     } else if (s.kind == "calib_f2i" || s.kind == "calib_i2f") {
       pred->AddCalib(s.in, s.out, s.scale, s.kind == "calib_f2i");
+    } else if (s.kind == "image_to_tensor") {
+      const FeedDesc& f = feeds_[s.image_feed];
+      pred->AddImageToTensor(s.in, s.out, f.image_format, f.means, f.scales, s.image_int8 ? s.scale : 0.f);
     } else {
       GraphOp& op = ops_[s.op];
       if (op.type == "conv2d" || op.type == "depthwise_conv2d") {
@@ -457,6 +557,15 @@ std::vector<std::string> GraphBuilder::Lower(HipPredictor* pred) {
         a.calib_scale = s.calib_scale;
         a.drop_fp32 = s.drop_f32;
         a.in_calib_scale = s.in_calib_scale;
+        if (s.image_feed >= 0) {  // (H1)
+          const FeedDesc& f = feeds_[s.image_feed];
+          a.image_format = f.image_format;
+          for (int q = 0; q < 3; ++q) {
+            a.image_means[q] = f.means[q];
+            a.image_scales[q] = f.scales[q];
+          }
+          a.image_x = s.via_in;
+        }
         if (s.pw_op >= 0) {
           const GraphOp& c = ops_[s.pw_op];
           a.pw_w = c.w.data();

@@ -47,6 +47,14 @@ struct GraphOp {
 class GraphBuilder {
  public:
   void Feed(const std::string& name, const std::vector<int64_t>& dims, PrecisionType prec);
+  // A feed the caller fills with a decoded uint8 image [n, h, w, cs] (format: plhip_image_format == cv::ImageFormat; means / scales
+  // indexed by the source byte of a pixel) instead of the normalised tensor: ImagePreprocess::image_to_tensor
+  // (lite/utils/cv/paddle_image_preprocess.h:217-244) moves onto the device.  The ops name `name` as the fp32 NCHW tensor
+  // [n, c, h, w] (c = 1 for GRAY, else 3); lowering emits io_copy of the bytes, then image_to_tensor ("<name>/tensor").  With
+  // set_fuse(true): (H1) image_to_tensor -> its only reader calib[fp32_to_int8] -> a 3x3 stride-2 stem plhip_conv2d_image_supported
+  // takes  => ONE conv instruction reading the image (plhip_conv2d_image_int8); (H2) otherwise image_to_tensor and its only-reader
+  // calib => one image_to_tensor/int8 instruction.
+  void FeedImage(const std::string& name, int n, int h, int w, int format, const float* means, const float* scales);
   void Fetch(const std::string& name) { fetches_.push_back(name); }
   // Graph-level fusions of the kHIP target on top of the reference's program (default on; results are bit-identical to
   // the unfused program, every fused value is rounded as the separate instructions round it):
@@ -75,7 +83,7 @@ class GraphBuilder {
  private:
   struct Step {
     int op{-1};              // index into ops_, or -1 for an inserted instruction
-    std::string kind;        // "op", "io_copy_h2d", "io_copy_d2h", "calib_f2i", "calib_i2f"
+    std::string kind;        // "op", "io_copy_h2d", "io_copy_d2h", "calib_f2i", "calib_i2f", "image_to_tensor"
     std::string in, out;
     float scale{0.f};
     bool int8_out{false};
@@ -97,6 +105,8 @@ class GraphBuilder {
     bool pw_tail{false};      // fusion G: pw_op is the 1x1 consumer with its tail (res / calib_out / drop_f32 are then its own)
     float in_calib_scale{0.f};  // conv that took the calib[fp32_to_int8] in front of it over (F): its input is the calib's fp32 input
     std::string via_in;       // name the calib's int8 result would have had
+    int image_feed{-1};       // image_to_tensor of feeds_[image_feed]; on a conv: it took that image_to_tensor over too (H1)
+    bool image_int8{false};   // image_to_tensor that took the calib behind it over (H2): int8 output, `scale` the calib's
   };
   std::vector<Step> Schedule();
   void FuseSteps(std::vector<Step>* steps);
@@ -104,6 +114,9 @@ class GraphBuilder {
     std::string name;
     std::vector<int64_t> dims;
     PrecisionType prec;
+    int image_format{-1};              // FeedImage: the host variable is the uint8 image, `dims` the NCHW tensor made from it
+    std::vector<int64_t> image_dims;   // [n, h, w, cs]
+    float means[3]{0.f, 0.f, 0.f}, scales[3]{1.f, 1.f, 1.f};
   };
   bool fuse_{true};
   int fuse_dwpw_{2};

@@ -2,6 +2,7 @@
 #include "lite/api/hip_predictor.h"
 
 #include "lite/kernels/hip/conv_fusion.h"
+#include "lite/kernels/hip/image_to_tensor.h"
 #include "plhip.h"
 
 #include <cstring>
@@ -52,7 +53,7 @@ void HipPredictor::Emit(std::shared_ptr<OpLite> op, std::unique_ptr<KernelBase> 
 Tensor* HipPredictor::AddFeed(const std::string& name, const std::vector<int64_t>& dims, PrecisionType prec) {
   Tensor* t = Var(name);
   t->Resize(dims);
-  const size_t esz = prec == PRECISION(kInt8) ? 1 : 4;
+  const size_t esz = prec == PRECISION(kInt8) || prec == PRECISION(kUInt8) ? 1 : 4;
   t->mutable_data(TARGET(kHost), static_cast<size_t>(t->numel()) * esz);
   t->set_precision(prec);
   return t;
@@ -74,6 +75,22 @@ void HipPredictor::AddCalib(const std::string& in, const std::string& out, float
   Emit(op, PickKernel("calib", Place(TARGET(kHIP), PRECISION(kInt8)), f2i ? "fp32_to_int8" : "int8_to_fp32"));
 }
 
+void HipPredictor::AddImageToTensor(const std::string& in, const std::string& out, int format, const float* means,
+                                    const float* scales, float calib_scale) {
+  auto op = std::make_shared<operators::ImageToTensorOp>();
+  auto& p = op->mutable_param();
+  p.x = Var(in);
+  p.output = Var(out);
+  p.format = format;
+  for (int i = 0; i < 3; ++i) {
+    p.means[i] = means[i];
+    p.scales[i] = scales[i];
+  }
+  p.int8_out = calib_scale > 0.f;
+  p.calib_scale = p.int8_out ? calib_scale : 1.f;
+  Emit(op, PickKernel("image_to_tensor", Place(TARGET(kHIP), PRECISION(kAny)), p.int8_out ? "int8" : "fp32"));
+}
+
 void HipPredictor::AddConv(const std::string& op_type, const std::string& in, const std::string& out, const int8_t* w,
                            const std::vector<int64_t>& w_dims, const float* bias, const ConvAttrs& a) {
   auto op = std::make_shared<operators::ConvOpLite>(op_type);
@@ -82,7 +99,7 @@ void HipPredictor::AddConv(const std::string& op_type, const std::string& in, co
   const bool fused = !a.calib_out.empty() || !a.residual.empty() || a.pw_w != nullptr || a.in_calib_scale > 0.f;
   size_t wn = 1;
   for (auto d : w_dims) wn *= static_cast<size_t>(d);
-  p.x = Var(in);
+  p.x = a.image_format >= 0 ? Var(a.image_x) : Var(in);
   p.output = Var(out);
   p.filter = NewParam(w, wn, w_dims, PRECISION(kInt8));
   p.bias = bias ? NewParam(bias, static_cast<size_t>(w_dims[0]) * 4, {w_dims[0]}, PRECISION(kFloat)) : nullptr;
@@ -139,6 +156,17 @@ void HipPredictor::AddConv(const std::string& op_type, const std::string& in, co
     }
   }
   if (a.in_calib_scale > 0.f) fz.calib_input_scale = a.in_calib_scale;
+  if (a.image_format >= 0) {  // fusion H1: the conv reads the uint8 image `in`; `x` only carries the NCHW shape made from it
+    CHECK(a.in_calib_scale > 0.f) << "an image source needs the calib scale of the int8 stem";
+    const Tensor* img = Var(in);
+    fz.image_input = img;
+    fz.image_format = a.image_format;
+    for (int i = 0; i < 3; ++i) {
+      fz.image_means[i] = a.image_means[i];
+      fz.image_scales[i] = a.image_scales[i];
+    }
+    op->set_image_input(img, operators::ImageChannels(a.image_format));
+  }
   op->set_padding_algorithm(a.padding_algorithm);
   auto kernel = PickKernel(op_type, Place(TARGET(kHIP), PRECISION(kInt8)), a.int8_out ? "int8_out" : "fp32_out");
   if (fused) {  // this target's fusion state goes to the kernel object, not into the reference's ConvParam (conv_fusion.h)

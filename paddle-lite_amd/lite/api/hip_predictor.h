@@ -47,6 +47,11 @@ struct ConvAttrs {
   bool pw_pool{false};  // ... and the global average pool2d behind it: `out` is the pool's output, [n, cout, 1, 1] fp32
   bool pw_tail{false};  // fusion G: residual / calib_out / drop_fp32 above are the 1x1 conv's tail (its fp32 output)
   float in_calib_scale{0.f};  // kHIP: the calib[fp32_to_int8] in front taken over: `in` of AddConv is the calib's fp32 input (0 = none)
+  // ... and the image_to_tensor in front of it (fusion H1): `in` of AddConv is then the uint8 image on the device, image_x the name
+  // of the (never allocated) NCHW variable that carries its shape; format < 0 = none
+  int image_format{-1};
+  float image_means[3]{0.f, 0.f, 0.f}, image_scales[3]{1.f, 1.f, 1.f};
+  std::string image_x;
 };
 
 class HipPredictor {
@@ -59,6 +64,10 @@ class HipPredictor {
   Tensor* AddFeed(const std::string& name, const std::vector<int64_t>& dims, PrecisionType prec);
   void AddIoCopy(const std::string& in, const std::string& out, bool host_to_device);
   void AddCalib(const std::string& in, const std::string& out, float scale, bool fp32_to_int8);
+  // image_to_tensor (lite/kernels/hip/image_to_tensor.h): uint8 image [n, h, w, cs] on the device -> fp32 NCHW, or int8 with the
+  // calib[fp32_to_int8](calib_scale) behind it folded in (calib_scale > 0)
+  void AddImageToTensor(const std::string& in, const std::string& out, int format, const float* means, const float* scales,
+                        float calib_scale);
   void AddConv(const std::string& op_type, const std::string& in, const std::string& out, const int8_t* w,
                const std::vector<int64_t>& w_dims, const float* bias, const ConvAttrs& attrs);
   void AddFc(const std::string& in, const std::string& out, const int8_t* w, int k, int n, const float* bias,

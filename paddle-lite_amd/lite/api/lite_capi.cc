@@ -135,6 +135,13 @@ int pllite_graph_feed(pllite_predictor* p, const char* name, const int64_t* dims
     p->graph.Feed(name, std::vector<int64_t>(dims, dims + ndims), static_cast<paddle::lite::PrecisionType>(precision));
   });
 }
+int pllite_graph_feed_image(pllite_predictor* p, const char* name, int n, int h, int w, int format, const float* means,
+                            const float* scales) {
+  return guarded([&] {
+    CHECK(means && scales) << "pllite_graph_feed_image: means / scales required";
+    p->graph.FeedImage(name, n, h, w, format, means, scales);
+  });
+}
 int pllite_graph_conv(pllite_predictor* p, const char* op_type, const char* in, const char* out, const int8_t* w,
                       const int64_t* w_dims, const float* bias, const int* strides, const int* paddings, int n_paddings,
                       const int* dilations, int groups, int act, float act_coef, float input_scale,

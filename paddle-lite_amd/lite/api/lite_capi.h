@@ -42,6 +42,11 @@ int pllite_add_elementwise_add(pllite_predictor* p, const char* x, const char* y
  * (int8_out / fp32_out), io_copy and calib placement are decided by pllite_graph_lower() with the reference's rules.
  * One graph per predictor; ops in topological order. ---- */
 int pllite_graph_feed(pllite_predictor* p, const char* name, const int64_t* dims, int ndims, int precision);
+/* A feed that takes a decoded uint8 image [n, h, w, cs] instead of the normalised tensor (GraphBuilder::FeedImage): format ==
+ * cv::ImageFormat (plhip_image_format), means / scales 3 floats each, indexed by the source byte of a pixel.  The ops name `name`
+ * as the fp32 NCHW tensor; pllite_set_input(name, bytes) takes the image's n * h * w * cs bytes. */
+int pllite_graph_feed_image(pllite_predictor* p, const char* name, int n, int h, int w, int format, const float* means,
+                            const float* scales);
 int pllite_graph_conv(pllite_predictor* p, const char* op_type, const char* in, const char* out, const int8_t* w,
                       const int64_t* w_dims, const float* bias, const int* strides, const int* paddings, int n_paddings,
                       const int* dilations, int groups, int act, float act_coef, float input_scale,

@@ -62,8 +62,14 @@ class ConvOpLite : public OpLite {
   void set_padding_algorithm(const std::string& a) { padding_algorithm_ = a; }
   void set_output_channels(int64_t c) { out_channels_override_ = c; }  // kHIP fusions only (lite/kernels/hip/conv_fusion.h)
   void set_output_pooled() { out_pooled_ = true; }                     // ... with the global average pool behind it: [n, c, 1, 1]
+  // kHIP fusion H1 (conv_fusion.h image_input): `x` takes the NCHW shape [n, channels, h, w] of the uint8 image [n, h, w, cs]
+  void set_image_input(const Tensor* img, int channels) {
+    image_ = img;
+    image_channels_ = channels;
+  }
   bool CheckShape() const override {
     CHECK(param_.x && param_.filter && param_.output) << "conv: x / filter / output must be set";
+    ImageShape();
     const auto in = param_.x->dims(), f = param_.filter->dims();
     CHECK_EQ(in.size(), 4UL) << "conv input must be NCHW";
     CHECK_EQ(f.size(), 4UL);
@@ -79,6 +85,7 @@ class ConvOpLite : public OpLite {
     return true;
   }
   bool InferShapeImpl() const override {
+    ImageShape();
     const auto in = param_.x->dims(), f = param_.filter->dims();
     UpdatePaddingAndDilation(param_.paddings.get(), param_.dilations.get(), param_.strides, padding_algorithm_, in, f);
     // kHIP dw -> pw fusion (opt-in): a depthwise conv that took its 1x1 consumer over writes THAT conv's output
@@ -94,10 +101,18 @@ class ConvOpLite : public OpLite {
   void AttachKernel(KernelBase* k) override { k->SetParam<ConvParam>(param_); }
 
  private:
+  void ImageShape() const {
+    if (!image_) return;
+    const auto d = image_->dims();
+    CHECK_EQ(d.size(), 4UL) << "conv: the image source must be [n, h, w, cs]";
+    param_.x->Resize(std::vector<int64_t>{d[0], image_channels_, d[1], d[2]});
+  }
   mutable ConvParam param_;
   std::string padding_algorithm_{""};
   int64_t out_channels_override_{0};
   bool out_pooled_{false};
+  const Tensor* image_{nullptr};
+  int64_t image_channels_{0};
 };
 
 class FcOpLite : public OpLite {

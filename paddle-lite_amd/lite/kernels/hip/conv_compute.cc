@@ -103,8 +103,20 @@ void ConvCompute<Ptype, OutType>::ReInitWhenNeeded() {
   if (fusion_.calib_input_scale > 0.f) {
     CHECK(!is_depthwise_ && !has_pw_ && !param.fuse_residual_connection && fusion_.calib_output == nullptr)
         << "kHIP: a conv that took the calib in front of it over has no other fusion";
-    calib_in_fused_ = plhip_conv2d_calib_supported(&desc_) != 0;
-    if (calib_in_fused_) kernel_func_name_ = "calib_fp32_to_int8+" + std::string(plhip_conv_impl_name(&desc_));
+    if (fusion_.image_input) {  // fusion H1: the uint8 image is the source, image_to_tensor + calib fold in
+      image_desc_ = plhip_image_desc{};
+      image_desc_.n = desc_.n; image_desc_.h = desc_.h; image_desc_.w = desc_.w;
+      image_desc_.format = fusion_.image_format;
+      for (int i = 0; i < 3; ++i) {
+        image_desc_.means[i] = fusion_.image_means[i];
+        image_desc_.scales[i] = fusion_.image_scales[i];
+      }
+      calib_in_fused_ = plhip_conv2d_image_supported(&desc_, &image_desc_) != 0;
+      kernel_func_name_ = (calib_in_fused_ ? "image_to_tensor_int8+" : "image_to_tensor_int8_hip+") + std::string(plhip_conv_impl_name(&desc_));
+    } else {
+      calib_in_fused_ = plhip_conv2d_calib_supported(&desc_) != 0;
+      if (calib_in_fused_) kernel_func_name_ = "calib_fp32_to_int8+" + std::string(plhip_conv_impl_name(&desc_));
+    }
   }
   if (has_pw_) {  // the pointwise conv sees the depthwise conv's output plane (`output` may be the pooled one: from the descriptor)
     pw_desc_.n = desc_.n;
@@ -258,11 +270,25 @@ template <PrecisionType Ptype, PrecisionType OutType>
 void ConvCompute<Ptype, OutType>::Run() {
   auto& param = this->template Param<param_t>();
   auto& ctx = this->ctx_->template As<HIPContext>();
-  CHECK(param.x->target() == TARGET(kHIP)) << "conv input must live on the HIP device (io_copy missing?)";
+  CHECK(fusion_.image_input || param.x->target() == TARGET(kHIP)) << "conv input must live on the HIP device (io_copy missing?)";
   const float* sc = scale_.data<float>();
   const float* bi = has_bias_ ? bias_.data<float>() : nullptr;
   const int8_t* x;
-  if (fusion_.calib_input_scale > 0.f) {  // `x` is the fp32 input of the calib this conv took over (fusion F)
+  if (fusion_.image_input) {  // the uint8 image in front of image_to_tensor + calib (fusion H1); `x` only carries the NCHW shape
+    CHECK(fusion_.image_input->target() == TARGET(kHIP)) << "conv image source must live on the HIP device (io_copy missing?)";
+    const uint8_t* src = static_cast<const uint8_t*>(fusion_.image_input->raw_data());
+    if (calib_in_fused_) {
+      void* yo = OutType == PRECISION(kInt8) ? static_cast<void*>(param.output->template mutable_data<int8_t>(TARGET(kHIP)))
+                                             : static_cast<void*>(param.output->template mutable_data<float>(TARGET(kHIP)));
+      HIP_CALL(ctx.ctx(), plhip_conv2d_image_int8(ctx.ctx(), &desc_, &image_desc_, src, fusion_.calib_input_scale, weights_.raw_data(), sc,
+                                                  bi, yo, OutType == PRECISION(kInt8) ? PLHIP_OUT_I8 : PLHIP_OUT_F32));
+      return;
+    }
+    xq_.Resize(param.x->dims());  // no one-launch form for this shape: the int8 tensor into a private tensor, then the conv
+    int8_t* q = xq_.mutable_data<int8_t>(TARGET(kHIP));
+    HIP_CALL(ctx.ctx(), plhip_image_to_tensor_i8(ctx.ctx(), &image_desc_, src, q, fusion_.calib_input_scale));
+    x = q;
+  } else if (fusion_.calib_input_scale > 0.f) {  // `x` is the fp32 input of the calib this conv took over (fusion F)
     const float* xf = param.x->template data<float>();
     if (calib_in_fused_) {
       void* yo = OutType == PRECISION(kInt8) ? static_cast<void*>(param.output->template mutable_data<int8_t>(TARGET(kHIP)))

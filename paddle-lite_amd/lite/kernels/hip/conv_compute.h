@@ -51,7 +51,8 @@ class ConvCompute : public KernelLite<TARGET(kHIP), Ptype>, public HipFusableKer
   plhip_conv_desc pw_desc_{};
   Tensor pw_weights_, pw_scale_, pw_bias_, mid_, mid2_;
   Tensor xq_;                      // fused calib in front (HipConvFusion::calib_input_scale) on a shape without the one-launch form
-  bool calib_in_fused_{false};
+  bool calib_in_fused_{false};     // ... or, with HipConvFusion::image_input, the image in front of it in the same launch
+  plhip_image_desc image_desc_{};  // HipConvFusion::image_input: the image, [n, h, w] from the descriptor
 };
 
 }  // namespace hip

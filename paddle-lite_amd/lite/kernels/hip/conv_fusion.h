@@ -15,6 +15,7 @@
 
 #include "lite/core/tensor.h"
 #include "lite/operators/op_params.h"
+#include "plhip.h"
 
 namespace paddle {
 namespace lite {
@@ -53,6 +54,15 @@ struct HipConvFusion {
   // fp32 input and this its scale; the kernel quantises while it stages the rows (plhip_conv2d_calib_int8) where it has that
   // form (the 3x3 stride-2 stem), otherwise the kernel object runs the calib into a private tensor first.  0 = none.
   float calib_input_scale{0.f};
+  // ... and the image_to_tensor in front of that calib too (graph_builder.cc, fusion H1): the conv's source is then the caller's
+  // uint8 image [n, h, w, cs] on the device (image_to_tensor.h), `x` of the ConvParam only carries the NCHW shape made from it
+  // (ConvOpLite::set_image_input) and is never allocated; calib_input_scale is the calib's scale.  The kernel reads the image while it
+  // stages its rows (plhip_conv2d_image_int8) where it has that form, otherwise it runs plhip_image_to_tensor_i8 into a private
+  // tensor first.  nullptr = none.
+  const lite::Tensor* image_input{nullptr};
+  int image_format{PLHIP_IMG_BGR};
+  float image_means[3]{0.f, 0.f, 0.f};
+  float image_scales[3]{1.f, 1.f, 1.f};
 };
 
 class HipFusableKernel {

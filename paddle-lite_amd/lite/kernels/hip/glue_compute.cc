@@ -5,6 +5,7 @@
 //   elementwise_add, fusion_elementwise_add_activation (relu), fp32   lite/kernels/arm/elementwise_compute.cc:182-207
 //   softmax fp32                          lite/kernels/arm/softmax_compute.cc
 #include "lite/core/op_registry.h"
+#include "lite/kernels/hip/image_to_tensor.h"
 #include "lite/operators/op_params.h"
 #include "plhip.h"
 
@@ -37,6 +38,37 @@ class CalibComputeInt8ToFp32 : public KernelLite<TARGET(kHIP), PRECISION(kInt8)>
                                               param.input->numel()));
   }
   void SetProfileRuntimeKernelInfo(profile::OpCharacter* ch) override { ch->kernel_func_name = "int8_to_fp32_hip"; }
+};
+
+// image_to_tensor (image_to_tensor.h): the caller's uint8 image -> the fp32 NCHW input tensor, ImagePreprocess::image_to_tensor
+// (paddle_image_preprocess.cc:143-172 -> image2tensor.cc) on the device; alias int8: with the calib[fp32_to_int8] behind it
+// (calib_compute.cc:25-40) folded in, bit-identical to the two instructions.
+class ImageToTensorCompute : public KernelLite<TARGET(kHIP), PRECISION(kAny)> {
+ public:
+  void Run() override {
+    auto& param = this->Param<operators::ImageToTensorParam>();
+    auto& ctx = this->ctx_->As<HIPContext>();
+    CHECK(param.x->target() == TARGET(kHIP)) << "image_to_tensor: the image must live on the HIP device (io_copy missing?)";
+    const auto d = param.x->dims();
+    plhip_image_desc img{};
+    img.n = static_cast<int>(d[0]);
+    img.h = static_cast<int>(d[1]);
+    img.w = static_cast<int>(d[2]);
+    img.format = param.format;
+    for (int i = 0; i < 3; ++i) {
+      img.means[i] = param.means[i];
+      img.scales[i] = param.scales[i];
+    }
+    const uint8_t* src = static_cast<const uint8_t*>(param.x->raw_data());
+    if (param.int8_out) {
+      HIP_CALL(ctx.ctx(), plhip_image_to_tensor_i8(ctx.ctx(), &img, src, param.output->mutable_data<int8_t>(TARGET(kHIP)), param.calib_scale));
+    } else {
+      HIP_CALL(ctx.ctx(), plhip_image_to_tensor_f32(ctx.ctx(), &img, src, param.output->mutable_data<float>(TARGET(kHIP))));
+    }
+  }
+  void SetProfileRuntimeKernelInfo(profile::OpCharacter* ch) override {
+    ch->kernel_func_name = this->Param<operators::ImageToTensorParam>().int8_out ? "image_to_tensor_int8_hip" : "image_to_tensor_fp32_hip";
+  }
 };
 
 // precision/layout kAny like the CUDA io_copy kernels: bytes are moved, whatever they mean.
@@ -197,6 +229,14 @@ REGISTER_LITE_KERNEL(calib, kHIP, kInt8, kNCHW, paddle::lite::kernels::hip::Cali
 REGISTER_LITE_KERNEL(calib, kHIP, kInt8, kNCHW, paddle::lite::kernels::hip::CalibComputeInt8ToFp32, int8_to_fp32)
     .BindInput("Input", {LiteType::GetTensorTy(TARGET(kHIP), PRECISION(kInt8))})
     .BindOutput("Out", {LiteType::GetTensorTy(TARGET(kHIP), PRECISION(kFloat))})
+    .Finalize();
+REGISTER_LITE_KERNEL(image_to_tensor, kHIP, kAny, kNCHW, paddle::lite::kernels::hip::ImageToTensorCompute, fp32)
+    .BindInput("X", {LiteType::GetTensorTy(TARGET(kHIP), PRECISION(kUInt8), DATALAYOUT(kAny))})
+    .BindOutput("Out", {LiteType::GetTensorTy(TARGET(kHIP), PRECISION(kFloat))})
+    .Finalize();
+REGISTER_LITE_KERNEL(image_to_tensor, kHIP, kAny, kNCHW, paddle::lite::kernels::hip::ImageToTensorCompute, int8)
+    .BindInput("X", {LiteType::GetTensorTy(TARGET(kHIP), PRECISION(kUInt8), DATALAYOUT(kAny))})
+    .BindOutput("Out", {LiteType::GetTensorTy(TARGET(kHIP), PRECISION(kInt8))})
     .Finalize();
 REGISTER_LITE_KERNEL(io_copy, kHIP, kAny, kAny, paddle::lite::kernels::hip::IoCopyHostToHipCompute, host_to_device)
     .BindInput("Input", {LiteType::GetTensorTy(TARGET(kHost), PRECISION(kAny), DATALAYOUT(kAny))})

@@ -9,6 +9,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libpaddle_lite_hip.so")
 PREC_FLOAT, PREC_INT8, PREC_ANY = 1, 2, 4
 LAYOUT_NCHW, LAYOUT_ANY = 1, 2
+# image formats of graph_feed_image == cv::ImageFormat (lite/utils/cv/paddle_image_preprocess.h) == plhip_image_format
+IMG_RGBA, IMG_BGRA, IMG_RGB, IMG_BGR, IMG_GRAY = 0, 1, 2, 3, 4
 
 
 class LiteError(RuntimeError):
@@ -47,6 +49,7 @@ def load():
     L.pllite_add_elementwise_add.argtypes = [vp, cs, cs, cs, cs]
     L.pllite_predictor_create_planner.restype = vp
     L.pllite_graph_feed.argtypes = [vp, cs, C.POINTER(i64), i32, i32]
+    L.pllite_graph_feed_image.argtypes = [vp, cs, i32, i32, i32, i32, C.POINTER(f32), C.POINTER(f32)]
     L.pllite_graph_conv.argtypes = [vp, cs, cs, cs, vp, C.POINTER(i64), vp, C.POINTER(i32), C.POINTER(i32), i32,
                                     C.POINTER(i32), i32, i32, f32, f32, vp, i32, cs]
     L.pllite_graph_fc.argtypes = [vp, cs, cs, vp, i32, i32, vp, f32, vp, i32, i32]
@@ -159,6 +162,14 @@ class Predictor:
     # ---- graph mode: ops as the optimiser sees them; graph_lower() applies the reference's kernel-pick / cast rules
     def graph_feed(self, name, dims, precision=PREC_FLOAT):
         self._ck(self.L.pllite_graph_feed(self.h, name.encode(), _ia(dims, C.c_int64), len(dims), precision))
+
+    def graph_feed_image(self, name, n, h, w, fmt, means, scales):
+        """A feed that takes a decoded uint8 image [n, h, w, cs] (fmt: IMG_*) instead of the normalised fp32 tensor: the ops
+        name `name` as the NCHW tensor (ImagePreprocess::image_to_tensor runs on the device); set_input(name, uint8 array).
+        means / scales: per source byte of a pixel (the first only for IMG_GRAY)."""
+        m = (C.c_float * 3)(*(list(map(float, means)) + [0.0] * 3)[:3])
+        s = (C.c_float * 3)(*(list(map(float, scales)) + [0.0] * 3)[:3])
+        self._ck(self.L.pllite_graph_feed_image(self.h, name.encode(), int(n), int(h), int(w), int(fmt), m, s))
 
     def graph_conv(self, op_type, src, dst, w, bias, strides, paddings, dilations, groups, act, act_coef, input_scale,
                    weight_scale, padding_algorithm=""):

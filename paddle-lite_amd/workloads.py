@@ -270,8 +270,10 @@ def net_stats(net):
     return macs
 
 
-def emit_graph(pred, net, batch, fuse=True, fuse_dwpw=None, fuse_dwconv=None):
+def emit_graph(pred, net, batch, fuse=True, fuse_dwpw=None, fuse_dwconv=None, image=None):
     """Feed the op list to the predictor's graph mode and lower it.  Returns the host name of the output variable.
+    image: None = the input is the normalised fp32 NCHW tensor; dict(format, means, scales) = the input is a decoded uint8 image
+    [batch, h, w, cs] of that format (liteapi.IMG_*), normalised on the device (Predictor.graph_feed_image).
     fuse=False: the reference program instruction for instruction (no kHIP graph-level fusion).
     fuse_dwpw: None = the builder's default (depthwise -> pointwise pairs the fused kernel takes become one instruction),
     True = every eligible pair (shapes outside the kernel run as two launches inside the instruction), False = none.
@@ -284,7 +286,10 @@ def emit_graph(pred, net, batch, fuse=True, fuse_dwpw=None, fuse_dwconv=None):
     if fuse_dwconv is not None:
         pred.graph_set_fuse_dwconv(fuse_dwconv)
     c, h, w = net["input_shape"]
-    pred.graph_feed(net["input"], (batch, c, h, w), liteapi.PREC_FLOAT)
+    if image is None:
+        pred.graph_feed(net["input"], (batch, c, h, w), liteapi.PREC_FLOAT)
+    else:
+        pred.graph_feed_image(net["input"], batch, h, w, image["format"], image["means"], image["scales"])
     for o in net["ops"]:
         t = o["op"]
         if t in ("conv2d", "depthwise_conv2d"):
