@@ -197,6 +197,39 @@ def test_mobilenet_v1_int8_program_at_batch_128(lite, wl, plref):
         np.testing.assert_allclose(p.get_var(out, np.float32), ref["prob"], rtol=1e-4, atol=1e-7)
     finally:
         p.close()
+    # the program bench.py times: the same network in graph form, lowered with the default fusions (wl.emit_graph(p, net, 128)):
+    # 19 instructions, 13 one-launch dw -> pw pairs, the pool folded into the last pair and the calib into the stem; every
+    # variable it materialises, all 128 images, against the same oracle
+    net = wl.mobilenet_v1_net(seed=1234)
+    p = lite.Predictor(0)
+    try:
+        out = wl.emit_graph(p, net, B)
+        plan = p.graph_plan()
+        assert len(plan) == 19 and sum("+pw=" in l for l in plan) == 13, plan
+        assert p.graph_lower() == [out]
+        p.set_input(net["input"], img)
+        p.run()
+        n_i8 = n_f32 = 0
+        for name, want in ref.items():
+            try:
+                got = p.get_var(name, want.dtype)
+            except Exception:  # noqa: BLE001  (fused away: the int8 image, pw14's plane)
+                continue
+            if want.dtype == np.int8:
+                assert np.array_equal(got, want), "fused program %s: %d of %d differ" % (name, (got != want).sum(), want.size)
+                n_i8 += 1
+            else:  # the pool is summed in the pair's own order: the fp32 values summed are the bit-identical pw14 outputs
+                np.testing.assert_allclose(got, want, rtol=1e-4 if name == out else 1e-5, atol=1e-5, err_msg=name)
+                n_f32 += 1
+        assert n_i8 >= 13 and n_f32 >= 3, (n_i8, n_f32)  # conv1, pw2..pw13: the dw outputs live in the fused launches
+    finally:
+        p.close()
+
+
+def test_mobilenet_v1_at_the_benchmark_batch_128(lite, wl, plref):
+    """The fused program bench.py times, at its batch: prefix == the batch-2 run, one mid-batch image == the oracle."""
+    n_i8, n_f32 = _big_batch_check(lite, wl, plref, wl.mobilenet_v1_net(), 128, 323, fuse=True, mid=93)
+    assert n_i8 >= 13 and n_f32 >= 2  # the dw outputs live in the fused launches
 
 
 def _big_batch_check(lite, wl, plref, net, B, seed, fuse, mid):
