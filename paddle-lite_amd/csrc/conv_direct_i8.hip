@@ -13,7 +13,7 @@
 
 #include "plhip_device.h"
 #include "plhip_kernels.h"
-#include "gemm_epilogue.h"
+#include "conv_stem_common.h"
 #include "dw_common.h"
 
 namespace plhip {
@@ -217,8 +217,8 @@ __global__ __launch_bounds__(256) void conv3x3s2_direct_kernel(DirectS2Args a) {
 // MFMA form of the stem (Cin*9 <= 27, OW % 4 == 0).  The 27 taps are ONE K-step of v_mfma_i32_32x32x32_i8.
 // Lane (c, h): c = quad (4 consecutive ox, one per MFMA i), h = k half.  The k order is free as long as the packed A
 // fragments agree, so it is chosen to give both halves the SAME structure: half h owns the row windows
-// cr = 5h .. 5h+4  (cr = ci*3 + filter row; windows >= 3*Cin do not exist and read as zero), 3 taps each:
-//     operand bytes = (L0.0 L0.1 L0.2 L1.0 | L1.1 L1.2 L2.0 L2.1 | L2.2 L3.0 L3.1 L3.2 | L4.0 L4.1 L4.2 0).
+// cr = 5h .. 5h+4  (cr = ci*3 + filter row; windows >= 3*Cin do not exist and read as zero), 3 taps each; the operand
+// bytes made of them, the MFMAs and the epilogue are stem3x3_mfma (conv_stem_common.h), shared with the fused-input stems.
 // A lane therefore fetches 5 rows (not 9), and builds each operand with 3 v_perm + 1 v_and using constant selectors.
 // PMC on the previous form (both halves fetched all 9 windows through the guarded general fetch, 64-bit index math):
 // 1057 VALU per wave against ~300 for the requantisation of its 4096 outputs -- the stem was VALU-bound at 2.5x its
@@ -241,18 +241,8 @@ __device__ __forceinline__ void stem_mfma_body(const DirectS2Args& a, const int8
   const int start = 8 * xq - a.pl;
   const int ncr = a.cin * 3;
 
-  GemmArgs g;
-  g.y = a.y;
-  g.scale = a.scale;
-  g.bias = a.bias;
-  g.M = a.cout;
-  g.HWY = a.oh * a.ow;
-  g.y_bstride = (size_t)a.cout * a.oh * a.ow;
-  g.act = a.act;
-  g.alpha = a.alpha;
-  g.res = nullptr; g.res_relu = 0; g.y2 = nullptr; g.inv_scale2 = 0.f;  // no fused graph tail on the stem
-  const v4i af0 = *reinterpret_cast<const v4i*>(afrag + (size_t)lane * 16);
-  if (OUT != OUT_I32) stage_scale_bias<1, OUT>(g, 0, lane, lsb);
+  GemmArgs g;  // (no fused graph tail on the stem)
+  const v4i af0 = stem3x3_begin<OUT>(a, afrag, lane, lsb, g);
 
   uint32_t cmask[3];
   dw_col_masks<3>(start, a.w, cmask);  // -4 < start < w (host check)
@@ -296,40 +286,7 @@ __device__ __forceinline__ void stem_mfma_body(const DirectS2Args& a, const int8
     win[2][L] = d[1];
     win[3][L] = __builtin_amdgcn_alignbyte(d[2], d[1], 2);
   }
-  v4i bf[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    bf[j][0] = (int)__builtin_amdgcn_perm(win[j][1], win[j][0], 0x04020100u);
-    bf[j][1] = (int)__builtin_amdgcn_perm(win[j][2], win[j][1], 0x05040201u);
-    bf[j][2] = (int)__builtin_amdgcn_perm(win[j][3], win[j][2], 0x06050402u);
-    bf[j][3] = (int)(win[j][4] & 0x00ffffffu);
-  }
-
-  const int hw = oy * a.ow + 4 * xq;
-  const int MT = (a.cout + 31) >> 5;
-  for (int mt = 0; mt < MT; ++mt) {  // uniform
-    v4i af = af0;
-    if (mt > 0) {
-      af = *reinterpret_cast<const v4i*>(afrag + ((size_t)mt * 64 + lane) * 16);
-      if (OUT != OUT_I32) stage_scale_bias<1, OUT>(g, mt, lane, lsb);
-    }
-    v16i acc[1][4];
-    const v16i zero16 = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // (an inline operand of the MFMA: no accumulator zeroing)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[0][j] = __builtin_amdgcn_mfma_i32_32x32x32_i8(af, bf[j], zero16, 0, 0, 0);
-    if (qvalid) {
-      if (OUT == OUT_I32) {
-        gemm_epilogue<1, OUT, true, MFULL, ACT_NONE>(g, acc, mt, h, b, hw, lsb, g.HWY - hw);
-      } else {
-        switch (a.act) {
-          case ACT_RELU: gemm_epilogue<1, OUT, true, MFULL, ACT_RELU>(g, acc, mt, h, b, hw, lsb, g.HWY - hw); break;
-          case ACT_RELU6: gemm_epilogue<1, OUT, true, MFULL, ACT_RELU6>(g, acc, mt, h, b, hw, lsb, g.HWY - hw); break;
-          case ACT_LEAKY: gemm_epilogue<1, OUT, true, MFULL, ACT_LEAKY>(g, acc, mt, h, b, hw, lsb, g.HWY - hw); break;
-          default: gemm_epilogue<1, OUT, true, MFULL, ACT_NONE>(g, acc, mt, h, b, hw, lsb, g.HWY - hw); break;
-        }
-      }
-    }
-  }
+  stem3x3_mfma<OUT, MFULL>(g, afrag, af0, win, lsb, lane, b, oy * a.ow + 4 * xq, qvalid);
 }
 
 template <int OUT, bool MFULL>
@@ -341,23 +298,16 @@ __global__ __launch_bounds__(256) void conv3x3s2_mfma_kernel(DirectS2Args a, con
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   float* lsb = lsb_all[wave];
-  // 1-D grid of 8 * per blocks; XCD x (= blockIdx % 8, round-robin dispatch) gets the x-th eighth of the (image, row
-  // group, column tile) space, so that row groups sharing an input row sit on one L2.  All of it is wave-uniform.
-  const int nx = ((a.ow >> 2) + 31) >> 5, ny = (a.oh + 3) >> 2;
-  const unsigned nb = (unsigned)(nx * ny * a.n), per = (nb + 7) >> 3;
-  const unsigned vb = (blockIdx.x & 7) * per + (blockIdx.x >> 3);
-  if (vb >= nb) return;
-  const int bx = (int)(vb % (unsigned)nx);
-  const unsigned t = vb / (unsigned)nx;
-  const int by = (int)(t % (unsigned)ny), bz = (int)(t / (unsigned)ny);
+  int bx, by, bz;
+  if (!stem_block(a, bx, by, bz)) return;
   // only the first rows of the first image / the last rows of the last image can touch bytes outside the tensor
-  const bool guard = (bz == 0 && by == 0) || (bz + 1 == a.n && by + 1 == ny);
+  const bool guard = (bz == 0 && by == 0) || (bz + 1 == a.n && by + 1 == ((a.oh + 3) >> 2));
   if (guard) stem_mfma_body<OUT, MFULL, true>(a, afrag, lsb, lane, wave, bx, by, bz);
   else stem_mfma_body<OUT, MFULL, false>(a, afrag, lsb, lane, wave, bx, by, bz);
 }
 
 // A fragments: tile mt, lane (r = lane&31, h = lane>>5), byte j  <-  W[mt*32 + r][window cr = 5h + j/3][tap j%3]
-// (h = 0: j < 15, h = 1: j < 12 and cr < 3*Cin; zero elsewhere) -- the k order of stem_mfma_body.
+// (h = 0: j < 15, h = 1: j < 12 and cr < 3*Cin; zero elsewhere) -- the k order of stem3x3_mfma (conv_stem_common.h).
 __global__ void pack_conv3x3s2_mfma_kernel(const int8_t* __restrict__ w, int8_t* __restrict__ afrag, int cin, int cout) {
   const int total = ((cout + 31) / 32) * 1024;
   for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gridDim.x * blockDim.x) {
@@ -385,19 +335,10 @@ void launch_conv3x3s2_direct(const DirectS2Args& a, int out, hipStream_t s) {
   const int owq = a.ow >> 2;
   if (mfma_env && a.cin * 3 <= 9 && (a.ow & 3) == 0 && ((uintptr_t)a.y & (4 * esz - 1)) == 0 && tensor < (1L << 31) &&
       8 * (owq - 1) - a.pl < a.w && (long)((owq + 31) / 32) * ((a.oh + 3) / 4) * a.n < (1L << 31) - 8) {
-    const long nblk = (long)((owq + 31) / 32) * ((a.oh + 3) / 4) * a.n;
-    const dim3 blocks((unsigned)((nblk + 7) / 8 * 8));
     const int8_t* afrag = reinterpret_cast<const int8_t*>(a.wp) + ds2_dot4_bytes(a.cin, a.cout);
-    const bool mfull = a.cout % 32 == 0;
-#define PLHIP_STEM(O)                                                                                       \
-  do {                                                                                                      \
-    if (mfull) hipLaunchKernelGGL((conv3x3s2_mfma_kernel<O, true>), blocks, dim3(256), 0, s, a, afrag);  \
-    else hipLaunchKernelGGL((conv3x3s2_mfma_kernel<O, false>), blocks, dim3(256), 0, s, a, afrag);       \
-  } while (0)
-    if (out == OUT_I32) PLHIP_STEM(OUT_I32);
-    else if (out == OUT_F32) PLHIP_STEM(OUT_F32);
-    else PLHIP_STEM(OUT_I8);
-#undef PLHIP_STEM
+    stem_dispatch(a, out, [&](auto O, auto MF) {
+      hipLaunchKernelGGL((conv3x3s2_mfma_kernel<decltype(O)::value, decltype(MF)::value>), stem_grid(a), dim3(256), 0, s, a, afrag);
+    });
     return;
   }
   const long total = (long)a.n * a.oh * ((a.ow + 3) >> 2);

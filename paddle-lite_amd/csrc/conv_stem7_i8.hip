@@ -17,7 +17,7 @@
 
 #include "plhip_device.h"
 #include "plhip_kernels.h"
-#include "gemm_epilogue.h"
+#include "conv_stem_common.h"
 #include "dw_common.h"
 
 namespace plhip {
@@ -72,15 +72,7 @@ __device__ __forceinline__ void stem7_body(const DirectS2Args& a, const int8_t* 
   const int ncr = a.cin * 7;
 
   GemmArgs g;
-  g.y = a.y;
-  g.scale = a.scale;
-  g.bias = a.bias;
-  g.M = a.cout;
-  g.HWY = a.oh * a.ow;
-  g.y_bstride = (size_t)a.cout * a.oh * a.ow;
-  g.act = a.act;
-  g.alpha = a.alpha;
-  g.res = a.res; g.res_relu = a.res_relu; g.y2 = a.y2; g.inv_scale2 = a.inv_scale2;
+  stem_gemm_args<true>(a, g);
   if (OUT != OUT_I32) stage_scale_bias<1, OUT>(g, 0, lane, lsb);
 
   // byte i of the window <-> column start + i: kept iff inside the row
@@ -158,18 +150,7 @@ __device__ __forceinline__ void stem7_body(const DirectS2Args& a, const int8_t* 
 #pragma unroll
       for (int ks = 1; ks < STEM7_KS; ++ks) acc[0][j] = __builtin_amdgcn_mfma_i32_32x32x32_i8(af[ks], bf[ks][j], acc[0][j], 0, 0, 0);
     }
-    if (qvalid) {
-      if (OUT == OUT_I32) {
-        gemm_epilogue<1, OUT, VEC, MFULL, ACT_NONE>(g, acc, mt, h, b, hw, lsb, g.HWY - hw);
-      } else {
-        switch (a.act) {
-          case ACT_RELU: gemm_epilogue<1, OUT, VEC, MFULL, ACT_RELU>(g, acc, mt, h, b, hw, lsb, g.HWY - hw); break;
-          case ACT_RELU6: gemm_epilogue<1, OUT, VEC, MFULL, ACT_RELU6>(g, acc, mt, h, b, hw, lsb, g.HWY - hw); break;
-          case ACT_LEAKY: gemm_epilogue<1, OUT, VEC, MFULL, ACT_LEAKY>(g, acc, mt, h, b, hw, lsb, g.HWY - hw); break;
-          default: gemm_epilogue<1, OUT, VEC, MFULL, ACT_NONE>(g, acc, mt, h, b, hw, lsb, g.HWY - hw); break;
-        }
-      }
-    }
+    if (qvalid) gemm_epilogue_act<1, OUT, VEC, MFULL>(g, acc, mt, h, b, hw, lsb, g.HWY - hw);
   }
 }
 
@@ -183,15 +164,8 @@ __global__ __launch_bounds__(256, 2) void conv7x7s2_stem_kernel(DirectS2Args a, 
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   float* lsb = lsb_all[wave];
-  // 1-D grid of 8 * per blocks; XCD x (= blockIdx % 8, round-robin dispatch) gets the x-th eighth of the (image, row group,
-  // column tile) space, so that row groups sharing input rows sit on one L2.  All of it is wave-uniform.
-  const int nx = ((a.ow >> 2) + 31) >> 5, ny = (a.oh + 3) >> 2;
-  const unsigned nb = (unsigned)(nx * ny * a.n), per = (nb + 7) >> 3;
-  const unsigned vb = (blockIdx.x & 7) * per + (blockIdx.x >> 3);
-  if (vb >= nb) return;
-  const int bx = (int)(vb % (unsigned)nx);
-  const unsigned t = vb / (unsigned)nx;
-  const int by = (int)(t % (unsigned)ny), bz = (int)(t / (unsigned)ny);
+  int bx, by, bz;
+  if (!stem_block(a, bx, by, bz)) return;
   // a 16-byte window starts up to 3 bytes before its row and ends up to 15 after it: only row groups of the first image that
   // reach input row 0 (or above) and row groups of the last image that reach its last row (or below) can touch bytes outside
   // the tensor: those fetch bytewise
@@ -202,22 +176,13 @@ __global__ __launch_bounds__(256, 2) void conv7x7s2_stem_kernel(DirectS2Args a, 
 
 // vec_store: y (and the tail operands) aligned for a lane's 4 consecutive outputs (dword / 16-byte accesses)
 void launch_conv7x7s2_stem(const DirectS2Args& a, int out, bool vec_store, hipStream_t s) {
-  const int owq = a.ow >> 2;
-  const long nblk = (long)((owq + 31) / 32) * ((a.oh + 3) / 4) * a.n;
-  const dim3 blocks((unsigned)((nblk + 7) / 8 * 8));
   const int8_t* afrag = reinterpret_cast<const int8_t*>(a.wp);
-  const bool mfull = a.cout % 32 == 0;
-#define PLHIP_STEM7(O)                                                                                                   \
-  do {                                                                                                                   \
-    if (mfull && vec_store) hipLaunchKernelGGL((conv7x7s2_stem_kernel<O, true, true>), blocks, dim3(256), 0, s, a, afrag);   \
-    else if (mfull) hipLaunchKernelGGL((conv7x7s2_stem_kernel<O, true, false>), blocks, dim3(256), 0, s, a, afrag);          \
-    else if (vec_store) hipLaunchKernelGGL((conv7x7s2_stem_kernel<O, false, true>), blocks, dim3(256), 0, s, a, afrag);      \
-    else hipLaunchKernelGGL((conv7x7s2_stem_kernel<O, false, false>), blocks, dim3(256), 0, s, a, afrag);                    \
-  } while (0)
-  if (out == OUT_I32) PLHIP_STEM7(OUT_I32);
-  else if (out == OUT_F32) PLHIP_STEM7(OUT_F32);
-  else PLHIP_STEM7(OUT_I8);
-#undef PLHIP_STEM7
+  stem_dispatch(a, out, [&](auto O, auto MF) {
+    constexpr int o = decltype(O)::value;
+    constexpr bool mf = decltype(MF)::value;
+    if (vec_store) hipLaunchKernelGGL((conv7x7s2_stem_kernel<o, mf, true>), stem_grid(a), dim3(256), 0, s, a, afrag);
+    else hipLaunchKernelGGL((conv7x7s2_stem_kernel<o, mf, false>), stem_grid(a), dim3(256), 0, s, a, afrag);
+  });
 }
 
 }  // namespace plhip

@@ -1,5 +1,5 @@
 // gemm_epilogue.h — the fused dequant / requant + bias + activation epilogue of the 32x32x32 int8 MFMA tile, shared by
-// the GEMM kernels (gemm_i8.hip) and the MFMA stem convolution (conv_direct_i8.hip).
+// the GEMM kernels (gemm_i8.hip) and the MFMA stem convolutions (conv_stem_common.h).  Callers enter through gemm_epilogue_act.
 #pragma once
 #include "plhip_device.h"
 #include "plhip_kernels.h"
@@ -197,6 +197,23 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, const v16i (&ac
         }
       }
     }
+  }
+}
+
+// The runtime-activation front door of every caller: g.act is wave-uniform, so one straight-line epilogue per activation runs.
+// int32 output ignores scale, bias and activation.
+template <int MA, int OUT, bool VEC_STORE, bool MFULL>
+__device__ __forceinline__ void gemm_epilogue_act(const GemmArgs& g, const v16i (&acc)[MA][4], int mt, int h, int b, int hw,
+                                                  const float* lsb, int hwy_room, int skip = 0) {
+  if (OUT == OUT_I32) {
+    gemm_epilogue<MA, OUT, VEC_STORE, MFULL, ACT_NONE>(g, acc, mt, h, b, hw, lsb, hwy_room, skip);
+    return;
+  }
+  switch (g.act) {
+    case ACT_RELU: gemm_epilogue<MA, OUT, VEC_STORE, MFULL, ACT_RELU>(g, acc, mt, h, b, hw, lsb, hwy_room, skip); break;
+    case ACT_RELU6: gemm_epilogue<MA, OUT, VEC_STORE, MFULL, ACT_RELU6>(g, acc, mt, h, b, hw, lsb, hwy_room, skip); break;
+    case ACT_LEAKY: gemm_epilogue<MA, OUT, VEC_STORE, MFULL, ACT_LEAKY>(g, acc, mt, h, b, hw, lsb, hwy_room, skip); break;
+    default: gemm_epilogue<MA, OUT, VEC_STORE, MFULL, ACT_NONE>(g, acc, mt, h, b, hw, lsb, hwy_room, skip); break;
   }
 }
 

@@ -142,16 +142,7 @@ __global__ __launch_bounds__(256, 2) void gemm_i8_nchw_kernel(GemmArgs g) {
 
   if (OUT != OUT_I32) store_scale_bias<MA, OUT>(lsb, lane, my_s, my_b);
   if (!nvalid) return;
-  if (OUT == OUT_I32) {
-    gemm_epilogue<MA, OUT, VEC_STORE, MFULL, ACT_NONE>(g, acc, mt, h, b, hw, lsb, g.HWY - hw);
-    return;
-  }
-  switch (g.act) {  // wave-uniform: one straight-line epilogue per activation
-    case ACT_RELU: gemm_epilogue<MA, OUT, VEC_STORE, MFULL, ACT_RELU>(g, acc, mt, h, b, hw, lsb, g.HWY - hw); break;
-    case ACT_RELU6: gemm_epilogue<MA, OUT, VEC_STORE, MFULL, ACT_RELU6>(g, acc, mt, h, b, hw, lsb, g.HWY - hw); break;
-    case ACT_LEAKY: gemm_epilogue<MA, OUT, VEC_STORE, MFULL, ACT_LEAKY>(g, acc, mt, h, b, hw, lsb, g.HWY - hw); break;
-    default: gemm_epilogue<MA, OUT, VEC_STORE, MFULL, ACT_NONE>(g, acc, mt, h, b, hw, lsb, g.HWY - hw); break;
-  }
+  gemm_epilogue_act<MA, OUT, VEC_STORE, MFULL>(g, acc, mt, h, b, hw, lsb, g.HWY - hw);
 }
 
 // =====================================================================================================================
@@ -263,16 +254,7 @@ __global__ __launch_bounds__(256, 2) void gemm_i8_lds_kernel(GemmArgs g) {
 
   if (OUT != OUT_I32) store_scale_bias<MA, OUT>(lsb, lane, my_s, my_b);
   if (!nvalid || !mactive) return;
-  if (OUT == OUT_I32) {
-    gemm_epilogue<MA, OUT, VEC_STORE, MFULL, ACT_NONE>(g, acc, mt, h, b, hw, lsb, g.HWY - hw);
-    return;
-  }
-  switch (g.act) {
-    case ACT_RELU: gemm_epilogue<MA, OUT, VEC_STORE, MFULL, ACT_RELU>(g, acc, mt, h, b, hw, lsb, g.HWY - hw); break;
-    case ACT_RELU6: gemm_epilogue<MA, OUT, VEC_STORE, MFULL, ACT_RELU6>(g, acc, mt, h, b, hw, lsb, g.HWY - hw); break;
-    case ACT_LEAKY: gemm_epilogue<MA, OUT, VEC_STORE, MFULL, ACT_LEAKY>(g, acc, mt, h, b, hw, lsb, g.HWY - hw); break;
-    default: gemm_epilogue<MA, OUT, VEC_STORE, MFULL, ACT_NONE>(g, acc, mt, h, b, hw, lsb, g.HWY - hw); break;
-  }
+  gemm_epilogue_act<MA, OUT, VEC_STORE, MFULL>(g, acc, mt, h, b, hw, lsb, g.HWY - hw);
 }
 
 // =====================================================================================================================
@@ -592,18 +574,7 @@ __global__ __launch_bounds__(256, GD_D <= 4 ? 2 : 1) void gemm_i8_dma_kernel(Gem
 
   if (OUT != OUT_I32) store_scale_bias<MA, OUT>(lsb, lane, my_s, my_b);
   PLHIP_STAMP(STAMP_SLOTS - 4);
-  if (nvalid && mactive) {
-    if (OUT == OUT_I32) {
-      gemm_epilogue<MA, OUT, VEC_STORE, MFULL, ACT_NONE>(g, acc, mt, h, b, hw, lsb, g.HWY - hw, skip);
-    } else {
-      switch (g.act) {
-        case ACT_RELU: gemm_epilogue<MA, OUT, VEC_STORE, MFULL, ACT_RELU>(g, acc, mt, h, b, hw, lsb, g.HWY - hw, skip); break;
-        case ACT_RELU6: gemm_epilogue<MA, OUT, VEC_STORE, MFULL, ACT_RELU6>(g, acc, mt, h, b, hw, lsb, g.HWY - hw, skip); break;
-        case ACT_LEAKY: gemm_epilogue<MA, OUT, VEC_STORE, MFULL, ACT_LEAKY>(g, acc, mt, h, b, hw, lsb, g.HWY - hw, skip); break;
-        default: gemm_epilogue<MA, OUT, VEC_STORE, MFULL, ACT_NONE>(g, acc, mt, h, b, hw, lsb, g.HWY - hw, skip); break;
-      }
-    }
-  }
+  if (nvalid && mactive) gemm_epilogue_act<MA, OUT, VEC_STORE, MFULL>(g, acc, mt, h, b, hw, lsb, g.HWY - hw, skip);
   if (diag) {  // wave-uniform
     PLHIP_STAMP(STAMP_SLOTS - 3);  // epilogue instructions issued
     wait_vmcnt<0>();

@@ -367,6 +367,26 @@ const char* plhip_conv_impl_name(const plhip_conv_desc* d) {
   return "conv_im2col_gemm_int8_mfma32x32x32";
 }
 
+// The output-kind / scale / activation checks of a compute entry point, in this order, `who` = its name in the texts.
+// gap_ok: PLHIP_OUT_F32_GAP is one of its kinds; scale_name: what it calls the scale; act: nullptr = no activation enum to check
+static plhip_status check_out_scale_act(plhip_ctx* ctx, const char* who, plhip_out_kind out, bool gap_ok, const float* scale,
+                                        const char* scale_name, const int* act, const char* act_name = "activation") {
+  if (out != PLHIP_OUT_I32_ACC && out != PLHIP_OUT_F32 && out != PLHIP_OUT_I8 && !(gap_ok && out == PLHIP_OUT_F32_GAP))
+    return fail(ctx, PLHIP_ERR_INVALID, "%s: bad out kind", who);
+  if (out != PLHIP_OUT_I32_ACC && !scale) return fail(ctx, PLHIP_ERR_INVALID, "%s: %s required", who, scale_name);
+  if (act && *act != PLHIP_ACT_NONE && *act != PLHIP_ACT_RELU && *act != PLHIP_ACT_RELU6 && *act != PLHIP_ACT_LEAKY_RELU)
+    return fail(ctx, PLHIP_ERR_UNSUPPORTED, "%s: unsupported %s", who, act_name);
+  return PLHIP_OK;
+}
+
+// the shape half of a stem kernel's arguments; the pointers and the fused front / tail are the caller's
+static plhip::DirectS2Args direct_s2_args(const plhip_conv_desc* d, const ConvGeom& g) {
+  plhip::DirectS2Args a = plhip::DirectS2Args();
+  a.n = d->n; a.cin = d->cin; a.h = d->h; a.w = d->w; a.cout = d->cout; a.coutp = rup(d->cout, 4);
+  a.oh = g.oh; a.ow = g.ow; a.pt = d->pad[0]; a.pl = d->pad[2]; a.act = d->act; a.alpha = d->act_alpha;
+  return a;
+}
+
 struct ConvTail {  // fused graph tail of an fp32-output conv (plhip_conv2d_int8_fused)
   const float* residual;
   int residual_relu;
@@ -381,11 +401,7 @@ static plhip_status conv2d_impl(plhip_ctx* ctx, const plhip_conv_desc* d, const 
   const bool y_opt = tail && tail->y_i8;  // the fp32 tensor itself may be dropped when only the int8 copy is consumed
   if (!ctx || !x || !w_packed || (!y && !y_opt)) return fail(ctx, PLHIP_ERR_INVALID, "plhip_conv2d_int8: null argument");
   if (!conv_geom(d, &g)) return fail(ctx, PLHIP_ERR_INVALID, "plhip_conv2d_int8: bad conv descriptor");
-  if (out != PLHIP_OUT_I32_ACC && out != PLHIP_OUT_F32 && out != PLHIP_OUT_I8)
-    return fail(ctx, PLHIP_ERR_INVALID, "plhip_conv2d_int8: bad out kind");
-  if (out != PLHIP_OUT_I32_ACC && !scale) return fail(ctx, PLHIP_ERR_INVALID, "plhip_conv2d_int8: scale required");
-  if (d->act != PLHIP_ACT_NONE && d->act != PLHIP_ACT_RELU && d->act != PLHIP_ACT_RELU6 && d->act != PLHIP_ACT_LEAKY_RELU)
-    return fail(ctx, PLHIP_ERR_UNSUPPORTED, "plhip_conv2d_int8: unsupported activation");
+  if (plhip_status st = check_out_scale_act(ctx, "plhip_conv2d_int8", out, false, scale, "scale", &d->act)) return st;
   if ((size_t)d->n * g.Np >= ((size_t)1 << 31) - 256 || (size_t)d->cin * d->h * d->w >= ((size_t)1 << 31) ||
       (size_t)d->cout * g.N >= ((size_t)1 << 31))
     return fail(ctx, PLHIP_ERR_UNSUPPORTED, "plhip_conv2d_int8: tensor too large for 32-bit column index");
@@ -397,28 +413,24 @@ static plhip_status conv2d_impl(plhip_ctx* ctx, const plhip_conv_desc* d, const 
   const bool has_tail = t_res || t_y2;
   if (g.impl == IMPL_DIRECT_3X3S2) {
     if (has_tail) return fail(ctx, PLHIP_ERR_UNSUPPORTED, "plhip_conv2d_int8_fused: the direct 3x3 s2 stem has no fused tail");
-    plhip::DirectS2Args a;
+    plhip::DirectS2Args a = direct_s2_args(d, g);
     a.x = x;
     a.wp = (const uint32_t*)w_packed;
     a.y = y;
     a.scale = scale;
     a.bias = bias;
-    a.n = d->n; a.cin = d->cin; a.h = d->h; a.w = d->w; a.cout = d->cout; a.coutp = rup(d->cout, 4);
-    a.oh = g.oh; a.ow = g.ow; a.pt = d->pad[0]; a.pl = d->pad[2]; a.act = d->act; a.alpha = d->act_alpha;
     plhip::launch_conv3x3s2_direct(a, (int)out, ctx->stream);
     LAUNCHCHK(ctx, "conv3x3s2_direct");
     return PLHIP_OK;
   }
   if (g.impl == IMPL_STEM_7X7S2) {
     if (!aligned(w_packed, 16)) return fail(ctx, PLHIP_ERR_INVALID, "plhip_conv2d_int8: packed weights must be 16-byte aligned");
-    plhip::DirectS2Args a;
+    plhip::DirectS2Args a = direct_s2_args(d, g);
     a.x = x;
     a.wp = (const uint32_t*)w_packed;
     a.y = y;
     a.scale = scale;
     a.bias = bias;
-    a.n = d->n; a.cin = d->cin; a.h = d->h; a.w = d->w; a.cout = d->cout; a.coutp = rup(d->cout, 4);
-    a.oh = g.oh; a.ow = g.ow; a.pt = d->pad[0]; a.pl = d->pad[2]; a.act = d->act; a.alpha = d->act_alpha;
     a.res = t_res; a.res_relu = t_relu; a.y2 = t_y2; a.inv_scale2 = t_inv;
     const size_t esz_s = out == PLHIP_OUT_I8 ? 1 : 4;
     const bool vec = aligned(y, 4 * esz_s) && aligned(t_res, 16) && aligned(t_y2, 4);
@@ -609,10 +621,23 @@ plhip_status plhip_conv2d_int8_fused(plhip_ctx* ctx, const plhip_conv_desc* d, c
 static bool calib_conv_args(const plhip_conv_desc* d, plhip::DirectS2Args* a) {
   ConvGeom g;
   if (!d || !conv_geom(d, &g) || g.impl != IMPL_DIRECT_3X3S2) return false;
-  *a = plhip::DirectS2Args();
-  a->n = d->n; a->cin = d->cin; a->h = d->h; a->w = d->w; a->cout = d->cout; a->coutp = rup(d->cout, 4);
-  a->oh = g.oh; a->ow = g.ow; a->pt = d->pad[0]; a->pl = d->pad[2]; a->act = d->act; a->alpha = d->act_alpha;
+  *a = direct_s2_args(d, g);
   return plhip::conv3x3s2_f32in_supported(*a);
+}
+
+// The calib and image stems behind their envelope checks.  false: a pointer is misaligned (in: in_align bytes, w_packed: 16, y: 4
+// elements); else a's pointers and quantiser are set and *afrag = the MFMA A fragments inside the packed block.
+static bool fused_stem_tail(plhip::DirectS2Args* a, const void* in, size_t in_align, float calib_scale, const void* w_packed,
+                            const float* scale, const float* bias, void* y, plhip_out_kind out, const int8_t** afrag) {
+  const size_t esz = out == PLHIP_OUT_I8 ? 1 : 4;
+  if (!aligned(in, in_align) || !aligned(y, 4 * esz) || !aligned(w_packed, 16)) return false;
+  a->x_inv_scale = 1.f / calib_scale;  // type_trans.cc:45
+  a->wp = (const uint32_t*)w_packed;
+  a->y = y;
+  a->scale = scale;
+  a->bias = bias;
+  *afrag = reinterpret_cast<const int8_t*>(w_packed) + plhip::conv3x3s2_dot4_bytes(a->cin, a->cout);
+  return true;
 }
 
 int plhip_conv2d_calib_supported(const plhip_conv_desc* d) {
@@ -623,23 +648,13 @@ int plhip_conv2d_calib_supported(const plhip_conv_desc* d) {
 plhip_status plhip_conv2d_calib_int8(plhip_ctx* ctx, const plhip_conv_desc* d, const float* x_f32, float calib_scale,
                                      const void* w_packed, const float* scale, const float* bias, void* y, plhip_out_kind out) {
   if (!ctx || !x_f32 || !w_packed || !y || !(calib_scale > 0.f)) return fail(ctx, PLHIP_ERR_INVALID, "plhip_conv2d_calib_int8: null / bad argument");
-  if (out != PLHIP_OUT_I32_ACC && out != PLHIP_OUT_F32 && out != PLHIP_OUT_I8)
-    return fail(ctx, PLHIP_ERR_INVALID, "plhip_conv2d_calib_int8: bad out kind");
-  if (out != PLHIP_OUT_I32_ACC && !scale) return fail(ctx, PLHIP_ERR_INVALID, "plhip_conv2d_calib_int8: scale required");
-  if (d && d->act != PLHIP_ACT_NONE && d->act != PLHIP_ACT_RELU && d->act != PLHIP_ACT_RELU6 && d->act != PLHIP_ACT_LEAKY_RELU)
-    return fail(ctx, PLHIP_ERR_UNSUPPORTED, "plhip_conv2d_calib_int8: unsupported activation");
+  if (plhip_status st = check_out_scale_act(ctx, "plhip_conv2d_calib_int8", out, false, scale, "scale", d ? &d->act : nullptr)) return st;
   plhip::DirectS2Args a;
   if (!calib_conv_args(d, &a)) return fail(ctx, PLHIP_ERR_UNSUPPORTED, "plhip_conv2d_calib_int8: shape outside the fused stem");
-  const size_t esz = out == PLHIP_OUT_I8 ? 1 : 4;
-  if (!aligned(x_f32, 16) || !aligned(y, 4 * esz) || !aligned(w_packed, 16))
+  const int8_t* afrag;
+  if (!fused_stem_tail(&a, x_f32, 16, calib_scale, w_packed, scale, bias, y, out, &afrag))
     return fail(ctx, PLHIP_ERR_INVALID, "plhip_conv2d_calib_int8: x / w_packed must be 16-byte aligned, y 4 elements");
   a.xf = x_f32;
-  a.x_inv_scale = 1.f / calib_scale;  // type_trans.cc:45
-  a.wp = (const uint32_t*)w_packed;
-  a.y = y;
-  a.scale = scale;
-  a.bias = bias;
-  const int8_t* afrag = reinterpret_cast<const int8_t*>(w_packed) + plhip::conv3x3s2_dot4_bytes(d->cin, d->cout);
   plhip::launch_conv3x3s2_f32in(a, afrag, (int)out, ctx->stream);
   LAUNCHCHK(ctx, "conv3x3s2_f32in");
   return PLHIP_OK;
@@ -689,25 +704,15 @@ plhip_status plhip_conv2d_image_int8(plhip_ctx* ctx, const plhip_conv_desc* d, c
                                      float calib_scale, const void* w_packed, const float* scale, const float* bias, void* y,
                                      plhip_out_kind out) {
   if (!ctx || !src || !w_packed || !y || !(calib_scale > 0.f)) return fail(ctx, PLHIP_ERR_INVALID, "plhip_conv2d_image_int8: null / bad argument");
-  if (out != PLHIP_OUT_I32_ACC && out != PLHIP_OUT_F32 && out != PLHIP_OUT_I8)
-    return fail(ctx, PLHIP_ERR_INVALID, "plhip_conv2d_image_int8: bad out kind");
-  if (out != PLHIP_OUT_I32_ACC && !scale) return fail(ctx, PLHIP_ERR_INVALID, "plhip_conv2d_image_int8: scale required");
-  if (d && d->act != PLHIP_ACT_NONE && d->act != PLHIP_ACT_RELU && d->act != PLHIP_ACT_RELU6 && d->act != PLHIP_ACT_LEAKY_RELU)
-    return fail(ctx, PLHIP_ERR_UNSUPPORTED, "plhip_conv2d_image_int8: unsupported activation");
+  if (plhip_status st = check_out_scale_act(ctx, "plhip_conv2d_image_int8", out, false, scale, "scale", d ? &d->act : nullptr)) return st;
   plhip::DirectS2Args a;
   plhip::ImageArgs im;
   if (!image_args(img, src, &im)) return fail(ctx, PLHIP_ERR_INVALID, "plhip_conv2d_image_int8: bad image descriptor");
   if (!calib_conv_args(d, &a) || !plhip::conv3x3s2_u8in_supported(a, im))
     return fail(ctx, PLHIP_ERR_UNSUPPORTED, "plhip_conv2d_image_int8: shape outside the fused stem");
-  const size_t esz = out == PLHIP_OUT_I8 ? 1 : 4;
-  if (!aligned(src, 4) || !aligned(y, 4 * esz) || !aligned(w_packed, 16))
+  const int8_t* afrag;
+  if (!fused_stem_tail(&a, src, 4, calib_scale, w_packed, scale, bias, y, out, &afrag))
     return fail(ctx, PLHIP_ERR_INVALID, "plhip_conv2d_image_int8: src must be 4-byte aligned, w_packed 16, y 4 elements");
-  a.x_inv_scale = 1.f / calib_scale;  // type_trans.cc:45
-  a.wp = (const uint32_t*)w_packed;
-  a.y = y;
-  a.scale = scale;
-  a.bias = bias;
-  const int8_t* afrag = reinterpret_cast<const int8_t*>(w_packed) + plhip::conv3x3s2_dot4_bytes(d->cin, d->cout);
   plhip::launch_conv3x3s2_u8in(a, im, afrag, (int)out, ctx->stream);
   LAUNCHCHK(ctx, "conv3x3s2_u8in");
   return PLHIP_OK;
@@ -721,11 +726,7 @@ plhip_status plhip_depthwise_conv_int8(plhip_ctx* ctx, const plhip_conv_desc* d,
   if (!conv_geom(d, &g)) return fail(ctx, PLHIP_ERR_INVALID, "plhip_depthwise_conv_int8: bad conv descriptor");
   if (d->groups != d->cin || d->cin != d->cout)
     return fail(ctx, PLHIP_ERR_UNSUPPORTED, "plhip_depthwise_conv_int8: needs groups == cin == cout");
-  if (out != PLHIP_OUT_I32_ACC && out != PLHIP_OUT_F32 && out != PLHIP_OUT_I8)
-    return fail(ctx, PLHIP_ERR_INVALID, "plhip_depthwise_conv_int8: bad out kind");
-  if (out != PLHIP_OUT_I32_ACC && !scale) return fail(ctx, PLHIP_ERR_INVALID, "plhip_depthwise_conv_int8: scale required");
-  if (d->act != PLHIP_ACT_NONE && d->act != PLHIP_ACT_RELU && d->act != PLHIP_ACT_RELU6 && d->act != PLHIP_ACT_LEAKY_RELU)
-    return fail(ctx, PLHIP_ERR_UNSUPPORTED, "plhip_depthwise_conv_int8: unsupported activation");
+  if (plhip_status st = check_out_scale_act(ctx, "plhip_depthwise_conv_int8", out, false, scale, "scale", &d->act)) return st;
   const size_t esz = out == PLHIP_OUT_I8 ? 1 : 4;
   if (!aligned(y, 4 * esz) && (g.ow & 3) == 0)
     return fail(ctx, PLHIP_ERR_UNSUPPORTED, "plhip_depthwise_conv_int8: output pointer must be 4-element aligned");
@@ -827,9 +828,7 @@ plhip_status plhip_dwpw_fused_int8(plhip_ctx* ctx, const plhip_conv_desc* dw, co
                                    plhip_out_kind out) {
   if (!ctx || !dw || !x || !dw_w_oihw || !dw_scale || !pw_w_packed || !y || pw_cout < 1)
     return fail(ctx, PLHIP_ERR_INVALID, "plhip_dwpw_fused_int8: null / bad argument");
-  if (out != PLHIP_OUT_I32_ACC && out != PLHIP_OUT_F32 && out != PLHIP_OUT_I8 && out != PLHIP_OUT_F32_GAP)
-    return fail(ctx, PLHIP_ERR_INVALID, "plhip_dwpw_fused_int8: bad out kind");
-  if (out != PLHIP_OUT_I32_ACC && !pw_scale) return fail(ctx, PLHIP_ERR_INVALID, "plhip_dwpw_fused_int8: pw_scale required");
+  if (plhip_status st = check_out_scale_act(ctx, "plhip_dwpw_fused_int8", out, true, pw_scale, "pw_scale", nullptr)) return st;
   plhip::FusedArgs a;
   const char* why;
   if (!dwpw_plan(dw, pw_cout, out, &a, &why)) {
@@ -896,11 +895,8 @@ plhip_status plhip_dw_conv1x1_fused_int8(plhip_ctx* ctx, const plhip_conv_desc* 
   const int has_tail = residual || y_i8;
   if (!ctx || !dw || !x || !dw_w_oihw || !dw_scale || !pw_w_packed || (!y && !y_i8) || pw_cout < 1)
     return fail(ctx, PLHIP_ERR_INVALID, "plhip_dw_conv1x1_fused_int8: null / bad argument");
-  if (out != PLHIP_OUT_I32_ACC && out != PLHIP_OUT_F32 && out != PLHIP_OUT_I8)
-    return fail(ctx, PLHIP_ERR_INVALID, "plhip_dw_conv1x1_fused_int8: bad out kind");
-  if (out != PLHIP_OUT_I32_ACC && !pw_scale) return fail(ctx, PLHIP_ERR_INVALID, "plhip_dw_conv1x1_fused_int8: pw_scale required");
-  if (pw_act != PLHIP_ACT_NONE && pw_act != PLHIP_ACT_RELU && pw_act != PLHIP_ACT_RELU6 && pw_act != PLHIP_ACT_LEAKY_RELU)
-    return fail(ctx, PLHIP_ERR_UNSUPPORTED, "plhip_dw_conv1x1_fused_int8: unsupported 1x1 activation");
+  if (plhip_status st = check_out_scale_act(ctx, "plhip_dw_conv1x1_fused_int8", out, false, pw_scale, "pw_scale", &pw_act, "1x1 activation"))
+    return st;
   plhip::DwConvArgs a;
   const char* why;
   if (!dw_conv1x1_plan(dw, pw_cout, out, has_tail, &a, &why)) return fail(ctx, PLHIP_ERR_UNSUPPORTED, "plhip_dw_conv1x1_fused_int8: %s", why);
@@ -943,9 +939,7 @@ plhip_status plhip_pack_fc_weights(plhip_ctx* ctx, int k, int n, const int8_t* w
 plhip_status plhip_fc_int8(plhip_ctx* ctx, int m, int k, int n, const int8_t* x, const void* w_packed, const float* scale,
                            const float* bias, int relu, void* y, plhip_out_kind out) {
   if (!ctx || !x || !w_packed || !y || m < 1 || k < 1 || n < 1) return fail(ctx, PLHIP_ERR_INVALID, "plhip_fc_int8: bad argument");
-  if (out != PLHIP_OUT_I32_ACC && out != PLHIP_OUT_F32 && out != PLHIP_OUT_I8)
-    return fail(ctx, PLHIP_ERR_INVALID, "plhip_fc_int8: bad out kind");
-  if (out != PLHIP_OUT_I32_ACC && !scale) return fail(ctx, PLHIP_ERR_INVALID, "plhip_fc_int8: scale required");
+  if (plhip_status st = check_out_scale_act(ctx, "plhip_fc_int8", out, false, scale, "scale", nullptr)) return st;
   if (!aligned(w_packed, 4)) return fail(ctx, PLHIP_ERR_INVALID, "plhip_fc_int8: packed weights must be 4-byte aligned");
   plhip::launch_fc(x, (const int8_t*)w_packed, scale, bias, y, m, k, n, relu, (int)out, ctx->stream);
   LAUNCHCHK(ctx, "fc_i8");
