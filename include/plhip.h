@@ -170,6 +170,39 @@ plhip_status plhip_conv2d_image_int8(plhip_ctx* ctx, const plhip_conv_desc* d, c
                                      float calib_scale, const void* w_packed, const float* scale, const float* bias, void* y,
                                      plhip_out_kind out);
 
+/* ---- uint8 frame input (ImagePreprocess::imageConvert and imageResize on the device) ----
+ * The two steps of ImagePreprocess in front of image_to_tensor (lite/utils/cv/paddle_image_preprocess.cc:44-98): a decoder's or
+ * camera's frame, at its own size, becomes the network-sized interleaved image, or the input tensor itself, without leaving the
+ * device.  Integer arithmetic fully given by the reference's library code; every result is bit-exact.
+ *  - convert (image_convert.cc:175-518): an NV12 / NV21 frame is [n][h * 3 / 2][w] bytes, h rows of Y then h / 2 rows of chroma
+ *    pairs, (u, v) for NV12, (v, u) for NV21, one pair per 2 x 2 luma block; w and h even.  ra = (179 (v - 128)) >> 7,
+ *    ga = (44 (u - 128) + 91 (v - 128)) >> 7, ba = (227 (u - 128)) >> 7; b = clamp(y + ba), g = clamp(y - ga), r = clamp(y + ra);
+ *    pixel bytes b, g, r.  Destination PLHIP_IMG_BGR, or PLHIP_IMG_BGRA with the 4th byte 255; anything else UNSUPPORTED.
+ *  - resize (image_resize.cc:184-926): bilinear with 11-bit weights; per axis plhip_image_resize_tables gives, for each output
+ *    index, a source index s (taps s and s + 1) and weights (c0, c1); source >= 2 per axis.  Per byte k of a pixel:
+ *    rows0 = (S0[sx cs + k] a0 + S0[(sx + 1) cs + k] a1) >> 4, rows1 likewise one row below,
+ *    dst = (((b0 rows0) >> 16) + ((b1 rows1) >> 16) + 2) >> 2.  GRAY / BGR / RGB / BGRA / RGBA, every byte alike; an NV frame is
+ *    converted (b, g, r) tap by tap and resized as BGR, equal to convert then resize.  Equal sizes: a copy.
+ *  - frame_to_tensor: resize, then image_to_tensor (above) of the resized image, in one launch; the resized image is never
+ *    written.  img: the destination (n == the frame's, h, w, means, scales); img->format must be the frame's, or BGR for an NV
+ *    frame.  Equal to plhip_image_convert_u8 -> plhip_image_resize_u8 -> plhip_image_to_tensor_* byte for byte.
+ * NV21 / NV12 are FRAME formats only: plhip_image_desc keeps refusing them.  The tables of a (frame size, image size) pair are
+ * uploaded on the first call that meets it (an allocation and a synchronous copy: make that call before a capture) and kept with
+ * the context.  w_out % 16 == 0 and a 16-byte aligned y take the vector path, anything else a scalar one. */
+enum { PLHIP_IMG_NV21 = 11, PLHIP_IMG_NV12 = 12 }; /* == cv::ImageFormat (lite/utils/cv/cv_enum.h:21-29) */
+typedef struct {
+  int n, h, w;
+  int format; /* plhip_image_format, or PLHIP_IMG_NV21 / PLHIP_IMG_NV12 */
+} plhip_frame_desc;
+/* one axis, host only, no device: ofs[out], coef[out][2].  0, or -1 when in < 2, out < 1 or a pointer is null. */
+int plhip_image_resize_tables(int in, int out, int32_t* ofs, int16_t* coef);
+plhip_status plhip_image_convert_u8(plhip_ctx* ctx, const plhip_frame_desc* src, const uint8_t* x, int dst_format, uint8_t* y);
+plhip_status plhip_image_resize_u8(plhip_ctx* ctx, const plhip_frame_desc* src, const uint8_t* x, int h_out, int w_out, uint8_t* y);
+plhip_status plhip_frame_to_tensor_f32(plhip_ctx* ctx, const plhip_frame_desc* src, const plhip_image_desc* img, const uint8_t* x,
+                                       float* y);
+plhip_status plhip_frame_to_tensor_i8(plhip_ctx* ctx, const plhip_frame_desc* src, const plhip_image_desc* img, const uint8_t* x,
+                                      int8_t* y, float calib_scale);
+
 /* ---- depthwise conv (groups == cin == cout) ----
  * Replaces: DepthwiseConv<kInt8,*>::Run (lite/kernels/arm/conv_depthwise.cc:357-446) ->
  * conv_depthwise_3x3_int8_{fp32,int8} / conv_depthwise_5x5_int8_{fp32,int8}

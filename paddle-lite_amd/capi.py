@@ -29,10 +29,12 @@ EXPORTS = [
     "plhip_pool2d_f32", "plhip_pool2d_max_i8", "plhip_elementwise_add_f32", "plhip_selftest",
     "plhip_debug_set", "plhip_conv2d_calib_supported", "plhip_conv2d_calib_int8",
     "plhip_image_to_tensor_f32", "plhip_image_to_tensor_i8", "plhip_conv2d_image_supported", "plhip_conv2d_image_int8",
+    "plhip_image_resize_tables", "plhip_image_convert_u8", "plhip_image_resize_u8", "plhip_frame_to_tensor_f32", "plhip_frame_to_tensor_i8",
 ]
 
 # plhip_image_format == cv::ImageFormat (lite/utils/cv/paddle_image_preprocess.h)
 IMG_RGBA, IMG_BGRA, IMG_RGB, IMG_BGR, IMG_GRAY = 0, 1, 2, 3, 4
+IMG_NV21, IMG_NV12 = 11, 12  # frame formats only (plhip_frame_desc): lite/utils/cv/cv_enum.h
 IMG_BYTES = {IMG_RGBA: 4, IMG_BGRA: 4, IMG_RGB: 3, IMG_BGR: 3, IMG_GRAY: 1}      # bytes a pixel of the interleaved image has
 IMG_CHANNELS = {IMG_RGBA: 3, IMG_BGRA: 3, IMG_RGB: 3, IMG_BGR: 3, IMG_GRAY: 1}   # channels of the NCHW tensor made from it
 
@@ -63,6 +65,27 @@ def image_desc(n, h, w, fmt, means, scales):
     d.means[:] = [float(v) for v in m[:3]]
     d.scales[:] = [float(v) for v in s[:3]]
     return d
+
+
+class FrameDesc(C.Structure):
+    _fields_ = [("n", C.c_int), ("h", C.c_int), ("w", C.c_int), ("format", C.c_int)]
+
+
+def frame_desc(n, h, w, fmt):
+    """plhip_frame_desc: n frames of h x w in an interleaved IMG_* format ([n, h, w, cs] bytes) or IMG_NV12 / IMG_NV21
+    ([n, h * 3 / 2, w] bytes)."""
+    d = FrameDesc()
+    d.n, d.h, d.w, d.format = n, h, w, fmt
+    return d
+
+
+def resize_tables(n_in, n_out):
+    """plhip_image_resize_tables for one axis (host only): (ofs int32 [n_out], coef int16 [n_out, 2]), or None when refused."""
+    L = load()
+    ofs, coef = np.zeros(max(n_out, 1), np.int32), np.zeros((max(n_out, 1), 2), np.int16)
+    if L.plhip_image_resize_tables(int(n_in), int(n_out), ofs.ctypes.data_as(C.c_void_p), coef.ctypes.data_as(C.c_void_p)) != 0:
+        return None
+    return ofs, coef
 
 
 def conv_desc(n, cin, h, w, cout, kh, kw, pad=(0, 0, 0, 0), stride=(1, 1), dil=(1, 1), groups=1,
@@ -151,6 +174,12 @@ def load():
     L.plhip_conv2d_calib_int8.argtypes = [vp, C.POINTER(ConvDesc), vp, f32, vp, vp, vp, vp, i32]
     L.plhip_image_to_tensor_f32.argtypes = [vp, C.POINTER(ImageDesc), vp, vp]
     L.plhip_image_to_tensor_i8.argtypes = [vp, C.POINTER(ImageDesc), vp, vp, f32]
+    L.plhip_image_resize_tables.argtypes = [i32, i32, vp, vp]
+    L.plhip_image_resize_tables.restype = i32
+    L.plhip_image_convert_u8.argtypes = [vp, C.POINTER(FrameDesc), vp, i32, vp]
+    L.plhip_image_resize_u8.argtypes = [vp, C.POINTER(FrameDesc), vp, i32, i32, vp]
+    L.plhip_frame_to_tensor_f32.argtypes = [vp, C.POINTER(FrameDesc), C.POINTER(ImageDesc), vp, vp]
+    L.plhip_frame_to_tensor_i8.argtypes = [vp, C.POINTER(FrameDesc), C.POINTER(ImageDesc), vp, vp, f32]
     L.plhip_conv2d_image_supported.argtypes = [C.POINTER(ConvDesc), C.POINTER(ImageDesc)]
     L.plhip_conv2d_image_supported.restype = i32
     L.plhip_conv2d_image_int8.argtypes = [vp, C.POINTER(ConvDesc), C.POINTER(ImageDesc), vp, f32, vp, vp, vp, vp, i32]
@@ -315,6 +344,43 @@ class Context:
             y = self.to_host(dy, shape, np.int8)
         self.free(dx), self.free(dy)
         return y
+
+    def image_convert(self, frame, src_u8, dst_format=IMG_BGR):
+        """plhip_image_convert_u8 on a host NV12 / NV21 frame [n, h * 3 / 2, w]: the interleaved image [n, h, w, 3 | 4]."""
+        dx = self.to_device(np.ascontiguousarray(src_u8, np.uint8))
+        shape = (frame.n, frame.h, frame.w, IMG_BYTES.get(dst_format, 4))
+        dy = self.malloc(int(np.prod(shape)))
+        try:
+            self.check(self.L.plhip_image_convert_u8(self.h, C.byref(frame), dx, int(dst_format), dy), "image_convert_u8")
+            return self.to_host(dy, shape, np.uint8)
+        finally:
+            self.free(dx), self.free(dy)
+
+    def image_resize(self, frame, src_u8, h_out, w_out):
+        """plhip_image_resize_u8 on a host frame: the resized interleaved image [n, h_out, w_out, cs] (BGR from an NV frame)."""
+        dx = self.to_device(np.ascontiguousarray(src_u8, np.uint8))
+        shape = (frame.n, h_out, w_out, IMG_BYTES.get(frame.format, 3))
+        dy = self.malloc(max(1, int(np.prod(shape))))
+        try:
+            self.check(self.L.plhip_image_resize_u8(self.h, C.byref(frame), dx, int(h_out), int(w_out), dy), "image_resize_u8")
+            return self.to_host(dy, shape, np.uint8)
+        finally:
+            self.free(dx), self.free(dy)
+
+    def frame_to_tensor(self, frame, img, src_u8, calib_scale=None):
+        """plhip_frame_to_tensor_f32 (calib_scale None) or _i8 on a host frame: the NCHW tensor of the resized image, one launch."""
+        dx = self.to_device(np.ascontiguousarray(src_u8, np.uint8))
+        shape = (img.n, IMG_CHANNELS.get(img.format, 3), img.h, img.w)
+        cnt = max(1, int(np.prod(shape)))
+        dy = self.malloc(cnt * (4 if calib_scale is None else 1))
+        try:
+            if calib_scale is None:
+                self.check(self.L.plhip_frame_to_tensor_f32(self.h, C.byref(frame), C.byref(img), dx, dy), "frame_to_tensor_f32")
+                return self.to_host(dy, shape, np.float32)
+            self.check(self.L.plhip_frame_to_tensor_i8(self.h, C.byref(frame), C.byref(img), dx, dy, float(calib_scale)), "frame_to_tensor_i8")
+            return self.to_host(dy, shape, np.int8)
+        finally:
+            self.free(dx), self.free(dy)
 
     def conv2d_image(self, d, img, src_u8, calib_scale, w, scale, bias, out_kind):
         """plhip_conv2d_image_int8 on host arrays: image_to_tensor + calib[fp32_to_int8](calib_scale) + conv2d in one launch."""

@@ -275,6 +275,44 @@ void launch_image_to_tensor_i8(const ImageArgs& a, int8_t* y, float calib_scale,
 bool conv3x3s2_u8in_supported(const DirectS2Args& a, const ImageArgs& im);
 void launch_conv3x3s2_u8in(const DirectS2Args& a, const ImageArgs& im, const int8_t* afrag, int out, hipStream_t s);
 
+// NV12 / NV21 frame [n][h * 3 / 2][w] -> interleaved BGR / BGRA [n, h, w, 3 | 4] (image_convert.hip); w, h even
+struct NvArgs {
+  const uint8_t* src;
+  int n, h, w;
+  int nv21;  // chroma pair order: 0 = (u, v) NV12, 1 = (v, u) NV21
+};
+void launch_nv_to_bgr(const NvArgs& a, uint8_t* y, int dst_cs, hipStream_t s);
+#ifdef __HIPCC__
+// one pixel of image_convert.cc:451-514: p = {b, g, r}.  Shared by the convert kernel and the fused frame kernel, so that a tap
+// converted while it is fetched is the converted image's byte, bit for bit.
+__device__ __forceinline__ void nv_pixel_bgr(int y, int u, int v, int (&p)[3]) {
+  const int ra = (179 * (v - 128)) >> 7, ga = (44 * (u - 128) + 91 * (v - 128)) >> 7, ba = (227 * (u - 128)) >> 7;
+  const int b = y + ba, g = y - ga, r = y + ra;
+  p[0] = b < 0 ? 0 : (b > 255 ? 255 : b);
+  p[1] = g < 0 ? 0 : (g > 255 ? 255 : g);
+  p[2] = r < 0 ? 0 : (r > 255 ? 255 : r);
+}
+#endif
+
+// bilinear resize of a frame (image_resize.hip): interleaved [n, h_in, w_in, cs] or (nv != 0) an NV12 / NV21 frame converted tap
+// by tap (cs = 3, b g r) -> the uint8 image [n, h_out, w_out, cs], or the normalised NCHW tensor made from it (fp32 / int8)
+struct ResizeArgs {
+  const uint8_t* src;
+  int n, h_in, w_in, h_out, w_out;
+  int cs;  // bytes per pixel of the image that is resized: 1 / 3 / 4
+  int nv;  // 0 = interleaved source, 1 = NV12, 2 = NV21
+  // host-made tables in device memory (plhip_image_resize_tables): per output column source column and (a0, a1), per output row
+  // source row and (b0, b1)
+  const int32_t* xofs;
+  const int16_t* xcoef;
+  const int32_t* yofs;
+  const int16_t* ycoef;
+  float mean[3], scale[3];  // tensor forms: as ImageArgs
+};
+enum { RESIZE_OUT_U8 = 0, RESIZE_OUT_F32 = 1, RESIZE_OUT_I8 = 2 };
+// y: uint8 [n, h_out, w_out, cs] | fp32 / int8 NCHW [n, cs == 1 ? 1 : 3, h_out, w_out]; calib_scale: RESIZE_OUT_I8 only
+void launch_image_resize(const ResizeArgs& a, void* y, int out, float calib_scale, hipStream_t s);
+
 size_t fc_packed_bytes(int k, int n);
 void launch_pack_fc(const int8_t* w_kn, int8_t* wp, int k, int n, hipStream_t s);
 void launch_fc(const int8_t* x, const int8_t* wp, const float* scale, const float* bias, void* y, int m, int k, int n,

@@ -4,6 +4,7 @@
 #include <string.h>
 
 #include "lite/core/mir/fusion/hip_conv_tail_matcher.h"
+#include "lite/kernels/hip/image_frame.h"
 #include "lite/kernels/hip/image_to_tensor.h"
 #include "plhip.h"
 
@@ -31,6 +32,24 @@ void GraphBuilder::FeedImage(const std::string& name, int n, int h, int w, int f
     f.scales[i] = scales[i];
   }
   feeds_.push_back(f);
+}
+
+void GraphBuilder::FeedFrame(const std::string& name, int n, int src_h, int src_w, int src_format, int dst_h, int dst_w,
+                             const float* means, const float* scales) {
+  const bool nv = operators::FrameIsNV(src_format);
+  CHECK(nv || (src_format >= PLHIP_IMG_RGBA && src_format <= PLHIP_IMG_GRAY)) << "FeedFrame: unsupported frame format " << src_format;
+  CHECK(n > 0 && src_h > 0 && src_w > 0 && dst_h > 0 && dst_w > 0) << "FeedFrame: bad frame / image size";
+  CHECK(!nv || (src_h % 2 == 0 && src_w % 2 == 0)) << "FeedFrame: an NV12 / NV21 frame needs even w and h";
+  const bool resized = src_h != dst_h || src_w != dst_w;
+  CHECK(!resized || (src_h >= 2 && src_w >= 2)) << "FeedFrame: a frame that is resized needs at least 2 rows and 2 columns";
+  const int fmt = nv ? static_cast<int>(PLHIP_IMG_BGR) : src_format;
+  FeedImage(name, n, dst_h, dst_w, fmt, means, scales);
+  if (!nv && !resized) return;  // nothing in front of image_to_tensor: an image feed
+  FeedDesc& f = feeds_.back();
+  f.frame_format = src_format;
+  f.frame_h = src_h;
+  f.frame_w = src_w;
+  f.image_dims = operators::FrameDims(n, src_h, src_w, src_format);
 }
 
 GraphOp& GraphBuilder::Add(const std::string& type, const std::vector<std::string>& inputs, const std::string& output) {
@@ -85,10 +104,29 @@ std::vector<GraphBuilder::Step> GraphBuilder::Schedule() {
     s.out = f.name + "/target_trans";
     steps.push_back(s);
     prec[f.name] = f.prec;
+    std::string img = s.out;
+    if (f.frame_format >= 0) {  // FeedFrame: imageConvert (NV only) and imageResize (unequal sizes only) in front
+      if (operators::FrameIsNV(f.frame_format)) {
+        Step c;
+        c.kind = "image_convert";
+        c.in = img;
+        c.out = img = f.name + "/bgr";
+        c.image_feed = static_cast<int>(k);
+        steps.push_back(c);
+      }
+      if (f.frame_h != f.dims[2] || f.frame_w != f.dims[3]) {
+        Step r;
+        r.kind = "image_resize";
+        r.in = img;
+        r.out = img = f.name + "/image";
+        r.image_feed = static_cast<int>(k);
+        steps.push_back(r);
+      }
+    }
     if (f.image_format >= 0) {  // FeedImage: the bytes on the device become the fp32 NCHW tensor the ops name
       Step t;
       t.kind = "image_to_tensor";
-      t.in = s.out;
+      t.in = img;
       t.out = f.name + "/tensor";
       t.image_feed = static_cast<int>(k);
       steps.push_back(t);
@@ -201,6 +239,36 @@ void GraphBuilder::FuseSteps(std::vector<Step>* steps_io) {
       st[i].drop_f32 = t.drop_f32;
       st[i].pool_int8 = t.pool_int8;
     }
+  }
+  // (I) a frame feed's image_resize takes the image_to_tensor behind it over, and with it the image_convert in front (the NV taps are
+  // converted as they are fetched) and, where it is the tensor's only reader (H2's condition), the calib[fp32_to_int8] behind: one
+  // launch, neither the converted frame nor the resized image nor the fp32 tensor is written.  In front of H, which would otherwise
+  // take the image_to_tensor; H1 does not apply to a resized feed.
+  for (size_t i = 0; i < st.size(); ++i) {
+    if (dead[i] || st[i].kind != "image_resize" || uses(st[i].out) != 1) continue;
+    int t = -1, c = -1, k = -1;
+    for (size_t q = 0; q < st.size(); ++q) {
+      if (dead[q]) continue;
+      if (st[q].kind == "image_to_tensor" && st[q].in == st[i].out) t = static_cast<int>(q);
+      if (st[q].kind == "image_convert" && st[q].out == st[i].in) c = static_cast<int>(q);
+    }
+    if (t < 0) continue;
+    st[i].out = st[t].out;
+    st[i].resize_tensor = true;
+    dead[t] = true;
+    if (c >= 0 && uses(st[c].out) == 1) {
+      st[i].in = st[c].in;
+      st[i].resize_nv = true;
+      dead[c] = true;
+    }
+    if (uses(st[i].out) != 1) continue;
+    for (size_t q = 0; q < st.size(); ++q)
+      if (!dead[q] && st[q].kind == "calib_f2i" && st[q].in == st[i].out) k = static_cast<int>(q);
+    if (k < 0) continue;
+    st[i].out = st[k].out;
+    st[i].scale = st[k].scale;
+    st[i].image_int8 = true;
+    dead[k] = true;
   }
   // (H) an image feed's image_to_tensor whose only reader is a calib[fp32_to_int8]: (H1) where that calib's only reader is a conv2d
   // plhip_conv2d_image_supported takes (the 3x3 stride-2 stem), the conv takes both over and reads the uint8 image itself (the fp32
@@ -510,6 +578,19 @@ std::vector<std::string> GraphBuilder::Plan() {
         snprintf(buf, sizeof buf, " scale=%.9g", s.scale);
         l += buf;
       }
+    } else if (s.kind == "image_convert") {
+      l = "image_convert/def in=" + s.in + " out=" + s.out + " src=" + operators::FrameFormatName(feeds_[s.image_feed].frame_format) + " dst=BGR";
+    } else if (s.kind == "image_resize") {
+      const FeedDesc& f = feeds_[s.image_feed];
+      const bool frame_src = s.in == f.name + "/target_trans";  // else: the BGR image an image_convert of its own made
+      l = std::string("image_resize/") + (!s.resize_tensor ? "uint8" : s.image_int8 ? "int8" : "fp32") + " in=" + s.in + " out=" + s.out +
+          " src=" + (frame_src ? operators::FrameFormatName(f.frame_format) : operators::ImageFormatName(f.image_format));
+      snprintf(buf, sizeof buf, " %dx%d->%dx%d", f.frame_h, f.frame_w, static_cast<int>(f.dims[2]), static_cast<int>(f.dims[3]));
+      l += buf;
+      if (s.image_int8) {
+        snprintf(buf, sizeof buf, " scale=%.9g", s.scale);
+        l += buf;
+      }
     } else {
       l = s.kind == "io_copy_h2d" ? "io_copy/host_to_device"
           : s.kind == "io_copy_d2h" ? "io_copy/device_to_host"
@@ -541,6 +622,13 @@ std::vector<std::string> GraphBuilder::Lower(HipPredictor* pred) {
       outs.push_back(s.out);
     } else if (s.kind == "calib_f2i" || s.kind == "calib_i2f") {
       pred->AddCalib(s.in, s.out, s.scale, s.kind == "calib_f2i");
+    } else if (s.kind == "image_convert") {
+      pred->AddImageConvert(s.in, s.out, feeds_[s.image_feed].frame_format, PLHIP_IMG_BGR);
+    } else if (s.kind == "image_resize") {
+      const FeedDesc& f = feeds_[s.image_feed];
+      const bool frame_src = s.in == f.name + "/target_trans";  // else: the BGR image an image_convert of its own made
+      pred->AddImageResize(s.in, s.out, frame_src ? f.frame_format : f.image_format, static_cast<int>(f.dims[2]), static_cast<int>(f.dims[3]),
+                           s.resize_tensor ? f.means : nullptr, f.scales, s.image_int8 ? s.scale : 0.f);
     } else if (s.kind == "image_to_tensor") {
       const FeedDesc& f = feeds_[s.image_feed];
       pred->AddImageToTensor(s.in, s.out, f.image_format, f.means, f.scales, s.image_int8 ? s.scale : 0.f);

@@ -55,6 +55,17 @@ class GraphBuilder {
   // takes  => ONE conv instruction reading the image (plhip_conv2d_image_int8); (H2) otherwise image_to_tensor and its only-reader
   // calib => one image_to_tensor/int8 instruction.
   void FeedImage(const std::string& name, int n, int h, int w, int format, const float* means, const float* scales);
+  // A feed the caller fills with a decoder's or camera's FRAME: n frames of src_h x src_w in src_format, an interleaved
+  // plhip_image_format ([n, src_h, src_w, cs] bytes) or PLHIP_IMG_NV12 / NV21 ([n, src_h * 3 / 2, src_w] bytes, even sizes), brought
+  // to the network's dst_h x dst_w on the device: ImagePreprocess::imageConvert -> imageResize -> image_to_tensor
+  // (lite/utils/cv/paddle_image_preprocess.cc:44-172).  The ops name `name` as the fp32 NCHW tensor [n, c, dst_h, dst_w] exactly as
+  // with FeedImage (means / scales indexed by the byte of the image that is normalised: b, g, r for an NV frame).  Lowering:
+  // io_copy -> image_convert "<name>/bgr" (NV only) -> image_resize "<name>/image" (omitted when the sizes are equal) ->
+  // image_to_tensor "<name>/tensor".  With set_fuse(true), (I), in front of H: image_resize takes the image_to_tensor behind it, the
+  // image_convert in front and, where it is the only reader (H2's condition), the calib[fp32_to_int8] over => ONE instruction, one
+  // launch; H1 does not apply to a resized feed (the stem reads the int8 tensor).  Equal sizes and an interleaved format: FeedImage.
+  void FeedFrame(const std::string& name, int n, int src_h, int src_w, int src_format, int dst_h, int dst_w, const float* means,
+                 const float* scales);
   void Fetch(const std::string& name) { fetches_.push_back(name); }
   // Graph-level fusions of the kHIP target on top of the reference's program (default on; results are bit-identical to
   // the unfused program, every fused value is rounded as the separate instructions round it):
@@ -83,7 +94,7 @@ class GraphBuilder {
  private:
   struct Step {
     int op{-1};              // index into ops_, or -1 for an inserted instruction
-    std::string kind;        // "op", "io_copy_h2d", "io_copy_d2h", "calib_f2i", "calib_i2f", "image_to_tensor"
+    std::string kind;        // "op", "io_copy_h2d", "io_copy_d2h", "calib_f2i", "calib_i2f", "image_to_tensor", "image_convert", "image_resize"
     std::string in, out;
     float scale{0.f};
     bool int8_out{false};
@@ -107,6 +118,8 @@ class GraphBuilder {
     std::string via_in;       // name the calib's int8 result would have had
     int image_feed{-1};       // image_to_tensor of feeds_[image_feed]; on a conv: it took that image_to_tensor over too (H1)
     bool image_int8{false};   // image_to_tensor that took the calib behind it over (H2): int8 output, `scale` the calib's
+    bool resize_tensor{false};  // image_resize that took the image_to_tensor behind it over (I); image_int8: and the calib behind that
+    bool resize_nv{false};      // ... and the image_convert in front: its source is the NV frame itself
   };
   std::vector<Step> Schedule();
   void FuseSteps(std::vector<Step>* steps);
@@ -117,6 +130,8 @@ class GraphBuilder {
     int image_format{-1};              // FeedImage: the host variable is the uint8 image, `dims` the NCHW tensor made from it
     std::vector<int64_t> image_dims;   // [n, h, w, cs]
     float means[3]{0.f, 0.f, 0.f}, scales[3]{1.f, 1.f, 1.f};
+    int frame_format{-1};              // FeedFrame: the host variable is the frame (image_dims = its dims), image_format what is normalised
+    int frame_h{0}, frame_w{0};
   };
   bool fuse_{true};
   int fuse_dwpw_{2};

@@ -2,6 +2,7 @@
 #include "lite/api/hip_predictor.h"
 
 #include "lite/kernels/hip/conv_fusion.h"
+#include "lite/kernels/hip/image_frame.h"
 #include "lite/kernels/hip/image_to_tensor.h"
 #include "plhip.h"
 
@@ -89,6 +90,35 @@ void HipPredictor::AddImageToTensor(const std::string& in, const std::string& ou
   p.int8_out = calib_scale > 0.f;
   p.calib_scale = p.int8_out ? calib_scale : 1.f;
   Emit(op, PickKernel("image_to_tensor", Place(TARGET(kHIP), PRECISION(kAny)), p.int8_out ? "int8" : "fp32"));
+}
+
+void HipPredictor::AddImageConvert(const std::string& in, const std::string& out, int src_format, int dst_format) {
+  auto op = std::make_shared<operators::ImageConvertOp>();
+  auto& p = op->mutable_param();
+  p.x = Var(in);
+  p.output = Var(out);
+  p.src_format = src_format;
+  p.dst_format = dst_format;
+  Emit(op, PickKernel("image_convert", Place(TARGET(kHIP), PRECISION(kAny)), "def"));
+}
+
+void HipPredictor::AddImageResize(const std::string& in, const std::string& out, int frame_format, int out_h, int out_w,
+                                  const float* means, const float* scales, float calib_scale) {
+  auto op = std::make_shared<operators::ImageResizeOp>();
+  auto& p = op->mutable_param();
+  p.x = Var(in);
+  p.output = Var(out);
+  p.format = frame_format;
+  p.out_h = out_h;
+  p.out_w = out_w;
+  p.to_tensor = means != nullptr;
+  for (int i = 0; i < 3 && p.to_tensor; ++i) {
+    p.means[i] = means[i];
+    p.scales[i] = scales[i];
+  }
+  p.int8_out = p.to_tensor && calib_scale > 0.f;
+  p.calib_scale = p.int8_out ? calib_scale : 1.f;
+  Emit(op, PickKernel("image_resize", Place(TARGET(kHIP), PRECISION(kAny)), !p.to_tensor ? "uint8" : p.int8_out ? "int8" : "fp32"));
 }
 
 void HipPredictor::AddConv(const std::string& op_type, const std::string& in, const std::string& out, const int8_t* w,

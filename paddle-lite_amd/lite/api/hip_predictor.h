@@ -68,6 +68,11 @@ class HipPredictor {
   // calib[fp32_to_int8](calib_scale) behind it folded in (calib_scale > 0)
   void AddImageToTensor(const std::string& in, const std::string& out, int format, const float* means, const float* scales,
                         float calib_scale);
+  // image_convert / image_resize (lite/kernels/hip/image_frame.h): the frame feed's instructions.  AddImageResize: frame_format may be
+  // NV12 / NV21 (converted in the same launch); means != nullptr folds the image_to_tensor behind it in, calib_scale > 0 the calib too
+  void AddImageConvert(const std::string& in, const std::string& out, int src_format, int dst_format);
+  void AddImageResize(const std::string& in, const std::string& out, int frame_format, int out_h, int out_w, const float* means,
+                      const float* scales, float calib_scale);
   void AddConv(const std::string& op_type, const std::string& in, const std::string& out, const int8_t* w,
                const std::vector<int64_t>& w_dims, const float* bias, const ConvAttrs& attrs);
   void AddFc(const std::string& in, const std::string& out, const int8_t* w, int k, int n, const float* bias,

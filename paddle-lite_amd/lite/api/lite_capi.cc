@@ -142,6 +142,13 @@ int pllite_graph_feed_image(pllite_predictor* p, const char* name, int n, int h,
     p->graph.FeedImage(name, n, h, w, format, means, scales);
   });
 }
+int pllite_graph_feed_frame(pllite_predictor* p, const char* name, int n, int src_h, int src_w, int src_format, int dst_h, int dst_w,
+                            const float* means, const float* scales) {
+  return guarded([&] {
+    CHECK(means && scales) << "pllite_graph_feed_frame: means / scales required";
+    p->graph.FeedFrame(name, n, src_h, src_w, src_format, dst_h, dst_w, means, scales);
+  });
+}
 int pllite_graph_conv(pllite_predictor* p, const char* op_type, const char* in, const char* out, const int8_t* w,
                       const int64_t* w_dims, const float* bias, const int* strides, const int* paddings, int n_paddings,
                       const int* dilations, int groups, int act, float act_coef, float input_scale,

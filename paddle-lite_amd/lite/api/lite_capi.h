@@ -47,6 +47,11 @@ int pllite_graph_feed(pllite_predictor* p, const char* name, const int64_t* dims
  * as the fp32 NCHW tensor; pllite_set_input(name, bytes) takes the image's n * h * w * cs bytes. */
 int pllite_graph_feed_image(pllite_predictor* p, const char* name, int n, int h, int w, int format, const float* means,
                             const float* scales);
+/* A feed that takes a decoder's / camera's frame (GraphBuilder::FeedFrame): n frames of src_h x src_w in src_format (a
+ * plhip_image_format, or PLHIP_IMG_NV12 / NV21), converted and resized to dst_h x dst_w on the device and normalised like an image
+ * feed.  pllite_set_input(name, bytes) takes the frames' bytes: n * src_h * src_w * cs, or n * src_h * 3 / 2 * src_w for NV. */
+int pllite_graph_feed_frame(pllite_predictor* p, const char* name, int n, int src_h, int src_w, int src_format, int dst_h, int dst_w,
+                            const float* means, const float* scales);
 int pllite_graph_conv(pllite_predictor* p, const char* op_type, const char* in, const char* out, const int8_t* w,
                       const int64_t* w_dims, const float* bias, const int* strides, const int* paddings, int n_paddings,
                       const int* dilations, int groups, int act, float act_coef, float input_scale,

@@ -5,6 +5,7 @@
 //   elementwise_add, fusion_elementwise_add_activation (relu), fp32   lite/kernels/arm/elementwise_compute.cc:182-207
 //   softmax fp32                          lite/kernels/arm/softmax_compute.cc
 #include "lite/core/op_registry.h"
+#include "lite/kernels/hip/image_frame.h"
 #include "lite/kernels/hip/image_to_tensor.h"
 #include "lite/operators/op_params.h"
 #include "plhip.h"
@@ -68,6 +69,73 @@ class ImageToTensorCompute : public KernelLite<TARGET(kHIP), PRECISION(kAny)> {
   }
   void SetProfileRuntimeKernelInfo(profile::OpCharacter* ch) override {
     ch->kernel_func_name = this->Param<operators::ImageToTensorParam>().int8_out ? "image_to_tensor_int8_hip" : "image_to_tensor_fp32_hip";
+  }
+};
+
+// image_convert / image_resize (image_frame.h): ImagePreprocess::imageConvert and imageResize (paddle_image_preprocess.cc:44-98 ->
+// image_convert.cc, image_resize.cc) on the device, in front of image_to_tensor.
+static plhip_frame_desc FrameDescOf(const lite::Tensor* x, int format) {
+  const auto d = x->dims();
+  plhip_frame_desc f{};
+  f.n = static_cast<int>(d[0]);
+  f.h = static_cast<int>(operators::FrameIsNV(format) ? d[1] / 3 * 2 : d[1]);
+  f.w = static_cast<int>(d[2]);
+  f.format = format;
+  return f;
+}
+
+class ImageConvertCompute : public KernelLite<TARGET(kHIP), PRECISION(kAny)> {
+ public:
+  void Run() override {
+    auto& param = this->Param<operators::ImageConvertParam>();
+    auto& ctx = this->ctx_->As<HIPContext>();
+    CHECK(param.x->target() == TARGET(kHIP)) << "image_convert: the frame must live on the HIP device (io_copy missing?)";
+    const plhip_frame_desc f = FrameDescOf(param.x, param.src_format);
+    uint8_t* y = static_cast<uint8_t*>(param.output->mutable_data(TARGET(kHIP), static_cast<size_t>(param.output->numel())));
+    param.output->set_precision(PRECISION(kUInt8));
+    HIP_CALL(ctx.ctx(), plhip_image_convert_u8(ctx.ctx(), &f, static_cast<const uint8_t*>(param.x->raw_data()), param.dst_format, y));
+  }
+  void SetProfileRuntimeKernelInfo(profile::OpCharacter* ch) override {
+    ch->kernel_func_name = this->Param<operators::ImageConvertParam>().src_format == PLHIP_IMG_NV21 ? "nv21_to_bgr_u8_hip" : "nv12_to_bgr_u8_hip";
+  }
+};
+
+// aliases: uint8 = the resized image; fp32 / int8 = with the image_to_tensor (and the calib[fp32_to_int8]) behind it folded in, one
+// launch, bit-identical to the separate instructions.  An NV12 / NV21 frame is converted tap by tap in the same launch.
+class ImageResizeCompute : public KernelLite<TARGET(kHIP), PRECISION(kAny)> {
+ public:
+  void Run() override {
+    auto& param = this->Param<operators::ImageResizeParam>();
+    auto& ctx = this->ctx_->As<HIPContext>();
+    CHECK(param.x->target() == TARGET(kHIP)) << "image_resize: the frame must live on the HIP device (io_copy missing?)";
+    const plhip_frame_desc f = FrameDescOf(param.x, param.format);
+    const uint8_t* src = static_cast<const uint8_t*>(param.x->raw_data());
+    if (!param.to_tensor) {
+      uint8_t* y = static_cast<uint8_t*>(param.output->mutable_data(TARGET(kHIP), static_cast<size_t>(param.output->numel())));
+      param.output->set_precision(PRECISION(kUInt8));
+      HIP_CALL(ctx.ctx(), plhip_image_resize_u8(ctx.ctx(), &f, src, param.out_h, param.out_w, y));
+      return;
+    }
+    plhip_image_desc img{};
+    img.n = f.n;
+    img.h = param.out_h;
+    img.w = param.out_w;
+    img.format = operators::FrameIsNV(param.format) ? static_cast<int>(PLHIP_IMG_BGR) : param.format;
+    for (int i = 0; i < 3; ++i) {
+      img.means[i] = param.means[i];
+      img.scales[i] = param.scales[i];
+    }
+    if (param.int8_out) {
+      HIP_CALL(ctx.ctx(), plhip_frame_to_tensor_i8(ctx.ctx(), &f, &img, src, param.output->mutable_data<int8_t>(TARGET(kHIP)), param.calib_scale));
+    } else {
+      HIP_CALL(ctx.ctx(), plhip_frame_to_tensor_f32(ctx.ctx(), &f, &img, src, param.output->mutable_data<float>(TARGET(kHIP))));
+    }
+  }
+  void SetProfileRuntimeKernelInfo(profile::OpCharacter* ch) override {
+    auto& param = this->Param<operators::ImageResizeParam>();
+    std::string name = operators::FrameIsNV(param.format) ? (param.format == PLHIP_IMG_NV21 ? "nv21_" : "nv12_") : "";
+    name += !param.to_tensor ? "image_resize_u8_hip" : param.int8_out ? "image_resize_to_tensor_int8_hip" : "image_resize_to_tensor_fp32_hip";
+    ch->kernel_func_name = name;
   }
 };
 
@@ -235,6 +303,22 @@ REGISTER_LITE_KERNEL(image_to_tensor, kHIP, kAny, kNCHW, paddle::lite::kernels::
     .BindOutput("Out", {LiteType::GetTensorTy(TARGET(kHIP), PRECISION(kFloat))})
     .Finalize();
 REGISTER_LITE_KERNEL(image_to_tensor, kHIP, kAny, kNCHW, paddle::lite::kernels::hip::ImageToTensorCompute, int8)
+    .BindInput("X", {LiteType::GetTensorTy(TARGET(kHIP), PRECISION(kUInt8), DATALAYOUT(kAny))})
+    .BindOutput("Out", {LiteType::GetTensorTy(TARGET(kHIP), PRECISION(kInt8))})
+    .Finalize();
+REGISTER_LITE_KERNEL(image_convert, kHIP, kAny, kNCHW, paddle::lite::kernels::hip::ImageConvertCompute, def)
+    .BindInput("X", {LiteType::GetTensorTy(TARGET(kHIP), PRECISION(kUInt8), DATALAYOUT(kAny))})
+    .BindOutput("Out", {LiteType::GetTensorTy(TARGET(kHIP), PRECISION(kUInt8), DATALAYOUT(kAny))})
+    .Finalize();
+REGISTER_LITE_KERNEL(image_resize, kHIP, kAny, kNCHW, paddle::lite::kernels::hip::ImageResizeCompute, uint8)
+    .BindInput("X", {LiteType::GetTensorTy(TARGET(kHIP), PRECISION(kUInt8), DATALAYOUT(kAny))})
+    .BindOutput("Out", {LiteType::GetTensorTy(TARGET(kHIP), PRECISION(kUInt8), DATALAYOUT(kAny))})
+    .Finalize();
+REGISTER_LITE_KERNEL(image_resize, kHIP, kAny, kNCHW, paddle::lite::kernels::hip::ImageResizeCompute, fp32)
+    .BindInput("X", {LiteType::GetTensorTy(TARGET(kHIP), PRECISION(kUInt8), DATALAYOUT(kAny))})
+    .BindOutput("Out", {LiteType::GetTensorTy(TARGET(kHIP), PRECISION(kFloat))})
+    .Finalize();
+REGISTER_LITE_KERNEL(image_resize, kHIP, kAny, kNCHW, paddle::lite::kernels::hip::ImageResizeCompute, int8)
     .BindInput("X", {LiteType::GetTensorTy(TARGET(kHIP), PRECISION(kUInt8), DATALAYOUT(kAny))})
     .BindOutput("Out", {LiteType::GetTensorTy(TARGET(kHIP), PRECISION(kInt8))})
     .Finalize();

@@ -11,6 +11,7 @@ PREC_FLOAT, PREC_INT8, PREC_ANY = 1, 2, 4
 LAYOUT_NCHW, LAYOUT_ANY = 1, 2
 # image formats of graph_feed_image == cv::ImageFormat (lite/utils/cv/paddle_image_preprocess.h) == plhip_image_format
 IMG_RGBA, IMG_BGRA, IMG_RGB, IMG_BGR, IMG_GRAY = 0, 1, 2, 3, 4
+IMG_NV21, IMG_NV12 = 11, 12  # frame formats of graph_feed_frame only
 
 
 class LiteError(RuntimeError):
@@ -50,6 +51,7 @@ def load():
     L.pllite_predictor_create_planner.restype = vp
     L.pllite_graph_feed.argtypes = [vp, cs, C.POINTER(i64), i32, i32]
     L.pllite_graph_feed_image.argtypes = [vp, cs, i32, i32, i32, i32, C.POINTER(f32), C.POINTER(f32)]
+    L.pllite_graph_feed_frame.argtypes = [vp, cs, i32, i32, i32, i32, i32, i32, C.POINTER(f32), C.POINTER(f32)]
     L.pllite_graph_conv.argtypes = [vp, cs, cs, cs, vp, C.POINTER(i64), vp, C.POINTER(i32), C.POINTER(i32), i32,
                                     C.POINTER(i32), i32, i32, f32, f32, vp, i32, cs]
     L.pllite_graph_fc.argtypes = [vp, cs, cs, vp, i32, i32, vp, f32, vp, i32, i32]
@@ -170,6 +172,16 @@ class Predictor:
         m = (C.c_float * 3)(*(list(map(float, means)) + [0.0] * 3)[:3])
         s = (C.c_float * 3)(*(list(map(float, scales)) + [0.0] * 3)[:3])
         self._ck(self.L.pllite_graph_feed_image(self.h, name.encode(), int(n), int(h), int(w), int(fmt), m, s))
+
+    def graph_feed_frame(self, name, n, src_h, src_w, src_fmt, dst_h, dst_w, means, scales):
+        """A feed that takes a decoder's / camera's frame: n frames of src_h x src_w in src_fmt, an interleaved IMG_* format (uint8
+        [n, src_h, src_w, cs]) or IMG_NV12 / IMG_NV21 (uint8 [n, src_h * 3 / 2, src_w]).  Convert, bilinear resize to dst_h x dst_w and
+        image_to_tensor run on the device; the ops name `name` as the NCHW tensor, as with graph_feed_image.  means / scales: per
+        byte of the pixel that is normalised (b, g, r for an NV frame)."""
+        m = (C.c_float * 3)(*(list(map(float, means)) + [0.0] * 3)[:3])
+        s = (C.c_float * 3)(*(list(map(float, scales)) + [0.0] * 3)[:3])
+        self._ck(self.L.pllite_graph_feed_frame(self.h, name.encode(), int(n), int(src_h), int(src_w), int(src_fmt), int(dst_h),
+                                                int(dst_w), m, s))
 
     def graph_conv(self, op_type, src, dst, w, bias, strides, paddings, dilations, groups, act, act_coef, input_scale,
                    weight_scale, padding_algorithm=""):

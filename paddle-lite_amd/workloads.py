@@ -270,10 +270,12 @@ def net_stats(net):
     return macs
 
 
-def emit_graph(pred, net, batch, fuse=True, fuse_dwpw=None, fuse_dwconv=None, image=None):
+def emit_graph(pred, net, batch, fuse=True, fuse_dwpw=None, fuse_dwconv=None, image=None, frame=None):
     """Feed the op list to the predictor's graph mode and lower it.  Returns the host name of the output variable.
     image: None = the input is the normalised fp32 NCHW tensor; dict(format, means, scales) = the input is a decoded uint8 image
     [batch, h, w, cs] of that format (liteapi.IMG_*), normalised on the device (Predictor.graph_feed_image).
+    frame: None = off; dict(h, w, format, means, scales) = the input is a frame batch of h x w in that format (liteapi.IMG_*, NV12 /
+    NV21 included), converted, resized to the network's size and normalised on the device (Predictor.graph_feed_frame).
     fuse=False: the reference program instruction for instruction (no kHIP graph-level fusion).
     fuse_dwpw: None = the builder's default (depthwise -> pointwise pairs the fused kernel takes become one instruction),
     True = every eligible pair (shapes outside the kernel run as two launches inside the instruction), False = none.
@@ -286,7 +288,10 @@ def emit_graph(pred, net, batch, fuse=True, fuse_dwpw=None, fuse_dwconv=None, im
     if fuse_dwconv is not None:
         pred.graph_set_fuse_dwconv(fuse_dwconv)
     c, h, w = net["input_shape"]
-    if image is None:
+    if frame is not None:
+        assert image is None, "emit_graph: image= and frame= exclude each other"
+        pred.graph_feed_frame(net["input"], batch, frame["h"], frame["w"], frame["format"], h, w, frame["means"], frame["scales"])
+    elif image is None:
         pred.graph_feed(net["input"], (batch, c, h, w), liteapi.PREC_FLOAT)
     else:
         pred.graph_feed_image(net["input"], batch, h, w, image["format"], image["means"], image["scales"])
