@@ -299,6 +299,44 @@ plhip_status plhip_pool2d_max_i8(plhip_ctx* ctx, const plhip_pool_desc* d, const
 plhip_status plhip_elementwise_add_f32(plhip_ctx* ctx, const float* x, const float* y, float* out, int64_t count,
                                        int relu);
 
+/* ---- the fp32 ops MobileNetV3 adds (hard_act.hip): the reference's int8 conv fuses relu / relu6 / leaky_relu only
+ * (lite/core/mir/fusion/conv_activation_fuse_pass.cc:26-44), so these run as fp32 ops between the convs ----
+ * plhip_hard_act_f32 replaces HardSwishCompute / HardSigmoidCompute (lite/kernels/arm/activation_compute.cc:150-195,
+ * 319-345) -> act_hard_swish / act_hard_sigmoid<float> (lite/backends/arm/math/activation.cc:716-731, 678-691):
+ *   PLHIP_HARD_SWISH    params {threshold, scale, offset}: min(max(0.f, x + offset), threshold) * x / scale, one add, one
+ *                       multiply, one IEEE division, each rounded to fp32
+ *   PLHIP_HARD_SIGMOID  params {slope, offset, unused}: t = x * slope + offset (two roundings); t < 1 ? t : 1; t > 0 ? t : 0
+ * Outputs: y_f32 (fp32), y_i8 (the calib[fp32_to_int8] with calib_scale behind it, quantised exactly as
+ * plhip_calib_f32_to_i8 does), or both in one launch; at least one is required, calib_scale > 0 with y_i8.  Any count;
+ * 16-byte aligned fp32 pointers and a 4-byte aligned y_i8 take the vector path, anything else the scalar one. */
+typedef enum { PLHIP_HARD_SWISH = 0, PLHIP_HARD_SIGMOID = 1 } plhip_hard_act_kind;
+plhip_status plhip_hard_act_f32(plhip_ctx* ctx, plhip_hard_act_kind kind, const float* params, const float* x, float* y_f32,
+                                int8_t* y_i8, float calib_scale, int64_t count);
+/* elementwise_mul with a per-(image, channel) operand, the squeeze-excite gate: out[n][c][i] = x[n][c][i] * gate[n][c],
+ * i < hw.  Replaces ElementwiseMulCompute's fast-broadcast case pre = 1, n = N * C, post = H * W
+ * (lite/kernels/arm/elementwise_compute.cc:30-84).  hw = 1 is the same-shape product.  Outputs as plhip_hard_act_f32. */
+plhip_status plhip_se_scale_f32(plhip_ctx* ctx, const float* x, const float* gate, int n, int c, int hw, float* y_f32,
+                                int8_t* y_i8, float calib_scale);
+
+/* The excite stage of a squeeze-excite block in ONE launch (se_gate.hip): pooled fp32 [n, c] (what plhip_global_avg_pool_f32
+ * wrote) -> calib[fp32_to_int8](calib_scale) -> conv2d 1x1 c -> cr [int8_out, act1] -> conv2d 1x1 cr -> c [fp32_out, act2] ->
+ * hard_sigmoid(slope, offset) -> gate fp32 [n, c]; bit-identical to the separate calls.  scale / bias are the convs' FOLDED
+ * per-channel arrays exactly as plhip_conv2d_int8 takes them (conv 1: the int8_out form, its output scale is conv 2's input
+ * scale); bias may be NULL.  Envelope (plhip_se_gate_supported): 8 <= c, cr <= 960, activations none / relu / relu6 / leaky.
+ * Packed weights: plhip_se_gate_packed_weight_bytes bytes, 4-byte aligned, made from the two filters [cr][c] and [c][cr]. */
+typedef struct {
+  int n, c, cr;
+  float calib_scale;
+  int act1, act2;            /* plhip_act */
+  float act1_alpha, act2_alpha;
+  float slope, offset;       /* hard_sigmoid */
+} plhip_se_gate_desc;
+int plhip_se_gate_supported(int c, int cr, int act1, int act2);
+size_t plhip_se_gate_packed_weight_bytes(int c, int cr);
+plhip_status plhip_pack_se_gate_weights(plhip_ctx* ctx, int c, int cr, const int8_t* w1_cr_c, const int8_t* w2_c_cr, void* w_packed);
+plhip_status plhip_se_gate_int8(plhip_ctx* ctx, const plhip_se_gate_desc* d, const float* pooled, const void* w_packed,
+                                const float* scale1, const float* bias1, const float* scale2, const float* bias2, float* gate);
+
 /* ---- introspection used by tests: operand-layout self-check of the MFMA tile on this device.
  * Runs a tiny known-answer GEMM through the MFMA path; returns PLHIP_OK iff bit-exact. ---- */
 plhip_status plhip_selftest(plhip_ctx* ctx);

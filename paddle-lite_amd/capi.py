@@ -30,7 +30,14 @@ EXPORTS = [
     "plhip_debug_set", "plhip_conv2d_calib_supported", "plhip_conv2d_calib_int8",
     "plhip_image_to_tensor_f32", "plhip_image_to_tensor_i8", "plhip_conv2d_image_supported", "plhip_conv2d_image_int8",
     "plhip_image_resize_tables", "plhip_image_convert_u8", "plhip_image_resize_u8", "plhip_frame_to_tensor_f32", "plhip_frame_to_tensor_i8",
+    "plhip_hard_act_f32", "plhip_se_scale_f32",
+    "plhip_se_gate_supported", "plhip_se_gate_packed_weight_bytes", "plhip_pack_se_gate_weights", "plhip_se_gate_int8",
 ]
+
+# plhip_hard_act_kind, and the reference's default parameters (lite/operators/op_params.h:406-412)
+HARD_SWISH, HARD_SIGMOID = 0, 1
+HARD_SWISH_DEFAULTS = (6.0, 6.0, 3.0)   # threshold, scale, offset
+HARD_SIGMOID_DEFAULTS = (0.2, 0.5)      # slope, offset
 
 # plhip_image_format == cv::ImageFormat (lite/utils/cv/paddle_image_preprocess.h)
 IMG_RGBA, IMG_BGRA, IMG_RGB, IMG_BGR, IMG_GRAY = 0, 1, 2, 3, 4
@@ -65,6 +72,11 @@ def image_desc(n, h, w, fmt, means, scales):
     d.means[:] = [float(v) for v in m[:3]]
     d.scales[:] = [float(v) for v in s[:3]]
     return d
+
+
+class SeGateDesc(C.Structure):
+    _fields_ = [("n", C.c_int), ("c", C.c_int), ("cr", C.c_int), ("calib_scale", C.c_float), ("act1", C.c_int), ("act2", C.c_int),
+                ("act1_alpha", C.c_float), ("act2_alpha", C.c_float), ("slope", C.c_float), ("offset", C.c_float)]
 
 
 class FrameDesc(C.Structure):
@@ -204,6 +216,13 @@ def load():
     L.plhip_pool2d_f32.argtypes = [vp, C.POINTER(PoolDesc), vp, vp]
     L.plhip_pool2d_max_i8.argtypes = [vp, C.POINTER(PoolDesc), vp, vp]
     L.plhip_elementwise_add_f32.argtypes = [vp, vp, vp, vp, C.c_int64, i32]
+    L.plhip_hard_act_f32.argtypes = [vp, i32, C.POINTER(f32), vp, vp, vp, f32, C.c_int64]
+    L.plhip_se_scale_f32.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, f32]
+    L.plhip_se_gate_supported.argtypes = [i32, i32, i32, i32]
+    L.plhip_se_gate_packed_weight_bytes.argtypes = [i32, i32]
+    L.plhip_se_gate_packed_weight_bytes.restype = C.c_size_t
+    L.plhip_pack_se_gate_weights.argtypes = [vp, i32, i32, vp, vp, vp]
+    L.plhip_se_gate_int8.argtypes = [vp, C.POINTER(SeGateDesc), vp, vp, vp, vp, vp, vp, vp]
     L.plhip_selftest.argtypes = [vp]
     _lib = L
     return L
@@ -571,3 +590,71 @@ class Context:
         o = self.to_host(do, x.shape, np.float32)
         self.free(dx), self.free(dy), self.free(do)
         return o
+
+    def _two_outputs(self, call, x, shape, mode, calib_scale, misalign):
+        """Runs call(dx, dyf, dyq) with the outputs `mode` asks for ("f32", "i8" or "both"); misalign: elements the input and
+        output bases are moved off their allocations' alignment (the scalar path).  Returns (y_f32 or None, y_i8 or None)."""
+        assert mode in ("f32", "i8", "both")
+        cnt = int(np.prod(shape))
+        buf = self.malloc(4 * (x.size + misalign))
+        dx = C.c_void_p(buf.value + 4 * misalign)
+        self.check(self.L.plhip_memcpy_h2d(self.h, dx, x.ctypes.data_as(C.c_void_p), x.nbytes), "h2d")
+        bf = self.malloc(4 * (cnt + misalign)) if mode != "i8" else None
+        bq = self.malloc(cnt + misalign + 4) if mode != "f32" else None
+        dyf = C.c_void_p(bf.value + 4 * misalign) if bf else C.c_void_p()
+        dyq = C.c_void_p(bq.value + misalign) if bq else C.c_void_p()
+        call(dx, dyf, dyq)
+        yf = self.to_host(dyf, shape, np.float32) if bf else None
+        yq = self.to_host(dyq, shape, np.int8) if bq else None
+        for p in (buf, bf, bq):
+            if p:
+                self.free(p)
+        return yf, yq
+
+    def hard_act(self, kind, x, params=None, mode="f32", calib_scale=1.0, misalign=0):
+        """plhip_hard_act_f32: kind HARD_SWISH (params threshold, scale, offset) or HARD_SIGMOID (slope, offset)."""
+        x = np.ascontiguousarray(x, np.float32)
+        if params is None:
+            params = HARD_SWISH_DEFAULTS if kind == HARD_SWISH else HARD_SIGMOID_DEFAULTS
+        pr = (C.c_float * 3)(*(list(map(float, params)) + [0.0] * 3)[:3])
+
+        def call(dx, dyf, dyq):
+            self.check(self.L.plhip_hard_act_f32(self.h, int(kind), pr, dx, dyf, dyq, float(calib_scale), x.size), "hard_act")
+        return self._two_outputs(call, x, x.shape, mode, calib_scale, misalign)
+
+    def se_scale(self, x, gate, mode="f32", calib_scale=1.0, misalign=0):
+        """plhip_se_scale_f32: x [n, c, ...] fp32 times gate [n, c] (any trailing 1s)."""
+        x = np.ascontiguousarray(x, np.float32)
+        gate = np.ascontiguousarray(gate, np.float32)
+        n, c = x.shape[:2]
+        hw = int(np.prod(x.shape[2:]))
+        assert gate.size == n * c
+        dg = self.to_device(gate)
+
+        def call(dx, dyf, dyq):
+            self.check(self.L.plhip_se_scale_f32(self.h, dx, dg, n, c, hw, dyf, dyq, float(calib_scale)), "se_scale")
+        r = self._two_outputs(call, x, x.shape, mode, calib_scale, misalign)
+        self.free(dg)
+        return r
+
+    def se_gate(self, pooled, calib_scale, w1, s1, b1, act1, alpha1, w2, s2, b2, act2=ACT_NONE, alpha2=0.0, slope=0.2, offset=0.5):
+        """plhip_se_gate_int8: pooled fp32 [n, c]; w1 [cr, c] / w2 [c, cr] int8; s / b the convs' folded scale / bias arrays
+        (b may be None).  Returns the fp32 gate [n, c]."""
+        pooled = np.ascontiguousarray(pooled, np.float32)
+        n, c = pooled.shape[0], int(np.prod(pooled.shape[1:]))
+        w1 = np.ascontiguousarray(w1, np.int8).reshape(-1, c)
+        cr = w1.shape[0]
+        w2 = np.ascontiguousarray(w2, np.int8).reshape(c, cr)
+        d = SeGateDesc(n, c, cr, float(calib_scale), int(act1), int(act2), float(alpha1), float(alpha2), float(slope), float(offset))
+        ptrs = [self.to_device(pooled), self.to_device(w1), self.to_device(w2), self.malloc(self.L.plhip_se_gate_packed_weight_bytes(c, cr)),
+                self.to_device(np.ascontiguousarray(s1, np.float32)), self.to_device(np.ascontiguousarray(s2, np.float32)),
+                self.malloc(n * c * 4)]
+        dx, dw1, dw2, dwp, ds1, ds2, dy = ptrs
+        db1 = self.to_device(np.ascontiguousarray(b1, np.float32)) if b1 is not None else None
+        db2 = self.to_device(np.ascontiguousarray(b2, np.float32)) if b2 is not None else None
+        self.check(self.L.plhip_pack_se_gate_weights(self.h, c, cr, dw1, dw2, dwp), "pack_se_gate")
+        self.check(self.L.plhip_se_gate_int8(self.h, C.byref(d), dx, dwp, ds1, db1 or C.c_void_p(), ds2, db2 or C.c_void_p(), dy), "se_gate")
+        y = self.to_host(dy, (n, c), np.float32)
+        for p in ptrs + [q for q in (db1, db2) if q is not None]:
+            self.free(p)
+        return y

@@ -1185,6 +1185,60 @@ plhip_status plhip_elementwise_add_f32(plhip_ctx* ctx, const float* x, const flo
   return PLHIP_OK;
 }
 
+plhip_status plhip_hard_act_f32(plhip_ctx* ctx, plhip_hard_act_kind kind, const float* params, const float* x, float* y_f32,
+                                int8_t* y_i8, float calib_scale, int64_t count) {
+  if (!ctx || !params || !x || (!y_f32 && !y_i8) || count < 0 || (y_i8 && !(calib_scale > 0.f)))
+    return fail(ctx, PLHIP_ERR_INVALID, "plhip_hard_act_f32: bad argument");
+  if (kind != PLHIP_HARD_SWISH && kind != PLHIP_HARD_SIGMOID) return fail(ctx, PLHIP_ERR_UNSUPPORTED, "plhip_hard_act_f32: unknown kind");
+  if (count == 0) return PLHIP_OK;
+  plhip::launch_hard_act(kind == PLHIP_HARD_SWISH ? plhip::HARD_ACT_SWISH : plhip::HARD_ACT_SIGMOID, params, x, y_f32, y_i8,
+                         calib_scale, count, ctx->stream);
+  LAUNCHCHK(ctx, "hard_act");
+  return PLHIP_OK;
+}
+
+plhip_status plhip_se_scale_f32(plhip_ctx* ctx, const float* x, const float* gate, int n, int c, int hw, float* y_f32, int8_t* y_i8,
+                                float calib_scale) {
+  if (!ctx || !x || !gate || (!y_f32 && !y_i8) || n < 1 || c < 1 || hw < 1 || (y_i8 && !(calib_scale > 0.f)))
+    return fail(ctx, PLHIP_ERR_INVALID, "plhip_se_scale_f32: bad argument");
+  const int64_t planes = (int64_t)n * c;
+  if (planes > ((int64_t)1 << 30)) return fail(ctx, PLHIP_ERR_UNSUPPORTED, "plhip_se_scale_f32: too many planes");
+  plhip::launch_se_scale(x, gate, y_f32, y_i8, calib_scale, planes, hw, ctx->stream);
+  LAUNCHCHK(ctx, "se_scale");
+  return PLHIP_OK;
+}
+
+static bool se_gate_act_ok(int act) { return act == PLHIP_ACT_NONE || act == PLHIP_ACT_RELU || act == PLHIP_ACT_RELU6 || act == PLHIP_ACT_LEAKY_RELU; }
+int plhip_se_gate_supported(int c, int cr, int act1, int act2) {
+  return c >= 8 && cr >= 8 && c <= plhip::SE_GATE_MAX_C && cr <= plhip::SE_GATE_MAX_C && se_gate_act_ok(act1) && se_gate_act_ok(act2);
+}
+size_t plhip_se_gate_packed_weight_bytes(int c, int cr) { return c < 1 || cr < 1 ? 0 : plhip::se_gate_packed_bytes(c, cr); }
+plhip_status plhip_pack_se_gate_weights(plhip_ctx* ctx, int c, int cr, const int8_t* w1, const int8_t* w2, void* w_packed) {
+  if (!ctx || !w1 || !w2 || !w_packed || !aligned(w_packed, 4)) return fail(ctx, PLHIP_ERR_INVALID, "plhip_pack_se_gate_weights: bad argument");
+  if (!plhip_se_gate_supported(c, cr, 0, 0)) return fail(ctx, PLHIP_ERR_UNSUPPORTED, "plhip_pack_se_gate_weights: c / cr outside 8..960");
+  plhip::launch_se_gate_pack(w1, w2, w_packed, c, cr, ctx->stream);
+  LAUNCHCHK(ctx, "se_gate_pack");
+  return PLHIP_OK;
+}
+plhip_status plhip_se_gate_int8(plhip_ctx* ctx, const plhip_se_gate_desc* d, const float* pooled, const void* w_packed,
+                                const float* scale1, const float* bias1, const float* scale2, const float* bias2, float* gate) {
+  if (!ctx || !d || !pooled || !w_packed || !scale1 || !scale2 || !gate || d->n < 1 || !(d->calib_scale > 0.f) || !aligned(w_packed, 4))
+    return fail(ctx, PLHIP_ERR_INVALID, "plhip_se_gate_int8: bad argument");
+  if (!plhip_se_gate_supported(d->c, d->cr, d->act1, d->act2)) return fail(ctx, PLHIP_ERR_UNSUPPORTED, "plhip_se_gate_int8: outside the envelope");
+  plhip::SeGateArgs a;
+  a.pooled = pooled;
+  a.inv = 1.f / d->calib_scale;  // type_trans.cc:45, as launch_calib_f32_to_i8
+  a.w1 = static_cast<const uint32_t*>(w_packed);
+  a.w2 = a.w1 + (size_t)((d->c + 3) / 4) * d->cr;
+  a.s1 = scale1; a.b1 = bias1; a.s2 = scale2; a.b2 = bias2;
+  a.act1 = d->act1; a.act2 = d->act2; a.alpha1 = d->act1_alpha; a.alpha2 = d->act2_alpha;
+  a.slope = d->slope; a.offset = d->offset;
+  a.gate = gate; a.c = d->c; a.cr = d->cr;
+  plhip::launch_se_gate(a, d->n, ctx->stream);
+  LAUNCHCHK(ctx, "se_gate");
+  return PLHIP_OK;
+}
+
 // ------------------------------------------------------------------ self test
 // Known-answer 1x1 conv (M = 70, K = 45, N = 2 x 36) with asymmetric data, int32 accumulators compared with a host
 // triple loop: proves the MFMA operand / accumulator lane maps and the in-register transpose on this device.

@@ -333,4 +333,31 @@ void launch_pool2d(const PoolArgs& a, hipStream_t s);
 void launch_pool2d_max_i8(const PoolArgs& a, hipStream_t s);  // x / y are int8 planes behind the float pointers
 void launch_eltwise_add(const float* x, const float* y, float* o, int64_t count, int relu, hipStream_t s);
 
+// hard_swish / hard_sigmoid and the squeeze-excite multiply, fp32 in, fp32 and / or int8 (calib form) out: hard_act.hip
+enum { HARD_ACT_SWISH = 0, HARD_ACT_SIGMOID = 1 };
+// params: hard_swish {threshold, scale, offset}, hard_sigmoid {slope, offset}; yf / yq: either may be null
+void launch_hard_act(int kind, const float* params, const float* x, float* yf, int8_t* yq, float calib_scale, int64_t count,
+                     hipStream_t s);
+// out[p][i] = x[p][i] * g[p], p < planes, i < hw
+void launch_se_scale(const float* x, const float* g, float* yf, int8_t* yq, float calib_scale, int64_t planes, int hw, hipStream_t s);
+
+// the excite stage of a squeeze-excite block in one launch: se_gate.hip
+constexpr int SE_GATE_MAX_C = 960;
+struct SeGateArgs {
+  const float* pooled;   // [n][c]
+  float inv;             // 1 / calib scale
+  const uint32_t* w1;    // packed [(c + 3) / 4][cr]
+  const uint32_t* w2;    // packed [(cr + 3) / 4][c]
+  const float *s1, *b1;  // folded scale / bias of conv 1 [cr] (b may be null)
+  const float *s2, *b2;  // ... of conv 2 [c]
+  int act1, act2;
+  float alpha1, alpha2;
+  float slope, offset;   // hard_sigmoid
+  float* gate;           // [n][c]
+  int c, cr;
+};
+size_t se_gate_packed_bytes(int c, int cr);
+void launch_se_gate_pack(const int8_t* w1, const int8_t* w2, void* packed, int c, int cr, hipStream_t s);
+void launch_se_gate(const SeGateArgs& a, int n, hipStream_t s);
+
 }  // namespace plhip

@@ -512,6 +512,68 @@ void GraphBuilder::FuseSteps(std::vector<Step>* steps_io) {
       dead[j] = true;
     }
   }
+  // (J2) the excite chain behind a global average pool: calib -> conv 1x1 [int8_out] -> conv 1x1 [fp32_out] -> hard_sigmoid, each the
+  // only reader of the one before and the convs without a tail of their own, becomes one instruction in the calib's place
+  if (fuse_hard_act_) {
+    auto sole_reader = [&](const std::string& v) {  // the one live step that reads v, or -1
+      if (uses(v) != 1) return -1;
+      for (size_t t = 0; t < st.size(); ++t) {
+        if (dead[t]) continue;
+        if (st[t].kind == "op" ? (st[t].op_inputs.size() == 1 && st[t].op_inputs[0] == v) : st[t].in == v) return static_cast<int>(t);
+      }
+      return -1;
+    };
+    auto plain_1x1 = [&](int t, bool int8_out) {
+      if (t < 0 || st[t].kind != "op") return false;
+      const GraphOp& c = ops_[st[t].op];
+      bool pad0 = true;
+      for (int v : c.conv.paddings) pad0 = pad0 && v == 0;
+      return c.type == "conv2d" && c.enable_int8 && st[t].int8_out == int8_out && c.w_dims.size() == 4 && c.w_dims[2] == 1 &&
+             c.w_dims[3] == 1 && c.conv.groups == 1 && c.conv.strides == std::vector<int>({1, 1}) &&
+             c.conv.dilations == std::vector<int>({1, 1}) && pad0 && st[t].res.empty() && st[t].calib_out.empty() && !st[t].drop_f32 &&
+             st[t].pw_op < 0 && !(st[t].in_calib_scale > 0.f) && st[t].image_feed < 0;
+    };
+    for (size_t i = 0; i < st.size(); ++i) {
+      if (dead[i] || st[i].kind != "op" || st[i].pool_int8) continue;
+      const GraphOp& po = ops_[st[i].op];
+      if (po.type != "pool2d" || po.pooling_type != "avg" || !po.global_pooling) continue;
+      const int k = sole_reader(st[i].out);
+      if (k < 0 || st[k].kind != "calib_f2i") continue;
+      const int a = sole_reader(st[k].out);
+      if (!plain_1x1(a, true)) continue;
+      const int b = sole_reader(st[a].out);
+      if (!plain_1x1(b, false)) continue;
+      const int g = sole_reader(st[b].out);
+      if (g < 0 || st[g].kind != "op" || ops_[st[g].op].type != "hard_sigmoid") continue;
+      const GraphOp &ca = ops_[st[a].op], &cb = ops_[st[b].op];
+      if (cb.w_dims[1] != ca.w_dims[0] || cb.w_dims[0] != ca.w_dims[1]) continue;
+      if (!plhip_se_gate_supported(static_cast<int>(ca.w_dims[1]), static_cast<int>(ca.w_dims[0]), ca.conv.act, cb.conv.act)) continue;
+      st[k].kind = "se_gate";
+      st[k].via = st[k].out + "," + st[a].out + "," + st[b].out;
+      st[k].out = st[g].out;
+      st[k].op = st[a].op;
+      st[k].pw_op = st[b].op;
+      st[k].out_scale = st[a].out_scale;
+      dead[a] = dead[b] = dead[g] = true;
+    }
+  }
+  // (J1) (J3) hard_swish / elementwise_mul whose fp32 output a calib[fp32_to_int8] reads takes that calib over: one launch writes
+  // the int8 tensor and, only where it has other readers, the fp32 one
+  if (fuse_hard_act_) {
+    for (size_t i = 0; i < st.size(); ++i) {
+      if (dead[i] || st[i].kind != "op" || !st[i].calib_out.empty()) continue;
+      const std::string& type = ops_[st[i].op].type;
+      if (type != "hard_swish" && type != "elementwise_mul") continue;
+      int k = -1;
+      for (size_t t = i + 1; t < st.size(); ++t)
+        if (!dead[t] && st[t].kind == "calib_f2i" && st[t].in == st[i].out) k = static_cast<int>(t);
+      if (k < 0) continue;
+      st[i].calib_out = st[k].out;
+      st[i].calib_scale = st[k].scale;
+      dead[k] = true;
+      st[i].drop_f32 = uses(st[i].out) == 0;
+    }
+  }
   std::vector<Step> kept;
   for (size_t i = 0; i < st.size(); ++i)
     if (!dead[i]) kept.push_back(st[i]);
@@ -532,7 +594,8 @@ std::vector<std::string> GraphBuilder::Plan() {
         const bool fc = op.type == "fc";
         l += s.int8_out ? (fc ? "/int8out" : "/int8_out") : (fc ? "/fp32out" : "/fp32_out");
       } else {
-        l += "/def";
+        const bool tail_op = op.type == "hard_swish" || op.type == "elementwise_mul";  // (J1) (J3): the alias that carries a calib tail
+        l += tail_op && !s.calib_out.empty() ? "/int8" : "/def";
       }
       l += " in=";
       for (size_t i = 0; i < s.op_inputs.size(); ++i) l += (i ? "," : "") + s.op_inputs[i];
@@ -578,6 +641,12 @@ std::vector<std::string> GraphBuilder::Plan() {
         snprintf(buf, sizeof buf, " scale=%.9g", s.scale);
         l += buf;
       }
+    } else if (s.kind == "se_gate") {  // (J2)
+      l = "hard_sigmoid/se_gate in=" + s.in + " out=" + s.out + " via=" + s.via;
+      snprintf(buf, sizeof buf, " scale=%.9g", s.scale);
+      l += buf;
+      snprintf(buf, sizeof buf, " mid_scale=%.9g", s.out_scale);
+      l += buf;
     } else if (s.kind == "image_convert") {
       l = "image_convert/def in=" + s.in + " out=" + s.out + " src=" + operators::FrameFormatName(feeds_[s.image_feed].frame_format) + " dst=BGR";
     } else if (s.kind == "image_resize") {
@@ -622,6 +691,11 @@ std::vector<std::string> GraphBuilder::Lower(HipPredictor* pred) {
       outs.push_back(s.out);
     } else if (s.kind == "calib_f2i" || s.kind == "calib_i2f") {
       pred->AddCalib(s.in, s.out, s.scale, s.kind == "calib_f2i");
+    } else if (s.kind == "se_gate") {
+      const GraphOp &ca = ops_[s.op], &cb = ops_[s.pw_op];
+      CHECK(ca.conv.input_scale == s.scale && cb.conv.input_scale == s.out_scale) << "se_gate: scales of the chain disagree";
+      pred->AddSeGate(s.in, s.out, s.scale, ca.w.data(), ca.w_dims, ca.has_bias ? ca.bias.data() : nullptr, ca.conv, cb.w.data(), cb.w_dims,
+                      cb.has_bias ? cb.bias.data() : nullptr, cb.conv);
     } else if (s.kind == "image_convert") {
       pred->AddImageConvert(s.in, s.out, feeds_[s.image_feed].frame_format, PLHIP_IMG_BGR);
     } else if (s.kind == "image_resize") {
@@ -682,6 +756,10 @@ std::vector<std::string> GraphBuilder::Lower(HipPredictor* pred) {
         pred->AddElementwiseAdd(s.op_inputs[0], s.op_inputs[1], s.out, op.act_type);
       } else if (op.type == "softmax") {
         pred->AddSoftmax(s.op_inputs[0], s.out);
+      } else if (op.type == "hard_swish" || op.type == "hard_sigmoid") {
+        pred->AddActivation(op.type, s.op_inputs[0], s.out, s.calib_out, s.calib_scale, s.drop_f32);
+      } else if (op.type == "elementwise_mul") {
+        pred->AddElementwiseMul(s.op_inputs[0], s.op_inputs[1], s.out, op.axis, s.calib_out, s.calib_scale, s.drop_f32);
       } else {
         LOG(FATAL) << "GraphBuilder: no kHIP kernel for op type " << op.type;
       }

@@ -25,7 +25,8 @@ namespace paddle {
 namespace lite {
 
 struct GraphOp {
-  std::string type;  // conv2d | depthwise_conv2d | fc | pool2d | elementwise_add | fusion_elementwise_add_activation | softmax
+  std::string type;  // conv2d | depthwise_conv2d | fc | pool2d | elementwise_add | fusion_elementwise_add_activation | softmax |
+                     // hard_swish | hard_sigmoid | elementwise_mul (fp32 ops like pool2d; the reference's default parameters)
   std::vector<std::string> inputs;
   std::string output;
   bool enable_int8{false};
@@ -42,6 +43,8 @@ struct GraphOp {
   bool global_pooling{false}, exclusive{true}, ceil_mode{false};
   // fusion_elementwise_add_activation
   std::string act_type;
+  // elementwise_mul: inputs {X [N, C, H, W], Y [N, C, 1, 1] | [N, C] | X's shape}
+  int axis{-1};
 };
 
 class GraphBuilder {
@@ -83,6 +86,16 @@ class GraphBuilder {
   // (default off): runs with set_fuse(true) only, after D / E / F, on the pairs D left alone, where
   // plhip_dw_conv1x1_fused_supported takes the shapes propagated from the feeds.  MobileNetV2's 17 block pairs.
   void set_fuse_dwconv(bool on) { fuse_dwconv_ = on; }
+  //   (J1) hard_swish -> calib[fp32_to_int8]      => ONE hard_swish/int8 instruction (plhip_hard_act_f32, both outputs when the
+  //        fp32 value has other readers: the pool and the multiply of a squeeze-excite block)
+  //   (J2) pool2d(avg, global) -> calib -> conv2d 1x1 [int8_out] -> conv2d 1x1 [fp32_out] -> hard_sigmoid, each the only reader
+  //        of the one before, where plhip_se_gate_supported takes C, Cr and the activations
+  //        => pool2d + ONE hard_sigmoid/se_gate instruction (plhip_se_gate_int8); otherwise the separate instructions stay
+  //   (J3) elementwise_mul -> calib[fp32_to_int8] => ONE elementwise_mul/int8 instruction (plhip_se_scale_f32); the fp32 product
+  //        is not written when the calib was its only reader
+  // With set_fuse(true) only; bit-identical to the instructions they replace (the quantiser is calib's own).  DEFAULT OFF: none of
+  // the three has been measured against the launches it replaces, as 8.5 keeps fusion G off.
+  void set_fuse_hard_act(bool on) { fuse_hard_act_ = on; }
   GraphOp& Add(const std::string& type, const std::vector<std::string>& inputs, const std::string& output);
   // Emits the program into `pred`; returns the host-side names of the fetched variables ("<name>/host").
   std::vector<std::string> Lower(HipPredictor* pred);
@@ -94,7 +107,7 @@ class GraphBuilder {
  private:
   struct Step {
     int op{-1};              // index into ops_, or -1 for an inserted instruction
-    std::string kind;        // "op", "io_copy_h2d", "io_copy_d2h", "calib_f2i", "calib_i2f", "image_to_tensor", "image_convert", "image_resize"
+    std::string kind;        // "op", "io_copy_h2d", "io_copy_d2h", "calib_f2i", "calib_i2f", "image_to_tensor", "image_convert", "image_resize", "se_gate"
     std::string in, out;
     float scale{0.f};
     bool int8_out{false};
@@ -120,6 +133,8 @@ class GraphBuilder {
     bool image_int8{false};   // image_to_tensor that took the calib behind it over (H2): int8 output, `scale` the calib's
     bool resize_tensor{false};  // image_resize that took the image_to_tensor behind it over (I); image_int8: and the calib behind that
     bool resize_nv{false};      // ... and the image_convert in front: its source is the NV frame itself
+    // kind "se_gate" (J2): `in` the pooled tensor, `out` the gate, `scale` the calib's; op / pw_op the two convs in ops_, `via` the
+    // names of the three tensors that are no longer written
   };
   std::vector<Step> Schedule();
   void FuseSteps(std::vector<Step>* steps);
@@ -136,6 +151,7 @@ class GraphBuilder {
   bool fuse_{true};
   int fuse_dwpw_{2};
   bool fuse_dwconv_{false};
+  bool fuse_hard_act_{false};
   std::vector<FeedDesc> feeds_;
   std::vector<std::string> fetches_;
   std::vector<GraphOp> ops_;

@@ -1,8 +1,10 @@
 // hip_predictor.cc — see hip_predictor.h.
 #include "lite/api/hip_predictor.h"
 
+#include "lite/kernels/hip/calib_tail.h"
 #include "lite/kernels/hip/conv_fusion.h"
 #include "lite/kernels/hip/image_frame.h"
+#include "lite/kernels/hip/se_gate_fusion.h"
 #include "lite/kernels/hip/image_to_tensor.h"
 #include "plhip.h"
 
@@ -279,6 +281,79 @@ void HipPredictor::AddSoftmax(const std::string& in, const std::string& out) {
   op->mutable_param().output = Var(out);
   op->mutable_param().axis = -1;
   Emit(op, PickKernel("softmax", Place(TARGET(kHIP), PRECISION(kFloat)), "def"));
+}
+
+// the "int8" alias of an fp32 op with its calib tail attached, or the plain "def" kernel
+static std::unique_ptr<KernelBase> PickWithCalibTail(const std::string& op_type, Tensor* calib_out, float calib_scale, bool drop_fp32) {
+  auto kernel = PickKernel(op_type, Place(TARGET(kHIP), PRECISION(kFloat)), calib_out ? "int8" : "def");
+  if (calib_out) {
+    auto* tk = dynamic_cast<kernels::hip::HipCalibTailKernel*>(kernel.get());
+    CHECK(tk) << "the picked " << op_type << " kernel does not take a calib tail";
+    kernels::hip::HipCalibTail t;
+    t.calib_output = calib_out;
+    t.calib_output->set_precision(PRECISION(kInt8));
+    t.calib_scale = calib_scale;
+    t.drop_fp32_output = drop_fp32;
+    tk->SetCalibTail(t);
+  }
+  return kernel;
+}
+
+void HipPredictor::AddActivation(const std::string& op_type, const std::string& in, const std::string& out,
+                                 const std::string& calib_out, float calib_scale, bool drop_fp32) {
+  CHECK(op_type == "hard_swish" || op_type == "hard_sigmoid") << "kHIP has no activation kernel for " << op_type;
+  auto op = std::make_shared<operators::ActivationOp>(op_type);
+  auto& p = op->mutable_param();
+  p.X = Var(in);
+  p.Out = Var(out);
+  p.has_active = true;
+  p.active_type = op_type == "hard_swish" ? lite_api::ActivationType::kHardSwish : lite_api::ActivationType::kHardSigmoid;
+  Emit(op, PickWithCalibTail(op_type, calib_out.empty() ? nullptr : Var(calib_out), calib_scale, drop_fp32));
+}
+
+void HipPredictor::AddSeGate(const std::string& in, const std::string& out, float calib_scale, const int8_t* w1,
+                             const std::vector<int64_t>& w1_dims, const float* bias1, const ConvAttrs& a1, const int8_t* w2,
+                             const std::vector<int64_t>& w2_dims, const float* bias2, const ConvAttrs& a2) {
+  auto op = std::make_shared<operators::ActivationOp>("hard_sigmoid");
+  auto& p = op->mutable_param();
+  p.X = Var(in);
+  p.Out = Var(out);
+  p.has_active = true;
+  p.active_type = lite_api::ActivationType::kHardSigmoid;
+  kernels::hip::HipSeGateFusion fz;
+  fz.calib_scale = calib_scale;
+  auto fill = [this](kernels::hip::HipSeGateConv* c, const int8_t* w, const std::vector<int64_t>& wd, const float* bias, const ConvAttrs& a) {
+    size_t wn = 1;
+    for (auto d : wd) wn *= static_cast<size_t>(d);
+    c->filter = NewParam(w, wn, wd, PRECISION(kInt8));
+    c->bias = bias ? NewParam(bias, static_cast<size_t>(wd[0]) * 4, {wd[0]}, PRECISION(kFloat)) : nullptr;
+    c->weight_scale = a.weight_scale;
+    c->input_scale = a.input_scale;
+    if (a.act != 0) {
+      c->activation_param.has_active = true;
+      c->activation_param.active_type = static_cast<lite_api::ActivationType>(a.act);
+      if (a.act == 2) c->activation_param.Relu_clipped_coef = a.act_coef;
+      if (a.act == 4) c->activation_param.Leaky_relu_alpha = a.act_coef;
+    }
+  };
+  fill(&fz.reduce, w1, w1_dims, bias1, a1);
+  fill(&fz.expand, w2, w2_dims, bias2, a2);
+  auto kernel = PickKernel("hard_sigmoid", Place(TARGET(kHIP), PRECISION(kFloat)), "se_gate");
+  auto* gk = dynamic_cast<kernels::hip::HipSeGateKernel*>(kernel.get());
+  CHECK(gk) << "the picked hard_sigmoid kernel does not take the se_gate fusion";
+  gk->SetSeGate(fz);
+  Emit(op, std::move(kernel));
+}
+
+void HipPredictor::AddElementwiseMul(const std::string& x, const std::string& y, const std::string& out, int axis,
+                                     const std::string& calib_out, float calib_scale, bool drop_fp32) {
+  auto op = std::make_shared<operators::ElementwiseMulOp>();
+  auto& p = op->mutable_param();
+  p.X = Var(x);
+  p.Y = Var(y);
+  p.Out = Var(out);
+  p.axis = axis;
+  Emit(op, PickWithCalibTail("elementwise_mul", calib_out.empty() ? nullptr : Var(calib_out), calib_scale, drop_fp32));
 }
 
 std::vector<std::string> HipPredictor::KernelNames() {

@@ -84,6 +84,19 @@ class HipPredictor {
   // act_type "" -> elementwise_add, "relu" -> fusion_elementwise_add_activation
   void AddElementwiseAdd(const std::string& x, const std::string& y, const std::string& out, const std::string& act_type);
   void AddSoftmax(const std::string& in, const std::string& out);
+  // hard_swish / hard_sigmoid with the reference's default parameters (lite/operators/op_params.h:406-412), and
+  // elementwise_mul (y: x's shape, or [N, C, 1, 1] / [N, C] at axis 0).  calib_out != "": the calib[fp32_to_int8](calib_scale)
+  // behind the op runs in the same launch and writes that variable (fusions J1 / J3, lite/kernels/hip/calib_tail.h);
+  // drop_fp32: `out` has no reader left and is not written.
+  void AddActivation(const std::string& op_type, const std::string& in, const std::string& out, const std::string& calib_out = "",
+                     float calib_scale = 1.f, bool drop_fp32 = false);
+  // fusion J2: hard_sigmoid that took calib(calib_scale) -> conv 1x1 (w1 [cr, c, 1, 1], a1; int8 out at a2.input_scale) -> conv 1x1
+  // (w2 [c, cr, 1, 1], a2; fp32 out) in front of it over: `in` is the pooled fp32 [N, C, 1, 1], `out` the gate
+  void AddSeGate(const std::string& in, const std::string& out, float calib_scale, const int8_t* w1, const std::vector<int64_t>& w1_dims,
+                 const float* bias1, const ConvAttrs& a1, const int8_t* w2, const std::vector<int64_t>& w2_dims, const float* bias2,
+                 const ConvAttrs& a2);
+  void AddElementwiseMul(const std::string& x, const std::string& y, const std::string& out, int axis, const std::string& calib_out = "",
+                         float calib_scale = 1.f, bool drop_fp32 = false);
 
   void Run(bool skip_io_copy = false) {
     TargetWrapperHip::SetDevice(device_);

@@ -208,6 +208,45 @@ int pllite_graph_elementwise_add(pllite_predictor* p, const char* x, const char*
     op.act_type = act;
   });
 }
+int pllite_graph_activation(pllite_predictor* p, const char* op_type, const char* in, const char* out) {
+  return guarded([&] {
+    const std::string t = op_type ? op_type : "";
+    CHECK(t == "hard_swish" || t == "hard_sigmoid") << "pllite_graph_activation: kHIP has hard_swish and hard_sigmoid, not " << t;
+    p->graph.Add(t, {in}, out);
+  });
+}
+int pllite_graph_elementwise_mul(pllite_predictor* p, const char* x, const char* y, const char* out, int axis) {
+  return guarded([&] { p->graph.Add("elementwise_mul", {x, y}, out).axis = axis; });
+}
+int pllite_graph_set_fuse_hard_act(pllite_predictor* p, int on) {
+  return guarded([&] { p->graph.set_fuse_hard_act(on != 0); });
+}
+int pllite_add_activation(pllite_predictor* p, const char* op_type, const char* in, const char* out, const char* calib_out,
+                          float calib_scale, int drop_fp32) {
+  return guarded([&] { p->pred.AddActivation(op_type ? op_type : "", in, out, calib_out ? calib_out : "", calib_scale, drop_fp32 != 0); });
+}
+int pllite_add_elementwise_mul(pllite_predictor* p, const char* x, const char* y, const char* out, int axis, const char* calib_out,
+                               float calib_scale, int drop_fp32) {
+  return guarded([&] { p->pred.AddElementwiseMul(x, y, out, axis, calib_out ? calib_out : "", calib_scale, drop_fp32 != 0); });
+}
+// The elementwise_mul kernel class's PrepareForRun on tensors of these shapes: it only reads the dims, so no device is needed.
+// 0 = the broadcast is taken; -1 = refused, pllite_last_error() holds the kernel's fatal message.
+int pllite_elementwise_mul_prepare(const int64_t* x_dims, int nx, const int64_t* y_dims, int ny, int axis) {
+  return guarded([&] {
+    CHECK(x_dims && y_dims && nx > 0 && ny > 0) << "pllite_elementwise_mul_prepare: bad argument";
+    Tensor x, y, out;
+    x.Resize(std::vector<int64_t>(x_dims, x_dims + nx));
+    y.Resize(std::vector<int64_t>(y_dims, y_dims + ny));
+    paddle::lite::operators::ElementwiseParam param;
+    param.X = &x;
+    param.Y = &y;
+    param.Out = &out;
+    param.axis = axis;
+    auto k = paddle::lite::PickKernel("elementwise_mul", paddle::lite::Place(TARGET(kHIP), PRECISION(kFloat)), "def");
+    k->SetParam<paddle::lite::operators::ElementwiseParam>(param);
+    k->PrepareForRun();
+  });
+}
 int pllite_graph_softmax(pllite_predictor* p, const char* in, const char* out) {
   return guarded([&] { p->graph.Add("softmax", {in}, out); });
 }

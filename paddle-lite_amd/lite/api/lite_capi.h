@@ -37,6 +37,13 @@ int pllite_add_softmax(pllite_predictor* p, const char* in, const char* out);
 int pllite_add_pool(pllite_predictor* p, const char* in, const char* out, const char* pooling_type, const int* ksize,
                     const int* strides, const int* paddings4, int global_pooling, int exclusive, int ceil_mode);
 int pllite_add_elementwise_add(pllite_predictor* p, const char* x, const char* y, const char* out, const char* act_type);
+/* op_type "hard_swish" | "hard_sigmoid" (the reference's default parameters); elementwise_mul: y is x's shape or [N, C, 1, 1] /
+ * [N, C] at axis 0.  calib_out != NULL / "": the int8 alias, the calib[fp32_to_int8](calib_scale) behind the op in the same launch
+ * writes that variable; drop_fp32: `out` is not written. */
+int pllite_add_activation(pllite_predictor* p, const char* op_type, const char* in, const char* out, const char* calib_out,
+                          float calib_scale, int drop_fp32);
+int pllite_add_elementwise_mul(pllite_predictor* p, const char* x, const char* y, const char* out, int axis, const char* calib_out,
+                               float calib_scale, int drop_fp32);
 
 /* ---- graph mode (lite/api/graph_builder.h): ops as the optimiser sees them after its fusion passes; kernel choice
  * (int8_out / fp32_out), io_copy and calib placement are decided by pllite_graph_lower() with the reference's rules.
@@ -62,6 +69,14 @@ int pllite_graph_pool(pllite_predictor* p, const char* in, const char* out, cons
                       const int* strides, const int* paddings4, int global_pooling, int exclusive, int ceil_mode);
 int pllite_graph_elementwise_add(pllite_predictor* p, const char* x, const char* y, const char* out, const char* act_type);
 int pllite_graph_softmax(pllite_predictor* p, const char* in, const char* out);
+/* fp32 ops of MobileNetV3: op_type "hard_swish" | "hard_sigmoid"; elementwise_mul with y [N, C, 1, 1] / [N, C] (axis 0) or x's shape */
+int pllite_graph_activation(pllite_predictor* p, const char* op_type, const char* in, const char* out);
+/* runs the elementwise_mul kernel class's PrepareForRun on these shapes (no device needed): 0 taken, -1 refused (pllite_last_error) */
+int pllite_elementwise_mul_prepare(const int64_t* x_dims, int nx, const int64_t* y_dims, int ny, int axis);
+int pllite_graph_elementwise_mul(pllite_predictor* p, const char* x, const char* y, const char* out, int axis);
+/* fusions J1 / J2 / J3 (hard_swish / elementwise_mul take the calib behind them over, hard_sigmoid the excite chain in front): off by
+ * default, effective with pllite_graph_set_fuse(1) only */
+int pllite_graph_set_fuse_hard_act(pllite_predictor* p, int on);
 int pllite_graph_fetch(pllite_predictor* p, const char* name);
 /* kHIP graph-level fusions (graph_builder.h set_fuse): on by default; 0 = the reference program instruction for instruction. */
 int pllite_graph_set_fuse(pllite_predictor* p, int on);

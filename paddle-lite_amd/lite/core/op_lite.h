@@ -259,6 +259,46 @@ class ElementwiseOp : public OpLite {
   mutable ElementwiseParam param_;
 };
 
+// elementwise_ops.cc for elementwise_mul: Out takes X's dims.  Y is X's shape, or the per-(image, channel) operand of a
+// squeeze-excite block ([N, C, 1, 1] or [N, C] along axis 0); the kernel refuses every other broadcast (PrepareForRun).
+class ElementwiseMulOp : public OpLite {
+ public:
+  ElementwiseMulOp() : OpLite("elementwise_mul") {}
+  ElementwiseParam& mutable_param() { return param_; }
+  bool CheckShape() const override {
+    CHECK(param_.X && param_.Y && param_.Out);
+    return true;
+  }
+  bool InferShapeImpl() const override {
+    CHECK_GE(param_.X->dims().size(), param_.Y->dims().size()) << "elementwise_mul: Y must not have more dims than X";
+    param_.Out->Resize(param_.X->dims());
+    return true;
+  }
+  void AttachKernel(KernelBase* k) override { k->SetParam<ElementwiseParam>(param_); }
+
+ private:
+  mutable ElementwiseParam param_;
+};
+
+// activation_ops.cc: Out takes X's dims.  hard_swish / hard_sigmoid read the ActivationParam fields of their names.
+class ActivationOp : public OpLite {
+ public:
+  explicit ActivationOp(const std::string& type) : OpLite(type) {}
+  ActivationParam& mutable_param() { return param_; }
+  bool CheckShape() const override {
+    CHECK(param_.X && param_.Out) << op_type_ << ": X / Out must be set";
+    return true;
+  }
+  bool InferShapeImpl() const override {
+    param_.Out->Resize(param_.X->dims());
+    return true;
+  }
+  void AttachKernel(KernelBase* k) override { k->SetParam<ActivationParam>(param_); }
+
+ private:
+  mutable ActivationParam param_;
+};
+
 // fusion_elementwise_activation_ops.cc
 class FusionElementwiseActivationOp : public OpLite {
  public:

@@ -66,6 +66,11 @@ struct ActivationParam : ParamBase {
   bool has_active{false};
   float Leaky_relu_alpha{0};
   float Relu_clipped_coef{6};
+  float hard_sigmoid_slope{0.2f};
+  float hard_sigmoid_offset{0.5f};
+  float hard_swish_threshold{6.0};
+  float hard_swish_scale{6.0};
+  float hard_swish_offset{3.0};
   float threshold{6.0f};
 };
 

@@ -58,6 +58,12 @@ def load():
     L.pllite_graph_pool.argtypes = [vp, cs, cs, cs, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), i32, i32, i32]
     L.pllite_graph_elementwise_add.argtypes = [vp, cs, cs, cs, cs]
     L.pllite_graph_softmax.argtypes = [vp, cs, cs]
+    L.pllite_graph_activation.argtypes = [vp, cs, cs, cs]
+    L.pllite_graph_elementwise_mul.argtypes = [vp, cs, cs, cs, i32]
+    L.pllite_graph_set_fuse_hard_act.argtypes = [vp, i32]
+    L.pllite_elementwise_mul_prepare.argtypes = [C.POINTER(i64), i32, C.POINTER(i64), i32, i32]
+    L.pllite_add_activation.argtypes = [vp, cs, cs, cs, cs, f32, i32]
+    L.pllite_add_elementwise_mul.argtypes = [vp, cs, cs, cs, i32, cs, f32, i32]
     L.pllite_graph_fetch.argtypes = [vp, cs]
     L.pllite_graph_set_fuse.argtypes = [vp, i32]
     L.pllite_graph_set_fuse_dwpw.argtypes = [vp, i32]
@@ -86,6 +92,13 @@ def load():
 
 def _ia(vals, t=C.c_int):
     return (t * len(vals))(*[int(v) for v in vals])
+
+
+def elementwise_mul_prepare(x_dims, y_dims, axis=0):
+    """The elementwise_mul kernel class's PrepareForRun on these shapes (host only).  Raises LiteError where it refuses the broadcast."""
+    L = load()
+    if L.pllite_elementwise_mul_prepare(_ia(x_dims, C.c_int64), len(x_dims), _ia(y_dims, C.c_int64), len(y_dims), int(axis)) != 0:
+        raise LiteError(L.pllite_last_error().decode())
 
 
 class Predictor:
@@ -161,6 +174,15 @@ class Predictor:
     def add_elementwise_add(self, x, y, dst, act_type=""):
         self._ck(self.L.pllite_add_elementwise_add(self.h, x.encode(), y.encode(), dst.encode(), act_type.encode()))
 
+    def add_activation(self, op_type, src, dst, calib_out="", calib_scale=1.0, drop_fp32=False):
+        """hard_swish | hard_sigmoid; calib_out: the int8 alias (the calib behind the op in the same launch writes that variable)."""
+        self._ck(self.L.pllite_add_activation(self.h, op_type.encode(), src.encode(), dst.encode(), calib_out.encode(),
+                                              calib_scale, int(drop_fp32)))
+
+    def add_elementwise_mul(self, x, y, dst, axis=0, calib_out="", calib_scale=1.0, drop_fp32=False):
+        self._ck(self.L.pllite_add_elementwise_mul(self.h, x.encode(), y.encode(), dst.encode(), int(axis), calib_out.encode(),
+                                                   calib_scale, int(drop_fp32)))
+
     # ---- graph mode: ops as the optimiser sees them; graph_lower() applies the reference's kernel-pick / cast rules
     def graph_feed(self, name, dims, precision=PREC_FLOAT):
         self._ck(self.L.pllite_graph_feed(self.h, name.encode(), _ia(dims, C.c_int64), len(dims), precision))
@@ -216,6 +238,21 @@ class Predictor:
 
     def graph_softmax(self, src, dst):
         self._ck(self.L.pllite_graph_softmax(self.h, src.encode(), dst.encode()))
+
+    def graph_hard_swish(self, src, dst):
+        self._ck(self.L.pllite_graph_activation(self.h, b"hard_swish", src.encode(), dst.encode()))
+
+    def graph_hard_sigmoid(self, src, dst):
+        self._ck(self.L.pllite_graph_activation(self.h, b"hard_sigmoid", src.encode(), dst.encode()))
+
+    def graph_elementwise_mul(self, x, y, dst, axis=0):
+        """x [N, C, H, W] times y [N, C, 1, 1] / [N, C] (axis 0), or y of x's shape."""
+        self._ck(self.L.pllite_graph_elementwise_mul(self.h, x.encode(), y.encode(), dst.encode(), int(axis)))
+
+    def graph_set_fuse_hard_act(self, on):
+        """Fusions J1 / J2 / J3 (default off; with graph_set_fuse(True) only): hard_swish / elementwise_mul take the calib[fp32_to_int8]
+        behind them over, hard_sigmoid the excite chain calib -> conv 1x1 -> conv 1x1 in front of it."""
+        self._ck(self.L.pllite_graph_set_fuse_hard_act(self.h, int(on)))
 
     def graph_set_fuse(self, on):
         self._ck(self.L.pllite_graph_set_fuse(self.h, int(on)))

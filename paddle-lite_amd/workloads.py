@@ -123,7 +123,7 @@ class _NetGen:
         self.act_scale[name] = np.float32(act_scale)
         self.sig_i8[name] = sig_i8
 
-    def conv(self, name, src, cout, k, stride, pad, groups=1, act=1, act_coef=0.0, out_range=4.0, op=None):
+    def conv(self, name, src, cout, k, stride, pad, groups=1, act=1, act_coef=0.0, out_range=4.0, op=None, headroom=1.0):
         cin, h, w = self.shape[src]
         kk = (cin // groups) * k * k
         wt = self.rng.integers(-127, 128, (cout, cin // groups, k, k)).astype(np.int8)
@@ -131,7 +131,8 @@ class _NetGen:
         out_scale = np.float32(out_range / 127.0)
         acc_std = np.sqrt(kk) * self.sig_i8[src] * 73.0
         var = (1.0 + (np.arange(cout) % 7) / 8.0) / 1.375
-        w_scale = (var * 45.0 * float(out_scale) / (acc_std * float(in_scale))).astype(np.float32)
+        # headroom > 1: the weight scales are sized for an int8 std of 45 / headroom (fewer saturated values)
+        w_scale = (var * 45.0 / headroom * float(out_scale) / (acc_std * float(in_scale))).astype(np.float32)
         bias = (self.rng.uniform(-0.5, 0.5, cout) * 45.0 * float(out_scale)).astype(np.float32)
         if op is None:
             op = "depthwise_conv2d" if (groups == cin and groups == cout and groups > 1) else "conv2d"
@@ -139,15 +140,15 @@ class _NetGen:
                              act_coef=float(act_coef), in_scale=in_scale, w_scale=w_scale))
         ho = (h + 2 * pad - k) // stride + 1
         wo = (w + 2 * pad - k) // stride + 1
-        self.tensor(name, cout, ho, wo, out_scale, 30.0 if act else 45.0)
+        self.tensor(name, cout, ho, wo, out_scale, (30.0 if act else 45.0) / headroom)
         return name
 
-    def pool(self, name, src, pooling_type, k, stride, pad, global_pooling=False):
+    def pool(self, name, src, pooling_type, k, stride, pad, global_pooling=False, act_scale=None, sig_i8=40.0):
         c, h, w = self.shape[src]
         self.ops.append(dict(op="pool2d", name=name, src=src, pooling_type=pooling_type, ksize=k, stride=stride, pad=pad,
                              global_pooling=global_pooling))
         if global_pooling:
-            self.tensor(name, c, 1, 1, np.float32(self.act_scale[src] * 100.0 / 127.0), 40.0)
+            self.tensor(name, c, 1, 1, np.float32(self.act_scale[src] * 100.0 / 127.0) if act_scale is None else act_scale, sig_i8)
         else:
             self.tensor(name, c, (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1, self.act_scale[src],
                         self.sig_i8[src] * 1.3)
@@ -160,6 +161,34 @@ class _NetGen:
         # has a std of ~45 before the relu, like every conv output
         real = float(np.hypot(self.sig_i8[x] * float(self.act_scale[x]), self.sig_i8[y] * float(self.act_scale[y])))
         self.tensor(name, c, h, w, np.float32(real / (28.0 if act else 45.0)), 42.0 if act else 45.0)
+        return name
+
+    def widen(self, name, f):
+        """Quantise `name` over a range f times wider than the sizing rule gave it (fewer saturated values)."""
+        self.act_scale[name] = np.float32(self.act_scale[name] * f)
+        self.sig_i8[name] = self.sig_i8[name] / f
+        return name
+
+    def hard_swish(self, name, src, out_range=12.0):
+        """fp32 op.  Its input is a conv output sized over [-8, 8] (std ~2.8: a real share of x <= -3, of the ramp and of x >= 3);
+        its own int8 consumers quantise it over [-out_range, out_range], which holds the zero region and the linear region."""
+        c, h, w = self.shape[src]
+        self.ops.append(dict(op="hard_swish", name=name, src=src))
+        self.tensor(name, c, h, w, np.float32(out_range / 127.0), 30.0)
+        return name
+
+    def hard_sigmoid(self, name, src):
+        c, h, w = self.shape[src]
+        self.ops.append(dict(op="hard_sigmoid", name=name, src=src))
+        self.tensor(name, c, h, w, np.float32(1.0 / 127.0), 60.0)  # a gate in [0, 1]; only the fp32 multiply reads it
+        return name
+
+    def mul(self, name, x, y):
+        """elementwise_mul, y [c, 1, 1] the gate of a squeeze-excite block (in [0, 1]): the product keeps x's range."""
+        c, h, w = self.shape[x]
+        assert self.shape[y] == (c, 1, 1), (self.shape[y], c)
+        self.ops.append(dict(op="mul", name=name, x=x, y=y))
+        self.tensor(name, c, h, w, self.act_scale[x], self.sig_i8[x] * 0.6)
         return name
 
     def fc(self, name, src, n):
@@ -230,6 +259,65 @@ def mobilenet_v2_net(seed=52, res=224, num_classes=NUM_CLASSES):
     return _finish(g, res, x)
 
 
+# MobileNetV3 (lite/tests/benchmark/src/convolution_configs.h:467-653 lists every conv, the excite convs on 1 x 1 planes included;
+# block structure as published, Howard et al. 2019, tables 1 and 2): (kernel, expanded, out, squeeze-excite, hard_swish, stride)
+MBV3_LARGE = [(3, 16, 16, 0, 0, 1), (3, 64, 24, 0, 0, 2), (3, 72, 24, 0, 0, 1), (5, 72, 40, 1, 0, 2), (5, 120, 40, 1, 0, 1),
+              (5, 120, 40, 1, 0, 1), (3, 240, 80, 0, 1, 2), (3, 200, 80, 0, 1, 1), (3, 184, 80, 0, 1, 1), (3, 184, 80, 0, 1, 1),
+              (3, 480, 112, 1, 1, 1), (3, 672, 112, 1, 1, 1), (5, 672, 160, 1, 1, 2), (5, 960, 160, 1, 1, 1), (5, 960, 160, 1, 1, 1)]
+MBV3_SMALL = [(3, 16, 16, 1, 0, 2), (3, 72, 24, 0, 0, 2), (3, 88, 24, 0, 0, 1), (5, 96, 40, 1, 1, 2), (5, 240, 40, 1, 1, 1),
+              (5, 240, 40, 1, 1, 1), (5, 120, 48, 1, 1, 1), (5, 144, 48, 1, 1, 1), (5, 288, 96, 1, 1, 2), (5, 576, 96, 1, 1, 1),
+              (5, 576, 96, 1, 1, 1)]
+MBV3_HEAD = {"large": (960, 1280), "small": (576, 1024)}
+
+
+def mbv3_squeeze_channels(c):
+    """make_divisible(c / 4, 8): 16 -> 8, 72 -> 24, 96 -> 24, 120 -> 32, 144 -> 40, 240 -> 64, 288 -> 72, 480 -> 120 ..."""
+    v = max(8, int(c / 4 + 4) // 8 * 8)
+    return v + 8 if v < 0.9 * c / 4 else v
+
+
+def mobilenet_v3_net(variant="large", seed=53, res=224, num_classes=NUM_CLASSES):
+    """MobileNetV3-Large / -Small as the reference's optimiser leaves it: relu is fused into the int8 convs, hard_swish and
+    hard_sigmoid are fp32 ops of their own (conv_activation_fuse_pass.cc:26-44), the squeeze-excite gate is applied by an fp32
+    elementwise_mul.  The convs in front of hard_swish are sized over [-8, 8] (both clamps of the op see data), the second
+    excite conv too (the gate 0.2 x + 0.5 reaches 0 and 1 at -+2.5)."""
+    table = {"large": MBV3_LARGE, "small": MBV3_SMALL}[variant]
+    g = _NetGen(seed)
+    g.tensor("image", 3, res, res, 1.0 / 127, 73.0)
+    HS = dict(act=0, out_range=8.0)
+    x = g.hard_swish("conv1_hs", g.conv("conv1", "image", 16, 3, 2, 1, **HS))
+    cin = 16
+    for bi, (k, exp, cout, se, hs, stride) in enumerate(table):
+        p = "b%d" % (bi + 1)
+        act = HS if hs else dict(act=1, headroom=1.6)
+        y = x
+        if exp != cin:
+            y = g.conv(p + "_expand", y, exp, 1, 1, 0, **act)
+            if hs:
+                y = g.hard_swish(p + "_expand_hs", y)
+        # (the depthwise taps see the hard_swish output, whose int8 rms the rule overestimates: sized over [-16, 16])
+        y = g.conv(p + "_dw", y, exp, k, stride, k // 2, groups=exp, **(dict(act=0, out_range=16.0) if hs else act))
+        if hs:
+            y = g.hard_swish(p + "_dw_hs", y)
+        if se:
+            # a plane's mean lies inside the plane's own range: the pooled tensor keeps its source's scale
+            q = g.pool(p + "_se_pool", y, "avg", g.shape[y][1], 1, 0, global_pooling=True, act_scale=g.act_scale[y] * 1.5, sig_i8=14.0)
+            q = g.conv(p + "_se_reduce", q, mbv3_squeeze_channels(exp), 1, 1, 0, act=1, headroom=2.0)
+            q = g.conv(p + "_se_expand", q, exp, 1, 1, 0, **HS)
+            q = g.hard_sigmoid(p + "_se_gate", q)
+            y = g.mul(p + "_se_mul", y, q)
+        y = g.conv(p + "_project", y, cout, 1, 1, 0, act=0, headroom=1.6)
+        x = g.widen(g.add(p + "_add", x, y), 1.5) if (stride == 1 and cin == cout) else y
+        cin = cout
+    c_last, c_head = MBV3_HEAD[variant]
+    x = g.hard_swish("conv_last_hs", g.conv("conv_last", x, c_last, 1, 1, 0, **HS))
+    x = g.pool("pool", x, "avg", g.shape[x][1], 1, 0, global_pooling=True, act_scale=g.act_scale[x], sig_i8=20.0)
+    x = g.hard_swish("conv_head_hs", g.conv("conv_head", x, c_head, 1, 1, 0, **HS))
+    x = g.fc("fc", x, num_classes)
+    x = g.softmax("prob", x)
+    return _finish(g, res, x)
+
+
 def mobilenet_v1_net(seed=1234, res=224):
     """MobileNetV1 in op-list form, same weights as make_mobilenet_v1_weights(seed): graph mode must arrive at exactly
     the Appendix-D program that build_mobilenet_v1 writes out by hand."""
@@ -270,7 +358,7 @@ def net_stats(net):
     return macs
 
 
-def emit_graph(pred, net, batch, fuse=True, fuse_dwpw=None, fuse_dwconv=None, image=None, frame=None):
+def emit_graph(pred, net, batch, fuse=True, fuse_dwpw=None, fuse_dwconv=None, image=None, frame=None, fuse_hard_act=None):
     """Feed the op list to the predictor's graph mode and lower it.  Returns the host name of the output variable.
     image: None = the input is the normalised fp32 NCHW tensor; dict(format, means, scales) = the input is a decoded uint8 image
     [batch, h, w, cs] of that format (liteapi.IMG_*), normalised on the device (Predictor.graph_feed_image).
@@ -280,13 +368,17 @@ def emit_graph(pred, net, batch, fuse=True, fuse_dwpw=None, fuse_dwconv=None, im
     fuse_dwpw: None = the builder's default (depthwise -> pointwise pairs the fused kernel takes become one instruction),
     True = every eligible pair (shapes outside the kernel run as two launches inside the instruction), False = none.
     fuse_dwconv: None = the builder's default (off); True = fusion G, a depthwise conv takes its 1x1 consumer over together with
-    that conv's fused tail (MobileNetV2's blocks), False = off."""
+    that conv's fused tail (MobileNetV2's blocks), False = off.
+    fuse_hard_act: None = the builder's default (off); True = fusions J1 / J2 / J3 of the MobileNetV3 ops (hard_swish and
+    elementwise_mul take the calib behind them over, the excite chain becomes one hard_sigmoid/se_gate instruction)."""
     from . import liteapi
     pred.graph_set_fuse(fuse)
     if fuse_dwpw is not None:
         pred.graph_set_fuse_dwpw(fuse_dwpw)
     if fuse_dwconv is not None:
         pred.graph_set_fuse_dwconv(fuse_dwconv)
+    if fuse_hard_act is not None:
+        pred.graph_set_fuse_hard_act(fuse_hard_act)
     c, h, w = net["input_shape"]
     if frame is not None:
         assert image is None, "emit_graph: image= and frame= exclude each other"
@@ -311,6 +403,12 @@ def emit_graph(pred, net, batch, fuse=True, fuse_dwpw=None, fuse_dwconv=None, im
             pred.graph_elementwise_add(o["x"], o["y"], o["name"], o["act"])
         elif t == "softmax":
             pred.graph_softmax(o["src"], o["name"])
+        elif t == "hard_swish":
+            pred.graph_hard_swish(o["src"], o["name"])
+        elif t == "hard_sigmoid":
+            pred.graph_hard_sigmoid(o["src"], o["name"])
+        elif t == "mul":
+            pred.graph_elementwise_mul(o["x"], o["y"], o["name"], 0)
         else:
             raise ValueError(t)
     pred.graph_fetch(net["output"])
@@ -347,6 +445,12 @@ def program_costs(net, batch, plan_lines):
         if op == "calib":
             esz[dst] = 1 if alias == "fp32_to_int8" else 4
             out.append(dict(name=dst, family="calib", ops=0, bytes=numel(ins[0]) * esz[ins[0]] + numel(dst) * esz[dst]))
+            continue
+        if alias == "se_gate":  # (J2): the calib and the two 1x1 convs on 1 x 1 planes inside the hard_sigmoid instruction
+            o1, o2 = next(int8_ops), next(int8_ops)
+            esz[dst] = 4
+            wb = int(o1["w"].size) + int(o2["w"].size)
+            out.append(dict(name=dst, family="se_gate", ops=2 * batch * wb, bytes=numel(ins[0]) * 4 + wb + numel(dst) * 4))
             continue
         if op in ("conv2d", "depthwise_conv2d", "fc"):
             o = next(int8_ops)
@@ -390,6 +494,10 @@ def program_costs(net, batch, plan_lines):
         else:
             esz[dst] = 1 if "int8" in flags else 4
             fam = {"pool2d": "pool2d", "elementwise_add": "elementwise_add", "fusion_elementwise_add_activation": "elementwise_add",
-                   "softmax": "softmax"}[op]
-            out.append(dict(name=dst, family=fam, ops=0, bytes=sum(numel(i) * esz[i] for i in ins) + numel(dst) * esz[dst]))
+                   "softmax": "softmax", "hard_swish": "hard_act", "hard_sigmoid": "hard_act", "elementwise_mul": "se_scale"}[op]
+            byts = sum(numel(i) * esz[i] for i in ins) + (0 if "-f32" in flags else numel(dst) * esz[dst])
+            if "+calib" in kv:    # (J1) (J3): the int8 copy of the same launch
+                esz[kv["+calib"]] = 1
+                byts += numel(kv["+calib"])
+            out.append(dict(name=dst, family=fam, ops=0, bytes=byts))
     return out
