@@ -118,7 +118,10 @@ __global__ __launch_bounds__(256) void pool2d_max_i8_kernel(PoolArgs a) {
 // 3x3 stride-2 int8 max pool (ResNet50's pool1: 256 x 64 planes of 112x112 per step): the generic kernel above walks
 // its window byte by byte (0.27 ms, 0.9 TB/s).  Here a lane = 4 consecutive outputs of one row: 3 row windows of 12 bytes
 // (dw_load_row: unaligned 12-byte fetch, row / left-border clamping, byte masks), bytes outside the image become -128,
-// then 27 v_bfe_i32 + 9 + 4 v_max3_i32.  A window always holds a real element (pad <= 1 < kernel), so -128 never wins.
+// then 27 v_bfe_i32 + 9 + 4 v_max3_i32.  A window that starts inside the image holds a real element (top / left pad <= 1 <
+// kernel), so -128 never wins there.  The bottom / right pads are not bounded: a window that starts at or past row h or
+// column w covers padding only, and the kernel writes 0 for it, like pooling_basic and the generic kernel above (it used to
+// leave the -128 of its padding bytes there; the launcher's condition was kept, so such launches still come here).
 template <bool TAIL>
 __device__ __forceinline__ void pool3x3s2_max_i8_body(const PoolArgs& a, int idx, int owq, size_t plane) {
   const int oy = idx / owq, oxq = idx - oy * owq;
@@ -150,6 +153,7 @@ __device__ __forceinline__ void pool3x3s2_max_i8_body(const PoolArgs& a, int idx
   for (int i = 0; i < 4; ++i) {
     const int m = v[2 * i] > v[2 * i + 1] ? v[2 * i] : v[2 * i + 1];
     o[i] = m > v[2 * i + 2] ? m : v[2 * i + 2];
+    if (oy * 2 - a.pt >= a.h || start + 2 * i >= a.w) o[i] = 0;  // the window covers padding only
   }
   const int ox0 = oxq * 4;
   if (ox0 + 3 < a.ow && (((uintptr_t)(yp + ox0)) & 3) == 0) {

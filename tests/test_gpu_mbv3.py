@@ -6,6 +6,7 @@ import importlib
 import numpy as np
 import pytest
 
+import glue_cases as G
 import mbv3_oracle as M
 
 pytestmark = pytest.mark.gpu
@@ -123,7 +124,8 @@ def _se_pairs(wl):
 @pytest.mark.parametrize("batch", [1, 3, 128])
 def test_se_gate_equals_the_separate_calls(gpu_ctx, pkg, wl, batch):
     """plhip_se_gate_int8 against calib -> conv 1x1 [int8] -> conv 1x1 [fp32] -> hard_sigmoid through the separate C ABI calls,
-    byte for byte, over every (C, Cr) pair of both networks; the gate must use both clamps and the ramp."""
+    byte for byte, over every (C, Cr) pair of both networks; the gate must use both clamps and the ramp.  Then over pairs outside
+    the tables (glue_cases.SE_EXTRA_PAIRS): the kernel promises any C, Cr in 8..960."""
     capi = pkg.capi
     pairs = _se_pairs(wl)
     assert (72, 24) in pairs and (960, 240) in pairs and (16, 8) in pairs and len(pairs) >= 11
@@ -162,6 +164,34 @@ def test_se_gate_equals_the_separate_calls(gpu_ctx, pkg, wl, batch):
     y = gpu_ctx.conv2d(capi.conv_desc(batch, cr, 1, 1, c, 1, 1), mid, w2, s2, None, capi.OUT_F32)
     want, _ = gpu_ctx.hard_act(capi.HARD_SIGMOID, y.reshape(batch, c))
     assert np.array_equal(_bits(gpu_ctx.se_gate(pooled, 0.025, w1, s1, None, capi.ACT_RELU, 0.0, w2, s2, None)), _bits(want))
+    # outside the network tables: C and Cr that are no multiples of 4 (both int8 vectors are zero padded in k), the ends of
+    # the 8..960 envelope.  Nonzero weights in the last input channel of each conv: a padding byte that is not zero moves a gate.
+    rng = np.random.default_rng(380 + batch)
+    for (c, cr) in G.SE_EXTRA_PAIRS:
+        assert (c, cr) not in pairs
+        pooled = rng.uniform(-0.5, 3.0, (batch, c)).astype(F32)
+        scale = F32(3.0 / 127)
+        w1 = rng.integers(-127, 128, (cr, c, 1, 1)).astype(np.int8)
+        w2 = rng.integers(-127, 128, (c, cr, 1, 1)).astype(np.int8)
+        w1[:, -1][w1[:, -1] == 0] = 77
+        w2[:, -1][w2[:, -1] == 0] = -77
+        var1, var2 = (1 + np.arange(cr) % 7 / 8.0), (1 + np.arange(c) % 7 / 8.0)
+        s1 = (var1 * 40.0 / (np.sqrt(c) * 60 * 73)).astype(F32)
+        b1 = rng.uniform(-20, 20, cr).astype(F32)
+        s2 = (var2 * 2.8 / (np.sqrt(cr) * 30 * 73)).astype(F32)
+        b2 = rng.uniform(-1, 1, c).astype(F32)
+        for act1, alpha1 in ((capi.ACT_RELU, 0.0), (capi.ACT_RELU6, 90.0)):
+            assert gpu_ctx.L.plhip_se_gate_supported(c, cr, act1, capi.ACT_NONE) == 1, (c, cr)
+            q = gpu_ctx.calib_f32_to_i8(pooled.reshape(batch, c, 1, 1), float(scale))
+            mid = gpu_ctx.conv2d(capi.conv_desc(batch, c, 1, 1, cr, 1, 1, act=act1, alpha=alpha1), q, w1, s1, b1, capi.OUT_I8)
+            y = gpu_ctx.conv2d(capi.conv_desc(batch, cr, 1, 1, c, 1, 1), mid, w2, s2, b2, capi.OUT_F32)
+            want, _ = gpu_ctx.hard_act(capi.HARD_SIGMOID, y.reshape(batch, c))
+            got = gpu_ctx.se_gate(pooled, float(scale), w1, s1, b1, act1, alpha1, w2, s2, b2)
+            assert np.array_equal(_bits(got), _bits(want)), "c %d cr %d batch %d act %d: %d gates differ" % (
+                c, cr, batch, act1, (_bits(got) != _bits(want)).sum())
+            _same_f32(want, M.hard_sigmoid(y.reshape(batch, c)), "hard_sigmoid of the separate calls")
+            if batch * c >= 48:
+                assert ((got > 0) & (got < 1)).any(), (c, cr)  # gates on the ramp: every accumulator bit shows
 
 
 def test_kernel_classes_through_the_factory(lite):
