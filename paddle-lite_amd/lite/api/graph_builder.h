@@ -105,9 +105,10 @@ class GraphBuilder {
   const std::vector<GraphOp>& ops() const { return ops_; }
 
  private:
+  enum class StepKind { kOp, kIoCopyH2D, kIoCopyD2H, kCalibF2I, kCalibI2F, kImageToTensor, kImageConvert, kImageResize, kSeGate };
   struct Step {
     int op{-1};              // index into ops_, or -1 for an inserted instruction
-    std::string kind;        // "op", "io_copy_h2d", "io_copy_d2h", "calib_f2i", "calib_i2f", "image_to_tensor", "image_convert", "image_resize", "se_gate"
+    StepKind kind{StepKind::kOp};
     std::string in, out;
     float scale{0.f};
     bool int8_out{false};
@@ -133,11 +134,18 @@ class GraphBuilder {
     bool image_int8{false};   // image_to_tensor that took the calib behind it over (H2): int8 output, `scale` the calib's
     bool resize_tensor{false};  // image_resize that took the image_to_tensor behind it over (I); image_int8: and the calib behind that
     bool resize_nv{false};      // ... and the image_convert in front: its source is the NV frame itself
-    // kind "se_gate" (J2): `in` the pooled tensor, `out` the gate, `scale` the calib's; op / pw_op the two convs in ops_, `via` the
+    // kind kSeGate (J2): `in` the pooled tensor, `out` the gate, `scale` the calib's; op / pw_op the two convs in ops_, `via` the
     // names of the three tensors that are no longer written
   };
+  struct Fuser;  // graph_builder.cc: the state the rewrites of FuseSteps share, one member function per rewrite
+  void FeedSteps(std::vector<Step>* steps) const;
+  void PickKernels(std::vector<bool>* int8_out, std::vector<float>* out_scale) const;  // pass 1, after checking the graph
   std::vector<Step> Schedule();
   void FuseSteps(std::vector<Step>* steps);
+  std::vector<Step> Program();  // Schedule(), then FuseSteps() unless set_fuse(false): what Plan() prints and Lower() emits
+  std::string OpLine(const Step& s) const;
+  ConvAttrs LoweredConvAttrs(const Step& s) const;
+  void LowerOp(const Step& s, HipPredictor* pred);
   struct FeedDesc {
     std::string name;
     std::vector<int64_t> dims;
