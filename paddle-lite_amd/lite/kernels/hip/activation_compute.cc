@@ -8,6 +8,7 @@
 // Alias se_gate (hard_sigmoid): fusion J2, the excite chain of a squeeze-excite block in one launch (se_gate_fusion.h).
 #include "lite/core/op_registry.h"
 #include "lite/kernels/hip/calib_tail.h"
+#include "lite/kernels/hip/quant_fold.h"
 #include "lite/kernels/hip/se_gate_fusion.h"
 #include "lite/operators/op_params.h"
 #include "plhip.h"
@@ -72,8 +73,15 @@ class SeGateCompute : public KernelLite<TARGET(kHIP), PRECISION(kFloat)>, public
     desc_.c = static_cast<int>(w1[1]);
     desc_.cr = static_cast<int>(w1[0]);
     desc_.calib_scale = fusion_.calib_scale;
-    Fold(fusion_.reduce, desc_.cr, true, fusion_.expand.input_scale, &s1_, &b1_, &has_b1_, &desc_.act1, &desc_.act1_alpha);
-    Fold(fusion_.expand, desc_.c, false, 1.f, &s2_, &b2_, &has_b2_, &desc_.act2, &desc_.act2_alpha);
+    // folded as two stand-alone conv2d (quant_fold.h): the reduce conv's int8 output scale is the expand conv's input scale
+    const auto& r = fusion_.reduce;
+    const auto& e = fusion_.expand;
+    const QuantFold f1 = FoldLayer(r.weight_scale, desc_.cr, r.input_scale, e.input_scale, true, r.bias, &r.activation_param, false);
+    const QuantFold f2 = FoldLayer(e.weight_scale, desc_.c, e.input_scale, 1.f, false, e.bias, &e.activation_param, false);
+    desc_.act1 = f1.act; desc_.act1_alpha = f1.alpha;
+    desc_.act2 = f2.act; desc_.act2_alpha = f2.alpha;
+    has_b1_ = UploadFold(f1, &s1_, &b1_);
+    has_b2_ = UploadFold(f2, &s2_, &b2_);
     if (!plhip_se_gate_supported(desc_.c, desc_.cr, desc_.act1, desc_.act2)) LOG(FATAL) << "se_gate: shape outside the fused kernel's envelope";
     auto& ctx = this->ctx_->As<HIPContext>();
     const size_t n1 = static_cast<size_t>(fusion_.reduce.filter->numel()), n2 = static_cast<size_t>(fusion_.expand.filter->numel());
@@ -101,39 +109,6 @@ class SeGateCompute : public KernelLite<TARGET(kHIP), PRECISION(kFloat)>, public
   void SetProfileRuntimeKernelInfo(profile::OpCharacter* ch) override { ch->kernel_func_name = "se_gate_int8_dot4_hip"; }
 
  private:
-  // scale / bias / activation folding exactly as ConvCompute folds a stand-alone conv2d (conv_gemmlike.cc:208-263)
-  static void Fold(const HipSeGateConv& c, int oc, bool int8_out, float out_scale, Tensor* scale, Tensor* bias, bool* has_bias, int* act,
-                   float* alpha) {
-    std::vector<float> ws = c.weight_scale;
-    if (ws.size() != 1 && ws.size() != static_cast<size_t>(oc)) LOG(FATAL) << "weights scale size must equal to filter size";
-    if (ws.size() == 1) ws.resize(oc, ws[0]);
-    const float in_scale = c.input_scale;
-    for (auto& v : ws) v = int8_out ? v * in_scale / out_scale : v * in_scale;
-    scale->Resize({oc});
-    TargetWrapperHip::MemcpySync(scale->mutable_data<float>(TARGET(kHIP)), ws.data(), oc * sizeof(float), IoDirection::HtoD);
-    *has_bias = c.bias != nullptr;
-    if (c.bias) {
-      CHECK_EQ(c.bias->numel(), oc) << "bias size must equal to filter number";
-      std::vector<float> b(oc);
-      TargetCopy(TARGET(kHost), c.bias->target(), b.data(), c.bias->raw_data(), oc * sizeof(float));
-      if (int8_out)
-        for (auto& v : b) v = v / out_scale;
-      bias->Resize({oc});
-      TargetWrapperHip::MemcpySync(bias->mutable_data<float>(TARGET(kHIP)), b.data(), oc * sizeof(float), IoDirection::HtoD);
-    }
-    *act = PLHIP_ACT_NONE;
-    *alpha = 0.f;
-    const auto& ap = c.activation_param;
-    if (ap.has_active) {
-      switch (ap.active_type) {
-        case lite_api::ActivationType::kRelu: *act = PLHIP_ACT_RELU; break;
-        case lite_api::ActivationType::kRelu6: *act = PLHIP_ACT_RELU6; *alpha = ap.Relu_clipped_coef; break;
-        case lite_api::ActivationType::kLeakyRelu: *act = PLHIP_ACT_LEAKY_RELU; *alpha = ap.Leaky_relu_alpha; break;
-        default: LOG(FATAL) << "this act_type: " << static_cast<int>(ap.active_type) << " fuse not support";
-      }
-    }
-    if (int8_out && *act == PLHIP_ACT_RELU6) *alpha = *alpha / out_scale;
-  }
   HipSeGateFusion fusion_;
   plhip_se_gate_desc desc_{};
   Tensor s1_, b1_, s2_, b2_, packed_;

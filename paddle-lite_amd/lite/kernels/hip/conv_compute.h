@@ -16,6 +16,18 @@ namespace lite {
 namespace kernels {
 namespace hip {
 
+// One conv as a launch takes it: the descriptor (desc.act / desc.act_alpha = the folded activation, quant_fold.h), the weights
+// (packed for the GEMM path, raw OIHW for the depthwise path; the process-wide shared copy where packed_weight_cache.h shares
+// them) and the folded per-channel scale and bias, all on the device.
+struct FoldedConv {
+  plhip_conv_desc desc{};
+  std::shared_ptr<Tensor> weights;
+  Tensor scale, bias;
+  bool has_bias{false};
+  const float* sc() const { return scale.data<float>(); }
+  const float* bi() const { return has_bias ? bias.data<float>() : nullptr; }
+};
+
 template <PrecisionType Ptype, PrecisionType OutType>
 class ConvCompute : public KernelLite<TARGET(kHIP), Ptype>, public HipFusableKernel {
  public:
@@ -28,30 +40,48 @@ class ConvCompute : public KernelLite<TARGET(kHIP), Ptype>, public HipFusableKer
   ~ConvCompute() override = default;
 
  private:
+  // What Run launches for the current input shape; ReInitWhenNeeded decides it (ResolveRoute), KernelFuncName names it.
+  enum class Route {
+    kImageStem,        // fusion H1: image_to_tensor + calib + conv in one launch
+    kCalibStem,        // fusion F: calib + conv in one launch
+    kConvTail,         // conv [fp32_out] with its residual add / calib copy
+    kDwConv1x1Fused,   // fusion G: depthwise + 1x1 conv with that conv's tail, one launch
+    kDwConv1x1Split,   //           ... the shape is outside the fused kernel: two launches through mid_
+    kDwPwFused,        // fusions D / E: depthwise + 1x1 conv (+ global average pool), one launch
+    kDwPwSplit,        //           ... two (three) launches through mid_ (mid2_)
+    kDepthwise,
+    kConv,
+  };
+  struct Tail {  // the graph tail of an fp32 conv output: residual operand, int8 copy
+    const float* residual{nullptr};
+    int8_t* calib_out{nullptr};
+  };
   void BuildDesc();
+  void PackWeights();
+  void PreparePointwise();
+  Route ResolveRoute();
+  std::string KernelFuncName() const;
+  const int8_t* Int8Input();
+  void* Output(bool int8, bool drop = false);
+  Tail GatherTail(bool f32);
+  const int8_t* DepthwiseIntoMid(const int8_t* x);
+  void RunStem();
+  void RunConvTail(const int8_t* x);
+  void RunDwConv1x1(const int8_t* x);
+  void RunDwPw(const int8_t* x);
+
   HipConvFusion fusion_;  // default-constructed = the plain conv of the reference
-  plhip_conv_desc desc_{};
+  FoldedConv conv_;       // the op's own conv
+  FoldedConv pw_;         // the 1x1 consumer a depthwise conv took over (HipConvFusion::pw_filter), its input plane from conv_.desc
   bool is_depthwise_{false};
   DDim last_shape_;
-  Tensor weights_;   // packed (GEMM path) or raw OIHW (depthwise path), on device
-  void PackWeights();
-  std::string packed_impl_;   // the implementation the weights are packed for, and their size: checked on every reshape
+  std::string packed_impl_;  // the implementation conv_.weights are packed for, and their size: checked on every reshape
   size_t packed_bytes_{0};
-  std::shared_ptr<Tensor> packed_owner_;  // the process-wide shared copy weights_ aliases (packed_weight_cache.h), if any
-  Tensor scale_;     // folded per-channel scale, device
-  Tensor bias_;      // folded bias, device (only if param.bias)
-  bool has_bias_{false};
-  float act_alpha_{0.f};
   size_t workspace_bytes_{0};
+  Route route_{Route::kConv};
   std::string kernel_func_name_{"NotImplForConv"};
-  // fused 1x1 consumer of a depthwise conv (HipConvFusion::pw_*): its descriptor, packed weights, folded scale / bias; `mid_`
-  // holds the depthwise result only when the shape is outside the fused kernel and the two kernels run instead
-  void PreparePointwise();
-  bool has_pw_{false}, pw_fused_{false}, pw_has_bias_{false};
-  plhip_conv_desc pw_desc_{};
-  Tensor pw_weights_, pw_scale_, pw_bias_, mid_, mid2_;
-  Tensor xq_;                      // fused calib in front (HipConvFusion::calib_input_scale) on a shape without the one-launch form
-  bool calib_in_fused_{false};     // ... or, with HipConvFusion::image_input, the image in front of it in the same launch
+  Tensor mid_, mid2_;              // the split routes' depthwise result (and the 1x1 conv's plane in front of the pool)
+  Tensor xq_;                      // the int8 input of a conv that took its calib (or image) over, on a shape without the one-launch form
   plhip_image_desc image_desc_{};  // HipConvFusion::image_input: the image, [n, h, w] from the descriptor
 };
 

@@ -5,6 +5,7 @@
 //   fc_compute.cc:154-163, which is a bug and is not reproduced); activation_type == "relu" only.
 // One device kernel serves every m (no gemv/gemm split) with a per-column scale.
 #include "lite/kernels/hip/packed_weight_cache.h"
+#include "lite/kernels/hip/quant_fold.h"
 #include <string>
 #include <vector>
 
@@ -46,46 +47,12 @@ class FcCompute : public KernelLite<TARGET(kHIP), Ptype> {
     // check_fc_use_gemm (fc_compute.cc:66-81): m > 1 and one weight scale -> gemm_s8, whose fp32 output gets its bias
     // from fill_bias_fc with a second rounding; otherwise gemv_int8 per row with one fused multiply-add
     single_scale_ = param.weight_scale.size() == 1;
-    std::vector<float> s(n_);
-    for (int j = 0; j < n_; ++j) {
-      const float ws = param.weight_scale[param.weight_scale.size() == 1 ? 0 : j];
-      s[j] = kInt8Out ? ws * param.input_scale / param.output_scale : ws * param.input_scale;
-    }
-    scale_.Resize({n_});
-    TargetWrapperHip::MemcpySync(scale_.mutable_data<float>(TARGET(kHIP)), s.data(), n_ * sizeof(float), IoDirection::HtoD);
-    has_bias_ = param.bias != nullptr;
-    if (has_bias_) {
-      CHECK_EQ(param.bias->numel(), n_);
-      std::vector<float> b(n_);
-      TargetCopy(TARGET(kHost), param.bias->target(), b.data(), param.bias->raw_data(), n_ * sizeof(float));
-      if (kInt8Out)
-        for (auto& v : b) v = v / param.output_scale;
-      bias_.Resize({n_});
-      TargetWrapperHip::MemcpySync(bias_.mutable_data<float>(TARGET(kHIP)), b.data(), n_ * sizeof(float), IoDirection::HtoD);
-    }
+    const QuantFold f = FoldLayer(param.weight_scale, n_, param.input_scale, param.output_scale, kInt8Out, param.bias, nullptr, false);
+    has_bias_ = UploadFold(f, &scale_, &bias_);
     // weight pre-pack [k,n] -> [k/4][n][4] (replaces the transpose of fc_compute.cc:53-62)
     // (one packed device copy per process and device, shared by the predictors that run the same model: packed_weight_cache.h)
-    const size_t wb = static_cast<size_t>(k_) * n_;
-    auto pack_into = [&](void* wp) {
-      Tensor staged;
-      const void* w_dev = param.w->raw_data();
-      if (param.w->target() != TARGET(kHIP)) {
-        void* d = staged.mutable_data(TARGET(kHIP), wb);
-        TargetWrapperHip::MemcpySync(d, param.w->raw_data(), wb, IoDirection::HtoD);
-        w_dev = d;
-      }
-      HIP_CALL(ctx.ctx(), plhip_pack_fc_weights(ctx.ctx(), k_, n_, static_cast<const int8_t*>(w_dev), wp));
-      ctx.Sync();
-    };
-    const size_t packed = plhip_fc_packed_weight_bytes(k_, n_);
-    if (param.w->target() == TARGET(kHost)) {
-      packed_owner_ = PackedWeightCache::Global().GetOrPack(static_cast<int>(TargetWrapperHip::GetCurDevice()),
-                                                            "fc_" + std::to_string(k_) + "_" + std::to_string(n_), param.w->raw_data(), wb,
-                                                            packed, pack_into);
-      weights_.ShareDataWith(*packed_owner_);
-    } else {
-      pack_into(weights_.mutable_data(TARGET(kHIP), packed));
-    }
+    weights_ = PackThroughCache(&ctx, param.w, "fc_" + std::to_string(k_) + "_" + std::to_string(n_), plhip_fc_packed_weight_bytes(k_, n_),
+                           [&](const int8_t* w_dev, void* wp) { HIP_CALL(ctx.ctx(), plhip_pack_fc_weights(ctx.ctx(), k_, n_, w_dev, wp)); });
   }
 
   void Run() override {
@@ -102,7 +69,7 @@ class FcCompute : public KernelLite<TARGET(kHIP), Ptype> {
       kind = PLHIP_OUT_F32;
     }
     const bool gemm_route = OutType == PRECISION(kFloat) && m_ > 1 && single_scale_;
-    HIP_CALL(ctx.ctx(), plhip_fc_int8(ctx.ctx(), m_, k_, n_, param.input->template data<int8_t>(), weights_.raw_data(),
+    HIP_CALL(ctx.ctx(), plhip_fc_int8(ctx.ctx(), m_, k_, n_, param.input->template data<int8_t>(), weights_->raw_data(),
                                       scale_.data<float>(), has_bias_ ? bias_.data<float>() : nullptr,
                                       (relu_ ? 1 : 0) | (gemm_route ? 2 : 0), y, kind));
   }
@@ -116,8 +83,8 @@ class FcCompute : public KernelLite<TARGET(kHIP), Ptype> {
   DDim last_shape_;
   int m_{0}, k_{0}, n_{0};
   bool relu_{false}, has_bias_{false}, single_scale_{false};
-  Tensor weights_, scale_, bias_;
-  std::shared_ptr<Tensor> packed_owner_;  // the shared copy weights_ aliases, if any
+  Tensor scale_, bias_;
+  std::shared_ptr<Tensor> weights_;  // packed, on the device: the process-wide shared copy where the cache shares it
 };
 
 }  // namespace hip

@@ -15,6 +15,7 @@
 #include <string>
 #include <tuple>
 
+#include "lite/core/context.h"
 #include "lite/core/tensor.h"
 
 namespace paddle {
@@ -76,6 +77,33 @@ class PackedWeightCache {
   std::map<Key, std::weak_ptr<Tensor>> map_;
   long hits_{0}, misses_{0};
 };
+
+// The packed device copy of a layer's int8 weights `src`: `pack(raw, dst)` fills `packed_bytes` at dst from the raw weights
+// on the device.  Persistable params may still live on the host (the reference moves them with an io_copy_once instruction
+// inserted by type_target_cast_pass): they are staged on the device first, and are the ones shared through the cache under
+// `layout`; weights already on the device, and any weights under an empty `layout`, are packed privately.  Returns the
+// tensor that owns the bytes, final (the stream of `ctx` is synchronised): keep it for as long as kernels read them.
+inline std::shared_ptr<Tensor> PackThroughCache(HIPContext* ctx, const Tensor* src, const std::string& layout, size_t packed_bytes,
+                                           const std::function<void(const int8_t*, void*)>& pack) {
+  const size_t raw_bytes = static_cast<size_t>(src->numel());
+  auto pack_into = [&](void* dst) {
+    Tensor staged;
+    const void* raw = src->raw_data();
+    if (src->target() != TARGET(kHIP)) {
+      void* d = staged.mutable_data(TARGET(kHIP), raw_bytes);
+      TargetWrapperHip::MemcpySync(d, raw, raw_bytes, IoDirection::HtoD);
+      raw = d;
+    }
+    pack(static_cast<const int8_t*>(raw), dst);
+    ctx->Sync();  // the bytes are final (and `staged` may die) before anybody else sees them
+  };
+  if (!layout.empty() && src->target() == TARGET(kHost))
+    return PackedWeightCache::Global().GetOrPack(static_cast<int>(TargetWrapperHip::GetCurDevice()), layout, src->raw_data(), raw_bytes,
+                                                 packed_bytes, pack_into);
+  auto owner = std::make_shared<Tensor>();
+  pack_into(owner->mutable_data(TARGET(kHIP), packed_bytes));
+  return owner;
+}
 
 }  // namespace hip
 }  // namespace kernels

@@ -8,6 +8,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libpaddle_lite_hip.so")
 PREC_FLOAT, PREC_INT8, PREC_ANY = 1, 2, 4
+PREC_UINT8 = 9  # the uint8 image of graph_feed_image / graph_feed_frame (add_feed resizes it)
 LAYOUT_NCHW, LAYOUT_ANY = 1, 2
 # image formats of graph_feed_image == cv::ImageFormat (lite/utils/cv/paddle_image_preprocess.h) == plhip_image_format
 IMG_RGBA, IMG_BGRA, IMG_RGB, IMG_BGR, IMG_GRAY = 0, 1, 2, 3, 4

@@ -538,3 +538,80 @@ def test_fused_program_with_its_feed_resized_off_the_fused_kernels(lite, wl, plr
         assert sum("conv_depthwise_3x3_pointwise_1x1_fused" in n for n in p.kernel_names()) == 13
     finally:
         p.close()
+
+
+def _stem_net(wl):
+    """image 32 x 32 -> 3x3 stride-2 stem -> 1x1 conv -> global average pool -> fc: the stem takes the calib in front of it over
+    (fusion F), with an image feed the image_to_tensor too (fusion H1)."""
+    g = wl._NetGen(11)
+    g.tensor("image", 3, 32, 32, 1.0 / 127, 73.0)
+    x = g.conv("stem", "image", 32, 3, 2, 1)
+    x = g.conv("head", x, 64, 1, 1, 0)
+    x = g.pool("pool", x, "avg", 16, 1, 0, global_pooling=True)
+    return wl._finish(g, 32, g.fc("fc", x, 10))
+
+
+@pytest.mark.parametrize("feed", ["tensor", "image"])
+def test_stem_front_falls_back_inside_the_kernel_object(lite, wl, plref, pkg, feed):
+    """A stem that took its calib (tensor feed: fusion F) or image_to_tensor + calib (image feed: H1) over is lowered at 32 x 32, where
+    the one-launch form exists; then the feed is resized to 32 x 31 (W % 4 != 0: the form refuses; OW stays 16, so the conv keeps its
+    implementation and its packed weights).  The kernel object must run the front into its private int8 tensor and then the plain
+    conv, name exactly that (no one-launch prefix left over from the first shape) and produce the oracle's numbers; back at 32 x 32
+    the first result is reproduced."""
+    from test_image_feed_host import BGR, MEANS, SCALES, image_to_tensor_ref
+    net = _stem_net(wl)
+    rng = np.random.default_rng(370)
+    stem_impl = "conv_3x3s2_direct_int8_mfma32x32x32"
+    one_launch, fallback = {"tensor": ("calib_fp32_to_int8+", ""), "image": ("image_to_tensor_int8+", "image_to_tensor_int8_hip+")}[feed]
+
+    def make(w):
+        if feed == "tensor":
+            x = rng.uniform(-1, 1, (2, 3, 32, w)).astype(np.float32)
+            return x, x
+        src = rng.integers(0, 256, (2, 32, w, 3)).astype(np.uint8)
+        return src, image_to_tensor_ref(src, BGR, MEANS, SCALES)
+
+    def check(p, ref, out):
+        compared = []
+        for name, want in ref.items():
+            try:
+                got = p.get_var(name, want.dtype)
+            except Exception:  # noqa: BLE001  (a variable the fused program does not materialise)
+                continue
+            assert got.shape == want.shape, name
+            if want.dtype == np.int8:
+                assert np.array_equal(got, want), "%s: %d of %d int8 values differ" % (name, (got != want).sum(), want.size)
+            else:
+                np.testing.assert_allclose(got, want, rtol=1e-5, atol=1e-5, err_msg=name)
+            compared.append(name)
+        # the stem's int8 output is what the fallback makes: it must have been read back and compared bit for bit
+        assert ref["stem"].dtype == np.int8 and {"stem", "head", "pool"} <= set(compared), compared
+
+    def stem_kernel(p):
+        return [n for n in p.kernel_names() if n.startswith("conv2d")][0].split(" -> ")[1]
+
+    (in32, x32), (in31, x31) = make(32), make(31)
+    d = pkg.capi.conv_desc(2, 3, 32, 31, 32, 3, 3, (1, 1, 1, 1), (2, 2))
+    assert pkg.capi.load().plhip_conv_impl_name(d).decode() == stem_impl
+    p = lite.Predictor(0)
+    try:
+        out = wl.emit_graph(p, net, 2, image=dict(format=BGR, means=MEANS, scales=SCALES) if feed == "image" else None)
+        assert ("+calib_in=" if feed == "tensor" else "+image_in=") in p.graph_plan()[1], p.graph_plan()[:3]
+        assert p.graph_lower() == [out]
+        p.set_input(net["input"], in32)
+        p.run()
+        assert stem_kernel(p) == one_launch + stem_impl
+        check(p, graph_oracle.forward(plref, net, x32), out)
+        first = p.get_var(out[:-len("/host")], np.float32)
+        p.add_feed(net["input"], in31.shape, lite.PREC_FLOAT if feed == "tensor" else lite.PREC_UINT8)
+        p.set_input(net["input"], in31)
+        p.run()
+        assert stem_kernel(p) == fallback + stem_impl
+        check(p, graph_oracle.forward(plref, net, x31), out)
+        p.add_feed(net["input"], in32.shape, lite.PREC_FLOAT if feed == "tensor" else lite.PREC_UINT8)
+        p.set_input(net["input"], in32)
+        p.run()
+        assert stem_kernel(p) == one_launch + stem_impl
+        assert np.array_equal(p.get_var(out[:-len("/host")], np.float32), first)
+    finally:
+        p.close()
