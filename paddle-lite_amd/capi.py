@@ -128,7 +128,7 @@ _lib = None
 # Diagnostic knobs this PROCESS set through plhip_debug_set (the library itself never reads the environment).  The binding
 # forwards PLHIP_<KNOB>=<int> variables of the A/B scripts (tools/*.sh) explicitly and records them here;
 # bench.py prints the dict in its JSON line, so a measurement taken with a knob says so.  The same keys, in the same order, as
-# the library's knob table (plhip_capi.hip); STAMPS exists in a `make EXPERIMENTS=1` build only, a default one refuses it.
+# the library's knob table (plhip_capi_ctx.hip); STAMPS exists in a `make EXPERIMENTS=1` build only, a default one refuses it.
 KNOBS = ("STEM_MFMA", "CONV_PATCH", "CONV_PATCH_S2", "STEM7", "DW_STAGE", "DW_STAGE_NP2", "DW_FASTV", "DW5_DIRECT", "DW_RS1",
          "DW_RS2", "GEMM_VARIANT", "GEMM_AREG", "GEMM_MA", "SUBSAMPLE_1X1", "GEMM_TR", "TR_CFG", "GEMM_WIDE", "WIDE_NTT", "FC_MFMA",
          "IMPLICIT_GEMM", "FUSED_STREAM", "FUSED_SMALL", "DWCONV_FUSED", "STAMPS")

@@ -694,6 +694,43 @@ static void launch_dw_t(const DwArgs& a, int fast, unsigned blocks, size_t lds, 
   }
 }
 
+// Tiling of the LDS-band kernel from the shape fields of `a`: a block covers PB planes x OB output rows; aim at ~2K quads (8 per
+// thread) per block and keep the LDS tile under 48 KiB so that several blocks share a CU.  Fills PB, OB, bands, in_rows, pitch;
+// false: a single row band does not fit in LDS (60 KiB).
+bool depthwise_plan(DwArgs* a) {
+  const int owq = (a->ow + 3) / 4;
+  const int OFF = (a->pl + 3) / 4 * 4;
+  const int maxcol = (4 * owq - 1) * a->sw - a->pl + (a->kw - 1) * a->dw + OFF;
+  const int pitch = ((maxcol > OFF + a->w ? maxcol : OFF + a->w) + 1 + 16 + 3) / 4 * 4;
+  const int target = 2048;
+  int OB, PB;
+  if (a->oh * owq >= target) {
+    PB = 1;
+    OB = target / owq;
+    if (OB < 1) OB = 1;
+    if (OB > a->oh) OB = a->oh;
+  } else {
+    OB = a->oh;
+    PB = target / (a->oh * owq);
+    if (PB < 1) PB = 1;
+    if (PB > 64) PB = 64;
+    if (PB > a->planes) PB = a->planes;
+  }
+  auto in_rows_of = [&](int ob) { return (ob - 1) * a->sh + (a->kh - 1) * a->dh + 1; };
+  auto lds_of = [&](int pb, int ob) {
+    return (size_t)pb * in_rows_of(ob) * pitch + (size_t)pb * a->kh * 8 + (size_t)pb * 8 + (size_t)pb * a->kh * a->kw + 16;
+  };
+  while (lds_of(PB, OB) > 48 * 1024 && PB > 1) PB = PB / 2;
+  while (lds_of(PB, OB) > 48 * 1024 && OB > 1) OB = (OB + 1) / 2;
+  if (lds_of(PB, OB) > 60 * 1024) return false;
+  a->PB = PB;
+  a->OB = OB;
+  a->bands = (a->oh + OB - 1) / OB;
+  a->in_rows = in_rows_of(OB);
+  a->pitch = pitch;
+  return true;
+}
+
 int launch_depthwise(const DwArgs& a, int out, hipStream_t s) {
   if (launch_dw_direct(a, out, s)) return 0;
   int fast = 0;

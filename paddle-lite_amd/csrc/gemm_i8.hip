@@ -652,7 +652,7 @@ __global__ __launch_bounds__(256) void im2col_i8_kernel(Im2colArgs a) {
   *reinterpret_cast<uint32_t*>(a.col + row * a.Np + (size_t)q4 * 4) = out;
 }
 
-// ---- host-side launchers (called from plhip_capi.hip) ----
+// ---- host-side launchers (called from plhip_capi_conv.hip) ----
 static int gemm_variant() {  // PLHIP_GEMM_VARIANT: 0 auto, 1 private-tile kernel, 2 register-staged LDS kernel, 3 LDS-DMA ring
   const int v = knob("GEMM_VARIANT", 0);
   return v;
@@ -754,7 +754,7 @@ int launch_gemm_i8(const GemmArgs& g_in, int ma, int out, bool vec_store, bool a
     if (launch_gemm_tr(t, out, s)) return 0;
     // stride-2 / short-row implicit GEMMs exist on that kernel ONLY: the first-generation kernels would read outside their
     // operands for these shapes.  conv_geom admits them under the same column-space bound launch_gemm_tr checks
-    // (plhip_capi.hip), so this is a defensive error, not a fallback
+    // (plhip_capi_conv.hip), so this is a defensive error, not a fallback
     if (tr_only) return -3;
   }
   if (ma == 2 && ((ma_env == 0 && g.M <= 128 && g.M > 64) || (ma_env == 1 && g.im_kw == 0))) ma = 1;

@@ -1,0 +1,153 @@
+// plhip_capi_ops.hip — the C ABI (include/plhip.h), part 4 of 4: fc, calib, pooling, softmax, elementwise add, the hard activations
+// and squeeze-excite.  Argument validation and one launch each.
+#include "plhip_capi.h"
+
+extern "C" {
+
+// ------------------------------------------------------------------ fc
+size_t plhip_fc_packed_weight_bytes(int k, int n) {
+  if (k < 1 || n < 1) return 0;
+  return plhip::fc_packed_bytes(k, n);  // [dot4 layout][MFMA A fragments]
+}
+
+plhip_status plhip_pack_fc_weights(plhip_ctx* ctx, int k, int n, const int8_t* w_kn, void* w_packed) {
+  if (!ctx || !w_kn || !w_packed || k < 1 || n < 1) return fail(ctx, PLHIP_ERR_INVALID, "plhip_pack_fc_weights: bad argument");
+  plhip::launch_pack_fc(w_kn, (int8_t*)w_packed, k, n, ctx->stream);
+  LAUNCHCHK(ctx, "pack_fc");
+  return PLHIP_OK;
+}
+
+plhip_status plhip_fc_int8(plhip_ctx* ctx, int m, int k, int n, const int8_t* x, const void* w_packed, const float* scale,
+                           const float* bias, int relu, void* y, plhip_out_kind out) {
+  if (!ctx || !x || !w_packed || !y || m < 1 || k < 1 || n < 1) return fail(ctx, PLHIP_ERR_INVALID, "plhip_fc_int8: bad argument");
+  if (plhip_status st = check_out_scale_act(ctx, "plhip_fc_int8", out, false, scale, "scale", nullptr)) return st;
+  if (!aligned(w_packed, 4)) return fail(ctx, PLHIP_ERR_INVALID, "plhip_fc_int8: packed weights must be 4-byte aligned");
+  plhip::launch_fc(x, (const int8_t*)w_packed, scale, bias, y, m, k, n, relu, (int)out, ctx->stream);
+  LAUNCHCHK(ctx, "fc_i8");
+  return PLHIP_OK;
+}
+
+// ------------------------------------------------------------------ calib / pool / softmax
+plhip_status plhip_calib_f32_to_i8(plhip_ctx* ctx, const float* x, int8_t* y, float scale, int64_t count) {
+  if (!ctx || !x || !y || count < 0 || !(scale > 0.f)) return fail(ctx, PLHIP_ERR_INVALID, "plhip_calib_f32_to_i8: bad argument");
+  if (count == 0) return PLHIP_OK;
+  plhip::launch_calib_f32_to_i8(x, y, scale, count, ctx->stream);
+  LAUNCHCHK(ctx, "calib_f32_to_i8");
+  return PLHIP_OK;
+}
+
+plhip_status plhip_calib_i8_to_f32(plhip_ctx* ctx, const int8_t* x, float* y, float scale, int64_t count) {
+  if (!ctx || !x || !y || count < 0) return fail(ctx, PLHIP_ERR_INVALID, "plhip_calib_i8_to_f32: bad argument");
+  if (count == 0) return PLHIP_OK;
+  plhip::launch_calib_i8_to_f32(x, y, scale, count, ctx->stream);
+  LAUNCHCHK(ctx, "calib_i8_to_f32");
+  return PLHIP_OK;
+}
+
+plhip_status plhip_global_avg_pool_f32(plhip_ctx* ctx, const float* x, int nc, int spatial, float* y) {
+  if (!ctx || !x || !y || nc < 1 || spatial < 1) return fail(ctx, PLHIP_ERR_INVALID, "plhip_global_avg_pool_f32: bad argument");
+  plhip::launch_global_avg_pool(x, nc, spatial, y, ctx->stream);
+  LAUNCHCHK(ctx, "global_avg_pool");
+  return PLHIP_OK;
+}
+
+plhip_status plhip_softmax_f32(plhip_ctx* ctx, const float* x, int rows, int cols, float* y) {
+  if (!ctx || !x || !y || rows < 1 || cols < 1) return fail(ctx, PLHIP_ERR_INVALID, "plhip_softmax_f32: bad argument");
+  plhip::launch_softmax(x, rows, cols, y, ctx->stream);
+  LAUNCHCHK(ctx, "softmax");
+  return PLHIP_OK;
+}
+
+static plhip_status pool2d_impl(plhip_ctx* ctx, const plhip_pool_desc* d, const void* x, void* y, bool i8);
+plhip_status plhip_pool2d_f32(plhip_ctx* ctx, const plhip_pool_desc* d, const float* x, float* y) {
+  return pool2d_impl(ctx, d, x, y, false);
+}
+plhip_status plhip_pool2d_max_i8(plhip_ctx* ctx, const plhip_pool_desc* d, const int8_t* x, int8_t* y) {
+  if (d && !d->is_max) return fail(ctx, PLHIP_ERR_UNSUPPORTED, "plhip_pool2d_max_i8: max pooling only (avg does not commute with the quantiser)");
+  return pool2d_impl(ctx, d, x, y, true);
+}
+static plhip_status pool2d_impl(plhip_ctx* ctx, const plhip_pool_desc* d, const void* x, void* y, bool i8) {
+  if (!ctx || !d || !x || !y) return fail(ctx, PLHIP_ERR_INVALID, "plhip_pool2d_f32: null argument");
+  if (d->planes < 1 || d->h < 1 || d->w < 1 || d->oh < 1 || d->ow < 1 || d->kh < 1 || d->kw < 1 || d->stride[0] < 1 ||
+      d->stride[1] < 1 || d->pad[0] < 0 || d->pad[1] < 0 || d->pad[2] < 0 || d->pad[3] < 0)
+    return fail(ctx, PLHIP_ERR_INVALID, "plhip_pool2d_f32: bad descriptor");
+  // every window must start inside the padded image (PoolOutputSize guarantees it, ceil_mode included; windows that
+  // only cover padding yield 0 like pooling_basic)
+  if ((d->oh - 1) * d->stride[0] - d->pad[0] >= d->h + d->pad[1] || (d->ow - 1) * d->stride[1] - d->pad[2] >= d->w + d->pad[3])
+    return fail(ctx, PLHIP_ERR_INVALID, "plhip_pool2d_f32: output dims do not match the window geometry");
+  if ((size_t)d->h * d->w >= ((size_t)1 << 31) || (size_t)d->oh * d->ow >= ((size_t)1 << 31))
+    return fail(ctx, PLHIP_ERR_UNSUPPORTED, "plhip_pool2d_f32: plane too large");
+  plhip::PoolArgs a;
+  a.x = (const float*)x; a.y = (float*)y;
+  a.planes = d->planes; a.h = d->h; a.w = d->w; a.oh = d->oh; a.ow = d->ow; a.kh = d->kh; a.kw = d->kw;
+  a.sh = d->stride[0]; a.sw = d->stride[1]; a.pt = d->pad[0]; a.pb = d->pad[1]; a.pl = d->pad[2]; a.pr = d->pad[3];
+  a.is_max = d->is_max ? 1 : 0; a.exclusive = d->exclusive ? 1 : 0;
+  if (i8) plhip::launch_pool2d_max_i8(a, ctx->stream);
+  else plhip::launch_pool2d(a, ctx->stream);
+  LAUNCHCHK(ctx, "pool2d");
+  return PLHIP_OK;
+}
+
+plhip_status plhip_elementwise_add_f32(plhip_ctx* ctx, const float* x, const float* y, float* out, int64_t count, int relu) {
+  if (!ctx || !x || !y || !out || count < 0) return fail(ctx, PLHIP_ERR_INVALID, "plhip_elementwise_add_f32: bad argument");
+  if (count == 0) return PLHIP_OK;
+  plhip::launch_eltwise_add(x, y, out, count, relu, ctx->stream);
+  LAUNCHCHK(ctx, "elementwise_add");
+  return PLHIP_OK;
+}
+
+plhip_status plhip_hard_act_f32(plhip_ctx* ctx, plhip_hard_act_kind kind, const float* params, const float* x, float* y_f32,
+                                int8_t* y_i8, float calib_scale, int64_t count) {
+  if (!ctx || !params || !x || (!y_f32 && !y_i8) || count < 0 || (y_i8 && !(calib_scale > 0.f)))
+    return fail(ctx, PLHIP_ERR_INVALID, "plhip_hard_act_f32: bad argument");
+  if (kind != PLHIP_HARD_SWISH && kind != PLHIP_HARD_SIGMOID) return fail(ctx, PLHIP_ERR_UNSUPPORTED, "plhip_hard_act_f32: unknown kind");
+  if (count == 0) return PLHIP_OK;
+  plhip::launch_hard_act(kind == PLHIP_HARD_SWISH ? plhip::HARD_ACT_SWISH : plhip::HARD_ACT_SIGMOID, params, x, y_f32, y_i8,
+                         calib_scale, count, ctx->stream);
+  LAUNCHCHK(ctx, "hard_act");
+  return PLHIP_OK;
+}
+
+plhip_status plhip_se_scale_f32(plhip_ctx* ctx, const float* x, const float* gate, int n, int c, int hw, float* y_f32, int8_t* y_i8,
+                                float calib_scale) {
+  if (!ctx || !x || !gate || (!y_f32 && !y_i8) || n < 1 || c < 1 || hw < 1 || (y_i8 && !(calib_scale > 0.f)))
+    return fail(ctx, PLHIP_ERR_INVALID, "plhip_se_scale_f32: bad argument");
+  const int64_t planes = (int64_t)n * c;
+  if (planes > ((int64_t)1 << 30)) return fail(ctx, PLHIP_ERR_UNSUPPORTED, "plhip_se_scale_f32: too many planes");
+  plhip::launch_se_scale(x, gate, y_f32, y_i8, calib_scale, planes, hw, ctx->stream);
+  LAUNCHCHK(ctx, "se_scale");
+  return PLHIP_OK;
+}
+
+static bool se_gate_act_ok(int act) { return act == PLHIP_ACT_NONE || act == PLHIP_ACT_RELU || act == PLHIP_ACT_RELU6 || act == PLHIP_ACT_LEAKY_RELU; }
+int plhip_se_gate_supported(int c, int cr, int act1, int act2) {
+  return c >= 8 && cr >= 8 && c <= plhip::SE_GATE_MAX_C && cr <= plhip::SE_GATE_MAX_C && se_gate_act_ok(act1) && se_gate_act_ok(act2);
+}
+size_t plhip_se_gate_packed_weight_bytes(int c, int cr) { return c < 1 || cr < 1 ? 0 : plhip::se_gate_packed_bytes(c, cr); }
+plhip_status plhip_pack_se_gate_weights(plhip_ctx* ctx, int c, int cr, const int8_t* w1, const int8_t* w2, void* w_packed) {
+  if (!ctx || !w1 || !w2 || !w_packed || !aligned(w_packed, 4)) return fail(ctx, PLHIP_ERR_INVALID, "plhip_pack_se_gate_weights: bad argument");
+  if (!plhip_se_gate_supported(c, cr, 0, 0)) return fail(ctx, PLHIP_ERR_UNSUPPORTED, "plhip_pack_se_gate_weights: c / cr outside 8..960");
+  plhip::launch_se_gate_pack(w1, w2, w_packed, c, cr, ctx->stream);
+  LAUNCHCHK(ctx, "se_gate_pack");
+  return PLHIP_OK;
+}
+plhip_status plhip_se_gate_int8(plhip_ctx* ctx, const plhip_se_gate_desc* d, const float* pooled, const void* w_packed,
+                                const float* scale1, const float* bias1, const float* scale2, const float* bias2, float* gate) {
+  if (!ctx || !d || !pooled || !w_packed || !scale1 || !scale2 || !gate || d->n < 1 || !(d->calib_scale > 0.f) || !aligned(w_packed, 4))
+    return fail(ctx, PLHIP_ERR_INVALID, "plhip_se_gate_int8: bad argument");
+  if (!plhip_se_gate_supported(d->c, d->cr, d->act1, d->act2)) return fail(ctx, PLHIP_ERR_UNSUPPORTED, "plhip_se_gate_int8: outside the envelope");
+  plhip::SeGateArgs a;
+  a.pooled = pooled;
+  a.inv = 1.f / d->calib_scale;  // type_trans.cc:45, as launch_calib_f32_to_i8
+  a.w1 = static_cast<const uint32_t*>(w_packed);
+  a.w2 = a.w1 + (size_t)((d->c + 3) / 4) * d->cr;
+  a.s1 = scale1; a.b1 = bias1; a.s2 = scale2; a.b2 = bias2;
+  a.act1 = d->act1; a.act2 = d->act2; a.alpha1 = d->act1_alpha; a.alpha2 = d->act2_alpha;
+  a.slope = d->slope; a.offset = d->offset;
+  a.gate = gate; a.c = d->c; a.cr = d->cr;
+  plhip::launch_se_gate(a, d->n, ctx->stream);
+  LAUNCHCHK(ctx, "se_gate");
+  return PLHIP_OK;
+}
+
+}  // extern "C"

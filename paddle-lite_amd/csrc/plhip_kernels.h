@@ -228,6 +228,8 @@ void launch_wide_n7(const GemmArgs& g, int out, hipStream_t s);
 void launch_wide_n8(const GemmArgs& g, int out, hipStream_t s);  // 4 / 7 / 8 force that tile, 0 = automatic, -1 = back to the environment's choice
 void launch_pack_weights(const int8_t* w, int8_t* wp, int G, int Mg, int Kg, int MT32, int KS, hipStream_t s);
 void launch_im2col(const Im2colArgs& a, hipStream_t s);
+// fills the LDS tiling (PB, OB, bands, in_rows, pitch) from the shape fields; false = a single row band does not fit in LDS
+bool depthwise_plan(DwArgs* a);
 int launch_depthwise(const DwArgs& a, int out, hipStream_t s);  // returns 0 or -3 (unsupported LDS size)
 
 // direct 3x3 stride-2 convolution for small Cin (network stems)

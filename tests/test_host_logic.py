@@ -27,8 +27,8 @@ def test_removed_and_experiment_only_knobs_are_refused(pkg):
 
 
 def test_binding_knobs_match_the_library_table(pkg):
-    """capi.KNOBS forwards exactly the keys of the knob table in plhip_capi.hip, in its order."""
-    src = open(os.path.join(ROOT, "paddle-lite_amd", "csrc", "plhip_capi.hip")).read()
+    """capi.KNOBS forwards exactly the keys of the knob table in plhip_capi_ctx.hip, in its order."""
+    src = open(os.path.join(ROOT, "paddle-lite_amd", "csrc", "plhip_capi_ctx.hip")).read()
     table = re.search(r"Knob g_knobs\[\] = \{(.*?)\n\};", src, re.S).group(1)
     assert list(pkg.capi.KNOBS) == re.findall(r'\{"(\w+)", 0, false\}', table)
 
