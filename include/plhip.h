@@ -100,11 +100,19 @@ plhip_status plhip_event_destroy(plhip_ctx* ctx, void* event);
  * 5263-5457) with its fused epilogue (:643-796).
  *
  * Weight pre-pack replaces prepackA_int8 (gemm_prepacked_int8.cc:109-224) / trans_gemm_weights<kInt8>
- * (conv_block_utils.h:65-73): OIHW int8 -> per-group MFMA A-fragment order, zero padded. */
+ * (conv_block_utils.h:65-73): OIHW int8 -> per-group MFMA A-fragment order, zero padded.
+ *
+ * Grouped 3x3 ("conv_grouped3x3_int8_mfma32x32x32"): 3x3, dilation 1, stride (1,1) or (2,2), every padding 0 or 1,
+ * groups >= 4, cin / groups == cout / groups in {4, 8, 16, 32} and cin % 32 == 0 (ResNeXt, RegNet), any n, h, w, every
+ * output kind, activation and fused tail.  One launch on the input itself for all groups, where the reference loops
+ * conv_im2col_gemm_int8's im2col + gemm_prepack_int8 over the groups (conv_impl.cc:490-598).  Packed weights: per chunk of 32
+ * consecutive channels (32 / Cg whole groups) and filter tap one 32x32 MFMA A fragment, zero outside the groups' diagonal
+ * blocks: (cin / 32) * 9 * 1024 bytes.  plhip_conv_workspace_bytes is 0 for it.  Other grouped shapes (groups 2, 1x1, dilated,
+ * cin / groups != cout / groups) keep the per-group GEMMs of the 1x1 / im2col routes. */
 size_t plhip_conv_packed_weight_bytes(const plhip_conv_desc* d);
 plhip_status plhip_pack_conv_weights(plhip_ctx* ctx, const plhip_conv_desc* d,
                                      const int8_t* w_oihw, void* w_packed);
-/* Scratch (0 for 1x1 s1 p0 and the small-Cin 3x3 / 7x7 s2 stems): the zero-padded input copy of the implicit-GEMM route
+/* Scratch (0 for 1x1 s1 p0, the small-Cin 3x3 / 7x7 s2 stems and the grouped 3x3 route): the zero-padded input copy of the implicit-GEMM route
  * (dense k x k, stride 1 or 2, wide enough GEMM: ~1.1x the input) or the im2col buffer (everything else: kh*kw x the
  * input); replaces ctx.workspace_data (conv_gemmlike.cc:131).  The caller passes at least this many bytes, 16-byte aligned
  * (4 suffices for every route but the dense 3x3 patch kernel's padded / phase-split copy). */
@@ -344,7 +352,8 @@ plhip_status plhip_selftest(plhip_ctx* ctx);
 /* ---- diagnostics: switches of the shipped library are set HERE, never through the environment, so that a stray variable
  * cannot change which kernel a benchmark measures.  Keys: the A/B knobs of DESIGN.md 3.6 without their former PLHIP_ prefix
  * ("GEMM_WIDE", "CONV_PATCH", "DW_STAGE", ...).  Each selects one of several kernels or tiles that compute the same result;
- * "DWCONV_FUSED" = 0: plhip_dw_conv1x1_fused_supported refuses every shape, so callers run the two instructions.  A
+ * "DWCONV_FUSED" = 0: plhip_dw_conv1x1_fused_supported refuses every shape, so callers run the two instructions;
+ * "CONV_GROUPED" = 0: the grouped 3x3 route takes no descriptor, grouped convs run im2col + one GEMM per group.  A
  * `make EXPERIMENTS=1` build also accepts "STAMPS" (in-kernel timelines).  Returns 0, or -1 for an unknown key. ---- */
 int plhip_debug_set(const char* key, int value);
 

@@ -131,7 +131,7 @@ _lib = None
 # the library's knob table (plhip_capi_ctx.hip); STAMPS exists in a `make EXPERIMENTS=1` build only, a default one refuses it.
 KNOBS = ("STEM_MFMA", "CONV_PATCH", "CONV_PATCH_S2", "STEM7", "DW_STAGE", "DW_STAGE_NP2", "DW_FASTV", "DW5_DIRECT", "DW_RS1",
          "DW_RS2", "GEMM_VARIANT", "GEMM_AREG", "GEMM_MA", "SUBSAMPLE_1X1", "GEMM_TR", "TR_CFG", "GEMM_WIDE", "WIDE_NTT", "FC_MFMA",
-         "IMPLICIT_GEMM", "FUSED_STREAM", "FUSED_SMALL", "DWCONV_FUSED", "STAMPS")
+         "IMPLICIT_GEMM", "FUSED_STREAM", "FUSED_SMALL", "DWCONV_FUSED", "CONV_GROUPED", "STAMPS")
 KNOBS_SET = {}
 
 

@@ -67,7 +67,7 @@ struct ConvIo {  // the operands of one conv2d call
 
 size_t out_elem_size(plhip_out_kind out) { return out == PLHIP_OUT_I8 ? 1 : 4; }
 
-// the fused tail of the argument structs that spell it alike: GemmArgs, PatchArgs, DirectS2Args, DwConvArgs
+// the fused tail of the argument structs that spell it alike: GemmArgs, PatchArgs, GroupedArgs, DirectS2Args, DwConvArgs
 template <class Args>
 void set_tail(Args& a, const ConvTail* t) {
   a.res = t ? t->residual : nullptr;
@@ -306,6 +306,34 @@ plhip_status run_patch_any(plhip_ctx* ctx, Desc d, Geom g, const ConvIo& io, boo
 plhip_status run_patch(plhip_ctx* ctx, Desc d, Geom g, const ConvIo& io) { return run_patch_any(ctx, d, g, io, false); }
 plhip_status run_patch_s2(plhip_ctx* ctx, Desc d, Geom g, const ConvIo& io) { return run_patch_any(ctx, d, g, io, true); }
 
+// ------------------------------------------------------------------ grouped 3x3 (conv_grouped_i8.hip)
+// Cg == Mg in {4, 8, 16, 32}, groups >= 4, Cin % 32 == 0, stride 1 | 2: cin / 32 block-diagonal dense 32 -> 32 convs in ONE launch
+// on the input itself (no im2col buffer, no padded copy) instead of an im2col launch and one GEMM launch per group
+bool takes_grouped3x3(Desc d, Geom) {
+  return plhip::conv_grouped3x3_supported(d->cin, d->cout, d->kh, d->kw, d->stride[0], d->stride[1], d->dil[0], d->dil[1], d->groups,
+                                          d->pad) &&
+         plhip::knob("CONV_GROUPED", 1) != 0;  // knob CONV_GROUPED = 0: A/B runs against the im2col route
+}
+size_t grouped3x3_packed_bytes(Desc d, Geom) { return plhip::conv_grouped3x3_packed_bytes(d->cin); }
+plhip_status pack_grouped3x3(plhip_ctx* ctx, Desc d, Geom, const int8_t* w_oihw, void* w_packed) {
+  plhip::launch_pack_conv_grouped3x3(w_oihw, (int8_t*)w_packed, d->cin, d->groups, ctx->stream);
+  return PLHIP_OK;
+}
+plhip_status run_grouped3x3(plhip_ctx* ctx, Desc d, Geom g, const ConvIo& io) {
+  if (!aligned(io.w_packed, 16)) return fail(ctx, PLHIP_ERR_INVALID, "plhip_conv2d_int8: packed weights must be 16-byte aligned");
+  plhip::GroupedArgs a;
+  memset(&a, 0, sizeof(a));
+  a.x = io.x; a.wp = (const int8_t*)io.w_packed; a.y = io.y; a.scale = io.scale; a.bias = io.bias;
+  a.n = d->n; a.cin = d->cin; a.cout = d->cout; a.h = d->h; a.w = d->w; a.oh = g.oh; a.ow = g.ow;
+  a.pt = d->pad[0]; a.pl = d->pad[2]; a.stride = d->stride[0];
+  a.act = d->act; a.alpha = d->act_alpha;
+  set_tail(a, io.tail);
+  if (!plhip::conv_grouped3x3_plan(&a)) return fail(ctx, PLHIP_ERR_UNSUPPORTED, "plhip_conv2d_int8: grouped 3x3 grid too large");
+  plhip::launch_conv_grouped3x3(a, (int)io.out, ctx->stream);
+  LAUNCHCHK(ctx, "conv_grouped3x3");
+  return PLHIP_OK;
+}
+
 // ------------------------------------------------------------------ implicit GEMM on a zero-padded copy of the input
 // dense k x k stride-1 convs whose GEMM fits the LDS-DMA ring kernel (64-row wave tiles: M > 128, 32-row tiles: 96 < M <=
 // 128 with K >= 256) skip the im2col buffer: 1.08x the input instead of kh*kw x (BASELINE config #2 spent 128 of 149 us writing
@@ -359,10 +387,11 @@ const char* name_direct_s2(Desc d, Geom g) {  // one MFMA K-step when the taps f
 const char* name_stem7(Desc, Geom) { return "conv_7x7s2_direct_int8_mfma32x32x32"; }
 const char* name_patch(Desc, Geom) { return "conv_patch_gemm_int8_mfma32x32x32"; }
 const char* name_patch_s2(Desc, Geom) { return "conv_patch_s2_gemm_int8_mfma32x32x32"; }
+const char* name_grouped3x3(Desc, Geom) { return "conv_grouped3x3_int8_mfma32x32x32"; }
 const char* name_implicit(Desc, Geom) { return "conv_implicit_gemm_int8_mfma32x32x32"; }
 const char* name_im2col(Desc, Geom) { return "conv_im2col_gemm_int8_mfma32x32x32"; }
 
-enum ConvImpl { IMPL_GEMM_1X1, IMPL_DIRECT_3X3S2, IMPL_STEM_7X7S2, IMPL_PATCH_GEMM, IMPL_PATCH_S2, IMPL_IMPLICIT_GEMM, IMPL_IM2COL_GEMM };
+enum ConvImpl { IMPL_GEMM_1X1, IMPL_DIRECT_3X3S2, IMPL_STEM_7X7S2, IMPL_PATCH_GEMM, IMPL_PATCH_S2, IMPL_GROUPED_3X3, IMPL_IMPLICIT_GEMM, IMPL_IM2COL_GEMM };
 
 struct ConvRoute {
   ConvImpl impl;
@@ -381,6 +410,7 @@ const ConvRoute kRoutes[] = {
     {IMPL_STEM_7X7S2, takes_stem7, stem7_packed_bytes, no_workspace, pack_stem7, run_stem7, name_stem7},
     {IMPL_PATCH_GEMM, takes_patch, patch_packed_bytes, patch_input_bytes, pack_patch, run_patch, name_patch},
     {IMPL_PATCH_S2, takes_patch_s2, patch_s2_packed_bytes, patch_s2_input_bytes, pack_patch_s2, run_patch_s2, name_patch_s2},
+    {IMPL_GROUPED_3X3, takes_grouped3x3, grouped3x3_packed_bytes, no_workspace, pack_grouped3x3, run_grouped3x3, name_grouped3x3},
     {IMPL_IMPLICIT_GEMM, takes_implicit, gemm_packed_bytes, padded_input_bytes, pack_gemm, run_implicit, name_implicit},
     {IMPL_IM2COL_GEMM, takes_im2col, gemm_packed_bytes, im2col_bytes, pack_gemm, run_im2col, name_im2col},
 };

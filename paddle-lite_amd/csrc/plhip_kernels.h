@@ -124,6 +124,35 @@ size_t conv_patch_s2_packed_bytes(int cin, int cout);
 void launch_pack_conv_patch_s2(const int8_t* w_oihw, int8_t* wp, int cin, int cout, hipStream_t s);
 void launch_pad_phase8(PadArgs a, hipStream_t s);
 
+// grouped 3x3 convolution, Cg == Mg in {4, 8, 16, 32}, Cin % 32 == 0, stride 1 | 2 (conv_grouped_i8.hip)
+struct GroupedArgs {
+  const int8_t* x;     // [n][cin][h][w]: the kernel stages its rows itself, zero borders included
+  const int8_t* wp;    // packed weights [cin / 32 chunks][9 taps][64 lanes][16 B], block-diagonal (launch_pack_conv_grouped3x3)
+  void* y;             // [n][cout][oh][ow] int8 / fp32 / int32 (may be nullptr with y2)
+  const float* scale;  // [cout] folded per-channel scale (unused for I32)
+  const float* bias;   // [cout] or nullptr
+  int n, cin, cout, h, w, oh, ow, pt, pl, stride;
+  int act;
+  float alpha;
+  // fused tail of an fp32-output conv (OUT_F32 only), as GemmArgs
+  const float* res;
+  int res_relu;
+  int8_t* y2;
+  float inv_scale2;
+  // launch plan (conv_grouped3x3_plan): 32-channel chunks; a block = TR output rows x CWq column quads of one (image, chunk);
+  // bands of TR rows and segments of CWq quads per plane; staged input rows IR of 4 * stride * WQ pixels; bytes between the LDS
+  // images of channels 0..15 and 16..31; LDS bytes
+  int NCH, TR, CWq, bands, nseg, IR, WQ, half;
+  unsigned nblocks, nblocks_per_xcd;
+  size_t lds;
+};
+bool conv_grouped3x3_supported(int cin, int cout, int kh, int kw, int sh, int sw, int dh, int dw, int groups, const int pad[4]);
+size_t conv_grouped3x3_packed_bytes(int cin);
+void launch_pack_conv_grouped3x3(const int8_t* w_oihw, int8_t* wp, int cin, int groups, hipStream_t s);
+// fills the plan from (n, cin, oh, ow, stride); false = more blocks than a grid holds
+bool conv_grouped3x3_plan(GroupedArgs* a);
+void launch_conv_grouped3x3(const GroupedArgs& a, int out, hipStream_t s);
+
 struct Im2colArgs {
   const int8_t* x;
   int8_t* col;

@@ -231,6 +231,29 @@ def resnet50_net(seed=50, res=224, num_classes=NUM_CLASSES):
     return _finish(g, res, x)
 
 
+def resnext50_net(seed=54, res=224, groups=32, base_width=4, num_classes=NUM_CLASSES):
+    """ResNeXt50 (32x4d by default): resnet50_net with branch2a / branch2b of groups * base_width * 2^stage channels (128, 256,
+    512, 1024) and `groups` on the 3x3 branch2b; the stride sits on the 3x3, as there."""
+    g = _NetGen(seed)
+    g.tensor("image", 3, res, res, 1.0 / 127, 73.0)
+    x = g.conv("conv1", "image", 64, 7, 2, 3, act=1)
+    x = g.pool("pool1", x, "max", 3, 2, 1)
+    for si, (width, blocks, stride) in enumerate([(64, 3, 1), (128, 4, 2), (256, 6, 2), (512, 3, 2)]):
+        inner = groups * base_width * 2 ** si
+        for b in range(blocks):
+            p = "res%d%s" % (si + 2, "abcdef"[b])
+            s = stride if b == 0 else 1
+            y = g.conv(p + "_branch2a", x, inner, 1, 1, 0, act=1)
+            y = g.conv(p + "_branch2b", y, inner, 3, s, 1, groups=groups, act=1)
+            y = g.conv(p + "_branch2c", y, 4 * width, 1, 1, 0, act=0)
+            sc = g.conv(p + "_branch1", x, 4 * width, 1, s, 0, act=0) if b == 0 else x
+            x = g.add(p, sc, y, act="relu")
+    x = g.pool("pool5", x, "avg", 7, 1, 0, global_pooling=True)
+    x = g.fc("fc", x, num_classes)
+    x = g.softmax("prob", x)
+    return _finish(g, res, x)
+
+
 MBV2_SETTING = [(1, 16, 1, 1), (6, 24, 2, 2), (6, 32, 3, 2), (6, 64, 4, 2), (6, 96, 3, 1), (6, 160, 3, 2), (6, 320, 1, 1)]
 
 

@@ -1,9 +1,11 @@
 #!/usr/bin/env python3
 """Per-op micro-benchmark through the C ABI (device-resident buffers, HIP events on the ctx stream).
-Usage: python tools/opbench.py [pw|dw|conv1|s2|all|<layer name>] [--batch 128] [--reps 30] [--net mobilenet_v1|dw5x5|resnet50_3x3]
+Usage: python tools/opbench.py [pw|dw|conv1|s2|all|<layer name>] [--batch 128] [--reps 30] [--net mobilenet_v1|dw5x5|resnet50_3x3|resnext50_3x3]
 Prints one line per layer: time, algorithmic GB/s, TOP/s.  --net dw5x5: depthwise 5x5 stride 1 / 2 planes (the shapes of
 lite/tests/math/conv_int8_compute_test.cc's 5x5 depthwise sweep at network sizes); --net resnet50_3x3: BASELINE config #2
-(at its own batch 32) and ResNet50's dense 3x3 layers."""
+(at its own batch 32) and ResNet50's dense 3x3 layers; --net resnext50_3x3: the seven distinct grouped 3x3 shapes of ResNeXt50-32x4d
+(int8 output, as the network runs them), the grouped route against the im2col route (knob CONV_GROUPED = 1 / 0) alternating in
+this one process: median of --rounds windows of --reps calls each, after a warm-up of both."""
 import argparse
 import ctypes as C
 import os
@@ -38,6 +40,65 @@ def time_op(ctx, fn, reps):
     return ms.value / reps
 
 
+# ResNeXt50-32x4d's grouped 3x3 convs: (name, channels, input plane, stride), 32 groups, padding 1
+RESNEXT50_3X3 = [("res2", 128, 56, 1), ("res3a", 256, 56, 2), ("res3", 256, 28, 1), ("res4a", 512, 28, 2), ("res4", 512, 14, 1),
+                 ("res5a", 1024, 14, 2), ("res5", 1024, 7, 1)]
+
+
+def resnext_ab(args):
+    """One line per shape: median time of the grouped route and of the im2col route (its im2col launch and 32 GEMM launches
+    included), their ratio, and the algorithmic bytes (input + output + filter) over each time."""
+    rng = np.random.default_rng(0)
+    B, groups = args.batch, 32
+    out_kind, esz = (capi.OUT_F32, 4) if args.f32 else (capi.OUT_I8, 1)
+    tot = [0.0, 0.0]
+    print("# batch %d, %s output, %d rounds x %d calls per route, alternating; time = median window / calls" % (
+        B, "fp32" if args.f32 else "int8", args.rounds, args.reps))
+    print("%-6s %-18s %12s %12s %7s %9s %10s %10s" % ("layer", "shape", "grouped us", "im2col us", "ratio", "MB", "grp TB/s", "i2c TB/s"))
+    with capi.Context(0) as ctx:
+        L = ctx.L
+        for name, c, hin, s in RESNEXT50_3X3:
+            if args.what not in ("all", name) and not (args.what == "s2" and s == 2):
+                continue
+            ho = (hin + 2 - 3) // s + 1
+            d = capi.conv_desc(B, c, hin, hin, c, 3, 3, (1, 1, 1, 1), (s, s), (1, 1), groups, capi.ACT_RELU, 0.0)
+            w = rng.integers(-127, 128, (c, c // groups, 3, 3), dtype=np.int8)
+            dx, dw = ctx.to_device(rng.integers(-127, 128, (B, c, hin, hin), dtype=np.int8)), ctx.to_device(w)
+            ds, db = ctx.to_device(np.full(c, 1e-4, np.float32)), ctx.to_device(np.zeros(c, np.float32))
+            dy = ctx.malloc(B * c * ho * ho * esz)
+            route = {}
+            for knob in (1, 0):  # each route's own packed weights and workspace
+                assert L.plhip_debug_set(b"CONV_GROUPED", knob) == 0
+                impl = L.plhip_conv_impl_name(C.byref(d)).decode()
+                dwp = ctx.malloc(L.plhip_conv_packed_weight_bytes(C.byref(d)))
+                ctx.check(L.plhip_pack_conv_weights(ctx.h, C.byref(d), dw, dwp), "pack")
+                wsb = L.plhip_conv_workspace_bytes(C.byref(d))
+                route[knob] = (impl, dwp, ctx.malloc(wsb) if wsb else C.c_void_p(), wsb)
+            assert route[1][0] != route[0][0], route
+
+            def window(knob, reps):
+                L.plhip_debug_set(b"CONV_GROUPED", knob)
+                _, dwp, dws, wsb = route[knob]
+                return time_op(ctx, lambda: ctx.check(L.plhip_conv2d_int8(ctx.h, C.byref(d), dx, dwp, ds, db, dy, out_kind, dws, wsb), "conv"), reps)
+
+            for knob in (1, 0):
+                window(knob, 5)  # warm-up of both routes
+            ms = {1: [], 0: []}
+            for _ in range(args.rounds):
+                for knob in (1, 0):
+                    ms[knob].append(window(knob, args.reps))
+            L.plhip_debug_set(b"CONV_GROUPED", 1)
+            g, i = float(np.median(ms[1])), float(np.median(ms[0]))
+            byts = B * (c * hin * hin + c * ho * ho * esz) + w.size
+            tot[0] += g
+            tot[1] += i
+            print("%-6s %4dx%3dx%-3d s%d g%d %12.2f %12.2f %7.2f %9.1f %10.2f %10.2f" % (
+                name, c, hin, hin, s, groups, g * 1e3, i * 1e3, i / g, byts / 1e6, byts / g / 1e9, byts / i / 1e9), flush=True)
+            for q in list(ctx._allocs):
+                ctx.free(q)
+    print("total  grouped %.2f us  im2col %.2f us  ratio %.2f" % (tot[0] * 1e3, tot[1] * 1e3, tot[1] / max(tot[0], 1e-9)))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("what", nargs="?", default="all")
@@ -45,7 +106,10 @@ def main():
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--f32", action="store_true", help="fp32 output instead of int8")
     ap.add_argument("--net", default="mobilenet_v1")
+    ap.add_argument("--rounds", type=int, default=7, help="resnext50_3x3: alternating windows per route")
     args = ap.parse_args()
+    if args.net == "resnext50_3x3":
+        return resnext_ab(args)
     rng = np.random.default_rng(0)
     B = args.batch
     tot = 0.0
