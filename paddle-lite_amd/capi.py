@@ -135,6 +135,19 @@ KNOBS = ("STEM_MFMA", "CONV_PATCH", "CONV_PATCH_S2", "STEM7", "DW_STAGE", "DW_ST
 KNOBS_SET = {}
 
 
+TAIL_RESIDUAL, TAIL_INT8_COPY, TAIL_NO_F32 = 1, 2, 4
+
+
+def gemm_plan_text(d, out, tail=0):
+    """The GEMM launch plan (csrc/gemm_plan.h) the library makes for conv descriptor d with output kind `out` and the fused tail
+    `tail` (TAIL_* bits) under the knobs in force, assuming aligned pointers: 'name family=... grid=... lds=...'.  '' for a conv
+    on a non-GEMM route.  Host only: launches nothing, needs no context."""
+    buf = C.create_string_buffer(512)
+    if load().plhip_debug_gemm_plan(C.byref(d), int(out), int(tail), buf, len(buf)) < 0:
+        raise PlhipError("plhip_debug_gemm_plan: bad conv descriptor")
+    return buf.value.decode()
+
+
 def load():
     """dlopen libplhip.so and declare prototypes.  Raises if the library is absent (no CPU fallback)."""
     global _lib
@@ -197,6 +210,11 @@ def load():
     L.plhip_conv2d_image_int8.argtypes = [vp, C.POINTER(ConvDesc), C.POINTER(ImageDesc), vp, f32, vp, vp, vp, vp, i32]
     L.plhip_conv_impl_name.argtypes = [C.POINTER(ConvDesc)]
     L.plhip_conv_impl_name.restype = C.c_char_p
+    # diagnostics outside include/plhip.h: the GEMM launch plan of a conv as text (gemm_plan_text below), the wide tile override
+    L.plhip_debug_gemm_plan.argtypes = [C.POINTER(ConvDesc), i32, i32, C.c_char_p, sz]
+    L.plhip_debug_gemm_plan.restype = i32
+    L.plhip_debug_wide_ntt.argtypes = [i32]
+    L.plhip_debug_wide_ntt.restype = None
     L.plhip_depthwise_conv_int8.argtypes = [vp, C.POINTER(ConvDesc), vp, vp, vp, vp, vp, i32]
     L.plhip_dwpw_fused_int8.argtypes = [vp, C.POINTER(ConvDesc), vp, vp, vp, vp, i32, vp, vp, vp, i32, f32, vp, i32]
     L.plhip_dwpw_fused_supported.argtypes = [C.POINTER(ConvDesc), i32, i32]

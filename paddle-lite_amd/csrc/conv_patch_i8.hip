@@ -135,23 +135,8 @@ __global__ __launch_bounds__(256) void pad_rows8_i8_kernel(PadArgs a) {
 }
 
 void launch_pad_rows8(PadArgs a, hipStream_t s) {  // a.pw % 8 == 0, a.total % 16 == 0, a.xp 16-byte aligned
-  unsigned m;
-  int sh;
-  auto magic = [&](long d) {
-    int l = 0;
-    while ((1L << l) < d) ++l;
-    if ((1L << l) == d) {
-      m = 0;
-      sh = l;
-    } else {
-      m = (unsigned)(((1ULL << (31 + l)) / (unsigned long long)d) + 1ULL);
-      sh = l - 1;
-    }
-  };
-  magic((long)a.ph * a.pw);
-  a.div_plane_m = m; a.div_plane_s = sh;
-  magic(a.pw);
-  a.div_pw_m = m; a.div_pw_s = sh;
+  fastdiv_magic((long)a.ph * a.pw, a.div_plane_m, a.div_plane_s);
+  fastdiv_magic(a.pw, a.div_pw_m, a.div_pw_s);
   long blocks = ((a.total >> 4) + 255) / 256;
   if (blocks > 65536) blocks = 65536;
   blocks = (blocks + 7) & ~7L;  // whole rounds over the 8 XCDs (the kernel's block map)
@@ -269,45 +254,24 @@ __global__ __launch_bounds__(256) void pad_phase8_i8_kernel(PadArgs a) {
   }
 }
 void launch_pad_phase8(PadArgs a, hipStream_t s) {  // a.pw % 8 == 0, a.total % 16 == 0, a.xp 16-byte aligned, a.tc = 4 C
-  unsigned m;
-  int sh;
-  auto magic = [&](long d) {
-    int l = 0;
-    while ((1L << l) < d) ++l;
-    if ((1L << l) == d) {
-      m = 0;
-      sh = l;
-    } else {
-      m = (unsigned)(((1ULL << (31 + l)) / (unsigned long long)d) + 1ULL);
-      sh = l - 1;
-    }
-  };
-  magic((long)a.ph * a.pw);
-  a.div_plane_m = m; a.div_plane_s = sh;
-  magic(a.pw);
-  a.div_pw_m = m; a.div_pw_s = sh;
-  magic(a.tc);
-  a.div_ph_m = m; a.div_ph_s = sh;
-  magic(a.tb > 0 ? a.tb : 1);
-  a.div_pwq_m = m; a.div_pwq_s = sh;
+  fastdiv_magic((long)a.ph * a.pw, a.div_plane_m, a.div_plane_s);
+  fastdiv_magic(a.pw, a.div_pw_m, a.div_pw_s);
+  fastdiv_magic(a.tc, a.div_ph_m, a.div_ph_s);
+  fastdiv_magic(a.tb > 0 ? a.tb : 1, a.div_pwq_m, a.div_pwq_s);
   long blocks = ((a.total >> 4) + 255) / 256;
   if (blocks > 65536) blocks = 65536;
   blocks = (blocks + 7) & ~7L;
   hipLaunchKernelGGL(pad_phase8_i8_kernel, dim3((unsigned)blocks), dim3(256), 0, s, a);
 }
 
-// fastdiv_u31's (magic, shift) for divisor d (dw_common.h); general_pow2: the multiply form for powers of two as well
-// (d >= 2: magic 2^31 + 1, shift l - 1), for device code that must not branch on the marker 0
+// fastdiv_magic (dw_common.h); general_pow2: the multiply form for powers of two as well (d >= 2: magic 2^31 + 1, shift l - 1),
+// for device code that must not branch on the marker 0
 static inline void magic_u31(long d, unsigned& m, int& sh, bool general_pow2 = false) {
-  int l = 0;
-  while ((1L << l) < d) ++l;
-  if ((1L << l) == d && !(general_pow2 && d >= 2)) {
-    m = 0;
-    sh = l;
-    return;
+  fastdiv_magic(d, m, sh);
+  if (general_pow2 && m == 0 && d >= 2) {
+    m = 0x80000001u;
+    sh -= 1;
   }
-  m = (unsigned)(((1ULL << (31 + l)) / (unsigned long long)d) + 1ULL);
-  sh = l - 1;
 }
 
 void launch_conv_patch(PatchArgs a, int out, hipStream_t s) {

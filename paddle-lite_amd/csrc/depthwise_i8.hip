@@ -604,17 +604,9 @@ static void launch_dw_direct_s(const DwArgs& a_in, int rs, hipStream_t s) {
   a.owq_log2 = lg2(owq);
   a.spp_log2 = lg2(spp);
   a.fast_div = a.owq_log2 >= 0 && a.spp_log2 >= 0 && lg2(a.C) >= 0;
-  auto magic = [&](long d, unsigned& m, int& sh) {
-    const int l = lg2(d);
-    if (l >= 0) { m = 0; sh = l; return; }
-    int sc = 0;
-    while ((1L << sc) < d) ++sc;  // ceil(log2 d)
-    m = (unsigned)(((1ULL << (31 + sc)) / (unsigned long long)d) + 1ULL);
-    sh = sc - 1;
-  };
-  magic(owq, a.div_owq_m, a.div_owq_s);
-  magic(spp, a.div_spp_m, a.div_spp_s);
-  magic(a.C, a.div_c_m, a.div_c_s);
+  fastdiv_magic(owq, a.div_owq_m, a.div_owq_s);
+  fastdiv_magic(spp, a.div_spp_m, a.div_spp_s);
+  fastdiv_magic(a.C, a.div_c_m, a.div_c_s);
   // output staging through LDS: int8 output, narrow planes, a wave = whole strips, strips = whole rows of the plane
   const int stage_env = knob("DW_STAGE", 1);
   // (owq a power of two: a wave = 64 lanes = whole strips; otherwise a wave uses (64 / owq) * owq lanes: 63 of 64 on

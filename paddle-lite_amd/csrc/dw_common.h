@@ -1,6 +1,27 @@
 // dw_common.h — device helpers shared by the depthwise kernels (depthwise_i8.hip) and the fused depthwise -> pointwise
 // kernel (fused_dwpw_i8.hip): the unaligned row-window fetch and the 4-wide int8 requantisation.
 #pragma once
+#include <stdint.h>
+
+namespace plhip {
+
+// host: the (magic, shift) pair fastdiv_u31 divides by d with, 1 <= d < 2^31.  A power of two: magic 0, shift log2 d; else
+// magic = floor(2^(31 + l) / d) + 1 with l = ceil(log2 d), shift l - 1: exact for every n < 2^31.
+inline void fastdiv_magic(long d, unsigned& m, int& sh) {
+  int l = 0;
+  while ((1L << l) < d) ++l;
+  if ((1L << l) == d) {
+    m = 0;
+    sh = l;
+    return;
+  }
+  m = (unsigned)(((1ULL << (31 + l)) / (unsigned long long)d) + 1ULL);
+  sh = l - 1;
+}
+
+}  // namespace plhip
+
+#ifdef __HIPCC__  // the rest is device code (the host half above also compiles alone: tests/test_gemm_plan_host.py)
 #include "plhip_device.h"
 
 namespace plhip {
@@ -101,3 +122,4 @@ __device__ __forceinline__ void dw_load_row(const int8_t* __restrict__ xplane, i
 }
 
 }  // namespace plhip
+#endif  // __HIPCC__

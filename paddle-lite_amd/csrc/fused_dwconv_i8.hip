@@ -223,19 +223,6 @@ __global__ __launch_bounds__(DC_THREADS) void dw_conv1x1_fused_kernel(DwConvArgs
   }
 }
 
-// exact n / d for n < 2^31 (fastdiv_u31's pair; magic 0 = power of two)
-static void dc_magic(long d, unsigned& m, int& sh) {
-  int l = 0;
-  while ((1L << l) < d) ++l;
-  if ((1L << l) == d) {
-    m = 0;
-    sh = l;
-    return;
-  }
-  m = (unsigned)(((1ULL << (31 + l)) / (unsigned long long)d) + 1ULL);
-  sh = l - 1;
-}
-
 static void dc_stage_plan(DwConvArgs* a, bool dword) {
   a->dword_stage = dword ? 1 : 0;
   a->wu = dword ? a->WP / 4 : a->WP;
@@ -276,12 +263,12 @@ bool dw_conv1x1_plan(DwConvArgs* a) {
   a->tpi = a->tr_tiles * a->cw_tiles;
   if ((long long)a->n * a->tpi >= (1ll << 31)) return false;
   dc_stage_plan(a, a->w % 4 == 0);
-  dc_magic(a->IR, a->ir_m, a->ir_s);
-  dc_magic(owq, a->owq_m, a->owq_s);
-  dc_magic(a->TR, a->tr_m, a->tr_s);
-  dc_magic(a->CW, a->cw_m, a->cw_s);
-  dc_magic(a->tpi, a->tpi_m, a->tpi_s);
-  dc_magic(a->cw_tiles, a->ctl_m, a->ctl_s);
+  fastdiv_magic(a->IR, a->ir_m, a->ir_s);
+  fastdiv_magic(owq, a->owq_m, a->owq_s);
+  fastdiv_magic(a->TR, a->tr_m, a->tr_s);
+  fastdiv_magic(a->CW, a->cw_m, a->cw_s);
+  fastdiv_magic(a->tpi, a->tpi_m, a->tpi_s);
+  fastdiv_magic(a->cw_tiles, a->ctl_m, a->ctl_s);
   return true;
 }
 

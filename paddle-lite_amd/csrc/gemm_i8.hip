@@ -1,10 +1,10 @@
 // gemm_i8.hip — int8 x int8 -> int32 GEMM on v_mfma_i32_32x32x32_i8 with NCHW-native operands and a fused
-// per-channel dequant/requant + bias + activation epilogue, plus the weight pre-pack and im2col kernels.
+// per-channel dequant/requant + bias + activation epilogue.  (The weight pre-pack, im2col and the padded copies: conv_glue_i8.hip;
+// which kernel runs a problem: gemm_plan.h.)
 //
 // Replaces (reference, ARM): gemm_prepack_int8 (lite/backends/arm/math/gemm_prepacked_int8.cc:5263-5457,
-// hot loop :2582-2744, epilogue :643-796), prepackA_int8 (:109-224), packb_int8 (:3285),
-// im2col<int8_t> (lite/backends/arm/math/conv_impl.cc:103-153) and the batch/group driver loops of
-// conv1x1s1_gemm_int8 / conv_im2col_gemm_int8 (conv_impl.cc:260-331, 490-598).
+// hot loop :2582-2744, epilogue :643-796), packb_int8 (:3285) and the batch/group driver loops of
+// conv1x1s1_gemm_int8 / conv_im2col_gemm_int8 (lite/backends/arm/math/conv_impl.cc:260-331, 490-598).
 //
 // Shape mapping (conv_impl.cc:275-299): per group  Y[b] (M x N) = W (M x K) * X[b] (K x N),
 // M = cout/g, K = cin/g*kh*kw, N = oh*ow.  Unlike the reference, the batch is folded into N
@@ -78,12 +78,30 @@ __device__ __forceinline__ void load_b(const int8_t* __restrict__ xb, int ks, in
   }
 }
 
+// the 16 raw row dwords of a lane (K rows 16h .. 16h+15, columns 4c .. 4c+3) -> its four B fragments (fragment i = column 4c+i,
+// 16 K-contiguous bytes)
+__device__ __forceinline__ void transpose_b16(const uint32_t (&raw)[16], v4i (&bf)[4]) {
+#pragma unroll
+  for (int jg = 0; jg < 4; ++jg) {
+    uint32_t o0, o1, o2, o3;
+    transpose4x4_b8(raw[4 * jg], raw[4 * jg + 1], raw[4 * jg + 2], raw[4 * jg + 3], o0, o1, o2, o3);
+    bf[0][jg] = (int)o0;
+    bf[1][jg] = (int)o1;
+    bf[2][jg] = (int)o2;
+    bf[3][jg] = (int)o3;
+  }
+}
+
+// the fields every kernel of this file reads, live in the entry block (PLHIP_PRELOAD, plhip_device.h)
+#define PLHIP_PRELOAD_GEMM(g)                                                                                                  \
+  PLHIP_PRELOAD(g.wp); PLHIP_PRELOAD(g.x); PLHIP_PRELOAD(g.y); PLHIP_PRELOAD(g.scale); PLHIP_PRELOAD(g.bias);                  \
+  PLHIP_PRELOAD(g.M); PLHIP_PRELOAD(g.K); PLHIP_PRELOAD(g.KS); PLHIP_PRELOAD(g.HWX); PLHIP_PRELOAD(g.HWY); PLHIP_PRELOAD(g.XP); \
+  PLHIP_PRELOAD(g.NB); PLHIP_PRELOAD(g.x_bstride); PLHIP_PRELOAD(g.y_bstride); PLHIP_PRELOAD(g.MT); PLHIP_PRELOAD(g.NT);       \
+  PLHIP_PRELOAD(g.act); PLHIP_PRELOAD(g.alpha)
+
 template <int MA, int OUT, bool VEC_STORE, bool MFULL, bool ALIGNED>
 __global__ __launch_bounds__(256, 2) void gemm_i8_nchw_kernel(GemmArgs g) {
-  PLHIP_PRELOAD(g.wp); PLHIP_PRELOAD(g.x); PLHIP_PRELOAD(g.y); PLHIP_PRELOAD(g.scale); PLHIP_PRELOAD(g.bias);
-  PLHIP_PRELOAD(g.M); PLHIP_PRELOAD(g.K); PLHIP_PRELOAD(g.KS); PLHIP_PRELOAD(g.HWX); PLHIP_PRELOAD(g.HWY); PLHIP_PRELOAD(g.XP);
-  PLHIP_PRELOAD(g.NB); PLHIP_PRELOAD(g.x_bstride); PLHIP_PRELOAD(g.y_bstride); PLHIP_PRELOAD(g.MT); PLHIP_PRELOAD(g.NT);
-  PLHIP_PRELOAD(g.act); PLHIP_PRELOAD(g.alpha);
+  PLHIP_PRELOAD_GEMM(g);
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // wave-uniform for the compiler too
   const uint32_t wid = blockIdx.x * 4u + (uint32_t)wave;  // MT * NT < 2^31 (launcher)
@@ -114,15 +132,7 @@ __global__ __launch_bounds__(256, 2) void gemm_i8_nchw_kernel(GemmArgs g) {
   auto kbody = [&](int ks, auto first_c) {
     constexpr bool FIRST = decltype(first_c)::value;
     v4i bf[4];
-#pragma unroll
-    for (int jg = 0; jg < 4; ++jg) {
-      uint32_t o0, o1, o2, o3;
-      transpose4x4_b8(raw[4 * jg], raw[4 * jg + 1], raw[4 * jg + 2], raw[4 * jg + 3], o0, o1, o2, o3);
-      bf[0][jg] = (int)o0;
-      bf[1][jg] = (int)o1;
-      bf[2][jg] = (int)o2;
-      bf[3][jg] = (int)o3;
-    }
+    transpose_b16(raw, bf);
     v4i ac[MA];
 #pragma unroll
     for (int a = 0; a < MA; ++a) ac[a] = af[a];
@@ -156,10 +166,7 @@ __global__ __launch_bounds__(256, 2) void gemm_i8_nchw_kernel(GemmArgs g) {
 // register ring with static indices.
 template <int MA, int OUT, bool VEC_STORE, bool MFULL, bool ALIGNED>
 __global__ __launch_bounds__(256, 2) void gemm_i8_lds_kernel(GemmArgs g) {
-  PLHIP_PRELOAD(g.wp); PLHIP_PRELOAD(g.x); PLHIP_PRELOAD(g.y); PLHIP_PRELOAD(g.scale); PLHIP_PRELOAD(g.bias);
-  PLHIP_PRELOAD(g.M); PLHIP_PRELOAD(g.K); PLHIP_PRELOAD(g.KS); PLHIP_PRELOAD(g.HWX); PLHIP_PRELOAD(g.HWY); PLHIP_PRELOAD(g.XP);
-  PLHIP_PRELOAD(g.NB); PLHIP_PRELOAD(g.x_bstride); PLHIP_PRELOAD(g.y_bstride); PLHIP_PRELOAD(g.MT); PLHIP_PRELOAD(g.NT);
-  PLHIP_PRELOAD(g.act); PLHIP_PRELOAD(g.alpha);
+  PLHIP_PRELOAD_GEMM(g);
   __shared__ __attribute__((aligned(16))) v4i bs[2][4][4][64];  // [buf][kstep][i][lane] : 32 KiB
   __shared__ __attribute__((aligned(16))) float lsb_all[4][2 * MA * 32];
   const int lane = threadIdx.x & 63;
@@ -192,15 +199,7 @@ __global__ __launch_bounds__(256, 2) void gemm_i8_lds_kernel(GemmArgs g) {
 
   auto stage_write = [&](int buf) {  // transpose raw (this wave's K-step) into 4 fragments of bs[buf][wave]
     v4i bf[4];
-#pragma unroll
-    for (int jg = 0; jg < 4; ++jg) {
-      uint32_t o0, o1, o2, o3;
-      transpose4x4_b8(raw[4 * jg], raw[4 * jg + 1], raw[4 * jg + 2], raw[4 * jg + 3], o0, o1, o2, o3);
-      bf[0][jg] = (int)o0;
-      bf[1][jg] = (int)o1;
-      bf[2][jg] = (int)o2;
-      bf[3][jg] = (int)o3;
-    }
+    transpose_b16(raw, bf);
 #pragma unroll
     for (int i = 0; i < 4; ++i) bs[buf][wave][i][lane] = bf[i];
   };
@@ -293,10 +292,7 @@ __device__ __forceinline__ void wait_vmcnt() {
 template <int MA, int OUT, bool VEC_STORE, bool MFULL, int GD_D, int NG>
 __global__ __launch_bounds__(256, GD_D <= 4 ? 2 : 1) void gemm_i8_dma_kernel(GemmArgs g) {
   constexpr bool AREG = NG > 0;
-  PLHIP_PRELOAD(g.wp); PLHIP_PRELOAD(g.x); PLHIP_PRELOAD(g.y); PLHIP_PRELOAD(g.scale); PLHIP_PRELOAD(g.bias);
-  PLHIP_PRELOAD(g.M); PLHIP_PRELOAD(g.K); PLHIP_PRELOAD(g.KS); PLHIP_PRELOAD(g.HWX); PLHIP_PRELOAD(g.HWY); PLHIP_PRELOAD(g.XP);
-  PLHIP_PRELOAD(g.NB); PLHIP_PRELOAD(g.x_bstride); PLHIP_PRELOAD(g.y_bstride); PLHIP_PRELOAD(g.MT); PLHIP_PRELOAD(g.NT);
-  PLHIP_PRELOAD(g.act); PLHIP_PRELOAD(g.alpha);
+  PLHIP_PRELOAD_GEMM(g);
   PLHIP_PRELOAD(g.im_kw); PLHIP_PRELOAD(g.im_khkw); PLHIP_PRELOAD(g.im_c); PLHIP_PRELOAD(g.im_ph); PLHIP_PRELOAD(g.im_pw); PLHIP_PRELOAD(g.im_oh);
   constexpr int GD_NS = GD_D + 1;
   constexpr int SLOT = AREG ? 4096 : 4096 + 4 * MA * 1024;
@@ -452,17 +448,6 @@ __global__ __launch_bounds__(256, GD_D <= 4 ? 2 : 1) void gemm_i8_dma_kernel(Gem
       for (int a = 0; a < MA; ++a) af[a] = *reinterpret_cast<const v4i*>(sb + 4096 + (wave * MA + a) * 1024 + lane * 16);
     }
   };
-  auto transpose = [&](const uint32_t (&raw)[16], v4i (&bf)[4]) {
-#pragma unroll
-    for (int jg = 0; jg < 4; ++jg) {
-      uint32_t o0, o1, o2, o3;
-      transpose4x4_b8(raw[4 * jg], raw[4 * jg + 1], raw[4 * jg + 2], raw[4 * jg + 3], o0, o1, o2, o3);
-      bf[0][jg] = (int)o0;
-      bf[1][jg] = (int)o1;
-      bf[2][jg] = (int)o2;
-      bf[3][jg] = (int)o3;
-    }
-  };
 
   PLHIP_STAMP(3);
   uint32_t raw[16];
@@ -473,7 +458,7 @@ __global__ __launch_bounds__(256, GD_D <= 4 ? 2 : 1) void gemm_i8_dma_kernel(Gem
   wait_vmcnt<(AHEAD - 1) * PER>();
   __builtin_amdgcn_s_barrier();
   read_slot(0, raw, af_cur);
-  transpose(raw, bf_cur);
+  transpose_b16(raw, bf_cur);
 
   // one iteration; YOUNGER = my K-steps issued after ks+1 that may still be in flight at the wait, ISSUE / NEXT: whether
   // K-step ks+AHEAD / ks+1 exists (compile-time in the steady state and in the peeled tail)
@@ -502,7 +487,7 @@ __global__ __launch_bounds__(256, GD_D <= 4 ? 2 : 1) void gemm_i8_dma_kernel(Gem
       for (int i = 0; i < 4; ++i)
         acc[a][i] = __builtin_amdgcn_mfma_i32_32x32x32_i8(AREG ? aring[RI][a] : af_cur[a], bf_cur[i],
                                                           (AREG && FIRST) ? zero16 : acc[a][i], 0, 0, 0);
-    if (NEXT) transpose(raw, bf_nxt);
+    if (NEXT) transpose_b16(raw, bf_nxt);
     // schedule: [MFMA + one DMA piece] x (pieces issued here), bare MFMAs, then the remaining MFMAs share the transposes
     constexpr int NM = 4 * MA;
     constexpr int NDMA = AREG ? 1 : PER;  // LDS-DMA pieces issued among the first MFMAs
@@ -584,367 +569,74 @@ __global__ __launch_bounds__(256, GD_D <= 4 ? 2 : 1) void gemm_i8_dma_kernel(Gem
   }
 }
 
+// ---- host side: launch_gemm_i8 plans (gemm_plan.h) and executes; called from plhip_capi_conv.hip ----
+static int g_wide_ntt_override = -1;  // tests / A-B runs: plhip_debug_wide_ntt (-1 = the knob WIDE_NTT or automatic)
+void debug_set_wide_ntt(int v) { g_wide_ntt_override = v; }
 
-// ---- weight pre-pack: [G][Mg][Kg] row-major (OIHW flattened) -> [G][MT32][KS][64 lanes][16 B] ----
-// lane (r = lane&31, h = lane>>5), byte j  <-  W[g][mt32*32 + r][ks*32 + 16h + j]   (0 outside).
-__global__ void pack_weights_kernel(const int8_t* __restrict__ w, int8_t* __restrict__ wp, int G, int Mg, int Kg,
-                                    int MT32, int KS) {
-  const size_t total = (size_t)G * MT32 * KS * 1024;
-  for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
-    const int j = idx & 15;
-    const int lane = (idx >> 4) & 63;
-    size_t t = idx >> 10;
-    const int ks = t % KS;
-    t /= KS;
-    const int mt32 = t % MT32;
-    const int grp = (int)(t / MT32);
-    const int m = mt32 * 32 + (lane & 31);
-    const int k = ks * 32 + 16 * (lane >> 5) + j;
-    int8_t v = 0;
-    if (m < Mg && k < Kg) v = w[((size_t)grp * Mg + m) * Kg + k];
-    wp[idx] = v;
-  }
+GemmKnobs gemm_knobs() {
+  GemmKnobs k;
+  k.variant = knob("GEMM_VARIANT", k.variant);
+  k.areg = knob("GEMM_AREG", k.areg);
+  k.ma = knob("GEMM_MA", k.ma);
+  k.tr = knob("GEMM_TR", k.tr);
+  k.tr_cfg = knob("TR_CFG", k.tr_cfg);
+  k.wide = knob("GEMM_WIDE", k.wide);
+  gemm_resolve_wide_force(&k, g_wide_ntt_override, knob("WIDE_NTT", 0));
+  k.stamp_lds_ring = (int)STAMP_LDS;
+  k.stamp_lds_tr = gemm_tr_stamp_lds();
+  k.stamp_lds_wide = gemm_wide_stamp_lds();
+  return k;
 }
 
-// ---- im2col: x NCHW -> col[b][g][Kg][Np], Np = roundup(oh*ow, 4), pad columns and OOB taps = 0 ----
-// Row index k = c*kh*kw + r*kw + q (conv_impl.cc:103-153).  One thread writes one dword (4 columns).
-// grid = (column-quad tiles, Kg, batch*groups): the row (image, group, channel, tap) is block-uniform, so its decode runs
-// on the scalar unit; a thread does ONE 32-bit division (its first column -> (oy, ox)) and walks the other three columns
-// with a carry.  Stride-1 quads that stay inside one input row are fetched as one unaligned dword.  (The former
-// 1-D form decoded everything per thread with 64-bit divisions: 128 us for the 57.8 MB buffer of BASELINE config #2.)
-__global__ __launch_bounds__(256) void im2col_i8_kernel(Im2colArgs a) {
-  const int np4 = a.Np >> 2;
-  const int q4 = blockIdx.x * 256 + threadIdx.x;
-  if (q4 >= np4) return;
-  const int k = blockIdx.y;
-  const int bg = blockIdx.z;
-  const int b = bg / a.G, grp = bg - b * a.G;
-  const int khkw = a.kh * a.kw;
-  const int ci = k / khkw, rs = k - ci * khkw;
-  const int kr = rs / a.kw, kq = rs - kr * a.kw;
-  const int8_t* xp = a.x + ((size_t)b * a.cin + (size_t)grp * a.cin_g + ci) * a.h * a.w;
-  const size_t row = (size_t)bg * a.Kg + k;
-  int n = q4 * 4;
-  int oy = (int)((uint32_t)n / (uint32_t)a.ow), ox = n - oy * a.ow;
-  uint32_t out = 0;
-  const int ih0 = oy * a.sh - a.pt + kr * a.dh, iw0 = ox * a.sw - a.pl + kq * a.dw;
-  if (a.sw == 1 && n + 3 < a.N && ox + 3 < a.ow && ih0 >= 0 && ih0 < a.h && iw0 >= 0 && iw0 + 3 < a.w) {
-    __builtin_memcpy(&out, xp + (size_t)ih0 * a.w + iw0, 4);
-  } else if (a.sw == 2 && n + 3 < a.N && ox + 3 < a.ow && ih0 >= 0 && ih0 < a.h && iw0 >= 0 && iw0 + 7 < a.w) {
-    // stride 2 (ResNet50's 1x1 stride-2 shortcuts): columns iw0, +2, +4, +6 of one row: one unaligned 8-byte fetch,
-    // every other byte kept (the byte-by-byte walk below ran the three shortcut copies at ~1 TB/s)
-    uint32_t d[2];
-    __builtin_memcpy(d, xp + (size_t)ih0 * a.w + iw0, 8);
-    out = __builtin_amdgcn_perm(d[1], d[0], 0x06040200u);
-  } else {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      if (n + i < a.N) {
-        const int ih = oy * a.sh - a.pt + kr * a.dh, iw = ox * a.sw - a.pl + kq * a.dw;
-        if (ih >= 0 && ih < a.h && iw >= 0 && iw < a.w) out |= (uint32_t)(uint8_t)xp[(size_t)ih * a.w + iw] << (8 * i);
-      }
-      if (++ox == a.ow) {
-        ox = 0;
-        ++oy;
-      }
-    }
-  }
-  *reinterpret_cast<uint32_t*>(a.col + row * a.Np + (size_t)q4 * 4) = out;
-}
-
-// ---- host-side launchers (called from plhip_capi_conv.hip) ----
-static int gemm_variant() {  // PLHIP_GEMM_VARIANT: 0 auto, 1 private-tile kernel, 2 register-staged LDS kernel, 3 LDS-DMA ring
-  const int v = knob("GEMM_VARIANT", 0);
-  return v;
-}
-
+// the first-generation kernels of this file: private tiles, LDS, ring
 template <int MA, int OUT>
-static void launch_gemm_t(const GemmArgs& g_in, bool vec_store, bool aligned, hipStream_t s) {
-  GemmArgs g = g_in;
-  const bool mfull = g.M % (32 * MA) == 0;
-  const int var = gemm_variant();
-  // (32-row wave tiles with a short K -- e.g. 128->128 at 56x56 -- run faster on the register-staged kernel: 24.8 vs 26.6 us)
-  const bool use_dma = g.im_kw > 0 ||  // the implicit-GEMM route exists only in the ring kernel (conv_geom checked the shape)
-                       (g.HWX >= 16 && g.KS >= 4 && (var == 3 || (var == 0 && g.MT >= 4 && (MA == 2 || g.KS >= 8))));
-  if (use_dma) {
-    // dense NCHW slabs whose rows are not a multiple of 4 bytes (HW = 49: the 7x7 layers) arrive with HWX rounded up to 4
-    // for the dword kernels; this kernel moves END-aligned 16-byte pieces and must know the TRUE row length, or the last
-    // piece of a row reaches HWX - XP bytes into the next row -- and past the end of the tensor on its last row
-    if (g.im_kw == 0 && g.XP > 0 && g.XP < g.HWX) g.HWX = g.XP;
+static void run_gemm_t(const GemmPlan& p, GemmArgs g, hipStream_t s) {
+  typedef std::integral_constant<int, 0> F_;
+  typedef std::integral_constant<int, 1> T_;
+  const dim3 grid(p.grid), block(p.block);
+  if (p.family == GEMM_RING) {
     PLHIP_SET_STAMPS(g, "gemm", sizeof(unsigned long long) * 1024 * 4 * STAMP_SLOTS);
-    g.NT = (int)(((long)g.NB * ((g.HWX + 15) & ~15) + 127) / 128);  // 16-byte padded column space of this kernel
-    const unsigned blocks = (unsigned)(((g.MT + 3) / 4) * (long)((g.NT + 7) / 8 * 8));
-    const int areg_env = knob("GEMM_AREG", 1);
-    const int ng = (areg_env && (g.KS & 3) == 0 && mfull && MA == 2) ? g.KS >> 2 : 0;
-    const bool areg = ng == 1 || ng == 2 || ng == 4 || ng == 8;  // K = 128 / 256 / 512 / 1024
-    const size_t lds = (size_t)(4 + 1) * (areg ? 4096 : 4096 + 4 * MA * 1024) + 4 * 2 * MA * 32 * 4 + STAMP_LDS;
-#define PLHIP_LAUNCH_DMA2(VS, MF, NGV)                                                                            \
-  do {                                                                                                            \
-    auto kfn = gemm_i8_dma_kernel<MA, OUT, VS, MF, 4, NGV>;                                                       \
-    if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-    hipLaunchKernelGGL(kfn, dim3(blocks), dim3(256), lds, s, g);                                                  \
-  } while (0)
-#define PLHIP_LAUNCH_DMA(VS, MF)                                            \
-  do {                                                                      \
-    if (MA == 2 && MF && areg) {                                            \
-      if (ng == 1) PLHIP_LAUNCH_DMA2(VS, MF, (MA == 2 && MF) ? 1 : 0);      \
-      else if (ng == 2) PLHIP_LAUNCH_DMA2(VS, MF, (MA == 2 && MF) ? 2 : 0); \
-      else if (ng == 4) PLHIP_LAUNCH_DMA2(VS, MF, (MA == 2 && MF) ? 4 : 0); \
-      else PLHIP_LAUNCH_DMA2(VS, MF, (MA == 2 && MF) ? 8 : 0);              \
-    } else {                                                                \
-      PLHIP_LAUNCH_DMA2(VS, MF, 0);                                         \
-    }                                                                       \
-  } while (0)
-    if (vec_store && mfull) PLHIP_LAUNCH_DMA(true, true);
-    else if (vec_store) PLHIP_LAUNCH_DMA(true, false);
-    else if (mfull) PLHIP_LAUNCH_DMA(false, true);
-    else PLHIP_LAUNCH_DMA(false, false);
-#undef PLHIP_LAUNCH_DMA2
-#undef PLHIP_LAUNCH_DMA
+    with_const<0, 1>(p.VEC_STORE, [&](auto vs) {
+      with_const<0, 1>(p.MFULL, [&](auto mf) {
+        constexpr bool VS = decltype(vs)::value != 0, MF = decltype(mf)::value != 0;
+        auto launch = [&](auto ng) {
+          auto kfn = gemm_i8_dma_kernel<MA, OUT, VS, MF, 4, decltype(ng)::value>;
+          if (p.lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
+          hipLaunchKernelGGL(kfn, grid, block, p.lds, s, g);
+        };
+        if constexpr (MA == 2 && MF) with_const<0, 1, 2, 4, 8>(p.NG, launch);  // the AREG forms exist for whole 64-row tiles only
+        else launch(F_{});
+      });
+    });
     return;
   }
-  const bool use_lds = var == 2 || (var == 0 && g.MT >= 2 && g.KS >= 2);
-  if (use_lds) {
-    const unsigned blocks = (unsigned)(((g.MT + 3) / 4) * (long)((g.NT + 7) / 8 * 8));
-    if (!aligned)
-      hipLaunchKernelGGL((gemm_i8_lds_kernel<MA, OUT, false, false, false>), dim3(blocks), dim3(256), 0, s, g);
-    else if (vec_store && mfull)
-      hipLaunchKernelGGL((gemm_i8_lds_kernel<MA, OUT, true, true, true>), dim3(blocks), dim3(256), 0, s, g);
-    else if (vec_store)
-      hipLaunchKernelGGL((gemm_i8_lds_kernel<MA, OUT, true, false, true>), dim3(blocks), dim3(256), 0, s, g);
-    else
-      hipLaunchKernelGGL((gemm_i8_lds_kernel<MA, OUT, false, false, true>), dim3(blocks), dim3(256), 0, s, g);
-    return;
-  }
-  const long waves = (long)g.MT * g.NT;
-  const unsigned blocks = (unsigned)((waves + 3) / 4);
-  if (!aligned)
-    hipLaunchKernelGGL((gemm_i8_nchw_kernel<MA, OUT, false, false, false>), dim3(blocks), dim3(256), 0, s, g);
-  else if (vec_store && mfull)
-    hipLaunchKernelGGL((gemm_i8_nchw_kernel<MA, OUT, true, true, true>), dim3(blocks), dim3(256), 0, s, g);
-  else if (vec_store)
-    hipLaunchKernelGGL((gemm_i8_nchw_kernel<MA, OUT, true, false, true>), dim3(blocks), dim3(256), 0, s, g);
-  else
-    hipLaunchKernelGGL((gemm_i8_nchw_kernel<MA, OUT, false, false, true>), dim3(blocks), dim3(256), 0, s, g);
+  auto launch = [&](auto vs, auto mf, auto al) {  // the four store / load forms the dword kernels are built in
+    constexpr bool VS = decltype(vs)::value != 0, MF = decltype(mf)::value != 0, AL = decltype(al)::value != 0;
+    if (p.family == GEMM_LDS) hipLaunchKernelGGL((gemm_i8_lds_kernel<MA, OUT, VS, MF, AL>), grid, block, 0, s, g);
+    else hipLaunchKernelGGL((gemm_i8_nchw_kernel<MA, OUT, VS, MF, AL>), grid, block, 0, s, g);
+  };
+  if (!p.ALIGNED) launch(F_{}, F_{}, F_{});
+  else if (p.MFULL) launch(T_{}, T_{}, T_{});
+  else if (p.VEC_STORE) launch(T_{}, F_{}, T_{});
+  else launch(F_{}, F_{}, T_{});
 }
 
-// returns 0, or -3 when the shape exists on one kernel only and that kernel declines it (nothing is launched)
 int launch_gemm_i8(const GemmArgs& g_in, int ma, int out, bool vec_store, bool aligned_loads, hipStream_t s) {
-  if (!aligned_loads) vec_store = false;
-  // The packed layout is a sequence of 32-row fragment tiles, so a layer packed for MA = 2 can also run with MA = 1
-  // (32-row wave tiles): do so for M <= 128, where 64-row tiles would leave waves of the 4-wave block without work.
-  const int ma_env = knob("GEMM_MA", 0);
+  const GemmPlan p = gemm_plan(gemm_problem(g_in, ma, out, vec_store, aligned_loads), gemm_knobs());
   GemmArgs g = g_in;
-  // The transposed-read ring kernel (gemm_tr_i8.hip) is the implicit-GEMM engine (any M > 32, rows down to 7 columns).
-  // For plain 1x1 / im2col GEMMs it is opt-in (PLHIP_GEMM_TR=2): measured on MobileNetV1's pointwise layers it ties
-  // the first-generation ring kernel at batch 128 and loses at batch 256 (both are bound by the
-  // ~21 B/clk a CU ingests through LDS-DMA and by the non-overlapped epilogue, not by the K loop's instruction mix).
-  // It moves END-aligned 16-byte pieces and must know the TRUE row length of a dense slab (HW = 49).
-  // Third generation (gemm_wide_i8.hip): plain 1x1 GEMMs with M >= 256 and K in {128, 256, 512, 1024}: one 256 x (128..256)
-  // tile per CU, the weight panel read once per CU, every operand byte in flight before the first MFMA.
-  if (g.im_kw == 0 && gemm_variant() == 0) {
-    GemmArgs t = g;
-    if (t.XP > 0 && t.XP < t.HWX) t.HWX = t.XP;  // the TRUE row length of a dense slab
-    if (launch_gemm_wide(t, out, s)) return 0;
-  }
-  const bool tr_only = g.im_kw > 0 && (g.im_s == 2 || g.HWX < 16);
-  if (g.M > 32 && (g.im_kw > 0 || (gemm_variant() == 0 && gemm_tr_enabled() >= 2))) {
-    GemmArgs t = g;
-    if (t.im_kw == 0 && t.XP > 0 && t.XP < t.HWX) t.HWX = t.XP;
-    if (launch_gemm_tr(t, out, s)) return 0;
-    // stride-2 / short-row implicit GEMMs exist on that kernel ONLY: the first-generation kernels would read outside their
-    // operands for these shapes.  conv_geom admits them under the same column-space bound launch_gemm_tr checks
-    // (plhip_capi_conv.hip), so this is a defensive error, not a fallback
-    if (tr_only) return -3;
-  }
-  if (ma == 2 && ((ma_env == 0 && g.M <= 128 && g.M > 64) || (ma_env == 1 && g.im_kw == 0))) ma = 1;
-  // 64-row tiles whose last tile is at most half full (M = 144: 192 rows computed and stored-checked for 144), and the
-  // streaming shapes with K <= 64 and M > 64 (MobileNetV2's expand convs: 24 -> 144 ran at 3.0 TB/s with 64-row tiles,
-  // 3.9 with 32-row ones; 64 -> 384 @14x14 12.1 -> 9.8 us): 32-row wave tiles
-  // (K = 32, M = 64 — MobileNetV1's first pointwise conv — too: 28.7 -> 27.4 us at batch 128)
-  if (ma == 2 && ma_env == 0 && g.im_kw == 0 && (((g.M & 63) != 0 && (g.M & 63) <= 32) || (g.KS <= 2 && g.M > 64) || (g.KS == 1 && g.M == 64))) ma = 1;
-  g.MT = (g.M + 32 * ma - 1) / (32 * ma);
-  if (ma == 1) {
-    if (out == OUT_I32) launch_gemm_t<1, OUT_I32>(g, vec_store, aligned_loads, s);
-    else if (out == OUT_F32) launch_gemm_t<1, OUT_F32>(g, vec_store, aligned_loads, s);
-    else launch_gemm_t<1, OUT_I8>(g, vec_store, aligned_loads, s);
-  } else {
-    if (out == OUT_I32) launch_gemm_t<2, OUT_I32>(g, vec_store, aligned_loads, s);
-    else if (out == OUT_F32) launch_gemm_t<2, OUT_F32>(g, vec_store, aligned_loads, s);
-    else launch_gemm_t<2, OUT_I8>(g, vec_store, aligned_loads, s);
+  g.HWX = p.HWX;
+  g.MT = p.MT;
+  g.NT = p.NT;
+  switch (p.family) {
+    case GEMM_NONE: return -3;
+    case GEMM_WIDE: run_gemm_wide(p, g, s); break;
+    case GEMM_TR: run_gemm_tr(p, g, s); break;
+    default:
+      with_const<1, 2>(p.MA, [&](auto ma_c) {
+        with_const<OUT_I32, OUT_F32, OUT_I8>(p.OUT, [&](auto out_c) { run_gemm_t<decltype(ma_c)::value, decltype(out_c)::value>(p, g, s); });
+      });
   }
   return 0;
-}
-
-void launch_pack_weights(const int8_t* w, int8_t* wp, int G, int Mg, int Kg, int MT32, int KS, hipStream_t s) {
-  const size_t total = (size_t)G * MT32 * KS * 1024;
-  const unsigned blocks = (unsigned)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
-  hipLaunchKernelGGL(pack_weights_kernel, dim3(blocks), dim3(256), 0, s, w, wp, G, Mg, Kg, MT32, KS);
-}
-
-// Zero-padded copy of the input for the implicit-GEMM route: xp[plane][ph][pw] = x[plane][ph - pt][pw - pl] or 0.
-// One thread = one aligned dword of the flat padded buffer (two divisions, then carry propagation byte by byte).
-__global__ void pad_input_i8_kernel(PadArgs a) {
-  const long nq = a.total >> 2;
-  const int plane_sz = a.ph * a.pw;
-  for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (long)gridDim.x * blockDim.x) {
-    // the padded buffer is < 2^31 bytes (conv_geom): magic-number divisions (two hardware divide sequences per dword made
-    // this copy VALU-bound: 35 us for ResNet50's 55 MB res2 planes)
-    const uint32_t o = (uint32_t)q << 2;
-    int plane = (int)fastdiv_u31(o, a.div_plane_m, a.div_plane_s);
-    const int rem = (int)(o - (uint32_t)plane * (uint32_t)plane_sz);
-    int ph = (int)fastdiv_u31((uint32_t)rem, a.div_pw_m, a.div_pw_s), pw = rem - ph * a.pw;
-    uint32_t v = 0;
-    {  // interior dword (the common case): one unaligned 4-byte load
-      const int ih = ph - a.pt, iw = pw - a.pl;
-      if (plane < a.planes && pw + 3 < a.pw && ih >= 0 && ih < a.h && iw >= 0 && iw + 3 < a.w) {
-        __builtin_memcpy(&v, a.x + ((size_t)plane * a.h + ih) * a.w + iw, 4);
-        reinterpret_cast<uint32_t*>(a.xp)[q] = v;
-        continue;
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int ih = ph - a.pt, iw = pw - a.pl;
-      if (plane < a.planes && ih >= 0 && ih < a.h && iw >= 0 && iw < a.w)
-        v |= (uint32_t)(uint8_t)a.x[((size_t)plane * a.h + ih) * a.w + iw] << (8 * i);
-      if (++pw == a.pw) {
-        pw = 0;
-        if (++ph == a.ph) {
-          ph = 0;
-          ++plane;
-        }
-      }
-    }
-    reinterpret_cast<uint32_t*>(a.xp)[q] = v;
-  }
-}
-
-// Phase-split padded copy for the stride-2 implicit GEMM: xp[plane][p][q][y][x] = padded[plane][2y + p][2x + q].
-// One thread = one aligned dword (4 consecutive x of one phase row): 4 source bytes at stride 2.
-__global__ void pad_input_phase2_i8_kernel(PadArgs a) {
-  const long nq = a.total >> 2;
-  const int pwq = a.pw >> 2;  // launcher: phase rows are padded to a multiple of 4 columns
-  for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (long)gridDim.x * blockDim.x) {
-    // q < 2^29 (the buffer is < 2^31 bytes): 32-bit magic-number divisions, no 64-bit divide sequences
-    const uint32_t t1 = fastdiv_u31((uint32_t)q, a.div_pwq_m, a.div_pwq_s);
-    const int xq = (int)((uint32_t)q - t1 * (uint32_t)pwq);
-    const uint32_t t2 = fastdiv_u31(t1, a.div_ph_m, a.div_ph_s);
-    const int y = (int)(t1 - t2 * (uint32_t)a.ph);
-    const int ph = (int)(t2 & 3);
-    const long plane = (long)(t2 >> 2);
-    uint32_t v = 0;
-    if (plane < a.planes) {
-      const int iy = 2 * y + (ph >> 1) - a.pt;
-      if (iy >= 0 && iy < a.h) {
-        const int8_t* row = a.x + ((size_t)plane * a.h + iy) * a.w;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int ix = 2 * (4 * xq + i) + (ph & 1) - a.pl;
-          if (ix >= 0 && ix < a.w) v |= (uint32_t)(uint8_t)row[ix] << (8 * i);
-        }
-      }
-    }
-    reinterpret_cast<uint32_t*>(a.xp)[q] = v;
-  }
-}
-
-static void pad_magic(long d, unsigned& m, int& sh) {  // fastdiv_u31's (magic, shift) for divisor d (dw_common.h)
-  int l = 0;
-  while ((1L << l) < d) ++l;
-  if ((1L << l) == d) {
-    m = 0;
-    sh = l;
-    return;
-  }
-  m = (unsigned)(((1ULL << (31 + l)) / (unsigned long long)d) + 1ULL);
-  sh = l - 1;
-}
-
-void launch_pad_input(const PadArgs& a_in, hipStream_t s) {
-  PadArgs a = a_in;
-  pad_magic((long)a.ph * a.pw, a.div_plane_m, a.div_plane_s);
-  pad_magic(a.pw, a.div_pw_m, a.div_pw_s);
-  pad_magic(a.pw >> 2 > 0 ? a.pw >> 2 : 1, a.div_pwq_m, a.div_pwq_s);
-  pad_magic(a.ph, a.div_ph_m, a.div_ph_s);
-  if (a.stride == 2) {
-    long blocks2 = ((a.total >> 2) + 255) / 256;
-    if (blocks2 > 65536) blocks2 = 65536;
-    hipLaunchKernelGGL(pad_input_phase2_i8_kernel, dim3((unsigned)blocks2), dim3(256), 0, s, a);
-    return;
-  }
-  long blocks = ((a.total >> 2) + 255) / 256;
-  if (blocks > 65536) blocks = 65536;
-  hipLaunchKernelGGL(pad_input_i8_kernel, dim3((unsigned)blocks), dim3(256), 0, s, a);
-}
-
-// 1x1 stride-2 convs (ResNet50's downsampling shortcuts: lite/backends/arm/math/conv_impl.cc:490-598 runs them through
-// im2col too): the "im2col" is a strided gather, col[b][c][oy * ow + ox] = x[b][c][2 oy][2 ox].  One thread = 16 output
-// bytes = 4 quads, each ONE unaligned 8-byte fetch with every other byte kept, one 16-byte store (the dword-per-thread
-// form above ran the three shortcut copies of a ResNet50 step at 2.3 TB/s, 0.33 ms per 256 images: 4-byte stores).
-// Needs kh = kw = 1, no padding in use, sw = 2.
-__global__ __launch_bounds__(256) void subsample2_1x1_i8_kernel(Im2colArgs a) {
-  // flat index -> (row = (image, group, channel), 16-byte chunk): a (chunks, channels, images) grid of mostly empty 256-thread
-  // blocks (49 chunks per 28x28 row) was bound by the workgroup dispatch rate: 65 k blocks for 51 MB
-  const int nch = (a.Np + 15) >> 4;
-  const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= a.rows * (size_t)nch) return;
-  const uint32_t rowi = (uint32_t)(idx / (uint32_t)nch);
-  const int q16 = (int)(idx - (size_t)rowi * nch);
-  const int bg = (int)(rowi / (uint32_t)a.Kg), k = (int)(rowi - (uint32_t)bg * a.Kg);
-  const int b = bg / a.G, grp = bg - b * a.G;
-  const int8_t* xp = a.x + ((size_t)b * a.cin + (size_t)grp * a.cin_g + k) * a.h * a.w;
-  const size_t row = (size_t)bg * a.Kg + k;
-  const int n0 = q16 * 16;
-  int oy = (int)((uint32_t)n0 / (uint32_t)a.ow), ox = n0 - oy * a.ow;
-  uint32_t out[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-  for (int d = 0; d < 4; ++d) {
-    const int n = n0 + 4 * d;
-    if (n + 3 < a.N && ox + 3 < a.ow && ox * 2 + 7 < a.w) {  // the quad inside one output row, its 8 source bytes inside the input row
-      uint32_t dd[2];
-      __builtin_memcpy(dd, xp + (size_t)(oy * a.sh) * a.w + ox * 2, 8);
-      out[d] = __builtin_amdgcn_perm(dd[1], dd[0], 0x06040200u);
-      ox += 4;
-      if (ox >= a.ow) {
-        ox -= a.ow;
-        ++oy;
-      }
-    } else {  // a quad across two output rows (14- and 7-wide planes), the row's last quad when w is odd, the plane's tail
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        if (n + i < a.N) out[d] |= (uint32_t)(uint8_t)xp[(size_t)(oy * a.sh) * a.w + ox * 2] << (8 * i);
-        if (++ox == a.ow) {
-          ox = 0;
-          ++oy;
-        }
-      }
-    }
-  }
-  int8_t* dst = a.col + row * a.Np + (size_t)n0;
-  if (n0 + 16 <= a.Np) {
-    const v4i v = {(int)out[0], (int)out[1], (int)out[2], (int)out[3]};
-    __builtin_memcpy(dst, &v, 16);  // (rows are 4-byte aligned: Np % 4 == 0)
-  } else {
-#pragma unroll
-    for (int d = 0; d < 4; ++d)
-      if (n0 + 4 * d < a.Np) __builtin_memcpy(dst + 4 * d, &out[d], 4);
-  }
-}
-
-void launch_im2col(const Im2colArgs& a, hipStream_t s) {
-  // rows = batch * G * Kg; Kg and batch*G ride on grid.y / grid.z (<= 65535 each, checked by the caller)
-  const unsigned bg = (unsigned)(a.rows / (size_t)a.Kg);
-  const int sub_env = knob("SUBSAMPLE_1X1", 1);  // 0 = the generic im2col kernel (A/B runs)
-  if (sub_env && a.kh == 1 && a.kw == 1 && a.pt == 0 && a.pl == 0 && a.sw == 2 && a.Kg == a.cin_g &&
-      (a.oh - 1) * a.sh < a.h && (a.ow - 1) * 2 < a.w) {  // (no tap in a bottom / right padding)
-    const size_t threads = a.rows * (size_t)((a.Np + 15) >> 4);
-    if (threads < ((size_t)1 << 31) * 256) {
-      hipLaunchKernelGGL(subsample2_1x1_i8_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, a);
-      return;
-    }
-  }
-  hipLaunchKernelGGL(im2col_i8_kernel, dim3((unsigned)(((a.Np >> 2) + 255) / 256), (unsigned)a.Kg, bg), dim3(256), 0, s, a);
 }
 
 }  // namespace plhip

@@ -285,7 +285,7 @@ __global__ __launch_bounds__(64 * WN * WM, 2) void gemm_i8_tr_kernel(GemmArgs g)
     __builtin_amdgcn_s_barrier();  // every wave has finished reading the ring: it becomes staging space
     PLHIP_STAMP(TR_STAMP_SLOTS - 6);
     uint8_t* stg = ring + wave * (64 * 144);
-    if (g.y2) {  // kernel-uniform: calib-only tail of an fp32-output conv (launch_gemm_tr): the int8 tensor is g.y2
+    if (g.y2) {  // kernel-uniform: calib-only tail of an fp32-output conv (gemm_plan): the int8 tensor is g.y2
       tr_stage_i8_calib(acc, sc, bi, g.act, g.alpha, g.inv_scale2, stg, c, h);
     } else {
       switch (g.act) {  // wave-uniform: straight-line requantisation per activation
@@ -422,61 +422,30 @@ __global__ __launch_bounds__(64 * WN * WM, 2) void gemm_i8_tr_kernel(GemmArgs g)
   }
 }
 
-int gemm_tr_enabled() {  // PLHIP_GEMM_TR=0: first-generation kernels only (A/B runs)
-  const int v = knob("GEMM_TR", 1);
-  return v;
+int gemm_tr_stamp_lds() { return (int)TR_STAMP_LDS; }
+
+template <int WN, int WM>
+static void run_tr_tile(const GemmPlan& p, const GemmArgs& g, hipStream_t s) {
+  with_const<OUT_I32, OUT_F32, OUT_I8>(p.OUT, [&](auto out_c) {
+    with_const<0, 1>(p.IM, [&](auto im_c) {
+      constexpr int D = WN * WM == 4 ? 3 : 4;  // as gemm_plan sizes the ring
+      auto kfn = gemm_i8_tr_kernel<WN, WM, decltype(out_c)::value, D, decltype(im_c)::value != 0>;
+      // per DEVICE and called from several predictor threads: set on every launch (a process-wide flag was wrong on a second GPU)
+      (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
+      hipLaunchKernelGGL(kfn, dim3(p.grid), dim3(p.block), p.lds, s, g);
+    });
+  });
 }
 
-template <int WN, int WM, int OUT, bool IM>
-static void launch_tr_cfg2(GemmArgs g, hipStream_t s) {
-  // 4-wave blocks (M <= 64): 3 K-steps in flight = 4 ring slots = 72 KiB, so that TWO blocks share a CU (with one, its
-  // four waves read LDS together and multiply together: 11 B/clk of ingest; two blocks de-phase each other)
-  constexpr int D = WN * WM == 4 ? 3 : 4;
-  constexpr int BN = WN * 128, BM = WM * 64;
-  const int HWP = (g.HWX + 15) & ~15;
-  g.NT = (int)(((long)g.NB * HWP + BN - 1) / BN);  // blocks along N
-  g.MT = (g.M + BM - 1) / BM;                      // blocks along M
-  const unsigned blocks = (unsigned)((long)g.MT * ((g.NT + 7) / 8 * 8));
-  const size_t lds = (size_t)(D + 1) * (BN * 32 + BM * 32) + TR_STAMP_LDS;
-  auto kfn = gemm_i8_tr_kernel<WN, WM, OUT, D, IM>;
-  // per DEVICE and called from several predictor threads: set on every launch (a process-wide flag was wrong on a second GPU)
-  (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL(kfn, dim3(blocks), dim3(64 * WN * WM), lds, s, g);
-}
-
-template <int WN, int WM, int OUT>
-static void launch_tr_cfg(const GemmArgs& g, hipStream_t s) {
-  if (g.im_kw > 0) launch_tr_cfg2<WN, WM, OUT, true>(g, s);
-  else launch_tr_cfg2<WN, WM, OUT, false>(g, s);
-}
-
-// Returns true when the launch was taken.  g.HWX must already be the TRUE row length (dense slabs) / the padded row
-// length of the im2col buffer / OW (implicit GEMM); KS >= 4, HWX >= 16.
-bool launch_gemm_tr(const GemmArgs& g_in, int out, hipStream_t s) {
-  GemmArgs g = g_in;
+// g.HWX is the TRUE row length (dense slabs) / the padded row length of the im2col buffer / OW (implicit GEMM); g.MT / g.NT
+// count blocks (gemm_plan)
+void run_gemm_tr(const GemmPlan& p, GemmArgs g, hipStream_t s) {
   PLHIP_SET_STAMPS(g, "tr", sizeof(unsigned long long) * 1024 * 8 * TR_STAMP_SLOTS);
-  // rows shorter than 16 bytes: only on the padded copy of the implicit route (a 16-byte piece may run past the row)
-  if (!gemm_tr_enabled() || g.KS < 4 || (g.HWX < 16 && g.im_kw == 0)) return false;
-  if ((long)g.NB * ((g.HWX + 15) & ~15) >= ((long)1 << 31) - 1024) return false;
-  // fp32-output conv whose fp32 value nobody reads and whose only tail is the calib: the staged int8 epilogue (16-byte
-  // row stores) instead of the row-per-lane 32-bit one (ResNet50's stem behind the int8 max pool: 0.54 -> see DESIGN 4)
-  if (out == OUT_F32 && !g.y && g.y2 && !g.res) out = OUT_I8;
-#define PLHIP_TR_OUT(WN_, WM_)                                          \
-  do {                                                                  \
-    if (out == OUT_I32) launch_tr_cfg<WN_, WM_, OUT_I32>(g, s);         \
-    else if (out == OUT_F32) launch_tr_cfg<WN_, WM_, OUT_F32>(g, s);    \
-    else launch_tr_cfg<WN_, WM_, OUT_I8>(g, s);                         \
-  } while (0)
-      // default 3: 4-wave blocks (128 x 256 / 256 x 128 tiles), two per CU, for every M (ResNet50's 3x3 layers: 5-8 % faster
-    // than one 8-wave block per CU, whose waves read LDS together and multiply together); 0 = the 8-wave tiles
-  const int cfg_env = knob("TR_CFG", 3);
-  if (g.M > 128 && (cfg_env & 1)) PLHIP_TR_OUT(1, 4);
-  else if (g.M > 128) PLHIP_TR_OUT(2, 4);
-  else if (g.M > 64 && (cfg_env & 2)) PLHIP_TR_OUT(2, 2);
-  else if (g.M > 64) PLHIP_TR_OUT(4, 2);
-  else PLHIP_TR_OUT(4, 1);
-#undef PLHIP_TR_OUT
-  return true;
+  if (p.WN == 1) run_tr_tile<1, 4>(p, g, s);
+  else if (p.WN == 2 && p.WM == 4) run_tr_tile<2, 4>(p, g, s);
+  else if (p.WN == 2) run_tr_tile<2, 2>(p, g, s);
+  else if (p.WM == 2) run_tr_tile<4, 2>(p, g, s);
+  else run_tr_tile<4, 1>(p, g, s);
 }
 
 }  // namespace plhip

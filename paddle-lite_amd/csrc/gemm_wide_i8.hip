@@ -30,66 +30,14 @@
 
 namespace plhip {
 
-static int g_wide_ntt_override = -1;  // tests / A-B runs: plhip_debug_wide_ntt (-1 = PLHIP_WIDE_NTT or automatic)
-void debug_set_wide_ntt(int v) { g_wide_ntt_override = v; }
+int gemm_wide_stamp_lds() { return WIDE_STAMP_LDS; }
 
-static int wide_env() {  // PLHIP_GEMM_WIDE: 1 (default) on, 0 = second-generation kernels only (A/B runs)
-  const int v = knob("GEMM_WIDE", 1);
-  return v;
-}
-
-// The tile of a launch: n tiles per block so that the blocks fill the CUs once with as little idle tail as possible.
-// Returns 0 when the shape is outside this kernel (the caller falls back to the ring kernels).
-int gemm_wide_ntt(const GemmArgs& g) {
-  if (!wide_env() || g.im_kw != 0 || g.res || g.y2) return 0;
-  if (g.K != g.KS * 32 || (g.KS != 4 && g.KS != 8 && g.KS != 16 && g.KS != 32)) return 0;
-  // dense slabs only: the column space IS the output row (an im2col buffer whose rows are padded to a multiple of 4 has
-  // HWX > HWY: its pad columns must not be stored, and the whole-chunk stores here would spill into the next row)
-  if (g.M < 256 || g.HWX < 16 || g.HWX != g.HWY) return 0;
-  const int CPI = (g.HWX + 15) >> 4;
-  const long chunks = (long)g.NB * CPI;
-  if (chunks * 16 >= ((long)1 << 31) - 4096) return 0;
-  const int force_env = knob("WIDE_NTT", 0);
-  const int force = g_wide_ntt_override >= 0 ? g_wide_ntt_override : force_env;
-  const int mblocks = (g.M + 255) / 256;
-  int best = 0;
-  double best_cost = 1e30;
-  const int cands[3] = {4, 7, 8};
-  for (int i = 0; i < 3; ++i) {
-    const int ntt = cands[i];
-    if (force && ntt != force) continue;
-    {  // the activation tile + the staging images must fit the LDS (wide_lds_bytes)
-      const int c1 = 2 * ntt > 8 ? 2 * ntt - 8 : 0;
-      if ((long)g.KS * 4 * (1024 + c1 * 128) + 8 * 32 * 48 + WIDE_STAMP_LDS > 160 * 1024) continue;
-    }
-    const long nblocks = (chunks + 2 * ntt - 1) / (2 * ntt);
-    const long blocks = nblocks * mblocks;
-    const long rounds = (blocks + 255) / 256;
-    // time ~ rounds x (operand ingest of a tile + a fixed prologue / epilogue share)
-    const double cost = (double)rounds * ((double)g.KS * 32 * (256 + 32 * ntt) + 40000.0);
-    if (cost < best_cost) {
-      best_cost = cost;
-      best = ntt;
-    }
-  }
-  return best;
-}
-
-bool launch_gemm_wide(const GemmArgs& g_in, int out, hipStream_t s) {
-  // 32-bit outputs: the ring kernels are faster on every MobileNetV1 layer (fp32 out, batch 256: 699 vs 764 us over the 13
-  // layers, 128 -> 256 @28x28 38.7 vs 54.0 us, 1024 -> 1024 @7x7 30.2 vs 37.6: profiles/r03_final_opbench_f32_*.txt): this
-  // kernel's row-per-lane 16-byte stores write 32 contiguous bytes per row and instruction, the ring kernels' epilogue 64.
-  // It stays reachable for them through the tile override (tests, A/B runs).
-  if (out != OUT_I8 && g_wide_ntt_override < 0 && knob("WIDE_NTT", 0) == 0) return false;
-  const int ntt = gemm_wide_ntt(g_in);
-  if (!ntt) return false;
-  GemmArgs g = g_in;
+// the tile (n tiles per block so that the blocks fill the CUs once with as little idle tail as possible) is gemm_plan's choice
+void run_gemm_wide(const GemmPlan& p, GemmArgs g, hipStream_t s) {
   PLHIP_SET_STAMPS(g, "wide", sizeof(unsigned long long) * 512 * 8 * WIDE_STAMP_SLOTS);
-  if (ntt == 4) launch_wide_n4(g, out, s);
-  else if (g.KS == 32) return false;
-  else if (ntt == 7) launch_wide_n7(g, out, s);
-  else launch_wide_n8(g, out, s);
-  return true;
+  if (p.NTT == 4) launch_wide_n4(p, g, s);
+  else if (p.NTT == 7) launch_wide_n7(p, g, s);
+  else launch_wide_n8(p, g, s);
 }
 
 }  // namespace plhip

@@ -371,48 +371,23 @@ __global__ __launch_bounds__(512, 2) void gemm_i8_wide_kernel(GemmArgs g) {
   }
 }
 
-static inline void cpi_magic(long d, unsigned& m, int& sh) {  // fastdiv_u31's (magic, shift) for divisor d (dw_common.h)
-  int l = 0;
-  while ((1L << l) < d) ++l;
-  if ((1L << l) == d) {
-    m = 0;
-    sh = l;
-    return;
-  }
-  m = (unsigned)(((1ULL << (31 + l)) / (unsigned long long)d) + 1ULL);
-  sh = l - 1;
-}
-
-template <int NTT, int KS, int OUT>
-static inline void launch_wide_t(GemmArgs g, hipStream_t s) {
+// the instance of a plan (gemm_plan.h: grid, LDS bytes, g.HWX / g.MT / g.NT) for this translation unit's NTT and one KS
+template <int NTT, int KS>
+static inline void launch_wide_t(const GemmPlan& p, GemmArgs g, hipStream_t s) {
   constexpr int A0 = 4, R = 2;
   constexpr int C1 = 2 * NTT > 8 ? 2 * NTT - 8 : 0, KSTEP = 4 * (1024 + C1 * 128);
-  constexpr int LDS_MAIN = KS * KSTEP + 8 * 32 * 48;
-  static_assert(LDS_MAIN + WIDE_STAMP_LDS <= 160 * 1024, "LDS");
-  const int CPI = (g.HWX + 15) >> 4;
-  const long chunks = (long)g.NB * CPI;
-  g.NT = (int)((chunks + 2 * NTT - 1) / (2 * NTT));
-  g.MT = (g.M + 255) / 256;
-  cpi_magic(CPI, g.cpi_m, g.cpi_s);
-  const unsigned blocks = (unsigned)((long)g.MT * ((g.NT + 7) / 8 * 8));
-  const size_t lds = (size_t)LDS_MAIN + WIDE_STAMP_LDS;
+  static_assert(KS * KSTEP + 8 * 32 * 48 + WIDE_STAMP_LDS <= 160 * 1024, "LDS");
+  fastdiv_magic((g.HWX + 15) >> 4, g.cpi_m, g.cpi_s);  // chunks per image
   const bool nonneg = g.act == ACT_RELU || g.act == ACT_RELU6;
-  if (OUT == OUT_I8 && !nonneg) {
-    auto kfn = gemm_i8_wide_kernel<NTT, KS, OUT, A0, R, false>;
-    (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(kfn, dim3(blocks), dim3(512), lds, s, g);
-  } else {
-    auto kfn = gemm_i8_wide_kernel<NTT, KS, OUT, A0, R, true>;
-    (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(kfn, dim3(blocks), dim3(512), lds, s, g);
-  }
-}
-
-template <int NTT, int KS>
-static inline void launch_wide_o(const GemmArgs& g, int out, hipStream_t s) {
-  if (out == OUT_I32) launch_wide_t<NTT, KS, OUT_I32>(g, s);
-  else if (out == OUT_F32) launch_wide_t<NTT, KS, OUT_F32>(g, s);
-  else launch_wide_t<NTT, KS, OUT_I8>(g, s);
+  with_const<OUT_I32, OUT_F32, OUT_I8>(p.OUT, [&](auto out_c) {
+    constexpr int OUT = decltype(out_c)::value;
+    auto launch = [&](auto nn) {
+      auto kfn = gemm_i8_wide_kernel<NTT, KS, OUT, A0, R, decltype(nn)::value != 0>;
+      (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
+      hipLaunchKernelGGL(kfn, dim3(p.grid), dim3(512), p.lds, s, g);
+    };
+    with_const<0, 1>(OUT == OUT_I8 && !nonneg ? 0 : 1, launch);  // NONNEG: the packed requantisation of relu / relu6
+  });
 }
 
 }  // namespace plhip

@@ -4,11 +4,11 @@
 
 namespace plhip {
 
-void launch_wide_n4(const GemmArgs& g, int out, hipStream_t s) {
-  if (g.KS == 4) launch_wide_o<4, 4>(g, out, s);
-  else if (g.KS == 8) launch_wide_o<4, 8>(g, out, s);
-  else if (g.KS == 16) launch_wide_o<4, 16>(g, out, s);
-  else if (g.KS == 32) launch_wide_o<4, 32>(g, out, s);
+void launch_wide_n4(const GemmPlan& p, const GemmArgs& g, hipStream_t s) {
+  if (g.KS == 4) launch_wide_t<4, 4>(p, g, s);
+  else if (g.KS == 8) launch_wide_t<4, 8>(p, g, s);
+  else if (g.KS == 16) launch_wide_t<4, 16>(p, g, s);
+  else if (g.KS == 32) launch_wide_t<4, 32>(p, g, s);
 }
 
 }  // namespace plhip

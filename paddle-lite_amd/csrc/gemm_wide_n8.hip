@@ -4,10 +4,10 @@
 
 namespace plhip {
 
-void launch_wide_n8(const GemmArgs& g, int out, hipStream_t s) {
-  if (g.KS == 4) launch_wide_o<8, 4>(g, out, s);
-  else if (g.KS == 8) launch_wide_o<8, 8>(g, out, s);
-  else if (g.KS == 16) launch_wide_o<8, 16>(g, out, s);
+void launch_wide_n8(const GemmPlan& p, const GemmArgs& g, hipStream_t s) {
+  if (g.KS == 4) launch_wide_t<8, 4>(p, g, s);
+  else if (g.KS == 8) launch_wide_t<8, 8>(p, g, s);
+  else if (g.KS == 16) launch_wide_t<8, 16>(p, g, s);
 }
 
 }  // namespace plhip

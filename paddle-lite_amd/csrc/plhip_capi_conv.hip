@@ -151,40 +151,49 @@ plhip::GemmArgs gemm_args(Desc d, Geom g) {
   a.im_s = 1;
   return a;
 }
+// One launch_gemm_i8 call without its pointers: the shape half of the arguments, as direct_s2_args for the stems, and what the
+// shape alone says about vector stores and aligned rows.  The caller adds the pointers and their alignment.
+struct GemmCall {
+  plhip::GemmArgs a;
+  bool vec_store, aligned_loads;
+};
 struct GemmB {  // the B operand of the GEMM route: the NCHW slab itself (1x1) or the im2col buffer
-  const int8_t* base;
   size_t bstride, gstride;
   int xp;
   long bytes;
-  bool aligned_loads;
+  bool aligned_rows;
 };
-plhip_status run_gemm_groups(plhip_ctx* ctx, Desc d, Geom g, const ConvIo& io, const GemmB& b) {
+GemmB gemm_b_1x1(Desc d, Geom g) { return {(size_t)d->cin * g.N, (size_t)g.Cg * g.N, g.N, (long)d->n * d->cin * g.N, (g.N & 3) == 0}; }
+GemmB gemm_b_im2col(Desc d, Geom g) { return {(size_t)g.G * g.Kg * g.Np, (size_t)g.Kg * g.Np, g.Np, (long)im2col_bytes(d, g), true}; }
+GemmCall gemm_call(Desc d, Geom g, const GemmB& b, int grp) {  // group grp of the 1x1 / im2col GEMM
+  GemmCall c = {gemm_args(d, g), g.Np == g.N, b.aligned_rows};
+  c.a.HWX = g.Np; c.a.XP = b.xp; c.a.NB = d->n; c.a.NT = cdiv(d->n * g.Np, 128);
+  c.a.x_bytes = b.bytes - (long)grp * (long)b.gstride;
+  c.a.x_bstride = b.bstride;
+  return c;
+}
+plhip_status run_gemm_groups(plhip_ctx* ctx, Desc d, Geom g, const ConvIo& io, const GemmB& b, const int8_t* base) {
   const size_t esz = out_elem_size(io.out);
-  const int hwx = g.Np;
-  const bool vec_store = hwx == g.N && vec_store_ok(io);
   for (int grp = 0; grp < g.G; ++grp) {
     const size_t yoff = (size_t)grp * g.Mg * g.N;
-    plhip::GemmArgs a = gemm_args(d, g);
+    GemmCall c = gemm_call(d, g, b, grp);
+    plhip::GemmArgs& a = c.a;
     set_tail(a, io.tail);
     a.wp = (const int8_t*)io.w_packed + (size_t)grp * g.MT32 * g.KS * 1024;
-    a.x = b.base + (size_t)grp * b.gstride;
+    a.x = base + (size_t)grp * b.gstride;
     a.y = io.y ? (char*)io.y + yoff * esz : nullptr;
     if (a.res) a.res += yoff;
     if (a.y2) a.y2 += yoff;
     a.scale = io.scale ? io.scale + (size_t)grp * g.Mg : nullptr;
     a.bias = io.bias ? io.bias + (size_t)grp * g.Mg : nullptr;
-    a.HWX = hwx; a.XP = b.xp; a.NB = d->n; a.NT = cdiv(d->n * hwx, 128);
-    a.x_bytes = b.bytes - (long)grp * (long)b.gstride;
-    a.x_bstride = b.bstride;
-    if (plhip::launch_gemm_i8(a, g.MA, (int)io.out, vec_store, b.aligned_loads, ctx->stream) != 0)
+    if (plhip::launch_gemm_i8(a, g.MA, (int)io.out, c.vec_store && vec_store_ok(io), c.aligned_loads && aligned(base, 4), ctx->stream) != 0)
       return fail(ctx, PLHIP_ERR_UNSUPPORTED, "conv2d: GEMM shape outside every kernel");
     LAUNCHCHK(ctx, "gemm_i8");
   }
   return PLHIP_OK;
 }
 plhip_status run_gemm_1x1(plhip_ctx* ctx, Desc d, Geom g, const ConvIo& io) {
-  const GemmB b = {io.x, (size_t)d->cin * g.N, (size_t)g.Cg * g.N, g.N, (long)d->n * d->cin * g.N, (g.N & 3) == 0 && aligned(io.x, 4)};
-  return run_gemm_groups(ctx, d, g, io, b);
+  return run_gemm_groups(ctx, d, g, io, gemm_b_1x1(d, g), io.x);
 }
 plhip_status run_im2col(plhip_ctx* ctx, Desc d, Geom g, const ConvIo& io) {
   const size_t need = im2col_bytes(d, g);
@@ -201,8 +210,7 @@ plhip_status run_im2col(plhip_ctx* ctx, Desc d, Geom g, const ConvIo& io) {
   ia.rows = (size_t)d->n * g.G * g.Kg;
   plhip::launch_im2col(ia, ctx->stream);
   LAUNCHCHK(ctx, "im2col");
-  const GemmB b = {(const int8_t*)io.workspace, (size_t)g.G * g.Kg * g.Np, (size_t)g.Kg * g.Np, g.Np, (long)need, true};
-  return run_gemm_groups(ctx, d, g, io, b);
+  return run_gemm_groups(ctx, d, g, io, gemm_b_im2col(d, g), (const int8_t*)io.workspace);
 }
 
 // ------------------------------------------------------------------ the direct stems: 3x3 stride 2 (small Cin) and ResNet50's 7x7 stride 2
@@ -335,25 +343,37 @@ plhip_status run_grouped3x3(plhip_ctx* ctx, Desc d, Geom g, const ConvIo& io) {
 }
 
 // ------------------------------------------------------------------ implicit GEMM on a zero-padded copy of the input
-// dense k x k stride-1 convs whose GEMM fits the LDS-DMA ring kernel (64-row wave tiles: M > 128, 32-row tiles: 96 < M <=
-// 128 with K >= 256) skip the im2col buffer: 1.08x the input instead of kh*kw x (BASELINE config #2 spent 128 of 149 us writing
-// its 57.8 MB im2col buffer)
+// dense k x k convs skip the im2col buffer: 1.08x the input instead of kh*kw x (BASELINE config #2 spent 128 of 149 us writing its
+// 57.8 MB im2col buffer)
+GemmCall implicit_call(Desc d, Geom g) {
+  int PH, PW;
+  padded_dims(d, &PH, &PW);
+  GemmCall c = {gemm_args(d, g), (g.ow & 3) == 0, true};
+  plhip::GemmArgs& a = c.a;
+  a.HWX = g.ow;  // an "image" of the column space is one output row
+  a.x_bytes = (long)padded_input_bytes(d, g);
+  a.NB = d->n * g.oh;
+  a.NT = 0;      // the plan's; XP and x_bstride stay 0
+  a.im_kw = d->kw; a.im_khkw = d->kh * d->kw; a.im_c = d->cin; a.im_ph = PH; a.im_pw = PW; a.im_oh = g.oh;
+  a.im_s = d->stride[0];
+  return c;
+}
+// The route takes what the GEMM plan of its own launch runs on the transposed-read ring kernel (any M > 32, K >= 97, stride 2 on
+// a phase-split padded copy: ResNet50's 7x7 stem and its three 3x3 downsampling convs), or -- GEMM_TR = 0 -- what the
+// first-generation ring kernel's own thresholds choose.  So run_implicit cannot meet a plan that declines.
 bool takes_implicit(Desc d, Geom g) {
   const bool s1 = d->stride[0] == 1 && d->stride[1] == 1, s2 = d->stride[0] == 2 && d->stride[1] == 2;
   if (!(d->groups == 1 && (s1 || s2) && d->dil[0] == 1 && d->dil[1] == 1 && d->kw <= 11 && d->kh * d->kw <= 121 &&
         plhip::knob("IMPLICIT_GEMM", 1) != 0))  // knob IMPLICIT_GEMM = 0: A/B runs against the im2col route
     return false;
-  const size_t padded = padded_input_bytes(d, g);
-  const bool fits = padded < ((size_t)1 << 31) - 4096 && (size_t)d->n * g.oh * rup(g.ow, 16) < ((size_t)1 << 31) - 1024;  // launch_gemm_tr's own bound (gemm_tr_i8.hip)
-  // transposed-read ring kernel: any M > 32, K >= 97, output rows down to 7 columns (one start-aligned 16-byte
-  // chunk per row: the 14x14 and 7x7 planes of ResNet50's last stages), and stride 2 on a phase-split padded copy
-  // (ResNet50's 7x7 stem and its three 3x3 downsampling convs); a 1x1 stride-2 conv would use one phase plane of
-  // four: it keeps the (strided-copy) im2col route
-  if (plhip::gemm_tr_enabled()) return fits && g.Mg > 32 && g.KS >= 4 && g.ow >= 7 && !(s2 && d->kh * d->kw == 1);
-  if (!s1) return false;
-  const int ma = (g.MA == 2 && g.Mg <= 128 && g.Mg > 64) ? 1 : g.MA;  // launch_gemm_i8's tile choice
-  const int mt = cdiv(g.Mg, 32 * ma);
-  return fits && g.ow >= 16 && mt >= 4 && g.KS >= 4 && (ma == 2 || g.KS >= 8);
+  // output rows down to 7 columns (one start-aligned 16-byte chunk per row: the 14x14 and 7x7 planes of ResNet50's last
+  // stages); a 1x1 stride-2 conv would use one phase plane of four: it keeps the (strided-copy) im2col route
+  if (padded_input_bytes(d, g) >= ((size_t)1 << 31) - 4096 || g.ow < 7 || (s2 && d->kh * d->kw == 1)) return false;
+  const GemmCall c = implicit_call(d, g);
+  plhip::GemmKnobs kn = plhip::gemm_knobs();
+  kn.variant = kn.ma = 0;  // these two pick a kernel for A/B runs; they never moved a conv to another route
+  const plhip::GemmPlan p = plhip::gemm_plan(plhip::gemm_problem(c.a, g.MA, plhip::GEMM_OUT_I8, c.vec_store, c.aligned_loads), kn);
+  return p.family == plhip::GEMM_TR || (p.family == plhip::GEMM_RING && p.on_merit);
 }
 plhip_status run_implicit(plhip_ctx* ctx, Desc d, Geom g, const ConvIo& io) {
   const size_t need = padded_input_bytes(d, g);
@@ -363,17 +383,11 @@ plhip_status run_implicit(plhip_ctx* ctx, Desc d, Geom g, const ConvIo& io) {
   padded_dims(d, &PH, &PW);
   plhip::launch_pad_input(pad_args(d, io, d->n * d->cin, PH, PW, need), ctx->stream);
   LAUNCHCHK(ctx, "pad_input");
-  plhip::GemmArgs a = gemm_args(d, g);
+  GemmCall c = implicit_call(d, g);
+  plhip::GemmArgs& a = c.a;
   set_tail(a, io.tail);
   a.wp = (const int8_t*)io.w_packed; a.x = (const int8_t*)io.workspace; a.y = io.y; a.scale = io.scale; a.bias = io.bias;
-  a.HWX = g.ow;  // an "image" of the column space is one output row
-  a.x_bytes = (long)need;
-  a.NB = d->n * g.oh;
-  a.NT = 0;      // set by the launcher from NB and HWX; XP and x_bstride stay 0
-  a.im_kw = d->kw; a.im_khkw = d->kh * d->kw; a.im_c = d->cin; a.im_ph = PH; a.im_pw = PW; a.im_oh = g.oh;
-  a.im_s = d->stride[0];
-  const bool vec_store = (g.ow & 3) == 0 && vec_store_ok(io);
-  if (plhip::launch_gemm_i8(a, g.MA, (int)io.out, vec_store, true, ctx->stream) != 0)
+  if (plhip::launch_gemm_i8(a, g.MA, (int)io.out, c.vec_store && vec_store_ok(io), c.aligned_loads, ctx->stream) != 0)
     return fail(ctx, PLHIP_ERR_UNSUPPORTED, "conv2d: implicit GEMM outside the transposed-read kernel's column space");
   LAUNCHCHK(ctx, "gemm_i8_implicit");
   return PLHIP_OK;
@@ -454,6 +468,27 @@ const char* plhip_conv_impl_name(const plhip_conv_desc* d) {
   ConvGeom g;
   const ConvRoute* r = pick_route(d, &g);
   return r ? r->name(d, g) : "invalid";
+}
+
+// Diagnostics, host only (not in include/plhip.h; paddle-lite_amd/capi.py declares it): the GEMM launch plan (gemm_plan.h) of a
+// conv on one of the three GEMM routes, as text, from the route's own argument builder and the knobs in force, assuming aligned
+// pointers.  out: the output kind; tail: bit 0 a residual, bit 1 the int8 copy, bit 2 the fp32 output dropped.  A non-GEMM route
+// answers the empty string.  Returns the text's length, or -1 for a bad descriptor or buffer.
+int plhip_debug_gemm_plan(const plhip_conv_desc* d, int out, int tail, char* buf, size_t cap) {
+  ConvGeom g;
+  const ConvRoute* r = pick_route(d, &g);
+  if (!r || !buf || cap == 0) return -1;
+  buf[0] = 0;
+  GemmCall c;
+  if (r->impl == IMPL_GEMM_1X1) c = gemm_call(d, g, gemm_b_1x1(d, g), 0);
+  else if (r->impl == IMPL_IM2COL_GEMM) c = gemm_call(d, g, gemm_b_im2col(d, g), 0);
+  else if (r->impl == IMPL_IMPLICIT_GEMM) c = implicit_call(d, g);
+  else return 0;
+  plhip::GemmProblem p = plhip::gemm_problem(c.a, g.MA, out, c.vec_store, c.aligned_loads);
+  p.res = (tail & 1) != 0;
+  p.y2 = (tail & 2) != 0;
+  p.y = (tail & 4) == 0;
+  return plhip::gemm_plan_text(plhip::gemm_plan(p, plhip::gemm_knobs()), buf, cap);
 }
 
 static plhip_status conv2d_impl(plhip_ctx* ctx, const plhip_conv_desc* d, const ConvIo& io) {

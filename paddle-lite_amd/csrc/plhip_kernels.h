@@ -4,6 +4,10 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <type_traits>
+
+#include "gemm_plan.h"
+
 namespace plhip {
 
 // A/B knobs of the launchers: name -> value set through plhip_debug_set (include/plhip.h), else the
@@ -244,17 +248,30 @@ struct DwConvArgs {
 bool dw_conv1x1_plan(DwConvArgs* a);
 void launch_dw_conv1x1(const DwConvArgs& a, int out, hipStream_t s);
 
-int launch_gemm_i8(const GemmArgs& g, int ma, int out, bool vec_store, bool aligned_loads, hipStream_t s);  // 0 or -3
-// second-generation ring kernel (gemm_tr_i8.hip); false = shape outside it, the caller falls back
-bool launch_gemm_tr(const GemmArgs& g, int out, hipStream_t s);
-int gemm_tr_enabled();
-// third-generation kernel: one wide tile per CU (gemm_wide_i8.hip); false = shape outside it, the caller falls back
-bool launch_gemm_wide(const GemmArgs& g, int out, hipStream_t s);
-int gemm_wide_ntt(const GemmArgs& g);  // n tiles per block it would use, 0 = not taken
-void debug_set_wide_ntt(int v);
-void launch_wide_n4(const GemmArgs& g, int out, hipStream_t s);  // per-tile translation units (gemm_wide_n*.hip)
-void launch_wide_n7(const GemmArgs& g, int out, hipStream_t s);
-void launch_wide_n8(const GemmArgs& g, int out, hipStream_t s);  // 4 / 7 / 8 force that tile, 0 = automatic, -1 = back to the environment's choice
+// ---- the GEMM kernels.  gemm_plan (gemm_plan.h) decides the whole launch; the three files below only execute a plan.
+inline GemmProblem gemm_problem(const GemmArgs& g, int ma, int out, bool vec_store, bool aligned_loads) {
+  return GemmProblem{g.M, g.K, g.KS, g.HWX, g.HWY, g.XP, g.NB, g.im_kw, g.im_s, g.res != nullptr, g.y2 != nullptr, g.y != nullptr,
+                     out, ma, vec_store, aligned_loads};
+}
+// the knobs the plan reads, the two ways to force the wide tile resolved (gemm_i8.hip).  Host only.
+GemmKnobs gemm_knobs();
+void debug_set_wide_ntt(int v);  // plhip_debug_wide_ntt: 4 / 7 / 8 force that tile, 0 = automatic, -1 = back to the knob WIDE_NTT
+int gemm_tr_stamp_lds();         // LDS bytes of the timeline stamps (EXPERIMENTS=1 builds, else 0)
+int gemm_wide_stamp_lds();
+// plans and launches; 0, or -3 when the operand exists on one kernel only and that kernel declines it (nothing is launched)
+int launch_gemm_i8(const GemmArgs& g, int ma, int out, bool vec_store, bool aligned_loads, hipStream_t s);
+// executors: g carries the plan's HWX / MT / NT already
+void run_gemm_tr(const GemmPlan& p, GemmArgs g, hipStream_t s);    // gemm_tr_i8.hip
+void run_gemm_wide(const GemmPlan& p, GemmArgs g, hipStream_t s);  // gemm_wide_i8.hip
+void launch_wide_n4(const GemmPlan& p, const GemmArgs& g, hipStream_t s);  // per-tile translation units (gemm_wide_n*.hip)
+void launch_wide_n7(const GemmPlan& p, const GemmArgs& g, hipStream_t s);
+void launch_wide_n8(const GemmPlan& p, const GemmArgs& g, hipStream_t s);
+// A run-time value as a template argument: calls f(std::integral_constant<int, V>{}) for the V of Vs... that equals v (bools
+// as 0 / 1); false when none does.  Only the listed values are instantiated.
+template <int... Vs, class F>
+inline bool with_const(int v, F&& f) {
+  return ((v == Vs ? (f(std::integral_constant<int, Vs>{}), true) : false) || ...);
+}
 void launch_pack_weights(const int8_t* w, int8_t* wp, int G, int Mg, int Kg, int MT32, int KS, hipStream_t s);
 void launch_im2col(const Im2colArgs& a, hipStream_t s);
 // fills the LDS tiling (PB, OB, bands, in_rows, pitch) from the shape fields; false = a single row band does not fit in LDS

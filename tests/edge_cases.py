@@ -131,7 +131,8 @@ ROUTES = [
     _r("gemm_wide_n4", "conv", (2, 128, 4, 8, 256, 1, 1, (0,) * 4, 1, 1, 1), G1, {"WIDE_NTT": 4}, 1024),
     _r("gemm_wide_n7", "conv", (2, 128, 4, 8, 256, 1, 1, (0,) * 4, 1, 1, 1), G1, {"WIDE_NTT": 7}, 512),
     _r("gemm_wide_n8", "conv", (2, 128, 4, 8, 256, 1, 1, (0,) * 4, 1, 1, 1), G1, {"WIDE_NTT": 8}, 512),
-    _r("implicit_gemm_tr", "conv", (2, 24, 9, 16, 128, 5, 5, (2,) * 4, 1, 1, 1), "conv_implicit_gemm_int8_mfma32x32x32", {}, 48),
+    _r("implicit_gemm_tr", "conv", (2, 24, 9, 16, 128, 5, 5, (2,) * 4, 1, 1, 1), "conv_implicit_gemm_int8_mfma32x32x32", {}, 48,
+       kernel="gemm_tr_2x2"),
     _r("patch_s1", "conv", (2, 64, 8, 14, 96, 3, 3, (1,) * 4, 1, 1, 1), "conv_patch_gemm_int8_mfma32x32x32", {}, 128),
     _r("patch_s2", "conv", (2, 64, 12, 14, 96, 3, 3, (1,) * 4, 2, 1, 1), "conv_patch_s2_gemm_int8_mfma32x32x32", {}, 128),
     _r("direct3x3s2_mfma", "conv", (2, 3, 16, 16, 40, 3, 3, (1,) * 4, 2, 1, 1), "conv_3x3s2_direct_int8_mfma32x32x32"),
@@ -166,55 +167,34 @@ ROUTES = [
 STREAM_SHAPES = {(32, 112, 1, 64), (128, 56, 1, 128), (256, 28, 1, 256), (64, 112, 2, 128), (128, 56, 2, 256), (256, 28, 2, 512)}
 
 
-def _wide_ntt(m, k, hw, nb, kn, out):
-    """gemm_wide_ntt + launch_gemm_wide (gemm_wide_i8.hip): the n tiles of the wide kernel, 0 when it declines."""
-    ks = (k + 31) // 32
-    if kn.get("GEMM_WIDE", 1) == 0 or k != ks * 32 or ks not in (4, 8, 16, 32) or m < 256 or hw < 16:
-        return 0
-    force = kn.get("WIDE_NTT", 0)
-    if out != "i8" and force == 0:
-        return 0
-    chunks, best, best_cost = nb * ((hw + 15) >> 4), 0, 1e30
-    for ntt in (4, 7, 8):
-        if force and ntt != force:
-            continue
-        c1 = max(2 * ntt - 8, 0)
-        if ks * 4 * (1024 + c1 * 128) + 8 * 32 * 48 > 160 * 1024:
-            continue
-        cost = (((chunks + 2 * ntt - 1) // (2 * ntt)) * ((m + 255) // 256) + 255) // 256 * (ks * 32 * (256 + 32 * ntt) + 40000.0)
-        if cost < best_cost:
-            best, best_cost = ntt, cost
-    return 0 if (best != 4 and ks == 32) else best
+class Knobs:
+    """The route's knobs forced through plhip_debug_set for a `with` block, then back at KNOB_DEFAULTS."""
+
+    def __init__(self, lib, knobs):
+        self.lib, self.knobs = lib, knobs
+
+    def __enter__(self):
+        for k, v in self.knobs.items():
+            assert self.lib.plhip_debug_set(k.encode(), int(v)) == 0, k
+
+    def __exit__(self, *a):
+        for k in self.knobs:
+            self.lib.plhip_debug_set(k.encode(), KNOB_DEFAULTS[k])
 
 
-def gemm_kernel(m, k, hw, nb, kn, out):
-    """Which kernel launch_gemm_i8 (gemm_i8.hip) runs for a dense 1x1 stride-1 conv (M = cout, K = cin, HW = the plane,
-    nb images) under the knobs kn: a host-side restatement of the launcher's choice."""
-    var, ks = kn.get("GEMM_VARIANT", 0), (k + 31) // 32
-    if var == 0:
-        ntt = _wide_ntt(m, k, hw, nb, kn, out)
-        if ntt:
-            return "gemm_wide_n%d" % ntt
-    ma, ma_env = (2 if m > 32 else 1), kn.get("GEMM_MA", 0)
-    if ma == 2 and ((ma_env == 0 and 64 < m <= 128) or ma_env == 1):
-        ma = 1
-    if ma == 2 and ma_env == 0 and ((m & 63) and (m & 63) <= 32 or (ks <= 2 and m > 64) or (ks == 1 and m == 64)):
-        ma = 1
-    mt = (m + 32 * ma - 1) // (32 * ma)
-    if hw >= 16 and ks >= 4 and (var == 3 or (var == 0 and mt >= 4 and (ma == 2 or ks >= 8))):
-        areg = kn.get("GEMM_AREG", 1) and ks % 4 == 0 and m % 64 == 0 and ma == 2 and ks // 4 in (1, 2, 4, 8)
-        return "gemm_areg" if areg else ("gemm_ring" if ma == 2 else "gemm_ring_ma1")
-    if var == 2 or (var == 0 and mt >= 2 and ks >= 2):
-        return "gemm_vperm_lds"
-    return "gemm_nchw"
+GEMM_IMPLS = (G1, "conv_implicit_gemm_int8_mfma32x32x32")
+OUT_KINDS = {"i32": 0, "f32": 1, "i8": 2}  # plhip_out_kind
 
 
-def kernel_of(route, cin, out):
-    """The kernel the route's launch reaches (the route table's `kernel`), from the launchers' host logic."""
+def kernel_of(capi, route, cin, out):
+    """The kernel the route's launch reaches (the route table's `kernel`) under the knobs in force.  The GEMM routes ask the
+    library for its own launch plan (capi.gemm_plan_text: csrc/gemm_plan.h, the function the launcher executes); the others
+    restate their launchers' host logic."""
     n, _, h, w, cout, kh, kw, pads, st, dl, g = route["shape"]
     kn = route["knobs"]
-    if route["kind"] == "conv" and route["impl"] == G1:
-        return gemm_kernel(cout, cin, h * w, n, kn, out)
+    if route["kind"] == "conv" and route["impl"] in GEMM_IMPLS:
+        d = capi.conv_desc(n, cin, h, w, cout, kh, kw, pads, (st, st), (dl, dl), g)
+        return capi.gemm_plan_text(d, OUT_KINDS[out]).split(" ")[0]
     if route["kind"] == "dwpw":
         oh = (h + pads[0] + pads[1] - 3) // st + 1
         if (cin, h, st, route["m"]) in STREAM_SHAPES:

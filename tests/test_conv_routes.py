@@ -50,3 +50,29 @@ def test_sweep_equals_snapshot(pkg, setting):
     assert len(got) == len(want) == 48
     for g, w in zip(got, want):
         assert g == w, "the sweep group differs\n  library : %s\n  recorded: %s" % (g, w)
+
+
+GEMM_IMPLS = {"conv1x1s1_gemm_int8_mfma32x32x32", "conv_implicit_gemm_int8_mfma32x32x32", "conv_im2col_gemm_int8_mfma32x32x32"}
+
+
+def test_every_gemm_route_line_has_a_launch_plan(pkg):
+    """What takes_implicit used to guarantee by copying the launchers' thresholds: a descriptor the route table sends to a GEMM
+    route gets a launch plan from the same function the launcher executes (csrc/gemm_plan.h), for every output kind and fused
+    tail, and never the "none" outcome that run_implicit reports as unsupported.  The other routes answer no plan."""
+    capi, n_gemm = pkg.capi, 0
+    for ln in dump.load_fixture("lines.txt"):
+        f, impl = ln.split(" | ")[0].split(), ln.split(" | ")[1].split()[0]
+        if impl == "invalid":
+            continue
+        v = [int(x) for x in f]
+        d = capi.conv_desc(*v[:7], pad=v[7:11], stride=v[11:13], dil=v[13:15], groups=v[15])
+        cases = [(capi.OUT_I32, 0), (capi.OUT_I8, 0), (capi.OUT_F32, 0), (capi.OUT_F32, capi.TAIL_RESIDUAL),
+                 (capi.OUT_F32, capi.TAIL_INT8_COPY | capi.TAIL_NO_F32)]
+        for out, tail in cases:
+            plan = capi.gemm_plan_text(d, out, tail)
+            if impl in GEMM_IMPLS:
+                assert plan and " family=" in plan and " family=none " not in plan, (ln, out, tail, plan)
+            else:
+                assert plan == "", (ln, plan)
+        n_gemm += impl in GEMM_IMPLS
+    assert n_gemm >= 100

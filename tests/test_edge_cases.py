@@ -45,16 +45,18 @@ def test_generator_reaches_every_edge(plref):
     assert len(over) >= 8, big
 
 
-def test_every_route_reaches_the_kernel_it_names():
-    """The route table against the launchers' host logic (edge_cases.kernel_of): each forced knob lands on its kernel, for
-    every output kind and for the maximum-magnitude K as well, and every kernel of the table is reached."""
+def test_every_route_reaches_the_kernel_it_names(pkg):
+    """The route table against the library's own launch plan for the GEMM routes and the launchers' restated host logic for the
+    others (edge_cases.kernel_of): each forced knob lands on its kernel, for every output kind and for the maximum-magnitude K
+    as well, and every kernel of the table is reached."""
     seen = set()
     for r in E.ROUTES:
-        for cin in {r["shape"][1], r["mm_cin"] or r["shape"][1]}:
-            for out in ("i32", "i8", "f32"):
-                k = E.kernel_of(r, cin, out)
-                assert k == r["kernel"], (r["name"], cin, out, k)
-                seen.add(k)
+        with E.Knobs(pkg.capi.load(), r["knobs"]):
+            for cin in {r["shape"][1], r["mm_cin"] or r["shape"][1]}:
+                for out in ("i32", "i8", "f32"):
+                    k = E.kernel_of(pkg.capi, r, cin, out)
+                    assert k == r["kernel"], (r["name"], cin, out, k)
+                    seen.add(k)
     assert {"gemm_nchw", "gemm_vperm_lds", "gemm_ring", "gemm_ring_ma1", "gemm_areg", "gemm_wide_n4", "gemm_wide_n7",
             "gemm_wide_n8", "dwpw_14x14", "dwpw_14x14_mtw2", "dwpw_stream", "dwpw_7x7", "dw_band", "dw_generic", "fc_dot4",
             "fc_mfma"} <= seen

@@ -15,19 +15,6 @@ import edge_cases as E
 pytestmark = pytest.mark.gpu
 
 
-class _Knobs:
-    def __init__(self, lib, knobs):
-        self.lib, self.knobs = lib, knobs
-
-    def __enter__(self):
-        for k, v in self.knobs.items():
-            assert self.lib.plhip_debug_set(k.encode(), int(v)) == 0, k
-
-    def __exit__(self, *a):
-        for k in self.knobs:
-            self.lib.plhip_debug_set(k.encode(), E.KNOB_DEFAULTS[k])
-
-
 def _eq(got, want, what):
     assert got.dtype == want.dtype, what
     if got.dtype == np.float32:  # bit for bit (the same fmaf on both sides); -0.0 and 0.0 differ here
@@ -46,10 +33,11 @@ def _desc(capi, c, route, act, alpha):
     return capi.conv_desc(n, cin, h, w, cout, kh, kw, pads, (st, st), (dl, dl), g, act, alpha)
 
 
-def _ran(route, c):
-    """The kernels the route's launches reach for every output kind (the launchers' host logic, edge_cases.kernel_of)."""
+def _ran(capi, route, c):
+    """The kernels the route's launches reach for every output kind under the knobs in force (edge_cases.kernel_of: the
+    library's own launch plan for the GEMM routes)."""
     cin = c["cin"] if "cin" in c else c["x"].shape[1]
-    return {E.kernel_of(route, cin, out) for out in ("i32", "i8", "f32")}
+    return {E.kernel_of(capi, route, cin, out) for out in ("i32", "i8", "f32")}
 
 
 def _run(ctx, capi, route, c, act, alpha):
@@ -114,11 +102,11 @@ def test_every_route_on_its_value_edges(gpu_ctx, pkg, plref, maxmag):
         acts = E.acts_of(route)
         if maxmag:  # no activation, and leaky where the route has it
             acts = acts[:1] if route["kind"] in ("fc", "tail") else (acts[0], (E.ACT_LEAKY, 0.375))
-        with _Knobs(lib, route["knobs"]):
+        with E.Knobs(lib, route["knobs"]):
             for j, (act, alpha) in enumerate(acts):
                 c = E.make_case(plref, route, act, alpha, maxmag, 7000 * maxmag + 100 * i + j)
                 _run(gpu_ctx, capi, route, c, act, alpha)
-                k = _ran(route, c)
+                k = _ran(capi, route, c)
                 assert k == {route["kernel"]}, (route["name"], k)  # the knob reached the kernel the route names
                 ran |= k
     assert ran == {r["kernel"] for r in E.ROUTES}, sorted(ran)
@@ -196,7 +184,7 @@ def test_batch_sweep_matches_single_images(gpu_ctx, pkg, plref):
         c = E.make_case(plref, route, act, alpha, False, 9000 + i)
         ref = c["ref_i8"]
         assert len({ref[b].tobytes() for b in range(big)}) == big, name  # distinct images, distinct outputs
-        with _Knobs(lib, route["knobs"]), _Poisoned(gpu_ctx):
+        with E.Knobs(lib, route["knobs"]), _Poisoned(gpu_ctx):
             for n in ns:
                 y = _y(gpu_ctx, capi, *reversed(_first(c, route, n)), act, alpha)
                 for b in range(n):
