@@ -137,6 +137,10 @@ plhip_status plhip_conv2d_int8_fused(plhip_ctx* ctx, const plhip_conv_desc* d, c
                                      const float* scale, const float* bias, float* y_f32, const float* residual,
                                      int residual_relu, int8_t* y_i8, float calib_scale, void* workspace,
                                      size_t workspace_bytes);
+/* 1 where the route that runs `d` takes a residual operand / an int8 copy; 0 for a bad descriptor and for the direct 3x3
+ * stride-2 stem, which has no fused tail (plhip_conv2d_int8_fused with a tail returns PLHIP_ERR_UNSUPPORTED there).  The graph
+ * builder asks before it lets a conv take its tail over. */
+int plhip_conv2d_fused_supported(const plhip_conv_desc* d);
 
 /* ---- calib[fp32_to_int8] + conv2d in one launch (graph-level fusion on this target) ----
  * Replaces the instruction pair  calib[fp32_to_int8](scale) ; conv2d 3x3 s2 (Cin <= 3)  at the head of the MobileNet programs
@@ -344,6 +348,40 @@ size_t plhip_se_gate_packed_weight_bytes(int c, int cr);
 plhip_status plhip_pack_se_gate_weights(plhip_ctx* ctx, int c, int cr, const int8_t* w1_cr_c, const int8_t* w2_c_cr, void* w_packed);
 plhip_status plhip_se_gate_int8(plhip_ctx* ctx, const plhip_se_gate_desc* d, const float* pooled, const void* w_packed,
                                 const float* scale1, const float* bias1, const float* scale2, const float* bias2, float* gate);
+
+/* ---- the fp32 ops that join, part and permute tensors along an axis (shuffle_ops.hip).  All tensors are dense fp32.  An op
+ * along `axis` of dims is described by outer = prod(dims[:axis]), the extent of each part along the axis, and inner =
+ * prod(dims[axis+1:]).  fp32 values are moved: the output bits equal the input bits (NaN payloads, -0.0).  Where every row of
+ * every operand starts 16-byte aligned (aligned bases, extent * inner a multiple of 4 for each part) a lane moves 16 bytes,
+ * anything else takes a scalar path.  No call copies to the device or synchronises: all may be captured by plhip_graph_begin.
+ *
+ * plhip_concat_f32 replaces ConcatCompute (lite/kernels/arm/concat_compute.cc:37-57): `count` >= 1 inputs xs[i] of
+ * [outer][extents[i]][inner] into y [outer][sum extents][inner].  outer, inner, extents[i] >= 1; xs, every xs[i], extents and y
+ * non-null; outer * sum(extents) * inner <= 2^40 elements.  The input pointers travel in the kernel's arguments, 8 per launch: more inputs are several launches of the one
+ * call.  xs / extents are host arrays, read before the call returns. */
+plhip_status plhip_concat_f32(plhip_ctx* ctx, const float* const* xs, const int64_t* extents, int count, int64_t outer,
+                              int64_t inner, float* y);
+/* plhip_split_f32 replaces SplitCompute (lite/backends/arm/math/split.cc:54-82, shapes lite/operators/split_op.cc:32-75):
+ * x [outer][extent][inner] into `count` >= 1 outputs ys[i] [outer][e_i][inner].  num > 0: equal parts, e_i = extent / num,
+ * num must divide extent and count == num (sections is ignored, may be NULL); num == 0: e_i = sections[i] >= 1, which must add
+ * up to extent; outer * extent * inner <= 2^40 elements.  Anything else is refused. */
+plhip_status plhip_split_f32(plhip_ctx* ctx, const float* x, int64_t outer, int64_t extent, int64_t inner, int num,
+                             const int64_t* sections, int count, float* const* ys);
+/* plhip_shuffle_channel_f32 replaces ShuffleChannelCompute -> shuffle_channel<float>
+ * (lite/backends/arm/math/shuffle_channel.cc:24-55): x [n][c][hw], out[b][j * group + i] = in[b][i * (c / group) + j].
+ * n, c, hw, group >= 1, group divides c, n * c <= 2^30.  Outputs as plhip_hard_act_f32: y_f32, y_i8 (the calib[fp32_to_int8]
+ * with calib_scale behind it, quantised exactly as plhip_calib_f32_to_i8 does: calib_scale > 0 required), or both; at least
+ * one.  Vector path: hw % 4 == 0, x / y_f32 16-byte and y_i8 4-byte aligned. */
+plhip_status plhip_shuffle_channel_f32(plhip_ctx* ctx, const float* x, int n, int c, int hw, int group, float* y_f32, int8_t* y_i8,
+                                       float calib_scale);
+/* The tail of a ShuffleNetV2 unit in ONE launch: concat([a, b], axis 1) -> shuffle_channel(group 2) -> split at channel split_at
+ * -> calib[fp32_to_int8] of the second part; byte for byte what the four calls write.  a, b [n][h][hw] fp32, non-null.  Shuffled
+ * channel c' in [0, 2 h) is (c' % 2 ? b : a)[c' / 2]; channels < split_at go to lo_f32 [n][split_at][hw], the rest to hi_f32
+ * and / or hi_i8 [n][2 h - split_at][hw].  0 <= split_at <= 2 h; lo_f32 is NULL exactly when split_at == 0; with split_at < 2 h at
+ * least one of hi_f32 / hi_i8 is required, with split_at == 2 h both are ignored; calib_scale > 0 with hi_i8.  n, h, hw >= 1,
+ * n * h <= 2^29.  Vector path: hw % 4 == 0, fp32 pointers 16-byte and hi_i8 4-byte aligned. */
+plhip_status plhip_shuffle_unit_f32(plhip_ctx* ctx, const float* a, const float* b, int n, int h, int hw, int split_at,
+                                    float* lo_f32, float* hi_f32, int8_t* hi_i8, float calib_scale);
 
 /* ---- introspection used by tests: operand-layout self-check of the MFMA tile on this device.
  * Runs a tiny known-answer GEMM through the MFMA path; returns PLHIP_OK iff bit-exact. ---- */

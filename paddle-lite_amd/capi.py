@@ -23,7 +23,7 @@ EXPORTS = [
     "plhip_memcpy_d2h", "plhip_memcpy_d2d", "plhip_memset", "plhip_stream_sync", "plhip_event_create",
     "plhip_event_record", "plhip_event_elapsed_ms", "plhip_event_destroy",
     "plhip_conv_packed_weight_bytes", "plhip_pack_conv_weights", "plhip_conv_workspace_bytes",
-    "plhip_conv2d_int8", "plhip_conv2d_int8_fused", "plhip_conv_impl_name", "plhip_depthwise_conv_int8", "plhip_dwpw_fused_int8", "plhip_dwpw_fused_supported", "plhip_dw_conv1x1_fused_int8", "plhip_dw_conv1x1_fused_supported", "plhip_graph_begin", "plhip_graph_end", "plhip_graph_launch", "plhip_graph_destroy",
+    "plhip_conv2d_int8", "plhip_conv2d_int8_fused", "plhip_conv2d_fused_supported", "plhip_conv_impl_name", "plhip_depthwise_conv_int8", "plhip_dwpw_fused_int8", "plhip_dwpw_fused_supported", "plhip_dw_conv1x1_fused_int8", "plhip_dw_conv1x1_fused_supported", "plhip_graph_begin", "plhip_graph_end", "plhip_graph_launch", "plhip_graph_destroy",
     "plhip_fc_packed_weight_bytes", "plhip_pack_fc_weights", "plhip_fc_int8",
     "plhip_calib_f32_to_i8", "plhip_calib_i8_to_f32", "plhip_global_avg_pool_f32", "plhip_softmax_f32",
     "plhip_pool2d_f32", "plhip_pool2d_max_i8", "plhip_elementwise_add_f32", "plhip_selftest",
@@ -32,6 +32,7 @@ EXPORTS = [
     "plhip_image_resize_tables", "plhip_image_convert_u8", "plhip_image_resize_u8", "plhip_frame_to_tensor_f32", "plhip_frame_to_tensor_i8",
     "plhip_hard_act_f32", "plhip_se_scale_f32",
     "plhip_se_gate_supported", "plhip_se_gate_packed_weight_bytes", "plhip_pack_se_gate_weights", "plhip_se_gate_int8",
+    "plhip_concat_f32", "plhip_split_f32", "plhip_shuffle_channel_f32", "plhip_shuffle_unit_f32",
 ]
 
 # plhip_hard_act_kind, and the reference's default parameters (lite/operators/op_params.h:406-412)
@@ -196,6 +197,7 @@ def load():
     L.plhip_conv2d_int8.argtypes = [vp, C.POINTER(ConvDesc), vp, vp, vp, vp, vp, i32, vp, sz]
     L.plhip_conv2d_int8_fused.argtypes = [vp, C.POINTER(ConvDesc), vp, vp, vp, vp, vp, vp, i32, vp, f32, vp, sz]
     L.plhip_conv2d_calib_supported.argtypes = [C.POINTER(ConvDesc)]
+    L.plhip_conv2d_fused_supported.argtypes = [C.POINTER(ConvDesc)]
     L.plhip_conv2d_calib_int8.argtypes = [vp, C.POINTER(ConvDesc), vp, f32, vp, vp, vp, vp, i32]
     L.plhip_image_to_tensor_f32.argtypes = [vp, C.POINTER(ImageDesc), vp, vp]
     L.plhip_image_to_tensor_i8.argtypes = [vp, C.POINTER(ImageDesc), vp, vp, f32]
@@ -241,6 +243,10 @@ def load():
     L.plhip_se_gate_packed_weight_bytes.restype = C.c_size_t
     L.plhip_pack_se_gate_weights.argtypes = [vp, i32, i32, vp, vp, vp]
     L.plhip_se_gate_int8.argtypes = [vp, C.POINTER(SeGateDesc), vp, vp, vp, vp, vp, vp, vp]
+    L.plhip_concat_f32.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int64), i32, C.c_int64, C.c_int64, vp]
+    L.plhip_split_f32.argtypes = [vp, vp, C.c_int64, C.c_int64, C.c_int64, i32, C.POINTER(C.c_int64), i32, C.POINTER(vp)]
+    L.plhip_shuffle_channel_f32.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, f32]
+    L.plhip_shuffle_unit_f32.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, f32]
     L.plhip_selftest.argtypes = [vp]
     _lib = L
     return L
@@ -676,3 +682,92 @@ class Context:
         for p in ptrs + [q for q in (db1, db2) if q is not None]:
             self.free(p)
         return y
+
+    # ---- concat / split / shuffle_channel and the fused unit tail (shuffle_ops.hip).  misalign: elements every device base is
+    # moved off its allocation's alignment (the scalar path)
+    def _up_f32(self, x, misalign):
+        """Uploads x behind `misalign` elements of slack; returns (allocation, pointer to the data)."""
+        x = np.ascontiguousarray(x, np.float32)
+        buf = self.malloc(4 * (x.size + misalign) + 4)
+        d = C.c_void_p(buf.value + 4 * misalign)
+        if x.nbytes:
+            self.check(self.L.plhip_memcpy_h2d(self.h, d, x.ctypes.data_as(C.c_void_p), x.nbytes), "h2d")
+        return buf, d
+
+    def _out_buf(self, count, esize, misalign):
+        buf = self.malloc(esize * (count + misalign) + 8)
+        return buf, C.c_void_p(buf.value + esize * misalign)
+
+    def concat(self, xs, axis, misalign=0):
+        """plhip_concat_f32 of fp32 arrays along `axis`."""
+        xs = [np.ascontiguousarray(x, np.float32) for x in xs]
+        axis = axis + xs[0].ndim if axis < 0 else axis
+        outer = int(np.prod(xs[0].shape[:axis], dtype=np.int64))
+        inner = int(np.prod(xs[0].shape[axis + 1:], dtype=np.int64))
+        ups = [self._up_f32(x, misalign) for x in xs]
+        shape = list(xs[0].shape)
+        shape[axis] = sum(x.shape[axis] for x in xs)
+        ybuf, dy = self._out_buf(int(np.prod(shape)), 4, misalign)
+        ptrs = (C.c_void_p * len(xs))(*[d for _b, d in ups])
+        ext = (C.c_int64 * len(xs))(*[x.shape[axis] for x in xs])
+        self.check(self.L.plhip_concat_f32(self.h, ptrs, ext, len(xs), outer, inner, dy), "concat")
+        y = self.to_host(dy, tuple(shape), np.float32)
+        for b in [ybuf] + [b for b, _d in ups]:
+            self.free(b)
+        return y
+
+    def split(self, x, axis, num=0, sections=(), misalign=0):
+        """plhip_split_f32: num > 0 equal parts, else `sections`.  Returns the list of parts."""
+        x = np.ascontiguousarray(x, np.float32)
+        axis = axis + x.ndim if axis < 0 else axis
+        outer = int(np.prod(x.shape[:axis], dtype=np.int64))
+        inner = int(np.prod(x.shape[axis + 1:], dtype=np.int64))
+        ext = [x.shape[axis] // num] * num if num > 0 else list(sections)
+        xbuf, dx = self._up_f32(x, misalign)
+        outs = [self._out_buf(outer * e * inner, 4, misalign) for e in ext]
+        ptrs = (C.c_void_p * len(ext))(*[d for _b, d in outs])
+        sec = (C.c_int64 * max(1, len(sections)))(*sections) if num == 0 else None
+        self.check(self.L.plhip_split_f32(self.h, dx, outer, x.shape[axis], inner, int(num), sec, len(ext), ptrs), "split")
+        ys = []
+        for e, (_b, d) in zip(ext, outs):
+            shape = list(x.shape)
+            shape[axis] = e
+            ys.append(self.to_host(d, tuple(shape), np.float32))
+        for b in [xbuf] + [b for b, _d in outs]:
+            self.free(b)
+        return ys
+
+    def shuffle_channel(self, x, group, mode="f32", calib_scale=1.0, misalign=0):
+        """plhip_shuffle_channel_f32: x [n, c, ...]; returns (y_f32 or None, y_i8 or None)."""
+        x = np.ascontiguousarray(x, np.float32)
+        n, c = x.shape[:2]
+        hw = int(np.prod(x.shape[2:], dtype=np.int64))
+
+        def call(dx, dyf, dyq):
+            self.check(self.L.plhip_shuffle_channel_f32(self.h, dx, n, c, hw, int(group), dyf, dyq, float(calib_scale)), "shuffle_channel")
+        return self._two_outputs(call, x, x.shape, mode, calib_scale, misalign)
+
+    def shuffle_unit(self, a, b, split_at, mode="f32", calib_scale=1.0, misalign=0):
+        """plhip_shuffle_unit_f32: a, b [n, h, ...].  Returns (lo_f32 or None, hi_f32 or None, hi_i8 or None); mode names the
+        outputs of the high part ("f32", "i8", "both")."""
+        assert mode in ("f32", "i8", "both")
+        a = np.ascontiguousarray(a, np.float32)
+        b = np.ascontiguousarray(b, np.float32)
+        n, h = a.shape[:2]
+        hw = int(np.prod(a.shape[2:], dtype=np.int64))
+        rest = tuple(a.shape[2:])
+        hi_c = 2 * h - split_at
+        abuf, da = self._up_f32(a, misalign)
+        bbuf, db = self._up_f32(b, misalign)
+        lo = self._out_buf(n * split_at * hw, 4, misalign) if split_at > 0 else None
+        hf = self._out_buf(n * hi_c * hw, 4, misalign) if mode != "i8" else None
+        hq = self._out_buf(n * hi_c * hw, 1, misalign) if mode != "f32" else None
+        null = C.c_void_p()
+        self.check(self.L.plhip_shuffle_unit_f32(self.h, da, db, n, h, hw, int(split_at), lo[1] if lo else null, hf[1] if hf else null,
+                                                 hq[1] if hq else null, float(calib_scale)), "shuffle_unit")
+        r = (self.to_host(lo[1], (n, split_at) + rest, np.float32) if lo else None,
+             self.to_host(hf[1], (n, hi_c) + rest, np.float32) if hf else None,
+             self.to_host(hq[1], (n, hi_c) + rest, np.int8) if hq else None)
+        for p in (abuf, bbuf) + tuple(q[0] for q in (lo, hf, hq) if q):
+            self.free(p)
+        return r

@@ -415,18 +415,19 @@ struct ConvRoute {
   plhip_status (*pack)(plhip_ctx* ctx, Desc d, Geom g, const int8_t* w_oihw, void* w_packed);
   plhip_status (*run)(plhip_ctx* ctx, Desc d, Geom g, const ConvIo& io);
   const char* (*name)(Desc d, Geom g);
+  bool fused_tail;  // run() takes a residual operand / an int8 copy (plhip_conv2d_int8_fused); plhip_conv2d_fused_supported answers from it
 };
 // In priority order: the first row whose predicate holds runs the conv (the stem kernel wins over patch / implicit; the im2col
 // route takes what is left).  Every predicate is a pure function of the descriptor and the knobs.
 const ConvRoute kRoutes[] = {
-    {IMPL_GEMM_1X1, takes_gemm_1x1, gemm_packed_bytes, no_workspace, pack_gemm, run_gemm_1x1, name_gemm_1x1},
-    {IMPL_DIRECT_3X3S2, takes_direct_s2, direct_s2_packed_bytes, no_workspace, pack_direct_s2, run_direct_s2, name_direct_s2},
-    {IMPL_STEM_7X7S2, takes_stem7, stem7_packed_bytes, no_workspace, pack_stem7, run_stem7, name_stem7},
-    {IMPL_PATCH_GEMM, takes_patch, patch_packed_bytes, patch_input_bytes, pack_patch, run_patch, name_patch},
-    {IMPL_PATCH_S2, takes_patch_s2, patch_s2_packed_bytes, patch_s2_input_bytes, pack_patch_s2, run_patch_s2, name_patch_s2},
-    {IMPL_GROUPED_3X3, takes_grouped3x3, grouped3x3_packed_bytes, no_workspace, pack_grouped3x3, run_grouped3x3, name_grouped3x3},
-    {IMPL_IMPLICIT_GEMM, takes_implicit, gemm_packed_bytes, padded_input_bytes, pack_gemm, run_implicit, name_implicit},
-    {IMPL_IM2COL_GEMM, takes_im2col, gemm_packed_bytes, im2col_bytes, pack_gemm, run_im2col, name_im2col},
+    {IMPL_GEMM_1X1, takes_gemm_1x1, gemm_packed_bytes, no_workspace, pack_gemm, run_gemm_1x1, name_gemm_1x1, true},
+    {IMPL_DIRECT_3X3S2, takes_direct_s2, direct_s2_packed_bytes, no_workspace, pack_direct_s2, run_direct_s2, name_direct_s2, false},
+    {IMPL_STEM_7X7S2, takes_stem7, stem7_packed_bytes, no_workspace, pack_stem7, run_stem7, name_stem7, true},
+    {IMPL_PATCH_GEMM, takes_patch, patch_packed_bytes, patch_input_bytes, pack_patch, run_patch, name_patch, true},
+    {IMPL_PATCH_S2, takes_patch_s2, patch_s2_packed_bytes, patch_s2_input_bytes, pack_patch_s2, run_patch_s2, name_patch_s2, true},
+    {IMPL_GROUPED_3X3, takes_grouped3x3, grouped3x3_packed_bytes, no_workspace, pack_grouped3x3, run_grouped3x3, name_grouped3x3, true},
+    {IMPL_IMPLICIT_GEMM, takes_implicit, gemm_packed_bytes, padded_input_bytes, pack_gemm, run_implicit, name_implicit, true},
+    {IMPL_IM2COL_GEMM, takes_im2col, gemm_packed_bytes, im2col_bytes, pack_gemm, run_im2col, name_im2col, true},
 };
 
 // the route of a descriptor and its geometry; nullptr: a bad descriptor
@@ -462,6 +463,12 @@ size_t plhip_conv_workspace_bytes(const plhip_conv_desc* d) {
   ConvGeom g;
   const ConvRoute* r = pick_route(d, &g);
   return r ? r->workspace_bytes(d, g) : 0;
+}
+
+int plhip_conv2d_fused_supported(const plhip_conv_desc* d) {
+  ConvGeom g;
+  const ConvRoute* r = pick_route(d, &g);
+  return r && r->fused_tail ? 1 : 0;
 }
 
 const char* plhip_conv_impl_name(const plhip_conv_desc* d) {

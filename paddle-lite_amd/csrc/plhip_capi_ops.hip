@@ -1,6 +1,8 @@
-// plhip_capi_ops.hip — the C ABI (include/plhip.h), part 4 of 4: fc, calib, pooling, softmax, elementwise add, the hard activations
-// and squeeze-excite.  Argument validation and one launch each.
+// plhip_capi_ops.hip — the C ABI (include/plhip.h), part 4 of 4: fc, calib, pooling, softmax, elementwise add, the hard activations,
+// squeeze-excite, and concat / split / shuffle_channel.  Argument validation and one launch each.
 #include "plhip_capi.h"
+
+#include <vector>
 
 extern "C" {
 
@@ -147,6 +149,74 @@ plhip_status plhip_se_gate_int8(plhip_ctx* ctx, const plhip_se_gate_desc* d, con
   a.gate = gate; a.c = d->c; a.cr = d->cr;
   plhip::launch_se_gate(a, d->n, ctx->stream);
   LAUNCHCHK(ctx, "se_gate");
+  return PLHIP_OK;
+}
+
+// ------------------------------------------------------------------ concat / split / shuffle_channel
+// every extent, outer and inner >= 1 and the whole tensor outer * sum(extents) * inner at most 2^40 elements: no product of the
+// launch code (extent * inner, total * inner, row * stride) can leave int64
+static bool extents_ok(const int64_t* e, int count, int64_t outer, int64_t inner, int64_t* total) {
+  const int64_t cap = (int64_t)1 << 40;
+  if (!e || count < 1 || outer < 1 || inner < 1 || outer > cap || inner > cap) return false;
+  *total = 0;
+  for (int i = 0; i < count; ++i) {
+    if (e[i] < 1 || e[i] > cap) return false;
+    *total += e[i];
+    if (*total > cap) return false;
+  }
+  return *total <= cap / inner && *total * inner <= cap / outer;
+}
+
+plhip_status plhip_concat_f32(plhip_ctx* ctx, const float* const* xs, const int64_t* extents, int count, int64_t outer, int64_t inner,
+                              float* y) {
+  int64_t total = 0;
+  if (!ctx || !xs || !y || !extents_ok(extents, count, outer, inner, &total)) return fail(ctx, PLHIP_ERR_INVALID, "plhip_concat_f32: bad argument");
+  for (int i = 0; i < count; ++i)
+    if (!xs[i]) return fail(ctx, PLHIP_ERR_INVALID, "plhip_concat_f32: null input");
+  plhip::launch_concat_split(const_cast<float* const*>(xs), extents, count, outer, inner, y, 0, ctx->stream);
+  LAUNCHCHK(ctx, "concat");
+  return PLHIP_OK;
+}
+
+plhip_status plhip_split_f32(plhip_ctx* ctx, const float* x, int64_t outer, int64_t extent, int64_t inner, int num, const int64_t* sections,
+                             int count, float* const* ys) {
+  if (!ctx || !x || !ys || count < 1 || count > (1 << 20) || extent < 1 || num < 0) return fail(ctx, PLHIP_ERR_INVALID, "plhip_split_f32: bad argument");
+  if (num > 0 && (count != num || extent % num != 0)) return fail(ctx, PLHIP_ERR_INVALID, "plhip_split_f32: num must divide the axis and equal count");
+  if (num == 0 && !sections) return fail(ctx, PLHIP_ERR_INVALID, "plhip_split_f32: neither num nor sections");
+  std::vector<int64_t> e(count);
+  for (int i = 0; i < count; ++i) e[i] = num > 0 ? extent / num : sections[i];
+  int64_t total = 0;
+  if (!extents_ok(e.data(), count, outer, inner, &total) || total != extent)
+    return fail(ctx, PLHIP_ERR_INVALID, "plhip_split_f32: the sections do not add up to the axis");
+  for (int i = 0; i < count; ++i)
+    if (!ys[i]) return fail(ctx, PLHIP_ERR_INVALID, "plhip_split_f32: null output");
+  plhip::launch_concat_split(ys, e.data(), count, outer, inner, const_cast<float*>(x), 1, ctx->stream);
+  LAUNCHCHK(ctx, "split");
+  return PLHIP_OK;
+}
+
+plhip_status plhip_shuffle_channel_f32(plhip_ctx* ctx, const float* x, int n, int c, int hw, int group, float* y_f32, int8_t* y_i8,
+                                       float calib_scale) {
+  if (!ctx || !x || (!y_f32 && !y_i8) || n < 1 || c < 1 || hw < 1 || group < 1 || (y_i8 && !(calib_scale > 0.f)))
+    return fail(ctx, PLHIP_ERR_INVALID, "plhip_shuffle_channel_f32: bad argument");
+  if (c % group != 0) return fail(ctx, PLHIP_ERR_INVALID, "plhip_shuffle_channel_f32: group must divide c");
+  if ((int64_t)n * c > ((int64_t)1 << 30)) return fail(ctx, PLHIP_ERR_UNSUPPORTED, "plhip_shuffle_channel_f32: too many planes");
+  plhip::launch_shuffle_channel(x, y_f32, y_i8, calib_scale, n, c, hw, group, ctx->stream);
+  LAUNCHCHK(ctx, "shuffle_channel");
+  return PLHIP_OK;
+}
+
+plhip_status plhip_shuffle_unit_f32(plhip_ctx* ctx, const float* a, const float* b, int n, int h, int hw, int split_at, float* lo_f32,
+                                    float* hi_f32, int8_t* hi_i8, float calib_scale) {
+  if (!ctx || !a || !b || n < 1 || h < 1 || hw < 1) return fail(ctx, PLHIP_ERR_INVALID, "plhip_shuffle_unit_f32: bad argument");
+  if ((int64_t)n * h > ((int64_t)1 << 29)) return fail(ctx, PLHIP_ERR_UNSUPPORTED, "plhip_shuffle_unit_f32: too many planes");
+  if (split_at < 0 || split_at > 2 * h) return fail(ctx, PLHIP_ERR_INVALID, "plhip_shuffle_unit_f32: split_at outside 0 .. 2 h");
+  if ((split_at == 0) != (lo_f32 == nullptr)) return fail(ctx, PLHIP_ERR_INVALID, "plhip_shuffle_unit_f32: lo_f32 is null exactly when split_at is 0");
+  if (split_at == 2 * h) hi_f32 = nullptr, hi_i8 = nullptr;
+  else if (!hi_f32 && !hi_i8) return fail(ctx, PLHIP_ERR_INVALID, "plhip_shuffle_unit_f32: no output for the channels from split_at on");
+  if (hi_i8 && !(calib_scale > 0.f)) return fail(ctx, PLHIP_ERR_INVALID, "plhip_shuffle_unit_f32: int8 output needs a positive calib scale");
+  plhip::launch_shuffle_unit(a, b, lo_f32, hi_f32, hi_i8, calib_scale, n, h, hw, split_at, ctx->stream);
+  LAUNCHCHK(ctx, "shuffle_unit");
   return PLHIP_OK;
 }
 

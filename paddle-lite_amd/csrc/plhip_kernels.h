@@ -408,4 +408,24 @@ size_t se_gate_packed_bytes(int c, int cr);
 void launch_se_gate_pack(const int8_t* w1, const int8_t* w2, void* packed, int c, int cr, hipStream_t s);
 void launch_se_gate(const SeGateArgs& a, int n, hipStream_t s);
 
+// concat / split / shuffle_channel and the one-launch tail of a ShuffleNetV2 unit, fp32 moves (int8: the calib form): shuffle_ops.hip
+constexpr int CONCAT_MAX_PARTS = 8;  // operand pointers of one launch (they travel in the argument struct)
+struct ConcatArgs {
+  float* part[CONCAT_MAX_PARTS];    // [outer][len[p]]; read by concat, written by split
+  int64_t len[CONCAT_MAX_PARTS];    // c_p * inner floats
+  int64_t off[CONCAT_MAX_PARTS];    // where part p's row starts inside a row of `whole`
+  float* whole;                     // [outer][stride]
+  int64_t stride, outer;
+  int vec;
+};
+// parts[i]: [outer][extents[i]][inner]; whole: [outer][sum extents][inner]; split != 0 copies whole -> parts.  One launch per
+// CONCAT_MAX_PARTS parts.
+void launch_concat_split(float* const* parts, const int64_t* extents, int count, int64_t outer, int64_t inner, float* whole, int split,
+                         hipStream_t s);
+// out[b][j * group + i] = in[b][i * (c / group) + j]; yf / yq: either may be null
+void launch_shuffle_channel(const float* x, float* yf, int8_t* yq, float calib_scale, int n, int c, int hw, int group, hipStream_t s);
+// shuffled channel c' = 2 j + side of (side ? b : a) [n][h][hw]: c' < split_at -> lo [n][split_at][hw], else hf / hq [n][2 h - split_at][hw]
+void launch_shuffle_unit(const float* a, const float* b, float* lo, float* hf, int8_t* hq, float calib_scale, int n, int h, int hw,
+                         int split_at, hipStream_t s);
+
 }  // namespace plhip

@@ -80,6 +80,129 @@ void GraphBuilder::FeedSteps(std::vector<Step>* steps) const {
   }
 }
 
+namespace {
+
+std::vector<std::string> OutputsOf(const GraphOp& op) { return op.outputs.empty() ? std::vector<std::string>{op.output} : op.outputs; }
+
+std::string DimsStr(const std::vector<int64_t>& d) {
+  std::string s = "{";
+  for (size_t i = 0; i < d.size(); ++i) s += (i ? "," : "") + std::to_string(d[i]);
+  return s + "}";
+}
+
+// conv_op.h:149-161: 2-element paddings mean {top = bottom, left = right}
+std::vector<int> Pad4(const std::vector<int>& p) { return p.size() == 2 ? std::vector<int>{p[0], p[0], p[1], p[1]} : p; }
+
+// The conv's attributes have the sizes every rewrite below indexes: OIHW weights, four paddings, two strides, two dilations, explicit padding.
+bool ConvSizesOk(const GraphOp& op, const std::vector<int>& pad4) {
+  return op.w_dims.size() == 4 && pad4.size() == 4 && op.conv.strides.size() == 2 && op.conv.dilations.size() == 2 &&
+         op.conv.padding_algorithm.empty();
+}
+
+// Output shape of a conv on the NCHW shape `in` (conv_op.cc:25-52); empty where the attributes are not of those sizes
+std::vector<int64_t> ConvOutShape(const GraphOp& op, const std::vector<int64_t>& in) {
+  const std::vector<int> pd = Pad4(op.conv.paddings);
+  if (!ConvSizesOk(op, pd) || in.size() != 4) return {};
+  const int64_t keh = op.conv.dilations[0] * (op.w_dims[2] - 1) + 1, kew = op.conv.dilations[1] * (op.w_dims[3] - 1) + 1;
+  return {in[0], op.w_dims[0], (in[2] + pd[0] + pd[1] - keh) / op.conv.strides[0] + 1, (in[3] + pd[2] + pd[3] - kew) / op.conv.strides[1] + 1};
+}
+
+// concat_op.cc:22-62 on the operands' shapes; CHECKs that they differ along the axis only
+std::vector<int64_t> ConcatOutShape(const GraphOp& op, const std::vector<std::vector<int64_t>>& ins) {
+  std::vector<int64_t> o = ins[0];
+  const int rank = static_cast<int>(o.size());
+  const int axis = op.axis < 0 ? op.axis + rank : op.axis;
+  CHECK(axis >= 0 && axis < rank) << "concat " << op.output << ": axis " << op.axis << " outside the rank " << rank;
+  for (size_t i = 1; i < ins.size(); ++i) {
+    bool same = ins[i].size() == o.size();
+    for (int j = 0; same && j < rank; ++j) same = j == axis || ins[i][j] == ins[0][j];
+    CHECK(same) << "concat " << op.output << ": input " << op.inputs[i] << " " << DimsStr(ins[i]) << " differs from " << op.inputs[0] << " "
+                << DimsStr(ins[0]) << " outside axis " << axis;
+    o[axis] += ins[i][axis];
+  }
+  return o;
+}
+
+// split_op.cc:32-75 on the input's shape: the extent of every output along the axis; CHECKs num / sections against it
+std::vector<int64_t> SplitExtents(const GraphOp& op, const std::vector<int64_t>& in, int* axis_out) {
+  const int rank = static_cast<int>(in.size());
+  const int axis = op.axis < 0 ? op.axis + rank : op.axis;
+  CHECK(axis >= 0 && axis < rank) << "split " << op.inputs[0] << ": axis " << op.axis << " outside the rank " << rank;
+  const size_t n = OutputsOf(op).size();
+  std::vector<int64_t> e;
+  if (op.num > 0) {
+    CHECK(static_cast<size_t>(op.num) == n) << "split " << op.inputs[0] << ": num " << op.num << " but " << n << " outputs";
+    CHECK(in[axis] % op.num == 0) << "split " << op.inputs[0] << ": num " << op.num << " does not divide the axis (" << in[axis] << ")";
+    e.assign(n, in[axis] / op.num);
+  } else {
+    CHECK(op.sections.size() == n) << "split " << op.inputs[0] << ": " << op.sections.size() << " sections but " << n << " outputs";
+    int64_t sum = 0;
+    for (int v : op.sections) {
+      CHECK(v >= 1) << "split " << op.inputs[0] << ": a section of " << v;
+      sum += v;
+      e.push_back(v);
+    }
+    CHECK(sum == in[axis]) << "split " << op.inputs[0] << ": the sections do not add up to the axis (" << sum << " of " << in[axis] << ")";
+  }
+  *axis_out = axis;
+  return e;
+}
+
+void CheckShuffleGroup(const GraphOp& op, const std::vector<int64_t>& in) {
+  CHECK(in.size() >= 2) << "shuffle_channel " << op.output << ": input must have a channel axis";
+  CHECK(op.group >= 1 && in[1] % op.group == 0) << "shuffle_channel " << op.output << ": group " << op.group << " does not divide C = " << in[1];
+}
+
+}  // namespace
+
+std::map<std::string, std::vector<int64_t>> GraphBuilder::InferShapes() const {
+  std::map<std::string, std::vector<int64_t>> shape;
+  for (auto& f : feeds_) shape[f.name] = f.dims;
+  for (const GraphOp& op : ops_) {
+    std::vector<std::vector<int64_t>> ins;
+    for (auto& v : op.inputs) {
+      const auto it = shape.find(v);
+      if (it != shape.end()) ins.push_back(it->second);
+    }
+    if (ins.size() != op.inputs.size() || ins.empty()) continue;  // an operand of unknown shape: nothing to say
+    const std::vector<int64_t>& in = ins[0];
+    if (op.type == "concat") {
+      shape[op.output] = ConcatOutShape(op, ins);
+    } else if (op.type == "split") {
+      int axis = 0;
+      const std::vector<int64_t> e = SplitExtents(op, in, &axis);
+      const std::vector<std::string> outs = OutputsOf(op);
+      for (size_t i = 0; i < outs.size(); ++i) {
+        std::vector<int64_t> o = in;
+        o[axis] = e[i];
+        shape[outs[i]] = o;
+      }
+    } else if (op.type == "shuffle_channel") {
+      CheckShuffleGroup(op, in);
+      shape[op.output] = in;
+    } else if (op.type == "conv2d" || op.type == "depthwise_conv2d") {
+      const std::vector<int64_t> o = ConvOutShape(op, in);
+      if (!o.empty()) shape[op.output] = o;
+    } else if (op.type == "pool2d") {
+      const std::vector<int> pd = Pad4(op.pool_paddings);
+      if (in.size() != 4 || pd.size() != 4) continue;
+      if (op.global_pooling) {
+        shape[op.output] = {in[0], in[1], 1, 1};
+      } else if (op.ksize.size() == 2 && op.pool_strides.size() == 2) {
+        shape[op.output] = {in[0], in[1],
+                            operators::PoolOutputSize(static_cast<int>(in[2]), op.ksize[0], pd[0], pd[1], op.pool_strides[0], op.ceil_mode),
+                            operators::PoolOutputSize(static_cast<int>(in[3]), op.ksize[1], pd[2], pd[3], op.pool_strides[1], op.ceil_mode)};
+      }
+    } else if (op.type == "fc") {
+      if (op.w_dims.size() == 2) shape[op.output] = {in[0], op.w_dims[1]};
+    } else if (op.type == "elementwise_add" || op.type == "fusion_elementwise_add_activation" || op.type == "elementwise_mul" ||
+               op.type == "softmax" || op.type == "hard_swish" || op.type == "hard_sigmoid") {
+      shape[op.output] = in;
+    }
+  }
+  return shape;
+}
+
 void GraphBuilder::PickKernels(std::vector<bool>* int8_out, std::vector<float>* out_scale) const {
   // ---- who consumes what (fetch counts as a consumer that is not enable_int8)
   std::map<std::string, std::vector<int>> consumers;
@@ -90,9 +213,12 @@ void GraphBuilder::PickKernels(std::vector<bool>* int8_out, std::vector<float>* 
       CHECK(known.count(in)) << ops_[i].type << ": input " << in << " is not produced by an earlier op or feed";
       consumers[in].push_back(static_cast<int>(i));
     }
-    CHECK(!known.count(ops_[i].output)) << "variable " << ops_[i].output << " is written twice";
-    known.insert(ops_[i].output);
+    for (auto& out : OutputsOf(ops_[i])) {  // every output of a split is a variable of its own
+      CHECK(!known.count(out)) << "variable " << out << " is written twice";
+      known.insert(out);
+    }
   }
+
   std::set<std::string> fetched(fetches_.begin(), fetches_.end());
   for (auto& f : fetches_) CHECK(known.count(f)) << "fetch of unknown variable " << f;
 
@@ -156,11 +282,14 @@ std::vector<GraphBuilder::Step> GraphBuilder::Schedule() {
       s.op_inputs.push_back(use);
     }
     s.out = op.output;
+    s.outs = op.outputs;
     s.int8_out = int8_out[i];
     s.out_scale = out_scale[i];
     steps.push_back(s);
-    producer[op.output] = static_cast<int>(i);
-    prec[op.output] = (op.enable_int8 && int8_out[i]) ? PRECISION(kInt8) : PRECISION(kFloat);
+    for (auto& out : OutputsOf(op)) {
+      producer[out] = static_cast<int>(i);
+      prec[out] = (op.enable_int8 && int8_out[i]) ? PRECISION(kInt8) : PRECISION(kFloat);
+    }
   }
   for (auto& f : fetches_) {
     Step s;
@@ -173,15 +302,6 @@ std::vector<GraphBuilder::Step> GraphBuilder::Schedule() {
 }
 
 namespace {
-
-// conv_op.h:149-161: 2-element paddings mean {top = bottom, left = right}
-std::vector<int> Pad4(const std::vector<int>& p) { return p.size() == 2 ? std::vector<int>{p[0], p[0], p[1], p[1]} : p; }
-
-// The conv's attributes have the sizes every rewrite below indexes: OIHW weights, four paddings, two strides, two dilations, explicit padding.
-bool ConvSizesOk(const GraphOp& op, const std::vector<int>& pad4) {
-  return op.w_dims.size() == 4 && pad4.size() == 4 && op.conv.strides.size() == 2 && op.conv.dilations.size() == 2 &&
-         op.conv.padding_algorithm.empty();
-}
 
 // The plhip descriptor of `op` on an NCHW input of shape `in`; false (a rewrite then leaves the op alone) where the sizes are not those.
 bool ConvDesc(const GraphOp& op, const std::vector<int64_t>& in, plhip_conv_desc* d) {
@@ -210,7 +330,7 @@ bool IsPlain1x1Conv(const GraphOp& c) {
 }
 
 // Ops whose output has the shape of their first input (PropagateShapes)
-const char* const kSameShapeOps[] = {"elementwise_add", "fusion_elementwise_add_activation"};
+const char* const kSameShapeOps[] = {"elementwise_add", "fusion_elementwise_add_activation", "shuffle_channel"};
 
 void AppendNum(std::string* l, const char* key, float x) {
   char buf[64];
@@ -225,7 +345,9 @@ struct GraphBuilder::Fuser {
   std::vector<Step>& st;
   std::vector<bool> dead;
   std::map<std::string, std::vector<int64_t>> shape;  // PropagateShapes: NCHW shape of the variables it could follow from the feeds
-  Fuser(const GraphBuilder& gb, std::vector<Step>* steps) : g(gb), st(*steps), dead(steps->size(), false) {}
+  const std::map<std::string, std::vector<int64_t>>& var_shape;  // GraphBuilder::InferShapes, by graph variable: followed through every op type
+  Fuser(const GraphBuilder& gb, std::vector<Step>* steps, const std::map<std::string, std::vector<int64_t>>& shapes)
+      : g(gb), st(*steps), dead(steps->size(), false), var_shape(shapes) {}
 
   const GraphOp& Op(int t) const { return g.ops_[st[t].op]; }
   bool Live(size_t t, StepKind kind) const { return !dead[t] && st[t].kind == kind; }
@@ -283,12 +405,21 @@ struct GraphBuilder::Fuser {
   void DepthwiseConv1x1Tail();
   void SeGate();
   void HardActCalib();
+  void ShuffleTail();
 };
 
 // (A) (C) (B): the conv-tail patterns, matched by the SAME code a Paddle-Lite tree runs as a mir pass
 // (lite/core/mir/fusion/hip_conv_tail_matcher.h; patches/0006 carries it with its SSAGraph adapter)
 void GraphBuilder::Fuser::ConvTails() {
   using mir::fusion::TailInst;
+  // A conv whose route has no fused tail (plhip_conv2d_fused_supported: the direct 3x3 stride-2 stem) keeps its separate
+  // instructions.  ShuffleNetV2's stem -> max pool -> calib is the first program that asks.  Decided on the shape the program is
+  // lowered for, like D, F and G; a feed resized so that a conv with a tail lands on that route is refused by the C ABI, loudly.
+  auto takes_tail = [&](const GraphOp& op) {
+    const auto it = op.inputs.empty() ? var_shape.end() : var_shape.find(op.inputs[0]);
+    plhip_conv_desc d;
+    return it == var_shape.end() || !ConvDesc(op, it->second, &d) || plhip_conv2d_fused_supported(&d) != 0;
+  };
   std::vector<TailInst> prog(st.size());
   for (size_t i = 0; i < st.size(); ++i) {
     TailInst& t = prog[i];
@@ -296,7 +427,7 @@ void GraphBuilder::Fuser::ConvTails() {
     if (st[i].kind == StepKind::kOp) {
       const GraphOp& op = Op(i);
       t.inputs = st[i].op_inputs;
-      if (op.type == "conv2d" && op.enable_int8 && !st[i].int8_out) t.kind = TailInst::kConvF32;
+      if (op.type == "conv2d" && op.enable_int8 && !st[i].int8_out && takes_tail(op)) t.kind = TailInst::kConvF32;
       else if (op.type == "elementwise_add") t.kind = TailInst::kAdd;
       else if (op.type == "fusion_elementwise_add_activation" && op.act_type == "relu") t.kind = TailInst::kAddRelu;
       else if (op.type == "pool2d" && op.pooling_type == "max") t.kind = TailInst::kMaxPool;
@@ -395,7 +526,7 @@ void GraphBuilder::Fuser::ImageFeed() {
 }
 
 // The input shapes D (mode 2), F and G ask the kernels' predicates about: propagated from the feeds through io_copy / calib / image
-// steps, convs and kSameShapeOps (anything else: shape unknown, no fusion)
+// steps, convs, kSameShapeOps, concat and split (anything else: shape unknown, no fusion)
 void GraphBuilder::Fuser::PropagateShapes() {
   for (auto& f : g.feeds_) shape[f.name] = f.dims;
   for (size_t i = 0; i < st.size(); ++i) {
@@ -411,14 +542,25 @@ void GraphBuilder::Fuser::PropagateShapes() {
     if (it == shape.end() || it->second.size() != 4) continue;
     const std::vector<int64_t> in = it->second;
     std::vector<int64_t> o;
-    const std::vector<int> pd = Pad4(op.conv.paddings);
-    if ((op.type == "conv2d" || op.type == "depthwise_conv2d") && ConvSizesOk(op, pd)) {
-      const int64_t keh = op.conv.dilations[0] * (op.w_dims[2] - 1) + 1, kew = op.conv.dilations[1] * (op.w_dims[3] - 1) + 1;
-      o = {in[0], op.w_dims[0], (in[2] + pd[0] + pd[1] - keh) / op.conv.strides[0] + 1,
-           (in[3] + pd[2] + pd[3] - kew) / op.conv.strides[1] + 1};
-    }
+    if (op.type == "conv2d" || op.type == "depthwise_conv2d") o = ConvOutShape(op, in);
     for (const char* same : kSameShapeOps)
       if (op.type == same) o = in;
+    if (op.type == "concat") {  // every operand's shape must have come through
+      std::vector<std::vector<int64_t>> ins;
+      for (auto& v : st[i].op_inputs)
+        if (shape.count(v)) ins.push_back(shape[v]);
+      if (ins.size() == st[i].op_inputs.size()) o = ConcatOutShape(op, ins);
+    }
+    if (op.type == "split") {
+      int axis = 0;
+      const std::vector<int64_t> e = SplitExtents(op, in, &axis);
+      for (size_t q = 0; q < st[i].outs.size(); ++q) {
+        std::vector<int64_t> part = in;
+        part[axis] = e[q];
+        shape[st[i].outs[q]] = part;
+      }
+      continue;
+    }
     if (o.empty()) continue;
     shape[st[i].out] = o;
     if (!st[i].calib_out.empty()) shape[st[i].calib_out] = o;
@@ -551,6 +693,53 @@ void GraphBuilder::Fuser::HardActCalib() {
   }
 }
 
+// (K) concat(axis 1, two inputs of equal channels) whose only reader is a shuffle_channel(group 2): (K1) where that op's only reader
+// is a split(axis 1) in two equal parts whose second output a calib[fp32_to_int8] reads, the concat step becomes the unit
+// instruction: first half fp32, second half int8 and (only with another reader) fp32; (K2) where a calib[fp32_to_int8] reads the
+// shuffled tensor itself, the concat step becomes shuffle_channel/int8.  The one instruction runs where the concat ran: both
+// operands exist there, and everything it writes was written later before.
+void GraphBuilder::Fuser::ShuffleTail() {
+  const auto& shapes = var_shape;  // by graph variable: K needs the channels behind pools, which PropagateShapes does not follow
+  for (size_t i = 0; i < st.size(); ++i) {
+    if (dead[i] || !IsOp(static_cast<int>(i), "concat") || st[i].shuffle_tail) continue;
+    const GraphOp& cat = Op(i);
+    if (cat.inputs.size() != 2) continue;
+    const auto a = shapes.find(cat.inputs[0]), b = shapes.find(cat.inputs[1]);
+    if (a == shapes.end() || b == shapes.end() || a->second.size() != 4 || a->second != b->second) continue;
+    if (cat.axis != 1 && cat.axis != -3) continue;
+    const int j = SoleReader(st[i].out);
+    if (!IsOp(j, "shuffle_channel") || Op(j).group != 2) continue;
+    const int k = SoleReader(st[j].out);
+    if (IsOp(k, "split")) {  // (K1)
+      const GraphOp& sp = Op(k);
+      const int64_t h = a->second[1];
+      const bool halves = st[k].outs.size() == 2 && (sp.axis == 1 || sp.axis == -3) &&
+                          (sp.num == 2 || (sp.num == 0 && sp.sections == std::vector<int>({static_cast<int>(h), static_cast<int>(h)})));
+      if (!halves) continue;
+      const int c = FindByInput(StepKind::kCalibF2I, st[k].outs[1], k + 1);
+      if (c < 0) continue;
+      st[i].shuffle_tail = 2;
+      st[i].via = st[i].out + "," + st[j].out;
+      st[i].out = st[k].outs[0];
+      st[i].hi = st[k].outs[1];
+      st[i].calib_out = st[c].out;
+      st[i].calib_scale = st[c].scale;
+      dead[j] = dead[k] = dead[c] = true;
+      st[i].drop_f32 = Uses(st[i].hi) == 0;
+      continue;
+    }
+    const int c = FindByInput(StepKind::kCalibF2I, st[j].out, j + 1);  // (K2)
+    if (c < 0) continue;
+    st[i].shuffle_tail = 1;
+    st[i].via = st[i].out;
+    st[i].out = st[j].out;
+    st[i].calib_out = st[c].out;
+    st[i].calib_scale = st[c].scale;
+    dead[j] = dead[c] = true;
+    st[i].drop_f32 = Uses(st[i].out) == 0;
+  }
+}
+
 // The rewrites in the one order that gives today's programs.  Each takes over steps that a later one would otherwise match:
 //   * I before H: H would take the image_to_tensor behind an image_resize (and its calib) and leave the resize a launch of its own.
 //   * H before F: F would take the calib behind an image_to_tensor into the stem alone, and the fp32 tensor would still be written.
@@ -560,8 +749,10 @@ void GraphBuilder::Fuser::HardActCalib() {
 //   * D (with E) before G: G is for the pairs D left alone (pw_op still < 0); F between them touches calibs and stems only.
 //   * J2 and J1/J3 commute: J1/J3 take calibs that read a hard_swish / elementwise_mul, J2 the calib that reads a pool2d, and
 //     neither changes a use count the other tests.  J2 stays first, as the letters were added.
-void GraphBuilder::FuseSteps(std::vector<Step>* steps) {
-  Fuser f(*this, steps);
+//   * K last: it takes calibs that read a shuffle_channel or a split, which no other rewrite matches, and kills no step another
+//     rewrite looks at.
+void GraphBuilder::FuseSteps(std::vector<Step>* steps, const std::map<std::string, std::vector<int64_t>>& shapes) {
+  Fuser f(*this, steps, shapes);
   f.ConvTails();
   f.FrameResize();
   f.ImageFeed();
@@ -571,6 +762,7 @@ void GraphBuilder::FuseSteps(std::vector<Step>* steps) {
   if (fuse_dwconv_) f.DepthwiseConv1x1Tail();
   if (fuse_hard_act_) f.SeGate();
   if (fuse_hard_act_) f.HardActCalib();
+  if (fuse_shuffle_) f.ShuffleTail();
   std::vector<Step> kept;
   for (size_t i = 0; i < steps->size(); ++i)
     if (!f.dead[i]) kept.push_back((*steps)[i]);
@@ -579,12 +771,22 @@ void GraphBuilder::FuseSteps(std::vector<Step>* steps) {
 
 std::vector<GraphBuilder::Step> GraphBuilder::Program() {
   auto steps = Schedule();
-  if (fuse_) FuseSteps(&steps);
+  const auto shapes = InferShapes();  // once per program: concat / split / shuffle_channel operands that do not fit fail here
+  if (fuse_) FuseSteps(&steps, shapes);
   return steps;
 }
 
 std::string GraphBuilder::OpLine(const Step& s) const {
   const GraphOp& op = ops_[s.op];
+  if (s.shuffle_tail) {  // (K): the concat step that became the one instruction
+    std::string l = std::string("shuffle_channel/") + (s.shuffle_tail == 2 ? "unit" : "int8") + " in=" + s.op_inputs[0] + "," + s.op_inputs[1] +
+                    " out=" + s.out;
+    if (s.shuffle_tail == 2 && !s.drop_f32) l += " +hi=" + s.hi;
+    l += " +calib=" + s.calib_out;
+    AppendNum(&l, "scale", s.calib_scale);
+    if (s.shuffle_tail == 1 && s.drop_f32) l += " -f32";
+    return l + " via=" + s.via + (s.shuffle_tail == 2 && s.drop_f32 ? "," + s.hi : "");
+  }
   std::string l = op.type;
   if (op.enable_int8) {
     const bool fc = op.type == "fc";
@@ -596,6 +798,14 @@ std::string GraphBuilder::OpLine(const Step& s) const {
   l += " in=";
   for (size_t i = 0; i < s.op_inputs.size(); ++i) l += (i ? "," : "") + s.op_inputs[i];
   l += " out=" + s.out;
+  for (size_t i = 1; i < s.outs.size(); ++i) l += "," + s.outs[i];
+  if (op.type == "concat" || op.type == "split") l += " axis=" + std::to_string(op.axis);
+  if (op.type == "split" && op.num > 0) l += " num=" + std::to_string(op.num);
+  if (op.type == "split" && op.num <= 0) {
+    l += " sections=";
+    for (size_t i = 0; i < op.sections.size(); ++i) l += (i ? "," : "") + std::to_string(op.sections[i]);
+  }
+  if (op.type == "shuffle_channel") l += " group=" + std::to_string(op.group);
   if (op.enable_int8 && s.int8_out) AppendNum(&l, "oscale", s.out_scale);
   if (s.image_feed >= 0) {  // (H1): image_to_tensor + calib taken over, the conv reads the uint8 image
     const FeedDesc& f = feeds_[s.image_feed];
@@ -716,6 +926,15 @@ void GraphBuilder::LowerOp(const Step& s, HipPredictor* pred) {
     pred->AddSoftmax(s.op_inputs[0], s.out);
   } else if (op.type == "hard_swish" || op.type == "hard_sigmoid") {
     pred->AddActivation(op.type, s.op_inputs[0], s.out, s.calib_out, s.calib_scale, s.drop_f32);
+  } else if (s.shuffle_tail) {
+    pred->AddShuffleUnit(s.op_inputs[0], s.op_inputs[1], s.shuffle_tail == 2 ? s.out : "", s.shuffle_tail == 2 ? s.hi : s.out, s.calib_out,
+                         s.calib_scale, s.drop_f32);
+  } else if (op.type == "concat") {
+    pred->AddConcat(s.op_inputs, s.out, op.axis);
+  } else if (op.type == "split") {
+    pred->AddSplit(s.op_inputs[0], s.outs.empty() ? std::vector<std::string>{s.out} : s.outs, op.axis, op.num, op.sections);
+  } else if (op.type == "shuffle_channel") {
+    pred->AddShuffleChannel(s.op_inputs[0], s.out, op.group);
   } else if (op.type == "elementwise_mul") {
     pred->AddElementwiseMul(s.op_inputs[0], s.op_inputs[1], s.out, op.axis, s.calib_out, s.calib_scale, s.drop_f32);
   } else {

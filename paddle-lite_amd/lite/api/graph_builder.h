@@ -26,9 +26,11 @@ namespace lite {
 
 struct GraphOp {
   std::string type;  // conv2d | depthwise_conv2d | fc | pool2d | elementwise_add | fusion_elementwise_add_activation | softmax |
-                     // hard_swish | hard_sigmoid | elementwise_mul (fp32 ops like pool2d; the reference's default parameters)
+                     // hard_swish | hard_sigmoid | elementwise_mul (fp32 ops like pool2d; the reference's default parameters) |
+                     // concat (N inputs) | split | shuffle_channel (fp32 ops like pool2d)
   std::vector<std::string> inputs;
-  std::string output;
+  std::string output;                // the first output
+  std::vector<std::string> outputs;  // split: all outputs, outputs[0] == output; empty for every other type
   bool enable_int8{false};
   // conv2d / depthwise_conv2d / fc
   std::vector<int8_t> w;
@@ -43,8 +45,13 @@ struct GraphOp {
   bool global_pooling{false}, exclusive{true}, ceil_mode{false};
   // fusion_elementwise_add_activation
   std::string act_type;
-  // elementwise_mul: inputs {X [N, C, H, W], Y [N, C, 1, 1] | [N, C] | X's shape}
+  // elementwise_mul: inputs {X [N, C, H, W], Y [N, C, 1, 1] | [N, C] | X's shape}; concat / split: the axis (negative: from the back)
   int axis{-1};
+  // split: num > 0 = equal parts, else sections (one per output): lite/operators/split_op.cc:32-75
+  int num{0};
+  std::vector<int> sections;
+  // shuffle_channel
+  int group{1};
 };
 
 class GraphBuilder {
@@ -96,6 +103,17 @@ class GraphBuilder {
   // With set_fuse(true) only; bit-identical to the instructions they replace (the quantiser is calib's own).  DEFAULT OFF: none of
   // the three has been measured against the launches it replaces, as 8.5 keeps fusion G off.
   void set_fuse_hard_act(bool on) { fuse_hard_act_ = on; }
+  //   (K1) concat(axis 1, two inputs of equal channels h) -> shuffle_channel(group 2) -> split(axis 1, two equal parts), each the
+  //        only reader of the one before, where a calib[fp32_to_int8] reads the split's second output
+  //        => ONE shuffle_channel/unit instruction (plhip_shuffle_unit_f32): the first half fp32, the second half int8 and, only
+  //        where it has another reader, fp32
+  //   (K2) the same concat -> shuffle_channel(group 2), whose output a calib[fp32_to_int8] reads
+  //        => ONE shuffle_channel/int8 instruction; the fp32 tensor is not written when the calib was its only reader
+  // Anything else (three inputs, unequal channels, another group, unequal sections, an intermediate that is fetched or read
+  // elsewhere) keeps the separate instructions.  With set_fuse(true) only; bit-identical to the instructions they replace (values
+  // are moved, the quantiser is calib's own).  DEFAULT ON: measured faster than the separate instructions by far more than the
+  // run-to-run spread; no program without a concat changes.
+  void set_fuse_shuffle(bool on) { fuse_shuffle_ = on; }
   GraphOp& Add(const std::string& type, const std::vector<std::string>& inputs, const std::string& output);
   // Emits the program into `pred`; returns the host-side names of the fetched variables ("<name>/host").
   std::vector<std::string> Lower(HipPredictor* pred);
@@ -114,6 +132,11 @@ class GraphBuilder {
     bool int8_out{false};
     float out_scale{1.f};
     std::vector<std::string> op_inputs;  // op inputs after cast renaming
+    std::vector<std::string> outs;       // split: every output (outs[0] == out)
+    int shuffle_tail{0};      // (K) a concat step that took shuffle_channel(2) and its tail over: 1 = K2 (shuffle_channel/int8: `out` the
+                              // shuffled tensor), 2 = K1 (shuffle_channel/unit: `out` the split's first half, `hi` its second);
+                              // calib_out / calib_scale / drop_f32 belong to the tensor the calib read, `via` the names no longer written
+    std::string hi;
     // kHIP fusions (FuseSteps): tail taken over by an fp32_out conv, int8 max pool behind a fused calib
     std::string res;          // residual operand of the fused elementwise_add ("" = none)
     bool res_relu{false};
@@ -139,9 +162,12 @@ class GraphBuilder {
   };
   struct Fuser;  // graph_builder.cc: the state the rewrites of FuseSteps share, one member function per rewrite
   void FeedSteps(std::vector<Step>* steps) const;
-  void PickKernels(std::vector<bool>* int8_out, std::vector<float>* out_scale) const;  // pass 1, after checking the graph
+  void PickKernels(std::vector<bool>* int8_out, std::vector<float>* out_scale) const;  // pass 1, after checking the graph's names
+  // The shape of every variable that follows from the feeds (an op type it does not know passes none on); CHECKs what concat,
+  // split and shuffle_channel require of their operands' shapes.  Program() runs it once and hands the result to the rewrites.
+  std::map<std::string, std::vector<int64_t>> InferShapes() const;
   std::vector<Step> Schedule();
-  void FuseSteps(std::vector<Step>* steps);
+  void FuseSteps(std::vector<Step>* steps, const std::map<std::string, std::vector<int64_t>>& shapes);
   std::vector<Step> Program();  // Schedule(), then FuseSteps() unless set_fuse(false): what Plan() prints and Lower() emits
   std::string OpLine(const Step& s) const;
   ConvAttrs LoweredConvAttrs(const Step& s) const;
@@ -160,6 +186,7 @@ class GraphBuilder {
   int fuse_dwpw_{2};
   bool fuse_dwconv_{false};
   bool fuse_hard_act_{false};
+  bool fuse_shuffle_{true};
   std::vector<FeedDesc> feeds_;
   std::vector<std::string> fetches_;
   std::vector<GraphOp> ops_;

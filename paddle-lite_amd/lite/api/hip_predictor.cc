@@ -5,6 +5,7 @@
 #include "lite/kernels/hip/conv_fusion.h"
 #include "lite/kernels/hip/image_frame.h"
 #include "lite/kernels/hip/se_gate_fusion.h"
+#include "lite/kernels/hip/shuffle_fusion.h"
 #include "lite/kernels/hip/image_to_tensor.h"
 #include "plhip.h"
 
@@ -354,6 +355,63 @@ void HipPredictor::AddElementwiseMul(const std::string& x, const std::string& y,
   p.Out = Var(out);
   p.axis = axis;
   Emit(op, PickWithCalibTail("elementwise_mul", calib_out.empty() ? nullptr : Var(calib_out), calib_scale, drop_fp32));
+}
+
+void HipPredictor::AddConcat(const std::vector<std::string>& inputs, const std::string& out, int axis) {
+  auto op = std::make_shared<operators::ConcatOpLite>();
+  auto& p = op->mutable_param();
+  for (auto& in : inputs) p.x.push_back(Var(in));
+  p.output = Var(out);
+  p.axis = axis;
+  Emit(op, PickKernel("concat", Place(TARGET(kHIP), PRECISION(kFloat)), "def"));
+}
+
+void HipPredictor::AddSplit(const std::string& in, const std::vector<std::string>& outs, int axis, int num,
+                            const std::vector<int>& sections) {
+  auto op = std::make_shared<operators::SplitOp>();
+  auto& p = op->mutable_param();
+  p.x = Var(in);
+  for (auto& o : outs) p.output.push_back(Var(o));
+  p.axis = axis;
+  p.num = num;
+  p.sections = sections;
+  Emit(op, PickKernel("split", Place(TARGET(kHIP), PRECISION(kFloat)), "def"));
+}
+
+void HipPredictor::AddShuffleChannel(const std::string& in, const std::string& out, int group) {
+  auto op = std::make_shared<operators::ShuffleChannelOpLite>();
+  auto& p = op->mutable_param();
+  p.X = Var(in);
+  p.Out = Var(out);
+  p.group = group;
+  Emit(op, PickKernel("shuffle_channel", Place(TARGET(kHIP), PRECISION(kFloat)), "def"));
+}
+
+void HipPredictor::AddShuffleUnit(const std::string& a, const std::string& b, const std::string& lo, const std::string& hi,
+                                  const std::string& calib_out, float calib_scale, bool drop_fp32) {
+  const bool unit = !lo.empty();
+  CHECK(!hi.empty()) << "AddShuffleUnit: the variable behind the shuffle (or its second half) must be named";
+  CHECK(!drop_fp32 || !calib_out.empty()) << "AddShuffleUnit: only a tensor whose int8 image is written can be dropped";
+  auto op = std::make_shared<operators::ShuffleChannelOpLite>();
+  auto& p = op->mutable_param();
+  p.X = Var(a);
+  p.Out = Var(unit ? lo : hi);
+  p.group = 2;
+  if (!unit) op->set_output_channel_factor(2);
+  kernels::hip::HipShuffleFusion fz;
+  fz.second = Var(b);
+  if (unit) fz.hi_output = Var(hi);
+  if (!calib_out.empty()) {
+    fz.calib_output = Var(calib_out);
+    fz.calib_output->set_precision(PRECISION(kInt8));
+    fz.calib_scale = calib_scale;
+    fz.drop_fp32_output = drop_fp32;
+  }
+  auto kernel = PickKernel("shuffle_channel", Place(TARGET(kHIP), PRECISION(kFloat)), unit ? "unit" : "int8");
+  auto* sk = dynamic_cast<kernels::hip::HipShuffleFusionKernel*>(kernel.get());
+  CHECK(sk) << "the picked shuffle_channel kernel does not take the shuffle fusion";
+  sk->SetShuffleFusion(fz);
+  Emit(op, std::move(kernel));
 }
 
 std::vector<std::string> HipPredictor::KernelNames() {

@@ -97,6 +97,17 @@ class HipPredictor {
                  const ConvAttrs& a2);
   void AddElementwiseMul(const std::string& x, const std::string& y, const std::string& out, int axis, const std::string& calib_out = "",
                          float calib_scale = 1.f, bool drop_fp32 = false);
+  // concat / split / shuffle_channel, fp32 ops with the reference's attributes (lite/operators/op_params.h:369-386, 590-608,
+  // 258-263).  AddSplit: num > 0 = equal parts, else `sections`, one per output.
+  void AddConcat(const std::vector<std::string>& inputs, const std::string& out, int axis);
+  void AddSplit(const std::string& in, const std::vector<std::string>& outs, int axis, int num, const std::vector<int>& sections);
+  void AddShuffleChannel(const std::string& in, const std::string& out, int group);
+  // fusion K (lite/kernels/hip/shuffle_fusion.h): concat([a, b], axis 1) -> shuffle_channel(2) and what follows, ONE launch.
+  // lo == "": K2, shuffle_channel/int8: `hi` names the shuffled fp32 tensor, calib_out its int8 image.  lo != "": K1,
+  // shuffle_channel/unit: `lo` / `hi` name the two halves of the split behind the shuffle, calib_out the int8 image of `hi`.
+  // drop_fp32: `hi` has no reader left and is not written.
+  void AddShuffleUnit(const std::string& a, const std::string& b, const std::string& lo, const std::string& hi,
+                      const std::string& calib_out, float calib_scale, bool drop_fp32);
 
   void Run(bool skip_io_copy = false) {
     TargetWrapperHip::SetDevice(device_);

@@ -4,6 +4,7 @@
 
 #include <cstring>
 #include <string>
+#include <vector>
 
 #include "lite/api/graph_builder.h"
 #include "lite/api/hip_predictor.h"
@@ -246,6 +247,54 @@ int pllite_elementwise_mul_prepare(const int64_t* x_dims, int nx, const int64_t*
     k->SetParam<paddle::lite::operators::ElementwiseParam>(param);
     k->PrepareForRun();
   });
+}
+static std::vector<std::string> names_of(const char* const* v, int n) {
+  std::vector<std::string> r;
+  for (int i = 0; i < n; ++i) {
+    CHECK(v && v[i]) << "null variable name";
+    r.push_back(v[i]);
+  }
+  return r;
+}
+int pllite_graph_concat(pllite_predictor* p, const char* const* inputs, int n_inputs, const char* out, int axis) {
+  return guarded([&] {
+    CHECK(n_inputs >= 1 && out) << "pllite_graph_concat: at least one input and an output";
+    p->graph.Add("concat", names_of(inputs, n_inputs), out).axis = axis;
+  });
+}
+int pllite_graph_split(pllite_predictor* p, const char* in, const char* const* outs, int n_outs, int axis, int num, const int* sections,
+                       int n_sections) {
+  return guarded([&] {
+    CHECK(in && n_outs >= 1 && n_sections >= 0) << "pllite_graph_split: an input and at least one output";
+    const auto o = names_of(outs, n_outs);
+    auto& op = p->graph.Add("split", {in}, o[0]);
+    op.outputs = o;
+    op.axis = axis;
+    op.num = num;
+    if (n_sections > 0) op.sections.assign(sections, sections + n_sections);
+  });
+}
+int pllite_graph_shuffle_channel(pllite_predictor* p, const char* in, const char* out, int group) {
+  return guarded([&] { p->graph.Add("shuffle_channel", {in}, out).group = group; });
+}
+int pllite_graph_set_fuse_shuffle(pllite_predictor* p, int on) {
+  return guarded([&] { p->graph.set_fuse_shuffle(on != 0); });
+}
+int pllite_add_concat(pllite_predictor* p, const char* const* inputs, int n_inputs, const char* out, int axis) {
+  return guarded([&] { p->pred.AddConcat(names_of(inputs, n_inputs), out, axis); });
+}
+int pllite_add_split(pllite_predictor* p, const char* in, const char* const* outs, int n_outs, int axis, int num, const int* sections,
+                     int n_sections) {
+  return guarded([&] {
+    p->pred.AddSplit(in, names_of(outs, n_outs), axis, num, n_sections > 0 ? std::vector<int>(sections, sections + n_sections) : std::vector<int>());
+  });
+}
+int pllite_add_shuffle_channel(pllite_predictor* p, const char* in, const char* out, int group) {
+  return guarded([&] { p->pred.AddShuffleChannel(in, out, group); });
+}
+int pllite_add_shuffle_unit(pllite_predictor* p, const char* a, const char* b, const char* lo, const char* hi, const char* calib_out,
+                            float calib_scale, int drop_fp32) {
+  return guarded([&] { p->pred.AddShuffleUnit(a, b, lo ? lo : "", hi ? hi : "", calib_out ? calib_out : "", calib_scale, drop_fp32 != 0); });
 }
 int pllite_graph_softmax(pllite_predictor* p, const char* in, const char* out) {
   return guarded([&] { p->graph.Add("softmax", {in}, out); });

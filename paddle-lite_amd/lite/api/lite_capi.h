@@ -44,6 +44,15 @@ int pllite_add_activation(pllite_predictor* p, const char* op_type, const char* 
                           float calib_scale, int drop_fp32);
 int pllite_add_elementwise_mul(pllite_predictor* p, const char* x, const char* y, const char* out, int axis, const char* calib_out,
                                float calib_scale, int drop_fp32);
+/* concat / split / shuffle_channel (fp32 ops, the reference's attributes) and the one-launch tail of a ShuffleNetV2 unit
+ * (lite/kernels/hip/shuffle_fusion.h): lo NULL / "" = shuffle_channel/int8 (`hi` the shuffled tensor), else shuffle_channel/unit
+ * (`lo` / `hi` the halves of the split); calib_out NULL / "" = no int8 image; drop_fp32: `hi` is not written. */
+int pllite_add_concat(pllite_predictor* p, const char* const* inputs, int n_inputs, const char* out, int axis);
+int pllite_add_split(pllite_predictor* p, const char* in, const char* const* outs, int n_outs, int axis, int num, const int* sections,
+                     int n_sections);
+int pllite_add_shuffle_channel(pllite_predictor* p, const char* in, const char* out, int group);
+int pllite_add_shuffle_unit(pllite_predictor* p, const char* a, const char* b, const char* lo, const char* hi, const char* calib_out,
+                            float calib_scale, int drop_fp32);
 
 /* ---- graph mode (lite/api/graph_builder.h): ops as the optimiser sees them after its fusion passes; kernel choice
  * (int8_out / fp32_out), io_copy and calib placement are decided by pllite_graph_lower() with the reference's rules.
@@ -77,6 +86,16 @@ int pllite_graph_elementwise_mul(pllite_predictor* p, const char* x, const char*
 /* fusions J1 / J2 / J3 (hard_swish / elementwise_mul take the calib behind them over, hard_sigmoid the excite chain in front): off by
  * default, effective with pllite_graph_set_fuse(1) only */
 int pllite_graph_set_fuse_hard_act(pllite_predictor* p, int on);
+/* fp32 ops along an axis: concat of n_inputs >= 1 variables; split into n_outs variables, num > 0 equal parts or `sections` (one
+ * per output); shuffle_channel(group).  Malformed graphs (other dims that differ, num / sections / group that do not fit, a
+ * variable written twice) fail in pllite_graph_plan / pllite_graph_lower with a message. */
+int pllite_graph_concat(pllite_predictor* p, const char* const* inputs, int n_inputs, const char* out, int axis);
+int pllite_graph_split(pllite_predictor* p, const char* in, const char* const* outs, int n_outs, int axis, int num, const int* sections,
+                       int n_sections);
+int pllite_graph_shuffle_channel(pllite_predictor* p, const char* in, const char* out, int group);
+/* fusion K (concat -> shuffle_channel(2) -> [split ->] calib in one launch): on by default, effective with
+ * pllite_graph_set_fuse(1) only; 0 keeps the separate instructions */
+int pllite_graph_set_fuse_shuffle(pllite_predictor* p, int on);
 int pllite_graph_fetch(pllite_predictor* p, const char* name);
 /* kHIP graph-level fusions (graph_builder.h set_fuse): on by default; 0 = the reference program instruction for instruction. */
 int pllite_graph_set_fuse(pllite_predictor* p, int on);

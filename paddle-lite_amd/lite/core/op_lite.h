@@ -1,7 +1,7 @@
 // op_lite.h — OpLite (lite/core/op_lite.h:54-) reduced to what Instruction::Run needs (program.cc:436-467):
 // CheckShape() once, InferShape() before every launch, AttachKernel() to hand the op's parameter struct to the
 // picked kernel.  The ops below restate the shape inference of lite/operators/{conv_op.cc:25-111, fc_op.cc,
-// calib_op.cc, io_copy_op.cc, pool_op.cc, softmax_op.cc}; attributes are set on the param struct directly, as the
+// calib_op.cc, io_copy_op.cc, pool_op.cc, softmax_op.cc, concat_op.cc, split_op.cc, shuffle_channel_op.cc}; attributes are set on the param struct directly, as the
 // reference's math tests do (conv_int8_compute_test.cc:90-117), because there is no model parser in this build.
 #pragma once
 #include <algorithm>
@@ -317,6 +317,105 @@ class FusionElementwiseActivationOp : public OpLite {
 
  private:
   mutable FusionElementwiseActivationParam param_;
+};
+
+// concat_op.cc:22-62: every input has the first one's dims outside `axis` (negative: from the back); Out sums the axis
+class ConcatOpLite : public OpLite {
+ public:
+  ConcatOpLite() : OpLite("concat") {}
+  ConcatParam& mutable_param() { return param_; }
+  bool CheckShape() const override {
+    CHECK_GE(param_.x.size(), 1UL) << "concat: at least one input";
+    CHECK(param_.output) << "concat: output must be set";
+    return true;
+  }
+  bool InferShapeImpl() const override {
+    CHECK(param_.axis_tensor == nullptr) << "concat: kHIP takes the axis attribute only";
+    auto out = param_.x[0]->dims().Vectorize();
+    const int rank = static_cast<int>(out.size());
+    const int axis = param_.axis < 0 ? param_.axis + rank : param_.axis;
+    CHECK(axis >= 0 && axis < rank) << "concat: axis " << param_.axis << " outside the rank " << rank;
+    for (size_t i = 1; i < param_.x.size(); ++i) {
+      const auto d = param_.x[i]->dims();
+      CHECK_EQ(static_cast<int>(d.size()), rank) << "concat: input " << i << " has another rank";
+      for (int j = 0; j < rank; ++j) {
+        if (j == axis) out[j] += d[j];
+        else CHECK_EQ(out[j], d[j]) << "concat: input " << i << " differs from input 0 in dim " << j;
+      }
+    }
+    param_.output->Resize(out);
+    return true;
+  }
+  void AttachKernel(KernelBase* k) override { k->SetParam<ConcatParam>(param_); }
+
+ private:
+  mutable ConcatParam param_;
+};
+
+// split_op.cc:32-75: num > 0: `num` equal parts of the axis; else sections[i] along it
+class SplitOp : public OpLite {
+ public:
+  SplitOp() : OpLite("split") {}
+  SplitParam& mutable_param() { return param_; }
+  bool CheckShape() const override {
+    CHECK(param_.x) << "split: x must be set";
+    CHECK_GT(param_.output.size(), 0UL) << "split: at least one output";
+    const int rank = static_cast<int>(param_.x->dims().size());
+    CHECK(param_.axis >= -rank && param_.axis < rank) << "split: axis " << param_.axis << " outside the rank " << rank;
+    return true;
+  }
+  bool InferShapeImpl() const override {
+    CHECK(param_.axis_tensor == nullptr && param_.sections_tensor_list.empty()) << "split: kHIP takes the attributes only";
+    const auto in = param_.x->dims().Vectorize();
+    const int axis = param_.axis < 0 ? param_.axis + static_cast<int>(in.size()) : param_.axis;
+    const size_t n = param_.output.size();
+    if (param_.num > 0) {
+      CHECK(static_cast<size_t>(param_.num) == n && in[axis] % param_.num == 0)
+          << "split: num " << param_.num << " must equal the number of outputs and divide the axis (" << in[axis] << ")";
+    } else {
+      CHECK_EQ(param_.sections.size(), n) << "split: one section per output";
+      int64_t sum = 0;
+      for (int v : param_.sections) sum += v;
+      CHECK_EQ(sum, in[axis]) << "split: the sections do not add up to the axis";
+    }
+    for (size_t i = 0; i < n; ++i) {
+      auto d = in;
+      d[axis] = param_.num > 0 ? in[axis] / param_.num : param_.sections[i];
+      param_.output[i]->Resize(d);
+    }
+    return true;
+  }
+  void AttachKernel(KernelBase* k) override { k->SetParam<SplitParam>(param_); }
+
+ private:
+  mutable SplitParam param_;
+};
+
+// shuffle_channel_op.cc:23-31: Out takes X's dims.  kHIP fusion K2 (lite/kernels/hip/shuffle_fusion.h): X is the first of the two
+// operands of the concat taken over, Out the shuffled tensor of twice its channels.
+class ShuffleChannelOpLite : public OpLite {
+ public:
+  ShuffleChannelOpLite() : OpLite("shuffle_channel") {}
+  ShuffleChannelParam& mutable_param() { return param_; }
+  void set_output_channel_factor(int f) { channel_factor_ = f; }  // kHIP fusion K2 only
+  bool CheckShape() const override {
+    CHECK(param_.X && param_.Out) << "shuffle_channel: X / Out must be set";
+    return true;
+  }
+  bool InferShapeImpl() const override {
+    auto d = param_.X->dims().Vectorize();
+    if (channel_factor_ != 1) {
+      CHECK_GE(d.size(), 2UL);
+      d[1] *= channel_factor_;
+    }
+    param_.Out->Resize(d);
+    return true;
+  }
+  void AttachKernel(KernelBase* k) override { k->SetParam<ShuffleChannelParam>(param_); }
+
+ private:
+  mutable ShuffleChannelParam param_;
+  int channel_factor_{1};
 };
 
 class SoftmaxOp : public OpLite {

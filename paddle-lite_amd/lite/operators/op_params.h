@@ -2,7 +2,7 @@
 // defaults) with the subset of lite/operators/op_params.h the ARM int8 kernels read:
 //   WITH_INT8_CONFIG :49-54, IoCopyParam :70, CalibParam :82, FcParam :115-143, SoftmaxParam :319,
 //   ActivationParam :395-419, ConvParam :446-502, PoolParam :539-, ElementwiseParam :643-651,
-//   FusionElementwiseActivationParam :678-680.
+//   FusionElementwiseActivationParam :678-680, ShuffleChannelParam :258-263, ConcatParam :369-386, SplitParam :590-608.
 // Tensors are NOT owned: params hold raw lite::Tensor* into the caller's scope (conv_op.h:72-74); bias may be null;
 // paddings / dilations are shared_ptrs the op may mutate (UpdatePaddingAndDilation, conv_op.cc:55-81).
 #pragma once
@@ -122,6 +122,29 @@ struct ElementwiseParam : ParamBase {
 
 struct FusionElementwiseActivationParam : public ElementwiseParam {
   std::string act_type;
+};
+
+struct ShuffleChannelParam : ParamBase {
+  const lite::Tensor* X{};
+  lite::Tensor* Out{};
+  int group;
+};
+
+struct ConcatParam : ParamBase {
+  std::vector<lite::Tensor*> x{};
+  lite::Tensor* output{};
+  int axis{0};
+  lite::Tensor* axis_tensor{};
+};
+
+struct SplitParam : ParamBase {
+  lite::Tensor* x{};
+  std::vector<lite::Tensor*> output{};
+  lite::Tensor* axis_tensor{};
+  std::vector<lite::Tensor*> sections_tensor_list{};
+  int axis{-1};
+  int num{0};
+  std::vector<int> sections;
 };
 
 }  // namespace operators

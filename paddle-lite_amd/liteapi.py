@@ -65,6 +65,14 @@ def load():
     L.pllite_elementwise_mul_prepare.argtypes = [C.POINTER(i64), i32, C.POINTER(i64), i32, i32]
     L.pllite_add_activation.argtypes = [vp, cs, cs, cs, cs, f32, i32]
     L.pllite_add_elementwise_mul.argtypes = [vp, cs, cs, cs, i32, cs, f32, i32]
+    L.pllite_graph_concat.argtypes = [vp, C.POINTER(cs), i32, cs, i32]
+    L.pllite_graph_split.argtypes = [vp, cs, C.POINTER(cs), i32, i32, i32, C.POINTER(i32), i32]
+    L.pllite_graph_shuffle_channel.argtypes = [vp, cs, cs, i32]
+    L.pllite_graph_set_fuse_shuffle.argtypes = [vp, i32]
+    L.pllite_add_concat.argtypes = [vp, C.POINTER(cs), i32, cs, i32]
+    L.pllite_add_split.argtypes = [vp, cs, C.POINTER(cs), i32, i32, i32, C.POINTER(i32), i32]
+    L.pllite_add_shuffle_channel.argtypes = [vp, cs, cs, i32]
+    L.pllite_add_shuffle_unit.argtypes = [vp, cs, cs, cs, cs, cs, f32, i32]
     L.pllite_graph_fetch.argtypes = [vp, cs]
     L.pllite_graph_set_fuse.argtypes = [vp, i32]
     L.pllite_graph_set_fuse_dwpw.argtypes = [vp, i32]
@@ -93,6 +101,10 @@ def load():
 
 def _ia(vals, t=C.c_int):
     return (t * len(vals))(*[int(v) for v in vals])
+
+
+def _names(vals):
+    return (C.c_char_p * len(vals))(*[v.encode() for v in vals])
 
 
 def elementwise_mul_prepare(x_dims, y_dims, axis=0):
@@ -184,6 +196,22 @@ class Predictor:
         self._ck(self.L.pllite_add_elementwise_mul(self.h, x.encode(), y.encode(), dst.encode(), int(axis), calib_out.encode(),
                                                    calib_scale, int(drop_fp32)))
 
+    def add_concat(self, srcs, dst, axis=1):
+        self._ck(self.L.pllite_add_concat(self.h, _names(srcs), len(srcs), dst.encode(), int(axis)))
+
+    def add_split(self, src, dsts, axis=1, num=0, sections=()):
+        """num > 0: equal parts; else one section per output."""
+        self._ck(self.L.pllite_add_split(self.h, src.encode(), _names(dsts), len(dsts), int(axis), int(num), _ia(sections), len(sections)))
+
+    def add_shuffle_channel(self, src, dst, group):
+        self._ck(self.L.pllite_add_shuffle_channel(self.h, src.encode(), dst.encode(), int(group)))
+
+    def add_shuffle_unit(self, a, b, lo, hi, calib_out="", calib_scale=1.0, drop_fp32=False):
+        """concat([a, b], 1) -> shuffle_channel(2) and what follows in one launch.  lo == "": shuffle_channel/int8, `hi` the shuffled
+        tensor; else shuffle_channel/unit, lo / hi the two halves.  calib_out: the int8 image of `hi`; drop_fp32: `hi` is not written."""
+        self._ck(self.L.pllite_add_shuffle_unit(self.h, a.encode(), b.encode(), lo.encode(), hi.encode(), calib_out.encode(),
+                                                calib_scale, int(drop_fp32)))
+
     # ---- graph mode: ops as the optimiser sees them; graph_lower() applies the reference's kernel-pick / cast rules
     def graph_feed(self, name, dims, precision=PREC_FLOAT):
         self._ck(self.L.pllite_graph_feed(self.h, name.encode(), _ia(dims, C.c_int64), len(dims), precision))
@@ -249,6 +277,21 @@ class Predictor:
     def graph_elementwise_mul(self, x, y, dst, axis=0):
         """x [N, C, H, W] times y [N, C, 1, 1] / [N, C] (axis 0), or y of x's shape."""
         self._ck(self.L.pllite_graph_elementwise_mul(self.h, x.encode(), y.encode(), dst.encode(), int(axis)))
+
+    def graph_concat(self, srcs, dst, axis=1):
+        self._ck(self.L.pllite_graph_concat(self.h, _names(srcs), len(srcs), dst.encode(), int(axis)))
+
+    def graph_split(self, src, dsts, axis=1, num=0, sections=()):
+        """num > 0: `num` equal parts of the axis; else one section per output."""
+        self._ck(self.L.pllite_graph_split(self.h, src.encode(), _names(dsts), len(dsts), int(axis), int(num), _ia(sections), len(sections)))
+
+    def graph_shuffle_channel(self, src, dst, group):
+        self._ck(self.L.pllite_graph_shuffle_channel(self.h, src.encode(), dst.encode(), int(group)))
+
+    def graph_set_fuse_shuffle(self, on):
+        """Fusion K (default on; with graph_set_fuse(True) only): concat -> shuffle_channel(2) -> split -> calib becomes one
+        shuffle_channel/unit instruction (K1), concat -> shuffle_channel(2) -> calib one shuffle_channel/int8 instruction (K2)."""
+        self._ck(self.L.pllite_graph_set_fuse_shuffle(self.h, int(on)))
 
     def graph_set_fuse_hard_act(self, on):
         """Fusions J1 / J2 / J3 (default off; with graph_set_fuse(True) only): hard_swish / elementwise_mul take the calib[fp32_to_int8]

@@ -107,6 +107,7 @@ def build_mobilenet_v1(pred, W, batch, res=224):
 #   fc: src, w [k, n], bias, in_scale, w_scale [n]
 #   pool2d: src, pooling_type, ksize, stride, pad, global_pooling
 #   add: x, y, act ("" | "relu")      softmax: src
+#   concat: srcs [..], axis      split: src, names [..] (name = names[0]), axis, num, sections      shuffle_channel: src, group
 # On the reference's ARM target pool2d and elementwise_add exist in fp32 only, so the kernel-pick
 # rule gives the convs in front of them the fp32_out kernel and the consumers behind them a calib.
 # =====================================================================================================================
@@ -123,7 +124,7 @@ class _NetGen:
         self.act_scale[name] = np.float32(act_scale)
         self.sig_i8[name] = sig_i8
 
-    def conv(self, name, src, cout, k, stride, pad, groups=1, act=1, act_coef=0.0, out_range=4.0, op=None, headroom=1.0):
+    def conv(self, name, src, cout, k, stride, pad, groups=1, act=1, act_coef=0.0, out_range=4.0, op=None, headroom=1.0, bias_shift=0.0):
         cin, h, w = self.shape[src]
         kk = (cin // groups) * k * k
         wt = self.rng.integers(-127, 128, (cout, cin // groups, k, k)).astype(np.int8)
@@ -133,7 +134,9 @@ class _NetGen:
         var = (1.0 + (np.arange(cout) % 7) / 8.0) / 1.375
         # headroom > 1: the weight scales are sized for an int8 std of 45 / headroom (fewer saturated values)
         w_scale = (var * 45.0 / headroom * float(out_scale) / (acc_std * float(in_scale))).astype(np.float32)
-        bias = (self.rng.uniform(-0.5, 0.5, cout) * 45.0 * float(out_scale)).astype(np.float32)
+        # bias_shift: the centre of the biases in units of the sizing rule's int8 spread (0: centred, as conv_bn fusion leaves a
+        # batch norm without a learnt offset; > 0: a positive offset, so that fewer values of a relu tensor are zero)
+        bias = ((self.rng.uniform(-0.5, 0.5, cout) + bias_shift) * 45.0 * float(out_scale)).astype(np.float32)
         if op is None:
             op = "depthwise_conv2d" if (groups == cin and groups == cout and groups > 1) else "conv2d"
         self.ops.append(dict(op=op, name=name, src=src, w=wt, bias=bias, stride=stride, pad=pad, groups=groups, act=act,
@@ -189,6 +192,37 @@ class _NetGen:
         assert self.shape[y] == (c, 1, 1), (self.shape[y], c)
         self.ops.append(dict(op="mul", name=name, x=x, y=y))
         self.tensor(name, c, h, w, self.act_scale[x], self.sig_i8[x] * 0.6)
+        return name
+
+    def concat(self, name, srcs, axis=1):
+        """fp32 op along the channel axis.  Its int8 consumers quantise the whole tensor with ONE scale, which must hold every
+        operand: the largest of the operands' scales (a smaller one would saturate the operand that was sized over the wider
+        range); an operand of a smaller scale then fills that much less of the int8 range."""
+        assert axis == 1 and len({self.shape[v][1:] for v in srcs}) == 1, [self.shape[v] for v in srcs]
+        self.ops.append(dict(op="concat", name=name, srcs=list(srcs), axis=axis))
+        scale = max(float(self.act_scale[v]) for v in srcs)
+        cs = [self.shape[v][0] for v in srcs]
+        ms = sum(c * (self.sig_i8[v] * float(self.act_scale[v]) / scale) ** 2 for c, v in zip(cs, srcs)) / sum(cs)
+        _, h, w = self.shape[srcs[0]]
+        self.tensor(name, sum(cs), h, w, np.float32(scale), float(np.sqrt(ms)))
+        return name
+
+    def split(self, names, src, axis=1, num=0, sections=()):
+        """fp32 op: `num` equal parts of the channel axis, or `sections`; every part keeps the source's scale."""
+        c, h, w = self.shape[src]
+        assert axis == 1
+        parts = [c // num] * num if num > 0 else list(sections)
+        assert sum(parts) == c and len(parts) == len(names), (parts, c, names)
+        self.ops.append(dict(op="split", name=names[0], names=list(names), src=src, axis=axis, num=num, sections=tuple(sections)))
+        for n_, c_ in zip(names, parts):
+            self.tensor(n_, c_, h, w, self.act_scale[src], self.sig_i8[src])
+        return list(names)
+
+    def shuffle(self, name, src, group):
+        c, h, w = self.shape[src]
+        assert c % group == 0, (c, group)
+        self.ops.append(dict(op="shuffle_channel", name=name, src=src, group=group))
+        self.tensor(name, c, h, w, self.act_scale[src], self.sig_i8[src])
         return name
 
     def fc(self, name, src, n):
@@ -341,6 +375,74 @@ def mobilenet_v3_net(variant="large", seed=53, res=224, num_classes=NUM_CLASSES)
     return _finish(g, res, x)
 
 
+# ShuffleNetV2 (Ma et al. 2018, table 5; the reference runs it as lite/api/shufflenetv2_test.cc): stage widths by scale
+SHUFFLENET_V2_WIDTHS = {0.5: (48, 96, 192), 1.0: (116, 232, 464), 1.5: (176, 352, 704), 2.0: (244, 488, 976)}
+SHUFFLENET_V2_REPEATS = (4, 8, 4)
+
+
+def shufflenet_v2_net(scale=1.0, seed=55, res=224, num_classes=NUM_CLASSES):
+    """ShuffleNetV2 as the reference's optimiser leaves it: relu fused into the int8 convs, shuffle_channel already fused from
+    reshape / transpose / reshape (shuffle_channel_fuse_pass.cc), concat / shuffle_channel / split fp32 ops.  A stride-1 unit
+    splits its input in two, runs conv1x1+relu -> dw3x3 -> conv1x1+relu on the second half, concatenates and shuffles (group 2); a
+    stride-2 unit runs dw3x3 s2 -> conv1x1+relu on the left, conv1x1+relu -> dw3x3 s2 -> conv1x1+relu on the right.  Every conv
+    output is sized over [-4, 4], so the two operands of every concat share one scale."""
+    widths = SHUFFLENET_V2_WIDTHS[scale]
+    g = _NetGen(seed)
+    g.tensor("image", 3, res, res, 1.0 / 127, 73.0)
+    x = g.conv("conv1", "image", 24, 3, 2, 1, act=1)
+    x = g.pool("pool1", x, "max", 3, 2, 1)
+    cin = 24
+    # Sizing (checked on the oracle, tests/test_shufflenet_host.py, against MobileNetV2's worst tensor).  A depthwise conv
+    # without an activation saturates on both sides, and its taps see relu outputs of neighbouring pixels, whose sum spreads
+    # about 1.6 times wider than the rule for independent taps says: its weight scales are sized for a third of the usual int8
+    # spread and the spread its reader is sized by is corrected.  The 1x1 convs in front of a concat keep a quarter of headroom,
+    # so that the concat's one scale holds both operands.  The first 1x1 conv of a branch has as few as 24 channels, and a relu
+    # channel's share of zeros is decided by the sign of its offset: with biases centred on zero a narrow tensor can be mostly
+    # zeros by the luck of its weights, whatever the scales.  Its biases are centred a quarter of the spread above zero (a batch
+    # norm with a positive learnt offset), with the headroom that offset needs.
+    DW = dict(act=0, headroom=3.0)
+    PW = dict(act=1, headroom=1.25)
+    PW1 = dict(act=1, headroom=1.6, bias_shift=0.25)
+
+    def dw(name):
+        g.sig_i8[name] *= 1.6
+        return name
+    for si, (width, reps) in enumerate(zip(widths, SHUFFLENET_V2_REPEATS)):
+        h = width // 2
+        for u in range(reps):
+            p = "s%du%d" % (si + 2, u + 1)
+            if u == 0:  # stride 2: both branches read the whole input
+                left = dw(g.conv(p + "_l_dw", x, cin, 3, 2, 1, groups=cin, **DW))
+                left = g.conv(p + "_l_pw", left, h, 1, 1, 0, **PW)
+                y = g.conv(p + "_r_pw1", x, h, 1, 1, 0, **PW1)
+                y = dw(g.conv(p + "_r_dw", y, h, 3, 2, 1, groups=h, **DW))
+            else:
+                left, right = g.split([p + "_x1", p + "_x2"], x, 1, num=2)
+                y = g.conv(p + "_r_pw1", right, h, 1, 1, 0, **PW1)
+                y = dw(g.conv(p + "_r_dw", y, h, 3, 1, 1, groups=h, **DW))
+            y = g.conv(p + "_r_pw2", y, h, 1, 1, 0, **PW)
+            x = g.shuffle(p + "_shuffle", g.concat(p + "_concat", [left, y], 1), 2)
+            cin = width
+    x = g.conv("conv5", x, 2048 if scale == 2.0 else 1024, 1, 1, 0, act=1)
+    x = g.pool("pool", x, "avg", g.shape[x][1], 1, 0, global_pooling=True)
+    x = g.fc("fc", x, num_classes)
+    x = g.softmax("prob", x)
+    return _finish(g, res, x)
+
+
+def shuffle_unit_bytes(net, batch):
+    """Algorithmic bytes of the data movement of every stride-1 unit tail (split, calib of the second half, concat, shuffle_channel)
+    as separate instructions, and of the one fused launch: (53 h P, 13 h P) summed over the units, h the half width and P the
+    plane.  Counts, not measurements."""
+    sep = fused = 0
+    for o in net["ops"]:
+        if o["op"] == "split":
+            c, h_, w_ = net["shapes"][o["names"][1]]
+            sep += 53 * c * h_ * w_ * batch  # split 16, calib 5, concat 16, shuffle_channel 16
+            fused += 13 * c * h_ * w_ * batch
+    return sep, fused
+
+
 def mobilenet_v1_net(seed=1234, res=224):
     """MobileNetV1 in op-list form, same weights as make_mobilenet_v1_weights(seed): graph mode must arrive at exactly
     the Appendix-D program that build_mobilenet_v1 writes out by hand."""
@@ -366,7 +468,8 @@ def mobilenet_v1_net(seed=1234, res=224):
 
 def net_stats(net):
     """MACs and algorithmic activation bytes per image by op class (int8 tensors 1 B/elt, fp32 tensors 4 B/elt are
-    decided by the lowering; here: conv MACs and element counts only)."""
+    decided by the lowering; here: conv MACs and element counts only).  concat / split / shuffle_channel carry no MACs: their
+    bytes are program_costs' and shuffle_unit_bytes'."""
     macs = {"conv1x1": 0, "conv_kxk": 0, "depthwise": 0, "fc": 0}
     shapes = net["shapes"]
     for o in net["ops"]:
@@ -381,7 +484,7 @@ def net_stats(net):
     return macs
 
 
-def emit_graph(pred, net, batch, fuse=True, fuse_dwpw=None, fuse_dwconv=None, image=None, frame=None, fuse_hard_act=None):
+def emit_graph(pred, net, batch, fuse=True, fuse_dwpw=None, fuse_dwconv=None, image=None, frame=None, fuse_hard_act=None, fuse_shuffle=None):
     """Feed the op list to the predictor's graph mode and lower it.  Returns the host name of the output variable.
     image: None = the input is the normalised fp32 NCHW tensor; dict(format, means, scales) = the input is a decoded uint8 image
     [batch, h, w, cs] of that format (liteapi.IMG_*), normalised on the device (Predictor.graph_feed_image).
@@ -393,7 +496,9 @@ def emit_graph(pred, net, batch, fuse=True, fuse_dwpw=None, fuse_dwconv=None, im
     fuse_dwconv: None = the builder's default (off); True = fusion G, a depthwise conv takes its 1x1 consumer over together with
     that conv's fused tail (MobileNetV2's blocks), False = off.
     fuse_hard_act: None = the builder's default (off); True = fusions J1 / J2 / J3 of the MobileNetV3 ops (hard_swish and
-    elementwise_mul take the calib behind them over, the excite chain becomes one hard_sigmoid/se_gate instruction)."""
+    elementwise_mul take the calib behind them over, the excite chain becomes one hard_sigmoid/se_gate instruction).
+    fuse_shuffle: None = the builder's default (on); fusion K of the ShuffleNetV2 ops (concat -> shuffle_channel(2) ->
+    [split ->] calib becomes one shuffle_channel/unit or shuffle_channel/int8 instruction), False = the separate instructions."""
     from . import liteapi
     pred.graph_set_fuse(fuse)
     if fuse_dwpw is not None:
@@ -402,6 +507,8 @@ def emit_graph(pred, net, batch, fuse=True, fuse_dwpw=None, fuse_dwconv=None, im
         pred.graph_set_fuse_dwconv(fuse_dwconv)
     if fuse_hard_act is not None:
         pred.graph_set_fuse_hard_act(fuse_hard_act)
+    if fuse_shuffle is not None:
+        pred.graph_set_fuse_shuffle(fuse_shuffle)
     c, h, w = net["input_shape"]
     if frame is not None:
         assert image is None, "emit_graph: image= and frame= exclude each other"
@@ -432,6 +539,12 @@ def emit_graph(pred, net, batch, fuse=True, fuse_dwpw=None, fuse_dwconv=None, im
             pred.graph_hard_sigmoid(o["src"], o["name"])
         elif t == "mul":
             pred.graph_elementwise_mul(o["x"], o["y"], o["name"], 0)
+        elif t == "concat":
+            pred.graph_concat(o["srcs"], o["name"], o["axis"])
+        elif t == "split":
+            pred.graph_split(o["src"], o["names"], o["axis"], o["num"], o["sections"])
+        elif t == "shuffle_channel":
+            pred.graph_shuffle_channel(o["src"], o["name"], o["group"])
         else:
             raise ValueError(t)
     pred.graph_fetch(net["output"])
@@ -461,6 +574,24 @@ def program_costs(net, batch, plan_lines):
         flags = {f for f in toks if "=" not in f}
         ins, dst = kv["in"].split(","), kv["out"]
         op, alias = head.split("/")
+        if op in ("concat", "split") or op == "shuffle_channel":  # fp32 moves: every operand once, every written tensor once
+            outs = dst.split(",")
+            byts = sum(numel(i) * 4 for i in ins)
+            if alias == "unit" and "+hi" in kv:  # (K1): the split's second half, where it has another reader
+                outs.append(kv["+hi"])
+            if "-f32" in flags:                  # (K2): the shuffled fp32 tensor is not written
+                outs = []
+            for v in outs:
+                esz[v] = 4
+                byts += numel(v) * 4
+            for v in dst.split(","):
+                esz.setdefault(v, 4)
+            if "+calib" in kv:
+                esz[kv["+calib"]] = 1
+                byts += numel(kv["+calib"])
+            fam = {"def": op, "unit": "shuffle_unit", "int8": "shuffle_concat"}[alias]
+            out.append(dict(name=outs[0] if outs else kv["+calib"], family=fam, ops=0, bytes=byts))
+            continue
         if op == "io_copy":
             esz[dst] = esz.get(ins[0], 4)
             out.append(dict(name=dst, family="io_copy", ops=0, bytes=0))

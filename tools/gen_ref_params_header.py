@@ -9,7 +9,7 @@ import os
 import re
 
 STRUCTS = ["ParamBase", "IoCopyParam", "CalibParam", "FcParam", "SoftmaxParam", "ActivationParam", "ConvParam", "PoolParam",
-           "ElementwiseParam", "FusionElementwiseActivationParam"]
+           "ElementwiseParam", "FusionElementwiseActivationParam", "ShuffleChannelParam", "ConcatParam", "SplitParam"]
 
 
 def struct_text(src, name):
