@@ -395,6 +395,14 @@ plhip_status plhip_selftest(plhip_ctx* ctx);
  * `make EXPERIMENTS=1` build also accepts "STAMPS" (in-kernel timelines).  Returns 0, or -1 for an unknown key. ---- */
 int plhip_debug_set(const char* key, int value);
 
+/* The launch plan (csrc/dw_plan.h) of a depthwise conv (kind 0: plhip_depthwise_conv_int8), of a fused depthwise -> pointwise
+ * pair (kind 1: plhip_dwpw_fused_int8) or of a fused depthwise -> 1x1 conv (kind 2: plhip_dw_conv1x1_fused_int8) under the knobs
+ * in force, as one line of text: "name <template parameters> grid=x,y block=.. lds=.. | <launch-plan fields>", or
+ * "none why=<the entry point's error text>".  pw_cout, has_tail: the fused kinds; x_aligned: kind 2, the input pointer sits on
+ * 4 bytes.  Host logic only: launches nothing, needs no context.  Returns the text's length, -1 for a bad kind or buffer. */
+int plhip_debug_dw_plan(const plhip_conv_desc* dw, int kind /*0 depthwise, 1 D pair, 2 G pair*/, int pw_cout, int out, int has_tail,
+                        int x_aligned, char* buf, size_t cap);
+
 #ifdef __cplusplus
 }
 #endif

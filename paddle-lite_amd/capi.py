@@ -27,7 +27,7 @@ EXPORTS = [
     "plhip_fc_packed_weight_bytes", "plhip_pack_fc_weights", "plhip_fc_int8",
     "plhip_calib_f32_to_i8", "plhip_calib_i8_to_f32", "plhip_global_avg_pool_f32", "plhip_softmax_f32",
     "plhip_pool2d_f32", "plhip_pool2d_max_i8", "plhip_elementwise_add_f32", "plhip_selftest",
-    "plhip_debug_set", "plhip_conv2d_calib_supported", "plhip_conv2d_calib_int8",
+    "plhip_debug_set", "plhip_debug_dw_plan", "plhip_conv2d_calib_supported", "plhip_conv2d_calib_int8",
     "plhip_image_to_tensor_f32", "plhip_image_to_tensor_i8", "plhip_conv2d_image_supported", "plhip_conv2d_image_int8",
     "plhip_image_resize_tables", "plhip_image_convert_u8", "plhip_image_resize_u8", "plhip_frame_to_tensor_f32", "plhip_frame_to_tensor_i8",
     "plhip_hard_act_f32", "plhip_se_scale_f32",
@@ -149,6 +149,19 @@ def gemm_plan_text(d, out, tail=0):
     return buf.value.decode()
 
 
+DW_PLAN_DEPTHWISE, DW_PLAN_PAIR_D, DW_PLAN_PAIR_G = 0, 1, 2
+
+
+def dw_plan_text(d, kind, pw_cout=0, out=2, has_tail=0, x_aligned=1):
+    """The launch plan (csrc/dw_plan.h) the library makes for depthwise descriptor d as a depthwise conv, a fused depthwise ->
+    pointwise pair or a fused depthwise -> 1x1 conv (DW_PLAN_*) under the knobs in force: 'name KS=... grid=... lds=... | ...', or
+    'none why=...'.  Host only: launches nothing, needs no context."""
+    buf = C.create_string_buffer(768)
+    if load().plhip_debug_dw_plan(C.byref(d), int(kind), int(pw_cout), int(out), int(has_tail), int(x_aligned), buf, len(buf)) < 0:
+        raise PlhipError("plhip_debug_dw_plan: bad kind")
+    return buf.value.decode()
+
+
 def load():
     """dlopen libplhip.so and declare prototypes.  Raises if the library is absent (no CPU fallback)."""
     global _lib
@@ -215,6 +228,8 @@ def load():
     # diagnostics outside include/plhip.h: the GEMM launch plan of a conv as text (gemm_plan_text below), the wide tile override
     L.plhip_debug_gemm_plan.argtypes = [C.POINTER(ConvDesc), i32, i32, C.c_char_p, sz]
     L.plhip_debug_gemm_plan.restype = i32
+    L.plhip_debug_dw_plan.argtypes = [C.POINTER(ConvDesc), i32, i32, i32, i32, i32, C.c_char_p, sz]
+    L.plhip_debug_dw_plan.restype = i32
     L.plhip_debug_wide_ntt.argtypes = [i32]
     L.plhip_debug_wide_ntt.restype = None
     L.plhip_depthwise_conv_int8.argtypes = [vp, C.POINTER(ConvDesc), vp, vp, vp, vp, vp, i32]

@@ -591,151 +591,63 @@ __global__ __launch_bounds__(256) void depthwise5x5_direct_kernel(DwArgs a) {
   dw_direct_kernel_body<OUT, S, RS, STAGE, FASTV, 5>(a);
 }
 
-template <int OUT, int S, int KS>
-static void launch_dw_direct_s(const DwArgs& a_in, int rs, hipStream_t s) {
-  const long owq = (a_in.ow + 3) >> 2;
-  const long spp = (a_in.oh + rs - 1) / rs;
-  const long total = (long)a_in.planes * spp * owq;
+// the knobs the three plans of dw_plan.h read.  Host only.
+DwKnobs dw_knobs() {
+  DwKnobs k;
+  k.stage = knob("DW_STAGE", k.stage);
+  k.stage_np2 = knob("DW_STAGE_NP2", k.stage_np2);
+  k.fastv = knob("DW_FASTV", k.fastv);
+  k.k5_direct = knob("DW5_DIRECT", k.k5_direct);
+  k.rs1 = knob("DW_RS1", k.rs1);
+  k.rs2 = knob("DW_RS2", k.rs2);
+  k.fused_stream = knob("FUSED_STREAM", k.fused_stream);
+  k.fused_small = knob("FUSED_SMALL", k.fused_small);
+  k.dwconv_fused = knob("DWCONV_FUSED", k.dwconv_fused);
+  return k;
+}
+
+// executes a plan of depthwise_launch_plan (dw_plan.h)
+void launch_depthwise(const DwArgs& a_in, const DwPlan& p, int out, hipStream_t s) {
   DwArgs a = a_in;
-  a.total_lanes = total;
-  a.hi2 = a.act == ACT_RELU6 ? (a.alpha + a.alpha < 254.f ? a.alpha + a.alpha : 254.f) : 254.f;
-  a.ones = 0x01010101u;
-  auto lg2 = [](long v) { int l = 0; while ((1L << l) < v) ++l; return (1L << l) == v ? l : -1; };
-  a.owq_log2 = lg2(owq);
-  a.spp_log2 = lg2(spp);
-  a.fast_div = a.owq_log2 >= 0 && a.spp_log2 >= 0 && lg2(a.C) >= 0;
-  fastdiv_magic(owq, a.div_owq_m, a.div_owq_s);
-  fastdiv_magic(spp, a.div_spp_m, a.div_spp_s);
-  fastdiv_magic(a.C, a.div_c_m, a.div_c_s);
-  // output staging through LDS: int8 output, narrow planes, a wave = whole strips, strips = whole rows of the plane
-  const int stage_env = knob("DW_STAGE", 1);
-  // (owq a power of two: a wave = 64 lanes = whole strips; otherwise a wave uses (64 / owq) * owq lanes: 63 of 64 on
-  // 28-wide planes, 56 of 64 on 56-wide ones — the 14x14 layers went 19.3 -> 11.0 us with staging, and a 28x28 layer
-  // moves the same bytes with the same arithmetic)
-  const int stage_np2 = knob("DW_STAGE_NP2", 1);
-  // measured: 28-wide planes gain ~5 % (dw6 19.7 -> 18.7 us), 56-wide ones lose ~5 %: the store-request granularity that
-  // staging cures is a narrow-row effect; stage_np2 = 2 forces it for every width <= 64
-  const bool stage = stage_env && OUT == OUT_I8 && a.ow <= 64 && owq <= 64 && a.oh % rs == 0 &&
-                     (a.owq_log2 >= 0 || (stage_np2 == 1 && a.ow <= 32) || stage_np2 >= 2);
-  a.lw = stage ? (int)((64 / owq) * owq) : 64;
-  a.nblocks = stage ? (int)(((total + a.lw - 1) / a.lw + 3) / 4) : (int)((total + 255) / 256);
-  const unsigned blocks = (unsigned)((a.nblocks + 7) / 8 * 8);  // 8 XCDs x equal shares (kernel: vb map)
-  a.stage_bytes = stage ? (int)(((64 / owq) * rs * a.ow + 15) & ~15) : 0;
-  const size_t lds = stage ? (size_t)4 * a.stage_bytes : 0;
-  // fast row fetch: only the first / last row of a strip can leave the image, windows start inside the row
-  const int fast_env = knob("DW_FASTV", 1);
-  constexpr int PV = (KS - 1) / 2;
-  const bool fastv = fast_env && a.pt <= PV && (a.oh - 1) * S + KS - 1 - a.pt <= a.h - 1 + PV && a.oh % rs == 0 &&
-                     (owq - 1) * 4 * S - a.pl < a.w;
-#define PLHIP_DW_LAUNCH(RSV, ST, FV)                                                                               \
-  do {                                                                                                             \
-    if (KS == 5) hipLaunchKernelGGL((depthwise5x5_direct_kernel<OUT, S, RSV, ST, FV>), dim3(blocks), dim3(256), lds, s, a); \
-    else hipLaunchKernelGGL((depthwise3x3_direct_kernel<OUT, S, RSV, ST, FV>), dim3(blocks), dim3(256), lds, s, a);         \
-  } while (0)
-#define PLHIP_DW_RS(ST, FV)              \
-  do {                                   \
-    if (rs == 8) PLHIP_DW_LAUNCH(8, ST, FV);      \
-    else if (rs == 7) PLHIP_DW_LAUNCH(7, ST, FV); \
-    else PLHIP_DW_LAUNCH(4, ST, FV);              \
-  } while (0)
-  if (stage && fastv) PLHIP_DW_RS(true, true);
-  else if (stage) PLHIP_DW_RS(true, false);
-  else if (fastv) PLHIP_DW_RS(false, true);
-  else PLHIP_DW_RS(false, false);
-#undef PLHIP_DW_RS
-#undef PLHIP_DW_LAUNCH
-}
-
-static bool launch_dw_direct(const DwArgs& a, int out, hipStream_t s) {
-  const int k5_env = knob("DW5_DIRECT", 1);  // 0 = 5x5 filters on the LDS-band kernel (A/B runs)
-  const bool k3 = a.kh == 3 && a.kw == 3, k5 = a.kh == 5 && a.kw == 5 && k5_env;
-  if (!((k3 || k5) && a.dh == 1 && a.dw == 1 && a.sh == a.sw && (a.sw == 1 || a.sw == 2) && a.pl <= 3)) return false;
-  if ((long)a.planes * a.h * a.w >= (1L << 31) || (long)a.planes * a.oh * a.ow >= (1L << 31)) return false;
-  // rows per strip: amortise the 2-row halo while keeping many lanes (and bytes) in flight
-  int rs;
-  const int rs1_env = knob("DW_RS1", 0);
-  if (a.sw == 1 && (rs1_env == 4 || rs1_env == 7 || rs1_env == 8)) rs = rs1_env;
-  else if (a.sw == 1) rs = (a.oh % 8 == 0) ? 8 : (a.oh % 7 == 0 ? 7 : (a.oh >= 8 ? 8 : (a.oh >= 5 ? 7 : 4)));
-  else {
-    // stride 2 fetches 2 rows per output row: a taller strip amortises the per-row fetch / mask work (VALU-bound op)
-    const int rs2_env = knob("DW_RS2", 0);
-    if (rs2_env == 4 || rs2_env == 7 || rs2_env == 8) rs = rs2_env;
-    else rs = (a.oh % 7 == 0 && a.oh <= 14) ? 7 : 4;  // taller strips measured slower (dw3 33.7 -> 37.1 us): not VALU-bound
-  }
-  const bool s1 = a.sw == 1;
-#define PLHIP_DW_OUT(O)                                                                              \
-  do {                                                                                               \
-    if (k5) s1 ? launch_dw_direct_s<O, 1, 5>(a, rs, s) : launch_dw_direct_s<O, 2, 5>(a, rs, s);      \
-    else s1 ? launch_dw_direct_s<O, 1, 3>(a, rs, s) : launch_dw_direct_s<O, 2, 3>(a, rs, s);         \
-  } while (0)
-  if (out == OUT_I32) PLHIP_DW_OUT(OUT_I32);
-  else if (out == OUT_F32) PLHIP_DW_OUT(OUT_F32);
-  else PLHIP_DW_OUT(OUT_I8);
-#undef PLHIP_DW_OUT
-  return true;
-}
-
-template <int OUT>
-static void launch_dw_t(const DwArgs& a, int fast, unsigned blocks, size_t lds, hipStream_t s) {
-  switch (fast) {
-    case 31: hipLaunchKernelGGL((depthwise_i8_kernel<OUT, 31>), dim3(blocks), dim3(256), lds, s, a); break;
-    case 32: hipLaunchKernelGGL((depthwise_i8_kernel<OUT, 32>), dim3(blocks), dim3(256), lds, s, a); break;
-    case 51: hipLaunchKernelGGL((depthwise_i8_kernel<OUT, 51>), dim3(blocks), dim3(256), lds, s, a); break;
-    case 52: hipLaunchKernelGGL((depthwise_i8_kernel<OUT, 52>), dim3(blocks), dim3(256), lds, s, a); break;
-    default: hipLaunchKernelGGL((depthwise_i8_kernel<OUT, 0>), dim3(blocks), dim3(256), lds, s, a); break;
-  }
-}
-
-// Tiling of the LDS-band kernel from the shape fields of `a`: a block covers PB planes x OB output rows; aim at ~2K quads (8 per
-// thread) per block and keep the LDS tile under 48 KiB so that several blocks share a CU.  Fills PB, OB, bands, in_rows, pitch;
-// false: a single row band does not fit in LDS (60 KiB).
-bool depthwise_plan(DwArgs* a) {
-  const int owq = (a->ow + 3) / 4;
-  const int OFF = (a->pl + 3) / 4 * 4;
-  const int maxcol = (4 * owq - 1) * a->sw - a->pl + (a->kw - 1) * a->dw + OFF;
-  const int pitch = ((maxcol > OFF + a->w ? maxcol : OFF + a->w) + 1 + 16 + 3) / 4 * 4;
-  const int target = 2048;
-  int OB, PB;
-  if (a->oh * owq >= target) {
-    PB = 1;
-    OB = target / owq;
-    if (OB < 1) OB = 1;
-    if (OB > a->oh) OB = a->oh;
-  } else {
-    OB = a->oh;
-    PB = target / (a->oh * owq);
-    if (PB < 1) PB = 1;
-    if (PB > 64) PB = 64;
-    if (PB > a->planes) PB = a->planes;
-  }
-  auto in_rows_of = [&](int ob) { return (ob - 1) * a->sh + (a->kh - 1) * a->dh + 1; };
-  auto lds_of = [&](int pb, int ob) {
-    return (size_t)pb * in_rows_of(ob) * pitch + (size_t)pb * a->kh * 8 + (size_t)pb * 8 + (size_t)pb * a->kh * a->kw + 16;
-  };
-  while (lds_of(PB, OB) > 48 * 1024 && PB > 1) PB = PB / 2;
-  while (lds_of(PB, OB) > 48 * 1024 && OB > 1) OB = (OB + 1) / 2;
-  if (lds_of(PB, OB) > 60 * 1024) return false;
-  a->PB = PB;
-  a->OB = OB;
-  a->bands = (a->oh + OB - 1) / OB;
-  a->in_rows = in_rows_of(OB);
-  a->pitch = pitch;
-  return true;
-}
-
-int launch_depthwise(const DwArgs& a, int out, hipStream_t s) {
-  if (launch_dw_direct(a, out, s)) return 0;
-  int fast = 0;
-  if (a.kh == a.kw && (a.kw == 3 || a.kw == 5) && a.sh == a.sw && (a.sw == 1 || a.sw == 2) && a.dh == 1 && a.dw == 1)
-    fast = a.kw * 10 + a.sw;
-  const size_t lds = (size_t)a.PB * a.in_rows * a.pitch + (size_t)a.PB * a.kh * 8 + (size_t)a.PB * 8 +
-                     (((size_t)a.PB * a.kh * a.kw + 15) & ~(size_t)15);
-  if (lds > 64 * 1024) return -3;
-  const unsigned blocks = (unsigned)(((a.planes + a.PB - 1) / a.PB) * a.bands);
-  if (out == OUT_I32) launch_dw_t<OUT_I32>(a, fast, blocks, lds, s);
-  else if (out == OUT_F32) launch_dw_t<OUT_F32>(a, fast, blocks, lds, s);
-  else launch_dw_t<OUT_I8>(a, fast, blocks, lds, s);
-  return 0;
+  const dim3 grid(p.grid_x), block(p.block);
+  with_const<OUT_I32, OUT_F32, OUT_I8>(out, [&](auto out_c) {
+    constexpr int OUT = decltype(out_c)::value;
+    if (p.family == DW_BAND) {
+      a.PB = p.b.PB;
+      a.OB = p.b.OB;
+      a.bands = p.b.bands;
+      a.in_rows = p.b.in_rows;
+      a.pitch = p.b.pitch;
+      with_const<31, 32, 51, 52, 0>(p.FAST, [&](auto fast) {
+        hipLaunchKernelGGL((depthwise_i8_kernel<OUT, decltype(fast)::value>), grid, block, p.lds, s, a);
+      });
+      return;
+    }
+    const DwPlan::Direct& d = p.d;
+    a.total_lanes = d.total_lanes;
+    a.owq_log2 = d.owq_log2;
+    a.spp_log2 = d.spp_log2;
+    a.fast_div = d.fast_div;
+    a.div_owq_m = d.div_owq_m; a.div_owq_s = d.div_owq_s;
+    a.div_spp_m = d.div_spp_m; a.div_spp_s = d.div_spp_s;
+    a.div_c_m = d.div_c_m; a.div_c_s = d.div_c_s;
+    a.stage_bytes = d.stage_bytes;
+    a.lw = d.lw;
+    a.nblocks = d.nblocks;
+    a.hi2 = a.act == ACT_RELU6 ? (a.alpha + a.alpha < 254.f ? a.alpha + a.alpha : 254.f) : 254.f;
+    with_const<1, 2>(p.S, [&](auto st) {
+      with_const<4, 7, 8>(p.RS, [&](auto rs) {
+        with_const<0, 1>(p.STAGE, [&](auto stage) {
+          with_const<0, 1>(p.FASTV, [&](auto fastv) {
+            constexpr int S = decltype(st)::value, RS = decltype(rs)::value;
+            constexpr bool STAGE = decltype(stage)::value != 0, FASTV = decltype(fastv)::value != 0;
+            if (p.KS == 5) hipLaunchKernelGGL((depthwise5x5_direct_kernel<OUT, S, RS, STAGE, FASTV>), grid, block, p.lds, s, a);
+            else hipLaunchKernelGGL((depthwise3x3_direct_kernel<OUT, S, RS, STAGE, FASTV>), grid, block, p.lds, s, a);
+          });
+        });
+      });
+    });
+  });
 }
 
 }  // namespace plhip

@@ -35,8 +35,7 @@
 
 namespace plhip {
 
-constexpr int DC_APITCH = 48;  // LDS bytes per pixel row of the activation tile (32 channels of a K-step + 16)
-constexpr int DC_THREADS = 256;
+// (DC_APITCH, DC_THREADS: dw_plan.h, which sizes the launch with them)
 
 // bytes O .. O + 3 of the dword array d (compile-time O)
 template <int O, int ND>
@@ -223,81 +222,27 @@ __global__ __launch_bounds__(DC_THREADS) void dw_conv1x1_fused_kernel(DwConvArgs
   }
 }
 
-static void dc_stage_plan(DwConvArgs* a, bool dword) {
-  a->dword_stage = dword ? 1 : 0;
-  a->wu = dword ? a->WP / 4 : a->WP;
-  a->rpp = a->wu <= 64 ? 64 / a->wu : 1;
-}
-
-bool dw_conv1x1_plan(DwConvArgs* a) {
-  if (a->n < 1 || a->h < 1 || a->w < 1 || a->oh < 1 || a->ow < 1) return false;
-  if (a->C < 16 || a->C % 16 != 0 || a->C > 1024) return false;
-  if (a->M < 8 || a->M % 8 != 0 || a->M > 1024) return false;
-  if (a->stride != 1 && a->stride != 2) return false;
-  if (a->pl != 0 && a->pl != 1) return false;
-  // int32 element offsets: every tensor index (input, output, residual, calib copy) below 2^31
-  if ((long long)a->n * a->C * a->h * a->w >= (1ll << 31) || (long long)a->n * a->M * a->oh * a->ow >= (1ll << 31)) return false;
-  const int S = a->stride;
-  a->KS = (a->C + 31) / 32;
-  a->mt32 = (a->M + 31) / 32;
-  // tile: whole rows, <= 128 pixels (wider rows: 128-column segments), LDS <= 64 KiB
-  a->CW = a->ow <= 128 ? a->ow : 128;
-  a->TR = a->ow <= 128 ? (128 / a->ow < a->oh ? 128 / a->ow : a->oh) : 1;
-  if (a->TR < 1) a->TR = 1;
-  const int nd = (7 + 3 * S) / 4 + 1, owq = (a->CW + 3) / 4;
-  for (;;) {
-    a->IR = (a->TR - 1) * S + 3;
-    a->WP = 4 * (owq - 1) * S + 4 * nd;
-    a->NT = (a->TR * a->CW + 31) / 32;
-    a->lds = (size_t)2 * 32 * a->IR * a->WP + (size_t)2 * a->NT * 32 * DC_APITCH;
-    if (a->lds <= 64 * 1024 || a->TR == 1) break;
-    a->TR = (a->TR + 1) / 2;
-  }
-  if (a->lds > 64 * 1024) return false;
-  a->mtpb = a->mt32 < 32 / a->NT ? a->mt32 : 32 / a->NT;
-  a->mgroups = (a->mt32 + a->mtpb - 1) / a->mtpb;
-  const int pairs = a->mtpb * a->NT;
-  a->nacc = pairs <= 4 ? 1 : (pairs <= 8 ? 2 : (pairs <= 16 ? 4 : 8));
-  a->tr_tiles = (a->oh + a->TR - 1) / a->TR;
-  a->cw_tiles = (a->ow + a->CW - 1) / a->CW;
-  a->tpi = a->tr_tiles * a->cw_tiles;
-  if ((long long)a->n * a->tpi >= (1ll << 31)) return false;
-  dc_stage_plan(a, a->w % 4 == 0);
-  fastdiv_magic(a->IR, a->ir_m, a->ir_s);
-  fastdiv_magic(owq, a->owq_m, a->owq_s);
-  fastdiv_magic(a->TR, a->tr_m, a->tr_s);
-  fastdiv_magic(a->CW, a->cw_m, a->cw_s);
-  fastdiv_magic(a->tpi, a->tpi_m, a->tpi_s);
-  fastdiv_magic(a->cw_tiles, a->ctl_m, a->ctl_s);
-  return true;
-}
-
-template <int NACC, int S, int PL>
-static void launch_dc_t(const DwConvArgs& a, int out, hipStream_t s) {
-  const dim3 grid((unsigned)(a.n * a.tpi), (unsigned)a.mgroups), block(DC_THREADS);
-  if (out == OUT_I32) hipLaunchKernelGGL((dw_conv1x1_fused_kernel<NACC, OUT_I32, S, PL>), grid, block, a.lds, s, a);
-  else if (out == OUT_I8) hipLaunchKernelGGL((dw_conv1x1_fused_kernel<NACC, OUT_I8, S, PL>), grid, block, a.lds, s, a);
-  else hipLaunchKernelGGL((dw_conv1x1_fused_kernel<NACC, OUT_F32, S, PL>), grid, block, a.lds, s, a);
-}
-
-template <int S, int PL>
-static void launch_dc_sp(const DwConvArgs& a, int out, hipStream_t s) {
-  if (a.nacc == 1) launch_dc_t<1, S, PL>(a, out, s);
-  else if (a.nacc == 2) launch_dc_t<2, S, PL>(a, out, s);
-  else if (a.nacc == 4) launch_dc_t<4, S, PL>(a, out, s);
-  else launch_dc_t<8, S, PL>(a, out, s);
-}
-
-void launch_dw_conv1x1(const DwConvArgs& a_in, int out, hipStream_t s) {
+// executes a plan of dw_conv1x1_launch_plan (dw_plan.h)
+void launch_dw_conv1x1(const DwConvArgs& a_in, const DwPlan& p, int out, hipStream_t s) {
   DwConvArgs a = a_in;
-  if (a.dword_stage && ((uintptr_t)a.x & 3)) dc_stage_plan(&a, false);  // an input not 4-byte aligned: byte copies
-  if (a.stride == 1) {
-    if (a.pl == 0) launch_dc_sp<1, 0>(a, out, s);
-    else launch_dc_sp<1, 1>(a, out, s);
-  } else {
-    if (a.pl == 0) launch_dc_sp<2, 0>(a, out, s);
-    else launch_dc_sp<2, 1>(a, out, s);
-  }
+  const DwPlan::G& g = p.g;
+  a.KS = g.KS; a.mt32 = g.mt32; a.mtpb = g.mtpb; a.mgroups = g.mgroups;
+  a.TR = g.TR; a.CW = g.CW; a.NT = g.NT; a.tr_tiles = g.tr_tiles; a.cw_tiles = g.cw_tiles; a.tpi = g.tpi;
+  a.IR = g.IR; a.WP = g.WP; a.dword_stage = p.DWORD; a.wu = g.wu; a.rpp = g.rpp; a.nacc = p.NACC;
+  a.ir_m = g.ir_m; a.ir_s = g.ir_s; a.owq_m = g.owq_m; a.owq_s = g.owq_s; a.tr_m = g.tr_m; a.tr_s = g.tr_s;
+  a.cw_m = g.cw_m; a.cw_s = g.cw_s; a.tpi_m = g.tpi_m; a.tpi_s = g.tpi_s; a.ctl_m = g.ctl_m; a.ctl_s = g.ctl_s;
+  a.lds = p.lds;
+  const dim3 grid(p.grid_x, p.grid_y), block(p.block);
+  with_const<1, 2, 4, 8>(p.NACC, [&](auto nacc) {
+    with_const<OUT_I32, OUT_I8, OUT_F32>(out, [&](auto out_c) {
+      with_const<1, 2>(p.S, [&](auto st) {
+        with_const<0, 1>(p.PL, [&](auto pl) {
+          hipLaunchKernelGGL((dw_conv1x1_fused_kernel<decltype(nacc)::value, decltype(out_c)::value, decltype(st)::value, decltype(pl)::value>),
+                             grid, block, p.lds, s, a);
+        });
+      });
+    });
+  });
 }
 
 }  // namespace plhip

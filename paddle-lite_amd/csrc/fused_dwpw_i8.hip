@@ -35,8 +35,7 @@ namespace plhip {
 
 constexpr int FW_TR = 7;       // output rows per tile
 constexpr int FW_NT = 4;       // 32-pixel n tiles per tile (2 rows of pitch 16 each; the second half of the last one is empty)
-constexpr int FW_SP = 112;     // staging pitch of a channel row (98 bytes used)
-constexpr int FW_KSTEP = 4096; // LDS bytes of one K-step of the activation image: [kg 4][k%8 8][chunk slot 8][16 B]
+// (FW_SP, FW_KSTEP: dw_plan.h, which sizes the launch with them)
 
 // timeline stamps (EXPERIMENTS=1 builds, plhip_device.h): per wave of the first 1024 tiles at the phase boundaries, straight
 // into the "fw" stamp buffer [tile][wave 8][FW_STAMP_SLOTS] (tools/fused_timeline.py).  Slots: 0 realtime start, 1 entry,
@@ -72,7 +71,7 @@ __global__ __launch_bounds__(512, 2) void fused_dwpw14_kernel(FusedArgs a) {
   unsigned long long* const lstamp = diag ? gstamp + ((size_t)vb * 8 + wave) * FW_STAMP_SLOTS : nullptr;
   PLHIP_STAMP_REAL(0);
   PLHIP_STAMP(1);
-  const int KS = g.KS, C = a.C, R = KS >> 2;  // rounds of 128 channels (K % 128 == 0: fused_dwpw_plan)
+  const int KS = g.KS, C = a.C, R = KS >> 2;  // rounds of 128 channels (K % 128 == 0: dwpw_launch_plan)
   const int c = lane & 31, h = lane >> 5;
 
   // ------------------------------------------------------------------ producer state
@@ -482,80 +481,23 @@ __global__ __launch_bounds__(512, 2) void fused_dwpw14_kernel(FusedArgs a) {
   }
 }
 
-// Fills the launch plan and says whether the shape is inside the fused path: 3x3, stride 1, dilation 1, pad 1 on a 14 x 14
-// plane, 128 | C <= 512 (whole rounds; the K x 128 activation image + the staging image fit the LDS), M = 256 or 512 (one or
-// two m tiles per wave), depthwise activation relu / relu6 / none / leaky, any pointwise activation.
-bool fused_dwpw_plan(FusedArgs* a, int kh, int kw, int sh, int sw, int dh, int dw, int out) {
-  if (!(kh == 3 && kw == 3 && sh == sw && (sh == 1 || sh == 2) && dh == 1 && dw == 1)) return false;
-  a->ones = 0x01010101u;
-  a->stream = 0;
-  const int fs = knob("FUSED_STREAM", 1);  // 1: every shape of the streaming kernel, 2: stride 1 only, 3: not the 14-wide plane, 0: off
-  // (the plane average as output, OUT_GAP, exists on the small-plane kernel only: nothing else may accept it)
-  if (out != OUT_GAP && fs && (sh == 1 || fs != 2) && !(fs == 3 && a->ow == 14) && fused_stream_supported(*a)) {  // the large planes: fused_dwpw_stream.hip
-    a->stream = 1;
-    return true;
-  }
-  if (knob("FUSED_SMALL", 1) && fused_small_supported(*a)) {  // the 7 x 7 planes: fused_dwpw_small.hip
-    a->stream = 2;
-    return true;
-  }
-  if (out == OUT_GAP) return false;  // the plane average: the small-plane kernel only
-  if (sh != 1) return false;
-  if (!(a->h == 14 && a->w == 14 && a->oh == 14 && a->ow == 14 && a->pt == 1 && a->pl == 1)) return false;
-  if (a->C % 128 != 0 || a->C < 128 || a->C > 512) return false;
-  if (a->pw.M != 256 && a->pw.M != 512) return false;
-  if (a->n < 1 || (long)a->n * a->C * 196 >= ((long)1 << 31) - 65536 || (long)a->n * a->pw.M * 196 >= ((long)1 << 31)) return false;
-  (void)out;
-  a->tiles = 2 * a->n;
-  a->ones = 0x01010101u;
-  return true;
-}
-
-template <int MTW, int OUT>
-static void launch_fused_t(const FusedArgs& a, hipStream_t s) {
-  const unsigned blocks = (unsigned)((a.tiles + 7) / 8 * 8);
-  const size_t lds = (size_t)a.pw.KS * FW_KSTEP + (OUT == OUT_I8 ? (size_t)8 * 32 * MTW * FW_SP : 0);
-  const bool dwnn = a.dw_act == ACT_RELU || a.dw_act == ACT_RELU6;
-  const bool pwnn = OUT == OUT_I8 && (a.pw.act == ACT_RELU || a.pw.act == ACT_RELU6);
-#define PLHIP_FW_LAUNCH(DN, PN)                                                                                  \
-  do {                                                                                                           \
-    auto kfn = fused_dwpw14_kernel<MTW, OUT, DN, PN>;                                                            \
-    (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);           \
-    hipLaunchKernelGGL(kfn, dim3(blocks), dim3(512), lds, s, a);                                                 \
-  } while (0)
-  if constexpr (OUT == OUT_I8) {
-    if (dwnn && pwnn) PLHIP_FW_LAUNCH(true, true);
-    else if (dwnn) PLHIP_FW_LAUNCH(true, false);
-    else if (pwnn) PLHIP_FW_LAUNCH(false, true);
-    else PLHIP_FW_LAUNCH(false, false);
-  } else {
-    if (dwnn) PLHIP_FW_LAUNCH(true, false);
-    else PLHIP_FW_LAUNCH(false, false);
-  }
-#undef PLHIP_FW_LAUNCH
-}
-
-// `a` must have passed fused_dwpw_plan with the same `out`.
-void launch_fused_dwpw(const FusedArgs& a_in, int out, hipStream_t s) {
+// executes a plan of dwpw_launch_plan (dw_plan.h): the 14 x 14 kernel of this file, or the streaming / 7 x 7 kernel
+void launch_fused_dwpw(const FusedArgs& a_in, const DwPlan& p, int out, hipStream_t s) {
   FusedArgs a = a_in;
-  if (a.stream == 2) {
-    launch_fused_small(a, out, s);
-    return;
-  }
-  if (a.stream) {
-    launch_fused_stream(a, out, s);
-    return;
-  }
+  a.tiles = p.tiles;
+  a.pw.NT = p.NT;
+  a.ones = 0x01010101u;
+  if (p.family == DWPW_7) return run_fused_small(p, a, out, s);
+  if (p.family == DWPW_STREAM) return run_fused_stream(p, a, out, s);
   PLHIP_SET_STAMPS(a.pw, "fw", sizeof(unsigned long long) * 1024 * 8 * FW_STAMP_SLOTS);
-  if (a.pw.M == 512) {
-    if (out == OUT_I32) launch_fused_t<2, OUT_I32>(a, s);
-    else if (out == OUT_F32) launch_fused_t<2, OUT_F32>(a, s);
-    else launch_fused_t<2, OUT_I8>(a, s);
-  } else {
-    if (out == OUT_I32) launch_fused_t<1, OUT_I32>(a, s);
-    else if (out == OUT_F32) launch_fused_t<1, OUT_F32>(a, s);
-    else launch_fused_t<1, OUT_I8>(a, s);
-  }
+  with_const<1, 2>(p.MTW, [&](auto mtw) {
+    with_out_nonneg<OUT_I32, OUT_F32, OUT_I8>(out, a.dw_act, a.pw.act, [&](auto out_c, auto dn, auto pn) {
+      constexpr int OUT = decltype(out_c)::value;
+      constexpr bool DN = decltype(dn)::value != 0, PN = decltype(pn)::value != 0;
+      // (PWNN exists for int8 output only)
+      if constexpr (OUT == OUT_I8 || !PN) launch_max_lds(fused_dwpw14_kernel<decltype(mtw)::value, OUT, DN, PN>, p, s, a);
+    });
+  });
 }
 
 }  // namespace plhip

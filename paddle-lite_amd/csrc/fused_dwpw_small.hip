@@ -31,7 +31,7 @@ namespace plhip {
 
 typedef float v2f_s __attribute__((ext_vector_type(2)));
 
-constexpr int F7_PITCH = 96;   // bytes per channel row of the image: 64 slots + pad
+// (F7_PITCH: dw_plan.h, which sizes the launch with it)
 constexpr int F7_WAVES = 8;
 
 // timeline stamps (EXPERIMENTS=1 builds, plhip_device.h): per wave of the first 1024 blocks, straight into the "f7" stamp
@@ -362,56 +362,20 @@ __global__ __launch_bounds__(512, K >= 1024 ? 1 : 2) void fused_dwpw7_kernel(Fus
   PLHIP_STAMP_REAL(7);
 }
 
-// shapes: 7 x 7 output planes, 3x3, pad 1: (stride 2, 512 -> 1024) and (stride 1, 1024 -> 1024): MobileNetV1's last two pairs
-bool fused_small_supported(const FusedArgs& a) {
-  if (!(a.oh == 7 && a.ow == 7 && a.h == a.w && a.pt == 1 && a.pl == 1 && (a.stride == 1 || a.stride == 2) && a.h == 7 * a.stride)) return false;
-  if (a.n < 1 || (long)a.n * a.C * a.h * a.w >= ((long)1 << 31) - 65536 || (long)a.n * a.pw.M * 49 >= ((long)1 << 31)) return false;
-  return (a.stride == 2 && a.C == 512 && a.pw.M == 1024) || (a.stride == 1 && a.C == 1024 && a.pw.M == 1024);
-}
-
-template <int K, int M, int S, int MB, int PD, int OUT>
-static void launch_small_t(FusedArgs a, hipStream_t s) {
-  a.tiles = a.n * MB;
-  const unsigned blocks = (unsigned)((a.tiles + 7) / 8 * 8);
-  size_t lds = (size_t)K * F7_PITCH + (size_t)K * 32;
-  static_assert((size_t)K * F7_PITCH + (size_t)K * 32 >= (size_t)F7_WAVES * 32 * 196, "the image's LDS holds the output staging of the 4-byte forms");
-  const bool dwnn = a.dw_act == ACT_RELU || a.dw_act == ACT_RELU6;
-  const bool pwnn = OUT == OUT_I8 && (a.pw.act == ACT_RELU || a.pw.act == ACT_RELU6);
-#define PLHIP_F7_LAUNCH(DN, PN)                                                                                  \
-  do {                                                                                                           \
-    auto kfn = fused_dwpw7_kernel<K, M, S, MB, PD, OUT, DN, PN>;                                                 \
-    (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);           \
-    hipLaunchKernelGGL(kfn, dim3(blocks), dim3(512), lds, s, a);                                                 \
-  } while (0)
-  if (dwnn && pwnn) PLHIP_F7_LAUNCH(true, true);
-  else if (dwnn) PLHIP_F7_LAUNCH(true, false);
-  else if (pwnn) PLHIP_F7_LAUNCH(false, true);
-  else PLHIP_F7_LAUNCH(false, false);
-#undef PLHIP_F7_LAUNCH
-}
-
-template <int K, int M, int S, int MB, int PD>
-static void launch_small_o(const FusedArgs& a, int out, hipStream_t s) {
-  if (out == OUT_I32) launch_small_t<K, M, S, MB, PD, OUT_I32>(a, s);
-  else if (out == OUT_GAP) launch_small_t<K, M, S, MB, PD, OUT_GAP>(a, s);
-  else if (out == OUT_F32) launch_small_t<K, M, S, MB, PD, OUT_F32>(a, s);
-  else launch_small_t<K, M, S, MB, PD, OUT_I8>(a, s);
-}
-
-void launch_fused_small(const FusedArgs& a_in, int out, hipStream_t s) {
-  FusedArgs a = a_in;
+// executes a dwpw_7x7 plan; a carries the plan's tiles already
+void run_fused_small(const DwPlan& p, FusedArgs a, int out, hipStream_t s) {
   PLHIP_SET_STAMPS(a.pw, "f7", sizeof(unsigned long long) * 1024 * F7_WAVES * 8);
-  // blocks per image along M: 1 (default) = no duplicated work, half the CUs at batch 128: what several predictors in flight
-  // prefer (c3: 379 k img/s against 370 k / 370 k with two blocks / the two kernels; one step in flight 300 k / 308 k / 291 k);
-  // 2 (knob FUSED_SMALL = 2) = every CU gets a block, the depthwise stage computed twice: best alone
-  const bool one = knob("FUSED_SMALL", 1) != 2;
-  if (a.stride == 2) {
-    if (one) launch_small_o<512, 1024, 2, 1, 2>(a, out, s);
-    else launch_small_o<512, 1024, 2, 2, 2>(a, out, s);
-  } else {
-    if (one) launch_small_o<1024, 1024, 1, 1, 2>(a, out, s);
-    else launch_small_o<1024, 1024, 1, 2, 2>(a, out, s);
-  }
+  auto run = [&](auto shape, auto mb) {
+    constexpr dw_plan_detail::SmallShape T = dw_plan_detail::kSmallShapes[decltype(shape)::value];
+    static_assert((size_t)T.K * F7_PITCH + (size_t)T.K * 32 >= (size_t)F7_WAVES * 32 * 196, "the image's LDS holds the output staging of the 4-byte forms");
+    with_out_nonneg<OUT_I32, OUT_GAP, OUT_F32, OUT_I8>(out, a.dw_act, a.pw.act, [&](auto out_c, auto dn, auto pn) {
+      launch_max_lds(fused_dwpw7_kernel<T.K, T.M, T.S, decltype(mb)::value, 2, decltype(out_c)::value, decltype(dn)::value != 0,
+                                        decltype(pn)::value != 0>, p, s, a);
+    });
+  };
+  with_const<0, 1>(p.S == dw_plan_detail::kSmallShapes[0].S ? 0 : 1, [&](auto shape) {
+    with_const<1, 2>(p.MB, [&](auto mb) { run(shape, mb); });
+  });
 }
 
 }  // namespace plhip

@@ -34,7 +34,7 @@ typedef float v2f __attribute__((ext_vector_type(2)));
 
 // TP pixels per tile (224 or 448 = 7 or 14 n tiles); LDS bytes per channel row of the activation image: TP + pad with
 // pitch / 4 = 8 (mod 16): 160 / 288 / 544
-constexpr int fs_pitch(int tp) { return tp == 128 ? 160 : (tp == 224 ? 288 : 544); }
+// (fs_pitch: dw_plan.h, which sizes the launch with it)
 
 // timeline stamps (EXPERIMENTS=1 builds, plhip_device.h): per wave of the first 2048 tiles, straight into the "fs" stamp
 // buffer [tile][wave 4][FS_STAMP_SLOTS]: 0 realtime, 1 entry, 2 operands of the first PD iterations requested, 3 produced,
@@ -424,58 +424,19 @@ __global__ __launch_bounds__(256, M / MP >= 256 ? 2 : 3) void fused_dwpw_stream_
   PLHIP_STAMP_REAL(7);
 }
 
-// shapes of the streaming kernel: (W, K, M) = (112, 32, 64), (56, 128, 128), (28, 256, 256): MobileNetV1's stride-1 pairs on
-// the large planes; 3x3, stride 1, dilation 1, pad 1, square planes
-bool fused_stream_supported(const FusedArgs& a) {
-  if (!(a.h == a.w && a.oh == a.ow && a.pt == 1 && a.pl == 1 && (a.stride == 1 || a.stride == 2) && a.h == a.oh * a.stride)) return false;
-  if (a.n < 1 || (long)a.n * a.C * a.h * a.w >= ((long)1 << 31) - 65536 || (long)a.n * a.pw.M * a.oh * a.ow >= ((long)1 << 31)) return false;
-  if (a.stride == 2)
-    return (a.ow == 56 && a.C == 64 && a.pw.M == 128) || (a.ow == 28 && a.C == 128 && a.pw.M == 256) ||
-           (a.ow == 14 && a.C == 256 && a.pw.M == 512);
-  return (a.w == 112 && a.C == 32 && a.pw.M == 64) || (a.w == 56 && a.C == 128 && a.pw.M == 128) || (a.w == 28 && a.C == 256 && a.pw.M == 256);
-}
-
-template <int W, int K, int M, int TP, int RS, int PD, int S, int MP, int OUT>
-static void launch_stream_t(FusedArgs a, hipStream_t s) {
-  constexpr int TR = W == 14 ? 7 : TP / W;
-  a.pw.NT = (a.oh + TR - 1) / TR;  // tiles per image
-  a.tiles = a.n * a.pw.NT;
-  const unsigned blocks = (unsigned)((a.tiles + 7) / 8 * 8);
-  // image, depthwise parameters, sink of the idle lanes (256 -> 256 @28 has none: its 80 KiB are exactly half a CU's LDS, and
-  // 512 bytes more made it one block per CU: 28.3 -> 34.0 us)
-  const size_t lds = (size_t)K * fs_pitch(TP) + (size_t)K * 32 + (M / MP < 256 ? 512 : 0);
-  const bool dwnn = a.dw_act == ACT_RELU || a.dw_act == ACT_RELU6;
-  const bool pwnn = OUT == OUT_I8 && (a.pw.act == ACT_RELU || a.pw.act == ACT_RELU6);
-#define PLHIP_FS_LAUNCH(DN, PN)                                                                                  \
-  do {                                                                                                           \
-    auto kfn = fused_dwpw_stream_kernel<W, K, M, TP, RS, PD, S, MP, OUT, DN, PN>;                                               \
-    (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);           \
-    hipLaunchKernelGGL(kfn, dim3(blocks), dim3(256), lds, s, a);                                                 \
-  } while (0)
-  if (dwnn && pwnn) PLHIP_FS_LAUNCH(true, true);
-  else if (dwnn) PLHIP_FS_LAUNCH(true, false);
-  else if (pwnn) PLHIP_FS_LAUNCH(false, true);
-  else PLHIP_FS_LAUNCH(false, false);
-#undef PLHIP_FS_LAUNCH
-}
-
-template <int W, int K, int M, int TP, int RS, int PD, int S = 1, int MP = 1>
-static void launch_stream_o(const FusedArgs& a, int out, hipStream_t s) {
-  if (out == OUT_I32) launch_stream_t<W, K, M, TP, RS, PD, S, MP, OUT_I32>(a, s);
-  else if (out == OUT_F32) launch_stream_t<W, K, M, TP, RS, PD, S, MP, OUT_F32>(a, s);
-  else launch_stream_t<W, K, M, TP, RS, PD, S, MP, OUT_I8>(a, s);
-}
-
-void launch_fused_stream(const FusedArgs& a_in, int out, hipStream_t s) {
-  FusedArgs a = a_in;
+// executes a dwpw_stream plan; a carries the plan's tiles / NT already
+void run_fused_stream(const DwPlan& p, FusedArgs a, int out, hipStream_t s) {
   PLHIP_SET_STAMPS(a.pw, "fs", sizeof(unsigned long long) * 2048 * 4 * FS_STAMP_SLOTS);
-  // 112-wide: 4-row tiles of 448 pixels (2-row tiles fetched and cut every input row twice: 61 us, the two kernels 56)
-  if (a.stride == 2 && a.ow == 14) launch_stream_o<14, 256, 512, 128, 7, 2, 2, 2>(a, out, s);  // half images, M in two passes
-  else if (a.stride == 2 && a.ow == 56) launch_stream_o<56, 64, 128, 224, 4, 2, 2>(a, out, s);
-  else if (a.stride == 2) launch_stream_o<28, 128, 256, 224, 4, 2, 2>(a, out, s);
-  else if (a.w == 112) launch_stream_o<112, 32, 64, 448, 4, 2>(a, out, s);
-  else if (a.w == 56) launch_stream_o<56, 128, 128, 224, 4, 2>(a, out, s);
-  else launch_stream_o<28, 256, 256, 224, 4, 2>(a, out, s);
+  auto run = [&](auto shape) {
+    constexpr dw_plan_detail::StreamShape T = dw_plan_detail::kStreamShapes[decltype(shape)::value];
+    with_out_nonneg<OUT_I32, OUT_F32, OUT_I8>(out, a.dw_act, a.pw.act, [&](auto out_c, auto dn, auto pn) {
+      launch_max_lds(fused_dwpw_stream_kernel<T.W, T.K, T.M, T.TP, T.RS, T.PD, T.S, T.MP, decltype(out_c)::value, decltype(dn)::value != 0,
+                                              decltype(pn)::value != 0>, p, s, a);
+    });
+  };
+  int i = 0;  // the plan's row of the shape table
+  while (!(dw_plan_detail::kStreamShapes[i].W == p.W && dw_plan_detail::kStreamShapes[i].S == p.S)) ++i;
+  with_const<0, 1, 2, 3, 4, 5>(i, run);
 }
 
 }  // namespace plhip

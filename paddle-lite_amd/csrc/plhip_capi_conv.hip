@@ -595,7 +595,16 @@ plhip_status plhip_conv2d_image_int8(plhip_ctx* ctx, const plhip_conv_desc* d, c
   return PLHIP_OK;
 }
 
-// ------------------------------------------------------------------ depthwise
+// ------------------------------------------------------------------ depthwise and the fused depthwise -> 1x1 pairs
+// what the plans of dw_plan.h read of a depthwise descriptor (pw_cout, x_aligned: the fused kinds)
+static plhip::DwProblem dw_problem(const plhip_conv_desc* d, const ConvGeom& g, int out, int pw_cout = 0, bool x_aligned = true) {
+  plhip::DwProblem p{d->n, d->cin, d->h, d->w, g.oh, g.ow, d->kh, d->kw, d->pad[0], d->pad[2], d->stride[0], d->stride[1],
+                     d->dil[0], d->dil[1], out};
+  p.pw_M = pw_cout;
+  p.x_aligned = x_aligned;
+  return p;
+}
+
 plhip_status plhip_depthwise_conv_int8(plhip_ctx* ctx, const plhip_conv_desc* d, const int8_t* x, const int8_t* w_oihw,
                                        const float* scale, const float* bias, void* y, plhip_out_kind out) {
   ConvGeom g;
@@ -606,8 +615,10 @@ plhip_status plhip_depthwise_conv_int8(plhip_ctx* ctx, const plhip_conv_desc* d,
   if (plhip_status st = check_out_scale_act(ctx, "plhip_depthwise_conv_int8", out, false, scale, "scale", &d->act)) return st;
   if (!aligned(y, 4 * out_elem_size(out)) && (g.ow & 3) == 0)
     return fail(ctx, PLHIP_ERR_UNSUPPORTED, "plhip_depthwise_conv_int8: output pointer must be 4-element aligned");
+  const plhip::DwPlan p = plhip::depthwise_launch_plan(dw_problem(d, g, (int)out), plhip::dw_knobs());
+  if (p.family == plhip::DW_NONE) return fail(ctx, PLHIP_ERR_UNSUPPORTED, "plhip_depthwise_conv_int8: %s", p.why);
 
-  plhip::DwArgs a;
+  plhip::DwArgs a{};
   a.x = x;
   a.wt = w_oihw;
   a.y = y;
@@ -629,42 +640,30 @@ plhip_status plhip_depthwise_conv_int8(plhip_ctx* ctx, const plhip_conv_desc* d,
   a.dw = d->dil[1];
   a.act = d->act;
   a.alpha = d->act_alpha;
-  if (!plhip::depthwise_plan(&a))
-    return fail(ctx, PLHIP_ERR_UNSUPPORTED, "plhip_depthwise_conv_int8: a single row band does not fit in LDS");
-  if (plhip::launch_depthwise(a, (int)out, ctx->stream) != 0)
-    return fail(ctx, PLHIP_ERR_UNSUPPORTED, "plhip_depthwise_conv_int8: LDS tile too large");
+  plhip::launch_depthwise(a, p, (int)out, ctx->stream);
   LAUNCHCHK(ctx, "depthwise_i8");
   return PLHIP_OK;
 }
 
-// ------------------------------------------------------------------ fused depthwise -> pointwise
-// geometry + launch plan of the fused pair; false: not a depthwise 3x3 the fused kernel takes (the caller runs two kernels)
-static bool dwpw_plan(const plhip_conv_desc* dw, int pw_cout, plhip_out_kind out, plhip::FusedArgs* a, const char** why) {
-  ConvGeom g;
+// ------------------------------------------------------------------ fused depthwise -> pointwise (fusion D)
+// geometry + launch plan of the fused pair; false: not a depthwise 3x3 the fused kernels take (the caller runs two kernels)
+static bool dwpw_plan(const plhip_conv_desc* dw, int pw_cout, plhip_out_kind out, ConvGeom* g, plhip::DwPlan* p, const char** why) {
   *why = "bad depthwise descriptor";
-  if (!dw || pw_cout < 1 || !conv_geom(dw, &g)) return false;
+  if (!dw || pw_cout < 1 || !conv_geom(dw, g)) return false;
   *why = "first conv must be depthwise";
   if (dw->groups != dw->cin || dw->cin != dw->cout) return false;
   *why = "tensor too large";
-  if ((size_t)pw_cout * g.N >= ((size_t)1 << 31) || (size_t)dw->cin * dw->h * dw->w >= ((size_t)1 << 31)) return false;
-  memset(a, 0, sizeof(*a));
-  a->dw_act = dw->act;
-  a->dw_alpha = dw->act_alpha;
-  a->n = dw->n; a->C = dw->cin; a->h = dw->h; a->w = dw->w; a->oh = g.oh; a->ow = g.ow;
-  a->pt = dw->pad[0]; a->pl = dw->pad[2]; a->stride = dw->stride[0];
-  a->pw.M = pw_cout;
-  a->pw.K = dw->cin;
-  a->pw.KS = cdiv(dw->cin, 32);
-  a->pw.HWY = g.N;
-  a->pw.y_bstride = (size_t)pw_cout * g.N;
-  *why = "shape outside the fused path";
-  return plhip::fused_dwpw_plan(a, dw->kh, dw->kw, dw->stride[0], dw->stride[1], dw->dil[0], dw->dil[1], (int)out);
+  if ((size_t)pw_cout * g->N >= ((size_t)1 << 31) || (size_t)dw->cin * dw->h * dw->w >= ((size_t)1 << 31)) return false;
+  *p = plhip::dwpw_launch_plan(dw_problem(dw, *g, (int)out, pw_cout), plhip::dw_knobs());
+  *why = p->why;
+  return p->family != plhip::DW_NONE;
 }
 
 int plhip_dwpw_fused_supported(const plhip_conv_desc* dw, int pw_cout, plhip_out_kind out) {
-  plhip::FusedArgs a;
+  ConvGeom g;
+  plhip::DwPlan p;
   const char* why;
-  return dwpw_plan(dw, pw_cout, out, &a, &why) ? 1 : 0;
+  return dwpw_plan(dw, pw_cout, out, &g, &p, &why) ? 1 : 0;
 }
 
 plhip_status plhip_dwpw_fused_int8(plhip_ctx* ctx, const plhip_conv_desc* dw, const int8_t* x, const int8_t* dw_w_oihw,
@@ -674,33 +673,42 @@ plhip_status plhip_dwpw_fused_int8(plhip_ctx* ctx, const plhip_conv_desc* dw, co
   if (!ctx || !dw || !x || !dw_w_oihw || !dw_scale || !pw_w_packed || !y || pw_cout < 1)
     return fail(ctx, PLHIP_ERR_INVALID, "plhip_dwpw_fused_int8: null / bad argument");
   if (plhip_status st = check_out_scale_act(ctx, "plhip_dwpw_fused_int8", out, true, pw_scale, "pw_scale", nullptr)) return st;
-  plhip::FusedArgs a;
+  ConvGeom g;
+  plhip::DwPlan p;
   const char* why;
-  if (!dwpw_plan(dw, pw_cout, out, &a, &why)) {
-    return fail(ctx, PLHIP_ERR_UNSUPPORTED, "plhip_dwpw_fused_int8: %s", why);
-  }
+  if (!dwpw_plan(dw, pw_cout, out, &g, &p, &why)) return fail(ctx, PLHIP_ERR_UNSUPPORTED, "plhip_dwpw_fused_int8: %s", why);
+  plhip::FusedArgs a;
+  memset(&a, 0, sizeof(a));
   a.x = x;
   a.dw_w = dw_w_oihw;
   a.dw_scale = dw_scale;
   a.dw_bias = dw_bias;
+  a.dw_act = dw->act;
+  a.dw_alpha = dw->act_alpha;
+  a.n = dw->n; a.C = dw->cin; a.h = dw->h; a.w = dw->w; a.oh = g.oh; a.ow = g.ow;
+  a.pt = dw->pad[0]; a.pl = dw->pad[2]; a.stride = dw->stride[0];
+  a.pw.M = pw_cout;
+  a.pw.K = dw->cin;
+  a.pw.KS = cdiv(dw->cin, 32);
+  a.pw.HWY = g.N;
+  a.pw.y_bstride = (size_t)pw_cout * g.N;
   a.pw.wp = (const int8_t*)pw_w_packed;
   a.pw.y = y;
   a.pw.scale = pw_scale;
   a.pw.bias = pw_bias;
   a.pw.act = pw_act;
   a.pw.alpha = pw_alpha;
-  plhip::launch_fused_dwpw(a, (int)out, ctx->stream);
+  plhip::launch_fused_dwpw(a, p, (int)out, ctx->stream);
   LAUNCHCHK(ctx, "fused_dwpw");
   return PLHIP_OK;
 }
 
 // ------------------------------------------------------------------ fused depthwise -> 1x1 conv with the conv's tail (fusion G)
 // geometry + launch plan; false: outside the kernel's envelope (the caller runs the two instructions).  Host logic only.
-static bool dw_conv1x1_plan(const plhip_conv_desc* dw, int pw_cout, plhip_out_kind out, int has_tail, plhip::DwConvArgs* a,
-                            const char** why) {
-  ConvGeom g;
+static bool dw_conv1x1_plan(const plhip_conv_desc* dw, int pw_cout, plhip_out_kind out, int has_tail, bool x_aligned, ConvGeom* g,
+                            plhip::DwPlan* p, const char** why) {
   *why = "bad depthwise descriptor";
-  if (!dw || !conv_geom(dw, &g)) return false;
+  if (!dw || !conv_geom(dw, g)) return false;
   *why = "output kind";
   if (out != PLHIP_OUT_I32_ACC && out != PLHIP_OUT_F32 && out != PLHIP_OUT_I8) return false;
   *why = "a graph tail needs fp32 output";
@@ -714,22 +722,16 @@ static bool dw_conv1x1_plan(const plhip_conv_desc* dw, int pw_cout, plhip_out_ki
   *why = "unsupported depthwise activation";
   if (dw->act != PLHIP_ACT_NONE && dw->act != PLHIP_ACT_RELU && dw->act != PLHIP_ACT_RELU6 && dw->act != PLHIP_ACT_LEAKY_RELU)
     return false;
-  memset(a, 0, sizeof(*a));
-  a->dw_act = dw->act;
-  a->dw_alpha = dw->act_alpha;
-  a->n = dw->n; a->C = dw->cin; a->h = dw->h; a->w = dw->w; a->oh = g.oh; a->ow = g.ow;
-  a->pt = dw->pad[0]; a->pl = dw->pad[2]; a->stride = dw->stride[0];
-  a->M = pw_cout;
-  *why = "fused depthwise -> 1x1 kernel switched off (diagnostics knob DWCONV_FUSED = 0)";
-  if (!plhip::knob("DWCONV_FUSED", 1)) return false;
-  *why = "shape outside the fused kernel (C % 16, C <= 1024, M % 8, M <= 1024, 32-bit element offsets)";
-  return plhip::dw_conv1x1_plan(a);
+  *p = plhip::dw_conv1x1_launch_plan(dw_problem(dw, *g, (int)out, pw_cout, x_aligned), plhip::dw_knobs());
+  *why = p->why;
+  return p->family != plhip::DW_NONE;
 }
 
 int plhip_dw_conv1x1_fused_supported(const plhip_conv_desc* dw, int pw_cout, plhip_out_kind out, int has_tail) {
-  plhip::DwConvArgs a;
+  ConvGeom g;
+  plhip::DwPlan p;
   const char* why;
-  return dw_conv1x1_plan(dw, pw_cout, out, has_tail, &a, &why) ? 1 : 0;
+  return dw_conv1x1_plan(dw, pw_cout, out, has_tail, true, &g, &p, &why) ? 1 : 0;
 }
 
 plhip_status plhip_dw_conv1x1_fused_int8(plhip_ctx* ctx, const plhip_conv_desc* dw, const int8_t* x, const int8_t* dw_w_oihw,
@@ -742,17 +744,26 @@ plhip_status plhip_dw_conv1x1_fused_int8(plhip_ctx* ctx, const plhip_conv_desc* 
     return fail(ctx, PLHIP_ERR_INVALID, "plhip_dw_conv1x1_fused_int8: null / bad argument");
   if (plhip_status st = check_out_scale_act(ctx, "plhip_dw_conv1x1_fused_int8", out, false, pw_scale, "pw_scale", &pw_act, "1x1 activation"))
     return st;
-  plhip::DwConvArgs a;
+  ConvGeom g;
+  plhip::DwPlan p;
   const char* why;
-  if (!dw_conv1x1_plan(dw, pw_cout, out, has_tail, &a, &why)) return fail(ctx, PLHIP_ERR_UNSUPPORTED, "plhip_dw_conv1x1_fused_int8: %s", why);
+  if (!dw_conv1x1_plan(dw, pw_cout, out, has_tail, aligned(x, 4), &g, &p, &why))
+    return fail(ctx, PLHIP_ERR_UNSUPPORTED, "plhip_dw_conv1x1_fused_int8: %s", why);
   if (!y && out != PLHIP_OUT_F32) return fail(ctx, PLHIP_ERR_INVALID, "plhip_dw_conv1x1_fused_int8: y required");
   if (y_i8 && !(calib_scale > 0.f)) return fail(ctx, PLHIP_ERR_INVALID, "plhip_dw_conv1x1_fused_int8: calib scale must be > 0");
   if (residual_relu && !residual) return fail(ctx, PLHIP_ERR_INVALID, "plhip_dw_conv1x1_fused_int8: residual_relu without a residual");
   if (!aligned(pw_w_packed, 16)) return fail(ctx, PLHIP_ERR_INVALID, "plhip_dw_conv1x1_fused_int8: packed weights must be 16-byte aligned");
+  plhip::DwConvArgs a;
+  memset(&a, 0, sizeof(a));
   a.x = x;
   a.dw_w = dw_w_oihw;
   a.dw_scale = dw_scale;
   a.dw_bias = dw_bias;
+  a.dw_act = dw->act;
+  a.dw_alpha = dw->act_alpha;
+  a.n = dw->n; a.C = dw->cin; a.h = dw->h; a.w = dw->w; a.oh = g.oh; a.ow = g.ow;
+  a.pt = dw->pad[0]; a.pl = dw->pad[2]; a.stride = dw->stride[0];
+  a.M = pw_cout;
   a.wp = (const int8_t*)pw_w_packed;
   a.y = y;
   a.scale = pw_scale;
@@ -761,9 +772,31 @@ plhip_status plhip_dw_conv1x1_fused_int8(plhip_ctx* ctx, const plhip_conv_desc* 
   a.alpha = pw_alpha;
   const ConvTail t{residual, residual_relu, y_i8, calib_scale};
   set_tail(a, &t);
-  plhip::launch_dw_conv1x1(a, (int)out, ctx->stream);
+  plhip::launch_dw_conv1x1(a, p, (int)out, ctx->stream);
   LAUNCHCHK(ctx, "dw_conv1x1_fused");
   return PLHIP_OK;
+}
+
+// Diagnostics, host only: the launch plan (dw_plan.h) of a depthwise conv (kind 0), of a fused depthwise -> pointwise pair (1,
+// fusion D) or of a fused depthwise -> 1x1 conv (2, fusion G) as one line of text under the knobs in force, made by the function
+// the entry point's launch executes after the entry point's own descriptor checks; a refusal reads "none why=<the error text>".
+// Returns the text's length, or -1 for a bad kind or buffer.
+int plhip_debug_dw_plan(const plhip_conv_desc* dw, int kind, int pw_cout, int out, int has_tail, int x_aligned, char* buf, size_t cap) {
+  if (!buf || cap == 0 || kind < 0 || kind > 2) return -1;
+  ConvGeom g;
+  plhip::DwPlan p;
+  const char* why = "";
+  if (kind == 0) {
+    if (!dw || !conv_geom(dw, &g)) why = "bad conv descriptor";
+    else if (dw->groups != dw->cin || dw->cin != dw->cout) why = "needs groups == cin == cout";
+    else why = (p = plhip::depthwise_launch_plan(dw_problem(dw, g, out), plhip::dw_knobs())).why;
+  } else if (kind == 1) {
+    dwpw_plan(dw, pw_cout, (plhip_out_kind)out, &g, &p, &why);
+  } else {
+    dw_conv1x1_plan(dw, pw_cout, (plhip_out_kind)out, has_tail, x_aligned != 0, &g, &p, &why);
+  }
+  if (p.family == plhip::DW_NONE) p.why = why;
+  return plhip::dw_plan_text(p, buf, cap);
 }
 
 }  // extern "C"

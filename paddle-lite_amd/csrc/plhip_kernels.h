@@ -6,7 +6,9 @@
 
 #include <type_traits>
 
+#include "dw_plan.h"
 #include "gemm_plan.h"
+#include "plhip_device.h"
 
 namespace plhip {
 
@@ -172,6 +174,7 @@ struct DwArgs {
   const float* scale;
   const float* bias;
   int planes, C, h, w, oh, ow, kh, kw, pt, pl, sh, sw, dh, dw;
+  // launch plan (depthwise_launch_plan, dw_plan.h; launch_depthwise copies it in).  LDS-band kernel:
   int PB;       // planes per block
   int OB;       // output rows per block band
   int bands;    // bands per plane
@@ -187,8 +190,9 @@ struct DwArgs {
   int lw, nblocks;                // direct kernel: lanes of a wave that own work (staging: whole strips), workgroups of work
   int act;
   float alpha;
-  // direct kernels, set by their launcher: the int8 clamp's upper bound on doubled values (relu6: min(2 alpha, 254)) and the
-  // byte-wise +1 of the packed rounding, as kernel arguments = scalar operands (the compiler re-made both per output row)
+  // direct kernels: the int8 clamp's upper bound on doubled values (relu6: min(2 alpha, 254); follows the activation, so the
+  // launcher sets it, not the plan) and the byte-wise +1 of the packed rounding, as kernel arguments = scalar operands (the
+  // compiler re-made both per output row)
   float hi2 = 254.f;
   unsigned ones = 0x01010101u;
 };
@@ -202,18 +206,13 @@ struct FusedArgs {
   int dw_act;
   float dw_alpha;
   int n, C, h, w, oh, ow, pt, pl, stride;
-  int tiles;              // launch plan (fused_dwpw_plan): (image, half-plane) tiles = 2 n
-  unsigned ones;          // 0x01010101 as a scalar operand (the byte-wise +1 of the packed rounding)
-  int stream;             // 1 = the streaming kernel of the large planes (fused_dwpw_stream.hip), 0 = the 14 x 14 kernel
+  // launch plan (dwpw_launch_plan, dw_plan.h; launch_fused_dwpw copies it in): tiles = blocks of work: (image, half-plane) = 2 n
+  // on the 14 x 14 kernel, n * pw.NT row tiles on the streaming kernel (pw.NT = tiles per image), n * MB on the 7 x 7 kernel
+  int tiles;
+  unsigned ones;          // 0x01010101 as a scalar operand (the byte-wise +1 of the packed rounding); launch_fused_dwpw sets it
+  int unused_;            // no kernel reads it (once the kernel selector, now DwPlan::family); it keeps the argument block's layout
   GemmArgs pw;            // wp, y, scale, bias, M, KS, HWY (= oh*ow), y_bstride, act, alpha
 };
-// fills the plan from (n, C, h, w, oh, ow, pt, pl, stride, pw.M); false = shape outside the fused path
-bool fused_dwpw_plan(FusedArgs* a, int kh, int kw, int sh, int sw, int dh, int dw, int out);
-void launch_fused_dwpw(const FusedArgs& a, int out, hipStream_t s);
-bool fused_stream_supported(const FusedArgs& a);   // fused_dwpw_stream.hip: the 112 / 56 / 28-wide stride-1 pairs
-void launch_fused_stream(const FusedArgs& a, int out, hipStream_t s);
-bool fused_small_supported(const FusedArgs& a);    // fused_dwpw_small.hip: the 7 x 7 planes (512 -> 1024 stride 2, 1024 -> 1024)
-void launch_fused_small(const FusedArgs& a, int out, hipStream_t s);
 
 // fused depthwise 3x3 (int8 out) -> 1x1 conv with the conv's graph tail (fused_dwconv_i8.hip, fusion G)
 struct DwConvArgs {
@@ -235,18 +234,15 @@ struct DwConvArgs {
   int res_relu;
   int8_t* y2;
   float inv_scale2;
-  // launch plan (dw_conv1x1_plan): K-steps of 32 channels; 32-row m tiles in all / per block (grid.y = m groups); tile = TR
+  // launch plan (dw_conv1x1_launch_plan, dw_plan.h; launch_dw_conv1x1 copies it in): K-steps of 32 channels; 32-row m tiles in all / per block (grid.y = m groups); tile = TR
   // output rows x CW columns of one image (CW = ow, or 128-column segments of wider rows) = NT 32-pixel n tiles; tiles per
   // image (tr_tiles x cw_tiles); staged input rows IR of WP bytes (LDS column = input column - CW-segment start + 4); stage
-  // units per row (dwords when w % 4 == 0, else bytes) and rows per wave pass; accumulators per wave; LDS bytes
+  // units per row (dwords when w % 4 == 0 and x sits on 4 bytes, else bytes) and rows per wave pass; accumulators per wave; LDS bytes
   int KS, mt32, mtpb, mgroups, TR, CW, NT, tr_tiles, cw_tiles, tpi, IR, WP, dword_stage, wu, rpp, nacc;
   unsigned ir_m, owq_m, tr_m, cw_m, tpi_m, ctl_m;  // fastdiv_u31 (magic, shift) for IR, CW / 4 quads, TR, CW, tpi, cw_tiles
   int ir_s, owq_s, tr_s, cw_s, tpi_s, ctl_s;
   size_t lds;
 };
-// fills the plan from (n, C, h, w, oh, ow, stride, M); false = shape outside the kernel's envelope
-bool dw_conv1x1_plan(DwConvArgs* a);
-void launch_dw_conv1x1(const DwConvArgs& a, int out, hipStream_t s);
 
 // ---- the GEMM kernels.  gemm_plan (gemm_plan.h) decides the whole launch; the three files below only execute a plan.
 inline GemmProblem gemm_problem(const GemmArgs& g, int ma, int out, bool vec_store, bool aligned_loads) {
@@ -274,9 +270,31 @@ inline bool with_const(int v, F&& f) {
 }
 void launch_pack_weights(const int8_t* w, int8_t* wp, int G, int Mg, int Kg, int MT32, int KS, hipStream_t s);
 void launch_im2col(const Im2colArgs& a, hipStream_t s);
-// fills the LDS tiling (PB, OB, bands, in_rows, pitch) from the shape fields; false = a single row band does not fit in LDS
-bool depthwise_plan(DwArgs* a);
-int launch_depthwise(const DwArgs& a, int out, hipStream_t s);  // returns 0 or -3 (unsupported LDS size)
+
+// ---- the depthwise and fused depthwise -> 1x1 kernels.  The three plan functions of dw_plan.h decide the whole launch; the five
+// files below only execute a plan: they copy its fields into the argument block and pick the instance it names.
+DwKnobs dw_knobs();  // the knobs the plans read (depthwise_i8.hip).  Host only.
+void launch_depthwise(const DwArgs& a, const DwPlan& p, int out, hipStream_t s);        // depthwise_i8.hip
+void launch_fused_dwpw(const FusedArgs& a, const DwPlan& p, int out, hipStream_t s);    // fused_dwpw_i8.hip: every dwpw_* plan
+void run_fused_stream(const DwPlan& p, FusedArgs a, int out, hipStream_t s);            // fused_dwpw_stream.hip
+void run_fused_small(const DwPlan& p, FusedArgs a, int out, hipStream_t s);             // fused_dwpw_small.hip
+void launch_dw_conv1x1(const DwConvArgs& a, const DwPlan& p, int out, hipStream_t s);   // fused_dwconv_i8.hip
+// fusion D's kernels: raises the kernel's dynamic-LDS limit to the plan's bytes and launches it on the plan's grid
+template <class Kernel, class Args>
+inline void launch_max_lds(Kernel kfn, const DwPlan& p, hipStream_t s, const Args& a) {
+  (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
+  hipLaunchKernelGGL(kfn, dim3(p.grid_x), dim3(p.block), p.lds, s, a);
+}
+// fusion D's instance split that no plan decides: calls f(OUT, DWNN, PWNN) as integral constants: OUT = `out` of Outs...; DWNN: the
+// depthwise activation is relu / relu6 (its int8 values are non-negative); PWNN: so is the pointwise one and the output is int8
+template <int... Outs, class F>
+inline void with_out_nonneg(int out, int dw_act, int pw_act, F&& f) {
+  const bool dwnn = dw_act == ACT_RELU || dw_act == ACT_RELU6;
+  const bool pwnn = out == OUT_I8 && (pw_act == ACT_RELU || pw_act == ACT_RELU6);
+  with_const<Outs...>(out, [&](auto o) {
+    with_const<0, 1>(dwnn, [&](auto dn) { with_const<0, 1>(pwnn, [&](auto pn) { f(o, dn, pn); }); });
+  });
+}
 
 // direct 3x3 stride-2 convolution for small Cin (network stems)
 struct DirectS2Args {

@@ -117,9 +117,15 @@ def edge_stats(y_f32, act, alpha):
 G1 = "conv1x1s1_gemm_int8_mfma32x32x32"
 
 
-def _r(name, kind, shape, impl=None, knobs=(), mm_cin=None, m=None, kernel=None):
+def _r(name, kind, shape, impl=None, knobs=(), mm_cin=None, m=None, kernel=None, seed_row=None):
     return {"name": name, "kind": kind, "shape": shape, "impl": impl, "knobs": dict(knobs), "mm_cin": mm_cin, "m": m,
-            "kernel": kernel or name}
+            "kernel": kernel or name, "seed_row": seed_row}
+
+
+def case_seed(i, route, j=0, maxmag=False):
+    """The seed of case j of ROUTES[i]: from the row's index, or from the number the row states where few channels need a draw
+    that puts an output on every anchor (test_edge_cases.py checks that it does)."""
+    return 7000 * maxmag + 100 * (i if route["seed_row"] is None else route["seed_row"]) + j
 
 
 ROUTES = [
@@ -142,10 +148,13 @@ ROUTES = [
     _r("stem7x7s2", "conv", (1, 3, 20, 32, 64, 7, 7, (3,) * 4, 2, 1, 1), "conv_7x7s2_direct_int8_mfma32x32x32"),
     _r("stem_f32_calib", "calib", (2, 3, 16, 16, 32, 3, 3, (1,) * 4, 2, 1, 1)),
     _r("stem_u8_image", "image", (2, 3, 16, 16, 32, 3, 3, (1,) * 4, 2, 1, 1)),
-    _r("dw3x3s1_direct", "dw", (2, 24, 14, 14, 24, 3, 3, (1,) * 4, 1, 1, 24)),
-    _r("dw3x3s1_unstaged", "dw", (2, 24, 14, 14, 24, 3, 3, (1,) * 4, 1, 1, 24), knobs={"DW_STAGE": 0}),
-    _r("dw3x3s2_general_fetch", "dw", (2, 24, 14, 14, 24, 3, 3, (1,) * 4, 2, 1, 24), knobs={"DW_FASTV": 0}),
-    _r("dw5x5s1_direct", "dw", (2, 16, 14, 14, 16, 5, 5, (2,) * 4, 1, 1, 16)),
+    # the direct strip kernel's rows name the whole instance of the int8 output (kernel_for: 32-bit outputs are never staged)
+    _r("dw3x3s1_direct", "dw", (2, 24, 14, 14, 24, 3, 3, (1,) * 4, 1, 1, 24), kernel="dw_direct KS=3 S=1 RS=7 STAGE=1 FASTV=1"),
+    _r("dw3x3s1_unstaged", "dw", (2, 24, 14, 14, 24, 3, 3, (1,) * 4, 1, 1, 24), knobs={"DW_STAGE": 0},
+       kernel="dw_direct KS=3 S=1 RS=7 STAGE=0 FASTV=1"),
+    _r("dw3x3s2_general_fetch", "dw", (2, 24, 14, 14, 24, 3, 3, (1,) * 4, 2, 1, 24), knobs={"DW_FASTV": 0},
+       kernel="dw_direct KS=3 S=2 RS=7 STAGE=1 FASTV=0"),
+    _r("dw5x5s1_direct", "dw", (2, 16, 14, 14, 16, 5, 5, (2,) * 4, 1, 1, 16), kernel="dw_direct KS=5 S=1 RS=7 STAGE=1 FASTV=1"),
     _r("dw5x5s2_band", "dw", (2, 16, 14, 14, 16, 5, 5, (2,) * 4, 2, 1, 16), knobs={"DW5_DIRECT": 0}, kernel="dw_band"),
     _r("dw3x3_dilated_generic", "dw", (2, 12, 13, 11, 12, 3, 3, (2,) * 4, 1, 2, 12), kernel="dw_generic"),
     _r("dwpw_14x14", "dwpw", (2, 128, 14, 14, 128, 3, 3, (1,) * 4, 1, 1, 128), m=256),
@@ -158,13 +167,17 @@ ROUTES = [
     _r("dwpw_stream_s2_28", "dwpw", (1, 256, 28, 28, 256, 3, 3, (1,) * 4, 2, 1, 256), m=512, kernel="dwpw_stream"),
     _r("dwpw_7x7", "dwpw", (1, 512, 14, 14, 512, 3, 3, (1,) * 4, 2, 1, 512), m=1024),
     _r("dwpw_7x7_s1", "dwpw", (1, 1024, 7, 7, 1024, 3, 3, (1,) * 4, 1, 1, 1024), m=1024, kernel="dwpw_7x7"),
-    _r("dw_conv1x1_fusion_g", "dwconv", (2, 384, 14, 14, 384, 3, 3, (1,) * 4, 1, 1, 384), m=64),
+    _r("dw_conv1x1_fusion_g", "dwconv", (2, 384, 14, 14, 384, 3, 3, (1,) * 4, 1, 1, 384), m=64, kernel="dw_conv1x1"),
     _r("fc_dot4", "fc", (6, 64, 1, 1, 40, 1, 1, (0,) * 4, 1, 1, 1), mm_cin=1088),
     _r("fc_mfma", "fc", (6, 64, 1, 1, 40, 1, 1, (0,) * 4, 1, 1, 1), knobs={"FC_MFMA": 1}, mm_cin=1088),
     _r("conv_tail_res_calib", "tail", (2, 64, 6, 6, 96, 1, 1, (0,) * 4, 1, 1, 1), G1),
+    # (new rows go last: a case's seed is its row's index)
+    # the direct depthwise kernel's other strip heights (the 14 x 14 rows above give RS = 7 only): strips of 8 rows, staged,
+    # power-of-two quads per row / strips of 4 rows, three quads per row: the smallest planes at which those instances differ.
+    # 8 channels give the anchors 8 draws: seeds at which every one of them is hit
+    _r("dw3x3s1_rs8", "dw", (2, 8, 8, 8, 8, 3, 3, (1,) * 4, 1, 1, 8), kernel="dw_direct KS=3 S=1 RS=8 STAGE=1 FASTV=1", seed_row=42),
+    _r("dw3x3s1_rs4", "dw", (2, 8, 4, 12, 8, 3, 3, (1,) * 4, 1, 1, 8), kernel="dw_direct KS=3 S=1 RS=4 STAGE=1 FASTV=1", seed_row=47),
 ]
-# the streaming kernel's whitelisted (C, H, stride, M) (fused_dwpw_stream.hip)
-STREAM_SHAPES = {(32, 112, 1, 64), (128, 56, 1, 128), (256, 28, 1, 256), (64, 112, 2, 128), (128, 56, 2, 256), (256, 28, 2, 512)}
 
 
 class Knobs:
@@ -184,31 +197,32 @@ class Knobs:
 
 GEMM_IMPLS = (G1, "conv_implicit_gemm_int8_mfma32x32x32")
 OUT_KINDS = {"i32": 0, "f32": 1, "i8": 2}  # plhip_out_kind
+DW_PLAN_KINDS = {"dw": 0, "dwpw": 1, "dwconv": 2}  # plhip_debug_dw_plan's kind
 
 
 def kernel_of(capi, route, cin, out):
-    """The kernel the route's launch reaches (the route table's `kernel`) under the knobs in force.  The GEMM routes ask the
-    library for its own launch plan (capi.gemm_plan_text: csrc/gemm_plan.h, the function the launcher executes); the others
-    restate their launchers' host logic."""
+    """The kernel the route's launch reaches (the route table's `kernel`) under the knobs in force.  The GEMM, depthwise and
+    fused depthwise routes ask the library for its own launch plan (capi.gemm_plan_text, capi.dw_plan_text: csrc/gemm_plan.h,
+    csrc/dw_plan.h, the functions the launchers execute): the plan's name, and for the direct depthwise kernel its template
+    parameters too."""
     n, _, h, w, cout, kh, kw, pads, st, dl, g = route["shape"]
-    kn = route["knobs"]
-    if route["kind"] == "conv" and route["impl"] in GEMM_IMPLS:
+    kind = route["kind"]
+    if kind == "conv" and route["impl"] in GEMM_IMPLS:
         d = capi.conv_desc(n, cin, h, w, cout, kh, kw, pads, (st, st), (dl, dl), g)
         return capi.gemm_plan_text(d, OUT_KINDS[out]).split(" ")[0]
-    if route["kind"] == "dwpw":
-        oh = (h + pads[0] + pads[1] - 3) // st + 1
-        if (cin, h, st, route["m"]) in STREAM_SHAPES:
-            return "dwpw_stream"
-        if oh == 7:
-            return "dwpw_7x7"
-        return "dwpw_14x14" if route["m"] == 256 else "dwpw_14x14_mtw2"
-    if route["kind"] == "dw":
-        if not ((kh, kw) in ((3, 3), (5, 5)) and dl == 1 and pads[2] <= 3 and (kh == 3 or kn.get("DW5_DIRECT", 1))):
-            return "dw_generic" if dl > 1 else "dw_band"
-        return route["name"]
-    if route["kind"] == "fc":
-        return "fc_mfma" if kn.get("FC_MFMA", 0) and cin % 32 == 0 else "fc_dot4"
+    if kind in DW_PLAN_KINDS:
+        d = capi.conv_desc(n, cin, h, w, cin, kh, kw, pads, (st, st), (dl, dl), cin)
+        t = capi.dw_plan_text(d, DW_PLAN_KINDS[kind], route["m"] or 0, OUT_KINDS[out]).split(" ")
+        return " ".join(t[:6]) if t[0] == "dw_direct" else t[0]
+    if kind == "fc":
+        return "fc_mfma" if route["knobs"].get("FC_MFMA", 0) and cin % 32 == 0 else "fc_dot4"
     return route["name"]
+
+
+def kernel_for(route, out):
+    """The kernel the route's row names for output kind `out`: the row's `kernel`; the direct depthwise kernel stages int8
+    output only, so its 32-bit outputs run the row's instance unstaged."""
+    return route["kernel"] if out == "i8" else route["kernel"].replace("STAGE=1", "STAGE=0")
 
 
 # the value each knob has when nobody set it (the launchers' defaults)

@@ -104,12 +104,12 @@ def test_every_route_on_its_value_edges(gpu_ctx, pkg, plref, maxmag):
             acts = acts[:1] if route["kind"] in ("fc", "tail") else (acts[0], (E.ACT_LEAKY, 0.375))
         with E.Knobs(lib, route["knobs"]):
             for j, (act, alpha) in enumerate(acts):
-                c = E.make_case(plref, route, act, alpha, maxmag, 7000 * maxmag + 100 * i + j)
+                c = E.make_case(plref, route, act, alpha, maxmag, E.case_seed(i, route, j, maxmag))
                 _run(gpu_ctx, capi, route, c, act, alpha)
                 k = _ran(capi, route, c)
-                assert k == {route["kernel"]}, (route["name"], k)  # the knob reached the kernel the route names
+                assert k == {E.kernel_for(route, out) for out in ("i32", "i8", "f32")}, (route["name"], k)  # the knob reached the kernel the route names
                 ran |= k
-    assert ran == {r["kernel"] for r in E.ROUTES}, sorted(ran)
+    assert ran == {E.kernel_for(r, out) for r in E.ROUTES for out in ("i32", "i8", "f32")}, sorted(ran)
     print("kernels on their edges:", sorted(ran))
 
 

@@ -145,7 +145,7 @@ def test_xcd_contiguous_maps_cover_every_tile_once():
 
 
 def test_magic_division_is_exact_below_2_31():
-    """Host mirror of fastdiv_u31 (csrc/dw_common.h) and of the (magic, shift) pairs launch_dw_direct_s prepares:
+    """Host mirror of fastdiv_u31 (csrc/dw_common.h) and of the (magic, shift) pairs depthwise_launch_plan (csrc/dw_plan.h) prepares:
     q = mulhi(n, floor(2^(31+s)/d) + 1) >> (s-1), s = ceil(log2 d), must equal n // d for every n < 2^31."""
     rng = np.random.default_rng(5)
     for d in list(range(1, 130)) + [196, 255, 257, 1000, 1023, 1025, 4097, 65535, 65537, 1 << 20, (1 << 20) + 1, (1 << 30) - 1]:

@@ -34,9 +34,8 @@ NAMES = ["gemm_nchw", "gemm_vperm_lds", "gemm_ring", "gemm_ring_ma1", "gemm_areg
 # register-ring form; tr 5 tiles x 3 OUT x 2 IM; wide (4 + 3 + 3) (NTT, KS) x 3 OUT
 INSTANCES = "instances private=24 lds=24 ring=48 tr=30 wide=30"
 
-# Shared by every program that prints the sweep: the includer defines Prob (the fields of GemmProblem, in its order), Setting and
-# Rec below and  void plan_rec(const Setting&, const Prob&, Rec*)  (the plan's fields; the driver prints them as gemm_plan_text does).
-DRIVER = r"""
+# Shared by every program that prints a sweep (tools/dump_dw_plans.py too): the includes and SHA-256.
+PRELUDE = r"""
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
@@ -109,7 +108,11 @@ struct Ctx {
   }
 };
 }  // namespace sha
+"""
 
+# The includer defines Prob (the fields of GemmProblem, in its order), Setting and Rec below and
+# void plan_rec(const Setting&, const Prob&, Rec*)  (the plan's fields; the driver prints them as gemm_plan_text does).
+DRIVER = PRELUDE + r"""
 static const Setting kSettings[] = {
     //                     variant areg ma tr cfg wide ntt_knob ntt_override
     {"default",                  0, 1, 0, 1, 3, 1, 0, -1}, {"GEMM_VARIANT=1",           1, 1, 0, 1, 3, 1, 0, -1},
