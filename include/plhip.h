@@ -361,6 +361,16 @@ plhip_status plhip_se_gate_int8(plhip_ctx* ctx, const plhip_se_gate_desc* d, con
  * call.  xs / extents are host arrays, read before the call returns. */
 plhip_status plhip_concat_f32(plhip_ctx* ctx, const float* const* xs, const int64_t* extents, int count, int64_t outer,
                               int64_t inner, float* y);
+/* concat -> calib[fp32_to_int8] in ONE launch (the tail of a fire / inception module): the operands as plhip_concat_f32 takes
+ * them, y_i8 [outer][sum extents][inner] = round_sat_i8((1.f / calib_scale) * v), the quantiser of plhip_calib_f32_to_i8, and,
+ * where y_f32 is not NULL, y_f32 of the same shape with the input bits unchanged: byte for byte what plhip_concat_f32 followed
+ * by plhip_calib_f32_to_i8 write.  Refused before any launch: count < 1, a NULL operand, an extent < 1, outer or inner < 1, NULL
+ * y_i8, a calib_scale that is not a positive finite number, more than 2^40 elements.  A lane takes 16 consecutive floats of a row
+ * (four 16-byte loads, one 16-byte int8 store) where every extents[i] * inner is a multiple of 16 and xs[i], y_f32, y_i8 are
+ * 16-byte aligned; quads where they are multiples of 4 (y_i8 4-byte aligned); else elements.  Pointers travel in the kernel's
+ * arguments, 8 per launch, as plhip_concat_f32's: no copy, no synchronise, capturable. */
+plhip_status plhip_concat_calib_f32(plhip_ctx* ctx, const float* const* xs, const int64_t* extents, int count, int64_t outer,
+                                    int64_t inner, float* y_f32, int8_t* y_i8, float calib_scale);
 /* plhip_split_f32 replaces SplitCompute (lite/backends/arm/math/split.cc:54-82, shapes lite/operators/split_op.cc:32-75):
  * x [outer][extent][inner] into `count` >= 1 outputs ys[i] [outer][e_i][inner].  num > 0: equal parts, e_i = extent / num,
  * num must divide extent and count == num (sections is ignored, may be NULL); num == 0: e_i = sections[i] >= 1, which must add

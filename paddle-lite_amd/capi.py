@@ -33,6 +33,7 @@ EXPORTS = [
     "plhip_hard_act_f32", "plhip_se_scale_f32",
     "plhip_se_gate_supported", "plhip_se_gate_packed_weight_bytes", "plhip_pack_se_gate_weights", "plhip_se_gate_int8",
     "plhip_concat_f32", "plhip_split_f32", "plhip_shuffle_channel_f32", "plhip_shuffle_unit_f32",
+    "plhip_concat_calib_f32",
 ]
 
 # plhip_hard_act_kind, and the reference's default parameters (lite/operators/op_params.h:406-412)
@@ -259,6 +260,7 @@ def load():
     L.plhip_pack_se_gate_weights.argtypes = [vp, i32, i32, vp, vp, vp]
     L.plhip_se_gate_int8.argtypes = [vp, C.POINTER(SeGateDesc), vp, vp, vp, vp, vp, vp, vp]
     L.plhip_concat_f32.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int64), i32, C.c_int64, C.c_int64, vp]
+    L.plhip_concat_calib_f32.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int64), i32, C.c_int64, C.c_int64, vp, vp, f32]
     L.plhip_split_f32.argtypes = [vp, vp, C.c_int64, C.c_int64, C.c_int64, i32, C.POINTER(C.c_int64), i32, C.POINTER(vp)]
     L.plhip_shuffle_channel_f32.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, f32]
     L.plhip_shuffle_unit_f32.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, f32]
@@ -730,6 +732,29 @@ class Context:
         for b in [ybuf] + [b for b, _d in ups]:
             self.free(b)
         return y
+
+    def concat_calib(self, xs, axis, calib_scale, with_f32=True, misalign=0):
+        """plhip_concat_calib_f32 of fp32 arrays along `axis`: returns (y_f32 or None, y_i8)."""
+        xs = [np.ascontiguousarray(x, np.float32) for x in xs]
+        axis = axis + xs[0].ndim if axis < 0 else axis
+        outer = int(np.prod(xs[0].shape[:axis], dtype=np.int64))
+        inner = int(np.prod(xs[0].shape[axis + 1:], dtype=np.int64))
+        ups = [self._up_f32(x, misalign) for x in xs]
+        shape = list(xs[0].shape)
+        shape[axis] = sum(x.shape[axis] for x in xs)
+        cnt = int(np.prod(shape))
+        fbuf, df = self._out_buf(cnt, 4, misalign) if with_f32 else (None, C.c_void_p())
+        qbuf, dq = self._out_buf(cnt, 1, misalign)
+        ptrs = (C.c_void_p * len(xs))(*[d for _b, d in ups])
+        ext = (C.c_int64 * len(xs))(*[x.shape[axis] for x in xs])
+        try:
+            self.check(self.L.plhip_concat_calib_f32(self.h, ptrs, ext, len(xs), outer, inner, df, dq, float(calib_scale)), "concat_calib")
+            yf = self.to_host(df, tuple(shape), np.float32) if with_f32 else None
+            yq = self.to_host(dq, tuple(shape), np.int8)
+        finally:
+            for b in [qbuf] + ([fbuf] if with_f32 else []) + [b for b, _d in ups]:
+                self.free(b)
+        return yf, yq
 
     def split(self, x, axis, num=0, sections=(), misalign=0):
         """plhip_split_f32: num > 0 equal parts, else `sections`.  Returns the list of parts."""

@@ -178,6 +178,26 @@ plhip_status plhip_concat_f32(plhip_ctx* ctx, const float* const* xs, const int6
   return PLHIP_OK;
 }
 
+plhip_status plhip_concat_calib_f32(plhip_ctx* ctx, const float* const* xs, const int64_t* extents, int count, int64_t outer, int64_t inner,
+                                    float* y_f32, int8_t* y_i8, float calib_scale) {
+  const char* who = "plhip_concat_calib_f32";
+  if (!ctx || !xs || !extents) return fail(ctx, PLHIP_ERR_INVALID, "%s: null ctx, xs or extents", who);
+  if (count < 1) return fail(ctx, PLHIP_ERR_INVALID, "%s: count must be at least 1", who);
+  for (int i = 0; i < count; ++i) {
+    if (!xs[i]) return fail(ctx, PLHIP_ERR_INVALID, "%s: null input", who);
+    if (extents[i] < 1) return fail(ctx, PLHIP_ERR_INVALID, "%s: every extent must be at least 1", who);
+  }
+  if (outer < 1 || inner < 1) return fail(ctx, PLHIP_ERR_INVALID, "%s: outer and inner must be at least 1", who);
+  if (!y_i8) return fail(ctx, PLHIP_ERR_INVALID, "%s: y_i8 is required", who);
+  if (!(calib_scale > 0.f) || !(calib_scale <= 3.402823466e38f))
+    return fail(ctx, PLHIP_ERR_INVALID, "%s: calib_scale must be a positive finite number", who);
+  int64_t total = 0;
+  if (!extents_ok(extents, count, outer, inner, &total)) return fail(ctx, PLHIP_ERR_INVALID, "%s: more than 2^40 elements", who);
+  plhip::launch_concat_calib(xs, extents, count, outer, inner, y_f32, y_i8, calib_scale, ctx->stream);
+  LAUNCHCHK(ctx, "concat_calib");
+  return PLHIP_OK;
+}
+
 plhip_status plhip_split_f32(plhip_ctx* ctx, const float* x, int64_t outer, int64_t extent, int64_t inner, int num, const int64_t* sections,
                              int count, float* const* ys) {
   if (!ctx || !x || !ys || count < 1 || count > (1 << 20) || extent < 1 || num < 0) return fail(ctx, PLHIP_ERR_INVALID, "plhip_split_f32: bad argument");

@@ -440,6 +440,18 @@ struct ConcatArgs {
 // CONCAT_MAX_PARTS parts.
 void launch_concat_split(float* const* parts, const int64_t* extents, int count, int64_t outer, int64_t inner, float* whole, int split,
                          hipStream_t s);
+// concat -> calib[fp32_to_int8] in one launch per CONCAT_MAX_PARTS parts: yq the int8 tensor, yf (may be null) the fp32 one
+struct ConcatCalibArgs {
+  const float* part[CONCAT_MAX_PARTS];  // [outer][len[p]]
+  int64_t len[CONCAT_MAX_PARTS];        // c_p * inner floats
+  int64_t off[CONCAT_MAX_PARTS];        // where part p's row starts inside an output row
+  float* yf;                            // [outer][stride] or null
+  int8_t* yq;                           // [outer][stride]
+  int64_t stride, outer;
+  float inv;                            // 1 / calib scale
+};
+void launch_concat_calib(const float* const* parts, const int64_t* extents, int count, int64_t outer, int64_t inner, float* yf,
+                         int8_t* yq, float calib_scale, hipStream_t s);
 // out[b][j * group + i] = in[b][i * (c / group) + j]; yf / yq: either may be null
 void launch_shuffle_channel(const float* x, float* yf, int8_t* yq, float calib_scale, int n, int c, int hw, int group, hipStream_t s);
 // shuffled channel c' = 2 j + side of (side ? b : a) [n][h][hw]: c' < split_at -> lo [n][split_at][hw], else hf / hq [n][2 h - split_at][hw]

@@ -1,5 +1,6 @@
 // shuffle_ops.hip — the fp32 ops that join, part and permute tensors along an axis, for gfx950: concat, split,
-// shuffle_channel, and the tail of a ShuffleNetV2 unit (concat -> shuffle_channel(2) -> split -> calib) in one launch.
+// shuffle_channel, the tail of a ShuffleNetV2 unit (concat -> shuffle_channel(2) -> split -> calib) in one launch, and
+// concat -> calib in one launch (the tail of a fire / inception module).
 //
 // Replaces (reference, ARM):
 //   concat           ConcatCompute lite/kernels/arm/concat_compute.cc:37-57 (-> concat_func): `count` inputs [outer][c_i][inner]
@@ -21,6 +22,11 @@ namespace plhip {
 
 namespace {
 
+// calib_f32_to_i8_kernel's quantiser on a quad: four int8 in one dword
+__device__ __forceinline__ uint32_t calib4_i8(const v4f& v, float inv) {
+  return pack4_i8(round_sat_i8(inv * v[0]), round_sat_i8(inv * v[1]), round_sat_i8(inv * v[2]), round_sat_i8(inv * v[3]));
+}
+
 // one row of `len` floats from src to df (fp32, may be null) and dq (int8, may be null): this lane takes the items (quads with vec,
 // else elements) first, first + step, ...; the lanes that share the row cover every item once
 __device__ __forceinline__ void move_row(const float* __restrict__ src, float* __restrict__ df, int8_t* __restrict__ dq, int64_t len,
@@ -30,9 +36,7 @@ __device__ __forceinline__ void move_row(const float* __restrict__ src, float* _
     for (int64_t q = first; q < nq; q += step) {
       const v4f v = reinterpret_cast<const v4f*>(src)[q];
       if (df) reinterpret_cast<v4f*>(df)[q] = v;
-      if (dq)
-        reinterpret_cast<uint32_t*>(dq)[q] =
-            pack4_i8(round_sat_i8(inv * v[0]), round_sat_i8(inv * v[1]), round_sat_i8(inv * v[2]), round_sat_i8(inv * v[3]));
+      if (dq) reinterpret_cast<uint32_t*>(dq)[q] = calib4_i8(v, inv);
     }
     return;
   }
@@ -113,6 +117,89 @@ void launch_concat_split(float* const* parts, const int64_t* extents, int count,
     a.vec = vec ? 1 : 0;
     if (split) launch_concat_split<1>(a, np, s);
     else launch_concat_split<0>(a, np, s);
+  }
+}
+
+// concat -> calib[fp32_to_int8]: part p's row o, a.len[p] floats, goes to yq (int8) and, where a.yf is given, yf (fp32, the bits
+// moved) at o * stride + off[p].  Unlike move_row's lanes, which have one quad in flight, a lane takes one ITEM of W consecutive
+// floats of a row: W == 16: four 16-byte loads in flight, one 16-byte int8 store (and four 16-byte fp32 stores); W == 4: a quad;
+// W == 1: an element.  grid: x = slices of 256 items of a row (a long row is shared by several blocks; what gridDim.x cannot
+// reach is taken in a loop), y = the row (loop), z = the part.  The part comes from blockIdx; no lane divides.
+template <int LOGW>
+__global__ __launch_bounds__(256) void concat_calib_kernel(ConcatCalibArgs a) {
+  constexpr int W = 1 << LOGW;
+  const int p = blockIdx.z;
+  const float* __restrict__ part = a.part[p];
+  const int64_t len = a.len[p], off = a.off[p];
+  const int64_t items = len >> LOGW;  // the host takes W only where it divides every len
+  const int64_t step = (int64_t)gridDim.x * 256;
+  const float inv = a.inv;
+  for (int64_t row = blockIdx.y; row < a.outer; row += gridDim.y) {
+    const float* __restrict__ src = part + row * len;
+    const int64_t dst = row * a.stride + off;
+    float* __restrict__ df = a.yf ? a.yf + dst : nullptr;
+    int8_t* __restrict__ dq = a.yq + dst;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < items; i += step) {
+      if constexpr (W == 16) {
+        const v4f* s4 = reinterpret_cast<const v4f*>(src) + 4 * i;
+        const v4f v0 = s4[0], v1 = s4[1], v2 = s4[2], v3 = s4[3];
+        if (df) {
+          v4f* d4 = reinterpret_cast<v4f*>(df) + 4 * i;
+          d4[0] = v0; d4[1] = v1; d4[2] = v2; d4[3] = v3;
+        }
+        v4i q;
+        q[0] = (int)calib4_i8(v0, inv); q[1] = (int)calib4_i8(v1, inv); q[2] = (int)calib4_i8(v2, inv); q[3] = (int)calib4_i8(v3, inv);
+        reinterpret_cast<v4i*>(dq)[i] = q;
+      } else if constexpr (W == 4) {
+        const v4f v = reinterpret_cast<const v4f*>(src)[i];
+        if (df) reinterpret_cast<v4f*>(df)[i] = v;
+        reinterpret_cast<uint32_t*>(dq)[i] = calib4_i8(v, inv);
+      } else {
+        const float v = src[i];
+        if (df) df[i] = v;
+        dq[i] = (int8_t)round_sat_i8(inv * v);
+      }
+    }
+  }
+}
+
+// parts[i]: `outer` rows of extents[i] * inner floats; yf (may be null) / yq: `outer` rows of sum(extents) * inner.  The item
+// width is decided once per call: 16 where every operand row and every output row offset is a multiple of 16 elements and every
+// base is aligned for 16-byte accesses, 4 likewise for quads (yq: 4 bytes), else 1.  CONCAT_MAX_PARTS parts per launch, as concat.
+void launch_concat_calib(const float* const* parts, const int64_t* extents, int count, int64_t outer, int64_t inner, float* yf,
+                         int8_t* yq, float calib_scale, hipStream_t s) {
+  int64_t total = 0, all = 0;
+  bool al = al16(yf);
+  for (int i = 0; i < count; ++i) {
+    const int64_t len = extents[i] * inner;
+    total += extents[i];
+    all |= len;  // a low bit clear here is clear in every len, so in every row offset and in the output stride
+    al = al && al16(parts[i]);
+  }
+  const int logw = al && (all & 15) == 0 && al16(yq) ? 4 : al && (all & 3) == 0 && ((uintptr_t)yq & 3) == 0 ? 2 : 0;
+  const float inv = 1.f / calib_scale;  // type_trans.cc:45, as launch_calib_f32_to_i8
+  int64_t off = 0;
+  for (int first = 0; first < count; first += CONCAT_MAX_PARTS) {
+    ConcatCalibArgs a;
+    const int np = count - first < CONCAT_MAX_PARTS ? count - first : CONCAT_MAX_PARTS;
+    int64_t longest = 0;
+    for (int p = 0; p < CONCAT_MAX_PARTS; ++p) {
+      const bool used = p < np;
+      a.part[p] = used ? parts[first + p] : nullptr;
+      a.len[p] = used ? extents[first + p] * inner : 0;
+      a.off[p] = off;
+      if (used) off += a.len[p];
+      longest = a.len[p] > longest ? a.len[p] : longest;
+    }
+    a.yf = yf;
+    a.yq = yq;
+    a.stride = total * inner;
+    a.outer = outer;
+    a.inv = inv;
+    const dim3 grid(grid_dim(((longest >> logw) + 255) / 256, 1 << 16), grid_dim(outer, 65535), (unsigned)np);
+    if (logw == 4) hipLaunchKernelGGL(concat_calib_kernel<4>, grid, dim3(256), 0, s, a);
+    else if (logw == 2) hipLaunchKernelGGL(concat_calib_kernel<2>, grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(concat_calib_kernel<0>, grid, dim3(256), 0, s, a);
   }
 }
 

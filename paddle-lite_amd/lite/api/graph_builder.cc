@@ -406,6 +406,7 @@ struct GraphBuilder::Fuser {
   void SeGate();
   void HardActCalib();
   void ShuffleTail();
+  void ConcatCalib();
 };
 
 // (A) (C) (B): the conv-tail patterns, matched by the SAME code a Paddle-Lite tree runs as a mir pass
@@ -740,6 +741,42 @@ void GraphBuilder::Fuser::ShuffleTail() {
   }
 }
 
+// (L) a concat K left alone whose output a calib[fp32_to_int8] reads (L1), and / or max pools whose only reader is such a calib
+// (L2): the concat step writes the int8 copy itself, the pools run on it.  The one instruction runs where the concat ran; the
+// pools stay where they were, behind it.
+void GraphBuilder::Fuser::ConcatCalib() {
+  auto same_bits = [](float a, float b) { return memcmp(&a, &b, sizeof a) == 0; };
+  for (size_t i = 0; i < st.size(); ++i) {
+    if (dead[i] || !IsOp(static_cast<int>(i), "concat") || st[i].shuffle_tail || st[i].concat_int8) continue;
+    const std::string out = st[i].out;
+    const int d = FindByInput(StepKind::kCalibF2I, out, i + 1);
+    std::vector<std::pair<int, int>> pools;  // (pool, its calib)
+    for (size_t t = i + 1; t < st.size(); ++t) {
+      if (dead[t] || !IsOp(static_cast<int>(t), "pool2d") || st[t].pool_int8 || st[t].op_inputs.size() != 1 || st[t].op_inputs[0] != out) continue;
+      if (Op(t).pooling_type != "max" || Op(t).global_pooling) continue;
+      const int k = SoleReader(st[t].out);
+      if (k >= 0 && st[k].kind == StepKind::kCalibF2I) pools.emplace_back(static_cast<int>(t), k);
+    }
+    if (d < 0 && pools.empty()) continue;
+    const float scale = d >= 0 ? st[d].scale : st[pools[0].second].scale;
+    bool common = true;
+    for (auto& pk : pools) common = common && same_bits(st[pk.second].scale, scale);
+    if (d < 0 && !common) continue;  // no direct calib and no one scale for the int8 copy
+    st[i].concat_int8 = true;
+    st[i].calib_out = d >= 0 ? st[d].out : out + "/precision_trans";
+    st[i].calib_scale = scale;
+    if (d >= 0) dead[d] = true;
+    for (auto& pk : pools) {
+      if (!same_bits(st[pk.second].scale, scale)) continue;
+      st[pk.first].op_inputs[0] = st[i].calib_out;
+      st[pk.first].out = st[pk.second].out;
+      st[pk.first].pool_int8 = true;
+      dead[pk.second] = true;
+    }
+    st[i].drop_f32 = Uses(out) == 0;
+  }
+}
+
 // The rewrites in the one order that gives today's programs.  Each takes over steps that a later one would otherwise match:
 //   * I before H: H would take the image_to_tensor behind an image_resize (and its calib) and leave the resize a launch of its own.
 //   * H before F: F would take the calib behind an image_to_tensor into the stem alone, and the fp32 tensor would still be written.
@@ -749,8 +786,10 @@ void GraphBuilder::Fuser::ShuffleTail() {
 //   * D (with E) before G: G is for the pairs D left alone (pw_op still < 0); F between them touches calibs and stems only.
 //   * J2 and J1/J3 commute: J1/J3 take calibs that read a hard_swish / elementwise_mul, J2 the calib that reads a pool2d, and
 //     neither changes a use count the other tests.  J2 stays first, as the letters were added.
-//   * K last: it takes calibs that read a shuffle_channel or a split, which no other rewrite matches, and kills no step another
-//     rewrite looks at.
+//   * K behind every rewrite above: it takes calibs that read a shuffle_channel or a split, which none of them matches, and kills
+//     no step they look at.
+//   * L last: it is for the concats K left alone, and takes calibs that read a concat or a max pool behind one; C took the max
+//     pools behind a conv long before.
 void GraphBuilder::FuseSteps(std::vector<Step>* steps, const std::map<std::string, std::vector<int64_t>>& shapes) {
   Fuser f(*this, steps, shapes);
   f.ConvTails();
@@ -763,6 +802,7 @@ void GraphBuilder::FuseSteps(std::vector<Step>* steps, const std::map<std::strin
   if (fuse_hard_act_) f.SeGate();
   if (fuse_hard_act_) f.HardActCalib();
   if (fuse_shuffle_) f.ShuffleTail();
+  if (fuse_concat_) f.ConcatCalib();
   std::vector<Step> kept;
   for (size_t i = 0; i < steps->size(); ++i)
     if (!f.dead[i]) kept.push_back((*steps)[i]);
@@ -786,6 +826,14 @@ std::string GraphBuilder::OpLine(const Step& s) const {
     AppendNum(&l, "scale", s.calib_scale);
     if (s.shuffle_tail == 1 && s.drop_f32) l += " -f32";
     return l + " via=" + s.via + (s.shuffle_tail == 2 && s.drop_f32 ? "," + s.hi : "");
+  }
+  if (s.concat_int8) {  // (L): the concat step that took the calib over
+    std::string l = "concat/int8 in=";
+    for (size_t i = 0; i < s.op_inputs.size(); ++i) l += (i ? "," : "") + s.op_inputs[i];
+    l += " out=" + s.out + " +calib=" + s.calib_out;
+    AppendNum(&l, "scale", s.calib_scale);
+    if (s.drop_f32) l += " -f32";
+    return l + " axis=" + std::to_string(op.axis);
   }
   std::string l = op.type;
   if (op.enable_int8) {
@@ -929,6 +977,8 @@ void GraphBuilder::LowerOp(const Step& s, HipPredictor* pred) {
   } else if (s.shuffle_tail) {
     pred->AddShuffleUnit(s.op_inputs[0], s.op_inputs[1], s.shuffle_tail == 2 ? s.out : "", s.shuffle_tail == 2 ? s.hi : s.out, s.calib_out,
                          s.calib_scale, s.drop_f32);
+  } else if (s.concat_int8) {
+    pred->AddConcatCalib(s.op_inputs, s.out, op.axis, s.calib_out, s.calib_scale, s.drop_f32);
   } else if (op.type == "concat") {
     pred->AddConcat(s.op_inputs, s.out, op.axis);
   } else if (op.type == "split") {

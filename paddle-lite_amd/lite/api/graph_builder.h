@@ -114,6 +114,21 @@ class GraphBuilder {
   // are moved, the quantiser is calib's own).  DEFAULT ON: measured faster than the separate instructions by far more than the
   // run-to-run spread; no program without a concat changes.
   void set_fuse_shuffle(bool on) { fuse_shuffle_ = on; }
+  //   (L) a concat (any axis, any number of inputs) that K did not take.  D: the calib[fp32_to_int8] that reads its output (at most
+  //       one per variable).  P: every pool2d(max, not global) reader of that output whose own output only a calib[fp32_to_int8]
+  //       reads (so it is not fetched).
+  //   (L1) D exists => the concat step becomes ONE concat/int8 instruction (plhip_concat_calib_f32) that writes D's tensor at D's
+  //        scale; D disappears.
+  //   (L2) a pool of P whose calib has bitwise D's scale becomes an int8 max pool that reads the int8 copy and writes its calib's
+  //        tensor (max commutes with the monotonic quantiser, as in C); that calib disappears.  Without D, where every pool of P
+  //        shares one scale, the int8 copy is made at that scale as "<concat>/precision_trans".  Pools of another scale stay fp32
+  //        readers.
+  // The fp32 concat output is written only where a reader or a fetch is left.  An average pool, a global pool, a pool that is
+  // fetched or has a second reader, a concat that only fp32 ops read: the separate instructions stay.  With set_fuse(true) only,
+  // after K; bit-identical to the instructions it replaces (values are moved, the quantiser is calib's own).  No program without a
+  // concat that a calib or a max pool reads changes.  DEFAULT ON: measured faster than the separate instructions by far more than
+  // the run-to-run spread.
+  void set_fuse_concat(bool on) { fuse_concat_ = on; }
   GraphOp& Add(const std::string& type, const std::vector<std::string>& inputs, const std::string& output);
   // Emits the program into `pred`; returns the host-side names of the fetched variables ("<name>/host").
   std::vector<std::string> Lower(HipPredictor* pred);
@@ -137,6 +152,7 @@ class GraphBuilder {
                               // shuffled tensor), 2 = K1 (shuffle_channel/unit: `out` the split's first half, `hi` its second);
                               // calib_out / calib_scale / drop_f32 belong to the tensor the calib read, `via` the names no longer written
     std::string hi;
+    bool concat_int8{false};  // (L) a concat step that took the calib behind it over: concat/int8, calib_out / calib_scale / drop_f32
     // kHIP fusions (FuseSteps): tail taken over by an fp32_out conv, int8 max pool behind a fused calib
     std::string res;          // residual operand of the fused elementwise_add ("" = none)
     bool res_relu{false};
@@ -187,6 +203,7 @@ class GraphBuilder {
   bool fuse_dwconv_{false};
   bool fuse_hard_act_{false};
   bool fuse_shuffle_{true};
+  bool fuse_concat_{true};
   std::vector<FeedDesc> feeds_;
   std::vector<std::string> fetches_;
   std::vector<GraphOp> ops_;

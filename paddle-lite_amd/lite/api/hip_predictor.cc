@@ -2,6 +2,7 @@
 #include "lite/api/hip_predictor.h"
 
 #include "lite/kernels/hip/calib_tail.h"
+#include "lite/kernels/hip/concat_fusion.h"
 #include "lite/kernels/hip/conv_fusion.h"
 #include "lite/kernels/hip/image_frame.h"
 #include "lite/kernels/hip/se_gate_fusion.h"
@@ -411,6 +412,26 @@ void HipPredictor::AddShuffleUnit(const std::string& a, const std::string& b, co
   auto* sk = dynamic_cast<kernels::hip::HipShuffleFusionKernel*>(kernel.get());
   CHECK(sk) << "the picked shuffle_channel kernel does not take the shuffle fusion";
   sk->SetShuffleFusion(fz);
+  Emit(op, std::move(kernel));
+}
+
+void HipPredictor::AddConcatCalib(const std::vector<std::string>& inputs, const std::string& out, int axis, const std::string& calib_out,
+                                  float calib_scale, bool drop_fp32) {
+  CHECK(!calib_out.empty()) << "AddConcatCalib: the int8 tensor must be named";
+  auto op = std::make_shared<operators::ConcatOpLite>();
+  auto& p = op->mutable_param();
+  for (auto& in : inputs) p.x.push_back(Var(in));
+  p.output = Var(out);
+  p.axis = axis;
+  kernels::hip::HipConcatFusion fz;
+  fz.calib_output = Var(calib_out);
+  fz.calib_output->set_precision(PRECISION(kInt8));
+  fz.calib_scale = calib_scale;
+  fz.drop_fp32_output = drop_fp32;
+  auto kernel = PickKernel("concat", Place(TARGET(kHIP), PRECISION(kAny)), "int8");
+  auto* ck = dynamic_cast<kernels::hip::HipConcatFusionKernel*>(kernel.get());
+  CHECK(ck) << "the picked concat kernel does not take the concat fusion";
+  ck->SetConcatFusion(fz);
   Emit(op, std::move(kernel));
 }
 

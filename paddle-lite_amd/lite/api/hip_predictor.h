@@ -100,6 +100,10 @@ class HipPredictor {
   // concat / split / shuffle_channel, fp32 ops with the reference's attributes (lite/operators/op_params.h:369-386, 590-608,
   // 258-263).  AddSplit: num > 0 = equal parts, else `sections`, one per output.
   void AddConcat(const std::vector<std::string>& inputs, const std::string& out, int axis);
+  // fusion L (lite/kernels/hip/concat_fusion.h): concat -> calib[fp32_to_int8](calib_scale) in ONE launch, concat/int8.  `out` names
+  // the fp32 tensor, calib_out its int8 image; drop_fp32: `out` has no reader left and is not written (it carries the shape).
+  void AddConcatCalib(const std::vector<std::string>& inputs, const std::string& out, int axis, const std::string& calib_out,
+                      float calib_scale, bool drop_fp32);
   void AddSplit(const std::string& in, const std::vector<std::string>& outs, int axis, int num, const std::vector<int>& sections);
   void AddShuffleChannel(const std::string& in, const std::string& out, int group);
   // fusion K (lite/kernels/hip/shuffle_fusion.h): concat([a, b], axis 1) -> shuffle_channel(2) and what follows, ONE launch.

@@ -296,6 +296,13 @@ int pllite_add_shuffle_unit(pllite_predictor* p, const char* a, const char* b, c
                             float calib_scale, int drop_fp32) {
   return guarded([&] { p->pred.AddShuffleUnit(a, b, lo ? lo : "", hi ? hi : "", calib_out ? calib_out : "", calib_scale, drop_fp32 != 0); });
 }
+int pllite_add_concat_calib(pllite_predictor* p, const char* const* inputs, int n_inputs, const char* out, int axis, const char* calib_out,
+                            float calib_scale, int drop_fp32) {
+  return guarded([&] { p->pred.AddConcatCalib(names_of(inputs, n_inputs), out, axis, calib_out ? calib_out : "", calib_scale, drop_fp32 != 0); });
+}
+int pllite_graph_set_fuse_concat(pllite_predictor* p, int on) {
+  return guarded([&] { p->graph.set_fuse_concat(on != 0); });
+}
 int pllite_graph_softmax(pllite_predictor* p, const char* in, const char* out) {
   return guarded([&] { p->graph.Add("softmax", {in}, out); });
 }

@@ -53,6 +53,10 @@ int pllite_add_split(pllite_predictor* p, const char* in, const char* const* out
 int pllite_add_shuffle_channel(pllite_predictor* p, const char* in, const char* out, int group);
 int pllite_add_shuffle_unit(pllite_predictor* p, const char* a, const char* b, const char* lo, const char* hi, const char* calib_out,
                             float calib_scale, int drop_fp32);
+/* concat/int8 (lite/kernels/hip/concat_fusion.h): concat -> calib[fp32_to_int8](calib_scale) in one launch; `out` the fp32 tensor,
+ * calib_out its int8 image (required); drop_fp32: `out` is not written. */
+int pllite_add_concat_calib(pllite_predictor* p, const char* const* inputs, int n_inputs, const char* out, int axis, const char* calib_out,
+                            float calib_scale, int drop_fp32);
 
 /* ---- graph mode (lite/api/graph_builder.h): ops as the optimiser sees them after its fusion passes; kernel choice
  * (int8_out / fp32_out), io_copy and calib placement are decided by pllite_graph_lower() with the reference's rules.
@@ -96,6 +100,9 @@ int pllite_graph_shuffle_channel(pllite_predictor* p, const char* in, const char
 /* fusion K (concat -> shuffle_channel(2) -> [split ->] calib in one launch): on by default, effective with
  * pllite_graph_set_fuse(1) only; 0 keeps the separate instructions */
 int pllite_graph_set_fuse_shuffle(pllite_predictor* p, int on);
+/* fusion L (concat -> calib in one launch, the int8 max pool behind a concat): on by default, effective with
+ * pllite_graph_set_fuse(1) only; 0 keeps the separate instructions */
+int pllite_graph_set_fuse_concat(pllite_predictor* p, int on);
 int pllite_graph_fetch(pllite_predictor* p, const char* name);
 /* kHIP graph-level fusions (graph_builder.h set_fuse): on by default; 0 = the reference program instruction for instruction. */
 int pllite_graph_set_fuse(pllite_predictor* p, int on);

@@ -4,10 +4,14 @@
 //   shuffle_channel  lite/kernels/arm/shuffle_channel_compute.cc -> lite/backends/arm/math/shuffle_channel.cc:24-55
 // Alias def: the reference's op.  Aliases int8 / unit (shuffle_channel): the products of the graph builder's fusion K, the
 // tail of a ShuffleNetV2 unit in one launch (shuffle_fusion.h), bit-identical to the instructions they replace.
+// concat, alias int8: the product of fusion L, concat -> calib[fp32_to_int8] in one launch (concat_fusion.h).  It reads fp32 and
+// writes int8 (and fp32 where that still has a reader), so it is registered at kAny precision: concat/def stays the one kernel a
+// pick at kFloat finds.
 // Every class reads its dims in Run: a resized feed needs no new lowering.
 #include <vector>
 
 #include "lite/core/op_registry.h"
+#include "lite/kernels/hip/concat_fusion.h"
 #include "lite/kernels/hip/shuffle_fusion.h"
 #include "lite/operators/op_params.h"
 #include "plhip.h"
@@ -50,6 +54,37 @@ class ConcatCompute : public KernelLite<TARGET(kHIP), PRECISION(kFloat)> {
                                          param.output->mutable_data<float>(TARGET(kHIP))));
   }
   void SetProfileRuntimeKernelInfo(profile::OpCharacter* ch) override { ch->kernel_func_name = "concat_hip"; }
+};
+
+// concat that took the calib[fp32_to_int8] behind it over (fusion L): one launch of plhip_concat_calib_f32 per 8 operands
+class ConcatCalibCompute : public KernelLite<TARGET(kHIP), PRECISION(kAny)>, public HipConcatFusionKernel {
+ public:
+  void SetConcatFusion(const HipConcatFusion& f) override { fusion_ = f; }
+  void Run() override {
+    auto& param = this->Param<operators::ConcatParam>();
+    auto& ctx = this->ctx_->As<HIPContext>();
+    CHECK(!param.x.empty() && param.output) << "concat/int8: inputs / output must be set";
+    CHECK(fusion_.calib_output) << "concat/int8 needs the fusion state the graph builder attaches (concat_fusion.h)";
+    const AxisSplit s = SplitAtAxis(param.x[0]->dims(), param.axis, "concat/int8");
+    std::vector<const float*> xs;
+    std::vector<int64_t> extents;
+    for (auto* t : param.x) {
+      CHECK(t->target() == TARGET(kHIP)) << "concat/int8: every input must live on the HIP device";
+      xs.push_back(t->data<float>());
+      extents.push_back(t->dims()[s.axis]);
+    }
+    fusion_.calib_output->Resize(param.output->dims());
+    int8_t* q = fusion_.calib_output->mutable_data<int8_t>(TARGET(kHIP));
+    float* y = fusion_.drop_fp32_output ? nullptr : param.output->mutable_data<float>(TARGET(kHIP));
+    HIP_CALL(ctx.ctx(), plhip_concat_calib_f32(ctx.ctx(), xs.data(), extents.data(), static_cast<int>(xs.size()), s.outer, s.inner, y, q,
+                                               fusion_.calib_scale));
+  }
+  void SetProfileRuntimeKernelInfo(profile::OpCharacter* ch) override {
+    ch->kernel_func_name = fusion_.drop_fp32_output ? "concat_int8_hip" : "concat_fp32_int8_hip";
+  }
+
+ private:
+  HipConcatFusion fusion_;
 };
 
 class SplitCompute : public KernelLite<TARGET(kHIP), PRECISION(kFloat)> {
@@ -144,6 +179,10 @@ class ShuffleTailCompute : public KernelLite<TARGET(kHIP), PRECISION(kFloat)>, p
 }  // namespace paddle
 
 REGISTER_LITE_KERNEL(concat, kHIP, kFloat, kNCHW, paddle::lite::kernels::hip::ConcatCompute, def)
+    .BindInput("X", {LiteType::GetTensorTy(TARGET(kHIP))})
+    .BindOutput("Out", {LiteType::GetTensorTy(TARGET(kHIP))})
+    .Finalize();
+REGISTER_LITE_KERNEL(concat, kHIP, kAny, kNCHW, paddle::lite::kernels::hip::ConcatCalibCompute, int8)
     .BindInput("X", {LiteType::GetTensorTy(TARGET(kHIP))})
     .BindOutput("Out", {LiteType::GetTensorTy(TARGET(kHIP))})
     .Finalize();

@@ -73,6 +73,8 @@ def load():
     L.pllite_add_split.argtypes = [vp, cs, C.POINTER(cs), i32, i32, i32, C.POINTER(i32), i32]
     L.pllite_add_shuffle_channel.argtypes = [vp, cs, cs, i32]
     L.pllite_add_shuffle_unit.argtypes = [vp, cs, cs, cs, cs, cs, f32, i32]
+    L.pllite_add_concat_calib.argtypes = [vp, C.POINTER(cs), i32, cs, i32, cs, f32, i32]
+    L.pllite_graph_set_fuse_concat.argtypes = [vp, i32]
     L.pllite_graph_fetch.argtypes = [vp, cs]
     L.pllite_graph_set_fuse.argtypes = [vp, i32]
     L.pllite_graph_set_fuse_dwpw.argtypes = [vp, i32]
@@ -199,6 +201,12 @@ class Predictor:
     def add_concat(self, srcs, dst, axis=1):
         self._ck(self.L.pllite_add_concat(self.h, _names(srcs), len(srcs), dst.encode(), int(axis)))
 
+    def add_concat_calib(self, srcs, dst, axis, calib_out, calib_scale, drop_fp32=False):
+        """concat -> calib[fp32_to_int8] in one launch (concat/int8): dst the fp32 tensor, calib_out its int8 image; drop_fp32: dst
+        is not written."""
+        self._ck(self.L.pllite_add_concat_calib(self.h, _names(srcs), len(srcs), dst.encode(), int(axis), calib_out.encode(),
+                                                calib_scale, int(drop_fp32)))
+
     def add_split(self, src, dsts, axis=1, num=0, sections=()):
         """num > 0: equal parts; else one section per output."""
         self._ck(self.L.pllite_add_split(self.h, src.encode(), _names(dsts), len(dsts), int(axis), int(num), _ia(sections), len(sections)))
@@ -292,6 +300,11 @@ class Predictor:
         """Fusion K (default on; with graph_set_fuse(True) only): concat -> shuffle_channel(2) -> split -> calib becomes one
         shuffle_channel/unit instruction (K1), concat -> shuffle_channel(2) -> calib one shuffle_channel/int8 instruction (K2)."""
         self._ck(self.L.pllite_graph_set_fuse_shuffle(self.h, int(on)))
+
+    def graph_set_fuse_concat(self, on):
+        """Fusion L (default on; with graph_set_fuse(True) only): a concat takes the calib[fp32_to_int8] that reads it over (concat/int8, L1), and a
+        max pool behind the concat whose only reader is a calib of the same scale becomes an int8 max pool on the int8 copy (L2)."""
+        self._ck(self.L.pllite_graph_set_fuse_concat(self.h, int(on)))
 
     def graph_set_fuse_hard_act(self, on):
         """Fusions J1 / J2 / J3 (default off; with graph_set_fuse(True) only): hard_swish / elementwise_mul take the calib[fp32_to_int8]

@@ -430,6 +430,82 @@ def shufflenet_v2_net(scale=1.0, seed=55, res=224, num_classes=NUM_CLASSES):
     return _finish(g, res, x)
 
 
+# SqueezeNet v1.1 (Iandola et al. 2016, the v1.1 revision: pools behind conv1, fire3 and fire5): (squeeze, expand) widths of fire2..9
+SQUEEZENET_V1_1_FIRES = [(16, 64), (16, 64), (32, 128), (32, 128), (48, 192), (48, 192), (64, 256), (64, 256)]
+
+
+def _spread(g, name, f):
+    """The int8 spread the readers of `name` are sized by is f times what the rule for independent taps gave it."""
+    g.sig_i8[name] *= f
+    return name
+
+
+def squeezenet_v1_1_net(seed=56, res=224, num_classes=NUM_CLASSES):
+    """SqueezeNet v1.1 as the reference's optimiser leaves it: relu fused into the int8 convs, concat and pool2d fp32 ops.  A fire
+    module is a squeeze 1x1 conv, then an expand 1x1 and an expand 3x3 (pad 1) conv on it, and the concat of the two.  A max pool
+    and a concat of relu tensors spread wider than the sizing rule for independent taps says (checked on the oracle,
+    tests/test_squeezenet_host.py, against MobileNetV2's worst tensor): the spread a reader is sized by is corrected, 1.6 times for
+    a max pool output, 1.4 times for a concat output and for a squeeze conv output, as shufflenet_v2_net does for its depthwise
+    outputs.  The global average pool's output is [N, classes, 1, 1] and softmax runs along the last axis, as everywhere in this
+    project: the tensor that carries the network's result is pool10."""
+    g = _NetGen(seed)
+    g.tensor("image", 3, res, res, 1.0 / 127, 73.0)
+    x = g.conv("conv1", "image", 64, 3, 2, 1, act=1)
+    x = _spread(g, g.pool("pool1", x, "max", 3, 2, 0), 1.6)
+    for i, (sq, ex) in enumerate(SQUEEZENET_V1_1_FIRES):
+        p = "fire%d" % (i + 2)
+        s = _spread(g, g.conv(p + "_squeeze", x, sq, 1, 1, 0, act=1), 1.4)
+        a = g.conv(p + "_expand1x1", s, ex, 1, 1, 0, act=1)
+        b = g.conv(p + "_expand3x3", s, ex, 3, 1, 1, act=1)
+        x = _spread(g, g.concat(p + "_concat", [a, b], 1), 1.4)
+        if p in ("fire3", "fire5"):
+            x = _spread(g, g.pool("pool%d" % (i + 2), x, "max", 3, 2, 0), 1.6)
+    x = g.conv("conv10", x, num_classes, 1, 1, 0, act=1)
+    x = g.pool("pool10", x, "avg", g.shape[x][1], 1, 0, global_pooling=True)
+    x = g.softmax("prob", x)
+    return _finish(g, res, x)
+
+
+# (1x1, 3x3 reduce, 3x3, 5x5 reduce, 5x5, pool projection) channels of the two blocks of inception_mini_net
+INCEPTION_MINI_BLOCKS = [(16, 24, 32, 4, 8, 8), (32, 32, 48, 8, 24, 16)]
+
+
+def inception_mini_net(seed=57, res=64, num_classes=10):
+    """Two GoogLeNet-style blocks (Szegedy et al. 2014) behind a two-conv stem: branches 1x1 | 1x1 -> 3x3 | 1x1 -> 5x5 | max pool
+    3x3 s1 -> 1x1, every conv with relu, and the concat of the four.  The smallest network with a four-operand concat, and with a
+    max pool that reads a concat beside int8 convs that read it through one calib.  Sizing: the spread corrections of
+    squeezenet_v1_1_net; the narrow 5x5 reduce conv as shufflenet_v2_net's first 1x1 conv of a branch; a 3x3 stride-1 max pool
+    spreads one saturated value over nine windows, so a block's input is quantised over a range 1.5 times wider."""
+    g = _NetGen(seed)
+    g.tensor("image", 3, res, res, 1.0 / 127, 73.0)
+    x = g.conv("conv1", "image", 32, 3, 2, 1, act=1)
+    x = g.conv("conv2", x, 64, 3, 1, 1, act=1)
+    for bi, (c1, r3, c3, r5, c5, cp) in enumerate(INCEPTION_MINI_BLOCKS):
+        p = "inc%d" % (bi + 1)
+        g.widen(x, 1.5)
+        b1 = g.conv(p + "_1x1", x, c1, 1, 1, 0, act=1)
+        b3 = g.conv(p + "_3x3", g.conv(p + "_3x3_reduce", x, r3, 1, 1, 0, act=1), c3, 3, 1, 1, act=1)
+        b5 = g.conv(p + "_5x5", g.conv(p + "_5x5_reduce", x, r5, 1, 1, 0, act=1, headroom=1.6, bias_shift=0.25), c5, 5, 1, 2, act=1)
+        bp = g.conv(p + "_pool_proj", _spread(g, g.pool(p + "_pool", x, "max", 3, 1, 1), 1.6), cp, 1, 1, 0, act=1)
+        x = _spread(g, g.concat(p + "_concat", [b1, b3, b5, bp], 1), 1.4)
+    x = g.pool("pool", x, "avg", g.shape[x][1], 1, 0, global_pooling=True)
+    x = g.fc("fc", x, num_classes)
+    x = g.softmax("prob", x)
+    return _finish(g, res, x)
+
+
+def concat_calib_bytes(net, batch):
+    """Algorithmic bytes of every concat that a calib reads directly or through a max pool, as separate concat and calib
+    instructions (17 per concatenated element: 4 + 4 for the move, 4 + 4 + 1 for the calib; counted where the calib reads the pool
+    as if it read the concat) and as the one fused launch (9: the operands once, the int8 tensor once).  Counts, not measurements."""
+    n = 0
+    for o in net["ops"]:
+        if o["op"] == "concat":
+            c, h, w = net["shapes"][o["name"]]
+            n += c * h * w * batch
+    return 17 * n, 9 * n
+
+
 def shuffle_unit_bytes(net, batch):
     """Algorithmic bytes of the data movement of every stride-1 unit tail (split, calib of the second half, concat, shuffle_channel)
     as separate instructions, and of the one fused launch: (53 h P, 13 h P) summed over the units, h the half width and P the
@@ -484,7 +560,8 @@ def net_stats(net):
     return macs
 
 
-def emit_graph(pred, net, batch, fuse=True, fuse_dwpw=None, fuse_dwconv=None, image=None, frame=None, fuse_hard_act=None, fuse_shuffle=None):
+def emit_graph(pred, net, batch, fuse=True, fuse_dwpw=None, fuse_dwconv=None, image=None, frame=None, fuse_hard_act=None, fuse_shuffle=None,
+               fuse_concat=None):
     """Feed the op list to the predictor's graph mode and lower it.  Returns the host name of the output variable.
     image: None = the input is the normalised fp32 NCHW tensor; dict(format, means, scales) = the input is a decoded uint8 image
     [batch, h, w, cs] of that format (liteapi.IMG_*), normalised on the device (Predictor.graph_feed_image).
@@ -498,7 +575,9 @@ def emit_graph(pred, net, batch, fuse=True, fuse_dwpw=None, fuse_dwconv=None, im
     fuse_hard_act: None = the builder's default (off); True = fusions J1 / J2 / J3 of the MobileNetV3 ops (hard_swish and
     elementwise_mul take the calib behind them over, the excite chain becomes one hard_sigmoid/se_gate instruction).
     fuse_shuffle: None = the builder's default (on); fusion K of the ShuffleNetV2 ops (concat -> shuffle_channel(2) ->
-    [split ->] calib becomes one shuffle_channel/unit or shuffle_channel/int8 instruction), False = the separate instructions."""
+    [split ->] calib becomes one shuffle_channel/unit or shuffle_channel/int8 instruction), False = the separate instructions.
+    fuse_concat: None = the builder's default (on); fusion L of the fire / inception modules (a concat takes the calib that reads it
+    over, concat/int8; a max pool behind it runs on the int8 copy), False = the separate instructions."""
     from . import liteapi
     pred.graph_set_fuse(fuse)
     if fuse_dwpw is not None:
@@ -509,6 +588,8 @@ def emit_graph(pred, net, batch, fuse=True, fuse_dwpw=None, fuse_dwconv=None, im
         pred.graph_set_fuse_hard_act(fuse_hard_act)
     if fuse_shuffle is not None:
         pred.graph_set_fuse_shuffle(fuse_shuffle)
+    if fuse_concat is not None:
+        pred.graph_set_fuse_concat(fuse_concat)
     c, h, w = net["input_shape"]
     if frame is not None:
         assert image is None, "emit_graph: image= and frame= exclude each other"
