@@ -393,6 +393,40 @@ plhip_status plhip_shuffle_channel_f32(plhip_ctx* ctx, const float* x, int n, in
 plhip_status plhip_shuffle_unit_f32(plhip_ctx* ctx, const float* a, const float* b, int n, int h, int hw, int split_at,
                                     float* lo_f32, float* hi_f32, int8_t* hi_i8, float calib_scale);
 
+/* ---- dense prediction (interp_ops.hip): bilinear_interp / nearest_interp of fp32 NCHW planes, arg_max along an axis, and
+ * interp -> arg_max(axis 1) in one launch.  Replaces lite/backends/arm/math/interpolate.cc:65-463 (bilinear), :465-499 (nearest)
+ * and argmax.cc:29-61.  Per axis, with `in`, `out` and output index l, every operation one rounded fp32 operation (no FMA):
+ *   ratio     align_corners ? (out > 1 ? float(in - 1) / float(out - 1) : 0.f) : float(in) / float(out)
+ *   bilinear  f = float(l) * ratio                                with align_corners, and with align_mode 1 without
+ *             f = max(ratio * (float(l) + 0.5f) - 0.5f, 0.f)      with align_mode 0 without align_corners
+ *             i0 = min((int)f, in - 1), i1 = min(i0 + 1, in - 1), w1 = f - float(i0), w0 = 1.f - w1
+ *             r0 = x[y0][x0] * a0 + x[y0][x1] * a1, r1 = x[y1][x0] * a0 + x[y1][x1] * a1, y = r0 * b0 + r1 * b1
+ *   nearest   i = min((int)(double(ratio * float(l)) + 0.5), in - 1) with align_corners (a double addition),
+ *             i = min((int)(ratio * float(l)), in - 1) without; align_mode is not read
+ *   in == out on both axes copies the bits, whatever the method.
+ * Refused before any launch, each with a text of its own: a NULL ctx, input or output; a dimension < 1; in_h, in_w, out_h, out_w
+ * or c above 2^15; a method other than the two below, an align_corners or align_mode other than 0 / 1; with y_i8 a calib_scale
+ * that is not a positive finite number; a dtype other than -1, 2, 3; more than 2^40 input or output elements.  No call copies
+ * tables to the device or synchronises: all three may be captured by plhip_graph_begin. */
+typedef enum { PLHIP_INTERP_BILINEAR = 0, PLHIP_INTERP_NEAREST = 1 } plhip_interp_method;
+/* x [planes][in_h][in_w] (planes = N * C) -> y_f32 and / or y_i8 [planes][out_h][out_w]; at least one.  y_i8 is the quantiser of
+ * plhip_calib_f32_to_i8 applied to the fp32 value, round_sat_i8((1.f / calib_scale) * v): byte for byte what this call with
+ * y_f32 followed by plhip_calib_f32_to_i8 write.  A lane owns 4 consecutive outputs of a row (16-byte fp32 and 4-byte int8
+ * stores) where out_w is a multiple of 4, y_f32 is 16-byte and y_i8 4-byte aligned; else one output. */
+plhip_status plhip_interp_f32(plhip_ctx* ctx, const float* x, int64_t planes, int in_h, int in_w, int out_h, int out_w, int method,
+                              int align_corners, int align_mode, float* y_f32, int8_t* y_i8, float calib_scale);
+/* x [outer][c][inner] -> y [outer][inner], the index of the maximum along c; among equal maxima the LARGEST index (the reference
+ * sorts (value, index) pairs with std::greater).  dtype -1 or 3: int64 labels, 2: int32.  A NaN never replaces the running
+ * maximum, so the result is always in [0, c).  Quads of inner positions per lane where inner is a multiple of 4 and x, y are
+ * 16-byte aligned. */
+plhip_status plhip_arg_max_f32(plhip_ctx* ctx, const float* x, int64_t outer, int c, int64_t inner, void* y, int dtype);
+/* x [n][c][in_h][in_w] -> y [n][out_h][out_w]: plhip_arg_max_f32 (axis 1) of plhip_interp_f32's output, which is never written.
+ * The resampled values come from the device function plhip_interp_f32 uses and the comparison from plhip_arg_max_f32's, so the
+ * labels equal the two calls' exactly.  A block stages the source tile of all c channels of its 32 x 32 output tile in LDS where
+ * it fits 64 KB, and reads global memory otherwise. */
+plhip_status plhip_interp_argmax_f32(plhip_ctx* ctx, const float* x, int n, int c, int in_h, int in_w, int out_h, int out_w,
+                                     int method, int align_corners, int align_mode, void* y, int dtype);
+
 /* ---- introspection used by tests: operand-layout self-check of the MFMA tile on this device.
  * Runs a tiny known-answer GEMM through the MFMA path; returns PLHIP_OK iff bit-exact. ---- */
 plhip_status plhip_selftest(plhip_ctx* ctx);

@@ -34,12 +34,18 @@ EXPORTS = [
     "plhip_se_gate_supported", "plhip_se_gate_packed_weight_bytes", "plhip_pack_se_gate_weights", "plhip_se_gate_int8",
     "plhip_concat_f32", "plhip_split_f32", "plhip_shuffle_channel_f32", "plhip_shuffle_unit_f32",
     "plhip_concat_calib_f32",
+    "plhip_interp_f32", "plhip_arg_max_f32", "plhip_interp_argmax_f32",
 ]
 
 # plhip_hard_act_kind, and the reference's default parameters (lite/operators/op_params.h:406-412)
 HARD_SWISH, HARD_SIGMOID = 0, 1
 HARD_SWISH_DEFAULTS = (6.0, 6.0, 3.0)   # threshold, scale, offset
 HARD_SIGMOID_DEFAULTS = (0.2, 0.5)      # slope, offset
+
+# plhip_interp_method; the arg_max output dtypes (ArgmaxParam::dtype: -1 and 3 are int64, 2 is int32)
+INTERP_BILINEAR, INTERP_NEAREST = 0, 1
+INTERP_METHODS = {"bilinear": INTERP_BILINEAR, "nearest": INTERP_NEAREST}
+ARGMAX_DTYPES = {-1: np.int64, 3: np.int64, 2: np.int32}
 
 # plhip_image_format == cv::ImageFormat (lite/utils/cv/paddle_image_preprocess.h)
 IMG_RGBA, IMG_BGRA, IMG_RGB, IMG_BGR, IMG_GRAY = 0, 1, 2, 3, 4
@@ -264,6 +270,9 @@ def load():
     L.plhip_split_f32.argtypes = [vp, vp, C.c_int64, C.c_int64, C.c_int64, i32, C.POINTER(C.c_int64), i32, C.POINTER(vp)]
     L.plhip_shuffle_channel_f32.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, f32]
     L.plhip_shuffle_unit_f32.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, f32]
+    L.plhip_interp_f32.argtypes = [vp, vp, C.c_int64, i32, i32, i32, i32, i32, i32, i32, vp, vp, f32]
+    L.plhip_arg_max_f32.argtypes = [vp, vp, C.c_int64, i32, C.c_int64, vp, i32]
+    L.plhip_interp_argmax_f32.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32]
     L.plhip_selftest.argtypes = [vp]
     _lib = L
     return L
@@ -811,3 +820,49 @@ class Context:
         for p in (abuf, bbuf) + tuple(q[0] for q in (lo, hf, hq) if q):
             self.free(p)
         return r
+
+    # ---- bilinear_interp / nearest_interp / arg_max and interp -> arg_max in one launch (interp_ops.hip)
+    def interp(self, x, out_hw, method="bilinear", align_corners=False, align_mode=1, mode="f32", calib_scale=1.0, misalign=0):
+        """plhip_interp_f32: x [..., h, w] fp32 resampled to out_hw.  Returns (y_f32 or None, y_i8 or None); mode names the outputs
+        ("f32", "i8", "both"); misalign: elements every device base is moved off its allocation's alignment."""
+        x = np.ascontiguousarray(x, np.float32)
+        ih, iw = x.shape[-2:]
+        oh, ow = (int(v) for v in out_hw)
+        planes = int(np.prod(x.shape[:-2], dtype=np.int64))
+
+        def call(dx, dyf, dyq):
+            self.check(self.L.plhip_interp_f32(self.h, dx, planes, ih, iw, oh, ow, INTERP_METHODS[method], int(align_corners),
+                                               int(align_mode), dyf, dyq, float(calib_scale)), "interp")
+        return self._two_outputs(call, x, tuple(x.shape[:-2]) + (oh, ow), mode, calib_scale, misalign)
+
+    def arg_max(self, x, axis, dtype=-1, keepdims=False, misalign=0):
+        """plhip_arg_max_f32 along `axis` of an fp32 array; dtype as ArgmaxParam's (-1 / 3 int64, 2 int32)."""
+        x = np.ascontiguousarray(x, np.float32)
+        axis = axis + x.ndim if axis < 0 else axis
+        outer = int(np.prod(x.shape[:axis], dtype=np.int64))
+        inner = int(np.prod(x.shape[axis + 1:], dtype=np.int64))
+        np_t = ARGMAX_DTYPES[dtype]
+        esz = np.dtype(np_t).itemsize
+        xbuf, dx = self._up_f32(x, misalign)
+        ybuf, dy = self._out_buf(outer * inner, esz, misalign)
+        try:
+            self.check(self.L.plhip_arg_max_f32(self.h, dx, outer, x.shape[axis], inner, dy, int(dtype)), "arg_max")
+            shape = x.shape[:axis] + ((1,) if keepdims else ()) + x.shape[axis + 1:]
+            return self.to_host(dy, shape, np_t)
+        finally:
+            self.free(xbuf), self.free(ybuf)
+
+    def interp_argmax(self, x, out_hw, method="bilinear", align_corners=False, align_mode=1, dtype=-1, misalign=0):
+        """plhip_interp_argmax_f32: x [n, c, h, w] fp32 -> labels [n, oh, ow] of the resampled tensor, which is never written."""
+        x = np.ascontiguousarray(x, np.float32)
+        n, c, ih, iw = x.shape
+        oh, ow = (int(v) for v in out_hw)
+        np_t = ARGMAX_DTYPES[dtype]
+        xbuf, dx = self._up_f32(x, misalign)
+        ybuf, dy = self._out_buf(n * oh * ow, np.dtype(np_t).itemsize, misalign)
+        try:
+            self.check(self.L.plhip_interp_argmax_f32(self.h, dx, n, c, ih, iw, oh, ow, INTERP_METHODS[method], int(align_corners),
+                                                      int(align_mode), dy, int(dtype)), "interp_argmax")
+            return self.to_host(dy, (n, oh, ow), np_t)
+        finally:
+            self.free(xbuf), self.free(ybuf)

@@ -1,5 +1,5 @@
 // plhip_capi_ops.hip — the C ABI (include/plhip.h), part 4 of 4: fc, calib, pooling, softmax, elementwise add, the hard activations,
-// squeeze-excite, and concat / split / shuffle_channel.  Argument validation and one launch each.
+// squeeze-excite, concat / split / shuffle_channel, and interp / arg_max.  Argument validation and one launch each.
 #include "plhip_capi.h"
 
 #include <vector>
@@ -237,6 +237,71 @@ plhip_status plhip_shuffle_unit_f32(plhip_ctx* ctx, const float* a, const float*
   if (hi_i8 && !(calib_scale > 0.f)) return fail(ctx, PLHIP_ERR_INVALID, "plhip_shuffle_unit_f32: int8 output needs a positive calib scale");
   plhip::launch_shuffle_unit(a, b, lo_f32, hi_f32, hi_i8, calib_scale, n, h, hw, split_at, ctx->stream);
   LAUNCHCHK(ctx, "shuffle_unit");
+  return PLHIP_OK;
+}
+
+// ------------------------------------------------------------------ bilinear_interp / nearest_interp / arg_max
+// the checks the three entry points share, in one order; planes_in / planes_out: how many planes of in_h x in_w are read and of
+// out_h x out_w written (arg_max over c channels writes one plane per image)
+static plhip_status interp_check(plhip_ctx* ctx, const char* who, const void* x, int64_t planes_in, int64_t planes_out, int in_h, int in_w,
+                                 int out_h, int out_w, int method, int align_corners, int align_mode) {
+  const int cap = 1 << 15;
+  if (!ctx || !x) return fail(ctx, PLHIP_ERR_INVALID, "%s: null ctx or x", who);
+  if (planes_in < 1 || planes_out < 1 || in_h < 1 || in_w < 1 || out_h < 1 || out_w < 1)
+    return fail(ctx, PLHIP_ERR_INVALID, "%s: every dimension must be at least 1", who);
+  if (in_h > cap || in_w > cap || out_h > cap || out_w > cap) return fail(ctx, PLHIP_ERR_UNSUPPORTED, "%s: a dimension above 2^15", who);
+  if (method != PLHIP_INTERP_BILINEAR && method != PLHIP_INTERP_NEAREST) return fail(ctx, PLHIP_ERR_UNSUPPORTED, "%s: unknown method", who);
+  if ((align_corners != 0 && align_corners != 1) || (align_mode != 0 && align_mode != 1))
+    return fail(ctx, PLHIP_ERR_UNSUPPORTED, "%s: unknown align_corners or align_mode", who);
+  const int64_t most = (int64_t)1 << 40;
+  if (planes_in > most / ((int64_t)in_h * in_w) || planes_out > most / ((int64_t)out_h * out_w))
+    return fail(ctx, PLHIP_ERR_UNSUPPORTED, "%s: more than 2^40 elements", who);
+  return PLHIP_OK;
+}
+
+// dtype of an arg_max output (ArgmaxParam::dtype): -1 and 3 int64, 2 int32; -1: neither
+static int label_is_i64(int dtype) { return dtype == -1 || dtype == 3 ? 1 : dtype == 2 ? 0 : -1; }
+
+plhip_status plhip_interp_f32(plhip_ctx* ctx, const float* x, int64_t planes, int in_h, int in_w, int out_h, int out_w, int method,
+                              int align_corners, int align_mode, float* y_f32, int8_t* y_i8, float calib_scale) {
+  const char* who = "plhip_interp_f32";
+  if (plhip_status st = interp_check(ctx, who, x, planes, planes, in_h, in_w, out_h, out_w, method, align_corners, align_mode)) return st;
+  if (!y_f32 && !y_i8) return fail(ctx, PLHIP_ERR_INVALID, "%s: null y_f32 and y_i8, one output is required", who);
+  if (y_i8 && (!(calib_scale > 0.f) || !(calib_scale <= 3.402823466e38f)))
+    return fail(ctx, PLHIP_ERR_INVALID, "%s: calib_scale must be a positive finite number", who);
+  plhip::launch_interp(plhip::interp_args(x, in_h, in_w, out_h, out_w, method, align_corners, align_mode), planes, y_f32, y_i8,
+                       calib_scale, ctx->stream);
+  LAUNCHCHK(ctx, "interp");
+  return PLHIP_OK;
+}
+
+plhip_status plhip_arg_max_f32(plhip_ctx* ctx, const float* x, int64_t outer, int c, int64_t inner, void* y, int dtype) {
+  const char* who = "plhip_arg_max_f32";
+  if (!ctx || !x || !y) return fail(ctx, PLHIP_ERR_INVALID, "%s: null ctx, x or y", who);
+  if (outer < 1 || c < 1 || inner < 1) return fail(ctx, PLHIP_ERR_INVALID, "%s: every dimension must be at least 1", who);
+  if (c > (1 << 15)) return fail(ctx, PLHIP_ERR_UNSUPPORTED, "%s: a dimension above 2^15 (the axis)", who);
+  const int i64 = label_is_i64(dtype);
+  if (i64 < 0) return fail(ctx, PLHIP_ERR_UNSUPPORTED, "%s: dtype must be -1 or 3 (int64) or 2 (int32)", who);
+  const int64_t most = (int64_t)1 << 40;
+  if (outer > most || inner > most || inner > most / c || outer > most / (inner * c))
+    return fail(ctx, PLHIP_ERR_UNSUPPORTED, "%s: more than 2^40 elements", who);
+  plhip::launch_arg_max(x, outer, c, inner, y, i64, ctx->stream);
+  LAUNCHCHK(ctx, "arg_max");
+  return PLHIP_OK;
+}
+
+plhip_status plhip_interp_argmax_f32(plhip_ctx* ctx, const float* x, int n, int c, int in_h, int in_w, int out_h, int out_w, int method,
+                                     int align_corners, int align_mode, void* y, int dtype) {
+  const char* who = "plhip_interp_argmax_f32";
+  if (n < 1 || c < 1) return fail(ctx, PLHIP_ERR_INVALID, "%s: every dimension must be at least 1", who);
+  if (c > (1 << 15)) return fail(ctx, PLHIP_ERR_UNSUPPORTED, "%s: a dimension above 2^15", who);
+  if (plhip_status st = interp_check(ctx, who, x, (int64_t)n * c, n, in_h, in_w, out_h, out_w, method, align_corners, align_mode)) return st;
+  if (!y) return fail(ctx, PLHIP_ERR_INVALID, "%s: null y", who);
+  const int i64 = label_is_i64(dtype);
+  if (i64 < 0) return fail(ctx, PLHIP_ERR_UNSUPPORTED, "%s: dtype must be -1 or 3 (int64) or 2 (int32)", who);
+  if ((int64_t)n * c > ((int64_t)1 << 40) / ((int64_t)out_h * out_w)) return fail(ctx, PLHIP_ERR_UNSUPPORTED, "%s: more than 2^40 elements", who);
+  plhip::launch_interp_argmax(plhip::interp_args(x, in_h, in_w, out_h, out_w, method, align_corners, align_mode), n, c, y, i64, ctx->stream);
+  LAUNCHCHK(ctx, "interp_argmax");
   return PLHIP_OK;
 }
 

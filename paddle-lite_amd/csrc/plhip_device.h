@@ -82,6 +82,11 @@ __device__ __forceinline__ uint32_t pack4_i8(int q0, int q1, int q2, int q3) {
   return lo | hi;
 }
 
+// calib_f32_to_i8_kernel's quantiser on a quad: four int8 in one dword (shuffle_ops.hip, interp_ops.hip)
+__device__ __forceinline__ uint32_t calib4_i8(const v4f& v, float inv) {
+  return pack4_i8(round_sat_i8(inv * v[0]), round_sat_i8(inv * v[1]), round_sat_i8(inv * v[2]), round_sat_i8(inv * v[3]));
+}
+
 // 4x4 byte transpose: in r0..r3 (row j holds bytes for columns 0..3), out o[i] holds column i's
 // bytes for rows 0..3 (row 0 in the low byte).  8 v_perm_b32.
 __device__ __forceinline__ void transpose4x4_b8(uint32_t r0, uint32_t r1, uint32_t r2, uint32_t r3,

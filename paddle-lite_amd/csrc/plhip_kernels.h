@@ -458,4 +458,22 @@ void launch_shuffle_channel(const float* x, float* yf, int8_t* yq, float calib_s
 void launch_shuffle_unit(const float* a, const float* b, float* lo, float* hf, int8_t* hq, float calib_scale, int n, int h, int hw,
                          int split_at, hipStream_t s);
 
+// bilinear_interp / nearest_interp of fp32 NCHW planes, arg_max along an axis, and interp -> arg_max(axis 1) in one launch: interp_ops.hip
+struct InterpArgs {
+  const float* x;   // [planes][ih][iw]
+  int ih, iw, oh, ow;
+  float ry, rx;     // the source step per output index of each axis (an fp32 division, done on the host)
+  int bilinear;     // 0: one source pixel (nearest_interp, and the copy that in == out on both axes is)
+  int half;         // bilinear: f = r * (l + 0.5) - 0.5 clamped at 0 (align_mode 0 without align_corners); else f = l * r
+  int round_up;     // nearest: (int)(double(r * l) + 0.5) (align_corners); else (int)(r * l)
+};
+// method 0 bilinear / 1 nearest; the ratios and the coordinate rule of (align_corners, align_mode) as interp_ops.hip states them
+InterpArgs interp_args(const float* x, int ih, int iw, int oh, int ow, int method, int align_corners, int align_mode);
+// yf / yq [planes][oh][ow]: either may be null
+void launch_interp(const InterpArgs& a, int64_t planes, float* yf, int8_t* yq, float calib_scale, hipStream_t s);
+// x [outer][c][inner] -> y [outer][inner]: the largest index among the maxima; i64: int64 labels, else int32
+void launch_arg_max(const float* x, int64_t outer, int c, int64_t inner, void* y, int i64, hipStream_t s);
+// a.x [n][c][ih][iw] -> y [n][oh][ow]: arg_max over c of the resampled tensor, which is never written
+void launch_interp_argmax(const InterpArgs& a, int n, int c, void* y, int i64, hipStream_t s);
+
 }  // namespace plhip

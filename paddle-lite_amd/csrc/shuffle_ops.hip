@@ -22,11 +22,6 @@ namespace plhip {
 
 namespace {
 
-// calib_f32_to_i8_kernel's quantiser on a quad: four int8 in one dword
-__device__ __forceinline__ uint32_t calib4_i8(const v4f& v, float inv) {
-  return pack4_i8(round_sat_i8(inv * v[0]), round_sat_i8(inv * v[1]), round_sat_i8(inv * v[2]), round_sat_i8(inv * v[3]));
-}
-
 // one row of `len` floats from src to df (fp32, may be null) and dq (int8, may be null): this lane takes the items (quads with vec,
 // else elements) first, first + step, ...; the lanes that share the row cover every item once
 __device__ __forceinline__ void move_row(const float* __restrict__ src, float* __restrict__ df, int8_t* __restrict__ dq, int64_t len,

@@ -148,6 +148,36 @@ std::vector<int64_t> SplitExtents(const GraphOp& op, const std::vector<int64_t>&
   return e;
 }
 
+bool IsInterp(const GraphOp& op) { return op.type == "bilinear_interp" || op.type == "nearest_interp"; }
+
+// interpolate_op.cc:37-82 with the size from the attributes; CHECKs what the kHIP kernels are fatal on
+std::vector<int64_t> InterpOutShape(const GraphOp& op, const std::vector<int64_t>& in) {
+  CHECK(in.size() == 4) << op.type << " " << op.output << ": input " << DimsStr(in) << " is not [N, C, H, W]";
+  CHECK(op.align_mode == 0 || op.align_mode == 1) << op.type << " " << op.output << ": align_mode " << op.align_mode;
+  int64_t oh = op.out_h, ow = op.out_w;
+  if (!(op.out_h > 0 && op.out_w > 0)) {
+    CHECK(op.interp_scale > 0.f) << op.type << " " << op.output << ": neither out_h / out_w nor a scale > 0";
+    oh = static_cast<int>(in[2] * op.interp_scale);
+    ow = static_cast<int>(in[3] * op.interp_scale);
+  }
+  CHECK(oh >= 1 && ow >= 1) << op.type << " " << op.output << ": the output size " << oh << " x " << ow << " is empty";
+  return {in[0], in[1], oh, ow};
+}
+
+// argmax_op.cc:29-60: the axis is dropped, or kept as 1
+std::vector<int64_t> ArgmaxOutShape(const GraphOp& op, const std::vector<int64_t>& in) {
+  const int rank = static_cast<int>(in.size());
+  const int axis = op.axis < 0 ? op.axis + rank : op.axis;
+  CHECK(axis >= 0 && axis < rank) << "arg_max " << op.output << ": axis " << op.axis << " outside the rank " << rank;
+  CHECK(op.dtype == -1 || op.dtype == 2 || op.dtype == 3) << "arg_max " << op.output << ": dtype " << op.dtype << " is neither int64 (-1, 3) nor int32 (2)";
+  std::vector<int64_t> o;
+  for (int i = 0; i < rank; ++i) {
+    if (i != axis) o.push_back(in[i]);
+    else if (op.keepdims) o.push_back(1);
+  }
+  return o;
+}
+
 void CheckShuffleGroup(const GraphOp& op, const std::vector<int64_t>& in) {
   CHECK(in.size() >= 2) << "shuffle_channel " << op.output << ": input must have a channel axis";
   CHECK(op.group >= 1 && in[1] % op.group == 0) << "shuffle_channel " << op.output << ": group " << op.group << " does not divide C = " << in[1];
@@ -180,6 +210,10 @@ std::map<std::string, std::vector<int64_t>> GraphBuilder::InferShapes() const {
     } else if (op.type == "shuffle_channel") {
       CheckShuffleGroup(op, in);
       shape[op.output] = in;
+    } else if (IsInterp(op)) {
+      shape[op.output] = InterpOutShape(op, in);
+    } else if (op.type == "arg_max") {
+      shape[op.output] = ArgmaxOutShape(op, in);
     } else if (op.type == "conv2d" || op.type == "depthwise_conv2d") {
       const std::vector<int64_t> o = ConvOutShape(op, in);
       if (!o.empty()) shape[op.output] = o;
@@ -407,6 +441,8 @@ struct GraphBuilder::Fuser {
   void HardActCalib();
   void ShuffleTail();
   void ConcatCalib();
+  void InterpArgmax();
+  void InterpCalib();
 };
 
 // (A) (C) (B): the conv-tail patterns, matched by the SAME code a Paddle-Lite tree runs as a mir pass
@@ -777,6 +813,34 @@ void GraphBuilder::Fuser::ConcatCalib() {
   }
 }
 
+// (M) an interp whose only reader (fetches count) is an arg_max along axis 1: the interp step becomes the arg_max/interp instruction.
+// It runs where the interp ran: its one operand exists there, and the labels were written later before.
+void GraphBuilder::Fuser::InterpArgmax() {
+  for (size_t i = 0; i < st.size(); ++i) {
+    if (dead[i] || st[i].kind != StepKind::kOp || !IsInterp(Op(i)) || st[i].argmax_op >= 0 || !st[i].calib_out.empty()) continue;
+    const int j = SoleReader(st[i].out);
+    if (!IsOp(j, "arg_max") || !(Op(j).axis == 1 || Op(j).axis == -3)) continue;
+    st[i].argmax_op = st[j].op;
+    st[i].via = st[i].out;
+    st[i].out = st[j].out;
+    dead[j] = true;
+  }
+}
+
+// (N) an interp M left alone whose fp32 output a calib[fp32_to_int8] reads takes that calib over, as J1 / J3 do: one launch writes
+// the int8 tensor and, only where it has other readers, the fp32 one
+void GraphBuilder::Fuser::InterpCalib() {
+  for (size_t i = 0; i < st.size(); ++i) {
+    if (dead[i] || st[i].kind != StepKind::kOp || !IsInterp(Op(i)) || st[i].argmax_op >= 0 || !st[i].calib_out.empty()) continue;
+    const int k = FindByInput(StepKind::kCalibF2I, st[i].out, i + 1);
+    if (k < 0) continue;
+    st[i].calib_out = st[k].out;
+    st[i].calib_scale = st[k].scale;
+    dead[k] = true;
+    st[i].drop_f32 = Uses(st[i].out) == 0;
+  }
+}
+
 // The rewrites in the one order that gives today's programs.  Each takes over steps that a later one would otherwise match:
 //   * I before H: H would take the image_to_tensor behind an image_resize (and its calib) and leave the resize a launch of its own.
 //   * H before F: F would take the calib behind an image_to_tensor into the stem alone, and the fp32 tensor would still be written.
@@ -790,6 +854,8 @@ void GraphBuilder::Fuser::ConcatCalib() {
 //     no step they look at.
 //   * L last: it is for the concats K left alone, and takes calibs that read a concat or a max pool behind one; C took the max
 //     pools behind a conv long before.
+//   * M and N behind L: they take an arg_max or a calib that reads an interp, which no rewrite above matches.  M first: an interp it
+//     took has no fp32 output for N to quantise (and an interp that a calib reads too has two readers, so M leaves it to N).
 void GraphBuilder::FuseSteps(std::vector<Step>* steps, const std::map<std::string, std::vector<int64_t>>& shapes) {
   Fuser f(*this, steps, shapes);
   f.ConvTails();
@@ -803,6 +869,8 @@ void GraphBuilder::FuseSteps(std::vector<Step>* steps, const std::map<std::strin
   if (fuse_hard_act_) f.HardActCalib();
   if (fuse_shuffle_) f.ShuffleTail();
   if (fuse_concat_) f.ConcatCalib();
+  if (fuse_interp_argmax_) f.InterpArgmax();
+  if (fuse_interp_calib_) f.InterpCalib();
   std::vector<Step> kept;
   for (size_t i = 0; i < steps->size(); ++i)
     if (!f.dead[i]) kept.push_back((*steps)[i]);
@@ -835,12 +903,23 @@ std::string GraphBuilder::OpLine(const Step& s) const {
     if (s.drop_f32) l += " -f32";
     return l + " axis=" + std::to_string(op.axis);
   }
+  auto interp_attrs = [](const GraphOp& o) {
+    std::string a = o.out_h > 0 && o.out_w > 0 ? " size=" + std::to_string(o.out_h) + "x" + std::to_string(o.out_w) : std::string();
+    if (a.empty()) AppendNum(&a, "by", o.interp_scale);
+    return a + " align_corners=" + std::to_string(o.align_corners ? 1 : 0) + " align_mode=" + std::to_string(o.align_mode);
+  };
+  auto argmax_attrs = [](const GraphOp& o) {
+    return " axis=" + std::to_string(o.axis) + " dtype=" + std::to_string(o.dtype) + " keepdims=" + std::to_string(o.keepdims ? 1 : 0);
+  };
+  if (s.argmax_op >= 0)  // (M): the interp step that became the one instruction
+    return "arg_max/interp in=" + s.op_inputs[0] + " out=" + s.out + " +interp=" + op.type + interp_attrs(op) + argmax_attrs(ops_[s.argmax_op]) +
+           " via=" + s.via;
   std::string l = op.type;
   if (op.enable_int8) {
     const bool fc = op.type == "fc";
     l += s.int8_out ? (fc ? "/int8out" : "/int8_out") : (fc ? "/fp32out" : "/fp32_out");
   } else {
-    const bool tail_op = op.type == "hard_swish" || op.type == "elementwise_mul";  // (J1) (J3): the alias that carries a calib tail
+    const bool tail_op = op.type == "hard_swish" || op.type == "elementwise_mul" || IsInterp(op);  // (J1) (J3) (N): the alias that carries a calib tail
     l += tail_op && !s.calib_out.empty() ? "/int8" : "/def";
   }
   l += " in=";
@@ -854,6 +933,8 @@ std::string GraphBuilder::OpLine(const Step& s) const {
     for (size_t i = 0; i < op.sections.size(); ++i) l += (i ? "," : "") + std::to_string(op.sections[i]);
   }
   if (op.type == "shuffle_channel") l += " group=" + std::to_string(op.group);
+  if (IsInterp(op)) l += interp_attrs(op);
+  if (op.type == "arg_max") l += argmax_attrs(op);
   if (op.enable_int8 && s.int8_out) AppendNum(&l, "oscale", s.out_scale);
   if (s.image_feed >= 0) {  // (H1): image_to_tensor + calib taken over, the conv reads the uint8 image
     const FeedDesc& f = feeds_[s.image_feed];
@@ -974,6 +1055,15 @@ void GraphBuilder::LowerOp(const Step& s, HipPredictor* pred) {
     pred->AddSoftmax(s.op_inputs[0], s.out);
   } else if (op.type == "hard_swish" || op.type == "hard_sigmoid") {
     pred->AddActivation(op.type, s.op_inputs[0], s.out, s.calib_out, s.calib_scale, s.drop_f32);
+  } else if (s.argmax_op >= 0) {
+    const GraphOp& am = ops_[s.argmax_op];
+    pred->AddInterpArgMax(op.type, s.op_inputs[0], s.out, op.out_h, op.out_w, op.interp_scale, op.align_corners, op.align_mode, am.dtype,
+                          am.keepdims);
+  } else if (IsInterp(op)) {
+    pred->AddInterp(op.type, s.op_inputs[0], s.out, op.out_h, op.out_w, op.interp_scale, op.align_corners, op.align_mode, s.calib_out,
+                    s.calib_scale, s.drop_f32);
+  } else if (op.type == "arg_max") {
+    pred->AddArgMax(s.op_inputs[0], s.out, op.axis, op.dtype, op.keepdims);
   } else if (s.shuffle_tail) {
     pred->AddShuffleUnit(s.op_inputs[0], s.op_inputs[1], s.shuffle_tail == 2 ? s.out : "", s.shuffle_tail == 2 ? s.hi : s.out, s.calib_out,
                          s.calib_scale, s.drop_f32);

@@ -27,7 +27,8 @@ namespace lite {
 struct GraphOp {
   std::string type;  // conv2d | depthwise_conv2d | fc | pool2d | elementwise_add | fusion_elementwise_add_activation | softmax |
                      // hard_swish | hard_sigmoid | elementwise_mul (fp32 ops like pool2d; the reference's default parameters) |
-                     // concat (N inputs) | split | shuffle_channel (fp32 ops like pool2d)
+                     // concat (N inputs) | split | shuffle_channel (fp32 ops like pool2d) |
+                     // bilinear_interp | nearest_interp | arg_max (fp32 ops like pool2d; arg_max writes int64 / int32 labels)
   std::vector<std::string> inputs;
   std::string output;                // the first output
   std::vector<std::string> outputs;  // split: all outputs, outputs[0] == output; empty for every other type
@@ -52,6 +53,14 @@ struct GraphOp {
   std::vector<int> sections;
   // shuffle_channel
   int group{1};
+  // bilinear_interp / nearest_interp (InterpolateParam): the output is out_h x out_w where both are > 0, else int(in * interp_scale)
+  int out_h{-1}, out_w{-1};
+  float interp_scale{0.f};
+  bool align_corners{true};
+  int align_mode{1};
+  // arg_max (ArgmaxParam): along `axis`; dtype -1 / 3 int64 labels, 2 int32
+  int dtype{-1};
+  bool keepdims{false};
 };
 
 class GraphBuilder {
@@ -129,6 +138,19 @@ class GraphBuilder {
   // concat that a calib or a max pool reads changes.  DEFAULT ON: measured faster than the separate instructions by far more than
   // the run-to-run spread.
   void set_fuse_concat(bool on) { fuse_concat_ = on; }
+  //   (M) a bilinear_interp / nearest_interp whose only reader is an arg_max along axis 1 and which is not fetched
+  //       => ONE arg_max/interp instruction (plhip_interp_argmax_f32) that reads the low-resolution tensor and writes the labels; the
+  //       resampled tensor is no variable of the program any more.
+  //   (N) a bilinear_interp / nearest_interp (that M did not take) whose output a calib[fp32_to_int8] reads
+  //       => ONE bilinear_interp/int8 | nearest_interp/int8 instruction (plhip_interp_f32 with y_i8) that writes the calib's tensor at
+  //       its scale; the fp32 tensor is written only where a reader or a fetch is left.
+  // Anything else (an arg_max along another axis, a second reader of the resampled tensor in front of an arg_max, an interp only
+  // fp32 ops read) keeps the separate instructions.  With set_fuse(true) only, after L; bit-identical to the instructions they
+  // replace (the resampled values come from one device function, the comparison and the quantiser are arg_max's and calib's own).
+  // No program without an interp changes.  DEFAULT ON, each with a switch of its own: each was measured faster than the separate
+  // instructions by far more than the run-to-run spread.
+  void set_fuse_interp_argmax(bool on) { fuse_interp_argmax_ = on; }
+  void set_fuse_interp_calib(bool on) { fuse_interp_calib_ = on; }
   GraphOp& Add(const std::string& type, const std::vector<std::string>& inputs, const std::string& output);
   // Emits the program into `pred`; returns the host-side names of the fetched variables ("<name>/host").
   std::vector<std::string> Lower(HipPredictor* pred);
@@ -152,6 +174,9 @@ class GraphBuilder {
                               // shuffled tensor), 2 = K1 (shuffle_channel/unit: `out` the split's first half, `hi` its second);
                               // calib_out / calib_scale / drop_f32 belong to the tensor the calib read, `via` the names no longer written
     std::string hi;
+    int argmax_op{-1};        // (M) an interp step that took the arg_max(axis 1) behind it over: arg_max/interp, that op's index in
+                              // ops_; `out` the labels, `via` the resampled tensor that is no longer written.  (N) an interp step that
+                              // took the calib behind it over carries calib_out / calib_scale / drop_f32
     bool concat_int8{false};  // (L) a concat step that took the calib behind it over: concat/int8, calib_out / calib_scale / drop_f32
     // kHIP fusions (FuseSteps): tail taken over by an fp32_out conv, int8 max pool behind a fused calib
     std::string res;          // residual operand of the fused elementwise_add ("" = none)
@@ -204,6 +229,8 @@ class GraphBuilder {
   bool fuse_hard_act_{false};
   bool fuse_shuffle_{true};
   bool fuse_concat_{true};
+  bool fuse_interp_argmax_{true};
+  bool fuse_interp_calib_{true};
   std::vector<FeedDesc> feeds_;
   std::vector<std::string> fetches_;
   std::vector<GraphOp> ops_;

@@ -3,6 +3,7 @@
 
 #include "lite/kernels/hip/calib_tail.h"
 #include "lite/kernels/hip/concat_fusion.h"
+#include "lite/kernels/hip/interp_fusion.h"
 #include "lite/kernels/hip/conv_fusion.h"
 #include "lite/kernels/hip/image_frame.h"
 #include "lite/kernels/hip/se_gate_fusion.h"
@@ -432,6 +433,72 @@ void HipPredictor::AddConcatCalib(const std::vector<std::string>& inputs, const 
   auto* ck = dynamic_cast<kernels::hip::HipConcatFusionKernel*>(kernel.get());
   CHECK(ck) << "the picked concat kernel does not take the concat fusion";
   ck->SetConcatFusion(fz);
+  Emit(op, std::move(kernel));
+}
+
+static void SetInterpAttrs(operators::InterpolateParam* p, const std::string& op_type, int out_h, int out_w, float scale,
+                           bool align_corners, int align_mode) {
+  CHECK(op_type == "bilinear_interp" || op_type == "nearest_interp") << "kHIP has no interp kernel for " << op_type;
+  p->out_h = out_h;
+  p->out_w = out_w;
+  p->scale = scale;
+  p->align_corners = align_corners;
+  p->align_mode = align_mode;
+  p->interp_method = op_type == "bilinear_interp" ? "Bilinear" : "Nearest";
+}
+
+void HipPredictor::AddInterp(const std::string& op_type, const std::string& in, const std::string& out, int out_h, int out_w, float scale,
+                             bool align_corners, int align_mode, const std::string& calib_out, float calib_scale, bool drop_fp32) {
+  CHECK(!drop_fp32 || !calib_out.empty()) << "AddInterp: only a tensor whose int8 image is written can be dropped";
+  auto op = std::make_shared<operators::InterpolateOp>(op_type);
+  auto& p = op->mutable_param();
+  SetInterpAttrs(&p, op_type, out_h, out_w, scale, align_corners, align_mode);
+  p.X = Var(in);
+  p.Out = Var(out);
+  if (calib_out.empty()) {
+    Emit(op, PickKernel(op_type, Place(TARGET(kHIP), PRECISION(kFloat)), "def"));
+    return;
+  }
+  kernels::hip::HipInterpFusion fz;
+  fz.calib_output = Var(calib_out);
+  fz.calib_output->set_precision(PRECISION(kInt8));
+  fz.calib_scale = calib_scale;
+  fz.drop_fp32_output = drop_fp32;
+  auto kernel = PickKernel(op_type, Place(TARGET(kHIP), PRECISION(kAny)), "int8");
+  auto* ik = dynamic_cast<kernels::hip::HipInterpFusionKernel*>(kernel.get());
+  CHECK(ik) << "the picked " << op_type << " kernel does not take the interp fusion";
+  ik->SetInterpFusion(fz);
+  Emit(op, std::move(kernel));
+}
+
+void HipPredictor::AddArgMax(const std::string& in, const std::string& out, int axis, int dtype, bool keepdims) {
+  auto op = std::make_shared<operators::ArgmaxOpLite>();
+  auto& p = op->mutable_param();
+  p.X = Var(in);
+  p.Out = Var(out);
+  p.Axis = axis;
+  p.dtype = dtype;
+  p.keepdims = keepdims;
+  Emit(op, PickKernel("arg_max", Place(TARGET(kHIP), PRECISION(kAny)), "def"));
+}
+
+void HipPredictor::AddInterpArgMax(const std::string& op_type, const std::string& in, const std::string& out, int out_h, int out_w,
+                                   float scale, bool align_corners, int align_mode, int dtype, bool keepdims) {
+  kernels::hip::HipInterpArgmaxFusion fz;
+  fz.op_type = op_type;
+  SetInterpAttrs(&fz.interp, op_type, out_h, out_w, scale, align_corners, align_mode);
+  auto op = std::make_shared<operators::ArgmaxOpLite>();
+  auto& p = op->mutable_param();
+  p.X = Var(in);
+  p.Out = Var(out);
+  p.Axis = 1;
+  p.dtype = dtype;
+  p.keepdims = keepdims;
+  op->set_interp(fz.interp);
+  auto kernel = PickKernel("arg_max", Place(TARGET(kHIP), PRECISION(kAny)), "interp");
+  auto* ak = dynamic_cast<kernels::hip::HipInterpArgmaxKernel*>(kernel.get());
+  CHECK(ak) << "the picked arg_max kernel does not take the interp fusion";
+  ak->SetInterpArgmax(fz);
   Emit(op, std::move(kernel));
 }
 

@@ -112,6 +112,17 @@ class HipPredictor {
   // drop_fp32: `hi` has no reader left and is not written.
   void AddShuffleUnit(const std::string& a, const std::string& b, const std::string& lo, const std::string& hi,
                       const std::string& calib_out, float calib_scale, bool drop_fp32);
+  // bilinear_interp / nearest_interp and arg_max with the reference's attributes (lite/operators/op_params.h:154-168, 821-827); the
+  // output size is out_h x out_w where both are > 0, else int(in * scale).  calib_out != "": fusion N (lite/kernels/hip/
+  // interp_fusion.h), the calib[fp32_to_int8](calib_scale) behind the interp runs in the same launch and writes that variable;
+  // drop_fp32: `out` has no reader left and is not written (it carries the shape).
+  void AddInterp(const std::string& op_type, const std::string& in, const std::string& out, int out_h, int out_w, float scale,
+                 bool align_corners, int align_mode, const std::string& calib_out = "", float calib_scale = 1.f, bool drop_fp32 = false);
+  void AddArgMax(const std::string& in, const std::string& out, int axis, int dtype, bool keepdims);
+  // fusion M: interp -> arg_max(axis 1) in ONE launch, arg_max/interp.  `in` is the interp's low-resolution input, `out` the labels;
+  // the resampled tensor is no variable of the program.
+  void AddInterpArgMax(const std::string& op_type, const std::string& in, const std::string& out, int out_h, int out_w, float scale,
+                       bool align_corners, int align_mode, int dtype, bool keepdims);
 
   void Run(bool skip_io_copy = false) {
     TargetWrapperHip::SetDevice(device_);

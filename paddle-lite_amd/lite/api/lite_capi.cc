@@ -300,6 +300,56 @@ int pllite_add_concat_calib(pllite_predictor* p, const char* const* inputs, int 
                             float calib_scale, int drop_fp32) {
   return guarded([&] { p->pred.AddConcatCalib(names_of(inputs, n_inputs), out, axis, calib_out ? calib_out : "", calib_scale, drop_fp32 != 0); });
 }
+int pllite_add_interp(pllite_predictor* p, const char* op_type, const char* in, const char* out, int out_h, int out_w, float scale,
+                      int align_corners, int align_mode, const char* calib_out, float calib_scale, int drop_fp32) {
+  return guarded([&] {
+    CHECK(op_type && in && out) << "pllite_add_interp: op_type, in and out";
+    p->pred.AddInterp(op_type, in, out, out_h, out_w, scale, align_corners != 0, align_mode, calib_out ? calib_out : "", calib_scale,
+                      drop_fp32 != 0);
+  });
+}
+int pllite_add_arg_max(pllite_predictor* p, const char* in, const char* out, int axis, int dtype, int keepdims) {
+  return guarded([&] {
+    CHECK(in && out) << "pllite_add_arg_max: in and out";
+    p->pred.AddArgMax(in, out, axis, dtype, keepdims != 0);
+  });
+}
+int pllite_add_interp_arg_max(pllite_predictor* p, const char* op_type, const char* in, const char* out, int out_h, int out_w, float scale,
+                              int align_corners, int align_mode, int dtype, int keepdims) {
+  return guarded([&] {
+    CHECK(op_type && in && out) << "pllite_add_interp_arg_max: op_type, in and out";
+    p->pred.AddInterpArgMax(op_type, in, out, out_h, out_w, scale, align_corners != 0, align_mode, dtype, keepdims != 0);
+  });
+}
+int pllite_graph_interp(pllite_predictor* p, const char* op_type, const char* in, const char* out, int out_h, int out_w, float scale,
+                        int align_corners, int align_mode) {
+  return guarded([&] {
+    CHECK(op_type && in && out) << "pllite_graph_interp: op_type, in and out";
+    const std::string t = op_type;
+    CHECK(t == "bilinear_interp" || t == "nearest_interp") << "pllite_graph_interp: op type " << t;
+    auto& op = p->graph.Add(t, {in}, out);
+    op.out_h = out_h;
+    op.out_w = out_w;
+    op.interp_scale = scale;
+    op.align_corners = align_corners != 0;
+    op.align_mode = align_mode;
+  });
+}
+int pllite_graph_arg_max(pllite_predictor* p, const char* in, const char* out, int axis, int dtype, int keepdims) {
+  return guarded([&] {
+    CHECK(in && out) << "pllite_graph_arg_max: in and out";
+    auto& op = p->graph.Add("arg_max", {in}, out);
+    op.axis = axis;
+    op.dtype = dtype;
+    op.keepdims = keepdims != 0;
+  });
+}
+int pllite_graph_set_fuse_interp_argmax(pllite_predictor* p, int on) {
+  return guarded([&] { p->graph.set_fuse_interp_argmax(on != 0); });
+}
+int pllite_graph_set_fuse_interp_calib(pllite_predictor* p, int on) {
+  return guarded([&] { p->graph.set_fuse_interp_calib(on != 0); });
+}
 int pllite_graph_set_fuse_concat(pllite_predictor* p, int on) {
   return guarded([&] { p->graph.set_fuse_concat(on != 0); });
 }

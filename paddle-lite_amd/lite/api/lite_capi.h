@@ -97,12 +97,31 @@ int pllite_graph_concat(pllite_predictor* p, const char* const* inputs, int n_in
 int pllite_graph_split(pllite_predictor* p, const char* in, const char* const* outs, int n_outs, int axis, int num, const int* sections,
                        int n_sections);
 int pllite_graph_shuffle_channel(pllite_predictor* p, const char* in, const char* out, int group);
+/* bilinear_interp / nearest_interp (op_type) and arg_max with the reference's attributes: the output size is out_h x out_w where
+ * both are > 0, else int(in * scale).  calib_out != NULL / "": the int8 alias (lite/kernels/hip/interp_fusion.h), the
+ * calib[fp32_to_int8](calib_scale) behind the interp in the same launch writes that variable; drop_fp32: `out` is not written.
+ * dtype: -1 or 3 int64 labels, 2 int32.  pllite_add_interp_arg_max: interp -> arg_max(axis 1) in one launch (arg_max/interp); `in`
+ * is the interp's low-resolution input, the resampled tensor is no variable. */
+int pllite_add_interp(pllite_predictor* p, const char* op_type, const char* in, const char* out, int out_h, int out_w, float scale,
+                      int align_corners, int align_mode, const char* calib_out, float calib_scale, int drop_fp32);
+int pllite_add_arg_max(pllite_predictor* p, const char* in, const char* out, int axis, int dtype, int keepdims);
+int pllite_add_interp_arg_max(pllite_predictor* p, const char* op_type, const char* in, const char* out, int out_h, int out_w, float scale,
+                              int align_corners, int align_mode, int dtype, int keepdims);
 /* fusion K (concat -> shuffle_channel(2) -> [split ->] calib in one launch): on by default, effective with
  * pllite_graph_set_fuse(1) only; 0 keeps the separate instructions */
 int pllite_graph_set_fuse_shuffle(pllite_predictor* p, int on);
 /* fusion L (concat -> calib in one launch, the int8 max pool behind a concat): on by default, effective with
  * pllite_graph_set_fuse(1) only; 0 keeps the separate instructions */
 int pllite_graph_set_fuse_concat(pllite_predictor* p, int on);
+/* bilinear_interp / nearest_interp (op_type; out_h x out_w where both are > 0, else int(in * scale)) and arg_max along `axis`
+ * (dtype -1 or 3: int64 labels, 2: int32), fp32 ops like pool2d.  Fusions M (interp -> arg_max(axis 1) in one launch) and N
+ * (interp -> calib in one launch): each has a switch of its own, on by default, effective with
+ * pllite_graph_set_fuse(p, 1) only. */
+int pllite_graph_interp(pllite_predictor* p, const char* op_type, const char* in, const char* out, int out_h, int out_w, float scale,
+                        int align_corners, int align_mode);
+int pllite_graph_arg_max(pllite_predictor* p, const char* in, const char* out, int axis, int dtype, int keepdims);
+int pllite_graph_set_fuse_interp_argmax(pllite_predictor* p, int on);
+int pllite_graph_set_fuse_interp_calib(pllite_predictor* p, int on);
 int pllite_graph_fetch(pllite_predictor* p, const char* name);
 /* kHIP graph-level fusions (graph_builder.h set_fuse): on by default; 0 = the reference program instruction for instruction. */
 int pllite_graph_set_fuse(pllite_predictor* p, int on);

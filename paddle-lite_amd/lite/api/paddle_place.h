@@ -50,6 +50,7 @@ template <typename T> struct PrecisionTypeTrait { static constexpr PrecisionType
 template <> struct PrecisionTypeTrait<float> { static constexpr PrecisionType Type() { return PrecisionType::kFloat; } };
 template <> struct PrecisionTypeTrait<int8_t> { static constexpr PrecisionType Type() { return PrecisionType::kInt8; } };
 template <> struct PrecisionTypeTrait<int32_t> { static constexpr PrecisionType Type() { return PrecisionType::kInt32; } };
+template <> struct PrecisionTypeTrait<int64_t> { static constexpr PrecisionType Type() { return PrecisionType::kInt64; } };
 
 // lite/api/paddle_place.h Place{target, precision, layout, device}
 struct Place {

@@ -418,6 +418,84 @@ class ShuffleChannelOpLite : public OpLite {
   int channel_factor_{1};
 };
 
+// interpolate_op.cc:34-82 with the size from the attributes: out_h / out_w where both are > 0, else int(in * scale) with
+// scale > 0.  kHIP: NCHW, and no OutSize / SizeTensor / Scale tensor (the kernel's PrepareForRun is fatal on them too).
+class InterpolateOp : public OpLite {
+ public:
+  explicit InterpolateOp(const std::string& type) : OpLite(type) {}
+  InterpolateParam& mutable_param() { return param_; }
+  // the output size the attributes give for an input of in_h x in_w
+  static void OutputSize(const InterpolateParam& p, int64_t in_h, int64_t in_w, int64_t* out_h, int64_t* out_w) {
+    if (p.out_h > 0 && p.out_w > 0) {
+      *out_h = p.out_h;
+      *out_w = p.out_w;
+    } else {
+      CHECK(p.scale > 0.f) << "interp: neither out_h / out_w nor a scale > 0";
+      *out_h = static_cast<int>(in_h * p.scale);
+      *out_w = static_cast<int>(in_w * p.scale);
+    }
+    CHECK(*out_h >= 1 && *out_w >= 1) << "interp: the output size " << *out_h << " x " << *out_w << " is empty";
+  }
+  bool CheckShape() const override {
+    CHECK(param_.X && param_.Out) << op_type_ << ": X / Out must be set";
+    CHECK_EQ(param_.X->dims().size(), 4UL) << op_type_ << ": X must be [N, C, H, W]";
+    return true;
+  }
+  bool InferShapeImpl() const override {
+    CHECK(!param_.OutSize && param_.SizeTensor.empty() && !param_.Scale) << op_type_ << ": kHIP takes the size attributes only";
+    CHECK(param_.data_layout == DATALAYOUT(kNCHW)) << op_type_ << ": NCHW only";
+    const auto d = param_.X->dims();
+    int64_t oh, ow;
+    OutputSize(param_, d[2], d[3], &oh, &ow);
+    param_.Out->Resize(std::vector<int64_t>{d[0], d[1], oh, ow});
+    return true;
+  }
+  void AttachKernel(KernelBase* k) override { k->SetParam<InterpolateParam>(param_); }
+
+ private:
+  mutable InterpolateParam param_;
+};
+
+// argmax_op.cc:29-60: Out drops (keepdims: keeps as 1) the axis.  kHIP alias interp (lite/kernels/hip/interp_fusion.h): X is the
+// low-resolution tensor of the interp taken over, and the spatial dims of Out come from that interp's attributes.
+class ArgmaxOpLite : public OpLite {
+ public:
+  ArgmaxOpLite() : OpLite("arg_max") {}
+  ArgmaxParam& mutable_param() { return param_; }
+  void set_interp(const InterpolateParam& p) {  // kHIP fusion M only
+    interp_ = p;
+    has_interp_ = true;
+  }
+  bool CheckShape() const override {
+    CHECK(param_.X && param_.Out) << "arg_max: X / Out must be set";
+    const int rank = static_cast<int>(param_.X->dims().size());
+    CHECK(param_.Axis >= -rank && param_.Axis < rank) << "arg_max: axis " << param_.Axis << " outside the rank " << rank;
+    return true;
+  }
+  bool InferShapeImpl() const override {
+    auto in = param_.X->dims().Vectorize();
+    if (has_interp_) {
+      CHECK_EQ(in.size(), 4UL) << "arg_max/interp: X must be [N, C, H, W]";
+      InterpolateOp::OutputSize(interp_, in[2], in[3], &in[2], &in[3]);
+    }
+    const int rank = static_cast<int>(in.size());
+    const int axis = param_.Axis < 0 ? param_.Axis + rank : param_.Axis;
+    std::vector<int64_t> out;
+    for (int i = 0; i < rank; ++i) {
+      if (i != axis) out.push_back(in[i]);
+      else if (param_.keepdims) out.push_back(1);
+    }
+    param_.Out->Resize(out);
+    return true;
+  }
+  void AttachKernel(KernelBase* k) override { k->SetParam<ArgmaxParam>(param_); }
+
+ private:
+  mutable ArgmaxParam param_;
+  InterpolateParam interp_;
+  bool has_interp_{false};
+};
+
 class SoftmaxOp : public OpLite {
  public:
   SoftmaxOp() : OpLite("softmax") {}

@@ -2,7 +2,8 @@
 // defaults) with the subset of lite/operators/op_params.h the ARM int8 kernels read:
 //   WITH_INT8_CONFIG :49-54, IoCopyParam :70, CalibParam :82, FcParam :115-143, SoftmaxParam :319,
 //   ActivationParam :395-419, ConvParam :446-502, PoolParam :539-, ElementwiseParam :643-651,
-//   FusionElementwiseActivationParam :678-680, ShuffleChannelParam :258-263, ConcatParam :369-386, SplitParam :590-608.
+//   FusionElementwiseActivationParam :678-680, ShuffleChannelParam :258-263, ConcatParam :369-386, SplitParam :590-608,
+//   InterpolateParam :154-168, ArgmaxParam :821-827.
 // Tensors are NOT owned: params hold raw lite::Tensor* into the caller's scope (conv_op.h:72-74); bias may be null;
 // paddings / dilations are shared_ptrs the op may mutate (UpdatePaddingAndDilation, conv_op.cc:55-81).
 #pragma once
@@ -10,6 +11,7 @@
 #include <string>
 #include <vector>
 
+#include "lite/api/paddle_place.h"
 #include "lite/core/tensor.h"
 
 namespace paddle {
@@ -145,6 +147,31 @@ struct SplitParam : ParamBase {
   int axis{-1};
   int num{0};
   std::vector<int> sections;
+};
+
+// bilinear_interp / nearest_interp.  kHIP takes the output size from the attributes only: OutSize, SizeTensor and Scale must
+// stay empty (fatal in PrepareForRun)
+struct InterpolateParam : ParamBase {
+  lite::Tensor* X{};
+  lite::Tensor* OutSize{};
+  lite::Tensor* Out{};
+  std::vector<const lite::Tensor*> SizeTensor;
+  lite::Tensor* Scale{};
+  float scale{0.f};
+  int out_h{-1};
+  int out_w{-1};
+  bool align_corners{true};
+  int align_mode{1};
+  std::string interp_method{"Nearest"};
+  DataLayoutType data_layout{DATALAYOUT(kNCHW)};
+};
+
+struct ArgmaxParam : ParamBase {
+  lite::Tensor* X{};
+  lite::Tensor* Out{};
+  int Axis{0};
+  int dtype{-1};
+  bool keepdims{false};
 };
 
 }  // namespace operators

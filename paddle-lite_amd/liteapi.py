@@ -75,6 +75,13 @@ def load():
     L.pllite_add_shuffle_unit.argtypes = [vp, cs, cs, cs, cs, cs, f32, i32]
     L.pllite_add_concat_calib.argtypes = [vp, C.POINTER(cs), i32, cs, i32, cs, f32, i32]
     L.pllite_graph_set_fuse_concat.argtypes = [vp, i32]
+    L.pllite_graph_interp.argtypes = [vp, cs, cs, cs, i32, i32, f32, i32, i32]
+    L.pllite_graph_arg_max.argtypes = [vp, cs, cs, i32, i32, i32]
+    L.pllite_graph_set_fuse_interp_argmax.argtypes = [vp, i32]
+    L.pllite_graph_set_fuse_interp_calib.argtypes = [vp, i32]
+    L.pllite_add_interp.argtypes = [vp, cs, cs, cs, i32, i32, f32, i32, i32, cs, f32, i32]
+    L.pllite_add_arg_max.argtypes = [vp, cs, cs, i32, i32, i32]
+    L.pllite_add_interp_arg_max.argtypes = [vp, cs, cs, cs, i32, i32, f32, i32, i32, i32, i32]
     L.pllite_graph_fetch.argtypes = [vp, cs]
     L.pllite_graph_set_fuse.argtypes = [vp, i32]
     L.pllite_graph_set_fuse_dwpw.argtypes = [vp, i32]
@@ -220,6 +227,24 @@ class Predictor:
         self._ck(self.L.pllite_add_shuffle_unit(self.h, a.encode(), b.encode(), lo.encode(), hi.encode(), calib_out.encode(),
                                                 calib_scale, int(drop_fp32)))
 
+    def add_interp(self, op_type, src, dst, out_hw=None, scale=0.0, align_corners=True, align_mode=1, calib_out="", calib_scale=1.0,
+                   drop_fp32=False):
+        """bilinear_interp | nearest_interp to out_hw, or by `scale` (int(in * scale)).  calib_out: the int8 alias (the calib behind the
+        interp in the same launch writes that variable); drop_fp32: dst is not written."""
+        oh, ow = out_hw if out_hw is not None else (-1, -1)
+        self._ck(self.L.pllite_add_interp(self.h, op_type.encode(), src.encode(), dst.encode(), int(oh), int(ow), float(scale),
+                                          int(align_corners), int(align_mode), calib_out.encode(), calib_scale, int(drop_fp32)))
+
+    def add_arg_max(self, src, dst, axis, dtype=-1, keepdims=False):
+        """dtype as ArgmaxParam's: -1 or 3 int64 labels, 2 int32."""
+        self._ck(self.L.pllite_add_arg_max(self.h, src.encode(), dst.encode(), int(axis), int(dtype), int(keepdims)))
+
+    def add_interp_arg_max(self, op_type, src, dst, out_hw=None, scale=0.0, align_corners=True, align_mode=1, dtype=-1, keepdims=False):
+        """interp -> arg_max(axis 1) in one launch (arg_max/interp): src is the interp's low-resolution input."""
+        oh, ow = out_hw if out_hw is not None else (-1, -1)
+        self._ck(self.L.pllite_add_interp_arg_max(self.h, op_type.encode(), src.encode(), dst.encode(), int(oh), int(ow), float(scale),
+                                                  int(align_corners), int(align_mode), int(dtype), int(keepdims)))
+
     # ---- graph mode: ops as the optimiser sees them; graph_lower() applies the reference's kernel-pick / cast rules
     def graph_feed(self, name, dims, precision=PREC_FLOAT):
         self._ck(self.L.pllite_graph_feed(self.h, name.encode(), _ia(dims, C.c_int64), len(dims), precision))
@@ -305,6 +330,26 @@ class Predictor:
         """Fusion L (default on; with graph_set_fuse(True) only): a concat takes the calib[fp32_to_int8] that reads it over (concat/int8, L1), and a
         max pool behind the concat whose only reader is a calib of the same scale becomes an int8 max pool on the int8 copy (L2)."""
         self._ck(self.L.pllite_graph_set_fuse_concat(self.h, int(on)))
+
+    def graph_interp(self, op_type, src, dst, out_hw=None, scale=0.0, align_corners=True, align_mode=1):
+        """bilinear_interp | nearest_interp to out_hw, or by `scale` (int(in * scale)); the reference's attribute defaults."""
+        oh, ow = out_hw if out_hw is not None else (-1, -1)
+        self._ck(self.L.pllite_graph_interp(self.h, op_type.encode(), src.encode(), dst.encode(), int(oh), int(ow), float(scale),
+                                            int(align_corners), int(align_mode)))
+
+    def graph_arg_max(self, src, dst, axis, dtype=-1, keepdims=False):
+        """dtype as ArgmaxParam's: -1 or 3 int64 labels, 2 int32."""
+        self._ck(self.L.pllite_graph_arg_max(self.h, src.encode(), dst.encode(), int(axis), int(dtype), int(keepdims)))
+
+    def graph_set_fuse_interp_argmax(self, on):
+        """Fusion M (default on; with graph_set_fuse(True) only): an interp whose only reader is arg_max(axis 1) becomes one
+        arg_max/interp instruction on the low-resolution tensor; the resampled tensor is never written."""
+        self._ck(self.L.pllite_graph_set_fuse_interp_argmax(self.h, int(on)))
+
+    def graph_set_fuse_interp_calib(self, on):
+        """Fusion N (default on; with graph_set_fuse(True) only): an interp takes the calib[fp32_to_int8] that reads it over
+        (bilinear_interp/int8, nearest_interp/int8)."""
+        self._ck(self.L.pllite_graph_set_fuse_interp_calib(self.h, int(on)))
 
     def graph_set_fuse_hard_act(self, on):
         """Fusions J1 / J2 / J3 (default off; with graph_set_fuse(True) only): hard_swish / elementwise_mul take the calib[fp32_to_int8]

@@ -108,6 +108,8 @@ def build_mobilenet_v1(pred, W, batch, res=224):
 #   pool2d: src, pooling_type, ksize, stride, pad, global_pooling
 #   add: x, y, act ("" | "relu")      softmax: src
 #   concat: srcs [..], axis      split: src, names [..] (name = names[0]), axis, num, sections      shuffle_channel: src, group
+#   bilinear_interp / nearest_interp: src, out_h, out_w, align_corners, align_mode      arg_max: src, axis, dtype, keepdims
+#   a conv with a dilation other than 1 carries `dilation` (both axes)
 # On the reference's ARM target pool2d and elementwise_add exist in fp32 only, so the kernel-pick
 # rule gives the convs in front of them the fp32_out kernel and the consumers behind them a calib.
 # =====================================================================================================================
@@ -124,7 +126,8 @@ class _NetGen:
         self.act_scale[name] = np.float32(act_scale)
         self.sig_i8[name] = sig_i8
 
-    def conv(self, name, src, cout, k, stride, pad, groups=1, act=1, act_coef=0.0, out_range=4.0, op=None, headroom=1.0, bias_shift=0.0):
+    def conv(self, name, src, cout, k, stride, pad, groups=1, act=1, act_coef=0.0, out_range=4.0, op=None, headroom=1.0, bias_shift=0.0,
+             dilation=1):
         cin, h, w = self.shape[src]
         kk = (cin // groups) * k * k
         wt = self.rng.integers(-127, 128, (cout, cin // groups, k, k)).astype(np.int8)
@@ -141,8 +144,11 @@ class _NetGen:
             op = "depthwise_conv2d" if (groups == cin and groups == cout and groups > 1) else "conv2d"
         self.ops.append(dict(op=op, name=name, src=src, w=wt, bias=bias, stride=stride, pad=pad, groups=groups, act=act,
                              act_coef=float(act_coef), in_scale=in_scale, w_scale=w_scale))
-        ho = (h + 2 * pad - k) // stride + 1
-        wo = (w + 2 * pad - k) // stride + 1
+        if dilation != 1:
+            self.ops[-1]["dilation"] = int(dilation)
+        ke = dilation * (k - 1) + 1
+        ho = (h + 2 * pad - ke) // stride + 1
+        wo = (w + 2 * pad - ke) // stride + 1
         self.tensor(name, cout, ho, wo, out_scale, (30.0 if act else 45.0) / headroom)
         return name
 
@@ -223,6 +229,25 @@ class _NetGen:
         assert c % group == 0, (c, group)
         self.ops.append(dict(op="shuffle_channel", name=name, src=src, group=group))
         self.tensor(name, c, h, w, self.act_scale[src], self.sig_i8[src])
+        return name
+
+    def interp(self, name, src, method, out_hw, align_corners=True, align_mode=1):
+        """fp32 op, bilinear_interp | nearest_interp to out_hw (the reference's attribute defaults).  A resampled value lies between
+        the source's values: the tensor keeps the source's scale and spread."""
+        assert method in ("bilinear", "nearest")
+        c, h, w = self.shape[src]
+        oh, ow = (int(v) for v in out_hw)
+        self.ops.append(dict(op=method + "_interp", name=name, src=src, out_h=oh, out_w=ow, align_corners=bool(align_corners),
+                             align_mode=int(align_mode)))
+        self.tensor(name, c, oh, ow, self.act_scale[src], self.sig_i8[src])
+        return name
+
+    def arg_max(self, name, src, axis=1, dtype=-1, keepdims=False):
+        """The labels along the channel axis of [c, h, w]: int64 (dtype -1, 3) or int32 (2); no int8 op reads them."""
+        assert axis == 1 and dtype in (-1, 2, 3)
+        c, h, w = self.shape[src]
+        self.ops.append(dict(op="arg_max", name=name, src=src, axis=axis, dtype=int(dtype), keepdims=bool(keepdims)))
+        self.shape[name] = (1, h, w) if keepdims else (h, w)
         return name
 
     def fc(self, name, src, n):
@@ -494,6 +519,48 @@ def inception_mini_net(seed=57, res=64, num_classes=10):
     return _finish(g, res, x)
 
 
+def seg_mini_net(seed=58, res=64, num_classes=19):
+    """A DeepLabV3+-shaped segmentation net (Chen et al. 2018) small enough for the CPU oracle: a depthwise-separable encoder to
+    res / 8, an ASPP of a 1x1 and two dilated 3x3 convs with their 1x1 projection, a decoder that raises the resolution twice
+    (bilinear to the `low` features at res / 4 and concat with their 1x1 reduction, then nearest to res / 2) and a head that
+    resamples the class logits to the input size and takes the per-pixel arg_max.  The first network here with interp ops, dilated
+    convs and an integer result.  Lowering with every fusion on: L takes both concats, N the nearest interp (a conv reads it), M the
+    head; the first bilinear interp feeds a concat and stays as it is.
+    Sizing: the spread corrections of squeezenet_v1_1_net for the concats (1.4), a depthwise conv sized with half as much
+    headroom again (its 9 taps see relu outputs of neighbouring pixels, whose sum spreads wider than the rule for independent taps
+    says, as shufflenet_v2_net's do), and an ASPP input quantised over a range 1.5
+    times wider, as inception_mini_net widens a block's input that several branches read.  The logits are fp32 and keep their sign
+    (no activation): tests/test_interp_host.py states the worst saturated and zero shares of the int8 tensors."""
+    assert res % 8 == 0
+    g = _NetGen(seed)
+    g.tensor("image", 3, res, res, 1.0 / 127, 73.0)
+    x = g.conv("stem", "image", 16, 3, 2, 1, act=1)
+
+    def block(p, x, cout, stride):
+        c = g.shape[x][0]
+        d = _spread(g, g.conv(p + "_dw", x, c, 3, stride, 1, groups=c, act=1, headroom=1.5), 1.4 * 1.5)
+        return g.conv(p + "_pw", d, cout, 1, 1, 0, act=1)
+
+    low = block("enc1", x, 24, 2)                      # res / 4
+    x = block("enc3", block("enc2", low, 64, 2), 64, 1)  # res / 8
+    g.widen(x, 1.5)
+    a1 = g.conv("aspp_1x1", x, 32, 1, 1, 0, act=1)
+    a2 = g.conv("aspp_d2", x, 32, 3, 1, 2, act=1, dilation=2)
+    a3 = g.conv("aspp_d3", x, 32, 3, 1, 3, act=1, dilation=3)
+    x = _spread(g, g.concat("aspp_concat", [a1, a2, a3], 1), 1.4)
+    x = g.conv("aspp_project", x, 32, 1, 1, 0, act=1)
+    x = g.interp("dec_up1", x, "bilinear", g.shape[low][1:], align_corners=False, align_mode=1)
+    r = g.conv("dec_low", low, 16, 1, 1, 0, act=1)
+    x = _spread(g, g.concat("dec_concat", [x, r], 1), 1.4)
+    x = g.conv("dec_conv1", x, 32, 3, 1, 1, act=1)
+    x = g.interp("dec_up2", x, "nearest", (res // 2, res // 2), align_corners=False)
+    x = g.conv("dec_conv2", x, 32, 3, 1, 1, act=1)
+    x = g.conv("logits", x, num_classes, 1, 1, 0, act=0)
+    x = g.interp("logits_up", x, "bilinear", (res, res), align_corners=True)
+    x = g.arg_max("label", x, 1, dtype=-1)
+    return _finish(g, res, x)
+
+
 def concat_calib_bytes(net, batch):
     """Algorithmic bytes of every concat that a calib reads directly or through a max pool, as separate concat and calib
     instructions (17 per concatenated element: 4 + 4 for the move, 4 + 4 + 1 for the calib; counted where the calib reads the pool
@@ -561,7 +628,7 @@ def net_stats(net):
 
 
 def emit_graph(pred, net, batch, fuse=True, fuse_dwpw=None, fuse_dwconv=None, image=None, frame=None, fuse_hard_act=None, fuse_shuffle=None,
-               fuse_concat=None):
+               fuse_concat=None, fuse_interp_argmax=None, fuse_interp_calib=None, fetch=()):
     """Feed the op list to the predictor's graph mode and lower it.  Returns the host name of the output variable.
     image: None = the input is the normalised fp32 NCHW tensor; dict(format, means, scales) = the input is a decoded uint8 image
     [batch, h, w, cs] of that format (liteapi.IMG_*), normalised on the device (Predictor.graph_feed_image).
@@ -577,7 +644,11 @@ def emit_graph(pred, net, batch, fuse=True, fuse_dwpw=None, fuse_dwconv=None, im
     fuse_shuffle: None = the builder's default (on); fusion K of the ShuffleNetV2 ops (concat -> shuffle_channel(2) ->
     [split ->] calib becomes one shuffle_channel/unit or shuffle_channel/int8 instruction), False = the separate instructions.
     fuse_concat: None = the builder's default (on); fusion L of the fire / inception modules (a concat takes the calib that reads it
-    over, concat/int8; a max pool behind it runs on the int8 copy), False = the separate instructions."""
+    over, concat/int8; a max pool behind it runs on the int8 copy), False = the separate instructions.
+    fuse_interp_argmax / fuse_interp_calib: None = the builder's default (on); False = the separate instructions; fusions M (an interp whose only reader is
+    arg_max(axis 1) becomes one arg_max/interp instruction) and N (an interp takes the calib that reads it over) of the dense
+    prediction ops, each with a switch of its own.
+    fetch: further variables to fetch beside net["output"] (host names: "<name>/host")."""
     from . import liteapi
     pred.graph_set_fuse(fuse)
     if fuse_dwpw is not None:
@@ -590,6 +661,10 @@ def emit_graph(pred, net, batch, fuse=True, fuse_dwpw=None, fuse_dwconv=None, im
         pred.graph_set_fuse_shuffle(fuse_shuffle)
     if fuse_concat is not None:
         pred.graph_set_fuse_concat(fuse_concat)
+    if fuse_interp_argmax is not None:
+        pred.graph_set_fuse_interp_argmax(fuse_interp_argmax)
+    if fuse_interp_calib is not None:
+        pred.graph_set_fuse_interp_calib(fuse_interp_calib)
     c, h, w = net["input_shape"]
     if frame is not None:
         assert image is None, "emit_graph: image= and frame= exclude each other"
@@ -602,7 +677,7 @@ def emit_graph(pred, net, batch, fuse=True, fuse_dwpw=None, fuse_dwconv=None, im
         t = o["op"]
         if t in ("conv2d", "depthwise_conv2d"):
             p = o["pad"]
-            pred.graph_conv(t, o["src"], o["name"], o["w"], o["bias"], (o["stride"],) * 2, (p, p, p, p), (1, 1), o["groups"],
+            pred.graph_conv(t, o["src"], o["name"], o["w"], o["bias"], (o["stride"],) * 2, (p, p, p, p), (o.get("dilation", 1),) * 2, o["groups"],
                             o["act"], o["act_coef"], float(o["in_scale"]), o["w_scale"])
         elif t == "fc":
             pred.graph_fc(o["src"], o["name"], o["w"], o["bias"], float(o["in_scale"]), o["w_scale"], False)
@@ -626,8 +701,14 @@ def emit_graph(pred, net, batch, fuse=True, fuse_dwpw=None, fuse_dwconv=None, im
             pred.graph_split(o["src"], o["names"], o["axis"], o["num"], o["sections"])
         elif t == "shuffle_channel":
             pred.graph_shuffle_channel(o["src"], o["name"], o["group"])
+        elif t in ("bilinear_interp", "nearest_interp"):
+            pred.graph_interp(t, o["src"], o["name"], (o["out_h"], o["out_w"]), 0.0, o["align_corners"], o["align_mode"])
+        elif t == "arg_max":
+            pred.graph_arg_max(o["src"], o["name"], o["axis"], o["dtype"], o["keepdims"])
         else:
             raise ValueError(t)
+    for v in fetch:
+        pred.graph_fetch(v)
     pred.graph_fetch(net["output"])
     return net["output"] + "/host"
 

@@ -9,7 +9,7 @@ import os
 import re
 
 STRUCTS = ["ParamBase", "IoCopyParam", "CalibParam", "FcParam", "SoftmaxParam", "ActivationParam", "ConvParam", "PoolParam",
-           "ElementwiseParam", "FusionElementwiseActivationParam", "ShuffleChannelParam", "ConcatParam", "SplitParam"]
+           "ElementwiseParam", "FusionElementwiseActivationParam", "ShuffleChannelParam", "ConcatParam", "SplitParam", "InterpolateParam", "ArgmaxParam"]
 
 
 def struct_text(src, name):
