@@ -427,6 +427,61 @@ plhip_status plhip_arg_max_f32(plhip_ctx* ctx, const float* x, int64_t outer, in
 plhip_status plhip_interp_argmax_f32(plhip_ctx* ctx, const float* x, int n, int c, int in_h, int in_w, int out_h, int out_w,
                                      int method, int align_corners, int align_mode, void* y, int dtype);
 
+/* ---- detection heads (transpose_ops.hip, detection_ops.hip): transpose, the one-launch join of an SSD head's feature maps,
+ * box_coder (decode_center_size) and multiclass_nms.  Every entry point checks its arguments before any launch, each failure
+ * with a text of its own; none synchronises with the host, copies tables or uses atomics, so all may be captured by
+ * plhip_graph_begin and every result is a function of the inputs alone. ---- */
+/* y = transpose(x, perm) (lite/kernels/arm/transpose_compute.cc): x fp32 of extents dims[rank], rank 2 .. 4, every extent >= 1,
+ * at most 2^40 elements; perm a permutation of 0 .. rank - 1; axis k of y is axis perm[k] of x.  The bits are moved.  x and y
+ * must not overlap.  Where the innermost source axis is not the innermost destination axis (NCHW -> NHWC, (0, 2, 1)) a block
+ * moves 64 x 64 tiles through LDS, whole rows on both sides, 16 bytes per lane where both extents are multiples of 4 and both
+ * bases 16-byte aligned. */
+plhip_status plhip_transpose_f32(plhip_ctx* ctx, const float* x, const int64_t* dims, const int* perm, int rank, float* y);
+/* transpose(0,2,3,1) -> reshape([0,-1,k]) -> concat(axis 1) of `count` NCHW tensors xs[i] [n][channels[i]][hw[i]] in ONE launch
+ * (per 8 operands): y [n][sum channels[i] * hw[i]], operand i of image b as [hw[i]][channels[i]] behind the operands in front
+ * of it; byte for byte what the three ops write, for every k that divides all channels[i]. */
+plhip_status plhip_concat_nhwc_f32(plhip_ctx* ctx, const float* const* xs, const int64_t* channels, const int64_t* hw, int count,
+                                   int64_t n, float* y);
+/* box_coder, code_type decode_center_size (lite/kernels/arm/box_coder_compute.cc:92-158): target, y [rows][cols][4]; the prior
+ * box of element (i, j) is row j of prior [cols][4] with axis 0 and row i of prior [rows][4] with axis 1; its variance is the
+ * same row of prior_var when that is given, else variance4[0 .. 3] (host memory, read during the call) when that is given, else
+ * none.  normalized == 0 adds 1 to widths and heights and subtracts it from the far corner.  fp32 in the reference's order of
+ * operations with no contraction; exp is the library's expf.  One lane per box, 16-byte accesses where every base is aligned. */
+plhip_status plhip_box_coder_decode_f32(plhip_ctx* ctx, const float* prior, const float* prior_var_or_null,
+                                        const float* variance4_or_null, const float* target, int64_t rows, int64_t cols, int axis,
+                                        int normalized, float* y);
+/* multiclass_nms (lite/kernels/host/multiclass_nms_compute.cc:31-322), the 3-D score form, exact to the host algorithm:
+ * a candidate needs score > score_threshold (a NaN never is one); candidates are ordered by descending score, equal scores (-0
+ * and +0 are equal) by ascending prior; the list is cut at nms_top_k (negative: all); a candidate is kept iff
+ * overlap <= nms_threshold against every box kept before it, overlap being JaccardOverlap as written there (0 for disjoint
+ * boxes, area 0 for an inverted box, +1 on every extent with normalized == 0, inter / (a1 + a2 - inter); 0 / 0 = NaN suppresses);
+ * background_label is skipped (-1: none); an image with more than keep_top_k kept boxes keeps the keep_top_k best by (score
+ * descending, label, order of selection) and lists them by label.
+ * Score of image i, class c, prior p: scores[i * C * P + c * score_stride_class + p * score_stride_prior] (strides in elements):
+ * [N, C, P] is (P, 1), [N, P, C] is (1, C), so a transpose in front of the op can be folded away. */
+typedef struct {
+  int n, c, p;
+  int64_t score_stride_class, score_stride_prior;
+  int background_label;
+  float score_threshold;
+  int nms_top_k;
+  float nms_threshold;
+  float nms_eta;
+  int keep_top_k;
+  int normalized;
+} plhip_nms_desc;
+/* Device bytes plhip_multiclass_nms_f32 needs for desc (the classes' kept lists); 0 for a descriptor it refuses. */
+size_t plhip_multiclass_nms_workspace_bytes(const plhip_nms_desc* desc);
+/* boxes [N][P][4]; out [N][keep_top_k][6] rows (label, score, x1, y1, x2, y2), rows past an image's count filled with -1;
+ * count [N] int32; index_or_null [N][keep_top_k] int32, i * P + prior, -1 past the count.  workspace: 8-byte aligned.
+ * PLHIP_ERR_INVALID: a NULL pointer, a dimension < 1, keep_top_k <= 0 (it sizes the output), strides that leave the image's
+ * C * P scores.  PLHIP_ERR_UNSUPPORTED, outside the envelope of the two kernels (each keeps its keys in one workgroup's LDS):
+ *   nms_eta < 1 (the adaptive threshold);  P > 16384;  min(nms_top_k, P) > 4096;
+ *   (classes other than the background) * min(nms_top_k, keep_top_k, P) > 16384;  N > 65535 or N * P >= 2^31.
+ * SSD300 (P 1917, C 21, top 400, keep 200) and YOLOv3-416 (P 10647, C 80, top 1000, keep 100) are inside. */
+plhip_status plhip_multiclass_nms_f32(plhip_ctx* ctx, const float* boxes, const float* scores, const plhip_nms_desc* desc,
+                                      void* workspace, float* out, int* index_or_null, int* count);
+
 /* ---- introspection used by tests: operand-layout self-check of the MFMA tile on this device.
  * Runs a tiny known-answer GEMM through the MFMA path; returns PLHIP_OK iff bit-exact. ---- */
 plhip_status plhip_selftest(plhip_ctx* ctx);

@@ -35,6 +35,8 @@ EXPORTS = [
     "plhip_concat_f32", "plhip_split_f32", "plhip_shuffle_channel_f32", "plhip_shuffle_unit_f32",
     "plhip_concat_calib_f32",
     "plhip_interp_f32", "plhip_arg_max_f32", "plhip_interp_argmax_f32",
+    "plhip_transpose_f32", "plhip_concat_nhwc_f32", "plhip_box_coder_decode_f32",
+    "plhip_multiclass_nms_workspace_bytes", "plhip_multiclass_nms_f32",
 ]
 
 # plhip_hard_act_kind, and the reference's default parameters (lite/operators/op_params.h:406-412)
@@ -85,6 +87,23 @@ def image_desc(n, h, w, fmt, means, scales):
 class SeGateDesc(C.Structure):
     _fields_ = [("n", C.c_int), ("c", C.c_int), ("cr", C.c_int), ("calib_scale", C.c_float), ("act1", C.c_int), ("act2", C.c_int),
                 ("act1_alpha", C.c_float), ("act2_alpha", C.c_float), ("slope", C.c_float), ("offset", C.c_float)]
+
+
+class NmsDesc(C.Structure):
+    _fields_ = [("n", C.c_int), ("c", C.c_int), ("p", C.c_int), ("score_stride_class", C.c_int64), ("score_stride_prior", C.c_int64),
+                ("background_label", C.c_int), ("score_threshold", C.c_float), ("nms_top_k", C.c_int), ("nms_threshold", C.c_float),
+                ("nms_eta", C.c_float), ("keep_top_k", C.c_int), ("normalized", C.c_int)]
+
+
+def nms_desc(n, c, p, background_label, score_threshold, nms_top_k, nms_threshold, keep_top_k, normalized=True, nms_eta=1.0,
+             layout="ncp"):
+    """plhip_nms_desc; layout: "ncp" scores [N, C, P] (strides P, 1) or "npc" scores [N, P, C] (strides 1, C)."""
+    d = NmsDesc()
+    d.n, d.c, d.p = int(n), int(c), int(p)
+    d.score_stride_class, d.score_stride_prior = {"ncp": (int(p), 1), "npc": (1, int(c))}[layout]
+    d.background_label, d.score_threshold, d.nms_top_k = int(background_label), float(score_threshold), int(nms_top_k)
+    d.nms_threshold, d.nms_eta, d.keep_top_k, d.normalized = float(nms_threshold), float(nms_eta), int(keep_top_k), int(bool(normalized))
+    return d
 
 
 class FrameDesc(C.Structure):
@@ -273,6 +292,12 @@ def load():
     L.plhip_interp_f32.argtypes = [vp, vp, C.c_int64, i32, i32, i32, i32, i32, i32, i32, vp, vp, f32]
     L.plhip_arg_max_f32.argtypes = [vp, vp, C.c_int64, i32, C.c_int64, vp, i32]
     L.plhip_interp_argmax_f32.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32]
+    L.plhip_transpose_f32.argtypes = [vp, vp, C.POINTER(C.c_int64), C.POINTER(i32), i32, vp]
+    L.plhip_concat_nhwc_f32.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int64), C.POINTER(C.c_int64), i32, C.c_int64, vp]
+    L.plhip_box_coder_decode_f32.argtypes = [vp, vp, vp, C.POINTER(f32), vp, C.c_int64, C.c_int64, i32, i32, vp]
+    L.plhip_multiclass_nms_workspace_bytes.argtypes = [C.POINTER(NmsDesc)]
+    L.plhip_multiclass_nms_workspace_bytes.restype = sz
+    L.plhip_multiclass_nms_f32.argtypes = [vp, vp, vp, C.POINTER(NmsDesc), vp, vp, vp, vp]
     L.plhip_selftest.argtypes = [vp]
     _lib = L
     return L
@@ -866,3 +891,73 @@ class Context:
             return self.to_host(dy, (n, oh, ow), np_t)
         finally:
             self.free(xbuf), self.free(ybuf)
+
+    # ---- detection heads: transpose, the one-launch head join, box_coder, multiclass_nms (transpose_ops.hip, detection_ops.hip)
+    def transpose(self, x, perm, misalign=0):
+        """plhip_transpose_f32: np.transpose(x, perm) of an fp32 array of rank 2 .. 4, the bits moved."""
+        x = np.ascontiguousarray(x, np.float32)
+        xbuf, dx = self._up_f32(x, misalign)
+        ybuf, dy = self._out_buf(x.size, 4, misalign)
+        try:
+            dims = (C.c_int64 * x.ndim)(*x.shape)
+            pm = (C.c_int * len(perm))(*[int(v) for v in perm])
+            self.check(self.L.plhip_transpose_f32(self.h, dx, dims, pm, x.ndim, dy), "transpose")
+            return self.to_host(dy, tuple(x.shape[k] for k in perm), np.float32)
+        finally:
+            self.free(xbuf), self.free(ybuf)
+
+    def concat_nhwc(self, xs, misalign=0):
+        """plhip_concat_nhwc_f32 of NCHW fp32 arrays [n, c_i, h_i, w_i]: returns [n, sum c_i * h_i * w_i]."""
+        xs = [np.ascontiguousarray(x, np.float32) for x in xs]
+        n = xs[0].shape[0]
+        ups = [self._up_f32(x, misalign) for x in xs]
+        total = sum(x[0].size for x in xs)
+        ybuf, dy = self._out_buf(n * total, 4, misalign)
+        try:
+            ptrs = (C.c_void_p * len(xs))(*[d for _b, d in ups])
+            ch = (C.c_int64 * len(xs))(*[x.shape[1] for x in xs])
+            hw = (C.c_int64 * len(xs))(*[x.shape[2] * x.shape[3] for x in xs])
+            self.check(self.L.plhip_concat_nhwc_f32(self.h, ptrs, ch, hw, len(xs), n, dy), "concat_nhwc")
+            return self.to_host(dy, (n, total), np.float32)
+        finally:
+            for b in [ybuf] + [b for b, _d in ups]:
+                self.free(b)
+
+    def box_coder_decode(self, prior, target, prior_var=None, variance=None, axis=0, normalized=True, misalign=0):
+        """plhip_box_coder_decode_f32: target [rows, cols, 4]; prior (and prior_var) [cols, 4] with axis 0, [rows, 4] with axis 1;
+        variance: the 4-float attribute, read when prior_var is None."""
+        target = np.ascontiguousarray(target, np.float32)
+        rows, cols = target.shape[:2]
+        bufs = [self._up_f32(prior, misalign), self._up_f32(target, misalign)]
+        if prior_var is not None:
+            bufs.append(self._up_f32(prior_var, misalign))
+        ybuf, dy = self._out_buf(target.size, 4, misalign)
+        try:
+            v4 = (C.c_float * 4)(*[float(v) for v in variance]) if variance is not None else None
+            self.check(self.L.plhip_box_coder_decode_f32(self.h, bufs[0][1], bufs[2][1] if prior_var is not None else None, v4,
+                                                         bufs[1][1], rows, cols, int(axis), int(bool(normalized)), dy), "box_coder_decode")
+            return self.to_host(dy, target.shape, np.float32)
+        finally:
+            for b in [ybuf] + [b for b, _d in bufs]:
+                self.free(b)
+
+    def multiclass_nms(self, boxes, scores, desc, with_index=True, misalign=0):
+        """plhip_multiclass_nms_f32: boxes [N, P, 4], scores in the layout desc's strides name.  Returns the padded device outputs
+        (out [N, keep_top_k, 6], count [N], index [N, keep_top_k] or None)."""
+        n, keep = desc.n, desc.keep_top_k
+        nbytes = self.L.plhip_multiclass_nms_workspace_bytes(C.byref(desc))
+        if nbytes == 0:
+            raise PlhipError("multiclass_nms refused: %s" % self.L.plhip_last_error(None).decode())
+        bufs = [self._up_f32(boxes, misalign), self._up_f32(scores, misalign)]
+        ws = self.malloc(nbytes)
+        obuf, do = self._out_buf(n * keep * 6, 4, 0)
+        ibuf, di = self._out_buf(n * keep, 4, 0)
+        cbuf, dc = self._out_buf(n, 4, 0)
+        try:
+            self.check(self.L.plhip_multiclass_nms_f32(self.h, bufs[0][1], bufs[1][1], C.byref(desc), ws, do, di if with_index else None,
+                                                       dc), "multiclass_nms")
+            return (self.to_host(do, (n, keep, 6), np.float32), self.to_host(dc, (n,), np.int32),
+                    self.to_host(di, (n, keep), np.int32) if with_index else None)
+        finally:
+            for b in [ws, obuf, ibuf, cbuf] + [b for b, _d in bufs]:
+                self.free(b)

@@ -1,5 +1,6 @@
 // plhip_capi_ops.hip — the C ABI (include/plhip.h), part 4 of 4: fc, calib, pooling, softmax, elementwise add, the hard activations,
-// squeeze-excite, concat / split / shuffle_channel, and interp / arg_max.  Argument validation and one launch each.
+// squeeze-excite, concat / split / shuffle_channel, interp / arg_max, and the detection heads (transpose, concat_nhwc, box_coder,
+// multiclass_nms).  Argument validation and one launch each (multiclass_nms: two).
 #include "plhip_capi.h"
 
 #include <vector>
@@ -302,6 +303,111 @@ plhip_status plhip_interp_argmax_f32(plhip_ctx* ctx, const float* x, int n, int 
   if ((int64_t)n * c > ((int64_t)1 << 40) / ((int64_t)out_h * out_w)) return fail(ctx, PLHIP_ERR_UNSUPPORTED, "%s: more than 2^40 elements", who);
   plhip::launch_interp_argmax(plhip::interp_args(x, in_h, in_w, out_h, out_w, method, align_corners, align_mode), n, c, y, i64, ctx->stream);
   LAUNCHCHK(ctx, "interp_argmax");
+  return PLHIP_OK;
+}
+
+// ------------------------------------------------------------------ transpose / concat_nhwc / box_coder / multiclass_nms
+plhip_status plhip_transpose_f32(plhip_ctx* ctx, const float* x, const int64_t* dims, const int* perm, int rank, float* y) {
+  const char* who = "plhip_transpose_f32";
+  if (!ctx || !x || !y) return fail(ctx, PLHIP_ERR_INVALID, "%s: null ctx, x or y", who);
+  if (!dims || !perm) return fail(ctx, PLHIP_ERR_INVALID, "%s: null dims or perm", who);
+  if (rank < 2 || rank > 4) return fail(ctx, PLHIP_ERR_UNSUPPORTED, "%s: rank must be 2, 3 or 4", who);
+  const int64_t most = (int64_t)1 << 40;
+  int64_t total = 1;
+  unsigned seen = 0;
+  for (int k = 0; k < rank; ++k) {
+    if (dims[k] < 1) return fail(ctx, PLHIP_ERR_INVALID, "%s: every dimension must be at least 1", who);
+    if (dims[k] > most / total) return fail(ctx, PLHIP_ERR_UNSUPPORTED, "%s: more than 2^40 elements", who);
+    total *= dims[k];
+    if (perm[k] < 0 || perm[k] >= rank || (seen & (1u << perm[k]))) return fail(ctx, PLHIP_ERR_INVALID, "%s: perm is not a permutation of the axes", who);
+    seen |= 1u << perm[k];
+  }
+  plhip::launch_transpose(x, dims, perm, rank, y, ctx->stream);
+  LAUNCHCHK(ctx, "transpose");
+  return PLHIP_OK;
+}
+
+plhip_status plhip_concat_nhwc_f32(plhip_ctx* ctx, const float* const* xs, const int64_t* channels, const int64_t* hw, int count,
+                                   int64_t n, float* y) {
+  const char* who = "plhip_concat_nhwc_f32";
+  if (!ctx || !xs || !channels || !hw || !y) return fail(ctx, PLHIP_ERR_INVALID, "%s: null ctx, xs, channels, hw or y", who);
+  if (count < 1) return fail(ctx, PLHIP_ERR_INVALID, "%s: count must be at least 1", who);
+  if (n < 1) return fail(ctx, PLHIP_ERR_INVALID, "%s: n must be at least 1", who);
+  const int64_t most = (int64_t)1 << 40;
+  int64_t total = 0;
+  for (int i = 0; i < count; ++i) {
+    if (!xs[i]) return fail(ctx, PLHIP_ERR_INVALID, "%s: null input", who);
+    if (channels[i] < 1 || hw[i] < 1) return fail(ctx, PLHIP_ERR_INVALID, "%s: every extent must be at least 1", who);
+    if (channels[i] > most / hw[i] || channels[i] * hw[i] > most - total) return fail(ctx, PLHIP_ERR_UNSUPPORTED, "%s: more than 2^40 elements", who);
+    total += channels[i] * hw[i];
+  }
+  if (n > most / total) return fail(ctx, PLHIP_ERR_UNSUPPORTED, "%s: more than 2^40 elements", who);
+  plhip::launch_concat_nhwc(xs, channels, hw, count, n, y, ctx->stream);
+  LAUNCHCHK(ctx, "concat_nhwc");
+  return PLHIP_OK;
+}
+
+plhip_status plhip_box_coder_decode_f32(plhip_ctx* ctx, const float* prior, const float* prior_var_or_null,
+                                        const float* variance4_or_null, const float* target, int64_t rows, int64_t cols, int axis,
+                                        int normalized, float* y) {
+  const char* who = "plhip_box_coder_decode_f32";
+  if (!ctx || !prior || !target || !y) return fail(ctx, PLHIP_ERR_INVALID, "%s: null ctx, prior, target or y", who);
+  if (rows < 1 || cols < 1) return fail(ctx, PLHIP_ERR_INVALID, "%s: rows and cols must be at least 1", who);
+  if (axis != 0 && axis != 1) return fail(ctx, PLHIP_ERR_INVALID, "%s: axis must be 0 or 1", who);
+  if (rows > ((int64_t)1 << 38) / cols) return fail(ctx, PLHIP_ERR_UNSUPPORTED, "%s: more than 2^40 elements", who);
+  plhip::BoxCoderArgs a;
+  a.prior = prior; a.pvar = prior_var_or_null; a.target = target; a.y = y;
+  a.var = prior_var_or_null ? 2 : variance4_or_null ? 1 : 0;
+  for (int k = 0; k < 4; ++k) a.variance[k] = a.var == 1 ? variance4_or_null[k] : 1.f;
+  a.rows = rows; a.cols = cols; a.axis = axis; a.normalized = normalized ? 1 : 0;
+  plhip::launch_box_coder_decode(a, ctx->stream);
+  LAUNCHCHK(ctx, "box_coder_decode");
+  return PLHIP_OK;
+}
+
+// the descriptor's checks, shared by the workspace query (ctx == nullptr: the text goes to the calling thread's slot)
+static plhip_status nms_check(plhip_ctx* ctx, const char* who, const plhip_nms_desc* d, int* kmax, int* cap, int* nact) {
+  if (!d) return fail(ctx, PLHIP_ERR_INVALID, "%s: null desc", who);
+  if (d->n < 1 || d->c < 1 || d->p < 1) return fail(ctx, PLHIP_ERR_INVALID, "%s: n, c and p must be at least 1", who);
+  if (d->keep_top_k <= 0) return fail(ctx, PLHIP_ERR_INVALID, "%s: keep_top_k must be positive (it sizes the output)", who);
+  if (!(d->nms_eta >= 1.f)) return fail(ctx, PLHIP_ERR_UNSUPPORTED, "%s: nms_eta < 1 (adaptive threshold) is outside the device kernel", who);
+  if (d->p > 16384) return fail(ctx, PLHIP_ERR_UNSUPPORTED, "%s: more than 16384 priors", who);
+  if (d->score_stride_class < 0 || d->score_stride_prior < 0 ||
+      (int64_t)(d->c - 1) * d->score_stride_class + (int64_t)(d->p - 1) * d->score_stride_prior > (int64_t)d->c * d->p - 1)
+    return fail(ctx, PLHIP_ERR_INVALID, "%s: the score strides leave the image's c * p scores", who);
+  plhip::nms_sizes(d->c, d->p, d->background_label, d->nms_top_k, d->keep_top_k, kmax, cap, nact);
+  if (*kmax > 4096) return fail(ctx, PLHIP_ERR_UNSUPPORTED, "%s: min(nms_top_k, p) above 4096", who);
+  if ((int64_t)*nact * *cap > 16384)
+    return fail(ctx, PLHIP_ERR_UNSUPPORTED, "%s: (classes other than the background) * min(nms_top_k, keep_top_k, p) above 16384", who);
+  if (d->n > 65535 || (int64_t)d->n * d->p >= ((int64_t)1 << 31)) return fail(ctx, PLHIP_ERR_UNSUPPORTED, "%s: n above 65535 or n * p above 2^31", who);
+  return PLHIP_OK;
+}
+
+size_t plhip_multiclass_nms_workspace_bytes(const plhip_nms_desc* desc) {
+  int kmax, cap, nact;
+  if (nms_check(nullptr, "plhip_multiclass_nms_workspace_bytes", desc, &kmax, &cap, &nact)) return 0;
+  const size_t slots = (size_t)desc->n * desc->c;
+  return slots * cap * 8 + slots * 4 + 16;
+}
+
+plhip_status plhip_multiclass_nms_f32(plhip_ctx* ctx, const float* boxes, const float* scores, const plhip_nms_desc* desc,
+                                      void* workspace, float* out, int* index_or_null, int* count) {
+  const char* who = "plhip_multiclass_nms_f32";
+  if (!ctx || !boxes || !scores) return fail(ctx, PLHIP_ERR_INVALID, "%s: null ctx, boxes or scores", who);
+  int kmax, cap, nact;
+  if (plhip_status st = nms_check(ctx, who, desc, &kmax, &cap, &nact)) return st;
+  if (!workspace || !aligned(workspace, 8)) return fail(ctx, PLHIP_ERR_INVALID, "%s: workspace is null or not 8-byte aligned", who);
+  if (!out || !count) return fail(ctx, PLHIP_ERR_INVALID, "%s: null out or count", who);
+  plhip::NmsArgs a;
+  a.boxes = boxes; a.scores = scores; a.out = out; a.index = index_or_null; a.count = count;
+  a.ws_list = (uint64_t*)workspace;
+  a.ws_len = (int*)((char*)workspace + (size_t)desc->n * desc->c * cap * 8);
+  a.C = desc->c; a.P = desc->p; a.ssc = desc->score_stride_class; a.ssp = desc->score_stride_prior;
+  a.bg = desc->background_label; a.sthr = desc->score_threshold; a.nthr = desc->nms_threshold;
+  a.keep = desc->keep_top_k; a.normalized = desc->normalized ? 1 : 0;
+  a.kmax = kmax; a.cap = cap; a.nact = nact;
+  plhip::launch_multiclass_nms(a, desc->n, ctx->stream);
+  LAUNCHCHK(ctx, "multiclass_nms");
   return PLHIP_OK;
 }
 

@@ -476,4 +476,58 @@ void launch_arg_max(const float* x, int64_t outer, int c, int64_t inner, void* y
 // a.x [n][c][ih][iw] -> y [n][oh][ow]: arg_max over c of the resampled tensor, which is never written
 void launch_interp_argmax(const InterpArgs& a, int n, int c, void* y, int i64, hipStream_t s);
 
+// transpose of fp32 tensors of rank <= 4 and the one-launch join of an SSD head: transpose_ops.hip
+struct TransposeArgs {
+  const float* x;
+  float* y;
+  int64_t total;
+  // rows copied whole: output extents and the source stride of every output axis (leading axes of extent 1 fill the rank)
+  int64_t od[4], ss[4];
+  // batch of 2-D transposes: D = the destination's innermost axis (source row stride sd), S = the source's innermost axis
+  // (destination row stride dd), two batch axes with their strides on both sides
+  int64_t D, S, sd, dd, B0, B1, bs[2], bd[2];
+};
+// y = transpose(x, perm): x of extents dims[rank], y axis k is x axis perm[k]
+void launch_transpose(const float* x, const int64_t* dims, const int* perm, int rank, float* y, hipStream_t s);
+struct ConcatNhwcArgs {
+  const float* part[CONCAT_MAX_PARTS];  // NCHW [n][c[p]][hw[p]]
+  int64_t c[CONCAT_MAX_PARTS], hw[CONCAT_MAX_PARTS];
+  int64_t off[CONCAT_MAX_PARTS];        // where operand p starts inside an image of y
+  float* y;                             // [n][stride]
+  int64_t stride, n;
+};
+// xs[i]: NCHW [n][channels[i]][hw[i]] -> y [n][sum channels * hw], operand i as [hw[i]][channels[i]].  One launch per
+// CONCAT_MAX_PARTS operands.
+void launch_concat_nhwc(const float* const* xs, const int64_t* channels, const int64_t* hw, int count, int64_t n, float* y, hipStream_t s);
+
+// box_coder (decode_center_size) and multiclass_nms: detection_ops.hip
+struct BoxCoderArgs {
+  const float* prior;   // [cols][4] (axis 0) | [rows][4] (axis 1)
+  const float* pvar;    // like prior, var == 2 only
+  const float* target;  // [rows][cols][4]
+  float* y;             // [rows][cols][4]
+  v4f variance;         // var == 1: the attribute; var == 0: ones
+  int64_t rows, cols, boxes;
+  int axis, normalized, var, vec;
+};
+void launch_box_coder_decode(BoxCoderArgs a, hipStream_t s);  // fills boxes and vec
+struct NmsArgs {
+  const float* boxes;   // [N][P][4]
+  const float* scores;  // image i, class c, prior p at scores[i * C * P + c * ssc + p * ssp]
+  float* out;           // [N][keep][6]
+  int* index;           // [N][keep] or null
+  int* count;           // [N]
+  uint64_t* ws_list;    // [N][C][cap]: (score bits << 32) | prior of the class's kept boxes, in the order they were kept
+  int* ws_len;          // [N][C]
+  int C, P;
+  int64_t ssc, ssp;
+  int bg;
+  float sthr, nthr;
+  int keep, normalized;
+  int kmax, cap, nact;  // nms_sizes
+  int box_off, kept_off, wcnt_off, removed_off, wcnt_off_b, vec;  // launch_multiclass_nms fills them
+};
+void nms_sizes(int C, int P, int bg, int nms_top_k, int keep_top_k, int* kmax, int* cap, int* nact);
+void launch_multiclass_nms(NmsArgs a, int N, hipStream_t s);
+
 }  // namespace plhip

@@ -6,6 +6,7 @@
 #include "lite/core/mir/fusion/hip_conv_tail_matcher.h"
 #include "lite/kernels/hip/image_frame.h"
 #include "lite/kernels/hip/image_to_tensor.h"
+#include "lite/kernels/hip/prior_box_host.h"
 #include "plhip.h"
 
 #include <cstdio>
@@ -178,6 +179,46 @@ std::vector<int64_t> ArgmaxOutShape(const GraphOp& op, const std::vector<int64_t
   return o;
 }
 
+// the output shapes of the detection-head ops on their operands' shapes `ins`; CHECKs what the kHIP kernels are fatal on
+std::vector<std::vector<int64_t>> DetectionOutShapes(const GraphOp& op, const std::vector<std::vector<int64_t>>& ins) {
+  const std::string who = op.type + " " + op.output;
+  if (op.type == "transpose") {
+    operators::TransposeOpLite::CheckPerm(op.perm, ins[0].size(), who);
+    std::vector<int64_t> o(ins[0].size());
+    for (size_t k = 0; k < o.size(); ++k) o[k] = ins[0][op.perm[k]];
+    return {o};
+  }
+  if (op.type == "reshape") return {operators::ReshapeOpLite::OutputDims(ins[0], op.shape, who)};
+  if (op.type == "prior_box") {
+    CHECK(ins.size() == 2 && ins[0].size() == 4 && ins[1].size() == 4) << who << ": Input and Image must be [N, C, H, W]";
+    CHECK(!op.min_sizes.empty() && (op.max_sizes.empty() || op.max_sizes.size() == op.min_sizes.size()) && op.variances.size() == 4)
+        << who << ": min_sizes, one max_size per min_size or none, and four variances";
+    const int64_t num = kernels::hip::PriorBoxNum(op.min_sizes, op.max_sizes, op.aspect_ratios, op.flip);
+    const std::vector<int64_t> o{ins[0][2], ins[0][3], num, 4};
+    return {o, o};
+  }
+  if (op.type == "box_coder") {
+    CHECK(ins.size() == 2 || ins.size() == 3) << who << ": {PriorBox, TargetBox} or {PriorBox, PriorBoxVar, TargetBox}";
+    CHECK(op.variances.empty() || op.variances.size() == 4) << who << ": the variance attribute has " << op.variances.size() << " values";
+    auto flat = [](std::vector<int64_t> d) { return d.size() == 4 ? std::vector<int64_t>{d[0] * d[1] * d[2], d[3]} : d; };
+    const std::vector<int64_t> pv = ins.size() == 3 ? flat(ins[1]) : std::vector<int64_t>{};
+    operators::BoxCoderOpLite::CheckDims(flat(ins[0]), ins.size() == 3 ? &pv : nullptr, ins.back(), op.axis);
+    return {ins.back()};
+  }
+  CHECK(op.type == "multiclass_nms") << who;
+  CHECK(ins.size() == 2) << who << ": {BBoxes, Scores}";
+  operators::MulticlassNmsParam p;
+  p.background_label = op.background_label; p.nms_top_k = op.nms_top_k; p.keep_top_k = op.keep_top_k; p.nms_eta = op.nms_eta;
+  operators::MulticlassNmsOpLite::CheckCall(ins[0], ins[1], false, p);
+  std::vector<std::vector<int64_t>> o{{ins[0][0], op.keep_top_k, 6}, {ins[0][0]}};
+  if (op.outputs.size() > 2) o.push_back({ins[0][0], op.keep_top_k});
+  return o;
+}
+
+bool IsDetectionOp(const GraphOp& op) {
+  return op.type == "transpose" || op.type == "reshape" || op.type == "prior_box" || op.type == "box_coder" || op.type == "multiclass_nms";
+}
+
 void CheckShuffleGroup(const GraphOp& op, const std::vector<int64_t>& in) {
   CHECK(in.size() >= 2) << "shuffle_channel " << op.output << ": input must have a channel axis";
   CHECK(op.group >= 1 && in[1] % op.group == 0) << "shuffle_channel " << op.output << ": group " << op.group << " does not divide C = " << in[1];
@@ -210,6 +251,11 @@ std::map<std::string, std::vector<int64_t>> GraphBuilder::InferShapes() const {
     } else if (op.type == "shuffle_channel") {
       CheckShuffleGroup(op, in);
       shape[op.output] = in;
+    } else if (IsDetectionOp(op)) {
+      const auto o = DetectionOutShapes(op, ins);
+      const std::vector<std::string> outs = OutputsOf(op);
+      CHECK(o.size() == outs.size()) << op.type << " " << op.output << ": " << outs.size() << " outputs named, " << o.size() << " expected";
+      for (size_t i = 0; i < outs.size(); ++i) shape[outs[i]] = o[i];
     } else if (IsInterp(op)) {
       shape[op.output] = InterpOutShape(op, in);
     } else if (op.type == "arg_max") {
@@ -443,6 +489,7 @@ struct GraphBuilder::Fuser {
   void ConcatCalib();
   void InterpArgmax();
   void InterpCalib();
+  void DetectionHead();
 };
 
 // (A) (C) (B): the conv-tail patterns, matched by the SAME code a Paddle-Lite tree runs as a mir pass
@@ -841,6 +888,58 @@ void GraphBuilder::Fuser::InterpCalib() {
   }
 }
 
+// (O1) a concat(axis 1) all of whose operands come from transpose(0,2,3,1) -> reshape([0,-1,k]) chains of one k becomes concat/nhwc on
+// the chains' NCHW inputs; it runs where the concat ran (every operand exists there).  (O2) a transpose(0,2,1) whose only reader is the
+// Scores operand of a multiclass_nms disappears; the NMS reads the transpose's input through its strides.
+void GraphBuilder::Fuser::DetectionHead() {
+  // the live op step that writes v and is read by nothing but step `reader` (fetches count as readers), or -1
+  auto sole_producer = [&](const std::string& v, const char* type) {
+    if (Uses(v) != 1) return -1;
+    for (size_t t = 0; t < st.size(); ++t)
+      if (!dead[t] && IsOp(static_cast<int>(t), type) && st[t].out == v) return static_cast<int>(t);
+    return -1;
+  };
+  for (size_t i = 0; i < st.size(); ++i) {
+    if (dead[i] || !IsOp(static_cast<int>(i), "concat") || st[i].shuffle_tail || st[i].concat_int8 || st[i].nhwc_k) continue;
+    const auto os = var_shape.find(Op(i).output);
+    if (os == var_shape.end() || os->second.size() != 3 || !(Op(i).axis == 1 || Op(i).axis == -2)) continue;
+    int k = 0;
+    std::vector<int> chain;  // reshape, transpose per operand
+    std::vector<std::string> srcs;
+    bool ok = !st[i].op_inputs.empty();
+    for (size_t q = 0; ok && q < st[i].op_inputs.size(); ++q) {
+      const int r = sole_producer(st[i].op_inputs[q], "reshape");
+      if (r < 0) { ok = false; break; }
+      const std::vector<int>& sh = Op(r).shape;
+      ok = sh.size() == 3 && sh[0] == 0 && sh[1] == -1 && sh[2] > 0 && (k == 0 || sh[2] == k);
+      if (!ok) break;
+      k = sh[2];
+      const int t = sole_producer(st[r].op_inputs[0], "transpose");
+      if (t < 0 || Op(t).perm != std::vector<int>({0, 2, 3, 1})) { ok = false; break; }
+      // one operand twice would make its chain's variables have two uses: the use counts above already refuse it
+      chain.push_back(r);
+      chain.push_back(t);
+      srcs.push_back(st[t].op_inputs[0]);
+    }
+    if (!ok) continue;
+    for (size_t q = 0; q < chain.size(); q += 2) {
+      st[i].via += (q ? "," : "") + st[chain[q + 1]].out + "," + st[chain[q]].out;
+      dead[chain[q]] = dead[chain[q + 1]] = true;
+    }
+    st[i].op_inputs = srcs;
+    st[i].nhwc_k = k;
+  }
+  for (size_t i = 0; i < st.size(); ++i) {
+    if (dead[i] || !IsOp(static_cast<int>(i), "multiclass_nms") || st[i].scores_npc) continue;
+    const int t = sole_producer(st[i].op_inputs[1], "transpose");
+    if (t < 0 || Op(t).perm != std::vector<int>({0, 2, 1})) continue;
+    st[i].via = st[t].out;
+    st[i].op_inputs[1] = st[t].op_inputs[0];
+    st[i].scores_npc = true;
+    dead[t] = true;
+  }
+}
+
 // The rewrites in the one order that gives today's programs.  Each takes over steps that a later one would otherwise match:
 //   * I before H: H would take the image_to_tensor behind an image_resize (and its calib) and leave the resize a launch of its own.
 //   * H before F: F would take the calib behind an image_to_tensor into the stem alone, and the fp32 tensor would still be written.
@@ -856,6 +955,8 @@ void GraphBuilder::Fuser::InterpCalib() {
 //     pools behind a conv long before.
 //   * M and N behind L: they take an arg_max or a calib that reads an interp, which no rewrite above matches.  M first: an interp it
 //     took has no fp32 output for N to quantise (and an interp that a calib reads too has two readers, so M leaves it to N).
+//   * O last: it takes transposes and reshapes, which no rewrite above matches, in front of a concat that K and L left alone (a
+//     concat whose output a calib reads stays L's) or of a multiclass_nms.
 void GraphBuilder::FuseSteps(std::vector<Step>* steps, const std::map<std::string, std::vector<int64_t>>& shapes) {
   Fuser f(*this, steps, shapes);
   f.ConvTails();
@@ -871,6 +972,7 @@ void GraphBuilder::FuseSteps(std::vector<Step>* steps, const std::map<std::strin
   if (fuse_concat_) f.ConcatCalib();
   if (fuse_interp_argmax_) f.InterpArgmax();
   if (fuse_interp_calib_) f.InterpCalib();
+  if (fuse_detection_head_) f.DetectionHead();
   std::vector<Step> kept;
   for (size_t i = 0; i < steps->size(); ++i)
     if (!f.dead[i]) kept.push_back((*steps)[i]);
@@ -902,6 +1004,20 @@ std::string GraphBuilder::OpLine(const Step& s) const {
     AppendNum(&l, "scale", s.calib_scale);
     if (s.drop_f32) l += " -f32";
     return l + " axis=" + std::to_string(op.axis);
+  }
+  auto list_of = [](const char* key, const std::vector<float>& v) {
+    std::string a = std::string(" ") + key + "=";
+    for (size_t i = 0; i < v.size(); ++i) {
+      char buf[32];
+      snprintf(buf, sizeof buf, "%s%.9g", i ? "," : "", v[i]);
+      a += buf;
+    }
+    return a;
+  };
+  if (s.nhwc_k) {  // (O1): the concat step that took the transpose -> reshape chains over
+    std::string l = "concat/nhwc in=";
+    for (size_t i = 0; i < s.op_inputs.size(); ++i) l += (i ? "," : "") + s.op_inputs[i];
+    return l + " out=" + s.out + " k=" + std::to_string(s.nhwc_k) + " via=" + s.via;
   }
   auto interp_attrs = [](const GraphOp& o) {
     std::string a = o.out_h > 0 && o.out_w > 0 ? " size=" + std::to_string(o.out_h) + "x" + std::to_string(o.out_w) : std::string();
@@ -935,6 +1051,32 @@ std::string GraphBuilder::OpLine(const Step& s) const {
   if (op.type == "shuffle_channel") l += " group=" + std::to_string(op.group);
   if (IsInterp(op)) l += interp_attrs(op);
   if (op.type == "arg_max") l += argmax_attrs(op);
+  if (op.type == "transpose" || op.type == "reshape") {
+    const std::vector<int>& v = op.type == "transpose" ? op.perm : op.shape;
+    l += op.type == "transpose" ? " perm=" : " shape=";
+    for (size_t i = 0; i < v.size(); ++i) l += (i ? "," : "") + std::to_string(v[i]);
+  }
+  if (op.type == "prior_box") {
+    l += list_of("min_sizes", op.min_sizes) + list_of("max_sizes", op.max_sizes) + list_of("aspect_ratios", op.aspect_ratios) +
+         list_of("variances", op.variances) + " flip=" + std::to_string(op.flip ? 1 : 0) + " clip=" + std::to_string(op.clip ? 1 : 0);
+    AppendNum(&l, "step_w", op.step_w);
+    AppendNum(&l, "step_h", op.step_h);
+    AppendNum(&l, "offset", op.offset);
+    l += " min_max_aspect_ratios_order=" + std::to_string(op.min_max_aspect_ratios_order ? 1 : 0);
+  }
+  if (op.type == "box_coder") {
+    l += " code_type=decode_center_size axis=" + std::to_string(op.axis) + " normalized=" + std::to_string(op.box_normalized ? 1 : 0);
+    if (op.inputs.size() == 2 && !op.variances.empty()) l += list_of("variance", op.variances);
+  }
+  if (op.type == "multiclass_nms") {
+    l += " background=" + std::to_string(op.background_label);
+    AppendNum(&l, "score_threshold", op.score_threshold);
+    l += " nms_top_k=" + std::to_string(op.nms_top_k);
+    AppendNum(&l, "nms_threshold", op.nms_threshold);
+    AppendNum(&l, "nms_eta", op.nms_eta);
+    l += " keep_top_k=" + std::to_string(op.keep_top_k) + " normalized=" + std::to_string(op.nms_normalized ? 1 : 0) + " count=" + s.outs[1];
+    if (s.scores_npc) l += " scores=npc via=" + s.via;  // (O2)
+  }
   if (op.enable_int8 && s.int8_out) AppendNum(&l, "oscale", s.out_scale);
   if (s.image_feed >= 0) {  // (H1): image_to_tensor + calib taken over, the conv reads the uint8 image
     const FeedDesc& f = feeds_[s.image_feed];
@@ -1069,6 +1211,23 @@ void GraphBuilder::LowerOp(const Step& s, HipPredictor* pred) {
                          s.calib_scale, s.drop_f32);
   } else if (s.concat_int8) {
     pred->AddConcatCalib(s.op_inputs, s.out, op.axis, s.calib_out, s.calib_scale, s.drop_f32);
+  } else if (s.nhwc_k) {
+    pred->AddConcatNhwc(s.op_inputs, s.out, s.nhwc_k);
+  } else if (op.type == "transpose") {
+    pred->AddTranspose(s.op_inputs[0], s.out, op.perm);
+  } else if (op.type == "reshape") {
+    pred->AddReshape(s.op_inputs[0], s.out, op.shape);
+  } else if (op.type == "prior_box") {
+    pred->AddPriorBox(s.op_inputs[0], s.op_inputs[1], s.outs[0], s.outs[1], op.min_sizes, op.max_sizes, op.aspect_ratios, op.variances, op.flip,
+                      op.clip, op.step_w, op.step_h, op.offset, op.min_max_aspect_ratios_order);
+  } else if (op.type == "box_coder") {
+    const bool pv = s.op_inputs.size() == 3;
+    pred->AddBoxCoder(s.op_inputs[0], pv ? s.op_inputs[1] : "", s.op_inputs.back(), s.out, pv ? std::vector<float>() : op.variances, op.axis,
+                      op.box_normalized);
+  } else if (op.type == "multiclass_nms") {
+    CHECK(s.outs.size() >= 2 && s.outs[1] == s.out + "/count") << "multiclass_nms " << s.out << ": the count variable must be <out>/count";
+    pred->AddMulticlassNms(s.op_inputs[0], s.op_inputs[1], s.out, s.outs.size() > 2 ? s.outs[2] : "", op.background_label, op.score_threshold,
+                           op.nms_top_k, op.nms_threshold, op.nms_eta, op.keep_top_k, op.nms_normalized, s.scores_npc);
   } else if (op.type == "concat") {
     pred->AddConcat(s.op_inputs, s.out, op.axis);
   } else if (op.type == "split") {

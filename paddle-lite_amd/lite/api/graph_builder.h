@@ -28,10 +28,12 @@ struct GraphOp {
   std::string type;  // conv2d | depthwise_conv2d | fc | pool2d | elementwise_add | fusion_elementwise_add_activation | softmax |
                      // hard_swish | hard_sigmoid | elementwise_mul (fp32 ops like pool2d; the reference's default parameters) |
                      // concat (N inputs) | split | shuffle_channel (fp32 ops like pool2d) |
-                     // bilinear_interp | nearest_interp | arg_max (fp32 ops like pool2d; arg_max writes int64 / int32 labels)
+                     // bilinear_interp | nearest_interp | arg_max (fp32 ops like pool2d; arg_max writes int64 / int32 labels) |
+                     // transpose | reshape | prior_box | box_coder | multiclass_nms (fp32 ops like pool2d)
   std::vector<std::string> inputs;
   std::string output;                // the first output
-  std::vector<std::string> outputs;  // split: all outputs, outputs[0] == output; empty for every other type
+  std::vector<std::string> outputs;  // split: all outputs, outputs[0] == output; prior_box: {Boxes, Variances}; multiclass_nms:
+                                     // {Out, "<Out>/count"[, Index]}; empty for every other type
   bool enable_int8{false};
   // conv2d / depthwise_conv2d / fc
   std::vector<int8_t> w;
@@ -61,6 +63,19 @@ struct GraphOp {
   // arg_max (ArgmaxParam): along `axis`; dtype -1 / 3 int64 labels, 2 int32
   int dtype{-1};
   bool keepdims{false};
+  // transpose: axis k of the output is axis perm[k] of the input; reshape: the shape attribute (0 copies a dim, one -1 is inferred)
+  std::vector<int> perm, shape;
+  // prior_box (PriorBoxParam): inputs {Input, Image}, outputs {Boxes, Variances}, each [H, W, prior_num, 4]
+  std::vector<float> min_sizes, max_sizes, aspect_ratios, variances;
+  bool flip{true}, clip{false}, min_max_aspect_ratios_order{false};
+  float step_w{0.f}, step_h{0.f}, offset{0.5f};
+  // box_coder, decode_center_size (BoxCoderParam): inputs {PriorBox, TargetBox} or {PriorBox, PriorBoxVar, TargetBox}; without a
+  // PriorBoxVar the 4 values of `variances` (or none); along `axis` (0 | 1)
+  bool box_normalized{true};
+  // multiclass_nms (MulticlassNmsParam): inputs {BBoxes [N, P, 4], Scores [N, C, P]}
+  int background_label{0}, nms_top_k{-1}, keep_top_k{-1};
+  float score_threshold{0.f}, nms_threshold{0.3f}, nms_eta{1.f};
+  bool nms_normalized{true};
 };
 
 class GraphBuilder {
@@ -151,6 +166,17 @@ class GraphBuilder {
   // instructions by far more than the run-to-run spread.
   void set_fuse_interp_argmax(bool on) { fuse_interp_argmax_ = on; }
   void set_fuse_interp_calib(bool on) { fuse_interp_calib_ = on; }
+  //   (O1) a concat along axis 1 ALL of whose operands are chains transpose(0,2,3,1) -> reshape([0,-1,k]) of one k on 4-D tensors,
+  //        each link the only reader of the one before and none fetched
+  //        => ONE concat/nhwc instruction (plhip_concat_nhwc_f32) that reads the NCHW tensors and writes the joined [N, P, k] tensor;
+  //        the transposed and reshaped tensors are no variables of the program any more.  SSD's six-map head: 13 instructions become 1.
+  //   (O2) a transpose(0,2,1) that is not fetched and whose only reader is the Scores operand of a multiclass_nms
+  //        => it disappears: the multiclass_nms instruction reads [N, P, C] through its strides.
+  // Anything else (a second reader or a fetch of a link, another perm, another shape, a concat with one plain operand) keeps the
+  // separate instructions.  With set_fuse(true) only, after N; bit-identical to the instructions it replaces (values are moved; the
+  // NMS reads the same scores).  No program without a transpose changes.  DEFAULT ON: the whole step of ssd_mini_net was measured
+  // faster than the separate instructions in every round, by more than the run-to-run spread.
+  void set_fuse_detection_head(bool on) { fuse_detection_head_ = on; }
   GraphOp& Add(const std::string& type, const std::vector<std::string>& inputs, const std::string& output);
   // Emits the program into `pred`; returns the host-side names of the fetched variables ("<name>/host").
   std::vector<std::string> Lower(HipPredictor* pred);
@@ -177,6 +203,9 @@ class GraphBuilder {
     int argmax_op{-1};        // (M) an interp step that took the arg_max(axis 1) behind it over: arg_max/interp, that op's index in
                               // ops_; `out` the labels, `via` the resampled tensor that is no longer written.  (N) an interp step that
                               // took the calib behind it over carries calib_out / calib_scale / drop_f32
+    int nhwc_k{0};            // (O1) a concat step that took the transpose -> reshape chains of its operands over: concat/nhwc, op_inputs
+                              // the NCHW tensors, `via` the names no longer written
+    bool scores_npc{false};   // (O2) a multiclass_nms step whose Scores operand is the [N, P, C] input of the transpose taken over (`via`)
     bool concat_int8{false};  // (L) a concat step that took the calib behind it over: concat/int8, calib_out / calib_scale / drop_f32
     // kHIP fusions (FuseSteps): tail taken over by an fp32_out conv, int8 max pool behind a fused calib
     std::string res;          // residual operand of the fused elementwise_add ("" = none)
@@ -231,6 +260,7 @@ class GraphBuilder {
   bool fuse_concat_{true};
   bool fuse_interp_argmax_{true};
   bool fuse_interp_calib_{true};
+  bool fuse_detection_head_{true};
   std::vector<FeedDesc> feeds_;
   std::vector<std::string> fetches_;
   std::vector<GraphOp> ops_;

@@ -3,7 +3,9 @@
 
 #include "lite/kernels/hip/calib_tail.h"
 #include "lite/kernels/hip/concat_fusion.h"
+#include "lite/kernels/hip/detection_fusion.h"
 #include "lite/kernels/hip/interp_fusion.h"
+#include "lite/kernels/hip/prior_box_host.h"
 #include "lite/kernels/hip/conv_fusion.h"
 #include "lite/kernels/hip/image_frame.h"
 #include "lite/kernels/hip/se_gate_fusion.h"
@@ -500,6 +502,104 @@ void HipPredictor::AddInterpArgMax(const std::string& op_type, const std::string
   CHECK(ak) << "the picked arg_max kernel does not take the interp fusion";
   ak->SetInterpArgmax(fz);
   Emit(op, std::move(kernel));
+}
+
+void HipPredictor::AddTranspose(const std::string& in, const std::string& out, const std::vector<int>& perm) {
+  auto op = std::make_shared<operators::TransposeOpLite>("transpose");
+  auto& p = op->mutable_param();
+  p.x = Var(in);
+  p.output = Var(out);
+  p.axis = perm;
+  Emit(op, PickKernel("transpose", Place(TARGET(kHIP), PRECISION(kFloat)), "def"));
+}
+
+void HipPredictor::AddReshape(const std::string& in, const std::string& out, const std::vector<int>& shape) {
+  auto op = std::make_shared<operators::ReshapeOpLite>("reshape");
+  auto& p = op->mutable_param();
+  p.x = Var(in);
+  p.output = Var(out);
+  p.shape_vct = shape;
+  Emit(op, PickKernel("reshape", Place(TARGET(kHIP), PRECISION(kFloat)), "def"));
+}
+
+void HipPredictor::AddPriorBox(const std::string& input, const std::string& image, const std::string& boxes, const std::string& variances,
+                               const std::vector<float>& min_sizes, const std::vector<float>& max_sizes,
+                               const std::vector<float>& aspect_ratios, const std::vector<float>& variance, bool flip, bool clip,
+                               float step_w, float step_h, float offset, bool min_max_aspect_ratios_order) {
+  auto op = std::make_shared<operators::PriorBoxOpLite>();
+  auto& p = op->mutable_param();
+  p.input = Var(input);
+  p.image = Var(image);
+  p.boxes = Var(boxes);
+  p.variances = Var(variances);
+  p.min_sizes = min_sizes;
+  p.max_sizes = max_sizes;
+  p.aspect_ratios = aspect_ratios;
+  p.variances_ = variance;
+  p.flip = flip;
+  p.clip = clip;
+  p.step_w = step_w;
+  p.step_h = step_h;
+  p.offset = offset;
+  p.min_max_aspect_ratios_order = min_max_aspect_ratios_order;
+  p.prior_num = kernels::hip::PriorBoxNum(min_sizes, max_sizes, aspect_ratios, flip);
+  Emit(op, PickKernel("prior_box", Place(TARGET(kHIP), PRECISION(kFloat)), "def"));
+}
+
+void HipPredictor::AddBoxCoder(const std::string& prior, const std::string& prior_var, const std::string& target, const std::string& out,
+                               const std::vector<float>& variance, int axis, bool normalized) {
+  auto op = std::make_shared<operators::BoxCoderOpLite>();
+  auto& p = op->mutable_param();
+  p.prior_box = Var(prior);
+  p.prior_box_var = prior_var.empty() ? nullptr : Var(prior_var);
+  p.target_box = Var(target);
+  p.proposals = Var(out);
+  p.code_type = "decode_center_size";
+  p.box_normalized = normalized;
+  p.axis = axis;
+  p.variance = variance;
+  Emit(op, PickKernel("box_coder", Place(TARGET(kHIP), PRECISION(kFloat)), "def"));
+}
+
+void HipPredictor::AddMulticlassNms(const std::string& boxes, const std::string& scores, const std::string& out, const std::string& index,
+                                    int background_label, float score_threshold, int nms_top_k, float nms_threshold, float nms_eta,
+                                    int keep_top_k, bool normalized, bool scores_npc) {
+  auto op = std::make_shared<operators::MulticlassNmsOpLite>();
+  auto& p = op->mutable_param();
+  p.bboxes = Var(boxes);
+  p.scores = Var(scores);
+  p.out = Var(out);
+  p.index = index.empty() ? nullptr : Var(index);
+  if (p.index) p.index->set_precision(PRECISION(kInt32));
+  p.background_label = background_label;
+  p.score_threshold = score_threshold;
+  p.nms_top_k = nms_top_k;
+  p.nms_threshold = nms_threshold;
+  p.nms_eta = nms_eta;
+  p.keep_top_k = keep_top_k;
+  p.normalized = normalized;
+  kernels::hip::HipNmsFusion fz;
+  fz.count = Var(out + "/count");
+  fz.count->set_precision(PRECISION(kInt32));
+  fz.scores_npc = scores_npc;
+  op->set_count(fz.count);
+  op->set_scores_npc(scores_npc);
+  auto kernel = PickKernel("multiclass_nms", Place(TARGET(kHIP), PRECISION(kFloat)), "def");
+  auto* nk = dynamic_cast<kernels::hip::HipNmsFusionKernel*>(kernel.get());
+  CHECK(nk) << "the picked multiclass_nms kernel does not take the count tensor";
+  nk->SetNmsFusion(fz);
+  Emit(op, std::move(kernel));
+}
+
+void HipPredictor::AddConcatNhwc(const std::vector<std::string>& inputs, const std::string& out, int k) {
+  CHECK(k > 0) << "AddConcatNhwc: k " << k;
+  auto op = std::make_shared<operators::ConcatOpLite>();
+  auto& p = op->mutable_param();
+  for (auto& in : inputs) p.x.push_back(Var(in));
+  p.output = Var(out);
+  p.axis = 1;
+  op->set_nhwc_k(k);
+  Emit(op, PickKernel("concat", Place(TARGET(kHIP), PRECISION(kFloat), DATALAYOUT(kNHWC)), "nhwc"));
 }
 
 std::vector<std::string> HipPredictor::KernelNames() {

@@ -124,6 +124,25 @@ class HipPredictor {
   void AddInterpArgMax(const std::string& op_type, const std::string& in, const std::string& out, int out_h, int out_w, float scale,
                        bool align_corners, int align_mode, int dtype, bool keepdims);
 
+  // detection heads (lite/kernels/hip/detection_compute.cc) with the reference's attributes (lite/operators/op_params.h:342, 617, 880,
+  // 910, 941).  AddReshape launches nothing: `out` shares `in`'s memory.  AddPriorBox computes on the host once per shape.
+  void AddTranspose(const std::string& in, const std::string& out, const std::vector<int>& perm);
+  void AddReshape(const std::string& in, const std::string& out, const std::vector<int>& shape);
+  void AddPriorBox(const std::string& input, const std::string& image, const std::string& boxes, const std::string& variances,
+                   const std::vector<float>& min_sizes, const std::vector<float>& max_sizes, const std::vector<float>& aspect_ratios,
+                   const std::vector<float>& variance, bool flip, bool clip, float step_w, float step_h, float offset,
+                   bool min_max_aspect_ratios_order);
+  // decode_center_size; prior_var "" = none: then `variance` (4 values, or empty = none)
+  void AddBoxCoder(const std::string& prior, const std::string& prior_var, const std::string& target, const std::string& out,
+                   const std::vector<float>& variance, int axis, bool normalized);
+  // out [N, keep_top_k, 6] padded with -1; the per-image counts go to the int32 variable "<out>/count"; index "" = none, else
+  // [N, keep_top_k] int32.  scores_npc: `scores` is [N, P, C] (fusion O2: the transpose in front of it folded away)
+  void AddMulticlassNms(const std::string& boxes, const std::string& scores, const std::string& out, const std::string& index,
+                        int background_label, float score_threshold, int nms_top_k, float nms_threshold, float nms_eta, int keep_top_k,
+                        bool normalized, bool scores_npc = false);
+  // fusion O1 (lite/kernels/hip/detection_fusion.h): transpose(0,2,3,1) -> reshape([0,-1,k]) -> concat(axis 1) of NCHW heads in ONE launch
+  void AddConcatNhwc(const std::vector<std::string>& inputs, const std::string& out, int k);
+
   void Run(bool skip_io_copy = false) {
     TargetWrapperHip::SetDevice(device_);
     program_.Run(skip_io_copy);

@@ -344,6 +344,116 @@ int pllite_graph_arg_max(pllite_predictor* p, const char* in, const char* out, i
     op.keepdims = keepdims != 0;
   });
 }
+static std::vector<float> floats_of(const float* v, int n) { return v && n > 0 ? std::vector<float>(v, v + n) : std::vector<float>(); }
+static std::vector<int> ints_of(const int* v, int n) { return v && n > 0 ? std::vector<int>(v, v + n) : std::vector<int>(); }
+static std::string name_or_empty(const char* s) { return s ? s : ""; }
+int pllite_add_transpose(pllite_predictor* p, const char* in, const char* out, const int* perm, int rank) {
+  return guarded([&] {
+    CHECK(in && out && perm) << "pllite_add_transpose: in, out and perm";
+    p->pred.AddTranspose(in, out, ints_of(perm, rank));
+  });
+}
+int pllite_add_reshape(pllite_predictor* p, const char* in, const char* out, const int* shape, int rank) {
+  return guarded([&] {
+    CHECK(in && out && shape) << "pllite_add_reshape: in, out and shape";
+    p->pred.AddReshape(in, out, ints_of(shape, rank));
+  });
+}
+int pllite_add_prior_box(pllite_predictor* p, const char* input, const char* image, const char* boxes, const char* variances,
+                         const float* min_sizes, int n_min, const float* max_sizes, int n_max, const float* aspect_ratios, int n_ar,
+                         const float* variance4, int flip, int clip, float step_w, float step_h, float offset,
+                         int min_max_aspect_ratios_order) {
+  return guarded([&] {
+    CHECK(input && image && boxes && variances && variance4) << "pllite_add_prior_box: input, image, boxes, variances and variance4";
+    p->pred.AddPriorBox(input, image, boxes, variances, floats_of(min_sizes, n_min), floats_of(max_sizes, n_max), floats_of(aspect_ratios, n_ar),
+                        floats_of(variance4, 4), flip != 0, clip != 0, step_w, step_h, offset, min_max_aspect_ratios_order != 0);
+  });
+}
+int pllite_add_box_coder(pllite_predictor* p, const char* prior, const char* prior_var, const char* target, const char* out,
+                         const float* variance4, int axis, int normalized) {
+  return guarded([&] {
+    CHECK(prior && target && out) << "pllite_add_box_coder: prior, target and out";
+    p->pred.AddBoxCoder(prior, name_or_empty(prior_var), target, out, floats_of(variance4, 4), axis, normalized != 0);
+  });
+}
+int pllite_add_multiclass_nms(pllite_predictor* p, const char* boxes, const char* scores, const char* out, const char* index,
+                              int background_label, float score_threshold, int nms_top_k, float nms_threshold, float nms_eta,
+                              int keep_top_k, int normalized, int scores_npc) {
+  return guarded([&] {
+    CHECK(boxes && scores && out) << "pllite_add_multiclass_nms: boxes, scores and out";
+    p->pred.AddMulticlassNms(boxes, scores, out, name_or_empty(index), background_label, score_threshold, nms_top_k, nms_threshold, nms_eta,
+                             keep_top_k, normalized != 0, scores_npc != 0);
+  });
+}
+int pllite_add_concat_nhwc(pllite_predictor* p, const char* const* inputs, int n_inputs, const char* out, int k) {
+  return guarded([&] {
+    CHECK(n_inputs >= 1 && out) << "pllite_add_concat_nhwc: at least one input and an output";
+    p->pred.AddConcatNhwc(names_of(inputs, n_inputs), out, k);
+  });
+}
+int pllite_graph_transpose(pllite_predictor* p, const char* in, const char* out, const int* perm, int rank) {
+  return guarded([&] {
+    CHECK(in && out && perm) << "pllite_graph_transpose: in, out and perm";
+    p->graph.Add("transpose", {in}, out).perm = ints_of(perm, rank);
+  });
+}
+int pllite_graph_reshape(pllite_predictor* p, const char* in, const char* out, const int* shape, int rank) {
+  return guarded([&] {
+    CHECK(in && out && shape) << "pllite_graph_reshape: in, out and shape";
+    p->graph.Add("reshape", {in}, out).shape = ints_of(shape, rank);
+  });
+}
+int pllite_graph_prior_box(pllite_predictor* p, const char* input, const char* image, const char* boxes, const char* variances,
+                           const float* min_sizes, int n_min, const float* max_sizes, int n_max, const float* aspect_ratios, int n_ar,
+                           const float* variance4, int flip, int clip, float step_w, float step_h, float offset,
+                           int min_max_aspect_ratios_order) {
+  return guarded([&] {
+    CHECK(input && image && boxes && variances && variance4) << "pllite_graph_prior_box: input, image, boxes, variances and variance4";
+    auto& op = p->graph.Add("prior_box", {input, image}, boxes);
+    op.outputs = {boxes, variances};
+    op.min_sizes = floats_of(min_sizes, n_min);
+    op.max_sizes = floats_of(max_sizes, n_max);
+    op.aspect_ratios = floats_of(aspect_ratios, n_ar);
+    op.variances = floats_of(variance4, 4);
+    op.flip = flip != 0;
+    op.clip = clip != 0;
+    op.step_w = step_w;
+    op.step_h = step_h;
+    op.offset = offset;
+    op.min_max_aspect_ratios_order = min_max_aspect_ratios_order != 0;
+  });
+}
+int pllite_graph_box_coder(pllite_predictor* p, const char* prior, const char* prior_var, const char* target, const char* out,
+                           const float* variance4, int axis, int normalized) {
+  return guarded([&] {
+    CHECK(prior && target && out) << "pllite_graph_box_coder: prior, target and out";
+    const std::string pv = name_or_empty(prior_var);
+    auto& op = pv.empty() ? p->graph.Add("box_coder", {prior, target}, out) : p->graph.Add("box_coder", {prior, pv, target}, out);
+    op.variances = floats_of(variance4, 4);
+    op.axis = axis;
+    op.box_normalized = normalized != 0;
+  });
+}
+int pllite_graph_multiclass_nms(pllite_predictor* p, const char* boxes, const char* scores, const char* out, const char* index,
+                                int background_label, float score_threshold, int nms_top_k, float nms_threshold, float nms_eta,
+                                int keep_top_k, int normalized) {
+  return guarded([&] {
+    CHECK(boxes && scores && out) << "pllite_graph_multiclass_nms: boxes, scores and out";
+    auto& op = p->graph.Add("multiclass_nms", {boxes, scores}, out);
+    op.outputs = {out, std::string(out) + "/count"};
+    if (!name_or_empty(index).empty()) op.outputs.push_back(index);
+    op.background_label = background_label;
+    op.score_threshold = score_threshold;
+    op.nms_top_k = nms_top_k;
+    op.nms_threshold = nms_threshold;
+    op.nms_eta = nms_eta;
+    op.keep_top_k = keep_top_k;
+    op.nms_normalized = normalized != 0;
+  });
+}
+int pllite_graph_set_fuse_detection_head(pllite_predictor* p, int on) {
+  return guarded([&] { p->graph.set_fuse_detection_head(on != 0); });
+}
 int pllite_graph_set_fuse_interp_argmax(pllite_predictor* p, int on) {
   return guarded([&] { p->graph.set_fuse_interp_argmax(on != 0); });
 }

@@ -122,6 +122,40 @@ int pllite_graph_interp(pllite_predictor* p, const char* op_type, const char* in
 int pllite_graph_arg_max(pllite_predictor* p, const char* in, const char* out, int axis, int dtype, int keepdims);
 int pllite_graph_set_fuse_interp_argmax(pllite_predictor* p, int on);
 int pllite_graph_set_fuse_interp_calib(pllite_predictor* p, int on);
+/* Detection heads (lite/kernels/hip/detection_compute.cc) with the reference's attributes.  transpose: rank 2 .. 4;
+ * reshape: the shape attribute only (0 copies a dim, one -1 is inferred), no launch.  prior_box: Boxes and Variances
+ * [H, W, prior_num, 4], computed on the host once per shape; max_sizes: none or one per min_size; variance: 4 values.  box_coder:
+ * decode_center_size; prior_var NULL / "": the 4 values of variance4, or none where that is NULL.  multiclass_nms: the 3-D score form;
+ * out [N, keep_top_k, 6] padded with -1, the per-image counts in the int32 variable "<out>/count", index (NULL / "": none)
+ * [N, keep_top_k] int32; keep_top_k <= 0, nms_eta < 1 and shapes outside the device kernel's envelope (include/plhip.h) are
+ * refused.  scores_npc (pllite_add_multiclass_nms): scores is [N, P, C].  pllite_add_concat_nhwc: transpose(0,2,3,1) ->
+ * reshape([0,-1,k]) -> concat(axis 1) of NCHW inputs in one launch (concat/nhwc). */
+int pllite_add_transpose(pllite_predictor* p, const char* in, const char* out, const int* perm, int rank);
+int pllite_add_reshape(pllite_predictor* p, const char* in, const char* out, const int* shape, int rank);
+int pllite_add_prior_box(pllite_predictor* p, const char* input, const char* image, const char* boxes, const char* variances,
+                         const float* min_sizes, int n_min, const float* max_sizes, int n_max, const float* aspect_ratios, int n_ar,
+                         const float* variance4, int flip, int clip, float step_w, float step_h, float offset,
+                         int min_max_aspect_ratios_order);
+int pllite_add_box_coder(pllite_predictor* p, const char* prior, const char* prior_var, const char* target, const char* out,
+                         const float* variance4, int axis, int normalized);
+int pllite_add_multiclass_nms(pllite_predictor* p, const char* boxes, const char* scores, const char* out, const char* index,
+                              int background_label, float score_threshold, int nms_top_k, float nms_threshold, float nms_eta,
+                              int keep_top_k, int normalized, int scores_npc);
+int pllite_add_concat_nhwc(pllite_predictor* p, const char* const* inputs, int n_inputs, const char* out, int k);
+int pllite_graph_transpose(pllite_predictor* p, const char* in, const char* out, const int* perm, int rank);
+int pllite_graph_reshape(pllite_predictor* p, const char* in, const char* out, const int* shape, int rank);
+int pllite_graph_prior_box(pllite_predictor* p, const char* input, const char* image, const char* boxes, const char* variances,
+                           const float* min_sizes, int n_min, const float* max_sizes, int n_max, const float* aspect_ratios, int n_ar,
+                           const float* variance4, int flip, int clip, float step_w, float step_h, float offset,
+                           int min_max_aspect_ratios_order);
+int pllite_graph_box_coder(pllite_predictor* p, const char* prior, const char* prior_var, const char* target, const char* out,
+                           const float* variance4, int axis, int normalized);
+int pllite_graph_multiclass_nms(pllite_predictor* p, const char* boxes, const char* scores, const char* out, const char* index,
+                                int background_label, float score_threshold, int nms_top_k, float nms_threshold, float nms_eta,
+                                int keep_top_k, int normalized);
+/* fusion O (the transpose -> reshape -> concat head join in one launch; the transpose in front of multiclass_nms's scores folded
+ * into its strides): on by default, effective with pllite_graph_set_fuse(1) only */
+int pllite_graph_set_fuse_detection_head(pllite_predictor* p, int on);
 int pllite_graph_fetch(pllite_predictor* p, const char* name);
 /* kHIP graph-level fusions (graph_builder.h set_fuse): on by default; 0 = the reference program instruction for instruction. */
 int pllite_graph_set_fuse(pllite_predictor* p, int on);

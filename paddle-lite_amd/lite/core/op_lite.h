@@ -319,11 +319,14 @@ class FusionElementwiseActivationOp : public OpLite {
   mutable FusionElementwiseActivationParam param_;
 };
 
-// concat_op.cc:22-62: every input has the first one's dims outside `axis` (negative: from the back); Out sums the axis
+// concat_op.cc:22-62: every input has the first one's dims outside `axis` (negative: from the back); Out sums the axis.
+// kHIP alias nhwc (fusion O1, lite/kernels/hip/detection_fusion.h): the inputs are the NCHW tensors in front of the
+// transpose(0,2,3,1) -> reshape([0,-1,k]) chains taken over, Out is [N, sum(C * H * W) / k, k].
 class ConcatOpLite : public OpLite {
  public:
   ConcatOpLite() : OpLite("concat") {}
   ConcatParam& mutable_param() { return param_; }
+  void set_nhwc_k(int k) { nhwc_k_ = k; }  // kHIP fusion O1 only
   bool CheckShape() const override {
     CHECK_GE(param_.x.size(), 1UL) << "concat: at least one input";
     CHECK(param_.output) << "concat: output must be set";
@@ -331,6 +334,17 @@ class ConcatOpLite : public OpLite {
   }
   bool InferShapeImpl() const override {
     CHECK(param_.axis_tensor == nullptr) << "concat: kHIP takes the axis attribute only";
+    if (nhwc_k_ > 0) {
+      int64_t rows = 0;
+      for (size_t i = 0; i < param_.x.size(); ++i) {
+        const auto d = param_.x[i]->dims();
+        CHECK(d.size() == 4 && d[0] == param_.x[0]->dims()[0]) << "concat/nhwc: input " << i << " is not [N, C, H, W] of input 0's N";
+        CHECK(d[1] % nhwc_k_ == 0) << "concat/nhwc: " << nhwc_k_ << " does not divide the " << d[1] << " channels of input " << i;
+        rows += d[1] / nhwc_k_ * d[2] * d[3];
+      }
+      param_.output->Resize(std::vector<int64_t>{param_.x[0]->dims()[0], rows, nhwc_k_});
+      return true;
+    }
     auto out = param_.x[0]->dims().Vectorize();
     const int rank = static_cast<int>(out.size());
     const int axis = param_.axis < 0 ? param_.axis + rank : param_.axis;
@@ -350,6 +364,7 @@ class ConcatOpLite : public OpLite {
 
  private:
   mutable ConcatParam param_;
+  int nhwc_k_{0};
 };
 
 // split_op.cc:32-75: num > 0: `num` equal parts of the axis; else sections[i] along it
@@ -494,6 +509,192 @@ class ArgmaxOpLite : public OpLite {
   mutable ArgmaxParam param_;
   InterpolateParam interp_;
   bool has_interp_{false};
+};
+
+// transpose_op.cc: Out axis k is X axis perm[k]; rank 2 to 4 on kHIP.  transpose2's XShape is not written.
+class TransposeOpLite : public OpLite {
+ public:
+  explicit TransposeOpLite(const std::string& type) : OpLite(type) {}
+  TransposeParam& mutable_param() { return param_; }
+  // fatal unless perm is a permutation of 0 .. rank - 1
+  static void CheckPerm(const std::vector<int>& perm, size_t rank, const std::string& who) {
+    CHECK(rank >= 2 && rank <= 4) << who << ": rank " << rank << " outside 2 .. 4";
+    CHECK_EQ(perm.size(), rank) << who << ": the perm has " << perm.size() << " entries for rank " << rank;
+    unsigned seen = 0;
+    for (int a : perm) {
+      CHECK(a >= 0 && a < static_cast<int>(rank) && !(seen & (1u << a))) << who << ": the perm is not a permutation of the axes";
+      seen |= 1u << a;
+    }
+  }
+  bool CheckShape() const override {
+    CHECK(param_.x && param_.output) << op_type_ << ": x / output must be set";
+    return true;
+  }
+  bool InferShapeImpl() const override {
+    const auto in = param_.x->dims().Vectorize();
+    CheckPerm(param_.axis, in.size(), op_type_);
+    std::vector<int64_t> out(in.size());
+    for (size_t k = 0; k < in.size(); ++k) out[k] = in[param_.axis[k]];
+    param_.output->Resize(out);
+    return true;
+  }
+  void AttachKernel(KernelBase* k) override { k->SetParam<TransposeParam>(param_); }
+
+ private:
+  mutable TransposeParam param_;
+};
+
+// reshape_op.cc ValidateShape for shape_vct: 0 copies the input's dim at that place, one -1 is inferred
+class ReshapeOpLite : public OpLite {
+ public:
+  explicit ReshapeOpLite(const std::string& type) : OpLite(type) {}
+  ReshapeParam& mutable_param() { return param_; }
+  static std::vector<int64_t> OutputDims(const std::vector<int64_t>& in, const std::vector<int>& shape, const std::string& who) {
+    int64_t total = 1, rest = 1;
+    for (auto d : in) total *= d;
+    int unknown = -1;
+    std::vector<int64_t> out(shape.size());
+    CHECK(!shape.empty()) << who << ": empty shape";
+    for (size_t i = 0; i < shape.size(); ++i) {
+      if (shape[i] == -1) {
+        CHECK(unknown < 0) << who << ": more than one -1 in the shape";
+        unknown = static_cast<int>(i);
+        continue;
+      }
+      if (shape[i] == 0) {
+        CHECK(i < in.size()) << who << ": 0 at place " << i << " beyond the input's rank";
+        out[i] = in[i];
+      } else {
+        CHECK(shape[i] > 0) << who << ": dim " << shape[i] << " in the shape";
+        out[i] = shape[i];
+      }
+      rest *= out[i];
+    }
+    if (unknown >= 0) {
+      CHECK(rest > 0 && total % rest == 0) << who << ": the shape does not divide the input's " << total << " elements";
+      out[unknown] = total / rest;
+      rest *= out[unknown];
+    }
+    CHECK_EQ(rest, total) << who << ": the shape holds another count than the input";
+    return out;
+  }
+  bool CheckShape() const override {
+    CHECK(param_.x && param_.output) << op_type_ << ": x / output must be set";
+    return true;
+  }
+  bool InferShapeImpl() const override {
+    CHECK(param_.shape_tensor_vct.empty() && !param_.shape_tensor) << op_type_ << ": kHIP takes the shape attribute only";
+    param_.output->Resize(OutputDims(param_.x->dims().Vectorize(), param_.shape_vct, op_type_));
+    return true;
+  }
+  void AttachKernel(KernelBase* k) override { k->SetParam<ReshapeParam>(param_); }
+
+ private:
+  mutable ReshapeParam param_;
+};
+
+// prior_box_op.cc: Boxes and Variances [H, W, prior_num, 4] of the input feature map; prior_num is set by the caller
+class PriorBoxOpLite : public OpLite {
+ public:
+  PriorBoxOpLite() : OpLite("prior_box") {}
+  PriorBoxParam& mutable_param() { return param_; }
+  bool CheckShape() const override {
+    CHECK(param_.input && param_.image && param_.boxes && param_.variances) << "prior_box: input / image / boxes / variances must be set";
+    CHECK_EQ(param_.input->dims().size(), 4UL) << "prior_box: Input must be [N, C, H, W]";
+    CHECK_EQ(param_.image->dims().size(), 4UL) << "prior_box: Image must be [N, C, H, W]";
+    return true;
+  }
+  bool InferShapeImpl() const override {
+    CHECK(param_.prior_num > 0) << "prior_box: prior_num " << param_.prior_num;
+    const auto d = param_.input->dims();
+    const std::vector<int64_t> out{d[2], d[3], param_.prior_num, 4};
+    param_.boxes->Resize(out);
+    param_.variances->Resize(out);
+    return true;
+  }
+  void AttachKernel(KernelBase* k) override { k->SetParam<PriorBoxParam>(param_); }
+
+ private:
+  mutable PriorBoxParam param_;
+};
+
+// box_coder_op.cc, decode_center_size: proposals take TargetBox's dims [rows, cols, 4]; PriorBox is [cols, 4] (axis 0) / [rows, 4]
+class BoxCoderOpLite : public OpLite {
+ public:
+  BoxCoderOpLite() : OpLite("box_coder") {}
+  BoxCoderParam& mutable_param() { return param_; }
+  static void CheckDims(const std::vector<int64_t>& prior, const std::vector<int64_t>* prior_var, const std::vector<int64_t>& target, int axis) {
+    CHECK(target.size() == 3 && target[2] == 4) << "box_coder: TargetBox must be [rows, cols, 4]";
+    CHECK(axis == 0 || axis == 1) << "box_coder: axis " << axis;
+    CHECK(prior.size() == 2 && prior[1] == 4 && prior[0] == target[1 - axis])
+        << "box_coder: PriorBox must be [" << target[1 - axis] << ", 4] for axis " << axis;
+    if (prior_var) CHECK(*prior_var == prior) << "box_coder: PriorBoxVar must have PriorBox's dims";
+  }
+  bool CheckShape() const override {
+    CHECK(param_.prior_box && param_.target_box && param_.proposals) << "box_coder: prior_box / target_box / proposals must be set";
+    return true;
+  }
+  bool InferShapeImpl() const override {
+    CHECK(param_.code_type == "decode_center_size") << "box_coder: kHIP has decode_center_size only, not " << param_.code_type;
+    CHECK(param_.variance.empty() || param_.variance.size() == 4) << "box_coder: the variance attribute has " << param_.variance.size() << " values";
+    // a prior_box output [H, W, A, 4] is read as [H * W * A, 4]
+    auto flat = [](const lite::Tensor* t) {
+      auto d = t->dims().Vectorize();
+      if (d.size() == 4) d = {d[0] * d[1] * d[2], d[3]};
+      return d;
+    };
+    const auto pv = param_.prior_box_var ? flat(param_.prior_box_var) : std::vector<int64_t>{};
+    CheckDims(flat(param_.prior_box), param_.prior_box_var ? &pv : nullptr, param_.target_box->dims().Vectorize(), param_.axis);
+    param_.proposals->Resize(param_.target_box->dims());
+    return true;
+  }
+  void AttachKernel(KernelBase* k) override { k->SetParam<BoxCoderParam>(param_); }
+
+ private:
+  mutable BoxCoderParam param_;
+};
+
+// multiclass_nms_op.cc, the 3-D score form.  kHIP: Out is [N, keep_top_k, 6] padded with -1, Index [N, keep_top_k], and the counts
+// [N] go to the tensor set_count names (lite/kernels/hip/detection_fusion.h); scores_npc: the scores are [N, P, C] (fusion O2)
+class MulticlassNmsOpLite : public OpLite {
+ public:
+  MulticlassNmsOpLite() : OpLite("multiclass_nms") {}
+  MulticlassNmsParam& mutable_param() { return param_; }
+  void set_count(lite::Tensor* t) { count_ = t; }
+  void set_scores_npc(bool v) { scores_npc_ = v; }
+  // fatal on what the kernel refuses; boxes [N, P, 4], scores [N, C, P] ([N, P, C] with npc)
+  static void CheckCall(const std::vector<int64_t>& boxes, const std::vector<int64_t>& scores, bool npc, const MulticlassNmsParam& p) {
+    CHECK(boxes.size() == 3 && boxes[2] == 4) << "multiclass_nms: BBoxes must be [N, P, 4]";
+    CHECK(scores.size() == 3) << "multiclass_nms: kHIP takes the 3-D score form [N, C, P] only";
+    const int64_t c = scores[npc ? 2 : 1], pr = scores[npc ? 1 : 2];
+    CHECK(scores[0] == boxes[0] && pr == boxes[1]) << "multiclass_nms: BBoxes and Scores disagree in N or P";
+    CHECK(p.keep_top_k > 0) << "multiclass_nms: keep_top_k " << p.keep_top_k << " must be positive on kHIP (it sizes the output)";
+    CHECK(p.nms_eta >= 1.f) << "multiclass_nms: nms_eta < 1 (adaptive threshold) is outside the device kernel";
+    const int64_t kmax = p.nms_top_k < 0 || p.nms_top_k > pr ? pr : p.nms_top_k;
+    const int64_t cap = kmax < p.keep_top_k ? kmax : p.keep_top_k;
+    const int64_t nact = c - (p.background_label >= 0 && p.background_label < c ? 1 : 0);
+    CHECK(pr <= 16384 && kmax <= 4096 && nact * cap <= 16384 && boxes[0] <= 65535)
+        << "multiclass_nms: N " << boxes[0] << " C " << c << " P " << pr << " nms_top_k " << p.nms_top_k << " keep_top_k " << p.keep_top_k
+        << " is outside the device kernel's envelope (P <= 16384, min(nms_top_k, P) <= 4096, classes * min(nms_top_k, keep_top_k, P) <= 16384)";
+  }
+  bool CheckShape() const override {
+    CHECK(param_.bboxes && param_.scores && param_.out) << "multiclass_nms: bboxes / scores / out must be set";
+    return true;
+  }
+  bool InferShapeImpl() const override {
+    const auto b = param_.bboxes->dims().Vectorize();
+    CheckCall(b, param_.scores->dims().Vectorize(), scores_npc_, param_);
+    param_.out->Resize(std::vector<int64_t>{b[0], param_.keep_top_k, 6});
+    if (param_.index) param_.index->Resize(std::vector<int64_t>{b[0], param_.keep_top_k});
+    if (count_) count_->Resize(std::vector<int64_t>{b[0]});
+    return true;
+  }
+  void AttachKernel(KernelBase* k) override { k->SetParam<MulticlassNmsParam>(param_); }
+
+ private:
+  mutable MulticlassNmsParam param_;
+  lite::Tensor* count_{nullptr};
+  bool scores_npc_{false};
 };
 
 class SoftmaxOp : public OpLite {

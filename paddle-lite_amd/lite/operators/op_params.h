@@ -3,7 +3,8 @@
 //   WITH_INT8_CONFIG :49-54, IoCopyParam :70, CalibParam :82, FcParam :115-143, SoftmaxParam :319,
 //   ActivationParam :395-419, ConvParam :446-502, PoolParam :539-, ElementwiseParam :643-651,
 //   FusionElementwiseActivationParam :678-680, ShuffleChannelParam :258-263, ConcatParam :369-386, SplitParam :590-608,
-//   InterpolateParam :154-168, ArgmaxParam :821-827.
+//   InterpolateParam :154-168, ArgmaxParam :821-827, ReshapeParam :342-, TransposeParam :617-, BoxCoderParam :880-,
+//   MulticlassNmsParam :910-922, PriorBoxParam :941-.
 // Tensors are NOT owned: params hold raw lite::Tensor* into the caller's scope (conv_op.h:72-74); bias may be null;
 // paddings / dilations are shared_ptrs the op may mutate (UpdatePaddingAndDilation, conv_op.cc:55-81).
 #pragma once
@@ -172,6 +173,75 @@ struct ArgmaxParam : ParamBase {
   int Axis{0};
   int dtype{-1};
   bool keepdims{false};
+};
+
+// reshape / reshape2.  kHIP takes the shape from shape_vct only: shape_tensor_vct and shape_tensor must stay empty
+struct ReshapeParam : ParamBase {
+  const lite::Tensor* x{};
+  std::vector<const lite::Tensor*> shape_tensor_vct{};
+  const lite::Tensor* shape_tensor{};
+  std::vector<int> shape_vct{};
+  lite::Tensor* output{};
+  lite::Tensor* xshape{};
+  bool inplace{false};
+};
+
+// transpose / transpose2
+struct TransposeParam : ParamBase {
+  const lite::Tensor* x{};
+  lite::Tensor* output{};
+  lite::Tensor* xshape{};
+  std::vector<int> axis;
+  bool use_mkldnn{false};
+  std::string data_format{"AnyLayout"};
+};
+
+struct BoxCoderParam : ParamBase {
+  const lite::Tensor* prior_box{};
+  const lite::Tensor* prior_box_var{};
+  const lite::Tensor* target_box{};
+  lite::Tensor* proposals{};
+  std::string code_type{"encode_center_size"};
+  bool box_normalized{true};
+  int axis{0};
+  std::vector<float> variance{};
+};
+
+// kHIP writes out [N, keep_top_k, 6] padded with -1 and the per-image counts into a tensor of its own, which has no field here:
+// lite/kernels/hip/detection_fusion.h
+struct MulticlassNmsParam : ParamBase {
+  const lite::Tensor* bboxes{};
+  const lite::Tensor* scores{};
+  lite::Tensor* out{};
+  lite::Tensor* index{};
+  int background_label{0};
+  float score_threshold{};
+  int nms_top_k{};
+  float nms_threshold{0.3f};
+  float nms_eta{1.0f};
+  int keep_top_k;
+  bool normalized{true};
+};
+
+struct PriorBoxParam : ParamBase {
+  lite::Tensor* input{};
+  lite::Tensor* image{};
+  lite::Tensor* boxes{};
+  lite::Tensor* variances{};
+  bool flip;
+  bool clip;
+  std::vector<float> min_sizes;
+  std::vector<float> max_sizes;
+  std::vector<float> aspect_ratios;
+  std::vector<float> variances_;
+  int img_w{0};
+  int img_h{0};
+  float step_w{0};
+  float step_h{0};
+  float offset{0.5};
+  int prior_num{0};
+  std::vector<std::string> order;
+  bool min_max_aspect_ratios_order{false};
 };
 
 }  // namespace operators

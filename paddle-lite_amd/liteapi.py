@@ -82,6 +82,19 @@ def load():
     L.pllite_add_interp.argtypes = [vp, cs, cs, cs, i32, i32, f32, i32, i32, cs, f32, i32]
     L.pllite_add_arg_max.argtypes = [vp, cs, cs, i32, i32, i32]
     L.pllite_add_interp_arg_max.argtypes = [vp, cs, cs, cs, i32, i32, f32, i32, i32, i32, i32]
+    fp, ip = C.POINTER(f32), C.POINTER(i32)
+    L.pllite_add_transpose.argtypes = [vp, cs, cs, ip, i32]
+    L.pllite_add_reshape.argtypes = [vp, cs, cs, ip, i32]
+    L.pllite_add_prior_box.argtypes = [vp, cs, cs, cs, cs, fp, i32, fp, i32, fp, i32, fp, i32, i32, f32, f32, f32, i32]
+    L.pllite_add_box_coder.argtypes = [vp, cs, cs, cs, cs, fp, i32, i32]
+    L.pllite_add_multiclass_nms.argtypes = [vp, cs, cs, cs, cs, i32, f32, i32, f32, f32, i32, i32, i32]
+    L.pllite_add_concat_nhwc.argtypes = [vp, C.POINTER(cs), i32, cs, i32]
+    L.pllite_graph_transpose.argtypes = [vp, cs, cs, ip, i32]
+    L.pllite_graph_reshape.argtypes = [vp, cs, cs, ip, i32]
+    L.pllite_graph_prior_box.argtypes = [vp, cs, cs, cs, cs, fp, i32, fp, i32, fp, i32, fp, i32, i32, f32, f32, f32, i32]
+    L.pllite_graph_box_coder.argtypes = [vp, cs, cs, cs, cs, fp, i32, i32]
+    L.pllite_graph_multiclass_nms.argtypes = [vp, cs, cs, cs, cs, i32, f32, i32, f32, f32, i32, i32]
+    L.pllite_graph_set_fuse_detection_head.argtypes = [vp, i32]
     L.pllite_graph_fetch.argtypes = [vp, cs]
     L.pllite_graph_set_fuse.argtypes = [vp, i32]
     L.pllite_graph_set_fuse_dwpw.argtypes = [vp, i32]
@@ -245,6 +258,45 @@ class Predictor:
         self._ck(self.L.pllite_add_interp_arg_max(self.h, op_type.encode(), src.encode(), dst.encode(), int(oh), int(ow), float(scale),
                                                   int(align_corners), int(align_mode), int(dtype), int(keepdims)))
 
+    # ---- detection heads (lite/kernels/hip/detection_compute.cc)
+    def add_transpose(self, src, dst, perm):
+        self._ck(self.L.pllite_add_transpose(self.h, src.encode(), dst.encode(), _ints(perm), len(perm)))
+
+    def add_reshape(self, src, dst, shape):
+        """The shape attribute: 0 copies the input's dim, one -1 is inferred.  No launch: dst shares src's memory."""
+        self._ck(self.L.pllite_add_reshape(self.h, src.encode(), dst.encode(), _ints(shape), len(shape)))
+
+    def add_prior_box(self, src, image, boxes, variances, min_sizes, max_sizes=(), aspect_ratios=(), variance=(0.1, 0.1, 0.2, 0.2), flip=True,
+                      clip=False, step_w=0.0, step_h=0.0, offset=0.5, min_max_aspect_ratios_order=False):
+        """Boxes and Variances [H, W, prior_num, 4] of the feature map src for the image; computed on the host once per shape."""
+        self._ck(self.L.pllite_add_prior_box(self.h, src.encode(), image.encode(), boxes.encode(), variances.encode(), *_prior_box_args(
+            min_sizes, max_sizes, aspect_ratios, variance, flip, clip, step_w, step_h, offset, min_max_aspect_ratios_order)))
+
+    def add_box_coder(self, prior, target, dst, prior_var="", variance=None, axis=0, normalized=True):
+        """decode_center_size.  The variance: the prior_var tensor, else the 4 values of `variance`, else none."""
+        self._ck(self.L.pllite_add_box_coder(self.h, prior.encode(), prior_var.encode(), target.encode(), dst.encode(),
+                                             _variance4(variance), int(axis), int(normalized)))
+
+    def add_multiclass_nms(self, boxes, scores, dst, background_label=0, score_threshold=0.0, nms_top_k=-1, nms_threshold=0.3, nms_eta=1.0,
+                           keep_top_k=100, normalized=True, index="", scores_npc=False):
+        """dst [N, keep_top_k, 6] padded with -1, the counts in the int32 variable dst + "/count", index [N, keep_top_k] int32."""
+        self._ck(self.L.pllite_add_multiclass_nms(self.h, boxes.encode(), scores.encode(), dst.encode(), index.encode(), int(background_label),
+                                                  float(score_threshold), int(nms_top_k), float(nms_threshold), float(nms_eta), int(keep_top_k),
+                                                  int(normalized), int(scores_npc)))
+
+    def add_concat_nhwc(self, srcs, dst, k):
+        """transpose(0,2,3,1) -> reshape([0,-1,k]) -> concat(axis 1) of NCHW variables in one launch (concat/nhwc)."""
+        arr = (C.c_char_p * len(srcs))(*[s.encode() for s in srcs])
+        self._ck(self.L.pllite_add_concat_nhwc(self.h, arr, len(srcs), dst.encode(), int(k)))
+
+    def detections(self, name, index=None, suffix="/host"):
+        """The reference's LoD form of a multiclass_nms output whose host copies were fetched: (rows [num_kept, 6], the batch offsets,
+        the index column or None); see detections_lod."""
+        out = self.get_var(name + suffix, np.float32)
+        count = self.get_var(name + "/count" + suffix, np.int32)
+        idx = self.get_var(index + suffix, np.int32) if index else None
+        return detections_lod(out, count, idx)
+
     # ---- graph mode: ops as the optimiser sees them; graph_lower() applies the reference's kernel-pick / cast rules
     def graph_feed(self, name, dims, precision=PREC_FLOAT):
         self._ck(self.L.pllite_graph_feed(self.h, name.encode(), _ia(dims, C.c_int64), len(dims), precision))
@@ -351,6 +403,34 @@ class Predictor:
         (bilinear_interp/int8, nearest_interp/int8)."""
         self._ck(self.L.pllite_graph_set_fuse_interp_calib(self.h, int(on)))
 
+    def graph_transpose(self, src, dst, perm):
+        self._ck(self.L.pllite_graph_transpose(self.h, src.encode(), dst.encode(), _ints(perm), len(perm)))
+
+    def graph_reshape(self, src, dst, shape):
+        self._ck(self.L.pllite_graph_reshape(self.h, src.encode(), dst.encode(), _ints(shape), len(shape)))
+
+    def graph_prior_box(self, src, image, boxes, variances, min_sizes, max_sizes=(), aspect_ratios=(), variance=(0.1, 0.1, 0.2, 0.2), flip=True,
+                        clip=False, step_w=0.0, step_h=0.0, offset=0.5, min_max_aspect_ratios_order=False):
+        self._ck(self.L.pllite_graph_prior_box(self.h, src.encode(), image.encode(), boxes.encode(), variances.encode(), *_prior_box_args(
+            min_sizes, max_sizes, aspect_ratios, variance, flip, clip, step_w, step_h, offset, min_max_aspect_ratios_order)))
+
+    def graph_box_coder(self, prior, target, dst, prior_var="", variance=None, axis=0, normalized=True):
+        self._ck(self.L.pllite_graph_box_coder(self.h, prior.encode(), prior_var.encode(), target.encode(), dst.encode(),
+                                               _variance4(variance), int(axis), int(normalized)))
+
+    def graph_multiclass_nms(self, boxes, scores, dst, background_label=0, score_threshold=0.0, nms_top_k=-1, nms_threshold=0.3, nms_eta=1.0,
+                             keep_top_k=100, normalized=True, index=""):
+        """The count variable is dst + "/count" (fetch it beside dst)."""
+        self._ck(self.L.pllite_graph_multiclass_nms(self.h, boxes.encode(), scores.encode(), dst.encode(), index.encode(), int(background_label),
+                                                    float(score_threshold), int(nms_top_k), float(nms_threshold), float(nms_eta), int(keep_top_k),
+                                                    int(normalized)))
+
+    def graph_set_fuse_detection_head(self, on):
+        """Fusion O (default on; with graph_set_fuse(True) only): (O1) a concat(axis 1) of transpose(0,2,3,1) ->
+        reshape([0,-1,k]) chains becomes one concat/nhwc instruction; (O2) a transpose(0,2,1) in front of multiclass_nms's scores
+        disappears into the kernel's strides."""
+        self._ck(self.L.pllite_graph_set_fuse_detection_head(self.h, int(on)))
+
     def graph_set_fuse_hard_act(self, on):
         """Fusions J1 / J2 / J3 (default off; with graph_set_fuse(True) only): hard_swish / elementwise_mul take the calib[fp32_to_int8]
         behind them over, hard_sigmoid the excite chain calib -> conv 1x1 -> conv 1x1 in front of it."""
@@ -378,7 +458,7 @@ class Predictor:
         return [s for s in buf.value.decode().split("\n") if s]
 
     def graph_lower(self):
-        buf = C.create_string_buffer(1 << 14)
+        buf = C.create_string_buffer(1 << 16)
         self._ck(self.L.pllite_graph_lower(self.h, buf, len(buf)))
         return [s for s in buf.value.decode().split("\n") if s]
 
@@ -454,3 +534,48 @@ class Predictor:
         buf = C.create_string_buffer(1 << 16)
         self._ck(self.L.pllite_kernel_names(self.h, buf, len(buf)))
         return [s for s in buf.value.decode().split("\n") if s]
+
+
+def _ints(v):
+    return (C.c_int * len(v))(*[int(x) for x in v])
+
+
+def _floats(v):
+    return (C.c_float * len(v))(*[float(x) for x in v])
+
+
+def _variance4(v):
+    """The 4-float variance attribute of box_coder as the C API takes it, or None."""
+    if v is None:
+        return None
+    if len(v) != 4:
+        raise ValueError("box_coder: the variance attribute has %d values, not 4" % len(v))
+    return _floats(v)
+
+
+def _prior_box_args(min_sizes, max_sizes, aspect_ratios, variance, flip, clip, step_w, step_h, offset, order):
+    if len(variance) != 4:
+        raise ValueError("prior_box: %d variances, not 4" % len(variance))
+    return (_floats(min_sizes), len(min_sizes), _floats(max_sizes), len(max_sizes), _floats(aspect_ratios), len(aspect_ratios), _floats(variance),
+            int(flip), int(clip), float(step_w), float(step_h), float(offset), int(order))
+
+
+def detections_lod(out, count, index=None):
+    """The reference's output form of multiclass_nms (lite/kernels/host/multiclass_nms_compute.cc:360-418) from the device's padded
+    one: out [N, keep_top_k, 6], count [N], index [N, keep_top_k] or None -> (rows [num_kept, 6], the batch offsets [N + 1], the index
+    column [num_kept, 1] or None).  No detection in any image: rows [[-1]] with offsets [0, 1] without an index output; rows [0, 6],
+    offsets of zeros and index [0, 1] with one."""
+    out = np.asarray(out, np.float32)
+    count = np.asarray(count).astype(np.int64).reshape(-1)
+    if out.ndim != 3 or out.shape[2] != 6 or out.shape[0] != count.size or (count < 0).any() or (count > out.shape[1]).any():
+        raise ValueError("detections_lod: out %r and count %r do not belong together" % (out.shape, count.tolist()))
+    offsets = np.concatenate([[0], np.cumsum(count)]).astype(np.int64)
+    if offsets[-1] == 0:
+        if index is None:
+            return np.array([[-1]], np.float32), np.array([0, 1], np.int64), None
+        return np.zeros((0, 6), np.float32), offsets, np.zeros((0, 1), np.int32)
+    rows = np.concatenate([out[i, :count[i]] for i in range(count.size)], axis=0)
+    if index is None:
+        return rows, offsets, None
+    index = np.asarray(index).reshape(count.size, -1)
+    return rows, offsets, np.concatenate([index[i, :count[i]] for i in range(count.size)]).astype(np.int32)[:, None]

@@ -250,6 +250,81 @@ class _NetGen:
         self.shape[name] = (1, h, w) if keepdims else (h, w)
         return name
 
+    # ---- detection heads: fp32 ops on tensors that are no [c, h, w] feature maps.  self.shape holds their dims without the batch
+    # axis; a tensor without one (prior boxes) is listed in self.batchless and keeps all its dims.  perm / shape / axis are the
+    # op's attributes, over the full dims.
+    def _full(self, v):
+        return tuple(self.shape[v]) if v in getattr(self, "batchless", ()) else (1,) + tuple(self.shape[v])
+
+    def _set_full(self, name, full, batchless):
+        if batchless:
+            self.batchless = getattr(self, "batchless", set()) | {name}
+        self.shape[name] = tuple(full) if batchless else tuple(full[1:])
+        return name
+
+    def transpose(self, name, src, perm):
+        full = self._full(src)
+        assert sorted(perm) == list(range(len(full))) and (src in getattr(self, "batchless", ()) or perm[0] == 0), perm
+        self.ops.append(dict(op="transpose", name=name, src=src, perm=tuple(int(p) for p in perm)))
+        return self._set_full(name, [full[p] for p in perm], src in getattr(self, "batchless", ()))
+
+    def reshape(self, name, src, shape):
+        """The reference's shape attribute: 0 copies the input's dim at that place, one -1 is inferred."""
+        full = self._full(src)
+        batchless = src in getattr(self, "batchless", ())
+        assert batchless or shape[0] == 0, shape
+        out = [full[i] if d == 0 else d for i, d in enumerate(shape)]
+        if -1 in out:
+            out[out.index(-1)] = int(np.prod(full)) // int(np.prod([d for d in out if d != -1]))
+        assert int(np.prod(out)) == int(np.prod(full)), (full, shape)
+        self.ops.append(dict(op="reshape", name=name, src=src, shape=tuple(int(d) for d in shape)))
+        return self._set_full(name, out, batchless)
+
+    def join(self, name, srcs, axis):
+        """concat of fp32 tensors nothing quantises (the joined heads, the prior boxes) along `axis` of their full dims."""
+        fulls = [self._full(v) for v in srcs]
+        batchless = srcs[0] in getattr(self, "batchless", ())
+        out = list(fulls[0])
+        out[axis] = sum(f[axis] for f in fulls)
+        assert all(f[:axis] + f[axis + 1:] == fulls[0][:axis] + fulls[0][axis + 1:] for f in fulls), fulls
+        self.ops.append(dict(op="concat", name=name, srcs=list(srcs), axis=int(axis)))
+        return self._set_full(name, out, batchless)
+
+    def prior_box(self, names, src, image, min_sizes, max_sizes, aspect_ratios, variances=(0.1, 0.1, 0.2, 0.2), flip=True, clip=False,
+                  step_w=0.0, step_h=0.0, offset=0.5, min_max_aspect_ratios_order=False):
+        """Boxes and Variances [H, W, A, 4] of the feature map src; A = (1 + the distinct ratios other than 1, twice with flip) per
+        min_size + one per max_size."""
+        _c, h, w = self.shape[src]
+        ars = [1.0]
+        for a in aspect_ratios:
+            if not any(abs(a - b) < 1e-6 for b in ars):
+                ars += [a, 1.0 / a] if flip else [a]
+        num = len(ars) * len(min_sizes) + len(max_sizes)
+        self.ops.append(dict(op="prior_box", name=names[0], names=list(names), src=src, image=image, min_sizes=tuple(min_sizes),
+                             max_sizes=tuple(max_sizes), aspect_ratios=tuple(aspect_ratios), variances=tuple(variances), flip=bool(flip),
+                             clip=bool(clip), step_w=float(step_w), step_h=float(step_h), offset=float(offset),
+                             min_max_aspect_ratios_order=bool(min_max_aspect_ratios_order)))
+        for n_ in names:
+            self._set_full(n_, (h, w, num, 4), True)
+        return list(names)
+
+    def box_coder(self, name, prior, target, prior_var="", variance=None, axis=0, normalized=True):
+        """decode_center_size of target [P, 4] per image against prior [P, 4]."""
+        self.ops.append(dict(op="box_coder", name=name, prior=prior, prior_var=prior_var, target=target,
+                             variance=None if variance is None else tuple(variance), axis=int(axis), normalized=bool(normalized)))
+        self.shape[name] = self.shape[target]
+        return name
+
+    def multiclass_nms(self, name, boxes, scores, background_label, score_threshold, nms_top_k, nms_threshold, keep_top_k, normalized=True,
+                       nms_eta=1.0, index=""):
+        """name [keep_top_k, 6] per image padded with -1, name + "/count" the per-image counts."""
+        self.ops.append(dict(op="multiclass_nms", name=name, boxes=boxes, scores=scores, background_label=int(background_label),
+                             score_threshold=float(score_threshold), nms_top_k=int(nms_top_k), nms_threshold=float(nms_threshold),
+                             nms_eta=float(nms_eta), keep_top_k=int(keep_top_k), normalized=bool(normalized), index=index))
+        self.shape[name] = (int(keep_top_k), 6)
+        self.shape[name + "/count"] = ()
+        return name
+
     def fc(self, name, src, n):
         c, h, w = self.shape[src]
         k = c * h * w
@@ -561,6 +636,61 @@ def seg_mini_net(seed=58, res=64, num_classes=19):
     return _finish(g, res, x)
 
 
+def ssd_mini_net(seed=59, res=96, num_classes=21, conf_range=12.0):
+    """An SSD-shaped detector (Liu et al. 2016) on a MobileNetV1-style backbone, small enough for the CPU oracle: depthwise-separable
+    blocks to res / 8 (12 x 12 at res 96), / 16, / 32 and a 3x3 conv without padding behind them (1 x 1 at res 96); on each of the
+    four maps a 3x3 pad-1 `loc` conv (A * 4 channels) and `conf` conv (A * num_classes), both linear with fp32 output, and a
+    prior_box with SSD's schedule (sizes from 0.2 to 0.9 of the image, ratios {2} on the first and last map, {2, 3} between:
+    A = 4 / 6).  The heads are joined as the reference's SSD models join them: transpose(0,2,3,1) -> reshape([0,-1,4 | classes]) ->
+    concat(axis 1); the prior boxes and variances reshape([-1,4]) -> concat(axis 0).  box_coder decodes with the prior variances,
+    softmax runs over the classes, transpose(0,2,1) brings the probabilities to [N, C, P] and multiclass_nms (background 0, score
+    threshold 0.01, top 400, IoU 0.45, keep 200, normalized) writes "det" and "det/count".  The first network here whose result
+    is a list of boxes.  Every feature map has a prior_box (an fp32 op) among its readers, so the kernel pick gives its conv the
+    fp32_out kernel and the convs that read it a calib, as for pool2d.  conf_range: the range the class logits are sized over (the
+    wider, the fewer probabilities pass the score threshold).  Random weights give every class some prior with a probability above
+    0.01, so the biases of the LAST class are lowered by 1.5 conf_range on every map: a class the net never predicts, as a trained
+    detector has for most images.  tests/test_detection_host.py states what the NMS of the committed seed then sees."""
+    assert res >= 65, "the last map needs 3 x 3 pixels"
+    g = _NetGen(seed)
+    g.tensor("image", 3, res, res, 1.0 / 127, 73.0)
+    x = g.conv("stem", "image", 16, 3, 2, 1, act=1)
+
+    def block(p, x, cout, stride):
+        c = g.shape[x][0]
+        d = _spread(g, g.conv(p + "_dw", x, c, 3, stride, 1, groups=c, act=1, headroom=1.5), 1.4 * 1.5)
+        return g.conv(p + "_pw", d, cout, 1, 1, 0, act=1)
+
+    x = block("b2", block("b1", x, 32, 2), 64, 2)      # res / 8
+    maps = [x]
+    maps.append(block("b3", maps[-1], 128, 2))          # res / 16
+    maps.append(block("b4", maps[-1], 128, 2))          # res / 32
+    maps.append(g.conv("extra", maps[-1], 64, 3, 1, 0, act=1))
+    m = len(maps)
+    sizes = [res * (0.2 + 0.7 * k / (m - 1)) for k in range(m)] + [float(res)]
+    locs, confs, pboxes, pvars = [], [], [], []
+    for k, f in enumerate(maps):
+        ratios = (2.0,) if k in (0, m - 1) else (2.0, 3.0)
+        a = 2 + 2 * len(ratios)
+        tag = "f%d" % k
+        loc = g.conv(tag + "_loc", f, a * 4, 3, 1, 1, act=0, out_range=2.0)
+        conf = g.conv(tag + "_conf", f, a * num_classes, 3, 1, 1, act=0, out_range=conf_range)
+        g.ops[-1]["bias"][num_classes - 1::num_classes] -= np.float32(1.5 * conf_range)  # channel a * num_classes + class
+        locs.append(g.reshape(tag + "_loc_flat", g.transpose(tag + "_loc_nhwc", loc, (0, 2, 3, 1)), (0, -1, 4)))
+        confs.append(g.reshape(tag + "_conf_flat", g.transpose(tag + "_conf_nhwc", conf, (0, 2, 3, 1)), (0, -1, num_classes)))
+        b, v = g.prior_box([tag + "_prior", tag + "_prior_var"], f, "image", (sizes[k],), (sizes[k + 1],), ratios)
+        pboxes.append(g.reshape(tag + "_prior_flat", b, (-1, 4)))
+        pvars.append(g.reshape(tag + "_prior_var_flat", v, (-1, 4)))
+    loc = g.join("loc", locs, 1)
+    conf = g.join("conf", confs, 1)
+    priors = g.join("priors", pboxes, 0)
+    prior_vars = g.join("prior_vars", pvars, 0)
+    boxes = g.box_coder("boxes", priors, loc, prior_var=prior_vars, axis=0, normalized=True)
+    prob = g.softmax("prob", conf)
+    scores = g.transpose("scores", prob, (0, 2, 1))
+    det = g.multiclass_nms("det", boxes, scores, 0, 0.01, 400, 0.45, 200, normalized=True)
+    return _finish(g, res, det)
+
+
 def concat_calib_bytes(net, batch):
     """Algorithmic bytes of every concat that a calib reads directly or through a max pool, as separate concat and calib
     instructions (17 per concatenated element: 4 + 4 for the move, 4 + 4 + 1 for the calib; counted where the calib reads the pool
@@ -628,7 +758,7 @@ def net_stats(net):
 
 
 def emit_graph(pred, net, batch, fuse=True, fuse_dwpw=None, fuse_dwconv=None, image=None, frame=None, fuse_hard_act=None, fuse_shuffle=None,
-               fuse_concat=None, fuse_interp_argmax=None, fuse_interp_calib=None, fetch=()):
+               fuse_concat=None, fuse_interp_argmax=None, fuse_interp_calib=None, fuse_detection_head=None, fetch=()):
     """Feed the op list to the predictor's graph mode and lower it.  Returns the host name of the output variable.
     image: None = the input is the normalised fp32 NCHW tensor; dict(format, means, scales) = the input is a decoded uint8 image
     [batch, h, w, cs] of that format (liteapi.IMG_*), normalised on the device (Predictor.graph_feed_image).
@@ -648,7 +778,10 @@ def emit_graph(pred, net, batch, fuse=True, fuse_dwpw=None, fuse_dwconv=None, im
     fuse_interp_argmax / fuse_interp_calib: None = the builder's default (on); False = the separate instructions; fusions M (an interp whose only reader is
     arg_max(axis 1) becomes one arg_max/interp instruction) and N (an interp takes the calib that reads it over) of the dense
     prediction ops, each with a switch of its own.
-    fetch: further variables to fetch beside net["output"] (host names: "<name>/host")."""
+    fuse_detection_head: None = the builder's default (on); False = the separate instructions; fusion O of the detection heads (a concat of transpose -> reshape
+    chains becomes one concat/nhwc instruction; the transpose in front of multiclass_nms's scores disappears into its strides).
+    fetch: further variables to fetch beside net["output"] (host names: "<name>/host").  A multiclass_nms output is fetched together
+    with its count variable "<name>/count"."""
     from . import liteapi
     pred.graph_set_fuse(fuse)
     if fuse_dwpw is not None:
@@ -665,6 +798,8 @@ def emit_graph(pred, net, batch, fuse=True, fuse_dwpw=None, fuse_dwconv=None, im
         pred.graph_set_fuse_interp_argmax(fuse_interp_argmax)
     if fuse_interp_calib is not None:
         pred.graph_set_fuse_interp_calib(fuse_interp_calib)
+    if fuse_detection_head is not None:
+        pred.graph_set_fuse_detection_head(fuse_detection_head)
     c, h, w = net["input_shape"]
     if frame is not None:
         assert image is None, "emit_graph: image= and frame= exclude each other"
@@ -705,10 +840,24 @@ def emit_graph(pred, net, batch, fuse=True, fuse_dwpw=None, fuse_dwconv=None, im
             pred.graph_interp(t, o["src"], o["name"], (o["out_h"], o["out_w"]), 0.0, o["align_corners"], o["align_mode"])
         elif t == "arg_max":
             pred.graph_arg_max(o["src"], o["name"], o["axis"], o["dtype"], o["keepdims"])
+        elif t == "transpose":
+            pred.graph_transpose(o["src"], o["name"], o["perm"])
+        elif t == "reshape":
+            pred.graph_reshape(o["src"], o["name"], o["shape"])
+        elif t == "prior_box":
+            pred.graph_prior_box(o["src"], o["image"], o["names"][0], o["names"][1], o["min_sizes"], o["max_sizes"], o["aspect_ratios"],
+                                 o["variances"], o["flip"], o["clip"], o["step_w"], o["step_h"], o["offset"], o["min_max_aspect_ratios_order"])
+        elif t == "box_coder":
+            pred.graph_box_coder(o["prior"], o["target"], o["name"], o["prior_var"], o["variance"], o["axis"], o["normalized"])
+        elif t == "multiclass_nms":
+            pred.graph_multiclass_nms(o["boxes"], o["scores"], o["name"], o["background_label"], o["score_threshold"], o["nms_top_k"],
+                                      o["nms_threshold"], o["nms_eta"], o["keep_top_k"], o["normalized"], o["index"])
         else:
             raise ValueError(t)
     for v in fetch:
         pred.graph_fetch(v)
+    if net["ops"] and net["ops"][-1]["op"] == "multiclass_nms" and net["ops"][-1]["name"] == net["output"]:
+        pred.graph_fetch(net["output"] + "/count")
     pred.graph_fetch(net["output"])
     return net["output"] + "/host"
 

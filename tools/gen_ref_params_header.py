@@ -9,7 +9,8 @@ import os
 import re
 
 STRUCTS = ["ParamBase", "IoCopyParam", "CalibParam", "FcParam", "SoftmaxParam", "ActivationParam", "ConvParam", "PoolParam",
-           "ElementwiseParam", "FusionElementwiseActivationParam", "ShuffleChannelParam", "ConcatParam", "SplitParam", "InterpolateParam", "ArgmaxParam"]
+           "ElementwiseParam", "FusionElementwiseActivationParam", "ShuffleChannelParam", "ConcatParam", "SplitParam", "InterpolateParam", "ArgmaxParam",
+           "ReshapeParam", "TransposeParam", "BoxCoderParam", "MulticlassNmsParam", "PriorBoxParam"]
 
 
 def struct_text(src, name):
