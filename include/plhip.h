@@ -142,6 +142,40 @@ plhip_status plhip_conv2d_int8_fused(plhip_ctx* ctx, const plhip_conv_desc* d, c
  * builder asks before it lets a conv take its tail over. */
 int plhip_conv2d_fused_supported(const plhip_conv_desc* d);
 
+/* ---- conv2d_transpose ----
+ * Replaces: the int8 form of conv2d_transpose, which the reference states in deconv_basic<int8_t, int>
+ * (lite/tests/utils/naive_math_impl.h:538-635: basic_gemm(trans_a) -> col2im -> fill_bias_relu; its ARM kernel,
+ * lite/kernels/arm/conv_transpose_compute.cc, is fp32 only), with the shape rule of lite/operators/conv_transpose_op.cc:45-95.
+ * The descriptor is a plhip_conv_desc whose cout is the OUTPUT channel count and whose filter is [cin][cout / groups][kh][kw]
+ * (IOHW, no flip), plus ConvParam::output_size (lite/operators/op_params.h): out_h / out_w, 0 = the default
+ *   OH = (h - 1) stride_h - pad_top - pad_bottom + dil_h (kh - 1) + 1        (the width alike);
+ * an entry o with OH <= o < OH + stride_h replaces OH.  int32 accumulator
+ *   acc[n, g Mg + m, iy sh - pt + r dh, ix sw - pl + s dw] += x[n, g Cg + c, iy, ix] * w[g Cg + c, m, r, s],
+ * targets outside the output dropped, outputs no tap reaches 0; then plhip_conv2d_int8's epilogue, indexed by output channel.
+ * Two routes (plhip_deconv_impl_name), no workspace, no atomics:
+ *  - "deconv_phase_int8_mfma32x32x32": groups 1, cin % 32 == 0, dilation 1, kh, kw <= 4, stride (1,1) or (2,2), every padding
+ *    < its kernel extent; any cout, n, h, w, output size, output kind and activation.  Per output phase ((oy + pt) % s,
+ *    (ox + pl) % s) a stride-1 conv of the input with the phase's taps on v_mfma_i32_32x32x32_i8; the input rows are staged by
+ *    the kernel itself.  Packed weights: one 32x32 MFMA A fragment per (32-output-channel tile, 32-input-channel chunk, tap),
+ *    lane (m, h) byte j = w[32 chunk + 16 h + j][32 tile + m][r][s], zero for output channels >= cout:
+ *    ceil(cout / 32) * (cin / 32) * kh * kw * 1024 bytes, 16-byte aligned.
+ *  - "deconv_direct_int8": everything else (any groups incl. depthwise, dilation, stride, kernel size, cin), one lane per
+ *    output over its valid taps: the slow path.  Packed weights: the filter itself, cin * cout / groups * kh * kw bytes.
+ * PLHIP_ERR_INVALID: a dimension, stride or dilation < 1, a negative padding, groups that do not divide cin and cout, a
+ * non-positive output, an output size outside [OH, OH + stride), PLHIP_OUT_F32_GAP.  PLHIP_ERR_UNSUPPORTED: cin * h * w or
+ * n * cout * oh * ow >= 2^31.  There is no fused tail.  The call is asynchronous, allocation-free and argument-static
+ * (capturable by plhip_graph_begin). */
+typedef struct {
+  plhip_conv_desc conv;
+  int out_h, out_w; /* ConvParam::output_size, 0 = the default */
+} plhip_deconv_desc;
+plhip_status plhip_deconv_out_dims(const plhip_deconv_desc* d, int* out_h, int* out_w);
+size_t plhip_deconv_packed_weight_bytes(const plhip_deconv_desc* d);
+plhip_status plhip_pack_deconv_weights(plhip_ctx* ctx, const plhip_deconv_desc* d, const int8_t* w_iohw, void* w_packed);
+plhip_status plhip_conv2d_transpose_int8(plhip_ctx* ctx, const plhip_deconv_desc* d, const int8_t* x, const void* w_packed,
+                                         const float* scale, const float* bias, void* y, plhip_out_kind out);
+const char* plhip_deconv_impl_name(const plhip_deconv_desc* d);
+
 /* ---- calib[fp32_to_int8] + conv2d in one launch (graph-level fusion on this target) ----
  * Replaces the instruction pair  calib[fp32_to_int8](scale) ; conv2d 3x3 s2 (Cin <= 3)  at the head of the MobileNet programs
  * (lite/kernels/arm/calib_compute.cc:25-40 -> type_trans.cc:34-187 ; lite/kernels/arm/conv_direct.cc): x_f32 is the calib's
@@ -490,7 +524,8 @@ plhip_status plhip_selftest(plhip_ctx* ctx);
  * cannot change which kernel a benchmark measures.  Keys: the A/B knobs of DESIGN.md 3.6 without their former PLHIP_ prefix
  * ("GEMM_WIDE", "CONV_PATCH", "DW_STAGE", ...).  Each selects one of several kernels or tiles that compute the same result;
  * "DWCONV_FUSED" = 0: plhip_dw_conv1x1_fused_supported refuses every shape, so callers run the two instructions;
- * "CONV_GROUPED" = 0: the grouped 3x3 route takes no descriptor, grouped convs run im2col + one GEMM per group.  A
+ * "CONV_GROUPED" = 0: the grouped 3x3 route takes no descriptor, grouped convs run im2col + one GEMM per group;
+ * "DECONV_ROUTE" = 1: every conv2d_transpose runs the direct route (name, packed bytes, packer and run alike), 0 = automatic.  A
  * `make EXPERIMENTS=1` build also accepts "STAMPS" (in-kernel timelines).  Returns 0, or -1 for an unknown key. ---- */
 int plhip_debug_set(const char* key, int value);
 

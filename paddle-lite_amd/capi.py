@@ -23,6 +23,8 @@ EXPORTS = [
     "plhip_memcpy_d2h", "plhip_memcpy_d2d", "plhip_memset", "plhip_stream_sync", "plhip_event_create",
     "plhip_event_record", "plhip_event_elapsed_ms", "plhip_event_destroy",
     "plhip_conv_packed_weight_bytes", "plhip_pack_conv_weights", "plhip_conv_workspace_bytes",
+    "plhip_deconv_out_dims", "plhip_deconv_packed_weight_bytes", "plhip_pack_deconv_weights", "plhip_conv2d_transpose_int8",
+    "plhip_deconv_impl_name",
     "plhip_conv2d_int8", "plhip_conv2d_int8_fused", "plhip_conv2d_fused_supported", "plhip_conv_impl_name", "plhip_depthwise_conv_int8", "plhip_dwpw_fused_int8", "plhip_dwpw_fused_supported", "plhip_dw_conv1x1_fused_int8", "plhip_dw_conv1x1_fused_supported", "plhip_graph_begin", "plhip_graph_end", "plhip_graph_launch", "plhip_graph_destroy",
     "plhip_fc_packed_weight_bytes", "plhip_pack_fc_weights", "plhip_fc_int8",
     "plhip_calib_f32_to_i8", "plhip_calib_i8_to_f32", "plhip_global_avg_pool_f32", "plhip_softmax_f32",
@@ -61,6 +63,10 @@ class ConvDesc(C.Structure):
                 ("cout", C.c_int), ("kh", C.c_int), ("kw", C.c_int),
                 ("pad", C.c_int * 4), ("stride", C.c_int * 2), ("dil", C.c_int * 2),
                 ("groups", C.c_int), ("act", C.c_int), ("act_alpha", C.c_float)]
+
+
+class DeconvDesc(C.Structure):
+    _fields_ = [("conv", ConvDesc), ("out_h", C.c_int), ("out_w", C.c_int)]
 
 
 class PoolDesc(C.Structure):
@@ -140,6 +146,30 @@ def conv_desc(n, cin, h, w, cout, kh, kw, pad=(0, 0, 0, 0), stride=(1, 1), dil=(
     return d
 
 
+def deconv_desc(n, cin, h, w, cout, kh, kw, pad=(0, 0, 0, 0), stride=(1, 1), dil=(1, 1), groups=1, act=ACT_NONE, alpha=0.0,
+                output_size=(0, 0)):
+    """plhip_deconv_desc: conv_desc's fields with cout the OUTPUT channels (filter [cin][cout / groups][kh][kw]) and
+    output_size (0 = the default of that dimension)."""
+    d = DeconvDesc()
+    d.conv = conv_desc(n, cin, h, w, cout, kh, kw, pad, stride, dil, groups, act, alpha)
+    d.out_h, d.out_w = int(output_size[0]), int(output_size[1])
+    return d
+
+
+def deconv_out_hw(d):
+    """plhip_deconv_out_dims (host only); raises PlhipError with the library's text for a descriptor it refuses."""
+    L = load()
+    oh, ow = C.c_int(), C.c_int()
+    st = L.plhip_deconv_out_dims(C.byref(d), C.byref(oh), C.byref(ow))
+    if st != 0:
+        raise PlhipError("plhip_deconv_out_dims failed (%d): %s" % (st, L.plhip_last_error(None).decode()))
+    return oh.value, ow.value
+
+
+def deconv_impl_name(d):
+    return load().plhip_deconv_impl_name(C.byref(d)).decode()
+
+
 def out_hw(d):
     keh = d.dil[0] * (d.kh - 1) + 1
     kew = d.dil[1] * (d.kw - 1) + 1
@@ -158,7 +188,7 @@ _lib = None
 # the library's knob table (plhip_capi_ctx.hip); STAMPS exists in a `make EXPERIMENTS=1` build only, a default one refuses it.
 KNOBS = ("STEM_MFMA", "CONV_PATCH", "CONV_PATCH_S2", "STEM7", "DW_STAGE", "DW_STAGE_NP2", "DW_FASTV", "DW5_DIRECT", "DW_RS1",
          "DW_RS2", "GEMM_VARIANT", "GEMM_AREG", "GEMM_MA", "SUBSAMPLE_1X1", "GEMM_TR", "TR_CFG", "GEMM_WIDE", "WIDE_NTT", "FC_MFMA",
-         "IMPLICIT_GEMM", "FUSED_STREAM", "FUSED_SMALL", "DWCONV_FUSED", "CONV_GROUPED", "STAMPS")
+         "IMPLICIT_GEMM", "FUSED_STREAM", "FUSED_SMALL", "DWCONV_FUSED", "CONV_GROUPED", "DECONV_ROUTE", "STAMPS")
 KNOBS_SET = {}
 
 
@@ -238,6 +268,13 @@ def load():
     L.plhip_conv2d_calib_supported.argtypes = [C.POINTER(ConvDesc)]
     L.plhip_conv2d_fused_supported.argtypes = [C.POINTER(ConvDesc)]
     L.plhip_conv2d_calib_int8.argtypes = [vp, C.POINTER(ConvDesc), vp, f32, vp, vp, vp, vp, i32]
+    L.plhip_deconv_out_dims.argtypes = [C.POINTER(DeconvDesc), C.POINTER(i32), C.POINTER(i32)]
+    L.plhip_deconv_packed_weight_bytes.argtypes = [C.POINTER(DeconvDesc)]
+    L.plhip_deconv_packed_weight_bytes.restype = sz
+    L.plhip_pack_deconv_weights.argtypes = [vp, C.POINTER(DeconvDesc), vp, vp]
+    L.plhip_conv2d_transpose_int8.argtypes = [vp, C.POINTER(DeconvDesc), vp, vp, vp, vp, vp, i32]
+    L.plhip_deconv_impl_name.argtypes = [C.POINTER(DeconvDesc)]
+    L.plhip_deconv_impl_name.restype = C.c_char_p
     L.plhip_image_to_tensor_f32.argtypes = [vp, C.POINTER(ImageDesc), vp, vp]
     L.plhip_image_to_tensor_i8.argtypes = [vp, C.POINTER(ImageDesc), vp, vp, f32]
     L.plhip_image_resize_tables.argtypes = [i32, i32, vp, vp]
@@ -405,6 +442,30 @@ class Context:
         for p in tmp + ([ds] if scale is not None else []) + ([db] if bias is not None else []):
             self.free(p)
         return y
+
+    def conv2d_transpose(self, d, x, w, scale, bias, out_kind, misalign=0, sentinel=None):
+        """plhip_conv2d_transpose_int8 on host arrays: x [n, cin, h, w], w [cin, cout / groups, kh, kw] (packed here).  misalign:
+        y starts that many BYTES into its buffer; sentinel: a byte value the buffer is filled with first, then the result is
+        (y, the bytes in front of and behind y)."""
+        oh, ow = deconv_out_hw(d)
+        c = d.conv
+        dx = self.to_device(np.ascontiguousarray(x, np.int8))
+        dw = self.to_device(np.ascontiguousarray(w, np.int8))
+        ds = self.to_device(np.ascontiguousarray(scale, np.float32)) if scale is not None else C.c_void_p()
+        db = self.to_device(np.ascontiguousarray(bias, np.float32)) if bias is not None else C.c_void_p()
+        nbytes = c.n * c.cout * oh * ow * (1 if out_kind == OUT_I8 else 4)
+        dy = self.to_device(np.full(nbytes + misalign + 64, 0 if sentinel is None else sentinel, np.uint8))
+        dwp = self.malloc(max(1, self.L.plhip_deconv_packed_weight_bytes(C.byref(d))))
+        self.check(self.L.plhip_pack_deconv_weights(self.h, C.byref(d), dw, dwp), "pack_deconv")
+        self.check(self.L.plhip_conv2d_transpose_int8(self.h, C.byref(d), dx, dwp, ds, db, C.c_void_p(dy.value + misalign), out_kind),
+                   "conv2d_transpose")
+        raw = self.to_host(dy, (nbytes + misalign + 64,), np.uint8)
+        for p in [dx, dw, dy, dwp] + ([ds] if scale is not None else []) + ([db] if bias is not None else []):
+            self.free(p)
+        y = raw[misalign:misalign + nbytes].copy().view(_OUT_DTYPE[out_kind]).reshape(c.n, c.cout, oh, ow)
+        if sentinel is None:
+            return y
+        return y, np.concatenate([raw[:misalign], raw[misalign + nbytes:]])
 
     def conv2d_calib(self, d, x_f32, calib_scale, w, scale, bias, out_kind):
         """plhip_conv2d_calib_int8 on host arrays: calib[fp32_to_int8](calib_scale) + conv2d in one launch."""

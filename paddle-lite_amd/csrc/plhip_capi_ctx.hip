@@ -211,7 +211,7 @@ Knob g_knobs[] = {
     {"DW_RS1", 0, false}, {"DW_RS2", 0, false}, {"GEMM_VARIANT", 0, false}, {"GEMM_AREG", 0, false}, {"GEMM_MA", 0, false},
     {"SUBSAMPLE_1X1", 0, false}, {"GEMM_TR", 0, false}, {"TR_CFG", 0, false},
     {"GEMM_WIDE", 0, false}, {"WIDE_NTT", 0, false}, {"FC_MFMA", 0, false}, {"IMPLICIT_GEMM", 0, false}, {"FUSED_STREAM", 0, false}, {"FUSED_SMALL", 0, false}, {"DWCONV_FUSED", 0, false},
-    {"CONV_GROUPED", 0, false},
+    {"CONV_GROUPED", 0, false}, {"DECONV_ROUTE", 0, false},
 #ifdef PLHIP_EXPERIMENTS
     {"STAMPS", 0, false},
 #endif

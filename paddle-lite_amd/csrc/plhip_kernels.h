@@ -6,6 +6,7 @@
 
 #include <type_traits>
 
+#include "deconv_plan.h"
 #include "dw_plan.h"
 #include "gemm_plan.h"
 #include "plhip_device.h"
@@ -158,6 +159,26 @@ void launch_pack_conv_grouped3x3(const int8_t* w_oihw, int8_t* wp, int cin, int 
 // fills the plan from (n, cin, oh, ow, stride); false = more blocks than a grid holds
 bool conv_grouped3x3_plan(GroupedArgs* a);
 void launch_conv_grouped3x3(const GroupedArgs& a, int out, hipStream_t s);
+
+// conv2d_transpose (deconv_i8.hip): the MFMA phase kernel and the direct kernel share the argument block
+struct DeconvArgs {
+  const int8_t* x;     // [n][cin][h][w]: the phase kernel stages its rows itself, zero borders included
+  const int8_t* wp;    // phase: packed A fragments [cout / 32 M tiles][cin / 32 chunks][kh * kw taps][64 lanes][16 B]
+                       // (launch_pack_deconv_phase); direct: the filter itself, [cin][cout / groups][kh][kw]
+  void* y;             // [n][cout][oh][ow] int8 / fp32 / int32
+  const float* scale;  // [cout] folded per-channel scale (unused for I32)
+  const float* bias;   // [cout] or nullptr
+  int n, cin, cout, h, w, oh, ow, kh, kw, pt, pl, sh, sw, dh, dw, groups;
+  int act;
+  float alpha;
+  // launch plan of the phase kernel (deconv_phase_plan, deconv_plan.h; launch_deconv_phase's caller copies it in)
+  int NCH, MT, TY, TX, NV, NUq, TR, CWq, bands, nseg, IR, WQ, half;
+  unsigned nblocks, nblocks_per_xcd;
+  size_t lds;
+};
+void launch_pack_deconv_phase(const int8_t* w_iohw, int8_t* wp, const DeconvProblem& p, hipStream_t s);
+void launch_deconv_phase(const DeconvArgs& a, int out, hipStream_t s);
+void launch_deconv_direct(const DeconvArgs& a, int out, hipStream_t s);
 
 struct Im2colArgs {
   const int8_t* x;

@@ -108,6 +108,30 @@ std::vector<int64_t> ConvOutShape(const GraphOp& op, const std::vector<int64_t>&
   return {in[0], op.w_dims[0], (in[2] + pd[0] + pd[1] - keh) / op.conv.strides[0] + 1, (in[3] + pd[2] + pd[3] - kew) / op.conv.strides[1] + 1};
 }
 
+// Output shape of a conv2d_transpose on the NCHW shape `in` (conv_transpose_op.cc:43-96); CHECKs what the kHIP kernel is fatal on
+std::vector<int64_t> ConvTransposeOutShape(const GraphOp& op, const std::vector<int64_t>& in) {
+  const std::string who = "conv2d_transpose " + op.output;
+  const std::vector<int> pd = Pad4(op.conv.paddings);
+  CHECK(ConvSizesOk(op, pd)) << who << ": a 4-D filter, 2 or 4 paddings, 2 strides, 2 dilations and explicit padding";
+  CHECK(in.size() == 4) << who << ": input " << DimsStr(in) << " is not [N, C, H, W]";
+  CHECK(op.conv.groups >= 1 && in[1] % op.conv.groups == 0 && in[1] == op.w_dims[0])
+      << who << ": the filter's first extent " << op.w_dims[0] << " must be the input's " << in[1] << " channels, divisible by groups " << op.conv.groups;
+  CHECK(op.conv.output_size.empty() || op.conv.output_size.size() == 2) << who << ": output_size has " << op.conv.output_size.size() << " entries";
+  std::vector<int64_t> o{in[0], op.w_dims[1] * op.conv.groups};
+  for (int i = 0; i < 2; ++i) {
+    CHECK(op.conv.strides[i] >= 1 && op.conv.dilations[i] >= 1 && pd[2 * i] >= 0 && pd[2 * i + 1] >= 0) << who << ": stride / dilation < 1 or a negative padding";
+    int64_t e = (in[i + 2] - 1) * op.conv.strides[i] - pd[2 * i] - pd[2 * i + 1] + op.conv.dilations[i] * (op.w_dims[i + 2] - 1) + 1;
+    CHECK(e >= 1) << who << ": the output extent " << e << " is empty";
+    if (!op.conv.output_size.empty()) {
+      const int64_t want = op.conv.output_size[i];
+      CHECK(want >= e && want < e + op.conv.strides[i]) << who << ": output_size " << want << " outside [" << e << ", " << e + op.conv.strides[i] << ")";
+      e = want;
+    }
+    o.push_back(e);
+  }
+  return o;
+}
+
 // concat_op.cc:22-62 on the operands' shapes; CHECKs that they differ along the axis only
 std::vector<int64_t> ConcatOutShape(const GraphOp& op, const std::vector<std::vector<int64_t>>& ins) {
   std::vector<int64_t> o = ins[0];
@@ -263,6 +287,8 @@ std::map<std::string, std::vector<int64_t>> GraphBuilder::InferShapes() const {
     } else if (op.type == "conv2d" || op.type == "depthwise_conv2d") {
       const std::vector<int64_t> o = ConvOutShape(op, in);
       if (!o.empty()) shape[op.output] = o;
+    } else if (op.type == "conv2d_transpose") {
+      shape[op.output] = ConvTransposeOutShape(op, in);
     } else if (op.type == "pool2d") {
       const std::vector<int> pd = Pad4(op.pool_paddings);
       if (in.size() != 4 || pd.size() != 4) continue;
@@ -627,6 +653,7 @@ void GraphBuilder::Fuser::PropagateShapes() {
     const std::vector<int64_t> in = it->second;
     std::vector<int64_t> o;
     if (op.type == "conv2d" || op.type == "depthwise_conv2d") o = ConvOutShape(op, in);
+    if (op.type == "conv2d_transpose") o = ConvTransposeOutShape(op, in);
     for (const char* same : kSameShapeOps)
       if (op.type == same) o = in;
     if (op.type == "concat") {  // every operand's shape must have come through
@@ -1049,6 +1076,8 @@ std::string GraphBuilder::OpLine(const Step& s) const {
     for (size_t i = 0; i < op.sections.size(); ++i) l += (i ? "," : "") + std::to_string(op.sections[i]);
   }
   if (op.type == "shuffle_channel") l += " group=" + std::to_string(op.group);
+  if (op.type == "conv2d_transpose" && !op.conv.output_size.empty())
+    l += " output_size=" + std::to_string(op.conv.output_size[0]) + "x" + std::to_string(op.conv.output_size[1]);
   if (IsInterp(op)) l += interp_attrs(op);
   if (op.type == "arg_max") l += argmax_attrs(op);
   if (op.type == "transpose" || op.type == "reshape") {
@@ -1182,6 +1211,11 @@ void GraphBuilder::LowerOp(const Step& s, HipPredictor* pred) {
   if (op.type == "conv2d" || op.type == "depthwise_conv2d") {
     CHECK(op.enable_int8) << "kHIP has int8 conv kernels only";
     pred->AddConv(op.type, s.op_inputs[0], s.out, op.w.data(), op.w_dims, bias, LoweredConvAttrs(s));
+  } else if (op.type == "conv2d_transpose") {
+    CHECK(op.enable_int8) << "kHIP has int8 conv2d_transpose kernels only";
+    CHECK(s.res.empty() && s.calib_out.empty() && s.pw_op < 0 && !(s.in_calib_scale > 0.f) && s.image_feed < 0 && !s.drop_f32)
+        << "conv2d_transpose " << s.out << ": no rewrite of FuseSteps may hand it a tail or a front";
+    pred->AddConvTranspose(s.op_inputs[0], s.out, op.w.data(), op.w_dims, bias, LoweredConvAttrs(s));
   } else if (op.type == "fc") {
     CHECK(op.enable_int8) << "kHIP has int8 fc kernels only";
     pred->AddFc(s.op_inputs[0], s.out, op.w.data(), static_cast<int>(op.w_dims[0]), static_cast<int>(op.w_dims[1]), bias,

@@ -25,7 +25,7 @@ namespace paddle {
 namespace lite {
 
 struct GraphOp {
-  std::string type;  // conv2d | depthwise_conv2d | fc | pool2d | elementwise_add | fusion_elementwise_add_activation | softmax |
+  std::string type;  // conv2d | depthwise_conv2d | conv2d_transpose (w [cin][cout / groups][kh][kw], conv.output_size) | fc | pool2d | elementwise_add | fusion_elementwise_add_activation | softmax |
                      // hard_swish | hard_sigmoid | elementwise_mul (fp32 ops like pool2d; the reference's default parameters) |
                      // concat (N inputs) | split | shuffle_channel (fp32 ops like pool2d) |
                      // bilinear_interp | nearest_interp | arg_max (fp32 ops like pool2d; arg_max writes int64 / int32 labels) |

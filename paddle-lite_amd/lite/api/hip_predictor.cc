@@ -214,6 +214,40 @@ void HipPredictor::AddConv(const std::string& op_type, const std::string& in, co
   Emit(op, std::move(kernel));
 }
 
+void HipPredictor::AddConvTranspose(const std::string& in, const std::string& out, const int8_t* w, const std::vector<int64_t>& w_dims,
+                                    const float* bias, const ConvAttrs& a) {
+  CHECK(a.residual.empty() && a.calib_out.empty() && !a.pw_w && !(a.in_calib_scale > 0.f) && a.image_format < 0)
+      << "conv2d_transpose takes no kHIP fusion";
+  CHECK_EQ(w_dims.size(), 4UL);
+  auto op = std::make_shared<operators::ConvTransposeOpLite>();
+  auto& p = op->mutable_param();
+  size_t wn = 1;
+  for (auto d : w_dims) wn *= static_cast<size_t>(d);
+  const int64_t cout = w_dims[1] * a.groups;
+  p.x = Var(in);
+  p.output = Var(out);
+  p.filter = NewParam(w, wn, w_dims, PRECISION(kInt8));
+  p.bias = bias ? NewParam(bias, static_cast<size_t>(cout) * 4, {cout}, PRECISION(kFloat)) : nullptr;
+  p.strides = a.strides;
+  p.paddings = std::make_shared<std::vector<int>>(a.paddings);
+  p.dilations = std::make_shared<std::vector<int>>(a.dilations);
+  p.groups = a.groups;
+  p.output_size = a.output_size;
+  p.enable_int8 = true;
+  p.input_scale = a.input_scale;
+  p.output_scale = a.output_scale;
+  p.weight_scale = a.weight_scale;
+  if (a.act != 0) {
+    p.activation_param.has_active = true;
+    p.activation_param.active_type = static_cast<lite_api::ActivationType>(a.act);
+    if (a.act == 1) p.fuse_relu = true;
+    if (a.act == 2) p.activation_param.Relu_clipped_coef = a.act_coef;
+    if (a.act == 4) p.activation_param.Leaky_relu_alpha = a.act_coef;
+  }
+  op->set_padding_algorithm(a.padding_algorithm);
+  Emit(op, PickKernel("conv2d_transpose", Place(TARGET(kHIP), PRECISION(kInt8)), a.int8_out ? "int8_out" : "fp32_out"));
+}
+
 void HipPredictor::AddFc(const std::string& in, const std::string& out, const int8_t* w, int k, int n, const float* bias,
                          float input_scale, const std::vector<float>& weight_scale, float output_scale, bool int8_out,
                          bool relu) {

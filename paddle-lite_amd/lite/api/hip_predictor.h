@@ -31,6 +31,7 @@ struct ConvAttrs {
   std::vector<float> weight_scale;
   bool int8_out{true};
   std::string padding_algorithm{""};
+  std::vector<int> output_size;  // conv2d_transpose only (ConvParam::output_size): empty, or {h, w}
   // kHIP fused tail of an fp32_out conv (op_params.h ConvParam, graph_builder.h): variable names, "" = none
   std::string residual, calib_out;
   bool residual_relu{false}, drop_fp32{false};
@@ -75,6 +76,10 @@ class HipPredictor {
                       const float* scales, float calib_scale);
   void AddConv(const std::string& op_type, const std::string& in, const std::string& out, const int8_t* w,
                const std::vector<int64_t>& w_dims, const float* bias, const ConvAttrs& attrs);
+  // conv2d_transpose: w [cin][cout / groups][kh][kw], bias per output channel (cout = w_dims[1] * groups); of `attrs` the conv's
+  // own fields and output_size are read, there is no fused form
+  void AddConvTranspose(const std::string& in, const std::string& out, const int8_t* w, const std::vector<int64_t>& w_dims,
+                        const float* bias, const ConvAttrs& attrs);
   void AddFc(const std::string& in, const std::string& out, const int8_t* w, int k, int n, const float* bias,
              float input_scale, const std::vector<float>& weight_scale, float output_scale, bool int8_out, bool relu);
   void AddGlobalAvgPool(const std::string& in, const std::string& out);

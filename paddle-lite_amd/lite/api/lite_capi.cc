@@ -175,6 +175,32 @@ int pllite_graph_conv(pllite_predictor* p, const char* op_type, const char* in, 
     a.padding_algorithm = padding_algorithm ? padding_algorithm : "";
   });
 }
+int pllite_graph_conv2d_transpose(pllite_predictor* p, const char* in, const char* out, const int8_t* w, const int64_t* w_dims,
+                                  const float* bias, const int* strides, const int* paddings, int n_paddings, const int* dilations,
+                                  int groups, int act, float act_coef, float input_scale, const float* weight_scale,
+                                  int n_weight_scale, const int* output_size) {
+  return guarded([&] {
+    CHECK(groups >= 1) << "pllite_graph_conv2d_transpose: groups " << groups;
+    auto& op = p->graph.Add("conv2d_transpose", {in}, out);
+    op.enable_int8 = true;
+    op.w_dims.assign(w_dims, w_dims + 4);
+    size_t wn = 1;
+    for (auto d : op.w_dims) wn *= static_cast<size_t>(d);
+    op.w.assign(w, w + wn);
+    op.has_bias = bias != nullptr;
+    if (bias) op.bias.assign(bias, bias + w_dims[1] * groups);
+    auto& a = op.conv;
+    a.strides = {strides[0], strides[1]};
+    a.paddings.assign(paddings, paddings + n_paddings);
+    a.dilations = {dilations[0], dilations[1]};
+    a.groups = groups;
+    a.act = act;
+    a.act_coef = act_coef;
+    a.input_scale = input_scale;
+    a.weight_scale.assign(weight_scale, weight_scale + n_weight_scale);
+    if (output_size) a.output_size = {output_size[0], output_size[1]};
+  });
+}
 int pllite_graph_fc(pllite_predictor* p, const char* in, const char* out, const int8_t* w, int k, int n, const float* bias,
                     float input_scale, const float* weight_scale, int n_ws, int relu) {
   return guarded([&] {

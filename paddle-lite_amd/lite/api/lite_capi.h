@@ -76,6 +76,12 @@ int pllite_graph_conv(pllite_predictor* p, const char* op_type, const char* in, 
                       const int64_t* w_dims, const float* bias, const int* strides, const int* paddings, int n_paddings,
                       const int* dilations, int groups, int act, float act_coef, float input_scale,
                       const float* weight_scale, int n_weight_scale, const char* padding_algorithm);
+/* conv2d_transpose: w [cin][cout / groups][kh][kw] (w_dims), bias cout = w_dims[1] * groups floats or NULL, output_size 2 ints
+ * (ConvParam::output_size) or NULL for the default.  Kernel pick as pllite_graph_conv; no fusion takes it. */
+int pllite_graph_conv2d_transpose(pllite_predictor* p, const char* in, const char* out, const int8_t* w, const int64_t* w_dims,
+                                  const float* bias, const int* strides, const int* paddings, int n_paddings, const int* dilations,
+                                  int groups, int act, float act_coef, float input_scale, const float* weight_scale,
+                                  int n_weight_scale, const int* output_size);
 int pllite_graph_fc(pllite_predictor* p, const char* in, const char* out, const int8_t* w, int k, int n, const float* bias,
                     float input_scale, const float* weight_scale, int n_weight_scale, int relu);
 int pllite_graph_pool(pllite_predictor* p, const char* in, const char* out, const char* pooling_type, const int* ksize,

@@ -115,6 +115,57 @@ class ConvOpLite : public OpLite {
   int64_t image_channels_{0};
 };
 
+// conv_transpose_op.cc:43-53: (in - 1) * stride - pads + the dilated kernel extent
+inline int ConvTransposeOutputSize(int input_size, int filter_size, int dilation, int pad_left, int pad_right, int stride) {
+  return (input_size - 1) * stride - pad_left - pad_right + dilation * (filter_size - 1) + 1;
+}
+
+// conv2d_transpose (conv_transpose_op.cc:25-96): ConvParam with the filter [cin][cout / groups][kh][kw]; output_size, where
+// given, replaces the computed extent and must lie in [extent, extent + stride)
+class ConvTransposeOpLite : public OpLite {
+ public:
+  ConvTransposeOpLite() : OpLite("conv2d_transpose") {}
+  ConvParam& mutable_param() { return param_; }
+  void set_padding_algorithm(const std::string& a) { padding_algorithm_ = a; }
+  bool CheckShape() const override {
+    CHECK(param_.x && param_.filter && param_.output) << "conv2d_transpose: x / filter / output must be set";
+    const auto in = param_.x->dims(), f = param_.filter->dims();
+    CHECK_EQ(in.size(), 4UL) << "conv2d_transpose input must be NCHW";
+    CHECK_EQ(f.size(), 4UL);
+    CHECK_EQ(param_.strides.size(), 2UL);
+    CHECK_EQ(in[1] % param_.groups, 0) << "input channels must be divisible by groups";
+    CHECK_EQ(in[1], f[0]) << "input channels must equal the filter's first extent";
+    CHECK(param_.paddings && param_.dilations);
+    if (param_.paddings->size() == 2UL) {  // 2-element paddings mean {top = bottom, left = right}
+      const int ph = (*param_.paddings)[0], pw = (*param_.paddings)[1];
+      *param_.paddings = {ph, ph, pw, pw};
+    }
+    CHECK_EQ(param_.paddings->size(), 4UL) << "paddings must have 2 or 4 entries";
+    CHECK(param_.output_size.empty() || param_.output_size.size() == 2UL) << "output_size must have 0 or 2 entries";
+    return true;
+  }
+  bool InferShapeImpl() const override {
+    const auto in = param_.x->dims(), f = param_.filter->dims();
+    UpdatePaddingAndDilation(param_.paddings.get(), param_.dilations.get(), param_.strides, padding_algorithm_, in, f);
+    std::vector<int64_t> out{in[0], f[1] * param_.groups};
+    for (size_t i = 0; i < param_.strides.size(); ++i)
+      out.push_back(ConvTransposeOutputSize(static_cast<int>(in[i + 2]), static_cast<int>(f[i + 2]), (*param_.dilations)[i],
+                                            (*param_.paddings)[i * 2], (*param_.paddings)[i * 2 + 1], param_.strides[i]));
+    for (size_t i = 0; i < param_.output_size.size(); ++i) {
+      CHECK_LT(param_.output_size[i], out[i + 2] + param_.strides[i]) << "conv2d_transpose: output_size must be below " << out[i + 2] + param_.strides[i];
+      CHECK_GE(param_.output_size[i], out[i + 2]) << "conv2d_transpose: output_size must be at least " << out[i + 2];
+      out[i + 2] = param_.output_size[i];
+    }
+    param_.output->Resize(out);
+    return true;
+  }
+  void AttachKernel(KernelBase* k) override { k->SetParam<ConvParam>(param_); }
+
+ private:
+  mutable ConvParam param_;
+  std::string padding_algorithm_{""};
+};
+
 class FcOpLite : public OpLite {
  public:
   FcOpLite() : OpLite("fc") {}

@@ -55,6 +55,8 @@ def load():
     L.pllite_graph_feed_frame.argtypes = [vp, cs, i32, i32, i32, i32, i32, i32, C.POINTER(f32), C.POINTER(f32)]
     L.pllite_graph_conv.argtypes = [vp, cs, cs, cs, vp, C.POINTER(i64), vp, C.POINTER(i32), C.POINTER(i32), i32,
                                     C.POINTER(i32), i32, i32, f32, f32, vp, i32, cs]
+    L.pllite_graph_conv2d_transpose.argtypes = [vp, cs, cs, vp, C.POINTER(i64), vp, C.POINTER(i32), C.POINTER(i32), i32,
+                                                C.POINTER(i32), i32, i32, f32, f32, vp, i32, C.POINTER(i32)]
     L.pllite_graph_fc.argtypes = [vp, cs, cs, vp, i32, i32, vp, f32, vp, i32, i32]
     L.pllite_graph_pool.argtypes = [vp, cs, cs, cs, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), i32, i32, i32]
     L.pllite_graph_elementwise_add.argtypes = [vp, cs, cs, cs, cs]
@@ -331,6 +333,21 @@ class Predictor:
                                           _ia(w.shape, C.c_int64), bp, _ia(strides), _ia(paddings), len(paddings),
                                           _ia(dilations), groups, act, act_coef, input_scale, ws.ctypes.data_as(C.c_void_p),
                                           ws.size, padding_algorithm.encode()))
+
+    def graph_conv2d_transpose(self, src, dst, w, bias, strides, paddings, dilations, groups, act, act_coef, input_scale,
+                               weight_scale, output_size=None):
+        """conv2d_transpose: w int8 [cin, cout / groups, kh, kw], bias per output channel or None, output_size (h, w) or None."""
+        w = np.ascontiguousarray(w, np.int8)
+        ws = np.ascontiguousarray(weight_scale, np.float32)
+        bp = None
+        if bias is not None:
+            bias = np.ascontiguousarray(bias, np.float32)
+            bp = bias.ctypes.data_as(C.c_void_p)
+        self._ck(self.L.pllite_graph_conv2d_transpose(self.h, src.encode(), dst.encode(), w.ctypes.data_as(C.c_void_p),
+                                                      _ia(w.shape, C.c_int64), bp, _ia(strides), _ia(paddings), len(paddings),
+                                                      _ia(dilations), groups, act, act_coef, input_scale,
+                                                      ws.ctypes.data_as(C.c_void_p), ws.size,
+                                                      _ia(output_size) if output_size else None))
 
     def graph_fc(self, src, dst, w, bias, input_scale, weight_scale, relu=False):
         w = np.ascontiguousarray(w, np.int8)

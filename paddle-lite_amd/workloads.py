@@ -110,6 +110,8 @@ def build_mobilenet_v1(pred, W, batch, res=224):
 #   concat: srcs [..], axis      split: src, names [..] (name = names[0]), axis, num, sections      shuffle_channel: src, group
 #   bilinear_interp / nearest_interp: src, out_h, out_w, align_corners, align_mode      arg_max: src, axis, dtype, keepdims
 #   a conv with a dilation other than 1 carries `dilation` (both axes)
+#   conv2d_transpose: conv2d's fields with w [cin, cout / g, k, k] (no flip), bias / w_scale per OUTPUT channel, and output_size
+#                     (None, or (h, w))
 # On the reference's ARM target pool2d and elementwise_add exist in fp32 only, so the kernel-pick
 # rule gives the convs in front of them the fp32_out kernel and the consumers behind them a calib.
 # =====================================================================================================================
@@ -150,6 +152,27 @@ class _NetGen:
         ho = (h + 2 * pad - ke) // stride + 1
         wo = (w + 2 * pad - ke) // stride + 1
         self.tensor(name, cout, ho, wo, out_scale, (30.0 if act else 45.0) / headroom)
+        return name
+
+    def deconv(self, name, src, cout, k, stride, pad, groups=1, act=1, act_coef=0.0, out_range=4.0, headroom=1.0, bias_shift=0.0,
+               output_size=None):
+        """conv2d_transpose, sized as conv sizes a conv: an output sums cin / groups * ceil(k / stride)^2 products at most (the taps of
+        its phase), fewer at the border and in the phases a k that stride does not divide leaves short."""
+        cin, h, w = self.shape[src]
+        taps = -(-k // stride)
+        kk = (cin // groups) * taps * taps
+        wt = self.rng.integers(-127, 128, (cin, cout // groups, k, k)).astype(np.int8)
+        in_scale = self.act_scale[src]
+        out_scale = np.float32(out_range / 127.0)
+        acc_std = np.sqrt(kk) * self.sig_i8[src] * 73.0
+        var = (1.0 + (np.arange(cout) % 7) / 8.0) / 1.375
+        w_scale = (var * 45.0 / headroom * float(out_scale) / (acc_std * float(in_scale))).astype(np.float32)
+        bias = ((self.rng.uniform(-0.5, 0.5, cout) + bias_shift) * 45.0 * float(out_scale)).astype(np.float32)
+        self.ops.append(dict(op="conv2d_transpose", name=name, src=src, w=wt, bias=bias, stride=stride, pad=pad, groups=groups, act=act,
+                             act_coef=float(act_coef), in_scale=in_scale, w_scale=w_scale,
+                             output_size=None if output_size is None else tuple(int(v) for v in output_size)))
+        ho, wo = ((h - 1) * stride - 2 * pad + k, (w - 1) * stride - 2 * pad + k) if output_size is None else output_size
+        self.tensor(name, cout, int(ho), int(wo), out_scale, (30.0 if act else 45.0) / headroom)
         return name
 
     def pool(self, name, src, pooling_type, k, stride, pad, global_pooling=False, act_scale=None, sig_i8=40.0):
@@ -636,6 +659,36 @@ def seg_mini_net(seed=58, res=64, num_classes=19):
     return _finish(g, res, x)
 
 
+def unet_mini_net(seed=60, res=64, num_classes=4):
+    """A U-Net (Ronneberger et al. 2015) small enough for the CPU oracle: two encoder stages of 3x3 convs and a 2x2 max pool, a
+    bottleneck at res / 4, two decoder stages conv2d_transpose -> concat with the encoder's skip tensor -> 3x3 conv, a 1x1 classifier
+    and the per-pixel arg_max.  The first network here with a learned upsampling: dec2_up is k 2 s 2 p 0 (128 -> 64 channels, every
+    output one tap), dec1_up is k 4 s 2 p 1 (64 -> 32, four taps), so both phase patterns of the MFMA route are in one program.
+    Both read an int8 tensor and write fp32 (a concat reads them).  Lowering with every fusion on: L takes both concats (concat/int8)
+    and the two max pools behind fp32 convs stay fp32 readers of tensors a concat reads too.
+    Sizing: the spread corrections of squeezenet_v1_1_net for the concats (1.4); the second max pool keeps the largest of four
+    relu outputs of a 64-channel conv, so its readers quantise it over a range 1.4 times wider (as inception_mini_net widens a
+    tensor behind a max pool), and the bottleneck conv that reads it and dec2_up behind that are sized with 1.3 and 1.25 times the headroom.  tests/test_deconv_host.py states the worst saturated and zero shares of the int8 tensors."""
+    assert res % 4 == 0
+    g = _NetGen(seed)
+    g.tensor("image", 3, res, res, 1.0 / 127, 73.0)
+    x = g.conv("enc1_conv1", "image", 32, 3, 1, 1, act=1)
+    skip1 = g.conv("enc1_conv2", x, 32, 3, 1, 1, act=1)
+    x = g.pool("enc1_pool", skip1, "max", 2, 2, 0)
+    skip2 = g.conv("enc2_conv", x, 64, 3, 1, 1, act=1)
+    x = g.widen(g.pool("enc2_pool", skip2, "max", 2, 2, 0), 1.4)
+    x = g.conv("bottleneck", x, 128, 3, 1, 1, act=1, headroom=1.3)
+    x = g.deconv("dec2_up", x, 64, 2, 2, 0, act=1, headroom=1.25)
+    x = _spread(g, g.concat("dec2_concat", [x, skip2], 1), 1.4)
+    x = g.conv("dec2_conv", x, 64, 3, 1, 1, act=1)
+    x = g.deconv("dec1_up", x, 32, 4, 2, 1, act=1)
+    x = _spread(g, g.concat("dec1_concat", [x, skip1], 1), 1.4)
+    x = g.conv("dec1_conv", x, 32, 3, 1, 1, act=1)
+    x = g.conv("logits", x, num_classes, 1, 1, 0, act=0)
+    x = g.arg_max("label", x, 1, dtype=-1)
+    return _finish(g, res, x)
+
+
 def ssd_mini_net(seed=59, res=96, num_classes=21, conf_range=12.0):
     """An SSD-shaped detector (Liu et al. 2016) on a MobileNetV1-style backbone, small enough for the CPU oracle: depthwise-separable
     blocks to res / 8 (12 x 12 at res 96), / 16, / 32 and a 3x3 conv without padding behind them (1 x 1 at res 96); on each of the
@@ -814,6 +867,10 @@ def emit_graph(pred, net, batch, fuse=True, fuse_dwpw=None, fuse_dwconv=None, im
             p = o["pad"]
             pred.graph_conv(t, o["src"], o["name"], o["w"], o["bias"], (o["stride"],) * 2, (p, p, p, p), (o.get("dilation", 1),) * 2, o["groups"],
                             o["act"], o["act_coef"], float(o["in_scale"]), o["w_scale"])
+        elif t == "conv2d_transpose":
+            p = o["pad"]
+            pred.graph_conv2d_transpose(o["src"], o["name"], o["w"], o["bias"], (o["stride"],) * 2, (p, p, p, p), (o.get("dilation", 1),) * 2,
+                                        o["groups"], o["act"], o["act_coef"], float(o["in_scale"]), o["w_scale"], o["output_size"])
         elif t == "fc":
             pred.graph_fc(o["src"], o["name"], o["w"], o["bias"], float(o["in_scale"]), o["w_scale"], False)
         elif t == "pool2d":
