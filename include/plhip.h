@@ -516,6 +516,36 @@ size_t plhip_multiclass_nms_workspace_bytes(const plhip_nms_desc* desc);
 plhip_status plhip_multiclass_nms_f32(plhip_ctx* ctx, const float* boxes, const float* scores, const plhip_nms_desc* desc,
                                       void* workspace, float* out, int* index_or_null, int* count);
 
+/* ---- YOLOv3 heads (yolo_ops.hip): yolo_box (lite/backends/arm/math/yolo_box.cc:24-178) of one feature map in the reference's
+ * output layout, and the head of up to 8 feature maps in one launch, written in the layout plhip_multiclass_nms_f32 reads.  x is
+ * fp32 [n][an * (5 + c)][h][w]; img_size int32 [n][2] = (height, width) of every image, on the device; anchors: `an` (width,
+ * height) pairs of int in HOST memory, read during the call and passed to the kernel by value (no table is copied; at most 16
+ * pairs per feature map).  conf = sigmoid(objectness); a cell with conf < conf_thresh is skipped (a NaN is kept); its box and
+ * scores are zeros.  The box centre uses h as the grid size on BOTH axes and downsample_ratio * h as the input size, as the
+ * reference does; bias = -0.5 * (scale_x_y - 1) is computed in double and narrowed; clip_bbox clamps as `v > 0 ? v : 0` and
+ * `v < img - 1 ? v : img - 1`, so a NaN becomes 0 and img - 1.  fp32 in the reference's order of operations with no contraction;
+ * exp is the library's expf.  Every output element is written by the call, the zeros included: the outputs need no clearing.
+ * Both check their arguments before any launch, each failure with a text of its own; PLHIP_ERR_INVALID: a NULL pointer, a
+ * dimension < 1, an empty or odd anchor list, downsample_ratio < 1, count outside 1 .. 8; PLHIP_ERR_UNSUPPORTED: n * P * max(c, 4)
+ * reaches 2^31 (P = the boxes of one image), downsample_ratio * h reaches 2^31, more than 16 anchor pairs in a feature map,
+ * (head) c above 2^18.  No atomics, no host synchronisation: both may be captured by plhip_graph_begin. ---- */
+/* boxes [n][an * h * w][4], one 16-byte store per box where boxes is 16-byte aligned; scores [n][an * h * w][c], the transposed
+ * side: a block stages 64 cells x 64 classes in LDS, reads whole rows of x and writes whole rows of scores.  Box an_idx * h * w
+ * + k * w + l is cell (row k, column l) of anchor an_idx. */
+plhip_status plhip_yolo_box_f32(plhip_ctx* ctx, const float* x, const int* img_size, int n, int an, int c, int h, int w,
+                                const int* anchors, float conf_thresh, int downsample_ratio, int clip_bbox, float scale_x_y,
+                                float* boxes, float* scores);
+/* `count` feature maps xs[i] [n][(anchor_lens[i] / 2) * (5 + c)][hs[i]][ws[i]] with anchors[i][0 .. anchor_lens[i] - 1] and
+ * downsample_ratios[i] (the arrays in host memory, as plhip_concat_nhwc_f32's); img_size, c, conf_thresh, clip_bbox and scale_x_y
+ * are shared.  ONE launch writes boxes [n][P][4] and scores [n][c][P], P = sum of (anchor_lens[i] / 2) * hs[i] * ws[i], feature
+ * map i behind the ones in front of it: byte for byte plhip_yolo_box_f32 per feature map -> plhip_concat_f32 (axis 1) of the
+ * boxes and of the scores -> plhip_transpose_f32 (0, 2, 1) of the scores, the per-cell arithmetic being the same device
+ * functions.  A lane owns 4 consecutive cells of a row of x where hs[i] * ws[i] % 4 == 0 and xs[i], scores, every row of scores
+ * (P % 4 == 0) and the feature map's offset into P are on 16 bytes, and one cell otherwise. */
+plhip_status plhip_yolo_head_f32(plhip_ctx* ctx, const float* const* xs, const int* hs, const int* ws, const int* const* anchors,
+                                 const int* anchor_lens, const int* downsample_ratios, int count, const int* img_size, int n, int c,
+                                 float conf_thresh, int clip_bbox, float scale_x_y, float* boxes, float* scores);
+
 /* ---- introspection used by tests: operand-layout self-check of the MFMA tile on this device.
  * Runs a tiny known-answer GEMM through the MFMA path; returns PLHIP_OK iff bit-exact. ---- */
 plhip_status plhip_selftest(plhip_ctx* ctx);

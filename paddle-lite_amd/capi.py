@@ -39,6 +39,7 @@ EXPORTS = [
     "plhip_interp_f32", "plhip_arg_max_f32", "plhip_interp_argmax_f32",
     "plhip_transpose_f32", "plhip_concat_nhwc_f32", "plhip_box_coder_decode_f32",
     "plhip_multiclass_nms_workspace_bytes", "plhip_multiclass_nms_f32",
+    "plhip_yolo_box_f32", "plhip_yolo_head_f32",
 ]
 
 # plhip_hard_act_kind, and the reference's default parameters (lite/operators/op_params.h:406-412)
@@ -335,6 +336,9 @@ def load():
     L.plhip_multiclass_nms_workspace_bytes.argtypes = [C.POINTER(NmsDesc)]
     L.plhip_multiclass_nms_workspace_bytes.restype = sz
     L.plhip_multiclass_nms_f32.argtypes = [vp, vp, vp, C.POINTER(NmsDesc), vp, vp, vp, vp]
+    ip = C.POINTER(i32)
+    L.plhip_yolo_box_f32.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, ip, f32, i32, i32, f32, vp, vp]
+    L.plhip_yolo_head_f32.argtypes = [vp, C.POINTER(vp), ip, ip, C.POINTER(ip), ip, ip, i32, vp, i32, i32, f32, i32, f32, vp, vp]
     L.plhip_selftest.argtypes = [vp]
     _lib = L
     return L
@@ -1000,6 +1004,68 @@ class Context:
             return self.to_host(dy, target.shape, np.float32)
         finally:
             for b in [ybuf] + [b for b, _d in bufs]:
+                self.free(b)
+
+    # ---- YOLOv3 heads (yolo_ops.hip)
+    def yolo_box_launch(self, dx, dimg, shape, anchors, class_num, conf_thresh, downsample_ratio, clip_bbox, scale_x_y, dboxes, dscores):
+        """plhip_yolo_box_f32 on device pointers; shape: x's [n, an * (5 + class_num), h, w].  Returns the status."""
+        n, _ch, h, w = shape
+        av = (C.c_int * max(1, len(anchors)))(*[int(v) for v in anchors])
+        return self.L.plhip_yolo_box_f32(self.h, dx, dimg, n, len(anchors) // 2, int(class_num), h, w, av, float(conf_thresh),
+                                         int(downsample_ratio), int(bool(clip_bbox)), float(scale_x_y), dboxes, dscores)
+
+    def yolo_head_launch(self, dxs, dimg, shapes, anchors, class_num, conf_thresh, downsample_ratios, clip_bbox, scale_x_y, dboxes, dscores):
+        """plhip_yolo_head_f32 on device pointers; shapes[i]: xs[i]'s [n, an_i * (5 + class_num), h_i, w_i].  Returns the status."""
+        k = len(dxs)
+        avs = [(C.c_int * max(1, len(a)))(*[int(v) for v in a]) for a in anchors]
+        ptrs = (C.c_void_p * k)(*dxs)
+        hs = (C.c_int * k)(*[s[2] for s in shapes])
+        ws = (C.c_int * k)(*[s[3] for s in shapes])
+        ap = (C.POINTER(C.c_int) * k)(*[C.cast(a, C.POINTER(C.c_int)) for a in avs])
+        lens = (C.c_int * k)(*[len(a) for a in anchors])
+        ratios = (C.c_int * k)(*[int(v) for v in downsample_ratios])
+        return self.L.plhip_yolo_head_f32(self.h, ptrs, hs, ws, ap, lens, ratios, k, dimg, shapes[0][0] if k else 1, int(class_num), float(conf_thresh),
+                                          int(bool(clip_bbox)), float(scale_x_y), dboxes, dscores)
+
+    def _filled(self, count, misalign, fill=0xFF):
+        """An fp32 output of `count` elements behind `misalign` elements of slack, every byte `fill`: an unwritten element shows."""
+        buf, d = self._out_buf(count, 4, misalign)
+        self.check(self.L.plhip_memset(self.h, buf, fill, 4 * (count + misalign) + 8), "memset")
+        return buf, d
+
+    def yolo_box(self, x, img_size, anchors, class_num, conf_thresh, downsample_ratio, clip_bbox=True, scale_x_y=1.0, misalign=0):
+        """plhip_yolo_box_f32: x [n, an * (5 + class_num), h, w] fp32, img_size [n, 2] int32 (height, width).  Returns
+        (boxes [n, an * h * w, 4], scores [n, an * h * w, class_num]); the outputs hold 0xFF bytes before the call."""
+        x = np.ascontiguousarray(x, np.float32)
+        n, _ch, h, w = x.shape
+        p = (len(anchors) // 2) * h * w
+        xbuf, dx = self._up_f32(x, misalign)
+        dimg = self.to_device(np.ascontiguousarray(img_size, np.int32))
+        bbuf, db = self._filled(n * p * 4, misalign)
+        sbuf, ds = self._filled(n * p * class_num, misalign)
+        try:
+            self.check(self.yolo_box_launch(dx, dimg, x.shape, anchors, class_num, conf_thresh, downsample_ratio, clip_bbox, scale_x_y, db, ds), "yolo_box")
+            return self.to_host(db, (n, p, 4), np.float32), self.to_host(ds, (n, p, class_num), np.float32)
+        finally:
+            for b in (xbuf, dimg, bbuf, sbuf):
+                self.free(b)
+
+    def yolo_head(self, xs, img_size, anchors, class_num, conf_thresh, downsample_ratios, clip_bbox=True, scale_x_y=1.0, misalign=0):
+        """plhip_yolo_head_f32 of the feature maps xs[i] with anchors[i] and downsample_ratios[i].  Returns (boxes [n, P, 4],
+        scores [n, class_num, P]); the outputs hold 0xFF bytes before the call."""
+        xs = [np.ascontiguousarray(x, np.float32) for x in xs]
+        n = xs[0].shape[0]
+        p = sum((len(a) // 2) * x.shape[2] * x.shape[3] for a, x in zip(anchors, xs))
+        ups = [self._up_f32(x, misalign) for x in xs]
+        dimg = self.to_device(np.ascontiguousarray(img_size, np.int32))
+        bbuf, db = self._filled(n * p * 4, misalign)
+        sbuf, ds = self._filled(n * p * class_num, misalign)
+        try:
+            self.check(self.yolo_head_launch([d for _b, d in ups], dimg, [x.shape for x in xs], anchors, class_num, conf_thresh,
+                                             downsample_ratios, clip_bbox, scale_x_y, db, ds), "yolo_head")
+            return self.to_host(db, (n, p, 4), np.float32), self.to_host(ds, (n, class_num, p), np.float32)
+        finally:
+            for b in [dimg, bbuf, sbuf] + [b for b, _d in ups]:
                 self.free(b)
 
     def multiclass_nms(self, boxes, scores, desc, with_index=True, misalign=0):

@@ -1,6 +1,6 @@
 // plhip_capi_ops.hip — the C ABI (include/plhip.h), part 4 of 4: fc, calib, pooling, softmax, elementwise add, the hard activations,
 // squeeze-excite, concat / split / shuffle_channel, interp / arg_max, and the detection heads (transpose, concat_nhwc, box_coder,
-// multiclass_nms).  Argument validation and one launch each (multiclass_nms: two).
+// multiclass_nms) and the YOLOv3 heads (yolo_box, yolo_head).  Argument validation and one launch each (multiclass_nms: two).
 #include "plhip_capi.h"
 
 #include <vector>
@@ -408,6 +408,81 @@ plhip_status plhip_multiclass_nms_f32(plhip_ctx* ctx, const float* boxes, const 
   a.kmax = kmax; a.cap = cap; a.nact = nact;
   plhip::launch_multiclass_nms(a, desc->n, ctx->stream);
   LAUNCHCHK(ctx, "multiclass_nms");
+  return PLHIP_OK;
+}
+
+// ------------------------------------------------------------------ yolo_box / yolo_head
+// one scale's checks and its YoloScale; *cells grows by an * h * w
+static plhip_status yolo_scale(plhip_ctx* ctx, const char* who, const float* x, int h, int w, const int* anchors, int anchor_len,
+                               int ratio, plhip::YoloScale* s, int64_t* cells) {
+  if (!x) return fail(ctx, PLHIP_ERR_INVALID, "%s: null x", who);
+  if (h < 1 || w < 1) return fail(ctx, PLHIP_ERR_INVALID, "%s: h and w must be at least 1", who);
+  if (!anchors) return fail(ctx, PLHIP_ERR_INVALID, "%s: null anchors", who);
+  if (anchor_len < 2 || (anchor_len & 1)) return fail(ctx, PLHIP_ERR_INVALID, "%s: the anchor list must hold at least one (width, height) pair and no odd value", who);
+  if (ratio < 1) return fail(ctx, PLHIP_ERR_INVALID, "%s: downsample_ratio must be at least 1", who);
+  if (anchor_len > 2 * plhip::YOLO_MAX_ANCHORS) return fail(ctx, PLHIP_ERR_UNSUPPORTED, "%s: more than 16 anchors in one scale", who);
+  const int64_t top = (int64_t)1 << 31;
+  if ((int64_t)h * w >= top / (anchor_len / 2)) return fail(ctx, PLHIP_ERR_UNSUPPORTED, "%s: n * P * max(c, 4) reaches 2^31", who);
+  if ((int64_t)ratio * h >= top) return fail(ctx, PLHIP_ERR_UNSUPPORTED, "%s: downsample_ratio * h reaches 2^31", who);
+  s->x = x; s->h = h; s->w = w; s->an = anchor_len / 2; s->ratio = ratio;
+  for (int k = 0; k < 2 * plhip::YOLO_MAX_ANCHORS; ++k) s->anchors[k] = k < anchor_len ? anchors[k] : 0;
+  s->p_off = s->chunks = s->vec = 0;
+  *cells += (int64_t)s->an * h * w;
+  return PLHIP_OK;
+}
+
+// what the scales share; P: the priors of one image
+static plhip_status yolo_common(plhip_ctx* ctx, const char* who, const int* img_size, int n, int c, int64_t P, float conf_thresh,
+                                int clip_bbox, float scale_x_y, const float* boxes, const float* scores, plhip::YoloCommon* o) {
+  if (!img_size) return fail(ctx, PLHIP_ERR_INVALID, "%s: null img_size", who);
+  if (!boxes || !scores) return fail(ctx, PLHIP_ERR_INVALID, "%s: null boxes or scores", who);
+  const int64_t top = (int64_t)1 << 31, widest = c > 4 ? c : 4;
+  if (P >= top || (int64_t)n * P >= top || (int64_t)n * P >= (top + widest - 1) / widest)
+    return fail(ctx, PLHIP_ERR_UNSUPPORTED, "%s: n * P * max(c, 4) reaches 2^31", who);
+  o->img_size = img_size; o->n = n; o->classes = c; o->clip = clip_bbox ? 1 : 0;
+  o->thresh = conf_thresh; o->scale = scale_x_y;
+  o->bias = (float)(-0.5 * ((double)scale_x_y - 1.));  // yolo_box_compute.cc:37: in double, then narrowed
+  return PLHIP_OK;
+}
+
+plhip_status plhip_yolo_box_f32(plhip_ctx* ctx, const float* x, const int* img_size, int n, int an, int c, int h, int w,
+                                const int* anchors, float conf_thresh, int downsample_ratio, int clip_bbox, float scale_x_y,
+                                float* boxes, float* scores) {
+  const char* who = "plhip_yolo_box_f32";
+  if (!ctx) return fail(ctx, PLHIP_ERR_INVALID, "%s: null ctx", who);
+  if (n < 1 || c < 1) return fail(ctx, PLHIP_ERR_INVALID, "%s: n and c must be at least 1", who);
+  if (an < 1) return fail(ctx, PLHIP_ERR_INVALID, "%s: an must be at least 1 (an empty anchor list)", who);
+  plhip::YoloBoxArgs a;
+  int64_t P = 0;
+  if (plhip_status st = yolo_scale(ctx, who, x, h, w, anchors, an > (1 << 20) ? (1 << 20) : 2 * an, downsample_ratio, &a.s, &P)) return st;
+  if (plhip_status st = yolo_common(ctx, who, img_size, n, c, P, conf_thresh, clip_bbox, scale_x_y, boxes, scores, &a.c)) return st;
+  a.boxes = boxes; a.scores = scores;
+  plhip::launch_yolo_box(a, ctx->stream);
+  LAUNCHCHK(ctx, "yolo_box");
+  return PLHIP_OK;
+}
+
+plhip_status plhip_yolo_head_f32(plhip_ctx* ctx, const float* const* xs, const int* hs, const int* ws, const int* const* anchors,
+                                 const int* anchor_lens, const int* downsample_ratios, int count, const int* img_size, int n, int c,
+                                 float conf_thresh, int clip_bbox, float scale_x_y, float* boxes, float* scores) {
+  const char* who = "plhip_yolo_head_f32";
+  if (!ctx) return fail(ctx, PLHIP_ERR_INVALID, "%s: null ctx", who);
+  if (!xs || !hs || !ws || !anchors || !anchor_lens || !downsample_ratios)
+    return fail(ctx, PLHIP_ERR_INVALID, "%s: null xs, hs, ws, anchors, anchor_lens or downsample_ratios", who);
+  if (count < 1 || count > plhip::YOLO_MAX_SCALES) return fail(ctx, PLHIP_ERR_INVALID, "%s: count must be 1 .. 8", who);
+  if (n < 1 || c < 1) return fail(ctx, PLHIP_ERR_INVALID, "%s: n and c must be at least 1", who);
+  if (c > (1 << 18)) return fail(ctx, PLHIP_ERR_UNSUPPORTED, "%s: c above 2^18", who);
+  plhip::YoloHeadArgs a;
+  memset(&a, 0, sizeof(a));
+  int64_t P = 0;
+  for (int i = 0; i < count; ++i) {
+    if (plhip_status st = yolo_scale(ctx, who, xs[i], hs[i], ws[i], anchors[i], anchor_lens[i], downsample_ratios[i], &a.s[i], &P)) return st;
+    if (P >= ((int64_t)1 << 31)) return fail(ctx, PLHIP_ERR_UNSUPPORTED, "%s: n * P * max(c, 4) reaches 2^31", who);
+  }
+  if (plhip_status st = yolo_common(ctx, who, img_size, n, c, P, conf_thresh, clip_bbox, scale_x_y, boxes, scores, &a.c)) return st;
+  a.boxes = boxes; a.scores = scores; a.count = count;
+  plhip::launch_yolo_head(a, ctx->stream);
+  LAUNCHCHK(ctx, "yolo_head");
   return PLHIP_OK;
 }
 

@@ -551,4 +551,37 @@ struct NmsArgs {
 void nms_sizes(int C, int P, int bg, int nms_top_k, int keep_top_k, int* kmax, int* cap, int* nact);
 void launch_multiclass_nms(NmsArgs a, int N, hipStream_t s);
 
+// yolo_box of one scale and the one-launch head of up to YOLO_MAX_SCALES scales: yolo_ops.hip
+constexpr int YOLO_MAX_SCALES = 8;    // as CONCAT_MAX_PARTS: the operands travel in the argument struct
+constexpr int YOLO_MAX_ANCHORS = 16;  // anchors of one scale; they travel in the argument struct too
+struct YoloScale {
+  const float* x;  // [n][an * (5 + classes)][h][w]
+  int h, w, an, ratio;
+  int anchors[2 * YOLO_MAX_ANCHORS];
+  int p_off, chunks, vec;  // the head: launch_yolo_head fills them
+};
+struct YoloCommon {
+  const int* img_size;  // [n][2]: height, width
+  int64_t n;
+  int classes, clip;
+  float thresh, scale, bias;
+};
+struct YoloBoxArgs {
+  YoloScale s;
+  YoloCommon c;
+  float* boxes;   // [n][an * h * w][4]
+  float* scores;  // [n][an * h * w][classes]
+  int vec;        // launch_yolo_box fills it
+};
+void launch_yolo_box(YoloBoxArgs a, hipStream_t s);
+struct YoloHeadArgs {
+  YoloScale s[YOLO_MAX_SCALES];
+  YoloCommon c;
+  float* boxes;   // [n][P][4], P = sum of an * h * w, scale i behind the scales in front of it
+  float* scores;  // [n][classes][P]
+  int count;
+  int P, box_vec, first[YOLO_MAX_SCALES];  // launch_yolo_head fills them; first: the scale's first block of grid x
+};
+void launch_yolo_head(YoloHeadArgs a, hipStream_t s);
+
 }  // namespace plhip

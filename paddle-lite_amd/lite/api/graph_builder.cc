@@ -280,6 +280,12 @@ std::map<std::string, std::vector<int64_t>> GraphBuilder::InferShapes() const {
       const std::vector<std::string> outs = OutputsOf(op);
       CHECK(o.size() == outs.size()) << op.type << " " << op.output << ": " << outs.size() << " outputs named, " << o.size() << " expected";
       for (size_t i = 0; i < outs.size(); ++i) shape[outs[i]] = o[i];
+    } else if (op.type == "yolo_box") {
+      const std::string who = "yolo_box " + op.output;
+      CHECK(ins.size() == 2 && op.outputs.size() == 2) << who << ": inputs {X, ImgSize} and outputs {Boxes, Scores}";
+      const int64_t p = operators::YoloBoxOpLite::CheckDims(ins[0], ins[1], op.anchors, op.class_num, who);
+      shape[op.outputs[0]] = {in[0], p, 4};
+      shape[op.outputs[1]] = {in[0], p, op.class_num};
     } else if (IsInterp(op)) {
       shape[op.output] = InterpOutShape(op, in);
     } else if (op.type == "arg_max") {
@@ -365,7 +371,7 @@ std::vector<GraphBuilder::Step> GraphBuilder::Schedule() {
     s.op = static_cast<int>(i);
     for (auto& in : op.inputs) {
       std::string use = dev_name(in);
-      if (prec[in] != want) {
+      if (prec[in] != want && prec[in] != PRECISION(kInt32)) {  // an int32 operand (yolo_box's ImgSize) is no tensor to quantise
         auto c = cast_of.find(in);
         if (c == cast_of.end()) {
           Step cs;
@@ -516,6 +522,7 @@ struct GraphBuilder::Fuser {
   void InterpArgmax();
   void InterpCalib();
   void DetectionHead();
+  void YoloHead();
 };
 
 // (A) (C) (B): the conv-tail patterns, matched by the SAME code a Paddle-Lite tree runs as a mir pass
@@ -967,6 +974,77 @@ void GraphBuilder::Fuser::DetectionHead() {
   }
 }
 
+// (P): see graph_builder.h
+void GraphBuilder::Fuser::YoloHead() {
+  // the live step of graph op `type` one of whose outputs is v, v being read by exactly one live step (a fetch counts), or -1
+  auto sole_producer = [&](const std::string& v, const char* type) {
+    if (Uses(v) != 1) return -1;
+    for (size_t t = 0; t < st.size(); ++t) {
+      if (dead[t] || !IsOp(static_cast<int>(t), type)) continue;
+      if (st[t].out == v || std::find(st[t].outs.begin(), st[t].outs.end(), v) != st[t].outs.end()) return static_cast<int>(t);
+    }
+    return -1;
+  };
+  auto plain_concat = [&](int t) {
+    if (t < 0 || st[t].shuffle_tail || st[t].concat_int8 || st[t].nhwc_k) return false;
+    const auto os = var_shape.find(Op(t).output);
+    return os != var_shape.end() && os->second.size() == 3 && (Op(t).axis == 1 || Op(t).axis == -2);
+  };
+  for (size_t i = 0; i < st.size(); ++i) {
+    if (dead[i] || !IsOp(static_cast<int>(i), "multiclass_nms") || st[i].scores_npc) continue;
+    const int tr = sole_producer(st[i].op_inputs[1], "transpose");
+    if (tr < 0 || Op(tr).perm != std::vector<int>({0, 2, 1})) continue;
+    std::vector<int> ys;  // the yolo_box steps in the boxes' order
+    int cb = -1, cs = -1;
+    const int y1 = sole_producer(st[i].op_inputs[0], "yolo_box");
+    if (y1 >= 0) {  // k = 1
+      if (st[y1].outs.size() != 2 || st[y1].outs[0] != st[i].op_inputs[0] || st[y1].outs[1] != st[tr].op_inputs[0] || Uses(st[y1].outs[1]) != 1) continue;
+      ys.push_back(y1);
+    } else {
+      cb = sole_producer(st[i].op_inputs[0], "concat");
+      cs = sole_producer(st[tr].op_inputs[0], "concat");
+      if (!plain_concat(cb) || !plain_concat(cs) || st[cb].op_inputs.size() != st[cs].op_inputs.size()) continue;
+      bool ok = true;
+      for (size_t q = 0; ok && q < st[cb].op_inputs.size(); ++q) {
+        const int y = sole_producer(st[cb].op_inputs[q], "yolo_box");
+        ok = y >= 0 && st[y].outs.size() == 2 && st[y].outs[0] == st[cb].op_inputs[q] && st[y].outs[1] == st[cs].op_inputs[q] &&
+             Uses(st[y].outs[1]) == 1 && std::find(ys.begin(), ys.end(), y) == ys.end();
+        if (ok) ys.push_back(y);
+      }
+      if (!ok) continue;
+    }
+    if (ys.empty() || ys.size() > 8) continue;
+    const GraphOp& a = Op(ys[0]);
+    bool same = true;
+    for (int y : ys) {
+      const GraphOp& b = Op(y);
+      same = same && st[y].op_inputs[1] == st[ys[0]].op_inputs[1] && b.class_num == a.class_num && b.conf_thresh == a.conf_thresh &&
+             b.clip_bbox == a.clip_bbox && b.scale_x_y == a.scale_x_y && b.anchors.size() <= 32;
+    }
+    if (!same) continue;
+    // the last of the yolo_box steps carries the instruction: every feature map has been written in front of it
+    const int at = *std::max_element(ys.begin(), ys.end());
+    Step head = st[at];
+    head.yolo_ops.clear();
+    head.op_inputs = {st[ys[0]].op_inputs[0], st[ys[0]].op_inputs[1]};
+    head.via.clear();
+    for (size_t q = 0; q < ys.size(); ++q) {
+      head.yolo_ops.push_back(st[ys[q]].op);
+      if (q) head.op_inputs.push_back(st[ys[q]].op_inputs[0]);
+      if (cb >= 0) head.via += (q ? "," : "") + st[ys[q]].outs[0] + "," + st[ys[q]].outs[1];
+      dead[ys[q]] = true;
+    }
+    head.via += (cb >= 0 ? "," + st[cs].out : st[ys[0]].outs[1]);
+    head.op = head.yolo_ops[0];
+    head.out = st[i].op_inputs[0];
+    head.outs = {st[i].op_inputs[0], st[tr].out};
+    st[at] = head;
+    dead[at] = false;
+    dead[tr] = true;
+    if (cb >= 0) dead[cb] = dead[cs] = true;
+  }
+}
+
 // The rewrites in the one order that gives today's programs.  Each takes over steps that a later one would otherwise match:
 //   * I before H: H would take the image_to_tensor behind an image_resize (and its calib) and leave the resize a launch of its own.
 //   * H before F: F would take the calib behind an image_to_tensor into the stem alone, and the fp32 tensor would still be written.
@@ -984,6 +1062,8 @@ void GraphBuilder::Fuser::DetectionHead() {
 //     took has no fp32 output for N to quantise (and an interp that a calib reads too has two readers, so M leaves it to N).
 //   * O last: it takes transposes and reshapes, which no rewrite above matches, in front of a concat that K and L left alone (a
 //     concat whose output a calib reads stays L's) or of a multiclass_nms.
+//   * P in front of O: O2 would fold the transpose P needs to see; P takes yolo_box ops and plain rank-3 concats of their outputs,
+//     which no rewrite above matches (no calib reads them).
 void GraphBuilder::FuseSteps(std::vector<Step>* steps, const std::map<std::string, std::vector<int64_t>>& shapes) {
   Fuser f(*this, steps, shapes);
   f.ConvTails();
@@ -999,6 +1079,7 @@ void GraphBuilder::FuseSteps(std::vector<Step>* steps, const std::map<std::strin
   if (fuse_concat_) f.ConcatCalib();
   if (fuse_interp_argmax_) f.InterpArgmax();
   if (fuse_interp_calib_) f.InterpCalib();
+  if (fuse_yolo_head_) f.YoloHead();
   if (fuse_detection_head_) f.DetectionHead();
   std::vector<Step> kept;
   for (size_t i = 0; i < steps->size(); ++i)
@@ -1041,6 +1122,30 @@ std::string GraphBuilder::OpLine(const Step& s) const {
     }
     return a;
   };
+  auto ints_of = [](const char* key, const std::vector<int>& v) {
+    std::string a = std::string(" ") + key + "=";
+    for (size_t i = 0; i < v.size(); ++i) a += (i ? "," : "") + std::to_string(v[i]);
+    return a;
+  };
+  if (op.type == "yolo_box") {  // yolo_box/def, or (P) yolo_box/head: the attributes of every feature map, '|' between the maps
+    const bool head = !s.yolo_ops.empty();
+    std::string l = std::string("yolo_box/") + (head ? "head" : "def") + " in=";
+    for (size_t i = 0; i < s.op_inputs.size(); ++i) l += (i ? "," : "") + s.op_inputs[i];
+    l += " out=" + s.outs[0] + "," + s.outs[1];
+    std::string anchors = " anchors=", ratios = " downsample_ratio=";
+    const std::vector<int> self{s.op};
+    const std::vector<int>& maps = head ? s.yolo_ops : self;
+    for (size_t q = 0; q < maps.size(); ++q) {
+      const GraphOp& y = ops_[maps[q]];
+      anchors += (q ? "|" : "") + ints_of("", y.anchors).substr(2);
+      ratios += (q ? "|" : "") + std::to_string(y.downsample_ratio);
+    }
+    l += anchors + " class_num=" + std::to_string(op.class_num);
+    AppendNum(&l, "conf_thresh", op.conf_thresh);
+    l += ratios + " clip_bbox=" + std::to_string(op.clip_bbox ? 1 : 0);
+    AppendNum(&l, "scale_x_y", op.scale_x_y);
+    return head ? l + " via=" + s.via : l;
+  }
   if (s.nhwc_k) {  // (O1): the concat step that took the transpose -> reshape chains over
     std::string l = "concat/nhwc in=";
     for (size_t i = 0; i < s.op_inputs.size(); ++i) l += (i ? "," : "") + s.op_inputs[i];
@@ -1258,6 +1363,20 @@ void GraphBuilder::LowerOp(const Step& s, HipPredictor* pred) {
     const bool pv = s.op_inputs.size() == 3;
     pred->AddBoxCoder(s.op_inputs[0], pv ? s.op_inputs[1] : "", s.op_inputs.back(), s.out, pv ? std::vector<float>() : op.variances, op.axis,
                       op.box_normalized);
+  } else if (op.type == "yolo_box" && !s.yolo_ops.empty()) {
+    std::vector<std::string> xs{s.op_inputs[0]};
+    xs.insert(xs.end(), s.op_inputs.begin() + 2, s.op_inputs.end());
+    std::vector<std::vector<int>> anchors;
+    std::vector<int> ratios;
+    for (int y : s.yolo_ops) {
+      anchors.push_back(ops_[y].anchors);
+      ratios.push_back(ops_[y].downsample_ratio);
+    }
+    pred->AddYoloHead(xs, s.op_inputs[1], s.outs[0], s.outs[1], anchors, op.class_num, op.conf_thresh, ratios, op.clip_bbox, op.scale_x_y);
+  } else if (op.type == "yolo_box") {
+    CHECK(s.outs.size() == 2) << "yolo_box " << s.out << ": outputs {Boxes, Scores}";
+    pred->AddYoloBox(s.op_inputs[0], s.op_inputs[1], s.outs[0], s.outs[1], op.anchors, op.class_num, op.conf_thresh, op.downsample_ratio,
+                     op.clip_bbox, op.scale_x_y);
   } else if (op.type == "multiclass_nms") {
     CHECK(s.outs.size() >= 2 && s.outs[1] == s.out + "/count") << "multiclass_nms " << s.out << ": the count variable must be <out>/count";
     pred->AddMulticlassNms(s.op_inputs[0], s.op_inputs[1], s.out, s.outs.size() > 2 ? s.outs[2] : "", op.background_label, op.score_threshold,

@@ -29,11 +29,12 @@ struct GraphOp {
                      // hard_swish | hard_sigmoid | elementwise_mul (fp32 ops like pool2d; the reference's default parameters) |
                      // concat (N inputs) | split | shuffle_channel (fp32 ops like pool2d) |
                      // bilinear_interp | nearest_interp | arg_max (fp32 ops like pool2d; arg_max writes int64 / int32 labels) |
-                     // transpose | reshape | prior_box | box_coder | multiclass_nms (fp32 ops like pool2d)
+                     // transpose | reshape | prior_box | box_coder | multiclass_nms (fp32 ops like pool2d) |
+                     // yolo_box (an fp32 op like box_coder whose second operand is an int32 feed)
   std::vector<std::string> inputs;
   std::string output;                // the first output
   std::vector<std::string> outputs;  // split: all outputs, outputs[0] == output; prior_box: {Boxes, Variances}; multiclass_nms:
-                                     // {Out, "<Out>/count"[, Index]}; empty for every other type
+                                     // {Out, "<Out>/count"[, Index]}; yolo_box: {Boxes, Scores}; empty for every other type
   bool enable_int8{false};
   // conv2d / depthwise_conv2d / fc
   std::vector<int8_t> w;
@@ -76,6 +77,12 @@ struct GraphOp {
   int background_label{0}, nms_top_k{-1}, keep_top_k{-1};
   float score_threshold{0.f}, nms_threshold{0.3f}, nms_eta{1.f};
   bool nms_normalized{true};
+  // yolo_box (YoloBoxParam): inputs {X [N, an * (5 + class_num), H, W], ImgSize int32 [N, 2]}, outputs {Boxes [N, an * H * W, 4],
+  // Scores [N, an * H * W, class_num]}
+  std::vector<int> anchors;
+  int class_num{0}, downsample_ratio{0};
+  float conf_thresh{0.f}, scale_x_y{1.f};
+  bool clip_bbox{true};
 };
 
 class GraphBuilder {
@@ -177,6 +184,19 @@ class GraphBuilder {
   // NMS reads the same scores).  No program without a transpose changes.  DEFAULT ON: the whole step of ssd_mini_net was measured
   // faster than the separate instructions in every round, by more than the run-to-run spread.
   void set_fuse_detection_head(bool on) { fuse_detection_head_ = on; }
+  //   (P) a multiclass_nms whose BBoxes operand is concat(axis 1) of the Boxes of k yolo_box ops (1 <= k <= 8) and whose Scores
+  //       operand is transpose(0,2,1) of concat(axis 1) of the Scores of the SAME ops in the SAME order, all of them sharing ImgSize,
+  //       class_num, conf_thresh, clip_bbox and scale_x_y, every link the only reader of the one before it and none fetched; k = 1:
+  //       one yolo_box without concats whose Scores go through the transpose
+  //       => ONE yolo_box/head instruction (plhip_yolo_head_f32) that reads the k feature maps and writes the boxes concat's
+  //       variable [N, P, 4] and the transpose's output variable [N, C, P]; the multiclass_nms is unchanged.  2 k + 3 instructions
+  //       (k = 3: 6 launches and, in the reference, 3 clearing passes) become 1.
+  // Anything else (a fetched link, a second reader, differing attributes, scores concatenated in another order, more than 16
+  // anchors in a map) keeps the separate instructions; with P off, O2 still folds the transpose.  With set_fuse(true) only, in
+  // front of O; bit-identical to the instructions it replaces (the per-cell arithmetic is one device function, the rest are
+  // moves).  No program without a yolo_box changes.  DEFAULT ON: the whole step of yolov3_mini_net was measured faster than the
+  // separate instructions in every round, by more than the run-to-run spread.
+  void set_fuse_yolo_head(bool on) { fuse_yolo_head_ = on; }
   GraphOp& Add(const std::string& type, const std::vector<std::string>& inputs, const std::string& output);
   // Emits the program into `pred`; returns the host-side names of the fetched variables ("<name>/host").
   std::vector<std::string> Lower(HipPredictor* pred);
@@ -205,6 +225,9 @@ class GraphBuilder {
                               // took the calib behind it over carries calib_out / calib_scale / drop_f32
     int nhwc_k{0};            // (O1) a concat step that took the transpose -> reshape chains of its operands over: concat/nhwc, op_inputs
                               // the NCHW tensors, `via` the names no longer written
+    std::vector<int> yolo_ops;  // (P) a yolo_box step that became the yolo_box/head instruction: the ops_ indices of the k yolo_box ops
+                              // in the concats' order; op_inputs {X_0, ImgSize, X_1 ..}, outs {boxes [N, P, 4], scores [N, C, P]}, `via`
+                              // the names no longer written
     bool scores_npc{false};   // (O2) a multiclass_nms step whose Scores operand is the [N, P, C] input of the transpose taken over (`via`)
     bool concat_int8{false};  // (L) a concat step that took the calib behind it over: concat/int8, calib_out / calib_scale / drop_f32
     // kHIP fusions (FuseSteps): tail taken over by an fp32_out conv, int8 max pool behind a fused calib
@@ -261,6 +284,7 @@ class GraphBuilder {
   bool fuse_interp_argmax_{true};
   bool fuse_interp_calib_{true};
   bool fuse_detection_head_{true};
+  bool fuse_yolo_head_{true};
   std::vector<FeedDesc> feeds_;
   std::vector<std::string> fetches_;
   std::vector<GraphOp> ops_;

@@ -10,6 +10,7 @@
 #include "lite/kernels/hip/image_frame.h"
 #include "lite/kernels/hip/se_gate_fusion.h"
 #include "lite/kernels/hip/shuffle_fusion.h"
+#include "lite/kernels/hip/yolo_fusion.h"
 #include "lite/kernels/hip/image_to_tensor.h"
 #include "plhip.h"
 
@@ -622,6 +623,53 @@ void HipPredictor::AddMulticlassNms(const std::string& boxes, const std::string&
   auto* nk = dynamic_cast<kernels::hip::HipNmsFusionKernel*>(kernel.get());
   CHECK(nk) << "the picked multiclass_nms kernel does not take the count tensor";
   nk->SetNmsFusion(fz);
+  Emit(op, std::move(kernel));
+}
+
+void HipPredictor::AddYoloBox(const std::string& x, const std::string& img_size, const std::string& boxes, const std::string& scores,
+                              const std::vector<int>& anchors, int class_num, float conf_thresh, int downsample_ratio, bool clip_bbox,
+                              float scale_x_y) {
+  auto op = std::make_shared<operators::YoloBoxOpLite>();
+  auto& p = op->mutable_param();
+  p.X = Var(x);
+  p.ImgSize = Var(img_size);
+  p.Boxes = Var(boxes);
+  p.Scores = Var(scores);
+  p.anchors = anchors;
+  p.class_num = class_num;
+  p.conf_thresh = conf_thresh;
+  p.downsample_ratio = downsample_ratio;
+  p.clip_bbox = clip_bbox;
+  p.scale_x_y = scale_x_y;
+  Emit(op, PickKernel("yolo_box", Place(TARGET(kHIP), PRECISION(kFloat)), "def"));
+}
+
+void HipPredictor::AddYoloHead(const std::vector<std::string>& xs, const std::string& img_size, const std::string& boxes,
+                               const std::string& scores, const std::vector<std::vector<int>>& anchors, int class_num, float conf_thresh,
+                               const std::vector<int>& downsample_ratios, bool clip_bbox, float scale_x_y) {
+  CHECK(!xs.empty() && xs.size() == anchors.size() && xs.size() == downsample_ratios.size()) << "AddYoloHead: one anchor list and one ratio per map";
+  auto op = std::make_shared<operators::YoloBoxOpLite>();
+  auto& p = op->mutable_param();
+  p.X = Var(xs[0]);
+  p.ImgSize = Var(img_size);
+  p.Boxes = Var(boxes);
+  p.Scores = Var(scores);
+  p.anchors = anchors[0];
+  p.class_num = class_num;
+  p.conf_thresh = conf_thresh;
+  p.downsample_ratio = downsample_ratios[0];
+  p.clip_bbox = clip_bbox;
+  p.scale_x_y = scale_x_y;
+  op->set_head();
+  kernels::hip::HipYoloHead hz;
+  for (size_t i = 1; i < xs.size(); ++i) {
+    op->add_scale(Var(xs[i]), anchors[i]);
+    hz.more.push_back({Var(xs[i]), anchors[i], downsample_ratios[i]});
+  }
+  auto kernel = PickKernel("yolo_box", Place(TARGET(kHIP), PRECISION(kFloat)), "head");
+  auto* hk = dynamic_cast<kernels::hip::HipYoloHeadKernel*>(kernel.get());
+  CHECK(hk) << "the picked yolo_box/head kernel does not take the further feature maps";
+  hk->SetYoloHead(hz);
   Emit(op, std::move(kernel));
 }
 

@@ -142,6 +142,14 @@ class HipPredictor {
                    const std::vector<float>& variance, int axis, bool normalized);
   // out [N, keep_top_k, 6] padded with -1; the per-image counts go to the int32 variable "<out>/count"; index "" = none, else
   // [N, keep_top_k] int32.  scores_npc: `scores` is [N, P, C] (fusion O2: the transpose in front of it folded away)
+  // yolo_box: x [N, an * (5 + class_num), H, W], img_size an int32 [N, 2] variable; boxes [N, an * H * W, 4], scores [N, an * H * W, class_num]
+  void AddYoloBox(const std::string& x, const std::string& img_size, const std::string& boxes, const std::string& scores,
+                  const std::vector<int>& anchors, int class_num, float conf_thresh, int downsample_ratio, bool clip_bbox, float scale_x_y);
+  // fusion P, yolo_box/head: the feature maps xs[i] with anchors[i] and downsample_ratios[i] in one launch; boxes [N, P, 4], scores
+  // [N, class_num, P], P the sum over the maps
+  void AddYoloHead(const std::vector<std::string>& xs, const std::string& img_size, const std::string& boxes, const std::string& scores,
+                   const std::vector<std::vector<int>>& anchors, int class_num, float conf_thresh, const std::vector<int>& downsample_ratios,
+                   bool clip_bbox, float scale_x_y);
   void AddMulticlassNms(const std::string& boxes, const std::string& scores, const std::string& out, const std::string& index,
                         int background_label, float score_threshold, int nms_top_k, float nms_threshold, float nms_eta, int keep_top_k,
                         bool normalized, bool scores_npc = false);

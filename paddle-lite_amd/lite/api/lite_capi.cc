@@ -477,6 +477,24 @@ int pllite_graph_multiclass_nms(pllite_predictor* p, const char* boxes, const ch
     op.nms_normalized = normalized != 0;
   });
 }
+int pllite_graph_yolo_box(pllite_predictor* p, const char* x, const char* img_size, const char* boxes, const char* scores,
+                          const int* anchors, int n_anchors, int class_num, float conf_thresh, int downsample_ratio, int clip_bbox,
+                          float scale_x_y) {
+  return guarded([&] {
+    CHECK(x && img_size && boxes && scores) << "pllite_graph_yolo_box: x, img_size, boxes and scores";
+    auto& op = p->graph.Add("yolo_box", {x, img_size}, boxes);
+    op.outputs = {boxes, scores};
+    op.anchors = ints_of(anchors, n_anchors);
+    op.class_num = class_num;
+    op.conf_thresh = conf_thresh;
+    op.downsample_ratio = downsample_ratio;
+    op.clip_bbox = clip_bbox != 0;
+    op.scale_x_y = scale_x_y;
+  });
+}
+int pllite_graph_set_fuse_yolo_head(pllite_predictor* p, int on) {
+  return guarded([&] { p->graph.set_fuse_yolo_head(on != 0); });
+}
 int pllite_graph_set_fuse_detection_head(pllite_predictor* p, int on) {
   return guarded([&] { p->graph.set_fuse_detection_head(on != 0); });
 }

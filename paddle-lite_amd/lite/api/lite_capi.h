@@ -159,6 +159,15 @@ int pllite_graph_box_coder(pllite_predictor* p, const char* prior, const char* p
 int pllite_graph_multiclass_nms(pllite_predictor* p, const char* boxes, const char* scores, const char* out, const char* index,
                                 int background_label, float score_threshold, int nms_top_k, float nms_threshold, float nms_eta,
                                 int keep_top_k, int normalized);
+/* yolo_box (YoloBoxParam): x [N, (n_anchors / 2) * (5 + class_num), H, W]; img_size a feed of precision 3 (int32) and dims [N, 2]
+ * = (height, width) per image; anchors: n_anchors ints, (width, height) pairs; boxes [N, P, 4] and scores [N, P, class_num] with
+ * P = (n_anchors / 2) * H * W. */
+int pllite_graph_yolo_box(pllite_predictor* p, const char* x, const char* img_size, const char* boxes, const char* scores,
+                          const int* anchors, int n_anchors, int class_num, float conf_thresh, int downsample_ratio, int clip_bbox,
+                          float scale_x_y);
+/* fusion P (k yolo_box ops -> the two concats -> the transpose in front of multiclass_nms's scores become ONE yolo_box/head
+ * instruction; GraphBuilder::set_fuse_yolo_head) */
+int pllite_graph_set_fuse_yolo_head(pllite_predictor* p, int on);
 /* fusion O (the transpose -> reshape -> concat head join in one launch; the transpose in front of multiclass_nms's scores folded
  * into its strides): on by default, effective with pllite_graph_set_fuse(1) only */
 int pllite_graph_set_fuse_detection_head(pllite_predictor* p, int on);

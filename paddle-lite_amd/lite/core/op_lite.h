@@ -705,6 +705,54 @@ class BoxCoderOpLite : public OpLite {
   mutable BoxCoderParam param_;
 };
 
+// yolo_box_op.cc:25-60: X [N, an * (5 + class_num), H, W], ImgSize int32 [N, 2]; Boxes [N, an * H * W, 4], Scores [N, an * H * W,
+// class_num].  kHIP alias head (fusion P, lite/kernels/hip/yolo_fusion.h): further feature maps behind X; Boxes is [N, P, 4] and
+// Scores [N, class_num, P] with P the sum over all maps.
+class YoloBoxOpLite : public OpLite {
+ public:
+  YoloBoxOpLite() : OpLite("yolo_box") {}
+  YoloBoxParam& mutable_param() { return param_; }
+  struct Scale {
+    const lite::Tensor* x;
+    std::vector<int> anchors;
+  };
+  // kHIP fusion P only: Scores is [N, class_num, P]; a further feature map behind X
+  void set_head() { head_ = true; }
+  void add_scale(const lite::Tensor* x, const std::vector<int>& anchors) { more_.push_back({x, anchors}); }
+  // YoloBoxOp::CheckShape on the operands' dims; returns the boxes of one image
+  static int64_t CheckDims(const std::vector<int64_t>& x, const std::vector<int64_t>& img, const std::vector<int>& anchors, int class_num,
+                           const std::string& who) {
+    CHECK(x.size() == 4) << who << ": X must be [N, C, H, W], has rank " << x.size();
+    CHECK(!anchors.empty() && anchors.size() % 2 == 0) << who << ": anchors must hold (width, height) pairs, has " << anchors.size() << " values";
+    CHECK(class_num > 0) << who << ": class_num " << class_num << " must be positive";
+    const int64_t an = static_cast<int64_t>(anchors.size() / 2);
+    CHECK(x[1] == an * (5 + class_num)) << who << ": X has " << x[1] << " channels, " << an << " anchors of " << class_num << " classes need "
+                                        << an * (5 + class_num);
+    CHECK(img.size() == 2 && img[0] == x[0] && img[1] == 2) << who << ": ImgSize must be [" << x[0] << ", 2]";
+    return an * x[2] * x[3];
+  }
+  bool CheckShape() const override {
+    CHECK(param_.X && param_.ImgSize && param_.Boxes && param_.Scores) << "yolo_box: X / ImgSize / Boxes / Scores must be set";
+    return true;
+  }
+  bool InferShapeImpl() const override {
+    const auto img = param_.ImgSize->dims().Vectorize();
+    const auto x = param_.X->dims().Vectorize();
+    int64_t p = CheckDims(x, img, param_.anchors, param_.class_num, "yolo_box");
+    for (auto& m : more_) p += CheckDims(m.x->dims().Vectorize(), img, m.anchors, param_.class_num, "yolo_box/head");
+    param_.Boxes->Resize(std::vector<int64_t>{x[0], p, 4});
+    if (head_) param_.Scores->Resize(std::vector<int64_t>{x[0], param_.class_num, p});
+    else param_.Scores->Resize(std::vector<int64_t>{x[0], p, param_.class_num});
+    return true;
+  }
+  void AttachKernel(KernelBase* k) override { k->SetParam<YoloBoxParam>(param_); }
+
+ private:
+  mutable YoloBoxParam param_;
+  std::vector<Scale> more_;
+  bool head_{false};
+};
+
 // multiclass_nms_op.cc, the 3-D score form.  kHIP: Out is [N, keep_top_k, 6] padded with -1, Index [N, keep_top_k], and the counts
 // [N] go to the tensor set_count names (lite/kernels/hip/detection_fusion.h); scores_npc: the scores are [N, P, C] (fusion O2)
 class MulticlassNmsOpLite : public OpLite {

@@ -4,7 +4,7 @@
 //   ActivationParam :395-419, ConvParam :446-502, PoolParam :539-, ElementwiseParam :643-651,
 //   FusionElementwiseActivationParam :678-680, ShuffleChannelParam :258-263, ConcatParam :369-386, SplitParam :590-608,
 //   InterpolateParam :154-168, ArgmaxParam :821-827, ReshapeParam :342-, TransposeParam :617-, BoxCoderParam :880-,
-//   MulticlassNmsParam :910-922, PriorBoxParam :941-.
+//   MulticlassNmsParam :910-922, PriorBoxParam :941-, YoloBoxParam :266-278.
 // Tensors are NOT owned: params hold raw lite::Tensor* into the caller's scope (conv_op.h:72-74); bias may be null;
 // paddings / dilations are shared_ptrs the op may mutate (UpdatePaddingAndDilation, conv_op.cc:55-81).
 #pragma once
@@ -221,6 +221,21 @@ struct MulticlassNmsParam : ParamBase {
   float nms_eta{1.0f};
   int keep_top_k;
   bool normalized{true};
+};
+
+// kHIP alias head (fusion P) reads further feature maps, which have no field here: lite/kernels/hip/yolo_fusion.h
+struct YoloBoxParam : ParamBase {
+  lite::Tensor* X{};
+  lite::Tensor* ImgSize{};
+  lite::Tensor* Boxes{};
+  lite::Tensor* Scores{};
+
+  std::vector<int> anchors{};
+  int class_num{0};
+  float conf_thresh{0.f};
+  int downsample_ratio{0};
+  bool clip_bbox{true};
+  float scale_x_y{1.0f};
 };
 
 struct PriorBoxParam : ParamBase {

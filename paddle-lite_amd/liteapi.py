@@ -8,6 +8,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libpaddle_lite_hip.so")
 PREC_FLOAT, PREC_INT8, PREC_ANY = 1, 2, 4
+PREC_INT32 = 3  # the ImgSize feed of yolo_box: lowering leaves it alone (no calib, an io_copy of 4-byte elements)
 PREC_UINT8 = 9  # the uint8 image of graph_feed_image / graph_feed_frame (add_feed resizes it)
 LAYOUT_NCHW, LAYOUT_ANY = 1, 2
 # image formats of graph_feed_image == cv::ImageFormat (lite/utils/cv/paddle_image_preprocess.h) == plhip_image_format
@@ -97,6 +98,8 @@ def load():
     L.pllite_graph_box_coder.argtypes = [vp, cs, cs, cs, cs, fp, i32, i32]
     L.pllite_graph_multiclass_nms.argtypes = [vp, cs, cs, cs, cs, i32, f32, i32, f32, f32, i32, i32]
     L.pllite_graph_set_fuse_detection_head.argtypes = [vp, i32]
+    L.pllite_graph_yolo_box.argtypes = [vp, cs, cs, cs, cs, C.POINTER(i32), i32, i32, f32, i32, i32, f32]
+    L.pllite_graph_set_fuse_yolo_head.argtypes = [vp, i32]
     L.pllite_graph_fetch.argtypes = [vp, cs]
     L.pllite_graph_set_fuse.argtypes = [vp, i32]
     L.pllite_graph_set_fuse_dwpw.argtypes = [vp, i32]
@@ -441,6 +444,17 @@ class Predictor:
         self._ck(self.L.pllite_graph_multiclass_nms(self.h, boxes.encode(), scores.encode(), dst.encode(), index.encode(), int(background_label),
                                                     float(score_threshold), int(nms_top_k), float(nms_threshold), float(nms_eta), int(keep_top_k),
                                                     int(normalized)))
+
+    def graph_yolo_box(self, x, img_size, boxes, scores, anchors, class_num, conf_thresh, downsample_ratio, clip_bbox=True, scale_x_y=1.0):
+        """yolo_box: x [N, an * (5 + class_num), H, W]; img_size a feed of PREC_INT32 and dims [N, 2] = (height, width) per image;
+        anchors: (width, height) pairs as a flat list of ints.  boxes [N, an * H * W, 4], scores [N, an * H * W, class_num]."""
+        self._ck(self.L.pllite_graph_yolo_box(self.h, x.encode(), img_size.encode(), boxes.encode(), scores.encode(), _ints(anchors), len(anchors),
+                                              int(class_num), float(conf_thresh), int(downsample_ratio), int(bool(clip_bbox)), float(scale_x_y)))
+
+    def graph_set_fuse_yolo_head(self, on):
+        """Fusion P (default on; with graph_set_fuse(True) only): the yolo_box ops of a YOLOv3 head, the concats of their Boxes and
+        Scores and the transpose(0,2,1) in front of multiclass_nms become one yolo_box/head instruction."""
+        self._ck(self.L.pllite_graph_set_fuse_yolo_head(self.h, int(on)))
 
     def graph_set_fuse_detection_head(self, on):
         """Fusion O (default on; with graph_set_fuse(True) only): (O1) a concat(axis 1) of transpose(0,2,3,1) ->

@@ -338,6 +338,19 @@ class _NetGen:
         self.shape[name] = self.shape[target]
         return name
 
+    def yolo_box(self, names, src, img_size, anchors, class_num, conf_thresh, downsample_ratio, clip_bbox=True, scale_x_y=1.0):
+        """names (Boxes [P, 4], Scores [P, class_num]) per image of the head map src [an * (5 + class_num), h, w], P = an * h * w; img_size:
+        the int32 [N, 2] feed."""
+        c, h, w = self.shape[src]
+        an = len(anchors) // 2
+        assert len(anchors) % 2 == 0 and c == an * (5 + class_num), (c, anchors, class_num)
+        self.ops.append(dict(op="yolo_box", name=names[0], names=list(names), src=src, img_size=img_size, anchors=tuple(int(a) for a in anchors),
+                             class_num=int(class_num), conf_thresh=float(conf_thresh), downsample_ratio=int(downsample_ratio),
+                             clip_bbox=bool(clip_bbox), scale_x_y=float(scale_x_y)))
+        self.shape[names[0]] = (an * h * w, 4)
+        self.shape[names[1]] = (an * h * w, int(class_num))
+        return list(names)
+
     def multiclass_nms(self, name, boxes, scores, background_label, score_threshold, nms_top_k, nms_threshold, keep_top_k, normalized=True,
                        nms_eta=1.0, index=""):
         """name [keep_top_k, 6] per image padded with -1, name + "/count" the per-image counts."""
@@ -744,6 +757,65 @@ def ssd_mini_net(seed=59, res=96, num_classes=21, conf_range=12.0):
     return _finish(g, res, det)
 
 
+COCO_ANCHORS = (10, 13, 16, 30, 33, 23, 30, 61, 62, 45, 59, 119, 116, 90, 156, 198, 373, 326)  # YOLOv3 at 416 (Redmon & Farhadi 2018)
+
+
+def yolov3_mini_net(seed=61, res=96, num_classes=20, obj_shift=1.4, head_range=6.0):
+    """A YOLOv3-shaped detector (Redmon & Farhadi 2018) small enough for the CPU oracle.  Backbone, darknet-style: a 3x3 stem, then
+    five 3x3 stride-2 downsampling convs, each followed by a residual block 1x1 (half the channels) -> 3x3 with an elementwise_add
+    that has no activation; LeakyReLU 0.1 on every conv.  The maps of stride 8 / 16 / 32 (12 x 12, 6 x 6, 3 x 3 at res 96) feed the
+    neck: 1x1 conv -> nearest_interp x2 -> concat with the finer map -> 3x3 conv, twice.  Three linear 1x1 head convs with fp32
+    output write 3 * (5 + num_classes) channels; yolo_box decodes each map with its three of the nine COCO anchors scaled from 416 to
+    res, downsample_ratio 32 / 16 / 8, conf_thresh 0.01 and clip_bbox; the Boxes and the Scores are concatenated along axis 1
+    (coarsest map first, as the reference's YOLOv3 models list them), the scores go through transpose(0,2,1), and multiclass_nms
+    (no background class, score threshold 0.01, top 400, IoU 0.45, keep 100, not normalized) writes "det" and "det/count".
+    P = 3 * (9 + 36 + 144) = 567 at res 96.  The second input is "img_size", int32 [N, 2] (net["img_size"]).
+    The head logits are sized over [-head_range, head_range]; random weights would put half of all cells above any threshold, so the
+    objectness biases are lowered by obj_shift * head_range: a clear share of cells on each side of conf_thresh, as a trained
+    detector leaves most cells empty.  tests/test_yolo_plugin_host.py states what the NMS of the committed seed then sees."""
+    assert res % 32 == 0 and res >= 64, "three maps of stride 8 / 16 / 32"
+    g = _NetGen(seed)
+    g.tensor("image", 3, res, res, 1.0 / 127, 73.0)
+    lk = dict(act=4, act_coef=0.1)
+    x = g.conv("stem", "image", 16, 3, 1, 1, **lk)
+
+    def stage(p, x, cout):
+        d = g.conv(p + "_down", x, cout, 3, 2, 1, **lk)
+        a = g.conv(p + "_a", d, cout // 2, 1, 1, 0, headroom=1.25, **lk)
+        b = g.conv(p + "_b", a, cout, 3, 1, 1, **lk)
+        return g.widen(g.add(p + "_res", d, b), 1.5)  # the sum of two leaky tensors has heavier tails than the sizing rule assumes
+
+    x = stage("s2", stage("s1", x, 32), 48)
+    m8 = stage("s3", x, 64)
+    m16 = stage("s4", m8, 96)
+    m32 = stage("s5", m16, 128)
+    anchors = [int(round(a * res / 416.0)) or 1 for a in COCO_ANCHORS]
+    ch = 3 * (5 + num_classes)
+    boxes, scores = [], []
+
+    def head(tag, f, k, ratio):
+        hc = g.conv(tag + "_head", f, ch, 1, 1, 0, act=0, out_range=head_range)
+        g.ops[-1]["bias"][4::5 + num_classes] -= np.float32(obj_shift * head_range)  # channel a * (5 + classes) + 4
+        b, s = g.yolo_box([tag + "_boxes", tag + "_scores"], hc, "img_size", anchors[6 * k:6 * k + 6], num_classes, 0.01, ratio, True, 1.0)
+        boxes.append(b)
+        scores.append(s)
+
+    p32 = g.conv("n32", m32, 64, 1, 1, 0, headroom=1.5, **lk)
+    head("y32", p32, 2, 32)
+    u = g.interp("n32_up", g.conv("n32_lat", p32, 32, 1, 1, 0, **lk), "nearest", (res // 16, res // 16), align_corners=False)
+    p16 = g.conv("n16", g.widen(g.concat("n16_cat", [u, m16]), 1.25), 64, 3, 1, 1, headroom=1.5, **lk)
+    head("y16", p16, 1, 16)
+    u = g.interp("n16_up", g.conv("n16_lat", p16, 32, 1, 1, 0, **lk), "nearest", (res // 8, res // 8), align_corners=False)
+    p8 = g.conv("n8", g.widen(g.concat("n8_cat", [u, m8]), 1.25), 64, 3, 1, 1, headroom=1.5, **lk)
+    head("y8", p8, 0, 8)
+    b = g.join("boxes", boxes, 1)
+    s = g.transpose("scores", g.join("scores_npc", scores, 1), (0, 2, 1))
+    det = g.multiclass_nms("det", b, s, -1, 0.01, 400, 0.45, 100, normalized=False)
+    net = _finish(g, res, det)
+    net["img_size"] = "img_size"
+    return net
+
+
 def concat_calib_bytes(net, batch):
     """Algorithmic bytes of every concat that a calib reads directly or through a max pool, as separate concat and calib
     instructions (17 per concatenated element: 4 + 4 for the move, 4 + 4 + 1 for the calib; counted where the calib reads the pool
@@ -811,7 +883,7 @@ def net_stats(net):
 
 
 def emit_graph(pred, net, batch, fuse=True, fuse_dwpw=None, fuse_dwconv=None, image=None, frame=None, fuse_hard_act=None, fuse_shuffle=None,
-               fuse_concat=None, fuse_interp_argmax=None, fuse_interp_calib=None, fuse_detection_head=None, fetch=()):
+               fuse_concat=None, fuse_interp_argmax=None, fuse_interp_calib=None, fuse_detection_head=None, fetch=(), fuse_yolo_head=None):
     """Feed the op list to the predictor's graph mode and lower it.  Returns the host name of the output variable.
     image: None = the input is the normalised fp32 NCHW tensor; dict(format, means, scales) = the input is a decoded uint8 image
     [batch, h, w, cs] of that format (liteapi.IMG_*), normalised on the device (Predictor.graph_feed_image).
@@ -833,6 +905,9 @@ def emit_graph(pred, net, batch, fuse=True, fuse_dwpw=None, fuse_dwconv=None, im
     prediction ops, each with a switch of its own.
     fuse_detection_head: None = the builder's default (on); False = the separate instructions; fusion O of the detection heads (a concat of transpose -> reshape
     chains becomes one concat/nhwc instruction; the transpose in front of multiclass_nms's scores disappears into its strides).
+    fuse_yolo_head: None = the builder's default (on); fusion P of a YOLOv3 head (the yolo_box ops, the concats of their
+    outputs and the transpose in front of multiclass_nms become one yolo_box/head instruction), False = the separate instructions.
+    A net with an "img_size" entry gets that variable as a second feed, int32 [batch, 2] = (height, width) of every image.
     fetch: further variables to fetch beside net["output"] (host names: "<name>/host").  A multiclass_nms output is fetched together
     with its count variable "<name>/count"."""
     from . import liteapi
@@ -853,6 +928,8 @@ def emit_graph(pred, net, batch, fuse=True, fuse_dwpw=None, fuse_dwconv=None, im
         pred.graph_set_fuse_interp_calib(fuse_interp_calib)
     if fuse_detection_head is not None:
         pred.graph_set_fuse_detection_head(fuse_detection_head)
+    if fuse_yolo_head is not None:
+        pred.graph_set_fuse_yolo_head(fuse_yolo_head)
     c, h, w = net["input_shape"]
     if frame is not None:
         assert image is None, "emit_graph: image= and frame= exclude each other"
@@ -861,6 +938,8 @@ def emit_graph(pred, net, batch, fuse=True, fuse_dwpw=None, fuse_dwconv=None, im
         pred.graph_feed(net["input"], (batch, c, h, w), liteapi.PREC_FLOAT)
     else:
         pred.graph_feed_image(net["input"], batch, h, w, image["format"], image["means"], image["scales"])
+    if net.get("img_size"):
+        pred.graph_feed(net["img_size"], (batch, 2), liteapi.PREC_INT32)
     for o in net["ops"]:
         t = o["op"]
         if t in ("conv2d", "depthwise_conv2d"):
@@ -906,6 +985,9 @@ def emit_graph(pred, net, batch, fuse=True, fuse_dwpw=None, fuse_dwconv=None, im
                                  o["variances"], o["flip"], o["clip"], o["step_w"], o["step_h"], o["offset"], o["min_max_aspect_ratios_order"])
         elif t == "box_coder":
             pred.graph_box_coder(o["prior"], o["target"], o["name"], o["prior_var"], o["variance"], o["axis"], o["normalized"])
+        elif t == "yolo_box":
+            pred.graph_yolo_box(o["src"], o["img_size"], o["names"][0], o["names"][1], o["anchors"], o["class_num"], o["conf_thresh"],
+                                o["downsample_ratio"], o["clip_bbox"], o["scale_x_y"])
         elif t == "multiclass_nms":
             pred.graph_multiclass_nms(o["boxes"], o["scores"], o["name"], o["background_label"], o["score_threshold"], o["nms_top_k"],
                                       o["nms_threshold"], o["nms_eta"], o["keep_top_k"], o["normalized"], o["index"])

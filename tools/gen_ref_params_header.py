@@ -10,7 +10,7 @@ import re
 
 STRUCTS = ["ParamBase", "IoCopyParam", "CalibParam", "FcParam", "SoftmaxParam", "ActivationParam", "ConvParam", "PoolParam",
            "ElementwiseParam", "FusionElementwiseActivationParam", "ShuffleChannelParam", "ConcatParam", "SplitParam", "InterpolateParam", "ArgmaxParam",
-           "ReshapeParam", "TransposeParam", "BoxCoderParam", "MulticlassNmsParam", "PriorBoxParam"]
+           "ReshapeParam", "TransposeParam", "BoxCoderParam", "MulticlassNmsParam", "PriorBoxParam", "YoloBoxParam"]
 
 
 def struct_text(src, name):
