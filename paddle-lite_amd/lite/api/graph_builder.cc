@@ -9,6 +9,7 @@
 #include "lite/kernels/hip/prior_box_host.h"
 #include "plhip.h"
 
+#include <algorithm>
 #include <cstdio>
 #include <set>
 
@@ -450,6 +451,16 @@ void AppendNum(std::string* l, const char* key, float x) {
   *l += buf;
 }
 
+// "a,b,c" of names or ints
+const std::string& Str(const std::string& s) { return s; }
+std::string Str(int v) { return std::to_string(v); }
+template <class T>
+std::string Join(const std::vector<T>& v) {
+  std::string a;
+  for (size_t i = 0; i < v.size(); ++i) a += (i ? "," : "") + Str(v[i]);
+  return a;
+}
+
 }  // namespace
 
 struct GraphBuilder::Fuser {
@@ -497,6 +508,26 @@ struct GraphBuilder::Fuser {
       if (Live(t, kind) && st[t].in == v) k = static_cast<int>(t);
     return k;
   }
+  // Step i takes the calib[fp32_to_int8] over that reads v at or behind step `from`: the calib's tensor and scale go to the step and the
+  // calib dies.  False (nothing changed) where there is none.  drop_f32 is the caller's: which variable must have no reader left
+  // (K1 asks about `hi`, not `out`) it alone knows, and it asks after it killed what else it took over.
+  bool TakeCalib(size_t i, const std::string& v, size_t from) {
+    const int k = FindByInput(StepKind::kCalibF2I, v, from);
+    if (k < 0) return false;
+    st[i].calib_out = st[k].out;
+    st[i].calib_scale = st[k].scale;
+    dead[k] = true;
+    return true;
+  }
+  // The live step of graph op `type` one of whose outputs is v, v being read by exactly one live step (a fetch counts), or -1
+  int SoleProducer(const std::string& v, const char* type) const {
+    if (Uses(v) != 1) return -1;
+    for (size_t t = 0; t < st.size(); ++t) {
+      if (dead[t] || !IsOp(static_cast<int>(t), type)) continue;
+      if (st[t].out == v || std::find(st[t].outs.begin(), st[t].outs.end(), v) != st[t].outs.end()) return static_cast<int>(t);
+    }
+    return -1;
+  }
   // The descriptor of conv step i on the propagated shape of its input
   bool InputDesc(int i, plhip_conv_desc* d) const {
     const auto it = st[i].op_inputs.empty() ? shape.end() : shape.find(st[i].op_inputs[0]);
@@ -516,6 +547,7 @@ struct GraphBuilder::Fuser {
   void CalibIntoStem();
   void DepthwiseConv1x1Tail();
   void SeGate();
+  void CalibBehind(bool (*takes)(const GraphOp&));
   void HardActCalib();
   void ShuffleTail();
   void ConcatCalib();
@@ -796,19 +828,18 @@ void GraphBuilder::Fuser::SeGate() {
   }
 }
 
-// (J1) (J3) hard_swish / elementwise_mul whose fp32 output a calib[fp32_to_int8] reads takes that calib over: one launch writes
-// the int8 tensor and, only where it has other readers, the fp32 one
-void GraphBuilder::Fuser::HardActCalib() {
+// (J1) (J3) (N) an untouched step of an op `takes` accepts whose fp32 output a calib[fp32_to_int8] reads takes that calib over: one
+// launch writes the int8 tensor and, only where it has other readers, the fp32 one
+void GraphBuilder::Fuser::CalibBehind(bool (*takes)(const GraphOp&)) {
   for (size_t i = 0; i < st.size(); ++i) {
-    if (dead[i] || !st[i].calib_out.empty() || !(IsOp(static_cast<int>(i), "hard_swish") || IsOp(static_cast<int>(i), "elementwise_mul")))
-      continue;
-    const int k = FindByInput(StepKind::kCalibF2I, st[i].out, i + 1);
-    if (k < 0) continue;
-    st[i].calib_out = st[k].out;
-    st[i].calib_scale = st[k].scale;
-    dead[k] = true;
-    st[i].drop_f32 = Uses(st[i].out) == 0;
+    if (!Live(i, StepKind::kOp) || st[i].form != Form::kPlain || !st[i].calib_out.empty() || !takes(Op(i))) continue;
+    if (TakeCalib(i, st[i].out, i + 1)) st[i].drop_f32 = Uses(st[i].out) == 0;
   }
+}
+
+// (J1) (J3) hard_swish / elementwise_mul
+void GraphBuilder::Fuser::HardActCalib() {
+  CalibBehind([](const GraphOp& op) { return op.type == "hard_swish" || op.type == "elementwise_mul"; });
 }
 
 // (K) concat(axis 1, two inputs of equal channels) whose only reader is a shuffle_channel(group 2): (K1) where that op's only reader
@@ -819,7 +850,7 @@ void GraphBuilder::Fuser::HardActCalib() {
 void GraphBuilder::Fuser::ShuffleTail() {
   const auto& shapes = var_shape;  // by graph variable: K needs the channels behind pools, which PropagateShapes does not follow
   for (size_t i = 0; i < st.size(); ++i) {
-    if (dead[i] || !IsOp(static_cast<int>(i), "concat") || st[i].shuffle_tail) continue;
+    if (dead[i] || !IsOp(static_cast<int>(i), "concat") || st[i].form != Form::kPlain) continue;
     const GraphOp& cat = Op(i);
     if (cat.inputs.size() != 2) continue;
     const auto a = shapes.find(cat.inputs[0]), b = shapes.find(cat.inputs[1]);
@@ -834,26 +865,20 @@ void GraphBuilder::Fuser::ShuffleTail() {
       const bool halves = st[k].outs.size() == 2 && (sp.axis == 1 || sp.axis == -3) &&
                           (sp.num == 2 || (sp.num == 0 && sp.sections == std::vector<int>({static_cast<int>(h), static_cast<int>(h)})));
       if (!halves) continue;
-      const int c = FindByInput(StepKind::kCalibF2I, st[k].outs[1], k + 1);
-      if (c < 0) continue;
-      st[i].shuffle_tail = 2;
+      if (!TakeCalib(i, st[k].outs[1], k + 1)) continue;
+      st[i].form = Form::kShuffleUnit;
       st[i].via = st[i].out + "," + st[j].out;
       st[i].out = st[k].outs[0];
       st[i].hi = st[k].outs[1];
-      st[i].calib_out = st[c].out;
-      st[i].calib_scale = st[c].scale;
-      dead[j] = dead[k] = dead[c] = true;
+      dead[j] = dead[k] = true;
       st[i].drop_f32 = Uses(st[i].hi) == 0;
       continue;
     }
-    const int c = FindByInput(StepKind::kCalibF2I, st[j].out, j + 1);  // (K2)
-    if (c < 0) continue;
-    st[i].shuffle_tail = 1;
+    if (!TakeCalib(i, st[j].out, j + 1)) continue;  // (K2)
+    st[i].form = Form::kShuffleInt8;
     st[i].via = st[i].out;
     st[i].out = st[j].out;
-    st[i].calib_out = st[c].out;
-    st[i].calib_scale = st[c].scale;
-    dead[j] = dead[c] = true;
+    dead[j] = true;
     st[i].drop_f32 = Uses(st[i].out) == 0;
   }
 }
@@ -864,9 +889,10 @@ void GraphBuilder::Fuser::ShuffleTail() {
 void GraphBuilder::Fuser::ConcatCalib() {
   auto same_bits = [](float a, float b) { return memcmp(&a, &b, sizeof a) == 0; };
   for (size_t i = 0; i < st.size(); ++i) {
-    if (dead[i] || !IsOp(static_cast<int>(i), "concat") || st[i].shuffle_tail || st[i].concat_int8) continue;
+    if (dead[i] || !IsOp(static_cast<int>(i), "concat") || st[i].form != Form::kPlain) continue;
     const std::string out = st[i].out;
-    const int d = FindByInput(StepKind::kCalibF2I, out, i + 1);
+    // D, taken at once: with D the step always becomes concat/int8, and a dead D changes no use count the pools below are asked about
+    const bool direct = TakeCalib(i, out, i + 1);
     std::vector<std::pair<int, int>> pools;  // (pool, its calib)
     for (size_t t = i + 1; t < st.size(); ++t) {
       if (dead[t] || !IsOp(static_cast<int>(t), "pool2d") || st[t].pool_int8 || st[t].op_inputs.size() != 1 || st[t].op_inputs[0] != out) continue;
@@ -874,15 +900,16 @@ void GraphBuilder::Fuser::ConcatCalib() {
       const int k = SoleReader(st[t].out);
       if (k >= 0 && st[k].kind == StepKind::kCalibF2I) pools.emplace_back(static_cast<int>(t), k);
     }
-    if (d < 0 && pools.empty()) continue;
-    const float scale = d >= 0 ? st[d].scale : st[pools[0].second].scale;
+    if (!direct && pools.empty()) continue;
+    const float scale = direct ? st[i].calib_scale : st[pools[0].second].scale;
     bool common = true;
     for (auto& pk : pools) common = common && same_bits(st[pk.second].scale, scale);
-    if (d < 0 && !common) continue;  // no direct calib and no one scale for the int8 copy
-    st[i].concat_int8 = true;
-    st[i].calib_out = d >= 0 ? st[d].out : out + "/precision_trans";
-    st[i].calib_scale = scale;
-    if (d >= 0) dead[d] = true;
+    if (!direct && !common) continue;  // no direct calib and no one scale for the int8 copy
+    st[i].form = Form::kConcatInt8;
+    if (!direct) {
+      st[i].calib_out = out + "/precision_trans";
+      st[i].calib_scale = scale;
+    }
     for (auto& pk : pools) {
       if (!same_bits(st[pk.second].scale, scale)) continue;
       st[pk.first].op_inputs[0] = st[i].calib_out;
@@ -898,9 +925,10 @@ void GraphBuilder::Fuser::ConcatCalib() {
 // It runs where the interp ran: its one operand exists there, and the labels were written later before.
 void GraphBuilder::Fuser::InterpArgmax() {
   for (size_t i = 0; i < st.size(); ++i) {
-    if (dead[i] || st[i].kind != StepKind::kOp || !IsInterp(Op(i)) || st[i].argmax_op >= 0 || !st[i].calib_out.empty()) continue;
+    if (!Live(i, StepKind::kOp) || !IsInterp(Op(i)) || st[i].form != Form::kPlain || !st[i].calib_out.empty()) continue;
     const int j = SoleReader(st[i].out);
     if (!IsOp(j, "arg_max") || !(Op(j).axis == 1 || Op(j).axis == -3)) continue;
+    st[i].form = Form::kArgmaxInterp;
     st[i].argmax_op = st[j].op;
     st[i].via = st[i].out;
     st[i].out = st[j].out;
@@ -908,33 +936,15 @@ void GraphBuilder::Fuser::InterpArgmax() {
   }
 }
 
-// (N) an interp M left alone whose fp32 output a calib[fp32_to_int8] reads takes that calib over, as J1 / J3 do: one launch writes
-// the int8 tensor and, only where it has other readers, the fp32 one
-void GraphBuilder::Fuser::InterpCalib() {
-  for (size_t i = 0; i < st.size(); ++i) {
-    if (dead[i] || st[i].kind != StepKind::kOp || !IsInterp(Op(i)) || st[i].argmax_op >= 0 || !st[i].calib_out.empty()) continue;
-    const int k = FindByInput(StepKind::kCalibF2I, st[i].out, i + 1);
-    if (k < 0) continue;
-    st[i].calib_out = st[k].out;
-    st[i].calib_scale = st[k].scale;
-    dead[k] = true;
-    st[i].drop_f32 = Uses(st[i].out) == 0;
-  }
-}
+// (N) an interp M left alone, as J1 / J3
+void GraphBuilder::Fuser::InterpCalib() { CalibBehind(IsInterp); }
 
 // (O1) a concat(axis 1) all of whose operands come from transpose(0,2,3,1) -> reshape([0,-1,k]) chains of one k becomes concat/nhwc on
 // the chains' NCHW inputs; it runs where the concat ran (every operand exists there).  (O2) a transpose(0,2,1) whose only reader is the
 // Scores operand of a multiclass_nms disappears; the NMS reads the transpose's input through its strides.
 void GraphBuilder::Fuser::DetectionHead() {
-  // the live op step that writes v and is read by nothing but step `reader` (fetches count as readers), or -1
-  auto sole_producer = [&](const std::string& v, const char* type) {
-    if (Uses(v) != 1) return -1;
-    for (size_t t = 0; t < st.size(); ++t)
-      if (!dead[t] && IsOp(static_cast<int>(t), type) && st[t].out == v) return static_cast<int>(t);
-    return -1;
-  };
   for (size_t i = 0; i < st.size(); ++i) {
-    if (dead[i] || !IsOp(static_cast<int>(i), "concat") || st[i].shuffle_tail || st[i].concat_int8 || st[i].nhwc_k) continue;
+    if (dead[i] || !IsOp(static_cast<int>(i), "concat") || st[i].form != Form::kPlain) continue;
     const auto os = var_shape.find(Op(i).output);
     if (os == var_shape.end() || os->second.size() != 3 || !(Op(i).axis == 1 || Op(i).axis == -2)) continue;
     int k = 0;
@@ -942,13 +952,13 @@ void GraphBuilder::Fuser::DetectionHead() {
     std::vector<std::string> srcs;
     bool ok = !st[i].op_inputs.empty();
     for (size_t q = 0; ok && q < st[i].op_inputs.size(); ++q) {
-      const int r = sole_producer(st[i].op_inputs[q], "reshape");
+      const int r = SoleProducer(st[i].op_inputs[q], "reshape");
       if (r < 0) { ok = false; break; }
       const std::vector<int>& sh = Op(r).shape;
       ok = sh.size() == 3 && sh[0] == 0 && sh[1] == -1 && sh[2] > 0 && (k == 0 || sh[2] == k);
       if (!ok) break;
       k = sh[2];
-      const int t = sole_producer(st[r].op_inputs[0], "transpose");
+      const int t = SoleProducer(st[r].op_inputs[0], "transpose");
       if (t < 0 || Op(t).perm != std::vector<int>({0, 2, 3, 1})) { ok = false; break; }
       // one operand twice would make its chain's variables have two uses: the use counts above already refuse it
       chain.push_back(r);
@@ -961,11 +971,12 @@ void GraphBuilder::Fuser::DetectionHead() {
       dead[chain[q]] = dead[chain[q + 1]] = true;
     }
     st[i].op_inputs = srcs;
+    st[i].form = Form::kConcatNhwc;
     st[i].nhwc_k = k;
   }
   for (size_t i = 0; i < st.size(); ++i) {
     if (dead[i] || !IsOp(static_cast<int>(i), "multiclass_nms") || st[i].scores_npc) continue;
-    const int t = sole_producer(st[i].op_inputs[1], "transpose");
+    const int t = SoleProducer(st[i].op_inputs[1], "transpose");
     if (t < 0 || Op(t).perm != std::vector<int>({0, 2, 1})) continue;
     st[i].via = st[t].out;
     st[i].op_inputs[1] = st[t].op_inputs[0];
@@ -976,37 +987,28 @@ void GraphBuilder::Fuser::DetectionHead() {
 
 // (P): see graph_builder.h
 void GraphBuilder::Fuser::YoloHead() {
-  // the live step of graph op `type` one of whose outputs is v, v being read by exactly one live step (a fetch counts), or -1
-  auto sole_producer = [&](const std::string& v, const char* type) {
-    if (Uses(v) != 1) return -1;
-    for (size_t t = 0; t < st.size(); ++t) {
-      if (dead[t] || !IsOp(static_cast<int>(t), type)) continue;
-      if (st[t].out == v || std::find(st[t].outs.begin(), st[t].outs.end(), v) != st[t].outs.end()) return static_cast<int>(t);
-    }
-    return -1;
-  };
   auto plain_concat = [&](int t) {
-    if (t < 0 || st[t].shuffle_tail || st[t].concat_int8 || st[t].nhwc_k) return false;
+    if (t < 0 || st[t].form != Form::kPlain) return false;
     const auto os = var_shape.find(Op(t).output);
     return os != var_shape.end() && os->second.size() == 3 && (Op(t).axis == 1 || Op(t).axis == -2);
   };
   for (size_t i = 0; i < st.size(); ++i) {
     if (dead[i] || !IsOp(static_cast<int>(i), "multiclass_nms") || st[i].scores_npc) continue;
-    const int tr = sole_producer(st[i].op_inputs[1], "transpose");
+    const int tr = SoleProducer(st[i].op_inputs[1], "transpose");
     if (tr < 0 || Op(tr).perm != std::vector<int>({0, 2, 1})) continue;
     std::vector<int> ys;  // the yolo_box steps in the boxes' order
     int cb = -1, cs = -1;
-    const int y1 = sole_producer(st[i].op_inputs[0], "yolo_box");
+    const int y1 = SoleProducer(st[i].op_inputs[0], "yolo_box");
     if (y1 >= 0) {  // k = 1
       if (st[y1].outs.size() != 2 || st[y1].outs[0] != st[i].op_inputs[0] || st[y1].outs[1] != st[tr].op_inputs[0] || Uses(st[y1].outs[1]) != 1) continue;
       ys.push_back(y1);
     } else {
-      cb = sole_producer(st[i].op_inputs[0], "concat");
-      cs = sole_producer(st[tr].op_inputs[0], "concat");
+      cb = SoleProducer(st[i].op_inputs[0], "concat");
+      cs = SoleProducer(st[tr].op_inputs[0], "concat");
       if (!plain_concat(cb) || !plain_concat(cs) || st[cb].op_inputs.size() != st[cs].op_inputs.size()) continue;
       bool ok = true;
       for (size_t q = 0; ok && q < st[cb].op_inputs.size(); ++q) {
-        const int y = sole_producer(st[cb].op_inputs[q], "yolo_box");
+        const int y = SoleProducer(st[cb].op_inputs[q], "yolo_box");
         ok = y >= 0 && st[y].outs.size() == 2 && st[y].outs[0] == st[cb].op_inputs[q] && st[y].outs[1] == st[cs].op_inputs[q] &&
              Uses(st[y].outs[1]) == 1 && std::find(ys.begin(), ys.end(), y) == ys.end();
         if (ok) ys.push_back(y);
@@ -1025,6 +1027,7 @@ void GraphBuilder::Fuser::YoloHead() {
     // the last of the yolo_box steps carries the instruction: every feature map has been written in front of it
     const int at = *std::max_element(ys.begin(), ys.end());
     Step head = st[at];
+    head.form = Form::kYoloHead;
     head.yolo_ops.clear();
     head.op_inputs = {st[ys[0]].op_inputs[0], st[ys[0]].op_inputs[1]};
     head.via.clear();
@@ -1064,6 +1067,11 @@ void GraphBuilder::Fuser::YoloHead() {
 //     concat whose output a calib reads stays L's) or of a multiclass_nms.
 //   * P in front of O: O2 would fold the transpose P needs to see; P takes yolo_box ops and plain rank-3 concats of their outputs,
 //     which no rewrite above matches (no calib reads them).
+// A rewrite that turns a step into ONE other instruction sets its Step::form, and one that needs an untouched step asks
+// form == kPlain.  That asks exactly what the flags of each form asked one by one: the forms of a concat step are set by K, L and
+// O1 in that order, and each of them, and P's plain_concat, refused every form set before it; the one form of an interp step is
+// M's, which M and N refused (N's calib_out is a modifier, so both still ask for it by name); the one form of a yolo_box step is
+// P's, which nothing asks about.  A form never sits on a step of a type whose rewrite did not test for it before.
 void GraphBuilder::FuseSteps(std::vector<Step>* steps, const std::map<std::string, std::vector<int64_t>>& shapes) {
   Fuser f(*this, steps, shapes);
   f.ConvTails();
@@ -1096,23 +1104,6 @@ std::vector<GraphBuilder::Step> GraphBuilder::Program() {
 
 std::string GraphBuilder::OpLine(const Step& s) const {
   const GraphOp& op = ops_[s.op];
-  if (s.shuffle_tail) {  // (K): the concat step that became the one instruction
-    std::string l = std::string("shuffle_channel/") + (s.shuffle_tail == 2 ? "unit" : "int8") + " in=" + s.op_inputs[0] + "," + s.op_inputs[1] +
-                    " out=" + s.out;
-    if (s.shuffle_tail == 2 && !s.drop_f32) l += " +hi=" + s.hi;
-    l += " +calib=" + s.calib_out;
-    AppendNum(&l, "scale", s.calib_scale);
-    if (s.shuffle_tail == 1 && s.drop_f32) l += " -f32";
-    return l + " via=" + s.via + (s.shuffle_tail == 2 && s.drop_f32 ? "," + s.hi : "");
-  }
-  if (s.concat_int8) {  // (L): the concat step that took the calib over
-    std::string l = "concat/int8 in=";
-    for (size_t i = 0; i < s.op_inputs.size(); ++i) l += (i ? "," : "") + s.op_inputs[i];
-    l += " out=" + s.out + " +calib=" + s.calib_out;
-    AppendNum(&l, "scale", s.calib_scale);
-    if (s.drop_f32) l += " -f32";
-    return l + " axis=" + std::to_string(op.axis);
-  }
   auto list_of = [](const char* key, const std::vector<float>& v) {
     std::string a = std::string(" ") + key + "=";
     for (size_t i = 0; i < v.size(); ++i) {
@@ -1122,22 +1113,15 @@ std::string GraphBuilder::OpLine(const Step& s) const {
     }
     return a;
   };
-  auto ints_of = [](const char* key, const std::vector<int>& v) {
-    std::string a = std::string(" ") + key + "=";
-    for (size_t i = 0; i < v.size(); ++i) a += (i ? "," : "") + std::to_string(v[i]);
-    return a;
-  };
-  if (op.type == "yolo_box") {  // yolo_box/def, or (P) yolo_box/head: the attributes of every feature map, '|' between the maps
-    const bool head = !s.yolo_ops.empty();
-    std::string l = std::string("yolo_box/") + (head ? "head" : "def") + " in=";
-    for (size_t i = 0; i < s.op_inputs.size(); ++i) l += (i ? "," : "") + s.op_inputs[i];
-    l += " out=" + s.outs[0] + "," + s.outs[1];
+  // yolo_box/def, or (P) yolo_box/head: the attributes of every feature map, '|' between the maps
+  auto yolo_line = [&](bool head) {
+    std::string l = std::string("yolo_box/") + (head ? "head" : "def") + " in=" + Join(s.op_inputs) + " out=" + s.outs[0] + "," + s.outs[1];
     std::string anchors = " anchors=", ratios = " downsample_ratio=";
     const std::vector<int> self{s.op};
     const std::vector<int>& maps = head ? s.yolo_ops : self;
     for (size_t q = 0; q < maps.size(); ++q) {
       const GraphOp& y = ops_[maps[q]];
-      anchors += (q ? "|" : "") + ints_of("", y.anchors).substr(2);
+      anchors += (q ? "|" : "") + Join(y.anchors);
       ratios += (q ? "|" : "") + std::to_string(y.downsample_ratio);
     }
     l += anchors + " class_num=" + std::to_string(op.class_num);
@@ -1145,12 +1129,7 @@ std::string GraphBuilder::OpLine(const Step& s) const {
     l += ratios + " clip_bbox=" + std::to_string(op.clip_bbox ? 1 : 0);
     AppendNum(&l, "scale_x_y", op.scale_x_y);
     return head ? l + " via=" + s.via : l;
-  }
-  if (s.nhwc_k) {  // (O1): the concat step that took the transpose -> reshape chains over
-    std::string l = "concat/nhwc in=";
-    for (size_t i = 0; i < s.op_inputs.size(); ++i) l += (i ? "," : "") + s.op_inputs[i];
-    return l + " out=" + s.out + " k=" + std::to_string(s.nhwc_k) + " via=" + s.via;
-  }
+  };
   auto interp_attrs = [](const GraphOp& o) {
     std::string a = o.out_h > 0 && o.out_w > 0 ? " size=" + std::to_string(o.out_h) + "x" + std::to_string(o.out_w) : std::string();
     if (a.empty()) AppendNum(&a, "by", o.interp_scale);
@@ -1159,9 +1138,31 @@ std::string GraphBuilder::OpLine(const Step& s) const {
   auto argmax_attrs = [](const GraphOp& o) {
     return " axis=" + std::to_string(o.axis) + " dtype=" + std::to_string(o.dtype) + " keepdims=" + std::to_string(o.keepdims ? 1 : 0);
   };
-  if (s.argmax_op >= 0)  // (M): the interp step that became the one instruction
-    return "arg_max/interp in=" + s.op_inputs[0] + " out=" + s.out + " +interp=" + op.type + interp_attrs(op) + argmax_attrs(ops_[s.argmax_op]) +
-           " via=" + s.via;
+  switch (s.form) {  // the step that became ONE other instruction
+    case Form::kShuffleInt8:
+    case Form::kShuffleUnit: {
+      const bool unit = s.form == Form::kShuffleUnit;
+      std::string l = std::string("shuffle_channel/") + (unit ? "unit" : "int8") + " in=" + s.op_inputs[0] + "," + s.op_inputs[1] + " out=" + s.out;
+      if (unit && !s.drop_f32) l += " +hi=" + s.hi;
+      l += " +calib=" + s.calib_out;
+      AppendNum(&l, "scale", s.calib_scale);
+      if (!unit && s.drop_f32) l += " -f32";
+      return l + " via=" + s.via + (unit && s.drop_f32 ? "," + s.hi : "");
+    }
+    case Form::kConcatInt8: {
+      std::string l = "concat/int8 in=" + Join(s.op_inputs) + " out=" + s.out + " +calib=" + s.calib_out;
+      AppendNum(&l, "scale", s.calib_scale);
+      if (s.drop_f32) l += " -f32";
+      return l + " axis=" + std::to_string(op.axis);
+    }
+    case Form::kConcatNhwc: return "concat/nhwc in=" + Join(s.op_inputs) + " out=" + s.out + " k=" + std::to_string(s.nhwc_k) + " via=" + s.via;
+    case Form::kArgmaxInterp:
+      return "arg_max/interp in=" + s.op_inputs[0] + " out=" + s.out + " +interp=" + op.type + interp_attrs(op) + argmax_attrs(ops_[s.argmax_op]) +
+             " via=" + s.via;
+    case Form::kYoloHead: return yolo_line(true);
+    case Form::kPlain: break;
+  }
+  if (op.type == "yolo_box") return yolo_line(false);
   std::string l = op.type;
   if (op.enable_int8) {
     const bool fc = op.type == "fc";
@@ -1170,26 +1171,18 @@ std::string GraphBuilder::OpLine(const Step& s) const {
     const bool tail_op = op.type == "hard_swish" || op.type == "elementwise_mul" || IsInterp(op);  // (J1) (J3) (N): the alias that carries a calib tail
     l += tail_op && !s.calib_out.empty() ? "/int8" : "/def";
   }
-  l += " in=";
-  for (size_t i = 0; i < s.op_inputs.size(); ++i) l += (i ? "," : "") + s.op_inputs[i];
-  l += " out=" + s.out;
+  l += " in=" + Join(s.op_inputs) + " out=" + s.out;
   for (size_t i = 1; i < s.outs.size(); ++i) l += "," + s.outs[i];
   if (op.type == "concat" || op.type == "split") l += " axis=" + std::to_string(op.axis);
   if (op.type == "split" && op.num > 0) l += " num=" + std::to_string(op.num);
-  if (op.type == "split" && op.num <= 0) {
-    l += " sections=";
-    for (size_t i = 0; i < op.sections.size(); ++i) l += (i ? "," : "") + std::to_string(op.sections[i]);
-  }
+  if (op.type == "split" && op.num <= 0) l += " sections=" + Join(op.sections);
   if (op.type == "shuffle_channel") l += " group=" + std::to_string(op.group);
   if (op.type == "conv2d_transpose" && !op.conv.output_size.empty())
     l += " output_size=" + std::to_string(op.conv.output_size[0]) + "x" + std::to_string(op.conv.output_size[1]);
   if (IsInterp(op)) l += interp_attrs(op);
   if (op.type == "arg_max") l += argmax_attrs(op);
-  if (op.type == "transpose" || op.type == "reshape") {
-    const std::vector<int>& v = op.type == "transpose" ? op.perm : op.shape;
-    l += op.type == "transpose" ? " perm=" : " shape=";
-    for (size_t i = 0; i < v.size(); ++i) l += (i ? "," : "") + std::to_string(v[i]);
-  }
+  if (op.type == "transpose") l += " perm=" + Join(op.perm);
+  if (op.type == "reshape") l += " shape=" + Join(op.shape);
   if (op.type == "prior_box") {
     l += list_of("min_sizes", op.min_sizes) + list_of("max_sizes", op.max_sizes) + list_of("aspect_ratios", op.aspect_ratios) +
          list_of("variances", op.variances) + " flip=" + std::to_string(op.flip ? 1 : 0) + " clip=" + std::to_string(op.clip ? 1 : 0);
@@ -1313,6 +1306,31 @@ ConvAttrs GraphBuilder::LoweredConvAttrs(const Step& s) const {
 void GraphBuilder::LowerOp(const Step& s, HipPredictor* pred) {
   GraphOp& op = ops_[s.op];
   const float* bias = op.has_bias ? op.bias.data() : nullptr;
+  switch (s.form) {  // the step that became ONE other instruction
+    case Form::kShuffleInt8: pred->AddShuffleUnit(s.op_inputs[0], s.op_inputs[1], "", s.out, s.calib_out, s.calib_scale, s.drop_f32); return;
+    case Form::kShuffleUnit: pred->AddShuffleUnit(s.op_inputs[0], s.op_inputs[1], s.out, s.hi, s.calib_out, s.calib_scale, s.drop_f32); return;
+    case Form::kConcatInt8: pred->AddConcatCalib(s.op_inputs, s.out, op.axis, s.calib_out, s.calib_scale, s.drop_f32); return;
+    case Form::kConcatNhwc: pred->AddConcatNhwc(s.op_inputs, s.out, s.nhwc_k); return;
+    case Form::kArgmaxInterp: {
+      const GraphOp& am = ops_[s.argmax_op];
+      pred->AddInterpArgMax(op.type, s.op_inputs[0], s.out, op.out_h, op.out_w, op.interp_scale, op.align_corners, op.align_mode, am.dtype,
+                            am.keepdims);
+      return;
+    }
+    case Form::kYoloHead: {
+      std::vector<std::string> xs{s.op_inputs[0]};
+      xs.insert(xs.end(), s.op_inputs.begin() + 2, s.op_inputs.end());
+      std::vector<std::vector<int>> anchors;
+      std::vector<int> ratios;
+      for (int y : s.yolo_ops) {
+        anchors.push_back(ops_[y].anchors);
+        ratios.push_back(ops_[y].downsample_ratio);
+      }
+      pred->AddYoloHead(xs, s.op_inputs[1], s.outs[0], s.outs[1], anchors, op.class_num, op.conf_thresh, ratios, op.clip_bbox, op.scale_x_y);
+      return;
+    }
+    case Form::kPlain: break;
+  }
   if (op.type == "conv2d" || op.type == "depthwise_conv2d") {
     CHECK(op.enable_int8) << "kHIP has int8 conv kernels only";
     pred->AddConv(op.type, s.op_inputs[0], s.out, op.w.data(), op.w_dims, bias, LoweredConvAttrs(s));
@@ -1336,22 +1354,11 @@ void GraphBuilder::LowerOp(const Step& s, HipPredictor* pred) {
     pred->AddSoftmax(s.op_inputs[0], s.out);
   } else if (op.type == "hard_swish" || op.type == "hard_sigmoid") {
     pred->AddActivation(op.type, s.op_inputs[0], s.out, s.calib_out, s.calib_scale, s.drop_f32);
-  } else if (s.argmax_op >= 0) {
-    const GraphOp& am = ops_[s.argmax_op];
-    pred->AddInterpArgMax(op.type, s.op_inputs[0], s.out, op.out_h, op.out_w, op.interp_scale, op.align_corners, op.align_mode, am.dtype,
-                          am.keepdims);
   } else if (IsInterp(op)) {
     pred->AddInterp(op.type, s.op_inputs[0], s.out, op.out_h, op.out_w, op.interp_scale, op.align_corners, op.align_mode, s.calib_out,
                     s.calib_scale, s.drop_f32);
   } else if (op.type == "arg_max") {
     pred->AddArgMax(s.op_inputs[0], s.out, op.axis, op.dtype, op.keepdims);
-  } else if (s.shuffle_tail) {
-    pred->AddShuffleUnit(s.op_inputs[0], s.op_inputs[1], s.shuffle_tail == 2 ? s.out : "", s.shuffle_tail == 2 ? s.hi : s.out, s.calib_out,
-                         s.calib_scale, s.drop_f32);
-  } else if (s.concat_int8) {
-    pred->AddConcatCalib(s.op_inputs, s.out, op.axis, s.calib_out, s.calib_scale, s.drop_f32);
-  } else if (s.nhwc_k) {
-    pred->AddConcatNhwc(s.op_inputs, s.out, s.nhwc_k);
   } else if (op.type == "transpose") {
     pred->AddTranspose(s.op_inputs[0], s.out, op.perm);
   } else if (op.type == "reshape") {
@@ -1363,16 +1370,6 @@ void GraphBuilder::LowerOp(const Step& s, HipPredictor* pred) {
     const bool pv = s.op_inputs.size() == 3;
     pred->AddBoxCoder(s.op_inputs[0], pv ? s.op_inputs[1] : "", s.op_inputs.back(), s.out, pv ? std::vector<float>() : op.variances, op.axis,
                       op.box_normalized);
-  } else if (op.type == "yolo_box" && !s.yolo_ops.empty()) {
-    std::vector<std::string> xs{s.op_inputs[0]};
-    xs.insert(xs.end(), s.op_inputs.begin() + 2, s.op_inputs.end());
-    std::vector<std::vector<int>> anchors;
-    std::vector<int> ratios;
-    for (int y : s.yolo_ops) {
-      anchors.push_back(ops_[y].anchors);
-      ratios.push_back(ops_[y].downsample_ratio);
-    }
-    pred->AddYoloHead(xs, s.op_inputs[1], s.outs[0], s.outs[1], anchors, op.class_num, op.conf_thresh, ratios, op.clip_bbox, op.scale_x_y);
   } else if (op.type == "yolo_box") {
     CHECK(s.outs.size() == 2) << "yolo_box " << s.out << ": outputs {Boxes, Scores}";
     pred->AddYoloBox(s.op_inputs[0], s.op_inputs[1], s.outs[0], s.outs[1], op.anchors, op.class_num, op.conf_thresh, op.downsample_ratio,

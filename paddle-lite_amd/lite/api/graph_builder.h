@@ -207,6 +207,21 @@ class GraphBuilder {
 
  private:
   enum class StepKind { kOp, kIoCopyH2D, kIoCopyD2H, kCalibF2I, kCalibI2F, kImageToTensor, kImageConvert, kImageResize, kSeGate };
+  // Which instruction a kOp step lowers to: its op's own (kPlain, with the modifiers further down), or the ONE fused instruction a
+  // rewrite of FuseSteps made of it.  `via` then holds the names that are no longer written.
+  enum class Form {
+    kPlain,
+    kShuffleInt8,   // (K2) a concat step that took shuffle_channel(2) and the calib behind it over: shuffle_channel/int8, `out` the
+                    // shuffled tensor; calib_out / calib_scale / drop_f32 belong to the tensor the calib read
+    kShuffleUnit,   // (K1) ... and the split behind the shuffle: shuffle_channel/unit, `out` the split's first half, `hi` its second
+    kConcatInt8,    // (L) a concat step that took the calib behind it over: concat/int8, calib_out / calib_scale / drop_f32
+    kConcatNhwc,    // (O1) a concat step that took the transpose -> reshape chains of its operands over: concat/nhwc, op_inputs the
+                    // NCHW tensors, nhwc_k the chains' k
+    kArgmaxInterp,  // (M) an interp step that took the arg_max(axis 1) behind it over: arg_max/interp, argmax_op that op's index in
+                    // ops_, `out` the labels
+    kYoloHead,      // (P) a yolo_box step that became the yolo_box/head instruction: yolo_ops the ops_ indices of the k yolo_box ops in
+                    // the concats' order; op_inputs {X_0, ImgSize, X_1 ..}, outs {boxes [N, P, 4], scores [N, C, P]}
+  };
   struct Step {
     int op{-1};              // index into ops_, or -1 for an inserted instruction
     StepKind kind{StepKind::kOp};
@@ -216,21 +231,14 @@ class GraphBuilder {
     float out_scale{1.f};
     std::vector<std::string> op_inputs;  // op inputs after cast renaming
     std::vector<std::string> outs;       // split: every output (outs[0] == out)
-    int shuffle_tail{0};      // (K) a concat step that took shuffle_channel(2) and its tail over: 1 = K2 (shuffle_channel/int8: `out` the
-                              // shuffled tensor), 2 = K1 (shuffle_channel/unit: `out` the split's first half, `hi` its second);
-                              // calib_out / calib_scale / drop_f32 belong to the tensor the calib read, `via` the names no longer written
-    std::string hi;
-    int argmax_op{-1};        // (M) an interp step that took the arg_max(axis 1) behind it over: arg_max/interp, that op's index in
-                              // ops_; `out` the labels, `via` the resampled tensor that is no longer written.  (N) an interp step that
-                              // took the calib behind it over carries calib_out / calib_scale / drop_f32
-    int nhwc_k{0};            // (O1) a concat step that took the transpose -> reshape chains of its operands over: concat/nhwc, op_inputs
-                              // the NCHW tensors, `via` the names no longer written
-    std::vector<int> yolo_ops;  // (P) a yolo_box step that became the yolo_box/head instruction: the ops_ indices of the k yolo_box ops
-                              // in the concats' order; op_inputs {X_0, ImgSize, X_1 ..}, outs {boxes [N, P, 4], scores [N, C, P]}, `via`
-                              // the names no longer written
+    Form form{Form::kPlain};
+    std::string hi;             // kShuffleUnit
+    int argmax_op{-1};          // kArgmaxInterp
+    int nhwc_k{0};              // kConcatNhwc
+    std::vector<int> yolo_ops;  // kYoloHead
     bool scores_npc{false};   // (O2) a multiclass_nms step whose Scores operand is the [N, P, C] input of the transpose taken over (`via`)
-    bool concat_int8{false};  // (L) a concat step that took the calib behind it over: concat/int8, calib_out / calib_scale / drop_f32
-    // kHIP fusions (FuseSteps): tail taken over by an fp32_out conv, int8 max pool behind a fused calib
+    // kHIP fusions (FuseSteps): tail taken over by an fp32_out conv or (J1 / J3 / N) by a hard_swish, an elementwise_mul or an interp,
+    // int8 max pool behind a fused calib
     std::string res;          // residual operand of the fused elementwise_add ("" = none)
     bool res_relu{false};
     std::string calib_out;    // int8 tensor of the fused calib ("" = none)

@@ -2,7 +2,6 @@
 #include "lite/api/hip_predictor.h"
 
 #include "lite/kernels/hip/calib_tail.h"
-#include "lite/kernels/hip/concat_fusion.h"
 #include "lite/kernels/hip/detection_fusion.h"
 #include "lite/kernels/hip/interp_fusion.h"
 #include "lite/kernels/hip/prior_box_host.h"
@@ -26,6 +25,42 @@ std::unique_ptr<KernelBase> PickKernel(const std::string& op_type, const Place& 
   LOG(FATAL) << "no kernel registered for " << op_type << "/" << alias << " at " << place.DebugString()
              << "; registered ops:\n" << KernelFactory::Global().DebugString();
   return nullptr;
+}
+
+// The picked kernel, and in *as the interface I of lite/kernels/hip/*_fusion.h through which this target's fusion state reaches it
+template <class I>
+static std::unique_ptr<KernelBase> PickAs(const std::string& op_type, const Place& place, const std::string& alias, I** as) {
+  auto kernel = PickKernel(op_type, place, alias);
+  *as = dynamic_cast<I*>(kernel.get());
+  CHECK(*as) << "the picked " << op_type << "/" << alias << " kernel does not take the kHIP fusion state it is handed";
+  return kernel;
+}
+
+// The calib[fp32_to_int8](scale) an fp32 op took over: it writes the int8 variable `name`; drop: the op's fp32 output is not written
+static kernels::hip::HipCalibTail MakeCalibTail(HipPredictor* pred, const std::string& name, float scale, bool drop) {
+  kernels::hip::HipCalibTail t;
+  t.calib_output = pred->Var(name);
+  t.calib_output->set_precision(PRECISION(kInt8));
+  t.calib_scale = scale;
+  t.drop_fp32_output = drop;
+  return t;
+}
+
+// ConvAttrs' act / act_coef as an ActivationParam.  ConvParam::fuse_relu has no counterpart here: the conv ops set it themselves.
+static void FillActivation(operators::ActivationParam* ap, int act, float coef) {
+  if (act == 0) return;
+  ap->has_active = true;
+  ap->active_type = static_cast<lite_api::ActivationType>(act);
+  if (act == 2) ap->Relu_clipped_coef = coef;
+  if (act == 4) ap->Leaky_relu_alpha = coef;
+}
+
+void HipPredictor::UploadWeights(const int8_t* w, const std::vector<int64_t>& w_dims, const float* bias, int64_t cout, Tensor** filter,
+                                 Tensor** bias_out) {
+  size_t wn = 1;
+  for (auto d : w_dims) wn *= static_cast<size_t>(d);
+  *filter = NewParam(w, wn, w_dims, PRECISION(kInt8));
+  *bias_out = bias ? NewParam(bias, static_cast<size_t>(cout) * 4, {cout}, PRECISION(kFloat)) : nullptr;
 }
 
 Tensor* HipPredictor::Var(const std::string& name) {
@@ -135,12 +170,9 @@ void HipPredictor::AddConv(const std::string& op_type, const std::string& in, co
   auto& p = op->mutable_param();
   kernels::hip::HipConvFusion fz;  // this target's graph-level fusion state (lite/kernels/hip/conv_fusion.h)
   const bool fused = !a.calib_out.empty() || !a.residual.empty() || a.pw_w != nullptr || a.in_calib_scale > 0.f;
-  size_t wn = 1;
-  for (auto d : w_dims) wn *= static_cast<size_t>(d);
   p.x = a.image_format >= 0 ? Var(a.image_x) : Var(in);
   p.output = Var(out);
-  p.filter = NewParam(w, wn, w_dims, PRECISION(kInt8));
-  p.bias = bias ? NewParam(bias, static_cast<size_t>(w_dims[0]) * 4, {w_dims[0]}, PRECISION(kFloat)) : nullptr;
+  UploadWeights(w, w_dims, bias, w_dims[0], &p.filter, &p.bias);
   p.strides = a.strides;
   p.paddings = std::make_shared<std::vector<int>>(a.paddings);
   p.dilations = std::make_shared<std::vector<int>>(a.dilations);
@@ -149,13 +181,8 @@ void HipPredictor::AddConv(const std::string& op_type, const std::string& in, co
   p.input_scale = a.input_scale;
   p.output_scale = a.output_scale;
   p.weight_scale = a.weight_scale;
-  if (a.act != 0) {
-    p.activation_param.has_active = true;
-    p.activation_param.active_type = static_cast<lite_api::ActivationType>(a.act);
-    if (a.act == 1) p.fuse_relu = true;
-    if (a.act == 2) p.activation_param.Relu_clipped_coef = a.act_coef;
-    if (a.act == 4) p.activation_param.Leaky_relu_alpha = a.act_coef;
-  }
+  FillActivation(&p.activation_param, a.act, a.act_coef);
+  if (a.act == 1) p.fuse_relu = true;
   if (!a.residual.empty()) {
     CHECK(!a.int8_out || (a.pw_tail && !a.pw_int8_out)) << "the fused residual add belongs to the fp32_out kernel";
     p.fuse_residual_connection = true;
@@ -164,27 +191,19 @@ void HipPredictor::AddConv(const std::string& op_type, const std::string& in, co
   }
   if (!a.calib_out.empty()) {
     CHECK(!a.int8_out || (a.pw_tail && !a.pw_int8_out)) << "the fused calib belongs to the fp32_out kernel";
-    fz.calib_output = Var(a.calib_out);
-    fz.calib_output->set_precision(PRECISION(kInt8));
-    fz.calib_scale = a.calib_scale;
-    fz.drop_fp32_output = a.drop_fp32;
+    const kernels::hip::HipCalibTail t = MakeCalibTail(this, a.calib_out, a.calib_scale, a.drop_fp32);
+    fz.calib_output = t.calib_output;  // HipConvFusion keeps the three fields flat (calib_tail.h says why)
+    fz.calib_scale = t.calib_scale;
+    fz.drop_fp32_output = t.drop_fp32_output;
   }
   if (a.pw_w) {
     CHECK(a.int8_out && op_type == "depthwise_conv2d") << "only a depthwise conv with int8 output takes a 1x1 consumer over";
-    size_t pn = 1;
-    for (auto d : a.pw_w_dims) pn *= static_cast<size_t>(d);
-    fz.pw_filter = NewParam(a.pw_w, pn, a.pw_w_dims, PRECISION(kInt8));
+    UploadWeights(a.pw_w, a.pw_w_dims, a.pw_bias, a.pw_w_dims[0], &fz.pw_filter, &fz.pw_bias);
     op->set_output_channels(a.pw_w_dims[0]);
-    fz.pw_bias = a.pw_bias ? NewParam(a.pw_bias, static_cast<size_t>(a.pw_w_dims[0]) * 4, {a.pw_w_dims[0]}, PRECISION(kFloat)) : nullptr;
     fz.pw_weight_scale = a.pw_weight_scale;
     fz.pw_output_scale = a.pw_output_scale;
     fz.pw_int8_out = a.pw_int8_out;
-    if (a.pw_act != 0) {
-      fz.pw_activation_param.has_active = true;
-      fz.pw_activation_param.active_type = static_cast<lite_api::ActivationType>(a.pw_act);
-      if (a.pw_act == 2) fz.pw_activation_param.Relu_clipped_coef = a.pw_act_coef;
-      if (a.pw_act == 4) fz.pw_activation_param.Leaky_relu_alpha = a.pw_act_coef;
-    }
+    FillActivation(&fz.pw_activation_param, a.pw_act, a.pw_act_coef);
     p.output->set_precision(a.pw_int8_out ? PRECISION(kInt8) : PRECISION(kFloat));
     fz.pw_tail = a.pw_tail;
     if (a.pw_pool) {
@@ -206,12 +225,11 @@ void HipPredictor::AddConv(const std::string& op_type, const std::string& in, co
     op->set_image_input(img, operators::ImageChannels(a.image_format));
   }
   op->set_padding_algorithm(a.padding_algorithm);
-  auto kernel = PickKernel(op_type, Place(TARGET(kHIP), PRECISION(kInt8)), a.int8_out ? "int8_out" : "fp32_out");
-  if (fused) {  // this target's fusion state goes to the kernel object, not into the reference's ConvParam (conv_fusion.h)
-    auto* fk = dynamic_cast<kernels::hip::HipFusableKernel*>(kernel.get());
-    CHECK(fk) << "the picked conv kernel does not take a kHIP fusion";
-    fk->SetFusion(fz);
-  }
+  // this target's fusion state goes to the kernel object, not into the reference's ConvParam (conv_fusion.h); every kHIP conv
+  // kernel takes one, and one that never receives it is the plain drop-in conv
+  kernels::hip::HipFusableKernel* fk;
+  auto kernel = PickAs(op_type, Place(TARGET(kHIP), PRECISION(kInt8)), a.int8_out ? "int8_out" : "fp32_out", &fk);
+  if (fused) fk->SetFusion(fz);
   Emit(op, std::move(kernel));
 }
 
@@ -222,13 +240,9 @@ void HipPredictor::AddConvTranspose(const std::string& in, const std::string& ou
   CHECK_EQ(w_dims.size(), 4UL);
   auto op = std::make_shared<operators::ConvTransposeOpLite>();
   auto& p = op->mutable_param();
-  size_t wn = 1;
-  for (auto d : w_dims) wn *= static_cast<size_t>(d);
-  const int64_t cout = w_dims[1] * a.groups;
   p.x = Var(in);
   p.output = Var(out);
-  p.filter = NewParam(w, wn, w_dims, PRECISION(kInt8));
-  p.bias = bias ? NewParam(bias, static_cast<size_t>(cout) * 4, {cout}, PRECISION(kFloat)) : nullptr;
+  UploadWeights(w, w_dims, bias, w_dims[1] * a.groups, &p.filter, &p.bias);
   p.strides = a.strides;
   p.paddings = std::make_shared<std::vector<int>>(a.paddings);
   p.dilations = std::make_shared<std::vector<int>>(a.dilations);
@@ -238,13 +252,8 @@ void HipPredictor::AddConvTranspose(const std::string& in, const std::string& ou
   p.input_scale = a.input_scale;
   p.output_scale = a.output_scale;
   p.weight_scale = a.weight_scale;
-  if (a.act != 0) {
-    p.activation_param.has_active = true;
-    p.activation_param.active_type = static_cast<lite_api::ActivationType>(a.act);
-    if (a.act == 1) p.fuse_relu = true;
-    if (a.act == 2) p.activation_param.Relu_clipped_coef = a.act_coef;
-    if (a.act == 4) p.activation_param.Leaky_relu_alpha = a.act_coef;
-  }
+  FillActivation(&p.activation_param, a.act, a.act_coef);
+  if (a.act == 1) p.fuse_relu = true;
   op->set_padding_algorithm(a.padding_algorithm);
   Emit(op, PickKernel("conv2d_transpose", Place(TARGET(kHIP), PRECISION(kInt8)), a.int8_out ? "int8_out" : "fp32_out"));
 }
@@ -323,19 +332,13 @@ void HipPredictor::AddSoftmax(const std::string& in, const std::string& out) {
   Emit(op, PickKernel("softmax", Place(TARGET(kHIP), PRECISION(kFloat)), "def"));
 }
 
-// the "int8" alias of an fp32 op with its calib tail attached, or the plain "def" kernel
-static std::unique_ptr<KernelBase> PickWithCalibTail(const std::string& op_type, Tensor* calib_out, float calib_scale, bool drop_fp32) {
-  auto kernel = PickKernel(op_type, Place(TARGET(kHIP), PRECISION(kFloat)), calib_out ? "int8" : "def");
-  if (calib_out) {
-    auto* tk = dynamic_cast<kernels::hip::HipCalibTailKernel*>(kernel.get());
-    CHECK(tk) << "the picked " << op_type << " kernel does not take a calib tail";
-    kernels::hip::HipCalibTail t;
-    t.calib_output = calib_out;
-    t.calib_output->set_precision(PRECISION(kInt8));
-    t.calib_scale = calib_scale;
-    t.drop_fp32_output = drop_fp32;
-    tk->SetCalibTail(t);
-  }
+// the "int8" alias of an fp32 op (registered at tail_precision) with its calib tail attached, or, calib_out == "", the plain "def" kernel
+static std::unique_ptr<KernelBase> PickWithCalibTail(HipPredictor* pred, const std::string& op_type, PrecisionType tail_precision,
+                                                     const std::string& calib_out, float calib_scale, bool drop_fp32) {
+  if (calib_out.empty()) return PickKernel(op_type, Place(TARGET(kHIP), PRECISION(kFloat)), "def");
+  kernels::hip::HipCalibTailKernel* tk;
+  auto kernel = PickAs(op_type, Place(TARGET(kHIP), tail_precision), "int8", &tk);
+  tk->SetCalibTail(MakeCalibTail(pred, calib_out, calib_scale, drop_fp32));
   return kernel;
 }
 
@@ -348,7 +351,7 @@ void HipPredictor::AddActivation(const std::string& op_type, const std::string& 
   p.Out = Var(out);
   p.has_active = true;
   p.active_type = op_type == "hard_swish" ? lite_api::ActivationType::kHardSwish : lite_api::ActivationType::kHardSigmoid;
-  Emit(op, PickWithCalibTail(op_type, calib_out.empty() ? nullptr : Var(calib_out), calib_scale, drop_fp32));
+  Emit(op, PickWithCalibTail(this, op_type, PRECISION(kFloat), calib_out, calib_scale, drop_fp32));
 }
 
 void HipPredictor::AddSeGate(const std::string& in, const std::string& out, float calib_scale, const int8_t* w1,
@@ -363,24 +366,15 @@ void HipPredictor::AddSeGate(const std::string& in, const std::string& out, floa
   kernels::hip::HipSeGateFusion fz;
   fz.calib_scale = calib_scale;
   auto fill = [this](kernels::hip::HipSeGateConv* c, const int8_t* w, const std::vector<int64_t>& wd, const float* bias, const ConvAttrs& a) {
-    size_t wn = 1;
-    for (auto d : wd) wn *= static_cast<size_t>(d);
-    c->filter = NewParam(w, wn, wd, PRECISION(kInt8));
-    c->bias = bias ? NewParam(bias, static_cast<size_t>(wd[0]) * 4, {wd[0]}, PRECISION(kFloat)) : nullptr;
+    UploadWeights(w, wd, bias, wd[0], &c->filter, &c->bias);
     c->weight_scale = a.weight_scale;
     c->input_scale = a.input_scale;
-    if (a.act != 0) {
-      c->activation_param.has_active = true;
-      c->activation_param.active_type = static_cast<lite_api::ActivationType>(a.act);
-      if (a.act == 2) c->activation_param.Relu_clipped_coef = a.act_coef;
-      if (a.act == 4) c->activation_param.Leaky_relu_alpha = a.act_coef;
-    }
+    FillActivation(&c->activation_param, a.act, a.act_coef);
   };
   fill(&fz.reduce, w1, w1_dims, bias1, a1);
   fill(&fz.expand, w2, w2_dims, bias2, a2);
-  auto kernel = PickKernel("hard_sigmoid", Place(TARGET(kHIP), PRECISION(kFloat)), "se_gate");
-  auto* gk = dynamic_cast<kernels::hip::HipSeGateKernel*>(kernel.get());
-  CHECK(gk) << "the picked hard_sigmoid kernel does not take the se_gate fusion";
+  kernels::hip::HipSeGateKernel* gk;
+  auto kernel = PickAs("hard_sigmoid", Place(TARGET(kHIP), PRECISION(kFloat)), "se_gate", &gk);
   gk->SetSeGate(fz);
   Emit(op, std::move(kernel));
 }
@@ -393,7 +387,7 @@ void HipPredictor::AddElementwiseMul(const std::string& x, const std::string& y,
   p.Y = Var(y);
   p.Out = Var(out);
   p.axis = axis;
-  Emit(op, PickWithCalibTail("elementwise_mul", calib_out.empty() ? nullptr : Var(calib_out), calib_scale, drop_fp32));
+  Emit(op, PickWithCalibTail(this, "elementwise_mul", PRECISION(kFloat), calib_out, calib_scale, drop_fp32));
 }
 
 void HipPredictor::AddConcat(const std::vector<std::string>& inputs, const std::string& out, int axis) {
@@ -440,15 +434,9 @@ void HipPredictor::AddShuffleUnit(const std::string& a, const std::string& b, co
   kernels::hip::HipShuffleFusion fz;
   fz.second = Var(b);
   if (unit) fz.hi_output = Var(hi);
-  if (!calib_out.empty()) {
-    fz.calib_output = Var(calib_out);
-    fz.calib_output->set_precision(PRECISION(kInt8));
-    fz.calib_scale = calib_scale;
-    fz.drop_fp32_output = drop_fp32;
-  }
-  auto kernel = PickKernel("shuffle_channel", Place(TARGET(kHIP), PRECISION(kFloat)), unit ? "unit" : "int8");
-  auto* sk = dynamic_cast<kernels::hip::HipShuffleFusionKernel*>(kernel.get());
-  CHECK(sk) << "the picked shuffle_channel kernel does not take the shuffle fusion";
+  if (!calib_out.empty()) fz.tail = MakeCalibTail(this, calib_out, calib_scale, drop_fp32);
+  kernels::hip::HipShuffleFusionKernel* sk;
+  auto kernel = PickAs("shuffle_channel", Place(TARGET(kHIP), PRECISION(kFloat)), unit ? "unit" : "int8", &sk);
   sk->SetShuffleFusion(fz);
   Emit(op, std::move(kernel));
 }
@@ -461,16 +449,7 @@ void HipPredictor::AddConcatCalib(const std::vector<std::string>& inputs, const 
   for (auto& in : inputs) p.x.push_back(Var(in));
   p.output = Var(out);
   p.axis = axis;
-  kernels::hip::HipConcatFusion fz;
-  fz.calib_output = Var(calib_out);
-  fz.calib_output->set_precision(PRECISION(kInt8));
-  fz.calib_scale = calib_scale;
-  fz.drop_fp32_output = drop_fp32;
-  auto kernel = PickKernel("concat", Place(TARGET(kHIP), PRECISION(kAny)), "int8");
-  auto* ck = dynamic_cast<kernels::hip::HipConcatFusionKernel*>(kernel.get());
-  CHECK(ck) << "the picked concat kernel does not take the concat fusion";
-  ck->SetConcatFusion(fz);
-  Emit(op, std::move(kernel));
+  Emit(op, PickWithCalibTail(this, "concat", PRECISION(kAny), calib_out, calib_scale, drop_fp32));
 }
 
 static void SetInterpAttrs(operators::InterpolateParam* p, const std::string& op_type, int out_h, int out_w, float scale,
@@ -492,20 +471,7 @@ void HipPredictor::AddInterp(const std::string& op_type, const std::string& in, 
   SetInterpAttrs(&p, op_type, out_h, out_w, scale, align_corners, align_mode);
   p.X = Var(in);
   p.Out = Var(out);
-  if (calib_out.empty()) {
-    Emit(op, PickKernel(op_type, Place(TARGET(kHIP), PRECISION(kFloat)), "def"));
-    return;
-  }
-  kernels::hip::HipInterpFusion fz;
-  fz.calib_output = Var(calib_out);
-  fz.calib_output->set_precision(PRECISION(kInt8));
-  fz.calib_scale = calib_scale;
-  fz.drop_fp32_output = drop_fp32;
-  auto kernel = PickKernel(op_type, Place(TARGET(kHIP), PRECISION(kAny)), "int8");
-  auto* ik = dynamic_cast<kernels::hip::HipInterpFusionKernel*>(kernel.get());
-  CHECK(ik) << "the picked " << op_type << " kernel does not take the interp fusion";
-  ik->SetInterpFusion(fz);
-  Emit(op, std::move(kernel));
+  Emit(op, PickWithCalibTail(this, op_type, PRECISION(kAny), calib_out, calib_scale, drop_fp32));
 }
 
 void HipPredictor::AddArgMax(const std::string& in, const std::string& out, int axis, int dtype, bool keepdims) {
@@ -532,9 +498,8 @@ void HipPredictor::AddInterpArgMax(const std::string& op_type, const std::string
   p.dtype = dtype;
   p.keepdims = keepdims;
   op->set_interp(fz.interp);
-  auto kernel = PickKernel("arg_max", Place(TARGET(kHIP), PRECISION(kAny)), "interp");
-  auto* ak = dynamic_cast<kernels::hip::HipInterpArgmaxKernel*>(kernel.get());
-  CHECK(ak) << "the picked arg_max kernel does not take the interp fusion";
+  kernels::hip::HipInterpArgmaxKernel* ak;
+  auto kernel = PickAs("arg_max", Place(TARGET(kHIP), PRECISION(kAny)), "interp", &ak);
   ak->SetInterpArgmax(fz);
   Emit(op, std::move(kernel));
 }
@@ -619,9 +584,8 @@ void HipPredictor::AddMulticlassNms(const std::string& boxes, const std::string&
   fz.scores_npc = scores_npc;
   op->set_count(fz.count);
   op->set_scores_npc(scores_npc);
-  auto kernel = PickKernel("multiclass_nms", Place(TARGET(kHIP), PRECISION(kFloat)), "def");
-  auto* nk = dynamic_cast<kernels::hip::HipNmsFusionKernel*>(kernel.get());
-  CHECK(nk) << "the picked multiclass_nms kernel does not take the count tensor";
+  kernels::hip::HipNmsFusionKernel* nk;
+  auto kernel = PickAs("multiclass_nms", Place(TARGET(kHIP), PRECISION(kFloat)), "def", &nk);
   nk->SetNmsFusion(fz);
   Emit(op, std::move(kernel));
 }
@@ -666,9 +630,8 @@ void HipPredictor::AddYoloHead(const std::vector<std::string>& xs, const std::st
     op->add_scale(Var(xs[i]), anchors[i]);
     hz.more.push_back({Var(xs[i]), anchors[i], downsample_ratios[i]});
   }
-  auto kernel = PickKernel("yolo_box", Place(TARGET(kHIP), PRECISION(kFloat)), "head");
-  auto* hk = dynamic_cast<kernels::hip::HipYoloHeadKernel*>(kernel.get());
-  CHECK(hk) << "the picked yolo_box/head kernel does not take the further feature maps";
+  kernels::hip::HipYoloHeadKernel* hk;
+  auto kernel = PickAs("yolo_box", Place(TARGET(kHIP), PRECISION(kFloat)), "head", &hk);
   hk->SetYoloHead(hz);
   Emit(op, std::move(kernel));
 }

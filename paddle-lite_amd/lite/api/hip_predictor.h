@@ -105,7 +105,7 @@ class HipPredictor {
   // concat / split / shuffle_channel, fp32 ops with the reference's attributes (lite/operators/op_params.h:369-386, 590-608,
   // 258-263).  AddSplit: num > 0 = equal parts, else `sections`, one per output.
   void AddConcat(const std::vector<std::string>& inputs, const std::string& out, int axis);
-  // fusion L (lite/kernels/hip/concat_fusion.h): concat -> calib[fp32_to_int8](calib_scale) in ONE launch, concat/int8.  `out` names
+  // fusion L (lite/kernels/hip/calib_tail.h): concat -> calib[fp32_to_int8](calib_scale) in ONE launch, concat/int8.  `out` names
   // the fp32 tensor, calib_out its int8 image; drop_fp32: `out` has no reader left and is not written (it carries the shape).
   void AddConcatCalib(const std::vector<std::string>& inputs, const std::string& out, int axis, const std::string& calib_out,
                       float calib_scale, bool drop_fp32);
@@ -119,7 +119,7 @@ class HipPredictor {
                       const std::string& calib_out, float calib_scale, bool drop_fp32);
   // bilinear_interp / nearest_interp and arg_max with the reference's attributes (lite/operators/op_params.h:154-168, 821-827); the
   // output size is out_h x out_w where both are > 0, else int(in * scale).  calib_out != "": fusion N (lite/kernels/hip/
-  // interp_fusion.h), the calib[fp32_to_int8](calib_scale) behind the interp runs in the same launch and writes that variable;
+  // calib_tail.h), the calib[fp32_to_int8](calib_scale) behind the interp runs in the same launch and writes that variable;
   // drop_fp32: `out` has no reader left and is not written (it carries the shape).
   void AddInterp(const std::string& op_type, const std::string& in, const std::string& out, int out_h, int out_w, float scale,
                  bool align_corners, int align_mode, const std::string& calib_out = "", float calib_scale = 1.f, bool drop_fp32 = false);
@@ -175,6 +175,8 @@ class HipPredictor {
  private:
   void Emit(std::shared_ptr<OpLite> op, std::unique_ptr<KernelBase> kernel);
   Tensor* NewParam(const void* host, size_t bytes, const std::vector<int64_t>& dims, PrecisionType prec);
+  // the int8 filter `w` and, bias != nullptr, the `cout` fp32 bias values of a conv as persistable host tensors
+  void UploadWeights(const int8_t* w, const std::vector<int64_t>& w_dims, const float* bias, int64_t cout, Tensor** filter, Tensor** bias_out);
   int device_;
   std::shared_ptr<HipExecState> state_;
   void* graph_exec_{nullptr};  // plhip launch graph of the program (RunGraph)

@@ -18,24 +18,6 @@ namespace lite {
 namespace kernels {
 namespace hip {
 
-// what both kernel classes do with a calib tail: the pointers of one launch
-struct TailOutputs {
-  float* f32{nullptr};
-  int8_t* i8{nullptr};
-  float scale{1.f};
-};
-static TailOutputs OutputsOf(const HipCalibTail& t, bool int8_alias, lite::Tensor* out) {
-  TailOutputs o;
-  if (int8_alias) {
-    CHECK(t.calib_output) << "the int8 alias needs the calib tail the graph builder attaches (calib_tail.h)";
-    t.calib_output->Resize(out->dims());
-    o.i8 = t.calib_output->mutable_data<int8_t>(TARGET(kHIP));
-    o.scale = t.calib_scale;
-  }
-  if (!int8_alias || !t.drop_fp32_output) o.f32 = out->mutable_data<float>(TARGET(kHIP));
-  return o;
-}
-
 template <plhip_hard_act_kind Kind>
 class HardActCompute : public KernelLite<TARGET(kHIP), PRECISION(kFloat)>, public HipCalibTailKernel {
  public:
@@ -52,8 +34,7 @@ class HardActCompute : public KernelLite<TARGET(kHIP), PRECISION(kFloat)>, publi
   }
   void SetProfileRuntimeKernelInfo(profile::OpCharacter* ch) override {
     std::string name = Kind == PLHIP_HARD_SWISH ? "hard_swish" : "hard_sigmoid";
-    if (alias() == "int8") name += tail_.drop_fp32_output ? "_int8" : "_fp32_int8";
-    ch->kernel_func_name = name + "_hip";
+    ch->kernel_func_name = name + TailSuffix(tail_, alias() == "int8") + "_hip";
   }
 
  private:
@@ -142,7 +123,7 @@ class ElementwiseMulCompute : public KernelLite<TARGET(kHIP), PRECISION(kFloat)>
                                            same ? 1 : static_cast<int>(x[2] * x[3]), o.f32, o.i8, o.scale));
   }
   void SetProfileRuntimeKernelInfo(profile::OpCharacter* ch) override {
-    ch->kernel_func_name = alias() != "int8" ? "se_scale_hip" : tail_.drop_fp32_output ? "se_scale_int8_hip" : "se_scale_fp32_int8_hip";
+    ch->kernel_func_name = std::string("se_scale") + TailSuffix(tail_, alias() == "int8") + "_hip";
   }
 
  private:

@@ -3,15 +3,16 @@
 //   nearest_interp   ... -> interpolate.cc:465-499
 //   arg_max          lite/kernels/arm/argmax_compute.cc -> lite/backends/arm/math/argmax.cc:29-61
 // Alias def: the reference's op.  bilinear_interp / nearest_interp alias int8: the product of the graph builder's fusion N, the
-// calib[fp32_to_int8] behind the interp written in the same launch (interp_fusion.h).  It reads fp32 and writes int8 (and fp32
+// calib[fp32_to_int8] behind the interp written in the same launch (calib_tail.h).  It reads fp32 and writes int8 (and fp32
 // where that still has a reader), so it is registered at kAny precision: the def alias stays the one kernel a pick at kFloat finds.
-// arg_max alias interp: the product of fusion M, interp -> arg_max(axis 1) in one launch; X is the low-resolution tensor.
+// arg_max alias interp: the product of fusion M, interp -> arg_max(axis 1) in one launch (interp_fusion.h); X is the low-resolution tensor.
 // The output size comes from the attributes (out_h / out_w, or scale > 0 as int(in * scale)); OutSize, SizeTensor and Scale
 // tensors and a layout other than NCHW are fatal in PrepareForRun.  Every class reads its dims in Run: a resized feed needs no
 // new lowering.
 #include <string>
 
 #include "lite/core/op_registry.h"
+#include "lite/kernels/hip/calib_tail.h"
 #include "lite/kernels/hip/interp_fusion.h"
 #include "lite/operators/op_params.h"
 #include "plhip.h"
@@ -72,30 +73,26 @@ class InterpCompute : public KernelLite<TARGET(kHIP), PRECISION(kFloat)> {
 };
 
 // interp that took the calib[fp32_to_int8] behind it over (fusion N): one launch of plhip_interp_f32 with the int8 output
-class InterpCalibCompute : public KernelLite<TARGET(kHIP), PRECISION(kAny)>, public HipInterpFusionKernel {
+class InterpCalibCompute : public KernelLite<TARGET(kHIP), PRECISION(kAny)>, public HipCalibTailKernel {
  public:
-  void SetInterpFusion(const HipInterpFusion& f) override { fusion_ = f; }
+  void SetCalibTail(const HipCalibTail& t) override { tail_ = t; }
   void PrepareForRun() override { CheckInterpAttrs(this->Param<operators::InterpolateParam>(), op_type() + "/int8"); }
   void Run() override {
     auto& param = this->Param<operators::InterpolateParam>();
     auto& ctx = this->ctx_->As<HIPContext>();
     const std::string who = op_type() + "/int8";
     CHECK(param.X && param.Out) << who << ": X / Out must be set";
-    CHECK(fusion_.calib_output) << who << " needs the fusion state the graph builder attaches (interp_fusion.h)";
+    CHECK(tail_.calib_output) << who << " needs the calib tail the graph builder attaches (calib_tail.h)";
     CHECK(param.X->target() == TARGET(kHIP)) << who << ": X must live on the HIP device";
     const InterpCall k = MakeInterpCall(op_type(), param, param.X->dims(), who);
-    fusion_.calib_output->Resize(param.Out->dims());
-    int8_t* q = fusion_.calib_output->mutable_data<int8_t>(TARGET(kHIP));
-    float* y = fusion_.drop_fp32_output ? nullptr : param.Out->mutable_data<float>(TARGET(kHIP));
+    const TailOutputs o = OutputsOf(tail_, true, param.Out);
     HIP_CALL(ctx.ctx(), plhip_interp_f32(ctx.ctx(), param.X->data<float>(), static_cast<int64_t>(k.n) * k.c, k.in_h, k.in_w, k.out_h, k.out_w,
-                                         k.method, param.align_corners ? 1 : 0, param.align_mode, y, q, fusion_.calib_scale));
+                                         k.method, param.align_corners ? 1 : 0, param.align_mode, o.f32, o.i8, o.scale));
   }
-  void SetProfileRuntimeKernelInfo(profile::OpCharacter* ch) override {
-    ch->kernel_func_name = op_type() + (fusion_.drop_fp32_output ? "_int8_hip" : "_fp32_int8_hip");
-  }
+  void SetProfileRuntimeKernelInfo(profile::OpCharacter* ch) override { ch->kernel_func_name = op_type() + TailSuffix(tail_, true) + "_hip"; }
 
  private:
-  HipInterpFusion fusion_;
+  HipCalibTail tail_;
 };
 
 static void CheckArgmaxDtype(int dtype, const std::string& who) {

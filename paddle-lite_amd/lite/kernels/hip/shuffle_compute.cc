@@ -4,14 +4,14 @@
 //   shuffle_channel  lite/kernels/arm/shuffle_channel_compute.cc -> lite/backends/arm/math/shuffle_channel.cc:24-55
 // Alias def: the reference's op.  Aliases int8 / unit (shuffle_channel): the products of the graph builder's fusion K, the
 // tail of a ShuffleNetV2 unit in one launch (shuffle_fusion.h), bit-identical to the instructions they replace.
-// concat, alias int8: the product of fusion L, concat -> calib[fp32_to_int8] in one launch (concat_fusion.h).  It reads fp32 and
+// concat, alias int8: the product of fusion L, concat -> calib[fp32_to_int8] in one launch (calib_tail.h).  It reads fp32 and
 // writes int8 (and fp32 where that still has a reader), so it is registered at kAny precision: concat/def stays the one kernel a
 // pick at kFloat finds.
 // Every class reads its dims in Run: a resized feed needs no new lowering.
 #include <vector>
 
 #include "lite/core/op_registry.h"
-#include "lite/kernels/hip/concat_fusion.h"
+#include "lite/kernels/hip/calib_tail.h"
 #include "lite/kernels/hip/shuffle_fusion.h"
 #include "lite/operators/op_params.h"
 #include "plhip.h"
@@ -57,14 +57,14 @@ class ConcatCompute : public KernelLite<TARGET(kHIP), PRECISION(kFloat)> {
 };
 
 // concat that took the calib[fp32_to_int8] behind it over (fusion L): one launch of plhip_concat_calib_f32 per 8 operands
-class ConcatCalibCompute : public KernelLite<TARGET(kHIP), PRECISION(kAny)>, public HipConcatFusionKernel {
+class ConcatCalibCompute : public KernelLite<TARGET(kHIP), PRECISION(kAny)>, public HipCalibTailKernel {
  public:
-  void SetConcatFusion(const HipConcatFusion& f) override { fusion_ = f; }
+  void SetCalibTail(const HipCalibTail& t) override { tail_ = t; }
   void Run() override {
     auto& param = this->Param<operators::ConcatParam>();
     auto& ctx = this->ctx_->As<HIPContext>();
     CHECK(!param.x.empty() && param.output) << "concat/int8: inputs / output must be set";
-    CHECK(fusion_.calib_output) << "concat/int8 needs the fusion state the graph builder attaches (concat_fusion.h)";
+    CHECK(tail_.calib_output) << "concat/int8 needs the calib tail the graph builder attaches (calib_tail.h)";
     const AxisSplit s = SplitAtAxis(param.x[0]->dims(), param.axis, "concat/int8");
     std::vector<const float*> xs;
     std::vector<int64_t> extents;
@@ -73,18 +73,16 @@ class ConcatCalibCompute : public KernelLite<TARGET(kHIP), PRECISION(kAny)>, pub
       xs.push_back(t->data<float>());
       extents.push_back(t->dims()[s.axis]);
     }
-    fusion_.calib_output->Resize(param.output->dims());
-    int8_t* q = fusion_.calib_output->mutable_data<int8_t>(TARGET(kHIP));
-    float* y = fusion_.drop_fp32_output ? nullptr : param.output->mutable_data<float>(TARGET(kHIP));
-    HIP_CALL(ctx.ctx(), plhip_concat_calib_f32(ctx.ctx(), xs.data(), extents.data(), static_cast<int>(xs.size()), s.outer, s.inner, y, q,
-                                               fusion_.calib_scale));
+    const TailOutputs o = OutputsOf(tail_, true, param.output);
+    HIP_CALL(ctx.ctx(), plhip_concat_calib_f32(ctx.ctx(), xs.data(), extents.data(), static_cast<int>(xs.size()), s.outer, s.inner, o.f32,
+                                               o.i8, o.scale));
   }
   void SetProfileRuntimeKernelInfo(profile::OpCharacter* ch) override {
-    ch->kernel_func_name = fusion_.drop_fp32_output ? "concat_int8_hip" : "concat_fp32_int8_hip";
+    ch->kernel_func_name = std::string("concat") + TailSuffix(tail_, true) + "_hip";
   }
 
  private:
-  HipConcatFusion fusion_;
+  HipCalibTail tail_;
 };
 
 class SplitCompute : public KernelLite<TARGET(kHIP), PRECISION(kFloat)> {
@@ -147,26 +145,20 @@ class ShuffleTailCompute : public KernelLite<TARGET(kHIP), PRECISION(kFloat)>, p
     CHECK(param.X->dims() == fusion_.second->dims()) << "shuffle_channel/" << alias() << ": the two operands must have one shape";
     int n, h, hw;
     PlaneDims(param.X->dims(), "shuffle_channel", &n, &h, &hw);
-    float *lo = nullptr, *hi = nullptr;
-    int8_t* q = nullptr;
+    float* lo = nullptr;
     lite::Tensor* hi_t = unit ? fusion_.hi_output : param.Out;  // the fp32 tensor the calib read
     if (unit) {
       CHECK(hi_t) << "shuffle_channel/unit: the split's second output must be set";
       hi_t->Resize(param.X->dims());
       lo = param.Out->mutable_data<float>(TARGET(kHIP));
     }
-    if (fusion_.calib_output) {
-      fusion_.calib_output->Resize(hi_t->dims());
-      q = fusion_.calib_output->mutable_data<int8_t>(TARGET(kHIP));
-    }
-    if (!fusion_.calib_output || !fusion_.drop_fp32_output) hi = hi_t->mutable_data<float>(TARGET(kHIP));
+    const TailOutputs o = OutputsOf(fusion_.tail, fusion_.tail.calib_output != nullptr, hi_t);
     HIP_CALL(ctx.ctx(), plhip_shuffle_unit_f32(ctx.ctx(), param.X->data<float>(), fusion_.second->data<float>(), n, h, hw, unit ? h : 0, lo,
-                                               hi, q, fusion_.calib_scale));
+                                               o.f32, o.i8, o.scale));
   }
   void SetProfileRuntimeKernelInfo(profile::OpCharacter* ch) override {
-    std::string name = alias() == "unit" ? "shuffle_unit" : "shuffle_concat";
-    if (fusion_.calib_output) name += fusion_.drop_fp32_output ? "_int8" : "_fp32_int8";
-    ch->kernel_func_name = name + "_hip";
+    ch->kernel_func_name = std::string(alias() == "unit" ? "shuffle_unit" : "shuffle_concat") +
+                           TailSuffix(fusion_.tail, fusion_.tail.calib_output != nullptr) + "_hip";
   }
 
  private:

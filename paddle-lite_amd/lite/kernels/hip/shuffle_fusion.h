@@ -9,6 +9,7 @@
 // HipShuffleFusionKernel::SetShuffleFusion, after SetParam.
 #pragma once
 #include "lite/core/tensor.h"
+#include "lite/kernels/hip/calib_tail.h"
 
 namespace paddle {
 namespace lite {
@@ -17,10 +18,8 @@ namespace hip {
 
 struct HipShuffleFusion {
   const lite::Tensor* second{nullptr};  // the concat's second operand, X's shape
-  lite::Tensor* hi_output{nullptr};     // unit: the split's second output (fp32), written unless drop_fp32_output
-  lite::Tensor* calib_output{nullptr};  // the int8 tensor of the calib taken over: of Out (int8) or of hi_output (unit)
-  float calib_scale{1.f};
-  bool drop_fp32_output{false};         // the calib's fp32 input has no other reader: it only carries the shape
+  lite::Tensor* hi_output{nullptr};     // unit: the split's second output (fp32), written unless the tail drops it
+  HipCalibTail tail;                    // the calib taken over (calib_output == nullptr: none): of Out (int8) or of hi_output (unit)
 };
 
 class HipShuffleFusionKernel {

@@ -226,8 +226,9 @@ def test_interp_compute_compiles_against_the_reference_param_structs():
         subprocess.check_call([sys.executable, os.path.join(ROOT, "tools", "gen_ref_params_header.py"), "--out", tmp], stdout=subprocess.DEVNULL)
         gen = open(os.path.join(tmp, "lite", "operators", "op_params.h")).read()
         assert "struct InterpolateParam" in gen and "struct ArgmaxParam" in gen and "calib_output" not in gen
-        side = open(os.path.join(LITE, "lite", "kernels", "hip", "interp_fusion.h")).read()
-        assert "calib_output" in side and "calib_scale" in side and "drop_fp32_output" in side and "HipInterpArgmaxFusion" in side
+        side = open(os.path.join(LITE, "lite", "kernels", "hip", "calib_tail.h")).read()
+        assert "calib_output" in side and "calib_scale" in side and "drop_fp32_output" in side
+        assert "HipInterpArgmaxFusion" in open(os.path.join(LITE, "lite", "kernels", "hip", "interp_fusion.h")).read()
         p = subprocess.run(["g++", "-std=c++14", "-fsyntax-only", "-I", tmp, "-I", LITE, "-I", os.path.join(ROOT, "include"),
                             os.path.join(LITE, "lite", "kernels", "hip", "interp_compute.cc")], stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
         assert p.returncode == 0, "interp_compute.cc does not compile against the reference's structs:\n%s" % p.stdout.decode()[-3000:]

@@ -66,7 +66,7 @@ def test_concat_calib_compute_compiles_against_the_reference_param_struct():
         subprocess.check_call([sys.executable, os.path.join(ROOT, "tools", "gen_ref_params_header.py"), "--out", tmp], stdout=subprocess.DEVNULL)
         gen = open(os.path.join(tmp, "lite", "operators", "op_params.h")).read()
         assert "struct ConcatParam" in gen and "calib_output" not in gen and "drop_fp32_output" not in gen
-        side = open(os.path.join(LITE, "lite", "kernels", "hip", "concat_fusion.h")).read()
+        side = open(os.path.join(LITE, "lite", "kernels", "hip", "calib_tail.h")).read()
         assert "calib_output" in side and "calib_scale" in side and "drop_fp32_output" in side
         p = subprocess.run(["g++", "-std=c++14", "-fsyntax-only", "-I", tmp, "-I", LITE, "-I", os.path.join(ROOT, "include"),
                             os.path.join(LITE, "lite", "kernels", "hip", "shuffle_compute.cc")], stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
