@@ -360,6 +360,106 @@ def read_stamps(family, shape):
     return buf
 
 
+def _outer_inner(shape, axis):
+    """(axis made non-negative, the product of the extents in front of it, the product of those behind it)."""
+    axis = axis + len(shape) if axis < 0 else axis
+    return axis, int(np.prod(shape[:axis], dtype=np.int64)), int(np.prod(shape[axis + 1:], dtype=np.int64))
+
+
+SCOPE_SLACK = 64  # bytes every DeviceScope allocation has behind its tensor, beyond any guard
+
+
+class DeviceOut:
+    """An output tensor inside one DeviceScope allocation: .ptr for the library, .get() the tensor, .margins() the allocation's
+    bytes in front of and behind the tensor, concatenated."""
+
+    def __init__(self, ctx, base, total, lead, shape, dtype):
+        self.ctx, self.base, self.total, self.lead = ctx, base, total, lead
+        self.shape, self.dtype = tuple(shape), np.dtype(dtype)
+        self.nbytes = int(np.prod(self.shape, dtype=np.int64)) * self.dtype.itemsize
+        self.ptr = C.c_void_p(base.value + lead)
+
+    def get(self):
+        return self.ctx.to_host(self.ptr, self.shape, self.dtype)
+
+    def margins(self):
+        raw = self.ctx.to_host(self.base, (self.total,), np.uint8)
+        return np.concatenate([raw[:self.lead], raw[self.lead + self.nbytes:]])
+
+
+class _NoOut:
+    """The handle of an output the caller did not ask for: a null pointer and nothing to download."""
+    ptr = None
+
+    def get(self):
+        return None
+
+
+class DeviceScope:
+    """The owner of a whole-op helper's temporary device buffers (Context.scope()): a context manager that frees everything it
+    handed out when it exits, an exception passing through or not.  Every allocation is [guard][off][tensor][guard][SCOPE_SLACK]
+    with a 16-byte-aligned base, so `off` (bytes) is the tensor's misalignment."""
+
+    def __init__(self, ctx):
+        self.ctx, self._owned = ctx, []
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.release()
+
+    def release(self):
+        """Frees everything handed out so far; the scope can go on handing out buffers."""
+        owned, self._owned = self._owned, []
+        for p in owned:
+            self.ctx.free(p)
+
+    def _place(self, nbytes, off, fill, guard):
+        assert guard % 16 == 0 and off >= 0
+        total = guard + off + nbytes + guard + SCOPE_SLACK
+        base = self.ctx.malloc(total)
+        self._owned.append(base)
+        assert base.value % 16 == 0
+        if fill is not None:
+            self.ctx.check(self.ctx.L.plhip_memset(self.ctx.h, base, int(fill), total), "memset")
+        return base, total
+
+    def put(self, arr, dtype=None, off=0):
+        """Uploads a contiguous copy of arr (cast to dtype if given); the pointer lies `off` bytes past a 16-byte boundary."""
+        arr = np.ascontiguousarray(arr, dtype)
+        base, _total = self._place(arr.nbytes, off, None, 0)
+        p = C.c_void_p(base.value + off)
+        if arr.nbytes:
+            self.ctx.check(self.ctx.L.plhip_memcpy_h2d(self.ctx.h, p, arr.ctypes.data_as(C.c_void_p), arr.nbytes), "h2d")
+        return p
+
+    def put_opt(self, arr, dtype):
+        """put() of an optional operand: a null pointer and no allocation when arr is None."""
+        return self.put(arr, dtype) if arr is not None else C.c_void_p()
+
+    def alloc(self, nbytes):
+        """Raw scratch (packed weights, workspaces)."""
+        return self._place(int(nbytes), 0, None, 0)[0]
+
+    def out(self, shape, dtype, off=0, fill=None, guard=0):
+        """An output tensor `off` bytes past a 16-byte boundary, as a DeviceOut; fill: the byte the whole allocation is set to
+        first; guard: bytes (a multiple of 16) added on both sides."""
+        nbytes = int(np.prod(tuple(shape), dtype=np.int64)) * np.dtype(dtype).itemsize
+        base, total = self._place(nbytes, off, fill, guard)
+        return DeviceOut(self.ctx, base, total, guard + off, shape, dtype)
+
+    def out_opt(self, wanted, shape, dtype, off=0):
+        """out() of an optional output: a handle with a null .ptr whose .get() is None when not wanted."""
+        return self.out(shape, dtype, off) if wanted else _NoOut()
+
+    def out_by_mode(self, shape, mode, misalign):
+        """The outputs `mode` names ("f32", "i8" or "both") as the handle pair (f32, i8), each base `misalign` ELEMENTS off its
+        allocation's alignment: the fp32 output 4 * misalign bytes, the int8 output misalign bytes."""
+        assert mode in ("f32", "i8", "both")
+        return self.out_opt(mode != "i8", shape, np.float32, 4 * misalign), self.out_opt(mode != "f32", shape, np.int8, misalign)
+
+
 class Context:
     """One plhip_ctx (device + stream).  Thin, explicit device-memory helpers for tests/bench."""
 
@@ -404,6 +504,18 @@ class Context:
         self._allocs = [q for q in self._allocs if q.value != p.value]
         self.check(self.L.plhip_free(self.h, p), "plhip_free")
 
+    def outstanding(self):
+        """The number of live allocations."""
+        return len(self._allocs)
+
+    def free_all(self):
+        for p in list(self._allocs):
+            self.free(p)
+
+    def scope(self):
+        """A DeviceScope: `with ctx.scope() as s:` owns the temporary buffers of one op and frees them on the way out."""
+        return DeviceScope(self)
+
     def to_device(self, arr):
         arr = np.ascontiguousarray(arr)
         p = self.malloc(max(1, arr.nbytes))
@@ -423,29 +535,32 @@ class Context:
     def selftest(self):
         self.check(self.L.plhip_selftest(self.h), "plhip_selftest")
 
-    # ---- whole-op helpers on host arrays (upload, run through the C ABI, download) ----
+    # ---- whole-op helpers on host arrays (upload, run through the C ABI, download); every device buffer belongs to a scope
+    def _packed_conv(self, s, d, w):
+        """Uploads the int8 filter w of conv descriptor d and packs it: the packed pointer."""
+        dw = s.put(w, np.int8)
+        dwp = s.alloc(self.L.plhip_conv_packed_weight_bytes(C.byref(d)))
+        self.check(self.L.plhip_pack_conv_weights(self.h, C.byref(d), dw, dwp), "pack")
+        return dwp
+
+    def _conv_workspace(self, s, d):
+        """(pointer, bytes) of the workspace conv descriptor d asks for; a null pointer when it asks for none."""
+        wsb = self.L.plhip_conv_workspace_bytes(C.byref(d))
+        return (s.alloc(wsb) if wsb else C.c_void_p()), wsb
+
     def conv2d(self, d, x, w, scale, bias, out_kind, depthwise=False):
         oh, ow = out_hw(d)
-        dx = self.to_device(np.ascontiguousarray(x, np.int8))
-        dw = self.to_device(np.ascontiguousarray(w, np.int8))
-        ds = self.to_device(np.ascontiguousarray(scale, np.float32)) if scale is not None else C.c_void_p()
-        db = self.to_device(np.ascontiguousarray(bias, np.float32)) if bias is not None else C.c_void_p()
-        esz = 1 if out_kind == OUT_I8 else 4
-        dy = self.malloc(d.n * d.cout * oh * ow * esz)
-        tmp = [dx, dw, dy]
-        if depthwise:
-            self.check(self.L.plhip_depthwise_conv_int8(self.h, C.byref(d), dx, dw, ds, db, dy, out_kind), "depthwise")
-        else:
-            dwp = self.malloc(self.L.plhip_conv_packed_weight_bytes(C.byref(d)))
-            self.check(self.L.plhip_pack_conv_weights(self.h, C.byref(d), dw, dwp), "pack")
-            wsb = self.L.plhip_conv_workspace_bytes(C.byref(d))
-            dws = self.malloc(wsb) if wsb else C.c_void_p()
-            self.check(self.L.plhip_conv2d_int8(self.h, C.byref(d), dx, dwp, ds, db, dy, out_kind, dws, wsb), "conv2d")
-            tmp += [dwp] + ([dws] if wsb else [])
-        y = self.to_host(dy, (d.n, d.cout, oh, ow), _OUT_DTYPE[out_kind])
-        for p in tmp + ([ds] if scale is not None else []) + ([db] if bias is not None else []):
-            self.free(p)
-        return y
+        with self.scope() as s:
+            dx = s.put(x, np.int8)
+            ds, db = s.put_opt(scale, np.float32), s.put_opt(bias, np.float32)
+            y = s.out((d.n, d.cout, oh, ow), _OUT_DTYPE[out_kind])
+            if depthwise:
+                self.check(self.L.plhip_depthwise_conv_int8(self.h, C.byref(d), dx, s.put(w, np.int8), ds, db, y.ptr, out_kind), "depthwise")
+            else:
+                dwp = self._packed_conv(s, d, w)
+                dws, wsb = self._conv_workspace(s, d)
+                self.check(self.L.plhip_conv2d_int8(self.h, C.byref(d), dx, dwp, ds, db, y.ptr, out_kind, dws, wsb), "conv2d")
+            return y.get()
 
     def conv2d_transpose(self, d, x, w, scale, bias, out_kind, misalign=0, sentinel=None):
         """plhip_conv2d_transpose_int8 on host arrays: x [n, cin, h, w], w [cin, cout / groups, kh, kw] (packed here).  misalign:
@@ -453,159 +568,104 @@ class Context:
         (y, the bytes in front of and behind y)."""
         oh, ow = deconv_out_hw(d)
         c = d.conv
-        dx = self.to_device(np.ascontiguousarray(x, np.int8))
-        dw = self.to_device(np.ascontiguousarray(w, np.int8))
-        ds = self.to_device(np.ascontiguousarray(scale, np.float32)) if scale is not None else C.c_void_p()
-        db = self.to_device(np.ascontiguousarray(bias, np.float32)) if bias is not None else C.c_void_p()
-        nbytes = c.n * c.cout * oh * ow * (1 if out_kind == OUT_I8 else 4)
-        dy = self.to_device(np.full(nbytes + misalign + 64, 0 if sentinel is None else sentinel, np.uint8))
-        dwp = self.malloc(max(1, self.L.plhip_deconv_packed_weight_bytes(C.byref(d))))
-        self.check(self.L.plhip_pack_deconv_weights(self.h, C.byref(d), dw, dwp), "pack_deconv")
-        self.check(self.L.plhip_conv2d_transpose_int8(self.h, C.byref(d), dx, dwp, ds, db, C.c_void_p(dy.value + misalign), out_kind),
-                   "conv2d_transpose")
-        raw = self.to_host(dy, (nbytes + misalign + 64,), np.uint8)
-        for p in [dx, dw, dy, dwp] + ([ds] if scale is not None else []) + ([db] if bias is not None else []):
-            self.free(p)
-        y = raw[misalign:misalign + nbytes].copy().view(_OUT_DTYPE[out_kind]).reshape(c.n, c.cout, oh, ow)
-        if sentinel is None:
-            return y
-        return y, np.concatenate([raw[:misalign], raw[misalign + nbytes:]])
+        with self.scope() as s:
+            dx, dw = s.put(x, np.int8), s.put(w, np.int8)
+            ds, db = s.put_opt(scale, np.float32), s.put_opt(bias, np.float32)
+            y = s.out((c.n, c.cout, oh, ow), _OUT_DTYPE[out_kind], off=misalign, fill=0 if sentinel is None else sentinel)
+            dwp = s.alloc(self.L.plhip_deconv_packed_weight_bytes(C.byref(d)))
+            self.check(self.L.plhip_pack_deconv_weights(self.h, C.byref(d), dw, dwp), "pack_deconv")
+            self.check(self.L.plhip_conv2d_transpose_int8(self.h, C.byref(d), dx, dwp, ds, db, y.ptr, out_kind), "conv2d_transpose")
+            return y.get() if sentinel is None else (y.get(), y.margins())
 
     def conv2d_calib(self, d, x_f32, calib_scale, w, scale, bias, out_kind):
         """plhip_conv2d_calib_int8 on host arrays: calib[fp32_to_int8](calib_scale) + conv2d in one launch."""
         oh, ow = out_hw(d)
-        dx = self.to_device(np.ascontiguousarray(x_f32, np.float32))
-        dw = self.to_device(np.ascontiguousarray(w, np.int8))
-        ds = self.to_device(np.ascontiguousarray(scale, np.float32)) if scale is not None else C.c_void_p()
-        db = self.to_device(np.ascontiguousarray(bias, np.float32)) if bias is not None else C.c_void_p()
-        dy = self.malloc(d.n * d.cout * oh * ow * (1 if out_kind == OUT_I8 else 4))
-        dwp = self.malloc(self.L.plhip_conv_packed_weight_bytes(C.byref(d)))
-        self.check(self.L.plhip_pack_conv_weights(self.h, C.byref(d), dw, dwp), "pack")
-        self.check(self.L.plhip_conv2d_calib_int8(self.h, C.byref(d), dx, calib_scale, dwp, ds, db, dy, out_kind), "conv2d_calib")
-        y = self.to_host(dy, (d.n, d.cout, oh, ow), _OUT_DTYPE[out_kind])
-        for p in [dx, dw, dy, dwp] + ([ds] if scale is not None else []) + ([db] if bias is not None else []):
-            self.free(p)
-        return y
+        with self.scope() as s:
+            dx = s.put(x_f32, np.float32)
+            ds, db = s.put_opt(scale, np.float32), s.put_opt(bias, np.float32)
+            y = s.out((d.n, d.cout, oh, ow), _OUT_DTYPE[out_kind])
+            dwp = self._packed_conv(s, d, w)
+            self.check(self.L.plhip_conv2d_calib_int8(self.h, C.byref(d), dx, calib_scale, dwp, ds, db, y.ptr, out_kind), "conv2d_calib")
+            return y.get()
 
     def image_to_tensor(self, img, src_u8, calib_scale=None):
         """plhip_image_to_tensor_f32 (calib_scale None) or _i8 on a host uint8 image [n, h, w, cs]: the NCHW tensor."""
-        src = np.ascontiguousarray(src_u8, np.uint8)
-        shape = (img.n, IMG_CHANNELS[img.format], img.h, img.w)
-        cnt = int(np.prod(shape))
-        dx = self.to_device(src)
-        if calib_scale is None:
-            dy = self.malloc(cnt * 4)
-            self.check(self.L.plhip_image_to_tensor_f32(self.h, C.byref(img), dx, dy), "image_to_tensor_f32")
-            y = self.to_host(dy, shape, np.float32)
-        else:
-            dy = self.malloc(cnt)
-            self.check(self.L.plhip_image_to_tensor_i8(self.h, C.byref(img), dx, dy, float(calib_scale)), "image_to_tensor_i8")
-            y = self.to_host(dy, shape, np.int8)
-        self.free(dx), self.free(dy)
-        return y
+        shape = (img.n, IMG_CHANNELS.get(img.format, 3), img.h, img.w)  # a format the library refuses gets its PlhipError
+        with self.scope() as s:
+            dx = s.put(src_u8, np.uint8)
+            y = s.out(shape, np.float32 if calib_scale is None else np.int8)
+            if calib_scale is None:
+                self.check(self.L.plhip_image_to_tensor_f32(self.h, C.byref(img), dx, y.ptr), "image_to_tensor_f32")
+            else:
+                self.check(self.L.plhip_image_to_tensor_i8(self.h, C.byref(img), dx, y.ptr, float(calib_scale)), "image_to_tensor_i8")
+            return y.get()
 
     def image_convert(self, frame, src_u8, dst_format=IMG_BGR):
         """plhip_image_convert_u8 on a host NV12 / NV21 frame [n, h * 3 / 2, w]: the interleaved image [n, h, w, 3 | 4]."""
-        dx = self.to_device(np.ascontiguousarray(src_u8, np.uint8))
-        shape = (frame.n, frame.h, frame.w, IMG_BYTES.get(dst_format, 4))
-        dy = self.malloc(int(np.prod(shape)))
-        try:
-            self.check(self.L.plhip_image_convert_u8(self.h, C.byref(frame), dx, int(dst_format), dy), "image_convert_u8")
-            return self.to_host(dy, shape, np.uint8)
-        finally:
-            self.free(dx), self.free(dy)
+        with self.scope() as s:
+            dx = s.put(src_u8, np.uint8)
+            y = s.out((frame.n, frame.h, frame.w, IMG_BYTES.get(dst_format, 4)), np.uint8)
+            self.check(self.L.plhip_image_convert_u8(self.h, C.byref(frame), dx, int(dst_format), y.ptr), "image_convert_u8")
+            return y.get()
 
     def image_resize(self, frame, src_u8, h_out, w_out):
         """plhip_image_resize_u8 on a host frame: the resized interleaved image [n, h_out, w_out, cs] (BGR from an NV frame)."""
-        dx = self.to_device(np.ascontiguousarray(src_u8, np.uint8))
-        shape = (frame.n, h_out, w_out, IMG_BYTES.get(frame.format, 3))
-        dy = self.malloc(max(1, int(np.prod(shape))))
-        try:
-            self.check(self.L.plhip_image_resize_u8(self.h, C.byref(frame), dx, int(h_out), int(w_out), dy), "image_resize_u8")
-            return self.to_host(dy, shape, np.uint8)
-        finally:
-            self.free(dx), self.free(dy)
+        with self.scope() as s:
+            dx = s.put(src_u8, np.uint8)
+            y = s.out((frame.n, h_out, w_out, IMG_BYTES.get(frame.format, 3)), np.uint8)
+            self.check(self.L.plhip_image_resize_u8(self.h, C.byref(frame), dx, int(h_out), int(w_out), y.ptr), "image_resize_u8")
+            return y.get()
 
     def frame_to_tensor(self, frame, img, src_u8, calib_scale=None):
         """plhip_frame_to_tensor_f32 (calib_scale None) or _i8 on a host frame: the NCHW tensor of the resized image, one launch."""
-        dx = self.to_device(np.ascontiguousarray(src_u8, np.uint8))
-        shape = (img.n, IMG_CHANNELS.get(img.format, 3), img.h, img.w)
-        cnt = max(1, int(np.prod(shape)))
-        dy = self.malloc(cnt * (4 if calib_scale is None else 1))
-        try:
+        with self.scope() as s:
+            dx = s.put(src_u8, np.uint8)
+            y = s.out((img.n, IMG_CHANNELS.get(img.format, 3), img.h, img.w), np.float32 if calib_scale is None else np.int8)
             if calib_scale is None:
-                self.check(self.L.plhip_frame_to_tensor_f32(self.h, C.byref(frame), C.byref(img), dx, dy), "frame_to_tensor_f32")
-                return self.to_host(dy, shape, np.float32)
-            self.check(self.L.plhip_frame_to_tensor_i8(self.h, C.byref(frame), C.byref(img), dx, dy, float(calib_scale)), "frame_to_tensor_i8")
-            return self.to_host(dy, shape, np.int8)
-        finally:
-            self.free(dx), self.free(dy)
+                self.check(self.L.plhip_frame_to_tensor_f32(self.h, C.byref(frame), C.byref(img), dx, y.ptr), "frame_to_tensor_f32")
+            else:
+                self.check(self.L.plhip_frame_to_tensor_i8(self.h, C.byref(frame), C.byref(img), dx, y.ptr, float(calib_scale)), "frame_to_tensor_i8")
+            return y.get()
 
     def conv2d_image(self, d, img, src_u8, calib_scale, w, scale, bias, out_kind):
         """plhip_conv2d_image_int8 on host arrays: image_to_tensor + calib[fp32_to_int8](calib_scale) + conv2d in one launch."""
         oh, ow = out_hw(d)
-        dx = self.to_device(np.ascontiguousarray(src_u8, np.uint8))
-        dw = self.to_device(np.ascontiguousarray(w, np.int8))
-        ds = self.to_device(np.ascontiguousarray(scale, np.float32)) if scale is not None else C.c_void_p()
-        db = self.to_device(np.ascontiguousarray(bias, np.float32)) if bias is not None else C.c_void_p()
-        dy = self.malloc(d.n * d.cout * oh * ow * (1 if out_kind == OUT_I8 else 4))
-        dwp = self.malloc(self.L.plhip_conv_packed_weight_bytes(C.byref(d)))
-        self.check(self.L.plhip_pack_conv_weights(self.h, C.byref(d), dw, dwp), "pack")
-        self.check(self.L.plhip_conv2d_image_int8(self.h, C.byref(d), C.byref(img), dx, float(calib_scale), dwp, ds, db, dy, out_kind),
-                   "conv2d_image")
-        y = self.to_host(dy, (d.n, d.cout, oh, ow), _OUT_DTYPE[out_kind])
-        for p in [dx, dw, dy, dwp] + ([ds] if scale is not None else []) + ([db] if bias is not None else []):
-            self.free(p)
-        return y
+        with self.scope() as s:
+            dx = s.put(src_u8, np.uint8)
+            ds, db = s.put_opt(scale, np.float32), s.put_opt(bias, np.float32)
+            y = s.out((d.n, d.cout, oh, ow), _OUT_DTYPE[out_kind])
+            dwp = self._packed_conv(s, d, w)
+            self.check(self.L.plhip_conv2d_image_int8(self.h, C.byref(d), C.byref(img), dx, float(calib_scale), dwp, ds, db, y.ptr, out_kind),
+                       "conv2d_image")
+            return y.get()
 
     def conv2d_fused(self, d, x, w, scale, bias, residual, residual_relu, calib_scale, want_f32=True):
         """plhip_conv2d_int8_fused on host arrays: returns (y_f32 or None, y_i8 or None)."""
         oh, ow = out_hw(d)
         shape = (d.n, d.cout, oh, ow)
-        dx = self.to_device(np.ascontiguousarray(x, np.int8))
-        dw = self.to_device(np.ascontiguousarray(w, np.int8))
-        ds = self.to_device(np.ascontiguousarray(scale, np.float32))
-        db = self.to_device(np.ascontiguousarray(bias, np.float32)) if bias is not None else C.c_void_p()
-        dr = self.to_device(np.ascontiguousarray(residual, np.float32)) if residual is not None else C.c_void_p()
-        n_out = int(np.prod(shape))
-        dyf = self.malloc(n_out * 4) if want_f32 else C.c_void_p()
-        dyq = self.malloc(n_out) if calib_scale is not None else C.c_void_p()
-        dwp = self.malloc(self.L.plhip_conv_packed_weight_bytes(C.byref(d)))
-        self.check(self.L.plhip_pack_conv_weights(self.h, C.byref(d), dw, dwp), "pack")
-        wsb = self.L.plhip_conv_workspace_bytes(C.byref(d))
-        dws = self.malloc(wsb) if wsb else C.c_void_p()
-        self.check(self.L.plhip_conv2d_int8_fused(self.h, C.byref(d), dx, dwp, ds, db, dyf, dr, int(residual_relu), dyq,
-                                                  float(calib_scale) if calib_scale is not None else 0.0, dws, wsb), "conv2d_fused")
-        yf = self.to_host(dyf, shape, np.float32) if want_f32 else None
-        yq = self.to_host(dyq, shape, np.int8) if calib_scale is not None else None
-        for p_ in [dx, dw, ds, dwp] + ([db] if bias is not None else []) + ([dr] if residual is not None else []) + \
-                ([dyf] if want_f32 else []) + ([dyq] if calib_scale is not None else []) + ([dws] if wsb else []):
-            self.free(p_)
-        return yf, yq
+        with self.scope() as s:
+            dx, ds = s.put(x, np.int8), s.put(scale, np.float32)
+            db, dr = s.put_opt(bias, np.float32), s.put_opt(residual, np.float32)
+            yf, yq = s.out_opt(want_f32, shape, np.float32), s.out_opt(calib_scale is not None, shape, np.int8)
+            dwp = self._packed_conv(s, d, w)
+            dws, wsb = self._conv_workspace(s, d)
+            self.check(self.L.plhip_conv2d_int8_fused(self.h, C.byref(d), dx, dwp, ds, db, yf.ptr, dr, int(residual_relu), yq.ptr,
+                                                      float(calib_scale) if calib_scale is not None else 0.0, dws, wsb), "conv2d_fused")
+            return yf.get(), yq.get()
 
     def dwpw_fused(self, d_dw, x, w_dw, s_dw, b_dw, w_pw, s_pw, b_pw, pw_act, pw_alpha, out_kind):
         """Fused depthwise -> pointwise through the C ABI (host arrays in, host array out)."""
         oh, ow = out_hw(d_dw)
         cout = w_pw.shape[0]
         d_pw = conv_desc(d_dw.n, d_dw.cin, oh, ow, cout, 1, 1, act=pw_act, alpha=pw_alpha)
-        dx = self.to_device(np.ascontiguousarray(x, np.int8))
-        dwd = self.to_device(np.ascontiguousarray(w_dw, np.int8))
-        dsd = self.to_device(np.ascontiguousarray(s_dw, np.float32))
-        dbd = self.to_device(np.ascontiguousarray(b_dw, np.float32)) if b_dw is not None else C.c_void_p()
-        dwp_raw = self.to_device(np.ascontiguousarray(w_pw, np.int8))
-        dwp = self.malloc(self.L.plhip_conv_packed_weight_bytes(C.byref(d_pw)))
-        self.check(self.L.plhip_pack_conv_weights(self.h, C.byref(d_pw), dwp_raw, dwp), "pack")
-        dsp = self.to_device(np.ascontiguousarray(s_pw, np.float32)) if s_pw is not None else C.c_void_p()
-        dbp = self.to_device(np.ascontiguousarray(b_pw, np.float32)) if b_pw is not None else C.c_void_p()
-        esz = 1 if out_kind == OUT_I8 else 4
-        dy = self.malloc(d_dw.n * cout * oh * ow * esz)
-        self.check(self.L.plhip_dwpw_fused_int8(self.h, C.byref(d_dw), dx, dwd, dsd, dbd, cout, dwp, dsp, dbp, pw_act, pw_alpha,
-                                                dy, out_kind), "dwpw_fused")
-        y = self.to_host(dy, (d_dw.n, cout, 1, 1), np.float32) if out_kind == OUT_F32_GAP else self.to_host(dy, (d_dw.n, cout, oh, ow), _OUT_DTYPE[out_kind])
-        for p in [dx, dwd, dsd, dwp_raw, dwp, dy] + ([dbd] if b_dw is not None else []) + ([dsp] if s_pw is not None else []) + \
-                ([dbp] if b_pw is not None else []):
-            self.free(p)
-        return y
+        with self.scope() as s:
+            dx, dwd, dsd, dbd = s.put(x, np.int8), s.put(w_dw, np.int8), s.put(s_dw, np.float32), s.put_opt(b_dw, np.float32)
+            dwp = self._packed_conv(s, d_pw, w_pw)
+            dsp, dbp = s.put_opt(s_pw, np.float32), s.put_opt(b_pw, np.float32)
+            y = s.out((d_dw.n, cout, oh, ow), _OUT_DTYPE.get(out_kind, np.float32))
+            self.check(self.L.plhip_dwpw_fused_int8(self.h, C.byref(d_dw), dx, dwd, dsd, dbd, cout, dwp, dsp, dbp, pw_act, pw_alpha,
+                                                    y.ptr, out_kind), "dwpw_fused")
+            return self.to_host(y.ptr, (d_dw.n, cout, 1, 1), np.float32) if out_kind == OUT_F32_GAP else y.get()
 
     def dw_conv1x1_fused(self, d_dw, x, w_dw, s_dw, b_dw, w_pw, s_pw, b_pw, pw_act, pw_alpha, out_kind,
                          residual=None, residual_relu=0, calib_scale=None, want_y=True):
@@ -615,88 +675,61 @@ class Context:
         cout = w_pw.shape[0]
         shape = (d_dw.n, cout, oh, ow)
         d_pw = conv_desc(d_dw.n, d_dw.cin, oh, ow, cout, 1, 1, act=pw_act, alpha=pw_alpha)
-        dx = self.to_device(np.ascontiguousarray(x, np.int8))
-        dwd = self.to_device(np.ascontiguousarray(w_dw, np.int8))
-        dsd = self.to_device(np.ascontiguousarray(s_dw, np.float32))
-        dbd = self.to_device(np.ascontiguousarray(b_dw, np.float32)) if b_dw is not None else C.c_void_p()
-        dwp_raw = self.to_device(np.ascontiguousarray(w_pw, np.int8))
-        dwp = self.malloc(self.L.plhip_conv_packed_weight_bytes(C.byref(d_pw)))
-        self.check(self.L.plhip_pack_conv_weights(self.h, C.byref(d_pw), dwp_raw, dwp), "pack")
-        dsp = self.to_device(np.ascontiguousarray(s_pw, np.float32)) if s_pw is not None else C.c_void_p()
-        dbp = self.to_device(np.ascontiguousarray(b_pw, np.float32)) if b_pw is not None else C.c_void_p()
-        dr = self.to_device(np.ascontiguousarray(residual, np.float32)) if residual is not None else C.c_void_p()
-        n_out = int(np.prod(shape))
-        esz = 1 if out_kind == OUT_I8 else 4
-        dy = self.malloc(n_out * esz) if want_y else C.c_void_p()
-        dyq = self.malloc(n_out) if calib_scale is not None else C.c_void_p()
-        self.check(self.L.plhip_dw_conv1x1_fused_int8(self.h, C.byref(d_dw), dx, dwd, dsd, dbd, cout, dwp, dsp, dbp, pw_act,
-                                                      pw_alpha, dy, out_kind, dr, int(residual_relu), dyq,
-                                                      float(calib_scale) if calib_scale is not None else 0.0),
-                   "dw_conv1x1_fused")
-        y = self.to_host(dy, shape, _OUT_DTYPE[out_kind]) if want_y else None
-        yq = self.to_host(dyq, shape, np.int8) if calib_scale is not None else None
-        for p in [dx, dwd, dsd, dwp_raw, dwp] + ([dy] if want_y else []) + ([dyq] if calib_scale is not None else []) + \
-                ([dbd] if b_dw is not None else []) + ([dsp] if s_pw is not None else []) + ([dbp] if b_pw is not None else []) + \
-                ([dr] if residual is not None else []):
-            self.free(p)
-        return y, yq
+        with self.scope() as s:
+            dx, dwd, dsd, dbd = s.put(x, np.int8), s.put(w_dw, np.int8), s.put(s_dw, np.float32), s.put_opt(b_dw, np.float32)
+            dwp = self._packed_conv(s, d_pw, w_pw)
+            dsp, dbp, dr = s.put_opt(s_pw, np.float32), s.put_opt(b_pw, np.float32), s.put_opt(residual, np.float32)
+            y, yq = s.out_opt(want_y, shape, _OUT_DTYPE[out_kind]), s.out_opt(calib_scale is not None, shape, np.int8)
+            self.check(self.L.plhip_dw_conv1x1_fused_int8(self.h, C.byref(d_dw), dx, dwd, dsd, dbd, cout, dwp, dsp, dbp, pw_act,
+                                                          pw_alpha, y.ptr, out_kind, dr, int(residual_relu), yq.ptr,
+                                                          float(calib_scale) if calib_scale is not None else 0.0),
+                       "dw_conv1x1_fused")
+            return y.get(), yq.get()
 
     def fc(self, x, w, scale, bias, relu, out_kind):
         x = np.ascontiguousarray(x, np.int8)
         w = np.ascontiguousarray(w, np.int8)
         m, k = x.shape
         n = w.shape[1]
-        dx, dw = self.to_device(x), self.to_device(w)
-        dwp = self.malloc(self.L.plhip_fc_packed_weight_bytes(k, n))
-        self.check(self.L.plhip_pack_fc_weights(self.h, k, n, dw, dwp), "pack_fc")
-        ds = self.to_device(np.ascontiguousarray(scale, np.float32)) if scale is not None else C.c_void_p()
-        db = self.to_device(np.ascontiguousarray(bias, np.float32)) if bias is not None else C.c_void_p()
-        esz = 1 if out_kind == OUT_I8 else 4
-        dy = self.malloc(m * n * esz)
-        self.check(self.L.plhip_fc_int8(self.h, m, k, n, dx, dwp, ds, db, int(relu), dy, out_kind), "fc")
-        y = self.to_host(dy, (m, n), _OUT_DTYPE[out_kind])
-        for p in [dx, dw, dwp, dy] + ([ds] if scale is not None else []) + ([db] if bias is not None else []):
-            self.free(p)
-        return y
+        with self.scope() as s:
+            dx, dw = s.put(x), s.put(w)
+            dwp = s.alloc(self.L.plhip_fc_packed_weight_bytes(k, n))
+            self.check(self.L.plhip_pack_fc_weights(self.h, k, n, dw, dwp), "pack_fc")
+            ds, db = s.put_opt(scale, np.float32), s.put_opt(bias, np.float32)
+            y = s.out((m, n), _OUT_DTYPE[out_kind])
+            self.check(self.L.plhip_fc_int8(self.h, m, k, n, dx, dwp, ds, db, int(relu), y.ptr, out_kind), "fc")
+            return y.get()
 
     def calib_f32_to_i8(self, x, scale):
         x = np.ascontiguousarray(x, np.float32)
-        dx = self.to_device(x)
-        dy = self.malloc(max(1, x.size))
-        self.check(self.L.plhip_calib_f32_to_i8(self.h, dx, dy, scale, x.size), "calib_f32_to_i8")
-        y = self.to_host(dy, x.shape, np.int8)
-        self.free(dx), self.free(dy)
-        return y
+        with self.scope() as s:
+            y = s.out(x.shape, np.int8)
+            self.check(self.L.plhip_calib_f32_to_i8(self.h, s.put(x), y.ptr, scale, x.size), "calib_f32_to_i8")
+            return y.get()
 
     def calib_i8_to_f32(self, x, scale):
         x = np.ascontiguousarray(x, np.int8)
-        dx = self.to_device(x)
-        dy = self.malloc(max(4, x.size * 4))
-        self.check(self.L.plhip_calib_i8_to_f32(self.h, dx, dy, scale, x.size), "calib_i8_to_f32")
-        y = self.to_host(dy, x.shape, np.float32)
-        self.free(dx), self.free(dy)
-        return y
+        with self.scope() as s:
+            y = s.out(x.shape, np.float32)
+            self.check(self.L.plhip_calib_i8_to_f32(self.h, s.put(x), y.ptr, scale, x.size), "calib_i8_to_f32")
+            return y.get()
 
     def global_avg_pool(self, x):
         x = np.ascontiguousarray(x, np.float32)
         n, c = x.shape[:2]
         sp = int(np.prod(x.shape[2:]))
-        dx = self.to_device(x)
-        dy = self.malloc(n * c * 4)
-        self.check(self.L.plhip_global_avg_pool_f32(self.h, dx, n * c, sp, dy), "pool")
-        y = self.to_host(dy, (n, c, 1, 1), np.float32)
-        self.free(dx), self.free(dy)
-        return y
+        with self.scope() as s:
+            y = s.out((n, c, 1, 1), np.float32)
+            self.check(self.L.plhip_global_avg_pool_f32(self.h, s.put(x), n * c, sp, y.ptr), "pool")
+            return y.get()
 
     def softmax(self, x):
         x = np.ascontiguousarray(x, np.float32)
         rows, cols = int(np.prod(x.shape[:-1])), x.shape[-1]
-        dx = self.to_device(x)
-        dy = self.malloc(x.size * 4)
-        self.check(self.L.plhip_softmax_f32(self.h, dx, rows, cols, dy), "softmax")
-        y = self.to_host(dy, x.shape, np.float32)
-        self.free(dx), self.free(dy)
-        return y
+        with self.scope() as s:
+            y = s.out(x.shape, np.float32)
+            self.check(self.L.plhip_softmax_f32(self.h, s.put(x), rows, cols, y.ptr), "softmax")
+            return y.get()
 
     def pool2d(self, x, pooling_type, ksize, strides, pads, exclusive=True, ceil_mode=False):
         """x [n,c,h,w] fp32; pads {top, bottom, left, right}; output dims by PoolOutputSize (pool_op.cc:44-61)."""
@@ -713,54 +746,32 @@ class Context:
         d.pad[:] = list(pads)
         d.stride[:] = list(strides)
         d.is_max, d.exclusive = int(pooling_type == "max"), int(exclusive)
-        dx = self.to_device(x)
-        dy = self.malloc(n * c * d.oh * d.ow * (1 if i8 else 4))
         fn = self.L.plhip_pool2d_max_i8 if i8 else self.L.plhip_pool2d_f32
-        self.check(fn(self.h, C.byref(d), dx, dy), "pool2d")
-        y = self.to_host(dy, (n, c, d.oh, d.ow), np.int8 if i8 else np.float32)
-        self.free(dx), self.free(dy)
-        return y
+        with self.scope() as s:
+            y = s.out((n, c, d.oh, d.ow), x.dtype)
+            self.check(fn(self.h, C.byref(d), s.put(x), y.ptr), "pool2d")
+            return y.get()
 
     def elementwise_add(self, x, y, relu=False):
         x = np.ascontiguousarray(x, np.float32)
-        y = np.ascontiguousarray(y, np.float32)
-        dx, dy = self.to_device(x), self.to_device(y)
-        do = self.malloc(max(4, x.size * 4))
-        self.check(self.L.plhip_elementwise_add_f32(self.h, dx, dy, do, x.size, int(relu)), "elementwise_add")
-        o = self.to_host(do, x.shape, np.float32)
-        self.free(dx), self.free(dy), self.free(do)
-        return o
+        with self.scope() as s:
+            dx, dy = s.put(x), s.put(y, np.float32)
+            o = s.out(x.shape, np.float32)
+            self.check(self.L.plhip_elementwise_add_f32(self.h, dx, dy, o.ptr, x.size, int(relu)), "elementwise_add")
+            return o.get()
 
-    def _two_outputs(self, call, x, shape, mode, calib_scale, misalign):
-        """Runs call(dx, dyf, dyq) with the outputs `mode` asks for ("f32", "i8" or "both"); misalign: elements the input and
-        output bases are moved off their allocations' alignment (the scalar path).  Returns (y_f32 or None, y_i8 or None)."""
-        assert mode in ("f32", "i8", "both")
-        cnt = int(np.prod(shape))
-        buf = self.malloc(4 * (x.size + misalign))
-        dx = C.c_void_p(buf.value + 4 * misalign)
-        self.check(self.L.plhip_memcpy_h2d(self.h, dx, x.ctypes.data_as(C.c_void_p), x.nbytes), "h2d")
-        bf = self.malloc(4 * (cnt + misalign)) if mode != "i8" else None
-        bq = self.malloc(cnt + misalign + 4) if mode != "f32" else None
-        dyf = C.c_void_p(bf.value + 4 * misalign) if bf else C.c_void_p()
-        dyq = C.c_void_p(bq.value + misalign) if bq else C.c_void_p()
-        call(dx, dyf, dyq)
-        yf = self.to_host(dyf, shape, np.float32) if bf else None
-        yq = self.to_host(dyq, shape, np.int8) if bq else None
-        for p in (buf, bf, bq):
-            if p:
-                self.free(p)
-        return yf, yq
-
+    # ---- misalign below: ELEMENTS every device base of the helper is moved off its allocation's alignment (the scalar path)
     def hard_act(self, kind, x, params=None, mode="f32", calib_scale=1.0, misalign=0):
         """plhip_hard_act_f32: kind HARD_SWISH (params threshold, scale, offset) or HARD_SIGMOID (slope, offset)."""
         x = np.ascontiguousarray(x, np.float32)
         if params is None:
             params = HARD_SWISH_DEFAULTS if kind == HARD_SWISH else HARD_SIGMOID_DEFAULTS
         pr = (C.c_float * 3)(*(list(map(float, params)) + [0.0] * 3)[:3])
-
-        def call(dx, dyf, dyq):
-            self.check(self.L.plhip_hard_act_f32(self.h, int(kind), pr, dx, dyf, dyq, float(calib_scale), x.size), "hard_act")
-        return self._two_outputs(call, x, x.shape, mode, calib_scale, misalign)
+        with self.scope() as s:
+            dx = s.put(x, off=4 * misalign)
+            yf, yq = s.out_by_mode(x.shape, mode, misalign)
+            self.check(self.L.plhip_hard_act_f32(self.h, int(kind), pr, dx, yf.ptr, yq.ptr, float(calib_scale), x.size), "hard_act")
+            return yf.get(), yq.get()
 
     def se_scale(self, x, gate, mode="f32", calib_scale=1.0, misalign=0):
         """plhip_se_scale_f32: x [n, c, ...] fp32 times gate [n, c] (any trailing 1s)."""
@@ -769,13 +780,11 @@ class Context:
         n, c = x.shape[:2]
         hw = int(np.prod(x.shape[2:]))
         assert gate.size == n * c
-        dg = self.to_device(gate)
-
-        def call(dx, dyf, dyq):
-            self.check(self.L.plhip_se_scale_f32(self.h, dx, dg, n, c, hw, dyf, dyq, float(calib_scale)), "se_scale")
-        r = self._two_outputs(call, x, x.shape, mode, calib_scale, misalign)
-        self.free(dg)
-        return r
+        with self.scope() as s:
+            dg, dx = s.put(gate), s.put(x, off=4 * misalign)
+            yf, yq = s.out_by_mode(x.shape, mode, misalign)
+            self.check(self.L.plhip_se_scale_f32(self.h, dx, dg, n, c, hw, yf.ptr, yq.ptr, float(calib_scale)), "se_scale")
+            return yf.get(), yq.get()
 
     def se_gate(self, pooled, calib_scale, w1, s1, b1, act1, alpha1, w2, s2, b2, act2=ACT_NONE, alpha2=0.0, slope=0.2, offset=0.5):
         """plhip_se_gate_int8: pooled fp32 [n, c]; w1 [cr, c] / w2 [c, cr] int8; s / b the convs' folded scale / bias arrays
@@ -786,130 +795,80 @@ class Context:
         cr = w1.shape[0]
         w2 = np.ascontiguousarray(w2, np.int8).reshape(c, cr)
         d = SeGateDesc(n, c, cr, float(calib_scale), int(act1), int(act2), float(alpha1), float(alpha2), float(slope), float(offset))
-        ptrs = [self.to_device(pooled), self.to_device(w1), self.to_device(w2), self.malloc(self.L.plhip_se_gate_packed_weight_bytes(c, cr)),
-                self.to_device(np.ascontiguousarray(s1, np.float32)), self.to_device(np.ascontiguousarray(s2, np.float32)),
-                self.malloc(n * c * 4)]
-        dx, dw1, dw2, dwp, ds1, ds2, dy = ptrs
-        db1 = self.to_device(np.ascontiguousarray(b1, np.float32)) if b1 is not None else None
-        db2 = self.to_device(np.ascontiguousarray(b2, np.float32)) if b2 is not None else None
-        self.check(self.L.plhip_pack_se_gate_weights(self.h, c, cr, dw1, dw2, dwp), "pack_se_gate")
-        self.check(self.L.plhip_se_gate_int8(self.h, C.byref(d), dx, dwp, ds1, db1 or C.c_void_p(), ds2, db2 or C.c_void_p(), dy), "se_gate")
-        y = self.to_host(dy, (n, c), np.float32)
-        for p in ptrs + [q for q in (db1, db2) if q is not None]:
-            self.free(p)
-        return y
+        with self.scope() as s:
+            dx, dw1, dw2 = s.put(pooled), s.put(w1), s.put(w2)
+            dwp = s.alloc(self.L.plhip_se_gate_packed_weight_bytes(c, cr))
+            ds1, ds2 = s.put(s1, np.float32), s.put(s2, np.float32)
+            db1, db2 = s.put_opt(b1, np.float32), s.put_opt(b2, np.float32)
+            y = s.out((n, c), np.float32)
+            self.check(self.L.plhip_pack_se_gate_weights(self.h, c, cr, dw1, dw2, dwp), "pack_se_gate")
+            self.check(self.L.plhip_se_gate_int8(self.h, C.byref(d), dx, dwp, ds1, db1, ds2, db2, y.ptr), "se_gate")
+            return y.get()
 
-    # ---- concat / split / shuffle_channel and the fused unit tail (shuffle_ops.hip).  misalign: elements every device base is
-    # moved off its allocation's alignment (the scalar path)
-    def _up_f32(self, x, misalign):
-        """Uploads x behind `misalign` elements of slack; returns (allocation, pointer to the data)."""
-        x = np.ascontiguousarray(x, np.float32)
-        buf = self.malloc(4 * (x.size + misalign) + 4)
-        d = C.c_void_p(buf.value + 4 * misalign)
-        if x.nbytes:
-            self.check(self.L.plhip_memcpy_h2d(self.h, d, x.ctypes.data_as(C.c_void_p), x.nbytes), "h2d")
-        return buf, d
-
-    def _out_buf(self, count, esize, misalign):
-        buf = self.malloc(esize * (count + misalign) + 8)
-        return buf, C.c_void_p(buf.value + esize * misalign)
-
+    # ---- concat / split / shuffle_channel and the fused unit tail (shuffle_ops.hip)
     def concat(self, xs, axis, misalign=0):
         """plhip_concat_f32 of fp32 arrays along `axis`."""
         xs = [np.ascontiguousarray(x, np.float32) for x in xs]
-        axis = axis + xs[0].ndim if axis < 0 else axis
-        outer = int(np.prod(xs[0].shape[:axis], dtype=np.int64))
-        inner = int(np.prod(xs[0].shape[axis + 1:], dtype=np.int64))
-        ups = [self._up_f32(x, misalign) for x in xs]
-        shape = list(xs[0].shape)
-        shape[axis] = sum(x.shape[axis] for x in xs)
-        ybuf, dy = self._out_buf(int(np.prod(shape)), 4, misalign)
-        ptrs = (C.c_void_p * len(xs))(*[d for _b, d in ups])
+        axis, outer, inner = _outer_inner(xs[0].shape, axis)
+        shape = xs[0].shape[:axis] + (sum(x.shape[axis] for x in xs),) + xs[0].shape[axis + 1:]
         ext = (C.c_int64 * len(xs))(*[x.shape[axis] for x in xs])
-        self.check(self.L.plhip_concat_f32(self.h, ptrs, ext, len(xs), outer, inner, dy), "concat")
-        y = self.to_host(dy, tuple(shape), np.float32)
-        for b in [ybuf] + [b for b, _d in ups]:
-            self.free(b)
-        return y
+        with self.scope() as s:
+            ptrs = (C.c_void_p * len(xs))(*[s.put(x, off=4 * misalign) for x in xs])
+            y = s.out(shape, np.float32, 4 * misalign)
+            self.check(self.L.plhip_concat_f32(self.h, ptrs, ext, len(xs), outer, inner, y.ptr), "concat")
+            return y.get()
 
     def concat_calib(self, xs, axis, calib_scale, with_f32=True, misalign=0):
         """plhip_concat_calib_f32 of fp32 arrays along `axis`: returns (y_f32 or None, y_i8)."""
         xs = [np.ascontiguousarray(x, np.float32) for x in xs]
-        axis = axis + xs[0].ndim if axis < 0 else axis
-        outer = int(np.prod(xs[0].shape[:axis], dtype=np.int64))
-        inner = int(np.prod(xs[0].shape[axis + 1:], dtype=np.int64))
-        ups = [self._up_f32(x, misalign) for x in xs]
-        shape = list(xs[0].shape)
-        shape[axis] = sum(x.shape[axis] for x in xs)
-        cnt = int(np.prod(shape))
-        fbuf, df = self._out_buf(cnt, 4, misalign) if with_f32 else (None, C.c_void_p())
-        qbuf, dq = self._out_buf(cnt, 1, misalign)
-        ptrs = (C.c_void_p * len(xs))(*[d for _b, d in ups])
+        axis, outer, inner = _outer_inner(xs[0].shape, axis)
+        shape = xs[0].shape[:axis] + (sum(x.shape[axis] for x in xs),) + xs[0].shape[axis + 1:]
         ext = (C.c_int64 * len(xs))(*[x.shape[axis] for x in xs])
-        try:
-            self.check(self.L.plhip_concat_calib_f32(self.h, ptrs, ext, len(xs), outer, inner, df, dq, float(calib_scale)), "concat_calib")
-            yf = self.to_host(df, tuple(shape), np.float32) if with_f32 else None
-            yq = self.to_host(dq, tuple(shape), np.int8)
-        finally:
-            for b in [qbuf] + ([fbuf] if with_f32 else []) + [b for b, _d in ups]:
-                self.free(b)
-        return yf, yq
+        with self.scope() as s:
+            ptrs = (C.c_void_p * len(xs))(*[s.put(x, off=4 * misalign) for x in xs])
+            yf, yq = s.out_opt(with_f32, shape, np.float32, 4 * misalign), s.out(shape, np.int8, misalign)
+            self.check(self.L.plhip_concat_calib_f32(self.h, ptrs, ext, len(xs), outer, inner, yf.ptr, yq.ptr, float(calib_scale)), "concat_calib")
+            return yf.get(), yq.get()
 
     def split(self, x, axis, num=0, sections=(), misalign=0):
         """plhip_split_f32: num > 0 equal parts, else `sections`.  Returns the list of parts."""
         x = np.ascontiguousarray(x, np.float32)
-        axis = axis + x.ndim if axis < 0 else axis
-        outer = int(np.prod(x.shape[:axis], dtype=np.int64))
-        inner = int(np.prod(x.shape[axis + 1:], dtype=np.int64))
+        axis, outer, inner = _outer_inner(x.shape, axis)
         ext = [x.shape[axis] // num] * num if num > 0 else list(sections)
-        xbuf, dx = self._up_f32(x, misalign)
-        outs = [self._out_buf(outer * e * inner, 4, misalign) for e in ext]
-        ptrs = (C.c_void_p * len(ext))(*[d for _b, d in outs])
         sec = (C.c_int64 * max(1, len(sections)))(*sections) if num == 0 else None
-        self.check(self.L.plhip_split_f32(self.h, dx, outer, x.shape[axis], inner, int(num), sec, len(ext), ptrs), "split")
-        ys = []
-        for e, (_b, d) in zip(ext, outs):
-            shape = list(x.shape)
-            shape[axis] = e
-            ys.append(self.to_host(d, tuple(shape), np.float32))
-        for b in [xbuf] + [b for b, _d in outs]:
-            self.free(b)
-        return ys
+        with self.scope() as s:
+            dx = s.put(x, off=4 * misalign)
+            outs = [s.out(x.shape[:axis] + (e,) + x.shape[axis + 1:], np.float32, 4 * misalign) for e in ext]
+            ptrs = (C.c_void_p * len(ext))(*[o.ptr for o in outs])
+            self.check(self.L.plhip_split_f32(self.h, dx, outer, x.shape[axis], inner, int(num), sec, len(ext), ptrs), "split")
+            return [o.get() for o in outs]
 
     def shuffle_channel(self, x, group, mode="f32", calib_scale=1.0, misalign=0):
         """plhip_shuffle_channel_f32: x [n, c, ...]; returns (y_f32 or None, y_i8 or None)."""
         x = np.ascontiguousarray(x, np.float32)
         n, c = x.shape[:2]
         hw = int(np.prod(x.shape[2:], dtype=np.int64))
-
-        def call(dx, dyf, dyq):
-            self.check(self.L.plhip_shuffle_channel_f32(self.h, dx, n, c, hw, int(group), dyf, dyq, float(calib_scale)), "shuffle_channel")
-        return self._two_outputs(call, x, x.shape, mode, calib_scale, misalign)
+        with self.scope() as s:
+            dx = s.put(x, off=4 * misalign)
+            yf, yq = s.out_by_mode(x.shape, mode, misalign)
+            self.check(self.L.plhip_shuffle_channel_f32(self.h, dx, n, c, hw, int(group), yf.ptr, yq.ptr, float(calib_scale)), "shuffle_channel")
+            return yf.get(), yq.get()
 
     def shuffle_unit(self, a, b, split_at, mode="f32", calib_scale=1.0, misalign=0):
         """plhip_shuffle_unit_f32: a, b [n, h, ...].  Returns (lo_f32 or None, hi_f32 or None, hi_i8 or None); mode names the
         outputs of the high part ("f32", "i8", "both")."""
-        assert mode in ("f32", "i8", "both")
         a = np.ascontiguousarray(a, np.float32)
         b = np.ascontiguousarray(b, np.float32)
         n, h = a.shape[:2]
         hw = int(np.prod(a.shape[2:], dtype=np.int64))
         rest = tuple(a.shape[2:])
-        hi_c = 2 * h - split_at
-        abuf, da = self._up_f32(a, misalign)
-        bbuf, db = self._up_f32(b, misalign)
-        lo = self._out_buf(n * split_at * hw, 4, misalign) if split_at > 0 else None
-        hf = self._out_buf(n * hi_c * hw, 4, misalign) if mode != "i8" else None
-        hq = self._out_buf(n * hi_c * hw, 1, misalign) if mode != "f32" else None
-        null = C.c_void_p()
-        self.check(self.L.plhip_shuffle_unit_f32(self.h, da, db, n, h, hw, int(split_at), lo[1] if lo else null, hf[1] if hf else null,
-                                                 hq[1] if hq else null, float(calib_scale)), "shuffle_unit")
-        r = (self.to_host(lo[1], (n, split_at) + rest, np.float32) if lo else None,
-             self.to_host(hf[1], (n, hi_c) + rest, np.float32) if hf else None,
-             self.to_host(hq[1], (n, hi_c) + rest, np.int8) if hq else None)
-        for p in (abuf, bbuf) + tuple(q[0] for q in (lo, hf, hq) if q):
-            self.free(p)
-        return r
+        with self.scope() as s:
+            da, db = s.put(a, off=4 * misalign), s.put(b, off=4 * misalign)
+            lo = s.out_opt(split_at > 0, (n, split_at) + rest, np.float32, 4 * misalign)
+            hf, hq = s.out_by_mode((n, 2 * h - split_at) + rest, mode, misalign)
+            self.check(self.L.plhip_shuffle_unit_f32(self.h, da, db, n, h, hw, int(split_at), lo.ptr, hf.ptr, hq.ptr, float(calib_scale)),
+                       "shuffle_unit")
+            return lo.get(), hf.get(), hq.get()
 
     # ---- bilinear_interp / nearest_interp / arg_max and interp -> arg_max in one launch (interp_ops.hip)
     def interp(self, x, out_hw, method="bilinear", align_corners=False, align_mode=1, mode="f32", calib_scale=1.0, misalign=0):
@@ -919,92 +878,74 @@ class Context:
         ih, iw = x.shape[-2:]
         oh, ow = (int(v) for v in out_hw)
         planes = int(np.prod(x.shape[:-2], dtype=np.int64))
-
-        def call(dx, dyf, dyq):
+        with self.scope() as s:
+            dx = s.put(x, off=4 * misalign)
+            yf, yq = s.out_by_mode(tuple(x.shape[:-2]) + (oh, ow), mode, misalign)
             self.check(self.L.plhip_interp_f32(self.h, dx, planes, ih, iw, oh, ow, INTERP_METHODS[method], int(align_corners),
-                                               int(align_mode), dyf, dyq, float(calib_scale)), "interp")
-        return self._two_outputs(call, x, tuple(x.shape[:-2]) + (oh, ow), mode, calib_scale, misalign)
+                                               int(align_mode), yf.ptr, yq.ptr, float(calib_scale)), "interp")
+            return yf.get(), yq.get()
 
     def arg_max(self, x, axis, dtype=-1, keepdims=False, misalign=0):
         """plhip_arg_max_f32 along `axis` of an fp32 array; dtype as ArgmaxParam's (-1 / 3 int64, 2 int32)."""
         x = np.ascontiguousarray(x, np.float32)
-        axis = axis + x.ndim if axis < 0 else axis
-        outer = int(np.prod(x.shape[:axis], dtype=np.int64))
-        inner = int(np.prod(x.shape[axis + 1:], dtype=np.int64))
-        np_t = ARGMAX_DTYPES[dtype]
-        esz = np.dtype(np_t).itemsize
-        xbuf, dx = self._up_f32(x, misalign)
-        ybuf, dy = self._out_buf(outer * inner, esz, misalign)
-        try:
-            self.check(self.L.plhip_arg_max_f32(self.h, dx, outer, x.shape[axis], inner, dy, int(dtype)), "arg_max")
-            shape = x.shape[:axis] + ((1,) if keepdims else ()) + x.shape[axis + 1:]
-            return self.to_host(dy, shape, np_t)
-        finally:
-            self.free(xbuf), self.free(ybuf)
+        axis, outer, inner = _outer_inner(x.shape, axis)
+        np_t = np.dtype(ARGMAX_DTYPES[dtype])
+        with self.scope() as s:
+            dx = s.put(x, off=4 * misalign)
+            y = s.out(x.shape[:axis] + ((1,) if keepdims else ()) + x.shape[axis + 1:], np_t, np_t.itemsize * misalign)
+            self.check(self.L.plhip_arg_max_f32(self.h, dx, outer, x.shape[axis], inner, y.ptr, int(dtype)), "arg_max")
+            return y.get()
 
     def interp_argmax(self, x, out_hw, method="bilinear", align_corners=False, align_mode=1, dtype=-1, misalign=0):
         """plhip_interp_argmax_f32: x [n, c, h, w] fp32 -> labels [n, oh, ow] of the resampled tensor, which is never written."""
         x = np.ascontiguousarray(x, np.float32)
         n, c, ih, iw = x.shape
         oh, ow = (int(v) for v in out_hw)
-        np_t = ARGMAX_DTYPES[dtype]
-        xbuf, dx = self._up_f32(x, misalign)
-        ybuf, dy = self._out_buf(n * oh * ow, np.dtype(np_t).itemsize, misalign)
-        try:
+        np_t = np.dtype(ARGMAX_DTYPES[dtype])
+        with self.scope() as s:
+            dx = s.put(x, off=4 * misalign)
+            y = s.out((n, oh, ow), np_t, np_t.itemsize * misalign)
             self.check(self.L.plhip_interp_argmax_f32(self.h, dx, n, c, ih, iw, oh, ow, INTERP_METHODS[method], int(align_corners),
-                                                      int(align_mode), dy, int(dtype)), "interp_argmax")
-            return self.to_host(dy, (n, oh, ow), np_t)
-        finally:
-            self.free(xbuf), self.free(ybuf)
+                                                      int(align_mode), y.ptr, int(dtype)), "interp_argmax")
+            return y.get()
 
     # ---- detection heads: transpose, the one-launch head join, box_coder, multiclass_nms (transpose_ops.hip, detection_ops.hip)
     def transpose(self, x, perm, misalign=0):
         """plhip_transpose_f32: np.transpose(x, perm) of an fp32 array of rank 2 .. 4, the bits moved."""
         x = np.ascontiguousarray(x, np.float32)
-        xbuf, dx = self._up_f32(x, misalign)
-        ybuf, dy = self._out_buf(x.size, 4, misalign)
-        try:
-            dims = (C.c_int64 * x.ndim)(*x.shape)
-            pm = (C.c_int * len(perm))(*[int(v) for v in perm])
-            self.check(self.L.plhip_transpose_f32(self.h, dx, dims, pm, x.ndim, dy), "transpose")
-            return self.to_host(dy, tuple(x.shape[k] for k in perm), np.float32)
-        finally:
-            self.free(xbuf), self.free(ybuf)
+        dims = (C.c_int64 * x.ndim)(*x.shape)
+        pm = (C.c_int * len(perm))(*[int(v) for v in perm])
+        with self.scope() as s:
+            dx = s.put(x, off=4 * misalign)
+            y = s.out(tuple(x.shape[k] for k in perm), np.float32, 4 * misalign)
+            self.check(self.L.plhip_transpose_f32(self.h, dx, dims, pm, x.ndim, y.ptr), "transpose")
+            return y.get()
 
     def concat_nhwc(self, xs, misalign=0):
         """plhip_concat_nhwc_f32 of NCHW fp32 arrays [n, c_i, h_i, w_i]: returns [n, sum c_i * h_i * w_i]."""
         xs = [np.ascontiguousarray(x, np.float32) for x in xs]
         n = xs[0].shape[0]
-        ups = [self._up_f32(x, misalign) for x in xs]
-        total = sum(x[0].size for x in xs)
-        ybuf, dy = self._out_buf(n * total, 4, misalign)
-        try:
-            ptrs = (C.c_void_p * len(xs))(*[d for _b, d in ups])
-            ch = (C.c_int64 * len(xs))(*[x.shape[1] for x in xs])
-            hw = (C.c_int64 * len(xs))(*[x.shape[2] * x.shape[3] for x in xs])
-            self.check(self.L.plhip_concat_nhwc_f32(self.h, ptrs, ch, hw, len(xs), n, dy), "concat_nhwc")
-            return self.to_host(dy, (n, total), np.float32)
-        finally:
-            for b in [ybuf] + [b for b, _d in ups]:
-                self.free(b)
+        ch = (C.c_int64 * len(xs))(*[x.shape[1] for x in xs])
+        hw = (C.c_int64 * len(xs))(*[x.shape[2] * x.shape[3] for x in xs])
+        with self.scope() as s:
+            ptrs = (C.c_void_p * len(xs))(*[s.put(x, off=4 * misalign) for x in xs])
+            y = s.out((n, sum(x[0].size for x in xs)), np.float32, 4 * misalign)
+            self.check(self.L.plhip_concat_nhwc_f32(self.h, ptrs, ch, hw, len(xs), n, y.ptr), "concat_nhwc")
+            return y.get()
 
     def box_coder_decode(self, prior, target, prior_var=None, variance=None, axis=0, normalized=True, misalign=0):
         """plhip_box_coder_decode_f32: target [rows, cols, 4]; prior (and prior_var) [cols, 4] with axis 0, [rows, 4] with axis 1;
         variance: the 4-float attribute, read when prior_var is None."""
         target = np.ascontiguousarray(target, np.float32)
         rows, cols = target.shape[:2]
-        bufs = [self._up_f32(prior, misalign), self._up_f32(target, misalign)]
-        if prior_var is not None:
-            bufs.append(self._up_f32(prior_var, misalign))
-        ybuf, dy = self._out_buf(target.size, 4, misalign)
-        try:
-            v4 = (C.c_float * 4)(*[float(v) for v in variance]) if variance is not None else None
-            self.check(self.L.plhip_box_coder_decode_f32(self.h, bufs[0][1], bufs[2][1] if prior_var is not None else None, v4,
-                                                         bufs[1][1], rows, cols, int(axis), int(bool(normalized)), dy), "box_coder_decode")
-            return self.to_host(dy, target.shape, np.float32)
-        finally:
-            for b in [ybuf] + [b for b, _d in bufs]:
-                self.free(b)
+        v4 = (C.c_float * 4)(*[float(v) for v in variance]) if variance is not None else None
+        with self.scope() as s:
+            dp, dt = s.put(prior, np.float32, 4 * misalign), s.put(target, off=4 * misalign)
+            dv = s.put(prior_var, np.float32, 4 * misalign) if prior_var is not None else None
+            y = s.out(target.shape, np.float32, 4 * misalign)
+            self.check(self.L.plhip_box_coder_decode_f32(self.h, dp, dv, v4, dt, rows, cols, int(axis), int(bool(normalized)), y.ptr),
+                       "box_coder_decode")
+            return y.get()
 
     # ---- YOLOv3 heads (yolo_ops.hip)
     def yolo_box_launch(self, dx, dimg, shape, anchors, class_num, conf_thresh, downsample_ratio, clip_bbox, scale_x_y, dboxes, dscores):
@@ -1027,28 +968,19 @@ class Context:
         return self.L.plhip_yolo_head_f32(self.h, ptrs, hs, ws, ap, lens, ratios, k, dimg, shapes[0][0] if k else 1, int(class_num), float(conf_thresh),
                                           int(bool(clip_bbox)), float(scale_x_y), dboxes, dscores)
 
-    def _filled(self, count, misalign, fill=0xFF):
-        """An fp32 output of `count` elements behind `misalign` elements of slack, every byte `fill`: an unwritten element shows."""
-        buf, d = self._out_buf(count, 4, misalign)
-        self.check(self.L.plhip_memset(self.h, buf, fill, 4 * (count + misalign) + 8), "memset")
-        return buf, d
-
     def yolo_box(self, x, img_size, anchors, class_num, conf_thresh, downsample_ratio, clip_bbox=True, scale_x_y=1.0, misalign=0):
         """plhip_yolo_box_f32: x [n, an * (5 + class_num), h, w] fp32, img_size [n, 2] int32 (height, width).  Returns
         (boxes [n, an * h * w, 4], scores [n, an * h * w, class_num]); the outputs hold 0xFF bytes before the call."""
         x = np.ascontiguousarray(x, np.float32)
         n, _ch, h, w = x.shape
         p = (len(anchors) // 2) * h * w
-        xbuf, dx = self._up_f32(x, misalign)
-        dimg = self.to_device(np.ascontiguousarray(img_size, np.int32))
-        bbuf, db = self._filled(n * p * 4, misalign)
-        sbuf, ds = self._filled(n * p * class_num, misalign)
-        try:
-            self.check(self.yolo_box_launch(dx, dimg, x.shape, anchors, class_num, conf_thresh, downsample_ratio, clip_bbox, scale_x_y, db, ds), "yolo_box")
-            return self.to_host(db, (n, p, 4), np.float32), self.to_host(ds, (n, p, class_num), np.float32)
-        finally:
-            for b in (xbuf, dimg, bbuf, sbuf):
-                self.free(b)
+        with self.scope() as s:
+            dx, dimg = s.put(x, off=4 * misalign), s.put(img_size, np.int32)
+            boxes = s.out((n, p, 4), np.float32, 4 * misalign, fill=0xFF)
+            scores = s.out((n, p, class_num), np.float32, 4 * misalign, fill=0xFF)
+            self.check(self.yolo_box_launch(dx, dimg, x.shape, anchors, class_num, conf_thresh, downsample_ratio, clip_bbox, scale_x_y,
+                                            boxes.ptr, scores.ptr), "yolo_box")
+            return boxes.get(), scores.get()
 
     def yolo_head(self, xs, img_size, anchors, class_num, conf_thresh, downsample_ratios, clip_bbox=True, scale_x_y=1.0, misalign=0):
         """plhip_yolo_head_f32 of the feature maps xs[i] with anchors[i] and downsample_ratios[i].  Returns (boxes [n, P, 4],
@@ -1056,17 +988,13 @@ class Context:
         xs = [np.ascontiguousarray(x, np.float32) for x in xs]
         n = xs[0].shape[0]
         p = sum((len(a) // 2) * x.shape[2] * x.shape[3] for a, x in zip(anchors, xs))
-        ups = [self._up_f32(x, misalign) for x in xs]
-        dimg = self.to_device(np.ascontiguousarray(img_size, np.int32))
-        bbuf, db = self._filled(n * p * 4, misalign)
-        sbuf, ds = self._filled(n * p * class_num, misalign)
-        try:
-            self.check(self.yolo_head_launch([d for _b, d in ups], dimg, [x.shape for x in xs], anchors, class_num, conf_thresh,
-                                             downsample_ratios, clip_bbox, scale_x_y, db, ds), "yolo_head")
-            return self.to_host(db, (n, p, 4), np.float32), self.to_host(ds, (n, class_num, p), np.float32)
-        finally:
-            for b in [dimg, bbuf, sbuf] + [b for b, _d in ups]:
-                self.free(b)
+        with self.scope() as s:
+            dxs, dimg = [s.put(x, off=4 * misalign) for x in xs], s.put(img_size, np.int32)
+            boxes = s.out((n, p, 4), np.float32, 4 * misalign, fill=0xFF)
+            scores = s.out((n, class_num, p), np.float32, 4 * misalign, fill=0xFF)
+            self.check(self.yolo_head_launch(dxs, dimg, [x.shape for x in xs], anchors, class_num, conf_thresh, downsample_ratios,
+                                             clip_bbox, scale_x_y, boxes.ptr, scores.ptr), "yolo_head")
+            return boxes.get(), scores.get()
 
     def multiclass_nms(self, boxes, scores, desc, with_index=True, misalign=0):
         """plhip_multiclass_nms_f32: boxes [N, P, 4], scores in the layout desc's strides name.  Returns the padded device outputs
@@ -1075,16 +1003,11 @@ class Context:
         nbytes = self.L.plhip_multiclass_nms_workspace_bytes(C.byref(desc))
         if nbytes == 0:
             raise PlhipError("multiclass_nms refused: %s" % self.L.plhip_last_error(None).decode())
-        bufs = [self._up_f32(boxes, misalign), self._up_f32(scores, misalign)]
-        ws = self.malloc(nbytes)
-        obuf, do = self._out_buf(n * keep * 6, 4, 0)
-        ibuf, di = self._out_buf(n * keep, 4, 0)
-        cbuf, dc = self._out_buf(n, 4, 0)
-        try:
-            self.check(self.L.plhip_multiclass_nms_f32(self.h, bufs[0][1], bufs[1][1], C.byref(desc), ws, do, di if with_index else None,
-                                                       dc), "multiclass_nms")
-            return (self.to_host(do, (n, keep, 6), np.float32), self.to_host(dc, (n,), np.int32),
-                    self.to_host(di, (n, keep), np.int32) if with_index else None)
-        finally:
-            for b in [ws, obuf, ibuf, cbuf] + [b for b, _d in bufs]:
-                self.free(b)
+        with self.scope() as s:
+            db, dsc = s.put(boxes, np.float32, 4 * misalign), s.put(scores, np.float32, 4 * misalign)
+            ws = s.alloc(nbytes)
+            out, count = s.out((n, keep, 6), np.float32), s.out((n,), np.int32)
+            index = s.out_opt(with_index, (n, keep), np.int32)
+            self.check(self.L.plhip_multiclass_nms_f32(self.h, db, dsc, C.byref(desc), ws, out.ptr, index.ptr, count.ptr), "multiclass_nms")
+            return out.get(), count.get(), index.get()
+

@@ -103,46 +103,45 @@ def test_concat_calib_equals_the_oracle_and_the_two_calls(gpu_ctx, outer, extent
 def test_bad_arguments_are_refused_before_any_launch(gpu_ctx, pkg):
     L = pkg.capi.load()
     h = gpu_ctx.h
-    src = gpu_ctx.to_device(np.arange(1024, dtype=F32))
-    out_f, out_q = gpu_ctx.malloc(4096), gpu_ctx.malloc(4096)
-    gpu_ctx.check(L.plhip_memset(h, out_f, 0x55, 4096), "memset")
-    gpu_ctx.check(L.plhip_memset(h, out_q, 0x55, 4096), "memset")
-    null = C.c_void_p()
-    two = (C.c_void_p * 2)(src, src)
-    one_null = (C.c_void_p * 2)(src, null)
+    with gpu_ctx.scope() as s:
+        src = s.put(np.arange(1024, dtype=F32))
+        out_f, out_q = s.alloc(4096), s.alloc(4096)
+        gpu_ctx.check(L.plhip_memset(h, out_f, 0x55, 4096), "memset")
+        gpu_ctx.check(L.plhip_memset(h, out_q, 0x55, 4096), "memset")
+        null = C.c_void_p()
+        two = (C.c_void_p * 2)(src, src)
+        one_null = (C.c_void_p * 2)(src, null)
 
-    def ext(*v):
-        return (C.c_int64 * len(v))(*v)
+        def ext(*v):
+            return (C.c_int64 * len(v))(*v)
 
-    def refused(words, *args):
-        st = L.plhip_concat_calib_f32(h, *args)
-        msg = L.plhip_last_error(h).decode()
-        assert st < 0 and msg.startswith("plhip_concat_calib_f32: ") and words in msg, (st, msg, words)
+        def refused(words, *args):
+            st = L.plhip_concat_calib_f32(h, *args)
+            msg = L.plhip_last_error(h).decode()
+            assert st < 0 and msg.startswith("plhip_concat_calib_f32: ") and words in msg, (st, msg, words)
 
-    refused("count", two, ext(2, 3), 0, 1, 4, out_f, out_q, 1.0)
-    refused("count", two, ext(2, 3), -1, 1, 4, out_f, out_q, 1.0)
-    refused("null input", one_null, ext(2, 3), 2, 1, 4, out_f, out_q, 1.0)
-    refused("extent", two, ext(2, 0), 2, 1, 4, out_f, out_q, 1.0)
-    refused("extent", two, ext(-1, 3), 2, 1, 4, out_f, out_q, 1.0)
-    refused("outer and inner", two, ext(2, 3), 2, 0, 4, out_f, out_q, 1.0)
-    refused("outer and inner", two, ext(2, 3), 2, 1, 0, out_f, out_q, 1.0)
-    refused("y_i8", two, ext(2, 3), 2, 1, 4, out_f, null, 1.0)
-    for bad in (0.0, -1.0, float("inf"), float("nan")):
-        refused("calib_scale", two, ext(2, 3), 2, 1, 4, out_f, out_q, bad)
-    refused("2^40", two, ext(1 << 30, 1 << 30), 2, 1 << 30, 4, out_f, out_q, 1.0)
-    refused("null", None, ext(2, 3), 2, 1, 4, out_f, out_q, 1.0)
-    gpu_ctx.sync()
-    # nothing was launched: both outputs still hold the fill
-    assert (gpu_ctx.to_host(out_f, (4096,), np.uint8) == 0x55).all() and (gpu_ctx.to_host(out_q, (4096,), np.uint8) == 0x55).all()
-    # and the same call with good arguments, with and without the fp32 output, is taken
-    assert L.plhip_concat_calib_f32(h, two, ext(2, 3), 2, 1, 4, out_f, out_q, 1.0) == 0
-    assert L.plhip_concat_calib_f32(h, two, ext(2, 3), 2, 1, 4, null, out_q, 1.0) == 0
-    gpu_ctx.sync()
-    want = np.concatenate([np.arange(8), np.arange(12)]).astype(np.int8)
-    assert np.array_equal(gpu_ctx.to_host(out_q, (20,), np.int8), want)
-    assert np.array_equal(gpu_ctx.to_host(out_f, (20,), F32), want.astype(F32))
-    for p in (src, out_f, out_q):
-        gpu_ctx.free(p)
+        refused("count", two, ext(2, 3), 0, 1, 4, out_f, out_q, 1.0)
+        refused("count", two, ext(2, 3), -1, 1, 4, out_f, out_q, 1.0)
+        refused("null input", one_null, ext(2, 3), 2, 1, 4, out_f, out_q, 1.0)
+        refused("extent", two, ext(2, 0), 2, 1, 4, out_f, out_q, 1.0)
+        refused("extent", two, ext(-1, 3), 2, 1, 4, out_f, out_q, 1.0)
+        refused("outer and inner", two, ext(2, 3), 2, 0, 4, out_f, out_q, 1.0)
+        refused("outer and inner", two, ext(2, 3), 2, 1, 0, out_f, out_q, 1.0)
+        refused("y_i8", two, ext(2, 3), 2, 1, 4, out_f, null, 1.0)
+        for bad in (0.0, -1.0, float("inf"), float("nan")):
+            refused("calib_scale", two, ext(2, 3), 2, 1, 4, out_f, out_q, bad)
+        refused("2^40", two, ext(1 << 30, 1 << 30), 2, 1 << 30, 4, out_f, out_q, 1.0)
+        refused("null", None, ext(2, 3), 2, 1, 4, out_f, out_q, 1.0)
+        gpu_ctx.sync()
+        # nothing was launched: both outputs still hold the fill
+        assert (gpu_ctx.to_host(out_f, (4096,), np.uint8) == 0x55).all() and (gpu_ctx.to_host(out_q, (4096,), np.uint8) == 0x55).all()
+        # and the same call with good arguments, with and without the fp32 output, is taken
+        assert L.plhip_concat_calib_f32(h, two, ext(2, 3), 2, 1, 4, out_f, out_q, 1.0) == 0
+        assert L.plhip_concat_calib_f32(h, two, ext(2, 3), 2, 1, 4, null, out_q, 1.0) == 0
+        gpu_ctx.sync()
+        want = np.concatenate([np.arange(8), np.arange(12)]).astype(np.int8)
+        assert np.array_equal(gpu_ctx.to_host(out_q, (20,), np.int8), want)
+        assert np.array_equal(gpu_ctx.to_host(out_f, (20,), F32), want.astype(F32))
 
 
 def test_kernel_class_through_the_factory(lite):

@@ -57,19 +57,19 @@ def test_transpose_shapes_aligned_and_not(gpu_ctx, shape, perm):
 
 def test_transpose_refusals(gpu_ctx):
     L = gpu_ctx.L
-    buf = gpu_ctx.malloc(64)
+    with gpu_ctx.scope() as s:
+        buf = s.alloc(64)
 
-    def call(dims, perm, x=buf, y=buf, rank=None):
-        st = L.plhip_transpose_f32(gpu_ctx.h, x, (C.c_int64 * len(dims))(*dims), (C.c_int * len(perm))(*perm), len(dims) if rank is None else rank, y)
-        return st, L.plhip_last_error(gpu_ctx.h).decode()
+        def call(dims, perm, x=buf, y=buf, rank=None):
+            st = L.plhip_transpose_f32(gpu_ctx.h, x, (C.c_int64 * len(dims))(*dims), (C.c_int * len(perm))(*perm), len(dims) if rank is None else rank, y)
+            return st, L.plhip_last_error(gpu_ctx.h).decode()
 
-    for args, status, part in ((((2, 2), (0, 0)), -1, "permutation"), (((2, 2), (0, 2)), -1, "permutation"), (((2, 0), (1, 0)), -1, "at least 1"),
-                               (((2, 2, 2, 2, 2), (0, 1, 2, 3, 4)), -3, "rank"), (((4,), (0,)), -3, "rank"),
-                               (((1 << 20, 1 << 20, 2), (0, 1, 2)), -3, "2^40")):
-        st, msg = call(*args)
-        assert st == status and msg.startswith("plhip_transpose_f32: ") and part in msg, (args, st, msg)
-    assert call((2, 2), (1, 0), x=None)[0] == -1 and call((2, 2), (1, 0), y=None)[0] == -1
-    gpu_ctx.free(buf)
+        for args, status, part in ((((2, 2), (0, 0)), -1, "permutation"), (((2, 2), (0, 2)), -1, "permutation"), (((2, 0), (1, 0)), -1, "at least 1"),
+                                   (((2, 2, 2, 2, 2), (0, 1, 2, 3, 4)), -3, "rank"), (((4,), (0,)), -3, "rank"),
+                                   (((1 << 20, 1 << 20, 2), (0, 1, 2)), -3, "2^40")):
+            st, msg = call(*args)
+            assert st == status and msg.startswith("plhip_transpose_f32: ") and part in msg, (args, st, msg)
+        assert call((2, 2), (1, 0), x=None)[0] == -1 and call((2, 2), (1, 0), y=None)[0] == -1
 
 
 # ------------------------------------------------------------------ concat_nhwc
@@ -95,13 +95,13 @@ def test_concat_nhwc_equals_transpose_reshape_concat(gpu_ctx, k, parts):
 
 def test_concat_nhwc_refusals(gpu_ctx):
     L = gpu_ctx.L
-    buf = gpu_ctx.malloc(64)
-    one = (C.c_int64 * 1)(2)
-    ptr = (C.c_void_p * 1)(buf)
-    for args, part in (((ptr, one, one, 0, 1, buf), "count"), ((ptr, one, one, 1, 0, buf), "n must"), ((ptr, (C.c_int64 * 1)(0), one, 1, 1, buf), "extent"),
-                       (((C.c_void_p * 1)(None), one, one, 1, 1, buf), "null input"), ((ptr, one, one, 1, 1, None), "null ctx")):
-        assert L.plhip_concat_nhwc_f32(gpu_ctx.h, *args) == -1 and part in L.plhip_last_error(gpu_ctx.h).decode(), part
-    gpu_ctx.free(buf)
+    with gpu_ctx.scope() as s:
+        buf = s.alloc(64)
+        one = (C.c_int64 * 1)(2)
+        ptr = (C.c_void_p * 1)(buf)
+        for args, part in (((ptr, one, one, 0, 1, buf), "count"), ((ptr, one, one, 1, 0, buf), "n must"), ((ptr, (C.c_int64 * 1)(0), one, 1, 1, buf), "extent"),
+                           (((C.c_void_p * 1)(None), one, one, 1, 1, buf), "null input"), ((ptr, one, one, 1, 1, None), "null ctx")):
+            assert L.plhip_concat_nhwc_f32(gpu_ctx.h, *args) == -1 and part in L.plhip_last_error(gpu_ctx.h).decode(), part
 
 
 # ------------------------------------------------------------------ box_coder
@@ -132,11 +132,11 @@ def test_box_coder_decode(gpu_ctx, cols):
 
 def test_box_coder_refusals(gpu_ctx):
     L = gpu_ctx.L
-    buf = gpu_ctx.malloc(64)
-    for args, part in (((buf, None, None, buf, 0, 1, 0, 1, buf), "at least 1"), ((buf, None, None, buf, 1, 1, 2, 1, buf), "axis"),
-                       ((None, None, None, buf, 1, 1, 0, 1, buf), "null ctx"), ((buf, None, None, buf, 1, 1, 0, 1, None), "null ctx")):
-        assert L.plhip_box_coder_decode_f32(gpu_ctx.h, *args) == -1 and part in L.plhip_last_error(gpu_ctx.h).decode(), part
-    gpu_ctx.free(buf)
+    with gpu_ctx.scope() as s:
+        buf = s.alloc(64)
+        for args, part in (((buf, None, None, buf, 0, 1, 0, 1, buf), "at least 1"), ((buf, None, None, buf, 1, 1, 2, 1, buf), "axis"),
+                           ((None, None, None, buf, 1, 1, 0, 1, buf), "null ctx"), ((buf, None, None, buf, 1, 1, 0, 1, None), "null ctx")):
+            assert L.plhip_box_coder_decode_f32(gpu_ctx.h, *args) == -1 and part in L.plhip_last_error(gpu_ctx.h).decode(), part
 
 
 # ------------------------------------------------------------------ multiclass_nms
@@ -213,29 +213,28 @@ def test_nms_largest_envelope(gpu_ctx, pkg):
 
 def test_nms_refusals_launch_nothing(gpu_ctx, pkg):
     capi, L = pkg.capi, gpu_ctx.L
-    boxes = gpu_ctx.to_device(np.zeros((1, 8, 4), F32))
-    scores = gpu_ctx.to_device(np.ones((1, 2, 8), F32))
-    ws = gpu_ctx.malloc(4096)
-    sentinel = np.full(64, 7.0, F32)
-    out = gpu_ctx.to_device(sentinel)
-    count = gpu_ctx.to_device(np.full(4, 7, np.int32))
-    good = dict(background_label=0, score_threshold=0.01, nms_top_k=4, nms_threshold=0.45, keep_top_k=4)
+    with gpu_ctx.scope() as sc:
+        boxes = sc.put(np.zeros((1, 8, 4), F32))
+        scores = sc.put(np.ones((1, 2, 8), F32))
+        ws = sc.alloc(4096)
+        sentinel = np.full(64, 7.0, F32)
+        out = sc.put(sentinel)
+        count = sc.put(np.full(4, 7, np.int32))
+        good = dict(background_label=0, score_threshold=0.01, nms_top_k=4, nms_threshold=0.45, keep_top_k=4)
 
-    def call(d, b=boxes, s=scores, w=ws, o=out, c=count):
-        st = L.plhip_multiclass_nms_f32(gpu_ctx.h, b, s, C.byref(d) if d is not None else None, w, o, None, c)
-        return st, L.plhip_last_error(gpu_ctx.h).decode()
+        def call(d, b=boxes, s=scores, w=ws, o=out, c=count):
+            st = L.plhip_multiclass_nms_f32(gpu_ctx.h, b, s, C.byref(d) if d is not None else None, w, o, None, c)
+            return st, L.plhip_last_error(gpu_ctx.h).decode()
 
-    for d, status, part in ((capi.nms_desc(1, 2, 8, **dict(good, nms_eta=0.9)), -3, "nms_eta"), (capi.nms_desc(1, 2, 8, **dict(good, keep_top_k=-1)), -1, "keep_top_k"),
-                            (capi.nms_desc(1, 2, 16385, **good), -3, "16384 priors"), (capi.nms_desc(1, 2, 5000, **dict(good, nms_top_k=-1)), -3, "4096"),
-                            (capi.nms_desc(1, 9000, 8, **dict(good, nms_top_k=-1, keep_top_k=8)), -3, "above 16384"), (capi.nms_desc(0, 2, 8, **good), -1, "at least 1")):
-        st, msg = call(d)
-        assert st == status and msg.startswith("plhip_multiclass_nms_f32: ") and part in msg, (st, msg)
-    ok = capi.nms_desc(1, 2, 8, **good)
-    assert call(None)[0] == -1 and call(ok, b=None)[0] == -1 and call(ok, s=None)[0] == -1 and call(ok, w=None)[0] == -1
-    assert call(ok, w=C.c_void_p(ws.value + 4))[0] == -1 and call(ok, o=None)[0] == -1 and call(ok, c=None)[0] == -1
-    gpu_ctx.sync()
-    assert np.array_equal(gpu_ctx.to_host(out, (64,), F32), sentinel) and gpu_ctx.to_host(count, (4,), np.int32).tolist() == [7] * 4
-    assert call(ok)[0] == 0  # and the accepted call writes: one box of eight coincident ones survives
-    assert gpu_ctx.to_host(count, (1,), np.int32).tolist() == [1]
-    for b in (boxes, scores, ws, out, count):
-        gpu_ctx.free(b)
+        for d, status, part in ((capi.nms_desc(1, 2, 8, **dict(good, nms_eta=0.9)), -3, "nms_eta"), (capi.nms_desc(1, 2, 8, **dict(good, keep_top_k=-1)), -1, "keep_top_k"),
+                                (capi.nms_desc(1, 2, 16385, **good), -3, "16384 priors"), (capi.nms_desc(1, 2, 5000, **dict(good, nms_top_k=-1)), -3, "4096"),
+                                (capi.nms_desc(1, 9000, 8, **dict(good, nms_top_k=-1, keep_top_k=8)), -3, "above 16384"), (capi.nms_desc(0, 2, 8, **good), -1, "at least 1")):
+            st, msg = call(d)
+            assert st == status and msg.startswith("plhip_multiclass_nms_f32: ") and part in msg, (st, msg)
+        ok = capi.nms_desc(1, 2, 8, **good)
+        assert call(None)[0] == -1 and call(ok, b=None)[0] == -1 and call(ok, s=None)[0] == -1 and call(ok, w=None)[0] == -1
+        assert call(ok, w=C.c_void_p(ws.value + 4))[0] == -1 and call(ok, o=None)[0] == -1 and call(ok, c=None)[0] == -1
+        gpu_ctx.sync()
+        assert np.array_equal(gpu_ctx.to_host(out, (64,), F32), sentinel) and gpu_ctx.to_host(count, (4,), np.int32).tolist() == [7] * 4
+        assert call(ok)[0] == 0  # and the accepted call writes: one box of eight coincident ones survives
+        assert gpu_ctx.to_host(count, (1,), np.int32).tolist() == [1]

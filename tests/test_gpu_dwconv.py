@@ -135,20 +135,19 @@ def test_unsupported_shapes_write_nothing(gpu_ctx, pkg):
         oh, ow = capi.out_hw(d)
         cnt = n * m * oh * ow
         sentinel = np.full(cnt * 4, 0x5a, np.uint8)
-        dy, dq = gpu_ctx.to_device(sentinel), gpu_ctx.to_device(sentinel[:cnt])
-        kx = gpu_ctx.malloc(n * d.cin * h * h + 64)
-        kw = gpu_ctx.malloc(d.cin * 25 + 64)
-        ks = gpu_ctx.malloc(4096 * 4)
-        kp = gpu_ctx.malloc(1 << 16)
-        dr = gpu_ctx.malloc(cnt * 4) if tail else ctypes.c_void_p()
-        st = gpu_ctx.L.plhip_dw_conv1x1_fused_int8(gpu_ctx.h, ctypes.byref(d), kx, kw, ks, None, m, kp, ks, None, 0, 0.0, dy, out,
-                                                   dr, 0, dq if tail else None, 1.0)
-        assert st == -3, st
-        gpu_ctx.sync()
-        assert np.array_equal(gpu_ctx.to_host(dy, sentinel.shape, np.uint8), sentinel)
-        assert np.array_equal(gpu_ctx.to_host(dq, (cnt,), np.uint8), sentinel[:cnt])
-        for p_ in [dy, dq, kx, kw, ks, kp] + ([dr] if tail else []):
-            gpu_ctx.free(p_)
+        with gpu_ctx.scope() as s:
+            dy, dq = s.put(sentinel), s.put(sentinel[:cnt])
+            kx = s.alloc(n * d.cin * h * h + 64)
+            kw = s.alloc(d.cin * 25 + 64)
+            ks = s.alloc(4096 * 4)
+            kp = s.alloc(1 << 16)
+            dr = s.alloc(cnt * 4) if tail else ctypes.c_void_p()
+            st = gpu_ctx.L.plhip_dw_conv1x1_fused_int8(gpu_ctx.h, ctypes.byref(d), kx, kw, ks, None, m, kp, ks, None, 0, 0.0, dy, out,
+                                                       dr, 0, dq if tail else None, 1.0)
+            assert st == -3, st
+            gpu_ctx.sync()
+            assert np.array_equal(gpu_ctx.to_host(dy, sentinel.shape, np.uint8), sentinel)
+            assert np.array_equal(gpu_ctx.to_host(dq, (cnt,), np.uint8), sentinel[:cnt])
 
 
 def _run_graph(lite, wl, net, img):

@@ -155,12 +155,12 @@ def test_refusals_return_a_status(gpu_ctx, pkg):
             gpu_ctx.image_resize(capi.frame_desc(1, h, w, capi.IMG_GRAY), np.zeros((1, h, w, 1), np.uint8), 4, 4)
     with pytest.raises(capi.PlhipError):  # the image's format must be BGR for an NV frame
         gpu_ctx.frame_to_tensor(capi.frame_desc(1, 480, 640, capi.IMG_NV12), capi.image_desc(1, 224, 224, capi.IMG_RGB, MEANS, SCALES), z)
-    d = gpu_ctx.to_device(z[:, :1])  # image_to_tensor keeps refusing NV (before it launches anything: d is never touched)
-    for fmt in (capi.IMG_NV12, capi.IMG_NV21):
-        nv_img = capi.image_desc(1, 480, 640, fmt, MEANS, SCALES)
-        assert gpu_ctx.L.plhip_image_to_tensor_f32(gpu_ctx.h, ctypes.byref(nv_img), d, d) == -1
-        assert gpu_ctx.L.plhip_image_to_tensor_i8(gpu_ctx.h, ctypes.byref(nv_img), d, d, 0.01) == -1
-    gpu_ctx.free(d)
+    with gpu_ctx.scope() as s:
+        d = s.put(z[:, :1])  # image_to_tensor keeps refusing NV (before it launches anything: d is never touched)
+        for fmt in (capi.IMG_NV12, capi.IMG_NV21):
+            nv_img = capi.image_desc(1, 480, 640, fmt, MEANS, SCALES)
+            assert gpu_ctx.L.plhip_image_to_tensor_f32(gpu_ctx.h, ctypes.byref(nv_img), d, d) == -1
+            assert gpu_ctx.L.plhip_image_to_tensor_i8(gpu_ctx.h, ctypes.byref(nv_img), d, d, 0.01) == -1
     gpu_ctx.sync()
 
 

@@ -136,7 +136,7 @@ def test_fused_unsupported_shapes_are_reported(gpu_ctx, pkg):
     import ctypes as C
     capi = pkg.capi
     d = capi.conv_desc(1, 8, 16, 16, 8, 5, 5, (2, 2, 2, 2), (1, 1), (1, 1), 8)  # 5x5 depthwise: not fused
-    z = gpu_ctx.malloc(1 << 16)
-    st = gpu_ctx.L.plhip_dwpw_fused_int8(gpu_ctx.h, C.byref(d), z, z, z, None, 8, z, z, None, 0, 0.0, z, capi.OUT_I8)
-    assert st == -3
-    gpu_ctx.free(z)
+    with gpu_ctx.scope() as s:
+        z = s.alloc(1 << 16)
+        st = gpu_ctx.L.plhip_dwpw_fused_int8(gpu_ctx.h, C.byref(d), z, z, z, None, 8, z, z, None, 0, 0.0, z, capi.OUT_I8)
+        assert st == -3

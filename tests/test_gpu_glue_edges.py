@@ -20,44 +20,32 @@ GUARD, POISON = 64, 0xA5
 
 
 class _Dev:
-    """Device buffers placed GUARD + off bytes into their allocations (allocations are at least 16-byte aligned, GUARD is a
-    multiple of 16: `off` is the base's misalignment)."""
+    """The buffers of one device scope, each with GUARD bytes on either side, `off` bytes past a 16-byte boundary."""
 
     def __init__(self, ctx):
-        self.ctx, self.allocs = ctx, []
-
-    def _alloc(self, nbytes, off, fill):
-        total = GUARD + off + nbytes + GUARD
-        base = self.ctx.malloc(total)
-        assert base.value % 16 == 0
-        self.allocs.append(base)
-        self.ctx.check(self.ctx.L.plhip_memset(self.ctx.h, base, fill, total), "memset")
-        return base, total, C.c_void_p(base.value + GUARD + off)
+        self.ctx, self.scope = ctx, ctx.scope()
 
     def put(self, arr, off=0):
         """An input: zeroed margins, the array `off` bytes past a 16-byte boundary."""
         arr = np.ascontiguousarray(arr)
-        _, _, p = self._alloc(arr.nbytes, off, 0)
+        p = self.scope.out(arr.shape, arr.dtype, off, fill=0, guard=GUARD).ptr
         self.ctx.check(self.ctx.L.plhip_memcpy_h2d(self.ctx.h, p, arr.ctypes.data_as(C.c_void_p), arr.nbytes), "h2d")
         return p
 
     def out(self, shape, dtype, off=0):
-        """A guarded output: (pointer, fetch); fetch() reads the whole allocation back, checks both bands and returns the array."""
-        nbytes = int(np.prod(shape)) * np.dtype(dtype).itemsize
-        base, total, p = self._alloc(nbytes, off, POISON)
+        """A guarded output: (pointer, fetch); fetch() reads the margins back, checks both bands and returns the array."""
+        o = self.scope.out(shape, dtype, off, fill=POISON, guard=GUARD)
 
         def fetch(what=""):
-            raw = self.ctx.to_host(base, (total,), np.uint8)
-            lo, hi = raw[:GUARD + off], raw[GUARD + off + nbytes:]
+            around = o.margins()
+            lo, hi = around[:GUARD + off], around[GUARD + off:]
             assert (lo == POISON).all(), "%s: %d bytes written before the output" % (what, (lo != POISON).sum())
             assert (hi == POISON).all(), "%s: %d bytes written past the output" % (what, (hi != POISON).sum())
-            return raw[GUARD + off:GUARD + off + nbytes].view(dtype).reshape(shape).copy()
-        return p, fetch
+            return o.get()
+        return o.ptr, fetch
 
     def release(self):
-        for p in self.allocs:
-            self.ctx.free(p)
-        self.allocs = []
+        self.scope.release()
 
 
 @pytest.fixture
@@ -401,19 +389,18 @@ def test_fc_dispatch_reaches_all_three_kernels(dev, pkg, plref):
     assert G.fc_lds_bytes(4096) == G.FC_LDS_BOUND
     for i, (m, k, n, off) in enumerate(G.FC_CASES):
         x, w, sc, sc8, bias = G.fc_inputs(m, k, n, k + n)
-        dw = ctx.to_device(w)
-        packed = ctx.malloc(ctx.L.plhip_fc_packed_weight_bytes(k, n))
-        ctx.check(ctx.L.plhip_pack_fc_weights(ctx.h, k, n, dw, packed), "pack_fc")
-        what = "fc %s m %d k %d n %d x+%d" % (routes[i], m, k, n, off)
-        y8, acc = plref.fc(x, w, bias, sc8, True, True)
-        assert np.array_equal(_fc(dev, packed, x, off, None, None, 0, capi.OUT_I32, n, what), acc), what + ": int32 accumulators differ"
-        _same_i8(_fc(dev, packed, x, off, sc8, bias, 1, capi.OUT_I8, n, what), y8, what + " int8 out")
-        for relu in (0, 1):
-            for route in (0, 1):
-                yf, _ = plref.fc(x, w, bias, sc, relu, False, route=route)
-                got = _fc(dev, packed, x, off, sc, bias, relu | (2 * route), capi.OUT_F32, n, what)
-                _same_bits(got, yf, what + " fp32 out relu %d route %d" % (relu, route))
-        # no bias
-        yf, _ = plref.fc(x, w, None, sc, 0, False, route=0)
-        _same_bits(_fc(dev, packed, x, off, sc, None, 0, capi.OUT_F32, n, what), yf, what + " fp32 out, no bias")
-        ctx.free(dw), ctx.free(packed)
+        with ctx.scope() as s:
+            packed = s.alloc(ctx.L.plhip_fc_packed_weight_bytes(k, n))
+            ctx.check(ctx.L.plhip_pack_fc_weights(ctx.h, k, n, s.put(w), packed), "pack_fc")
+            what = "fc %s m %d k %d n %d x+%d" % (routes[i], m, k, n, off)
+            y8, acc = plref.fc(x, w, bias, sc8, True, True)
+            assert np.array_equal(_fc(dev, packed, x, off, None, None, 0, capi.OUT_I32, n, what), acc), what + ": int32 accumulators differ"
+            _same_i8(_fc(dev, packed, x, off, sc8, bias, 1, capi.OUT_I8, n, what), y8, what + " int8 out")
+            for relu in (0, 1):
+                for route in (0, 1):
+                    yf, _ = plref.fc(x, w, bias, sc, relu, False, route=route)
+                    got = _fc(dev, packed, x, off, sc, bias, relu | (2 * route), capi.OUT_F32, n, what)
+                    _same_bits(got, yf, what + " fp32 out relu %d route %d" % (relu, route))
+            # no bias
+            yf, _ = plref.fc(x, w, None, sc, 0, False, route=0)
+            _same_bits(_fc(dev, packed, x, off, sc, None, 0, capi.OUT_F32, n, what), yf, what + " fp32 out, no bias")

@@ -172,21 +172,16 @@ def _conv_at_offset(ctx, capi, d, c, out_kind, off):
     """plhip_conv2d_int8 with y `off` elements into its buffer; returns (the output, the bytes in front of and behind it)."""
     C, L = ctypes, ctx.L
     oh, ow = capi.out_hw(d)
-    esz = 1 if out_kind == capi.OUT_I8 else 4
-    cnt = d.n * d.cout * oh * ow
-    dx, dw = ctx.to_device(c["x"]), ctx.to_device(c["w"])
-    ds, db = ctx.to_device(c["scale"]), ctx.to_device(c["bias"])
-    dy = ctx.to_device(np.full((cnt + 2 * off + 8) * esz, 0xA5, np.uint8))
-    dwp = ctx.malloc(L.plhip_conv_packed_weight_bytes(C.byref(d)))
-    ctx.check(L.plhip_pack_conv_weights(ctx.h, C.byref(d), dw, dwp), "pack")
-    assert L.plhip_conv_workspace_bytes(C.byref(d)) == 0
-    ctx.check(L.plhip_conv2d_int8(ctx.h, C.byref(d), dx, dwp, ds, db, C.c_void_p(dy.value + off * esz), out_kind, C.c_void_p(), 0),
-              "conv2d")
-    raw = ctx.to_host(dy, ((cnt + 2 * off + 8) * esz,), np.uint8)
-    for p in (dx, dw, ds, db, dy, dwp):
-        ctx.free(p)
-    body = raw[off * esz:(off + cnt) * esz].view(np.int8 if esz == 1 else np.float32).reshape(d.n, d.cout, oh, ow)
-    return body, np.concatenate([raw[:off * esz], raw[(off + cnt) * esz:]])
+    dt = np.dtype(np.int8 if out_kind == capi.OUT_I8 else np.float32)
+    with ctx.scope() as s:
+        dx, dw = s.put(c["x"]), s.put(c["w"])
+        ds, db = s.put(c["scale"]), s.put(c["bias"])
+        y = s.out((d.n, d.cout, oh, ow), dt, off=off * dt.itemsize, fill=0xA5)
+        dwp = s.alloc(L.plhip_conv_packed_weight_bytes(C.byref(d)))
+        ctx.check(L.plhip_pack_conv_weights(ctx.h, C.byref(d), dw, dwp), "pack")
+        assert L.plhip_conv_workspace_bytes(C.byref(d)) == 0
+        ctx.check(L.plhip_conv2d_int8(ctx.h, C.byref(d), dx, dwp, ds, db, y.ptr, out_kind, C.c_void_p(), 0), "conv2d")
+        return y.get(), y.margins()
 
 
 @pytest.mark.parametrize("st", [1, 2])

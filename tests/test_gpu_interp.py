@@ -190,77 +190,76 @@ def test_nan_logits_give_a_label_in_range_and_the_two_forms_agree(gpu_ctx):
 def test_bad_arguments_are_refused_before_any_launch(gpu_ctx, pkg):
     L = pkg.capi.load()
     h = gpu_ctx.h
-    src = gpu_ctx.to_device(np.arange(1024, dtype=F32))
-    out_f, out_q = gpu_ctx.malloc(4096), gpu_ctx.malloc(4096)
-    gpu_ctx.check(L.plhip_memset(h, out_f, 0x55, 4096), "memset")
-    gpu_ctx.check(L.plhip_memset(h, out_q, 0x55, 4096), "memset")
-    null = C.c_void_p()
-    big = (1 << 15) + 1
+    with gpu_ctx.scope() as s:
+        src = s.put(np.arange(1024, dtype=F32))
+        out_f, out_q = s.alloc(4096), s.alloc(4096)
+        gpu_ctx.check(L.plhip_memset(h, out_f, 0x55, 4096), "memset")
+        gpu_ctx.check(L.plhip_memset(h, out_q, 0x55, 4096), "memset")
+        null = C.c_void_p()
+        big = (1 << 15) + 1
 
-    def refused(fn, words, *args):
-        st = getattr(L, fn)(h, *args)
-        msg = L.plhip_last_error(h).decode()
-        assert st < 0 and msg.startswith(fn + ": ") and words in msg, (fn, st, msg, words)
+        def refused(fn, words, *args):
+            st = getattr(L, fn)(h, *args)
+            msg = L.plhip_last_error(h).decode()
+            assert st < 0 and msg.startswith(fn + ": ") and words in msg, (fn, st, msg, words)
 
-    # plhip_interp_f32(x, planes, in_h, in_w, out_h, out_w, method, align_corners, align_mode, y_f32, y_i8, calib_scale)
-    fn = "plhip_interp_f32"
-    refused(fn, "null", null, 2, 4, 4, 8, 8, 0, 0, 1, out_f, out_q, 1.0)
-    refused(fn, "one output is required", src, 2, 4, 4, 8, 8, 0, 0, 1, null, null, 1.0)
-    for k in range(5):
-        dims = [2, 4, 4, 8, 8]
-        dims[k] = 0
-        refused(fn, "at least 1", src, *dims, 0, 0, 1, out_f, out_q, 1.0)
-        if k:
-            dims[k] = big
-            refused(fn, "2^15", src, *dims, 0, 0, 1, out_f, out_q, 1.0)
-    refused(fn, "unknown method", src, 2, 4, 4, 8, 8, 2, 0, 1, out_f, out_q, 1.0)
-    refused(fn, "unknown method", src, 2, 4, 4, 8, 8, -1, 0, 1, out_f, out_q, 1.0)
-    refused(fn, "align_mode", src, 2, 4, 4, 8, 8, 0, 0, 2, out_f, out_q, 1.0)
-    refused(fn, "align_corners", src, 2, 4, 4, 8, 8, 0, 2, 1, out_f, out_q, 1.0)
-    for bad in (0.0, -1.0, float("inf"), float("nan")):
-        refused(fn, "calib_scale", src, 2, 4, 4, 8, 8, 0, 0, 1, out_f, out_q, bad)
-    refused(fn, "2^40", src, 1 << 30, 4, 4, 1 << 10, 1 << 10, 0, 0, 1, out_f, out_q, 1.0)
-    refused(fn, "2^40", src, 1 << 30, 1 << 10, 1 << 10, 4, 4, 0, 0, 1, out_f, out_q, 1.0)
-    # plhip_arg_max_f32(x, outer, c, inner, y, dtype)
-    fn = "plhip_arg_max_f32"
-    refused(fn, "null", null, 2, 4, 8, out_f, -1)
-    refused(fn, "null", src, 2, 4, 8, null, -1)
-    for dims in ((0, 4, 8), (2, 0, 8), (2, 4, 0), (-1, 4, 8)):
-        refused(fn, "at least 1", src, *dims, out_f, -1)
-    refused(fn, "2^15", src, 2, big, 8, out_f, -1)
-    for bad in (0, 1, 4, -2):
-        refused(fn, "dtype", src, 2, 4, 8, out_f, bad)
-    refused(fn, "2^40", src, 1 << 30, 4, 1 << 30, out_f, -1)
-    refused(fn, "2^40", src, 1 << 41, 4, 8, out_f, -1)
-    # plhip_interp_argmax_f32(x, n, c, in_h, in_w, out_h, out_w, method, align_corners, align_mode, y, dtype)
-    fn = "plhip_interp_argmax_f32"
-    refused(fn, "null", null, 2, 4, 4, 4, 8, 8, 0, 0, 1, out_f, -1)
-    refused(fn, "null", src, 2, 4, 4, 4, 8, 8, 0, 0, 1, null, -1)
-    for k in range(6):
-        dims = [2, 4, 4, 4, 8, 8]
-        dims[k] = 0
-        refused(fn, "at least 1", src, *dims, 0, 0, 1, out_f, -1)
-        if k:
-            dims[k] = big
-            refused(fn, "2^15", src, *dims, 0, 0, 1, out_f, -1)
-    refused(fn, "unknown method", src, 2, 4, 4, 4, 8, 8, 7, 0, 1, out_f, -1)
-    refused(fn, "align_mode", src, 2, 4, 4, 4, 8, 8, 0, 0, -1, out_f, -1)
-    refused(fn, "dtype", src, 2, 4, 4, 4, 8, 8, 0, 0, 1, out_f, 5)
-    refused(fn, "2^40", src, 1 << 20, 1 << 10, 4, 4, 1 << 10, 1 << 10, 0, 0, 1, out_f, -1)
-    gpu_ctx.sync()
-    # nothing was launched: both outputs still hold the fill
-    assert (gpu_ctx.to_host(out_f, (4096,), np.uint8) == 0x55).all() and (gpu_ctx.to_host(out_q, (4096,), np.uint8) == 0x55).all()
-    # and the same calls with good arguments are taken: 2 planes of 4 x 4 -> 8 x 8 nearest doubles every pixel
-    assert L.plhip_interp_f32(h, src, 2, 4, 4, 8, 8, 1, 0, 1, out_f, out_q, 1.0) == 0
-    gpu_ctx.sync()
-    want = np.arange(32, dtype=F32).reshape(2, 4, 4).repeat(2, axis=1).repeat(2, axis=2)
-    assert np.array_equal(gpu_ctx.to_host(out_f, (2, 8, 8), F32), want) and np.array_equal(gpu_ctx.to_host(out_q, (2, 8, 8), np.int8), want.astype(np.int8))
-    assert L.plhip_interp_argmax_f32(h, src, 2, 4, 4, 4, 8, 8, 0, 0, 1, out_f, 2) == 0   # the values grow with the channel
-    assert L.plhip_arg_max_f32(h, src, 2, 4, 8, out_q, 2) == 0
-    gpu_ctx.sync()
-    assert (gpu_ctx.to_host(out_f, (2, 8, 8), np.int32) == 3).all() and (gpu_ctx.to_host(out_q, (2, 8), np.int32) == 3).all()
-    for p in (src, out_f, out_q):
-        gpu_ctx.free(p)
+        # plhip_interp_f32(x, planes, in_h, in_w, out_h, out_w, method, align_corners, align_mode, y_f32, y_i8, calib_scale)
+        fn = "plhip_interp_f32"
+        refused(fn, "null", null, 2, 4, 4, 8, 8, 0, 0, 1, out_f, out_q, 1.0)
+        refused(fn, "one output is required", src, 2, 4, 4, 8, 8, 0, 0, 1, null, null, 1.0)
+        for k in range(5):
+            dims = [2, 4, 4, 8, 8]
+            dims[k] = 0
+            refused(fn, "at least 1", src, *dims, 0, 0, 1, out_f, out_q, 1.0)
+            if k:
+                dims[k] = big
+                refused(fn, "2^15", src, *dims, 0, 0, 1, out_f, out_q, 1.0)
+        refused(fn, "unknown method", src, 2, 4, 4, 8, 8, 2, 0, 1, out_f, out_q, 1.0)
+        refused(fn, "unknown method", src, 2, 4, 4, 8, 8, -1, 0, 1, out_f, out_q, 1.0)
+        refused(fn, "align_mode", src, 2, 4, 4, 8, 8, 0, 0, 2, out_f, out_q, 1.0)
+        refused(fn, "align_corners", src, 2, 4, 4, 8, 8, 0, 2, 1, out_f, out_q, 1.0)
+        for bad in (0.0, -1.0, float("inf"), float("nan")):
+            refused(fn, "calib_scale", src, 2, 4, 4, 8, 8, 0, 0, 1, out_f, out_q, bad)
+        refused(fn, "2^40", src, 1 << 30, 4, 4, 1 << 10, 1 << 10, 0, 0, 1, out_f, out_q, 1.0)
+        refused(fn, "2^40", src, 1 << 30, 1 << 10, 1 << 10, 4, 4, 0, 0, 1, out_f, out_q, 1.0)
+        # plhip_arg_max_f32(x, outer, c, inner, y, dtype)
+        fn = "plhip_arg_max_f32"
+        refused(fn, "null", null, 2, 4, 8, out_f, -1)
+        refused(fn, "null", src, 2, 4, 8, null, -1)
+        for dims in ((0, 4, 8), (2, 0, 8), (2, 4, 0), (-1, 4, 8)):
+            refused(fn, "at least 1", src, *dims, out_f, -1)
+        refused(fn, "2^15", src, 2, big, 8, out_f, -1)
+        for bad in (0, 1, 4, -2):
+            refused(fn, "dtype", src, 2, 4, 8, out_f, bad)
+        refused(fn, "2^40", src, 1 << 30, 4, 1 << 30, out_f, -1)
+        refused(fn, "2^40", src, 1 << 41, 4, 8, out_f, -1)
+        # plhip_interp_argmax_f32(x, n, c, in_h, in_w, out_h, out_w, method, align_corners, align_mode, y, dtype)
+        fn = "plhip_interp_argmax_f32"
+        refused(fn, "null", null, 2, 4, 4, 4, 8, 8, 0, 0, 1, out_f, -1)
+        refused(fn, "null", src, 2, 4, 4, 4, 8, 8, 0, 0, 1, null, -1)
+        for k in range(6):
+            dims = [2, 4, 4, 4, 8, 8]
+            dims[k] = 0
+            refused(fn, "at least 1", src, *dims, 0, 0, 1, out_f, -1)
+            if k:
+                dims[k] = big
+                refused(fn, "2^15", src, *dims, 0, 0, 1, out_f, -1)
+        refused(fn, "unknown method", src, 2, 4, 4, 4, 8, 8, 7, 0, 1, out_f, -1)
+        refused(fn, "align_mode", src, 2, 4, 4, 4, 8, 8, 0, 0, -1, out_f, -1)
+        refused(fn, "dtype", src, 2, 4, 4, 4, 8, 8, 0, 0, 1, out_f, 5)
+        refused(fn, "2^40", src, 1 << 20, 1 << 10, 4, 4, 1 << 10, 1 << 10, 0, 0, 1, out_f, -1)
+        gpu_ctx.sync()
+        # nothing was launched: both outputs still hold the fill
+        assert (gpu_ctx.to_host(out_f, (4096,), np.uint8) == 0x55).all() and (gpu_ctx.to_host(out_q, (4096,), np.uint8) == 0x55).all()
+        # and the same calls with good arguments are taken: 2 planes of 4 x 4 -> 8 x 8 nearest doubles every pixel
+        assert L.plhip_interp_f32(h, src, 2, 4, 4, 8, 8, 1, 0, 1, out_f, out_q, 1.0) == 0
+        gpu_ctx.sync()
+        want = np.arange(32, dtype=F32).reshape(2, 4, 4).repeat(2, axis=1).repeat(2, axis=2)
+        assert np.array_equal(gpu_ctx.to_host(out_f, (2, 8, 8), F32), want) and np.array_equal(gpu_ctx.to_host(out_q, (2, 8, 8), np.int8), want.astype(np.int8))
+        assert L.plhip_interp_argmax_f32(h, src, 2, 4, 4, 4, 8, 8, 0, 0, 1, out_f, 2) == 0   # the values grow with the channel
+        assert L.plhip_arg_max_f32(h, src, 2, 4, 8, out_q, 2) == 0
+        gpu_ctx.sync()
+        assert (gpu_ctx.to_host(out_f, (2, 8, 8), np.int32) == 3).all() and (gpu_ctx.to_host(out_q, (2, 8), np.int32) == 3).all()
 
 
 def test_kernel_classes_through_the_factory(lite):

@@ -85,13 +85,13 @@ def test_hard_act_refuses_bad_arguments(gpu_ctx, pkg):
     capi = pkg.capi
     L = capi.load()
     pr = (C.c_float * 3)(6, 6, 3)
-    d = gpu_ctx.malloc(64)
-    assert L.plhip_hard_act_f32(gpu_ctx.h, 0, pr, d, None, None, 1.0, 4) < 0       # no output
-    assert L.plhip_hard_act_f32(gpu_ctx.h, 0, pr, d, None, d, 0.0, 4) < 0          # int8 output without a scale
-    assert L.plhip_hard_act_f32(gpu_ctx.h, 7, pr, d, d, None, 1.0, 4) < 0          # unknown kind
-    assert L.plhip_se_scale_f32(gpu_ctx.h, d, d, 1, 0, 4, d, None, 1.0) < 0
-    assert L.plhip_se_scale_f32(gpu_ctx.h, d, None, 1, 1, 4, d, None, 1.0) < 0
-    gpu_ctx.free(d)
+    with gpu_ctx.scope() as s:
+        d = s.alloc(64)
+        assert L.plhip_hard_act_f32(gpu_ctx.h, 0, pr, d, None, None, 1.0, 4) < 0       # no output
+        assert L.plhip_hard_act_f32(gpu_ctx.h, 0, pr, d, None, d, 0.0, 4) < 0          # int8 output without a scale
+        assert L.plhip_hard_act_f32(gpu_ctx.h, 7, pr, d, d, None, 1.0, 4) < 0          # unknown kind
+        assert L.plhip_se_scale_f32(gpu_ctx.h, d, d, 1, 0, 4, d, None, 1.0) < 0
+        assert L.plhip_se_scale_f32(gpu_ctx.h, d, None, 1, 1, 4, d, None, 1.0) < 0
 
 
 @pytest.mark.parametrize("hw", [1, 9, 16, 25, 49, 64, 196, 3136])  # 1, 16, 64 and 256 lanes per plane, scalar and vector

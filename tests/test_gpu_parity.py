@@ -612,3 +612,21 @@ def test_full_size_properties_c2(gpu_ctx, pkg, plref):
     assert np.array_equal(gpu_ctx.conv2d(d1, x[b:b + 1], w1, None, None, capi.OUT_I32)[0], a1[b])
     s1 = plref.shape(1, cin, hw, hw, cout, 3, 3, (1, 1, 1, 1), (1, 1), (1, 1), 1)
     assert np.array_equal(plref.conv2d_acc(s1, x[3:4], w1)[0], a1[3])
+
+
+def test_helpers_leave_nothing_allocated(gpu_ctx, pkg):
+    """The binding's whole-op helpers own their device buffers through a scope: a refusal of the library (a status, before any
+    launch) and three small launches leave the context's count of live allocations where it was."""
+    capi = pkg.capi
+    before = gpu_ctx.outstanding()
+    with pytest.raises(capi.PlhipError):  # image_to_tensor refuses the frame formats
+        gpu_ctx.image_to_tensor(capi.image_desc(1, 4, 4, capi.IMG_NV12, (0, 0, 0), (1, 1, 1)), np.zeros((1, 6, 4), np.uint8))
+    assert gpu_ctx.outstanding() == before
+    gpu_ctx.hard_act(capi.HARD_SWISH, np.linspace(-4, 4, 17, dtype=np.float32), mode="both", misalign=1)
+    assert gpu_ctx.outstanding() == before
+    d = capi.conv_desc(1, 16, 4, 4, 16, 1, 1)
+    gpu_ctx.conv2d(d, np.ones((1, 16, 4, 4), np.int8), np.ones((16, 16, 1, 1), np.int8), None, None, capi.OUT_I32)
+    assert gpu_ctx.outstanding() == before
+    x = np.arange(15, dtype=np.float32).reshape(1, 3, 5)
+    gpu_ctx.concat_calib([x, x], 1, 0.25, misalign=1)
+    assert gpu_ctx.outstanding() == before

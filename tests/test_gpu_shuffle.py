@@ -136,46 +136,46 @@ def test_shuffle_unit_equals_the_oracle_and_the_four_calls(gpu_ctx, n, h, hw, sp
 
 def test_bad_arguments_are_refused(gpu_ctx, pkg):
     L = pkg.capi.load()
-    d = gpu_ctx.malloc(4096)
-    h = gpu_ctx.h
-    null = C.c_void_p()
-    two = (C.c_void_p * 2)(d, d)
-    one_null = (C.c_void_p * 2)(d, null)
+    with gpu_ctx.scope() as s:
+        d = s.alloc(4096)
+        h = gpu_ctx.h
+        null = C.c_void_p()
+        two = (C.c_void_p * 2)(d, d)
+        one_null = (C.c_void_p * 2)(d, null)
 
-    def ext(*v):
-        return (C.c_int64 * len(v))(*v)
-    assert L.plhip_concat_f32(h, two, ext(2, 3), 2, 1, 4, d) == 0
-    assert L.plhip_concat_f32(h, two, ext(2, 3), 2, 1, 4, null) < 0        # null output
-    assert L.plhip_concat_f32(h, one_null, ext(2, 3), 2, 1, 4, d) < 0      # a null input
-    assert L.plhip_concat_f32(h, two, ext(2, 0), 2, 1, 4, d) < 0           # an extent < 1
-    assert L.plhip_concat_f32(h, two, ext(2, 3), 0, 1, 4, d) < 0           # no inputs
-    assert L.plhip_concat_f32(h, two, ext(2, 3), 2, 0, 4, d) < 0
-    assert L.plhip_concat_f32(h, two, ext(1 << 30, 1 << 30), 2, 1 << 30, 4, d) < 0   # outer * sum * inner beyond 2^40 elements
-    assert L.plhip_concat_f32(h, two, ext(1 << 39, 1 << 39), 2, 1, 4, d) < 0
-    assert L.plhip_split_f32(h, d, 1 << 20, 1 << 20, 1 << 20, 2, None, 2, two) < 0
-    assert L.plhip_split_f32(h, d, 1, 6, 4, 2, None, 2, two) == 0
-    assert L.plhip_split_f32(h, d, 1, 6, 4, 0, ext(2, 4), 2, two) == 0
-    assert L.plhip_split_f32(h, d, 1, 7, 4, 2, None, 2, two) < 0           # num does not divide the axis
-    assert L.plhip_split_f32(h, d, 1, 6, 4, 3, None, 2, two) < 0           # num != count
-    assert L.plhip_split_f32(h, d, 1, 6, 4, 0, ext(2, 3), 2, two) < 0      # sections do not add up
-    assert L.plhip_split_f32(h, d, 1, 6, 4, 0, None, 2, two) < 0           # neither num nor sections
-    assert L.plhip_split_f32(h, d, 1, 6, 4, 2, None, 2, one_null) < 0      # a null output
-    assert L.plhip_shuffle_channel_f32(h, d, 1, 6, 4, 3, d, null, 1.0) == 0
-    assert L.plhip_shuffle_channel_f32(h, d, 1, 6, 4, 4, d, null, 1.0) < 0     # group does not divide c
-    assert L.plhip_shuffle_channel_f32(h, d, 1, 6, 4, 3, null, null, 1.0) < 0  # no output
-    assert L.plhip_shuffle_channel_f32(h, d, 1, 6, 4, 3, null, d, 0.0) < 0     # int8 output without a positive scale
-    assert L.plhip_shuffle_channel_f32(h, null, 1, 6, 4, 3, d, null, 1.0) < 0
-    assert L.plhip_shuffle_unit_f32(h, d, d, 1, 3, 4, 3, d, d, null, 1.0) == 0
-    assert L.plhip_shuffle_unit_f32(h, d, d, 1, 3, 4, 3, null, d, null, 1.0) < 0   # lo_f32 null with split_at > 0
-    assert L.plhip_shuffle_unit_f32(h, d, d, 1, 3, 4, 0, d, d, null, 1.0) < 0      # lo_f32 given with split_at == 0
-    assert L.plhip_shuffle_unit_f32(h, d, d, 1, 3, 4, 7, d, d, null, 1.0) < 0      # split_at > 2 h
-    assert L.plhip_shuffle_unit_f32(h, d, d, 1, 3, 4, -1, d, d, null, 1.0) < 0
-    assert L.plhip_shuffle_unit_f32(h, d, d, 1, 3, 4, 3, d, null, null, 1.0) < 0   # nothing for the second part
-    assert L.plhip_shuffle_unit_f32(h, d, d, 1, 3, 4, 3, d, null, d, 0.0) < 0      # int8 without a positive scale
-    assert L.plhip_shuffle_unit_f32(h, d, null, 1, 3, 4, 3, d, d, null, 1.0) < 0
-    assert L.plhip_shuffle_unit_f32(h, d, d, 1, 3, 4, 6, d, null, null, 1.0) == 0  # everything below split_at: no second part
-    gpu_ctx.sync()
-    gpu_ctx.free(d)
+        def ext(*v):
+            return (C.c_int64 * len(v))(*v)
+        assert L.plhip_concat_f32(h, two, ext(2, 3), 2, 1, 4, d) == 0
+        assert L.plhip_concat_f32(h, two, ext(2, 3), 2, 1, 4, null) < 0        # null output
+        assert L.plhip_concat_f32(h, one_null, ext(2, 3), 2, 1, 4, d) < 0      # a null input
+        assert L.plhip_concat_f32(h, two, ext(2, 0), 2, 1, 4, d) < 0           # an extent < 1
+        assert L.plhip_concat_f32(h, two, ext(2, 3), 0, 1, 4, d) < 0           # no inputs
+        assert L.plhip_concat_f32(h, two, ext(2, 3), 2, 0, 4, d) < 0
+        assert L.plhip_concat_f32(h, two, ext(1 << 30, 1 << 30), 2, 1 << 30, 4, d) < 0   # outer * sum * inner beyond 2^40 elements
+        assert L.plhip_concat_f32(h, two, ext(1 << 39, 1 << 39), 2, 1, 4, d) < 0
+        assert L.plhip_split_f32(h, d, 1 << 20, 1 << 20, 1 << 20, 2, None, 2, two) < 0
+        assert L.plhip_split_f32(h, d, 1, 6, 4, 2, None, 2, two) == 0
+        assert L.plhip_split_f32(h, d, 1, 6, 4, 0, ext(2, 4), 2, two) == 0
+        assert L.plhip_split_f32(h, d, 1, 7, 4, 2, None, 2, two) < 0           # num does not divide the axis
+        assert L.plhip_split_f32(h, d, 1, 6, 4, 3, None, 2, two) < 0           # num != count
+        assert L.plhip_split_f32(h, d, 1, 6, 4, 0, ext(2, 3), 2, two) < 0      # sections do not add up
+        assert L.plhip_split_f32(h, d, 1, 6, 4, 0, None, 2, two) < 0           # neither num nor sections
+        assert L.plhip_split_f32(h, d, 1, 6, 4, 2, None, 2, one_null) < 0      # a null output
+        assert L.plhip_shuffle_channel_f32(h, d, 1, 6, 4, 3, d, null, 1.0) == 0
+        assert L.plhip_shuffle_channel_f32(h, d, 1, 6, 4, 4, d, null, 1.0) < 0     # group does not divide c
+        assert L.plhip_shuffle_channel_f32(h, d, 1, 6, 4, 3, null, null, 1.0) < 0  # no output
+        assert L.plhip_shuffle_channel_f32(h, d, 1, 6, 4, 3, null, d, 0.0) < 0     # int8 output without a positive scale
+        assert L.plhip_shuffle_channel_f32(h, null, 1, 6, 4, 3, d, null, 1.0) < 0
+        assert L.plhip_shuffle_unit_f32(h, d, d, 1, 3, 4, 3, d, d, null, 1.0) == 0
+        assert L.plhip_shuffle_unit_f32(h, d, d, 1, 3, 4, 3, null, d, null, 1.0) < 0   # lo_f32 null with split_at > 0
+        assert L.plhip_shuffle_unit_f32(h, d, d, 1, 3, 4, 0, d, d, null, 1.0) < 0      # lo_f32 given with split_at == 0
+        assert L.plhip_shuffle_unit_f32(h, d, d, 1, 3, 4, 7, d, d, null, 1.0) < 0      # split_at > 2 h
+        assert L.plhip_shuffle_unit_f32(h, d, d, 1, 3, 4, -1, d, d, null, 1.0) < 0
+        assert L.plhip_shuffle_unit_f32(h, d, d, 1, 3, 4, 3, d, null, null, 1.0) < 0   # nothing for the second part
+        assert L.plhip_shuffle_unit_f32(h, d, d, 1, 3, 4, 3, d, null, d, 0.0) < 0      # int8 without a positive scale
+        assert L.plhip_shuffle_unit_f32(h, d, null, 1, 3, 4, 3, d, d, null, 1.0) < 0
+        assert L.plhip_shuffle_unit_f32(h, d, d, 1, 3, 4, 6, d, null, null, 1.0) == 0  # everything below split_at: no second part
+        gpu_ctx.sync()
 
 
 def test_kernel_classes_through_the_factory(lite):

@@ -116,85 +116,82 @@ def test_both_entry_points_in_one_captured_graph(gpu_ctx):
     img = Y.random_img_size(6401, n)
     want_box = gpu_ctx.yolo_box(xs[0], img, anchors[0], c, 0.5, 32, True, 1.0)
     want_head = gpu_ctx.yolo_head(xs, img, anchors, c, 0.5, [32, 16], True, 1.0)
-    dxs = [gpu_ctx.to_device(x) for x in xs]
-    dimg = gpu_ctx.to_device(img)
     p0, p = an * 16, an * 16 + an * 15
-    outs = [gpu_ctx._filled(cnt, 0) for cnt in (n * p0 * 4, n * p0 * c, n * p * 4, n * p * c)]
-    (_b0, b_box), (_b1, s_box), (_b2, b_head), (_b3, s_head) = outs
-    gpu_ctx.sync()
-    gpu_ctx.check(L.plhip_graph_begin(h), "graph_begin")
-    st1 = gpu_ctx.yolo_box_launch(dxs[0], dimg, xs[0].shape, anchors[0], c, 0.5, 32, True, 1.0, b_box, s_box)
-    st2 = gpu_ctx.yolo_head_launch(dxs, dimg, [x.shape for x in xs], anchors, c, 0.5, [32, 16], True, 1.0, b_head, s_head)
-    graph = C.c_void_p()
-    gpu_ctx.check(L.plhip_graph_end(h, C.byref(graph)), "graph_end")
-    assert st1 == 0 and st2 == 0
-    gpu_ctx.sync()
-    # captured, not run: the outputs still hold the fill
-    assert (gpu_ctx.to_host(b_box, (n * p0 * 4,), np.uint32) == 0xFFFFFFFF).all()
-    gpu_ctx.check(L.plhip_graph_launch(h, graph), "graph_launch")
-    gpu_ctx.sync()
-    _same_bytes(gpu_ctx.to_host(b_box, (n, p0, 4), F32), want_box[0], "replayed yolo_box boxes")
-    _same_bytes(gpu_ctx.to_host(s_box, (n, p0, c), F32), want_box[1], "replayed yolo_box scores")
-    _same_bytes(gpu_ctx.to_host(b_head, (n, p, 4), F32), want_head[0], "replayed yolo_head boxes")
-    _same_bytes(gpu_ctx.to_host(s_head, (n, c, p), F32), want_head[1], "replayed yolo_head scores")
-    gpu_ctx.check(L.plhip_graph_destroy(h, graph), "graph_destroy")
-    for b in dxs + [dimg] + [b for b, _d in outs]:
-        gpu_ctx.free(b)
+    with gpu_ctx.scope() as s:
+        dxs = [s.put(x) for x in xs]
+        dimg = s.put(img)
+        b_box, s_box, b_head, s_head = [s.out((cnt,), F32, fill=0xFF).ptr for cnt in (n * p0 * 4, n * p0 * c, n * p * 4, n * p * c)]
+        gpu_ctx.sync()
+        gpu_ctx.check(L.plhip_graph_begin(h), "graph_begin")
+        st1 = gpu_ctx.yolo_box_launch(dxs[0], dimg, xs[0].shape, anchors[0], c, 0.5, 32, True, 1.0, b_box, s_box)
+        st2 = gpu_ctx.yolo_head_launch(dxs, dimg, [x.shape for x in xs], anchors, c, 0.5, [32, 16], True, 1.0, b_head, s_head)
+        graph = C.c_void_p()
+        gpu_ctx.check(L.plhip_graph_end(h, C.byref(graph)), "graph_end")
+        assert st1 == 0 and st2 == 0
+        gpu_ctx.sync()
+        # captured, not run: the outputs still hold the fill
+        assert (gpu_ctx.to_host(b_box, (n * p0 * 4,), np.uint32) == 0xFFFFFFFF).all()
+        gpu_ctx.check(L.plhip_graph_launch(h, graph), "graph_launch")
+        gpu_ctx.sync()
+        _same_bytes(gpu_ctx.to_host(b_box, (n, p0, 4), F32), want_box[0], "replayed yolo_box boxes")
+        _same_bytes(gpu_ctx.to_host(s_box, (n, p0, c), F32), want_box[1], "replayed yolo_box scores")
+        _same_bytes(gpu_ctx.to_host(b_head, (n, p, 4), F32), want_head[0], "replayed yolo_head boxes")
+        _same_bytes(gpu_ctx.to_host(s_head, (n, c, p), F32), want_head[1], "replayed yolo_head scores")
+        gpu_ctx.check(L.plhip_graph_destroy(h, graph), "graph_destroy")
 
 
 def test_refusals_launch_nothing(gpu_ctx):
     L = gpu_ctx.L
-    x = gpu_ctx.to_device(np.zeros(3 * 8 * 16, F32))
-    img = gpu_ctx.to_device(np.array([[100, 100]], np.int32))
-    obuf, out = gpu_ctx._filled(1024, 0)
-    good = dict(x=x, img=img, shape=(1, 24, 4, 4), anchors=ANCHORS[3], c=3, ratio=32, boxes=out, scores=out)
+    with gpu_ctx.scope() as s:
+        x = s.put(np.zeros(3 * 8 * 16, F32))
+        img = s.put(np.array([[100, 100]], np.int32))
+        out = s.out((1024,), F32, fill=0xFF).ptr
+        good = dict(x=x, img=img, shape=(1, 24, 4, 4), anchors=ANCHORS[3], c=3, ratio=32, boxes=out, scores=out)
 
-    def box(**kw):
-        a = dict(good, **kw)
-        return gpu_ctx.yolo_box_launch(a["x"], a["img"], a["shape"], a["anchors"], a["c"], 0.5, a["ratio"], True, 1.0, a["boxes"], a["scores"])
+        def box(**kw):
+            a = dict(good, **kw)
+            return gpu_ctx.yolo_box_launch(a["x"], a["img"], a["shape"], a["anchors"], a["c"], 0.5, a["ratio"], True, 1.0, a["boxes"], a["scores"])
 
-    def head(count=1, **kw):
-        a = dict(good, **kw)
-        return gpu_ctx.yolo_head_launch([a["x"]] * count, a["img"], [a["shape"]] * count, [a["anchors"]] * count, a["c"], 0.5,
-                                        [a["ratio"]] * count, True, 1.0, a["boxes"], a["scores"])
+        def head(count=1, **kw):
+            a = dict(good, **kw)
+            return gpu_ctx.yolo_head_launch([a["x"]] * count, a["img"], [a["shape"]] * count, [a["anchors"]] * count, a["c"], 0.5,
+                                            [a["ratio"]] * count, True, 1.0, a["boxes"], a["scores"])
 
-    def refused(f, status, part, **kw):
-        st = f(**kw)
-        msg = L.plhip_last_error(gpu_ctx.h).decode()
-        assert st == status and msg.startswith("plhip_yolo_%s_f32: " % f.__name__) and part in msg, (f.__name__, kw, st, msg)
+        def refused(f, status, part, **kw):
+            st = f(**kw)
+            msg = L.plhip_last_error(gpu_ctx.h).decode()
+            assert st == status and msg.startswith("plhip_yolo_%s_f32: " % f.__name__) and part in msg, (f.__name__, kw, st, msg)
 
-    for f in (box, head):
-        refused(f, -1, "null x", x=None)
-        refused(f, -1, "null img_size", img=None)
-        refused(f, -1, "null boxes or scores", boxes=None)
-        refused(f, -1, "null boxes or scores", scores=None)
-        refused(f, -1, "n and c", shape=(0, 24, 4, 4))
-        refused(f, -1, "n and c", c=0)
-        refused(f, -1, "h and w", shape=(1, 24, 0, 4))
-        refused(f, -1, "h and w", shape=(1, 24, 4, -1))
-        refused(f, -1, "downsample_ratio", ratio=0)
-        refused(f, -1, "anchor", anchors=[])
-        refused(f, -3, "16 anchors", anchors=list(range(1, 35)))
-        refused(f, -3, "2^31", shape=(1 << 20, 24, 32, 32))            # n * P alone
-        refused(f, -3, "2^31", shape=(1, 24, 1 << 15, 1 << 15))        # P alone
-        refused(f, -3, "2^31", shape=(2, 24, 1 << 12, 1 << 12), c=80)  # only with the classes: 2 * 3 * 2^24 * 80
-        refused(f, -3, "downsample_ratio * h", shape=(1, 24, 1 << 12, 4), ratio=1 << 19)
-    refused(head, -1, "anchor", anchors=[10, 13, 16])                  # an odd list
-    refused(head, -1, "count", count=0)
-    refused(head, -1, "count", count=9)
-    refused(head, -3, "2^18", c=(1 << 18) + 1)
-    assert L.plhip_yolo_box_f32(None, x, img, 1, 3, 3, 4, 4, (C.c_int * 6)(*ANCHORS[3]), 0.5, 32, 1, 1.0, out, out) == -1
-    gpu_ctx.sync()
-    assert (gpu_ctx.to_host(out, (1024,), np.uint32) == 0xFFFFFFFF).all()
-    # and the accepted calls write: 48 boxes (4 floats each) in front of 48 x 3 scores
-    scores = C.c_void_p(out.value + 4 * 192)
-    assert box(scores=scores) == 0
-    gpu_ctx.sync()
-    first = gpu_ctx.to_host(out, (1024,), np.uint32)
-    assert not (first[:336] == 0xFFFFFFFF).any() and (first[336:] == 0xFFFFFFFF).all()
-    assert (first[192:336].view(F32) == F32(0.25)).all()               # sigmoid(0) = 0.5 is not below 0.5: conf * 0.5
-    assert head(scores=scores) == 0
-    gpu_ctx.sync()
-    assert np.array_equal(gpu_ctx.to_host(out, (1024,), np.uint32), first)  # one class value everywhere: the layouts agree
-    for b in (x, img, obuf):
-        gpu_ctx.free(b)
+        for f in (box, head):
+            refused(f, -1, "null x", x=None)
+            refused(f, -1, "null img_size", img=None)
+            refused(f, -1, "null boxes or scores", boxes=None)
+            refused(f, -1, "null boxes or scores", scores=None)
+            refused(f, -1, "n and c", shape=(0, 24, 4, 4))
+            refused(f, -1, "n and c", c=0)
+            refused(f, -1, "h and w", shape=(1, 24, 0, 4))
+            refused(f, -1, "h and w", shape=(1, 24, 4, -1))
+            refused(f, -1, "downsample_ratio", ratio=0)
+            refused(f, -1, "anchor", anchors=[])
+            refused(f, -3, "16 anchors", anchors=list(range(1, 35)))
+            refused(f, -3, "2^31", shape=(1 << 20, 24, 32, 32))            # n * P alone
+            refused(f, -3, "2^31", shape=(1, 24, 1 << 15, 1 << 15))        # P alone
+            refused(f, -3, "2^31", shape=(2, 24, 1 << 12, 1 << 12), c=80)  # only with the classes: 2 * 3 * 2^24 * 80
+            refused(f, -3, "downsample_ratio * h", shape=(1, 24, 1 << 12, 4), ratio=1 << 19)
+        refused(head, -1, "anchor", anchors=[10, 13, 16])                  # an odd list
+        refused(head, -1, "count", count=0)
+        refused(head, -1, "count", count=9)
+        refused(head, -3, "2^18", c=(1 << 18) + 1)
+        assert L.plhip_yolo_box_f32(None, x, img, 1, 3, 3, 4, 4, (C.c_int * 6)(*ANCHORS[3]), 0.5, 32, 1, 1.0, out, out) == -1
+        gpu_ctx.sync()
+        assert (gpu_ctx.to_host(out, (1024,), np.uint32) == 0xFFFFFFFF).all()
+        # and the accepted calls write: 48 boxes (4 floats each) in front of 48 x 3 scores
+        scores = C.c_void_p(out.value + 4 * 192)
+        assert box(scores=scores) == 0
+        gpu_ctx.sync()
+        first = gpu_ctx.to_host(out, (1024,), np.uint32)
+        assert not (first[:336] == 0xFFFFFFFF).any() and (first[336:] == 0xFFFFFFFF).all()
+        assert (first[192:336].view(F32) == F32(0.25)).all()               # sigmoid(0) = 0.5 is not below 0.5: conf * 0.5
+        assert head(scores=scores) == 0
+        gpu_ctx.sync()
+        assert np.array_equal(gpu_ctx.to_host(out, (1024,), np.uint32), first)  # one class value everywhere: the layouts agree

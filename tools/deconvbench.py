@@ -117,8 +117,7 @@ def bench_shape(ctx, rng, shape, batch, rounds, reps, warmup, window_ms):
         rec["phase_over_conv1x1"] = rec["median_ms"]["phase"] / rec["median_ms"]["conv"]
     if "phase" in ms:
         rec["direct_over_phase_per_round"] = [float(dv / pv) for dv, pv in zip(ms["direct"], ms["phase"])]
-    for q in list(ctx._allocs):
-        ctx.free(q)
+    ctx.free_all()
     return rec
 
 

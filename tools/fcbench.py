@@ -46,8 +46,7 @@ def main():
             us = ms.value / args.reps * 1e3
             print("fc m=%4d k=%4d n=%4d  %7.2f us  %6.1f TOP/s  %6.1f GB/s" % (
                 m, k, n, us, 2.0 * m * k * n / us / 1e6, (m * k + k * n + 4.0 * m * n) / us / 1e3), flush=True)
-            for q in list(ctx._allocs):
-                ctx.free(q)
+            ctx.free_all()
 
 
 if __name__ == "__main__":

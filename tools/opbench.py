@@ -94,8 +94,7 @@ def resnext_ab(args):
             tot[1] += i
             print("%-6s %4dx%3dx%-3d s%d g%d %12.2f %12.2f %7.2f %9.1f %10.2f %10.2f" % (
                 name, c, hin, hin, s, groups, g * 1e3, i * 1e3, i / g, byts / 1e6, byts / g / 1e9, byts / i / 1e9), flush=True)
-            for q in list(ctx._allocs):
-                ctx.free(q)
+            ctx.free_all()
     print("total  grouped %.2f us  im2col %.2f us  ratio %.2f" % (tot[0] * 1e3, tot[1] * 1e3, tot[1] / max(tot[0], 1e-9)))
 
 
@@ -156,8 +155,7 @@ def main():
             print("%-6s %-4s %4d->%4d %3dx%-3d s%d  %8.2f us  %7.1f GB/s  %7.1f TOP/s  %s" % (
                 name, kind, cin, cout, hin, hin, s, ms * 1e3, byts / ms / 1e6, 2 * macs / ms / 1e9,
                 L.plhip_conv_impl_name(C.byref(d)).decode() if g == 1 else "depthwise"), flush=True)
-            for q in list(ctx._allocs):
-                ctx.free(q)
+            ctx.free_all()
     if args.what in ("fused", "all") and args.net == "mobilenet_v1":
         ftot = 0.0
         with capi.Context(0) as ctx:
@@ -195,8 +193,7 @@ def main():
                 ftot += ms
                 print("%-4s+%-5s %s %4d->%4d %3dx%-3d s%d  %8.2f us  %7.1f GB/s  %7.1f TOP/s" % (
                     dn, pn, how, c, m, hin, hin, s, ms * 1e3, byts / ms / 1e6, 2 * macs / ms / 1e9), flush=True)
-                for q in list(ctx._allocs):
-                    ctx.free(q)
+                ctx.free_all()
         print("fused total %.2f us" % (ftot * 1e3))
     print("total %.2f us" % (tot * 1e3))
 
