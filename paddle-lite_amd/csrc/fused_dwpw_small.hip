@@ -175,14 +175,12 @@ __global__ __launch_bounds__(512, K >= 1024 ? 1 : 2) void fused_dwpw7_kernel(Fus
   const uint8_t* const wpk = reinterpret_cast<const uint8_t*>(g.wp) + (size_t)mt0 * KS * 1024;  // [mt][ks][64 lanes][16 B]
   const uint32_t wlane = (uint32_t)lane * 16;
   // weight fragments WD - 1 K-steps ahead (a fragment comes from L2: ~1 us; one step ahead every K-step waited for its weights:
-  // 1024 -> 1024 took 23.4 us for 4 us of MFMAs)
-  constexpr int WD = MW >= 4 ? 2 : 4;
+  // 1024 -> 1024 took 23.4 us for 4 us of MFMAs); four slots in the MW = 4 forms as well: 64 registers of fragments beside 128
+  // of accumulators, no spill (with two slots one K-step = 4 KiB per wave was in flight against that latency).  The depth is
+  // only real behind the scheduling fence in group(): see there
+  constexpr int WD = 4;
   static_assert(KS % WD == 0, "weight ring");
   v4i Wf[WD][MW];
-#pragma unroll
-  for (int u = 0; u < WD - 1; ++u)
-#pragma unroll
-    for (int m = 0; m < MW; ++m) Wf[u][m] = *reinterpret_cast<const v4i*>(wpk + ((size_t)m * KS + u) * 1024 + wlane);
   float psc[MW], pbi[MW];
 #pragma unroll
   for (int m = 0; m < MW; ++m) {
@@ -207,6 +205,12 @@ __global__ __launch_bounds__(512, K >= 1024 ? 1 : 2) void fused_dwpw7_kernel(Fus
     *reinterpret_cast<v4i*>(o) = pv;
     o[4] = __float_as_uint(bi + bi);
   }
+  // the ring's first WD - 1 K-steps, behind the parameters (loads return in order: requested in front of them, 12 KiB of
+  // fragments per wave held the parameters, and with them the whole produce phase, back by ~1 k cycles)
+#pragma unroll
+  for (int u = 0; u < WD - 1; ++u)
+#pragma unroll
+    for (int m = 0; m < MW; ++m) Wf[u][m] = *reinterpret_cast<const v4i*>(wpk + ((size_t)m * KS + u) * 1024 + wlane);
   __syncthreads();  // the parameters are in LDS (the row fetches above are in flight meanwhile)
   PLHIP_STAMP(3);
   auto steps = [&](auto self, auto it_c) __attribute__((always_inline)) -> void {
@@ -237,6 +241,9 @@ __global__ __launch_bounds__(512, K >= 1024 ? 1 : 2) void fused_dwpw7_kernel(Fus
         for (int m = 0; m < MW; ++m)
           Wf[(u + WD - 1) % WD][m] = *reinterpret_cast<const v4i*>(wpk + ((size_t)m * KS + kk + WD - 1) * 1024 + wlane);
       }
+      // the requests stay in front of this K-step's MFMAs (only LDS reads may cross): left to itself the scheduler moves each
+      // request down to its first use to save registers, and the ring is one deep whatever WD says
+      __builtin_amdgcn_sched_barrier(0x100);
       const uint32_t ka = trb + (uint32_t)kk * (32 * F7_PITCH);
 #pragma unroll
       for (int n = 0; n < 2; ++n) {

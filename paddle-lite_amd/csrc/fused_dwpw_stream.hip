@@ -249,8 +249,17 @@ __global__ __launch_bounds__(256, M / MP >= 256 ? 2 : 3) void fused_dwpw_stream_
   // parity; k half h -> kg {2h, 2h + 1}
   const uint32_t trb = (uint32_t)(((h * 2) * 8 + ((lane & 15) >> 1)) * FS_PITCH + ((lane >> 4) & 1) * 16 + (lane & 1) * 8 + n0 * 32);
   const uint32_t wlane = (uint32_t)lane * 16;
-  // weight fragments WD - 1 K-steps ahead (from L2: ~1 us each; two slots where the accumulators leave no registers)
-  constexpr int WD = KS < 4 || NW * MW * 16 > 112 ? 2 : 4;
+  // weight fragments ahead of the MFMAs (from L2: ~1 us each, a K-step is NW MW MFMAs of 32 cycles: with two slots every K-step
+  // waited for its weights).  The ring's depth comes from the registers the shape has left: accumulators + ring within WBUDGET
+  // of the 256 (the rest: row windows, addresses, the epilogue's temporaries).  A whole pass where it fits (WD = KS: every
+  // fragment of the pass requested at once, pass 0's under the depthwise arithmetic, the next pass's under the epilogue), else
+  // four slots, else two (the 28-wide forms: 224 registers of accumulators)
+  constexpr int WBUDGET = 192, ACCR = NW * MW * 16;
+  constexpr int WD = KS < 4 ? 2 : (ACCR + KS * MW * 4 <= WBUDGET ? KS : (ACCR + 4 * MW * 4 <= WBUDGET ? 4 : 2));
+  constexpr int WPRE = WD == KS ? KS : WD - 1;  // fragments requested ahead of a pass's first K-step
+  // the activation fragments (two transposed LDS reads each) a few n tiles ahead of their MFMAs, in the forms that run one wave
+  // per SIMD (M / MP >= 256: nobody else covers the LDS round trip, which came in front of every MW MFMAs) and have the registers
+  constexpr bool ALOOK = M / MP >= 256 && NSPLIT == 1 && ACCR + WD * MW * 4 <= WBUDGET;
   v4i Wf[WD][MW];
   float psc[2][MW], pbi[2][MW];  // [pass parity]
   auto pass_w = [&](int mp) { return reinterpret_cast<const uint8_t*>(g.wp) + (size_t)((mp * MSPLIT + ms) * MW) * KS * 1024; };  // [mt][ks][64 lanes][16 B]
@@ -259,7 +268,7 @@ __global__ __launch_bounds__(256, M / MP >= 256 ? 2 : 3) void fused_dwpw_stream_
     const uint8_t* const wpk = pass_w(mp);
     const int mt0 = (mp * MSPLIT + ms) * MW;
 #pragma unroll
-    for (int u = 0; u < WD - 1 && u < KS; ++u)
+    for (int u = 0; u < WPRE && u < KS; ++u)
 #pragma unroll
       for (int m = 0; m < MW; ++m) Wf[u][m] = *reinterpret_cast<const v4i*>(wpk + ((size_t)m * KS + u) * 1024 + wlane);
 #pragma unroll
@@ -310,20 +319,40 @@ __global__ __launch_bounds__(256, M / MP >= 256 ? 2 : 3) void fused_dwpw_stream_
       // (the first K-step multiplies into the constant 0, an inline operand of the MFMA: zeroing the accumulators first was
       // 16 v_mov per tile, 110-130 per wave = 4-6 % of everything these kernels issue)
       const v16i zero16 = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+      // the activation fragment of (K-step, n tile): two transposed reads
+      auto afrag = [&](int ks, int n) __attribute__((always_inline)) {
+        const uint32_t ka = trb + (uint32_t)ks * (32 * FS_PITCH) + n * 32;
+        const v2i lo = __builtin_amdgcn_ds_read_tr8_b64_v2i32((lds_v2i_ptr_t)(fs_lds + ka));
+        const v2i hi = __builtin_amdgcn_ds_read_tr8_b64_v2i32((lds_v2i_ptr_t)(fs_lds + ka + 8 * FS_PITCH));
+        const v4i av = {lo[0], lo[1], hi[0], hi[1]};
+        return av;
+      };
+      constexpr int AL = 3;  // 3 tiles of MW MFMAs = 192 cycles against the LDS round trip
+      static_assert(!ALOOK || AL < KS * NW, "lookahead");
+      v4i aq[AL + 1];
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks) {
-        if (ks + WD - 1 < KS) {
+        if (ks + WPRE < KS) {
 #pragma unroll
           for (int m = 0; m < MW; ++m)
-            Wf[(ks + WD - 1) % WD][m] = *reinterpret_cast<const v4i*>(wpk + ((size_t)m * KS + ks + WD - 1) * 1024 + wlane);
+            Wf[(ks + WPRE) % WD][m] = *reinterpret_cast<const v4i*>(wpk + ((size_t)m * KS + ks + WPRE) * 1024 + wlane);
         }
-        const uint32_t ka = trb + (uint32_t)ks * (32 * FS_PITCH);
 #pragma unroll
         for (int n = 0; n < NW; ++n) {
-          if (n < nmine) {
-            const v2i lo = __builtin_amdgcn_ds_read_tr8_b64_v2i32((lds_v2i_ptr_t)(fs_lds + ka + n * 32));
-            const v2i hi = __builtin_amdgcn_ds_read_tr8_b64_v2i32((lds_v2i_ptr_t)(fs_lds + ka + n * 32 + 8 * FS_PITCH));
-            const v4i av = {lo[0], lo[1], hi[0], hi[1]};
+          if (ALOOK || n < nmine) {  // (ALOOK: NSPLIT == 1, every wave owns all NW n tiles)
+            v4i av;
+            if constexpr (ALOOK) {  // this tile's fragment is on its way; request the one AL tiles on in front of this tile's MFMAs
+              const int i = ks * NW + n;
+              if (i == 0) {
+#pragma unroll
+                for (int j = 0; j < AL; ++j) aq[j] = afrag(j / NW, j % NW);
+              }
+              if (i + AL < KS * NW) aq[(i + AL) % (AL + 1)] = afrag((i + AL) / NW, (i + AL) % NW);
+              __builtin_amdgcn_sched_barrier(0);  // (the scheduler moves a request down to its first use)
+              av = aq[i % (AL + 1)];
+            } else {
+              av = afrag(ks, n);
+            }
 #pragma unroll
             for (int m = 0; m < MW; ++m)
               acc[n][m] = __builtin_amdgcn_mfma_i32_32x32x32_i8(av, Wf[ks % WD][m], ks == 0 ? zero16 : acc[n][m], 0, 0, 0);

@@ -46,7 +46,7 @@ with capi.Context(0) as ctx:
     ctx.sync()
     st = capi.read_stamps("f7", (1024, 8, 8)) if small else capi.read_stamps("fs", (2048, 4, 8))
 if small:
-    nt = min(1024, 2 * B)
+    nt = min(1024, (2 if os.environ.get("PLHIP_FUSED_SMALL") == "2" else 1) * B)  # blocks per image: the plan's MB
     names = ["entry", "first operands requested", "parameters staged", "produced", "behind the barrier", "multiplied"]
 else:
     tp = 448 if oh == 112 else (128 if oh == 14 else 224)
