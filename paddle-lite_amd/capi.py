@@ -367,6 +367,7 @@ def _outer_inner(shape, axis):
 
 
 SCOPE_SLACK = 64  # bytes every DeviceScope allocation has behind its tensor, beyond any guard
+MARGIN_GUARD = 64  # bytes a helper that returns an output's margins adds on both sides of it
 
 
 class DeviceOut:
@@ -392,6 +393,9 @@ class _NoOut:
     ptr = None
 
     def get(self):
+        return None
+
+    def margins(self):
         return None
 
 
@@ -449,9 +453,9 @@ class DeviceScope:
         base, total = self._place(nbytes, off, fill, guard)
         return DeviceOut(self.ctx, base, total, guard + off, shape, dtype)
 
-    def out_opt(self, wanted, shape, dtype, off=0):
-        """out() of an optional output: a handle with a null .ptr whose .get() is None when not wanted."""
-        return self.out(shape, dtype, off) if wanted else _NoOut()
+    def out_opt(self, wanted, shape, dtype, off=0, fill=None, guard=0):
+        """out() of an optional output: a handle with a null .ptr whose .get() and .margins() are None when not wanted."""
+        return self.out(shape, dtype, off, fill, guard) if wanted else _NoOut()
 
     def out_by_mode(self, shape, mode, misalign):
         """The outputs `mode` names ("f32", "i8" or "both") as the handle pair (f32, i8), each base `misalign` ELEMENTS off its
@@ -668,23 +672,31 @@ class Context:
             return self.to_host(y.ptr, (d_dw.n, cout, 1, 1), np.float32) if out_kind == OUT_F32_GAP else y.get()
 
     def dw_conv1x1_fused(self, d_dw, x, w_dw, s_dw, b_dw, w_pw, s_pw, b_pw, pw_act, pw_alpha, out_kind,
-                         residual=None, residual_relu=0, calib_scale=None, want_y=True):
+                         residual=None, residual_relu=0, calib_scale=None, want_y=True, misalign=0, sentinel=None):
         """Fused depthwise 3x3 -> 1x1 conv with the conv's graph tail (plhip_dw_conv1x1_fused_int8) on host arrays:
-        returns (y or None, y_i8 or None); y is of `out_kind`, y_i8 the calib copy when calib_scale is given."""
+        returns (y or None, y_i8 or None); y is of `out_kind`, y_i8 the calib copy when calib_scale is given.  misalign: (x, y,
+        y_i8): x starts that many BYTES past a 16-byte boundary (off 4 bytes the kernel stages its rows byte by byte), y that
+        many ELEMENTS, y_i8 that many bytes; one number stands for all three.  sentinel: a byte value both output allocations
+        (MARGIN_GUARD more bytes on either side) are filled with first; the result is then (y, y_i8, the bytes around y, the
+        bytes around y_i8), None for an output not asked for."""
         oh, ow = out_hw(d_dw)
         cout = w_pw.shape[0]
         shape = (d_dw.n, cout, oh, ow)
         d_pw = conv_desc(d_dw.n, d_dw.cin, oh, ow, cout, 1, 1, act=pw_act, alpha=pw_alpha)
+        xo, yo, qo = (misalign,) * 3 if isinstance(misalign, int) else misalign
+        ydt = np.dtype(_OUT_DTYPE[out_kind])
+        guard = 0 if sentinel is None else MARGIN_GUARD
         with self.scope() as s:
-            dx, dwd, dsd, dbd = s.put(x, np.int8), s.put(w_dw, np.int8), s.put(s_dw, np.float32), s.put_opt(b_dw, np.float32)
+            dx, dwd, dsd, dbd = s.put(x, np.int8, off=xo), s.put(w_dw, np.int8), s.put(s_dw, np.float32), s.put_opt(b_dw, np.float32)
             dwp = self._packed_conv(s, d_pw, w_pw)
             dsp, dbp, dr = s.put_opt(s_pw, np.float32), s.put_opt(b_pw, np.float32), s.put_opt(residual, np.float32)
-            y, yq = s.out_opt(want_y, shape, _OUT_DTYPE[out_kind]), s.out_opt(calib_scale is not None, shape, np.int8)
+            y = s.out_opt(want_y, shape, ydt, yo * ydt.itemsize, sentinel, guard)
+            yq = s.out_opt(calib_scale is not None, shape, np.int8, qo, sentinel, guard)
             self.check(self.L.plhip_dw_conv1x1_fused_int8(self.h, C.byref(d_dw), dx, dwd, dsd, dbd, cout, dwp, dsp, dbp, pw_act,
                                                           pw_alpha, y.ptr, out_kind, dr, int(residual_relu), yq.ptr,
                                                           float(calib_scale) if calib_scale is not None else 0.0),
                        "dw_conv1x1_fused")
-            return y.get(), yq.get()
+            return (y.get(), yq.get()) if sentinel is None else (y.get(), yq.get(), y.margins(), yq.margins())
 
     def fc(self, x, w, scale, bias, relu, out_kind):
         x = np.ascontiguousarray(x, np.int8)

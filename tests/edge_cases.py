@@ -177,6 +177,12 @@ ROUTES = [
     # 8 channels give the anchors 8 draws: seeds at which every one of them is hit
     _r("dw3x3s1_rs8", "dw", (2, 8, 8, 8, 8, 3, 3, (1,) * 4, 1, 1, 8), kernel="dw_direct KS=3 S=1 RS=8 STAGE=1 FASTV=1", seed_row=42),
     _r("dw3x3s1_rs4", "dw", (2, 8, 4, 12, 8, 3, 3, (1,) * 4, 1, 1, 8), kernel="dw_direct KS=3 S=1 RS=4 STAGE=1 FASTV=1", seed_row=47),
+    # fusion G off the square 14 x 14 plane (dwconv_cases.py has the whole launch plan): stride 2 without left / top padding,
+    # a 130-wide row (two 128-column segments, the second ragged, rows staged byte by byte; 16 channels: a stated seed), a ragged
+    # last M group with an M tail
+    _r("dw_conv1x1_s2_pl0", "dwconv", (2, 32, 9, 12, 32, 3, 3, (0, 1, 0, 1), 2, 1, 32), m=24, kernel="dw_conv1x1"),
+    _r("dw_conv1x1_wide130", "dwconv", (1, 16, 3, 130, 16, 3, 3, (1,) * 4, 1, 1, 16), m=16, kernel="dw_conv1x1", seed_row=55),
+    _r("dw_conv1x1_ragged_m", "dwconv", (1, 32, 14, 14, 32, 3, 3, (1,) * 4, 1, 1, 32), m=264, kernel="dw_conv1x1"),
 ]
 
 

@@ -121,7 +121,7 @@ BATCH_ROUTES = {"dwpw_14x14": (1, 7, 8, 9, 17, 128, 129), "dwpw_7x7": (1, 7, 8, 
                 "stem_f32_calib": (1, 7, 8, 9, 17, 128, 129), "stem_u8_image": (1, 7, 8, 9, 17, 128, 129),
                 "dwpw_stream_s2": (1, 7, 8, 9, 17), "dwpw_stream": (1, 7, 8, 9, 17), "stem7x7s2": (1, 7, 8, 9, 17),
                 "direct3x3s2_mfma": (1, 7, 8, 9, 17), "dw3x3s1_direct": (1, 7, 8, 9, 17), "gemm_ring": (1, 7, 8, 9, 17),
-                "gemm_wide_n4": (1, 7, 8, 9, 17)}
+                "gemm_wide_n4": (1, 7, 8, 9, 17), "dw_conv1x1_wide130": (1, 7, 8, 9, 17)}
 POISON = 0xA5
 
 
@@ -168,6 +168,9 @@ def _y(ctx, capi, route, c, act, alpha):
         return ctx.conv2d_image(d, img, c["src"], E.IMG_CALIB, c["w"], c["scale"], c["bias"], capi.OUT_I8)
     cin, pads, st = route["shape"][1], route["shape"][7], route["shape"][8]
     d_dw = capi.conv_desc(n, cin, h, w, cin, 3, 3, pads, (st, st), (1, 1), cin, c["dw_act"], c["dw_alpha"])
+    if kind == "dwconv":
+        return ctx.dw_conv1x1_fused(d_dw, c["x"], c["w_dw"], c["s1"], c["b1"], c["w"], c["scale"], c["bias"], act, alpha, capi.OUT_I8)[0]
+    assert kind == "dwpw", kind
     return ctx.dwpw_fused(d_dw, c["x"], c["w_dw"], c["s1"], c["b1"], c["w"], c["scale"], c["bias"], act, alpha, capi.OUT_I8)
 
 
