@@ -193,16 +193,26 @@ KNOBS = ("STEM_MFMA", "CONV_PATCH", "CONV_PATCH_S2", "STEM7", "DW_STAGE", "DW_ST
 KNOBS_SET = {}
 
 
-TAIL_RESIDUAL, TAIL_INT8_COPY, TAIL_NO_F32 = 1, 2, 4
+TAIL_RESIDUAL, TAIL_INT8_COPY, TAIL_NO_F32, TAIL_UNALIGNED = 1, 2, 4, 8
 
 
 def gemm_plan_text(d, out, tail=0):
     """The GEMM launch plan (csrc/gemm_plan.h) the library makes for conv descriptor d with output kind `out` and the fused tail
-    `tail` (TAIL_* bits) under the knobs in force, assuming aligned pointers: 'name family=... grid=... lds=...'.  '' for a conv
-    on a non-GEMM route.  Host only: launches nothing, needs no context."""
+    `tail` (TAIL_* bits) under the knobs in force: 'name family=... grid=... lds=...'.  Pointers are assumed aligned unless
+    TAIL_UNALIGNED says that an output or the residual is off its vector alignment.  '' for a conv on a non-GEMM route.  Host
+    only: launches nothing, needs no context."""
     buf = C.create_string_buffer(512)
     if load().plhip_debug_gemm_plan(C.byref(d), int(out), int(tail), buf, len(buf)) < 0:
         raise PlhipError("plhip_debug_gemm_plan: bad conv descriptor")
+    return buf.value.decode()
+
+
+def patch_plan_text(d):
+    """The patch kernel's launch plan (conv_patch_plan, csrc/conv_patch_i8.hip) of conv descriptor d on one of the two patch
+    routes: 'patch_stat_a glob=... TPI=... pitch=...'.  '' for a conv on another route.  Host only."""
+    buf = C.create_string_buffer(512)
+    if load().plhip_debug_patch_plan(C.byref(d), buf, len(buf)) < 0:
+        raise PlhipError("plhip_debug_patch_plan: bad conv descriptor")
     return buf.value.decode()
 
 
@@ -292,6 +302,8 @@ def load():
     # diagnostics outside include/plhip.h: the GEMM launch plan of a conv as text (gemm_plan_text below), the wide tile override
     L.plhip_debug_gemm_plan.argtypes = [C.POINTER(ConvDesc), i32, i32, C.c_char_p, sz]
     L.plhip_debug_gemm_plan.restype = i32
+    L.plhip_debug_patch_plan.argtypes = [C.POINTER(ConvDesc), C.c_char_p, sz]
+    L.plhip_debug_patch_plan.restype = i32
     L.plhip_debug_dw_plan.argtypes = [C.POINTER(ConvDesc), i32, i32, i32, i32, i32, C.c_char_p, sz]
     L.plhip_debug_dw_plan.restype = i32
     L.plhip_debug_wide_ntt.argtypes = [i32]
@@ -643,19 +655,27 @@ class Context:
                        "conv2d_image")
             return y.get()
 
-    def conv2d_fused(self, d, x, w, scale, bias, residual, residual_relu, calib_scale, want_f32=True):
-        """plhip_conv2d_int8_fused on host arrays: returns (y_f32 or None, y_i8 or None)."""
+    def conv2d_fused(self, d, x, w, scale, bias, residual, residual_relu, calib_scale, want_f32=True, misalign=0, sentinel=None):
+        """plhip_conv2d_int8_fused on host arrays: returns (y_f32 or None, y_i8 or None).  misalign: (x, y, residual, y_i8), as in
+        dw_conv1x1_fused: x and y_i8 start that many BYTES past a 16-byte boundary, y and the residual that many ELEMENTS; one
+        number stands for all four.  sentinel: a byte value both output allocations (MARGIN_GUARD more bytes on either side)
+        are filled with first; the result is then (y_f32, y_i8, the bytes around y_f32, the bytes around y_i8), None for an
+        output not asked for."""
         oh, ow = out_hw(d)
         shape = (d.n, d.cout, oh, ow)
+        xo, yo, ro, qo = (misalign,) * 4 if isinstance(misalign, int) else misalign
+        guard = 0 if sentinel is None else MARGIN_GUARD
         with self.scope() as s:
-            dx, ds = s.put(x, np.int8), s.put(scale, np.float32)
-            db, dr = s.put_opt(bias, np.float32), s.put_opt(residual, np.float32)
-            yf, yq = s.out_opt(want_f32, shape, np.float32), s.out_opt(calib_scale is not None, shape, np.int8)
+            dx, ds = s.put(x, np.int8, off=xo), s.put(scale, np.float32)
+            db = s.put_opt(bias, np.float32)
+            dr = s.put(residual, np.float32, off=4 * ro) if residual is not None else C.c_void_p()
+            yf = s.out_opt(want_f32, shape, np.float32, 4 * yo, sentinel, guard)
+            yq = s.out_opt(calib_scale is not None, shape, np.int8, qo, sentinel, guard)
             dwp = self._packed_conv(s, d, w)
             dws, wsb = self._conv_workspace(s, d)
             self.check(self.L.plhip_conv2d_int8_fused(self.h, C.byref(d), dx, dwp, ds, db, yf.ptr, dr, int(residual_relu), yq.ptr,
                                                       float(calib_scale) if calib_scale is not None else 0.0, dws, wsb), "conv2d_fused")
-            return yf.get(), yq.get()
+            return (yf.get(), yq.get()) if sentinel is None else (yf.get(), yq.get(), yf.margins(), yq.margins())
 
     def dwpw_fused(self, d_dw, x, w_dw, s_dw, b_dw, w_pw, s_pw, b_pw, pw_act, pw_alpha, out_kind):
         """Fused depthwise -> pointwise through the C ABI (host arrays in, host array out)."""

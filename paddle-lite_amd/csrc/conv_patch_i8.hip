@@ -274,8 +274,11 @@ static inline void magic_u31(long d, unsigned& m, int& sh, bool general_pow2 = f
   }
 }
 
-void launch_conv_patch(PatchArgs a, int out, hipStream_t s) {
-  PLHIP_SET_STAMPS(a, "patch", sizeof(unsigned long long) * 512 * 8 * PATCH_STAMP_SLOTS);
+// The launch plan of the patch kernel: ONE pure host function.  The caller has set the shape half of `a` (B, C, M, OH, OW, PWp,
+// PLANE, s2); this fills every field the kernel reads of the plan (global mode, tiles, blocks, the LDS pitch, the magic numbers)
+// and names the launcher.  launch_conv_patch executes it, plhip_debug_patch_plan prints it for the tests.
+int conv_patch_plan(PatchArgs* pa) {
+  PatchArgs& a = *pa;
   a.NCH = a.C / 32;
   a.HWY = a.OH * a.OW;
   a.y_bstride = (size_t)a.M * a.HWY;
@@ -317,10 +320,24 @@ void launch_conv_patch(PatchArgs a, int out, hipStream_t s) {
   magic_u31(a.PWp, a.pw_m, a.pw_s, true);
   magic_u31(a.TPI, a.tpi_m, a.tpi_s);
   magic_u31(a.pitch, a.pitch_m, a.pitch_s);
-  if (a.s2) launch_patch_s2(a, out, s);
-  else if (layout_b) launch_patch_stat_b(a, out, s);
-  else if (stat) launch_patch_stat_a(a, out, s);
-  else launch_patch_stream_a(a, out, s);
+  return a.s2 ? PATCH_S2 : layout_b ? PATCH_STAT_B : stat ? PATCH_STAT_A : PATCH_STREAM_A;
+}
+
+// the plan as one line of text (plhip_debug_patch_plan)
+int conv_patch_plan_text(const PatchArgs& a, int launcher, char* buf, size_t cap) {
+  static const char* const names[] = {"patch_stat_a", "patch_stat_b", "patch_stream_a", "patch_s2"};
+  return snprintf(buf, cap, "%s glob=%d NCH=%d TPI=%d T=%d T8=%d MB=%d NQ=%d rounds=%d pitch=%d PWp=%d PLANE=%d B=%d OH=%d OW=%d M=%d",
+                  names[launcher], a.glob, a.NCH, a.TPI, a.T, a.T8, a.MB, a.NQ, a.rounds, a.pitch, a.PWp, a.PLANE, a.B, a.OH, a.OW, a.M);
+}
+
+void launch_conv_patch(PatchArgs a, int out, hipStream_t s) {
+  PLHIP_SET_STAMPS(a, "patch", sizeof(unsigned long long) * 512 * 8 * PATCH_STAMP_SLOTS);
+  switch (conv_patch_plan(&a)) {
+    case PATCH_S2: launch_patch_s2(a, out, s); break;
+    case PATCH_STAT_B: launch_patch_stat_b(a, out, s); break;
+    case PATCH_STAT_A: launch_patch_stat_a(a, out, s); break;
+    default: launch_patch_stream_a(a, out, s); break;
+  }
 }
 
 void launch_patch_stat_a(const PatchArgs& a, int out, hipStream_t s) { launch_patch_o<1, 4, 1, 3, 4, true>(a, out, s); }

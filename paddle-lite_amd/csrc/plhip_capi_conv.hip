@@ -287,25 +287,33 @@ plhip_status pack_patch_s2(plhip_ctx* ctx, Desc d, Geom, const int8_t* w_oihw, v
   plhip::launch_pack_conv_patch_s2(w_oihw, (int8_t*)w_packed, d->cin, d->cout, ctx->stream);
   return PLHIP_OK;
 }
+// the shape half of the patch kernel's arguments (what conv_patch_plan reads); *ph: the rows of a plane of the padded copy
+plhip::PatchArgs patch_args(Desc d, Geom g, bool s2, int* ph) {
+  int PWp = plhip::conv_patch_row_pitch(d->w, d->pad[2], d->pad[3]), PH = d->h + d->pad[0] + d->pad[1];
+  if (s2) patch_s2_dims(d, &PH, &PWp);
+  plhip::PatchArgs a;
+  memset(&a, 0, sizeof(a));
+  a.B = d->n; a.M = d->cout; a.OH = g.oh; a.OW = g.ow;
+  a.C = s2 ? 4 * d->cin : d->cin;  // the kernel's channels: stride 2 = (channel, row phase, column phase)
+  a.PWp = PWp; a.PLANE = PH * PWp; a.s2 = s2 ? 1 : 0;
+  a.act = d->act; a.alpha = d->act_alpha;
+  *ph = PH;
+  return a;
+}
 plhip_status run_patch_any(plhip_ctx* ctx, Desc d, Geom g, const ConvIo& io, bool s2) {
   const size_t need = s2 ? patch_s2_input_bytes(d, g) : patch_input_bytes(d, g);
   if (!io.workspace || io.workspace_bytes < need || !aligned(io.workspace, 16))
     return fail(ctx, PLHIP_ERR_WORKSPACE, "plhip_conv2d_int8: padded-input workspace missing, too small or unaligned (16 bytes)");
-  int PWp = plhip::conv_patch_row_pitch(d->w, d->pad[2], d->pad[3]), PH = d->h + d->pad[0] + d->pad[1];
-  if (s2) patch_s2_dims(d, &PH, &PWp);
-  const int CE = s2 ? 4 * d->cin : d->cin;  // the kernel's channels: stride 2 = (channel, row phase, column phase)
+  int PH;
+  plhip::PatchArgs a = patch_args(d, g, s2, &PH);
+  const int PWp = a.PWp, CE = a.C;
   plhip::PadArgs pa = pad_args(d, io, d->n * CE, PH, PWp, need);
   pa.tb = plhip::conv_patch_global(PWp) ? d->n : 0;  // planes smaller than a tile: channel-major copy
   pa.tc = CE;
   if (s2) plhip::launch_pad_phase8(pa, ctx->stream);
   else plhip::launch_pad_rows8(pa, ctx->stream);
   LAUNCHCHK(ctx, "pad_rows8");
-  plhip::PatchArgs a;
-  memset(&a, 0, sizeof(a));
   a.xp = (const int8_t*)io.workspace; a.wp = (const int8_t*)io.w_packed; a.y = io.y; a.scale = io.scale; a.bias = io.bias;
-  a.B = d->n; a.C = CE; a.M = d->cout; a.OH = g.oh; a.OW = g.ow;
-  a.PWp = PWp; a.PLANE = PH * PWp; a.s2 = s2 ? 1 : 0;
-  a.act = d->act; a.alpha = d->act_alpha;
   set_tail(a, io.tail);
   plhip::launch_conv_patch(a, (int)io.out, ctx->stream);
   LAUNCHCHK(ctx, "conv_patch");
@@ -479,8 +487,9 @@ const char* plhip_conv_impl_name(const plhip_conv_desc* d) {
 
 // Diagnostics, host only (not in include/plhip.h; paddle-lite_amd/capi.py declares it): the GEMM launch plan (gemm_plan.h) of a
 // conv on one of the three GEMM routes, as text, from the route's own argument builder and the knobs in force, assuming aligned
-// pointers.  out: the output kind; tail: bit 0 a residual, bit 1 the int8 copy, bit 2 the fp32 output dropped.  A non-GEMM route
-// answers the empty string.  Returns the text's length, or -1 for a bad descriptor or buffer.
+// pointers.  out: the output kind; tail: bit 0 a residual, bit 1 the int8 copy, bit 2 the fp32 output dropped, bit 3 an output or
+// residual pointer is off its vector alignment (what vec_store_ok answers for the call's pointers).  A non-GEMM route answers the
+// empty string.  Returns the text's length, or -1 for a bad descriptor or buffer.
 int plhip_debug_gemm_plan(const plhip_conv_desc* d, int out, int tail, char* buf, size_t cap) {
   ConvGeom g;
   const ConvRoute* r = pick_route(d, &g);
@@ -491,11 +500,26 @@ int plhip_debug_gemm_plan(const plhip_conv_desc* d, int out, int tail, char* buf
   else if (r->impl == IMPL_IM2COL_GEMM) c = gemm_call(d, g, gemm_b_im2col(d, g), 0);
   else if (r->impl == IMPL_IMPLICIT_GEMM) c = implicit_call(d, g);
   else return 0;
-  plhip::GemmProblem p = plhip::gemm_problem(c.a, g.MA, out, c.vec_store, c.aligned_loads);
+  plhip::GemmProblem p = plhip::gemm_problem(c.a, g.MA, out, c.vec_store && (tail & 8) == 0, c.aligned_loads);
   p.res = (tail & 1) != 0;
   p.y2 = (tail & 2) != 0;
   p.y = (tail & 4) == 0;
   return plhip::gemm_plan_text(plhip::gemm_plan(p, plhip::gemm_knobs()), buf, cap);
+}
+
+// Diagnostics, host only: the patch kernel's launch plan (conv_patch_plan, the function launch_conv_patch executes) of a conv on
+// one of the two patch routes, as one line of text: the launcher, global mode, tiles, blocks and the LDS pitch.  Another route
+// answers the empty string.  Returns the text's length, or -1 for a bad descriptor or buffer.
+int plhip_debug_patch_plan(const plhip_conv_desc* d, char* buf, size_t cap) {
+  ConvGeom g;
+  const ConvRoute* r = pick_route(d, &g);
+  if (!r || !buf || cap == 0) return -1;
+  buf[0] = 0;
+  if (r->impl != IMPL_PATCH_GEMM && r->impl != IMPL_PATCH_S2) return 0;
+  int PH;
+  plhip::PatchArgs a = patch_args(d, g, r->impl == IMPL_PATCH_S2, &PH);
+  const int launcher = plhip::conv_patch_plan(&a);
+  return plhip::conv_patch_plan_text(a, launcher, buf, cap);
 }
 
 static plhip_status conv2d_impl(plhip_ctx* ctx, const plhip_conv_desc* d, const ConvIo& io) {

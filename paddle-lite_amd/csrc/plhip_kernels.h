@@ -119,7 +119,11 @@ bool conv_patch_global(int pwp);  // planes smaller than a tile: channel-major p
 bool conv_patch_supported(int cin, int cout, int kh, int kw, int sh, int sw, int dh, int dw, int groups, int w, int pl, int pr);
 size_t conv_patch_packed_bytes(int cin, int cout);
 void launch_pack_conv_patch(const int8_t* w_oihw, int8_t* wp, int cin, int cout, hipStream_t s);
-// fills the launch plan of `a` (B, C, M, OH, OW, PWp, PLANE set by the caller) and launches
+// the launch plan of `a` (B, C, M, OH, OW, PWp, PLANE, s2 set by the caller): fills the plan's fields, returns the launcher
+enum PatchLauncher { PATCH_STAT_A = 0, PATCH_STAT_B, PATCH_STREAM_A, PATCH_S2 };
+int conv_patch_plan(PatchArgs* a);
+int conv_patch_plan_text(const PatchArgs& a, int launcher, char* buf, size_t cap);  // one line of text
+// makes the plan of `a` and launches it
 void launch_conv_patch(PatchArgs a, int out, hipStream_t s);
 void launch_patch_stat_a(const PatchArgs& a, int out, hipStream_t s);    // per-variant translation units
 void launch_patch_stat_b(const PatchArgs& a, int out, hipStream_t s);
