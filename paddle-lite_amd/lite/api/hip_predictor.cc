@@ -100,6 +100,9 @@ Tensor* HipPredictor::AddFeed(const std::string& name, const std::vector<int64_t
   const size_t esz = prec == PRECISION(kInt8) || prec == PRECISION(kUInt8) ? 1 : 4;
   t->mutable_data(TARGET(kHost), static_cast<size_t>(t->numel()) * esz);
   t->set_precision(prec);
+  // a feed declared again: the kernel objects re-initialise on the next run (repacked weights, private tensors, grown buffers),
+  // and none of those addresses is in GraphKey — a recorded launch graph is stale even if every shape comes back to what it was
+  graph_stale_ = true;
   return t;
 }
 
@@ -654,7 +657,8 @@ std::vector<std::string> HipPredictor::KernelNames() {
   return r;
 }
 
-// Everything a recorded launch graph has baked in: the shape of every variable (grid sizes, strides), the instruction list
+// Everything a recorded launch graph has baked in: the shape of every variable (grid sizes, strides) and the address of every device
+// variable (Buffer::ResetLazy grows only: a feed resized up and back leaves the old shapes at new addresses), the instruction list
 // and the workspace arena (its address is a kernel argument; HipExecState::Workspace frees the arena when it grows).
 size_t HipPredictor::GraphKey() const {
   size_t h = 1469598103934665603ULL;
@@ -666,6 +670,7 @@ size_t HipPredictor::GraphKey() const {
     const auto d = kv.second->dims();
     mix(d.size());
     for (size_t i = 0; i < d.size(); ++i) mix(static_cast<size_t>(d[i]));
+    if (kv.second->target() == TARGET(kHIP)) mix(reinterpret_cast<size_t>(kv.second->raw_data()));
   }
   return h;
 }
@@ -675,7 +680,7 @@ void HipPredictor::RunGraph() {
   plhip_ctx* ctx = state()->ctx();
   // a feed resized, an instruction added or the arena re-allocated since the recording: the graph is stale (it would read
   // freed memory / use old shapes): drop it and record again
-  if (graph_exec_ && graph_key_ != GraphKey()) {
+  if (graph_exec_ && (graph_stale_ || graph_key_ != GraphKey())) {
     (void)plhip_graph_destroy(ctx, graph_exec_);
     graph_exec_ = nullptr;
   }
@@ -694,6 +699,7 @@ void HipPredictor::RunGraph() {
     }
     HIP_CALL(ctx, plhip_graph_end(ctx, &graph_exec_));
     graph_key_ = GraphKey();
+    graph_stale_ = false;
   }
   HIP_CALL(ctx, plhip_graph_launch(ctx, graph_exec_));
 }

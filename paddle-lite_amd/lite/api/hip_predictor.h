@@ -181,6 +181,7 @@ class HipPredictor {
   std::shared_ptr<HipExecState> state_;
   void* graph_exec_{nullptr};  // plhip launch graph of the program (RunGraph)
   size_t graph_key_{0};        // what the recorded graph depends on: shapes of every variable, instruction count, workspace arena
+  bool graph_stale_{false};    // AddFeed since the recording: addresses GraphKey does not see may have changed (RunGraph records again)
   size_t GraphKey() const;
   std::map<std::string, std::unique_ptr<Tensor>> vars_;
   std::vector<std::unique_ptr<Tensor>> params_;

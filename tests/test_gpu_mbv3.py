@@ -8,6 +8,7 @@ import pytest
 
 import glue_cases as G
 import mbv3_oracle as M
+from replay_cases import written
 
 pytestmark = pytest.mark.gpu
 F32 = np.float32
@@ -262,21 +263,6 @@ def _run(lite, wl, net, img, fuse, fuse_hard_act=None):
         raise
 
 
-def _written(plan):
-    """The device variables a plan writes, read off its lines: every out= (not behind -f32, not the host copy), every +calib=."""
-    names = set()
-    for l in plan:
-        toks = l.split(" ")
-        kv = dict(f.split("=", 1) for f in toks[1:] if "=" in f)
-        if l.startswith("io_copy/device_to_host"):
-            continue
-        if "-f32" not in toks:
-            names.add(kv["out"])
-        if "+calib" in kv:
-            names.add(kv["+calib"])
-    return names
-
-
 def _check(p, name, want, out):
     got = p.get_var(name, want.dtype)
     assert got.shape == want.shape, name
@@ -299,7 +285,7 @@ def test_mobilenet_v3_program_vs_oracle(lite, wl, plref, variant, n_se):
     try:
         names = "\n".join(pu.kernel_names())
         assert "hard_swish_hip" in names and "hard_sigmoid_hip" in names and "se_scale_hip" in names
-        assert {n for n in _written(plan_u) if "/target_trans" not in n} == set(ref)
+        assert {n for n in written(plan_u) if "/target_trans" not in n} == set(ref)
         for name, want in ref.items():
             _check(pu, name, want, "prob")
         for fha in (None, True):
@@ -311,7 +297,7 @@ def test_mobilenet_v3_program_vs_oracle(lite, wl, plref, variant, n_se):
                     assert "hard_swish_int8_hip" in fnames and (variant != "large" or "hard_swish_fp32_int8_hip" in fnames)
                 else:
                     assert not [k for k in ("se_gate_int8_dot4_hip", "hard_swish_int8_hip", "hard_swish_fp32_int8_hip", "se_scale_int8_hip") if k in fnames]
-                survive = sorted(n for n in _written(plan_f) if n in ref)
+                survive = sorted(n for n in written(plan_f) if n in ref)
                 gone = set(ref) - set(survive)
                 assert len(survive) > len(ref) // 2
                 if fha:  # J2 drops three tensors per block, J3's product is not written; J1's int8 outputs must be there
@@ -341,7 +327,7 @@ def test_mobilenet_v3_large_at_batch_128(lite, wl, plref):
         big, out_b, plan_b = _run(lite, wl, net, img, fuse=True, fuse_hard_act=True)
         try:
             assert [l.split(" ")[0] for l in plan_b] == [l.split(" ")[0] for l in plan_s]
-            names = sorted(n for n in _written(plan_b) if n in ref_mid)
+            names = sorted(n for n in written(plan_b) if n in ref_mid)
             assert len(names) > 60, len(names)
             for name in names:
                 want = ref_mid[name]

@@ -4,13 +4,15 @@ batch 3.  The programs with fusion O on, with O off, and with no graph-level fus
 device-read tensor; against detection_oracle.forward the int8 tensors and the prior boxes are exact, the decoded boxes and the class
 probabilities within 1e-5, and the device's detections are EXACTLY the oracle's multiclass_nms applied to the DEVICE's own boxes
 and probabilities: the chain that leaves nothing unexplained.  The symmetric difference to the oracle's own detections is printed,
-not asserted: it hangs on 1e-5 differences at the two thresholds.  One replay through run_graph() gives the bytes run() gave."""
+not asserted: it hangs on 1e-5 differences at the two thresholds.  One replay through run_graph() into poisoned variables
+gives the bytes run() gave."""
 import importlib
 
 import numpy as np
 import pytest
 
 import detection_oracle as D
+import replay_cases as R
 
 pytestmark = pytest.mark.gpu
 F32 = np.float32
@@ -46,7 +48,7 @@ def oracle(plref, ssdnet):
     return out
 
 
-def _run(lite, wl, net, img, replay=False, **kw):
+def _run(lite, wl, net, img, replay=False, ctx=None, **kw):
     """Lowers and runs the net twice (replay: then once more as a launch graph); returns (name -> array, plan, kernel names)."""
     p = lite.Predictor(0)
     try:
@@ -65,10 +67,18 @@ def _run(lite, wl, net, img, replay=False, **kw):
             return got
         got = read()
         if replay:
-            p.run_graph()
+            # every variable the plan writes but the priors (made on the host once) is poisoned: the replay has to write them all
+            names, kept = R.to_poison(plan, p.kernel_names())
+            assert len(kept) == 17 and "det" in names and "det/count" in names and "priors" in names, kept
+            before = R.read_bytes(p, names)
+            p.run_graph()  # records (after a plain run of its own), then launches
+            R.poison(p, ctx, names)
+            p.run_graph()  # replays
             p.sync()
             again = {"det": p.get_var("det", F32), "det/count": p.get_var("det/count", np.int32)}
             assert again["det"].tobytes() == got["det"].tobytes() and again["det/count"].tobytes() == got["det/count"].tobytes()
+            diff = R.first_difference(plan, R.read_bytes(p, names), before)
+            assert diff is None, "the replayed launch graph differs from run(): " + diff
         lod = p.detections("det")
         return got, plan, p.kernel_names(), lod
     finally:
@@ -76,9 +86,9 @@ def _run(lite, wl, net, img, replay=False, **kw):
 
 
 @pytest.mark.parametrize("batch", [2, 3])
-def test_ssd_mini_net_against_the_oracle_and_between_the_programs(lite, wl, ssdnet, oracle, batch):
+def test_ssd_mini_net_against_the_oracle_and_between_the_programs(lite, wl, ssdnet, oracle, gpu_ctx, batch):
     img, ref = oracle[batch]
-    on, plan_on, kernels_on, lod = _run(lite, wl, ssdnet, img, replay=True, fuse=True, fuse_detection_head=True)
+    on, plan_on, kernels_on, lod = _run(lite, wl, ssdnet, img, replay=True, ctx=gpu_ctx, fuse=True, fuse_detection_head=True)
     off, plan_off, kernels_off, _ = _run(lite, wl, ssdnet, img, fuse=True, fuse_detection_head=False)
     un, plan_un, _, _ = _run(lite, wl, ssdnet, img, fuse=False)
     heads = [l.split(" ")[0] for l in plan_on]

@@ -3,13 +3,14 @@ classifier and arg_max) as a whole program at res 64, batch 2.  The fused progra
 concats) and the unfused one are bit-identical in every fetched and device-read tensor; against deconv_oracle.forward the int8
 tensors are exact and the fp32 ones within 1e-5; the labels equal the oracle's except where its two largest logits are within
 1e-5 of each other, and the count of such pixels is 0 for the committed seed (tests/test_deconv_host.py checks that on the CPU).
-One replay through run_graph() gives the bytes run() gave."""
+One replay through run_graph() into poisoned variables gives the bytes run() gave."""
 import importlib
 
 import numpy as np
 import pytest
 
 import deconv_oracle as D
+import replay_cases as R
 
 pytestmark = pytest.mark.gpu
 F32 = np.float32
@@ -43,7 +44,7 @@ def oracle(plref, unet):
     return img, D.forward(plref, unet, img)
 
 
-def _run(lite, wl, net, img, replay=False, **kw):
+def _run(lite, wl, net, img, replay=False, ctx=None, **kw):
     """Lowers and runs the net twice; returns (name -> array, plan, kernel names)."""
     p = lite.Predictor(0)
     try:
@@ -61,20 +62,26 @@ def _run(lite, wl, net, img, replay=False, **kw):
             return got
         got = read()
         if replay:
+            names, kept = R.to_poison(plan, p.kernel_names())
+            assert kept == ["image/target_trans"] and {"label", "logits"} | {v for v, _ in DEVICE_VARS} <= set(names), (kept, names)
+            before = R.read_bytes(p, names)
             p.run_graph()  # records, then launches
+            R.poison(p, ctx, names)  # every variable the plan writes: the replay has to write them all
             p.run_graph()  # replays
             p.sync()
             again = {v: p.get_var(v, t) for v, t in DEVICE_VARS + (("label", np.int64), ("logits", F32))}
             for v in again:
                 assert again[v].tobytes() == got[v].tobytes(), v + ": the replayed graph differs from run()"
+            diff = R.first_difference(plan, R.read_bytes(p, names), before)
+            assert diff is None, "the replayed graph differs from run(): " + diff
         return got, plan, p.kernel_names()
     finally:
         p.close()
 
 
-def test_unet_mini_net_against_the_oracle_and_between_the_programs(lite, wl, unet, oracle):
+def test_unet_mini_net_against_the_oracle_and_between_the_programs(lite, wl, unet, oracle, gpu_ctx):
     img, ref = oracle
-    on, plan_on, kernels_on = _run(lite, wl, unet, img, replay=True, fuse=True)
+    on, plan_on, kernels_on = _run(lite, wl, unet, img, replay=True, ctx=gpu_ctx, fuse=True)
     un, plan_un, _ = _run(lite, wl, unet, img, fuse=False)
     heads = [l.split(" ")[0] for l in plan_on]
     assert heads.count("conv2d_transpose/fp32_out") == 2 and heads.count("concat/int8") == 2 and len(plan_un) - len(plan_on) == 2

@@ -5,13 +5,14 @@ no graph-level fusion at all are bit-identical in every fetched and device-read 
 are exact and the fp32 head maps within 1e-5; the boxes and scores are within yolo_oracle's derived bounds of the oracle's yolo_box
 applied to the DEVICE's own head maps; and the device's detections are EXACTLY detection_oracle.nms_padded applied to the
 device's own boxes and scores.  The symmetric difference to the oracle's own detections is printed, not asserted.  One replay
-through run_graph() gives the bytes run() gave."""
+through run_graph() into poisoned variables gives the bytes run() gave."""
 import importlib
 
 import numpy as np
 import pytest
 
 import detection_oracle as D
+import replay_cases as R
 import yolo_oracle as Y
 
 pytestmark = pytest.mark.gpu
@@ -49,7 +50,7 @@ def oracle(plref, yolonet):
     return {batch: (_feeds(batch), Y.forward(plref, yolonet, _feeds(batch))) for batch in (2, 3)}
 
 
-def _run(lite, wl, net, feeds, scores_var, replay=False, **kw):
+def _run(lite, wl, net, feeds, scores_var, replay=False, ctx=None, **kw):
     """Lowers and runs the net twice (replay: then once more as a launch graph); returns (name -> array, plan, kernel names, LoD)."""
     p = lite.Predictor(0)
     try:
@@ -66,8 +67,16 @@ def _run(lite, wl, net, feeds, scores_var, replay=False, **kw):
         got.update({v: p.get_var(v, F32) for v in HEADS})
         got.update({v: p.get_var(v, np.int8) for v in INT8_VARS})
         if replay:
-            p.run_graph()
+            # every variable the plan writes is poisoned (the two feeds' device tensors are not the replay's to write)
+            names, kept = R.to_poison(plan, p.kernel_names())
+            assert sorted(kept) == ["image/target_trans", "img_size/target_trans"] and {"det", "det/count", "boxes", scores_var} <= set(names)
+            before = R.read_bytes(p, names)
+            p.run_graph()  # records (after a plain run of its own), then launches
+            R.poison(p, ctx, names)
+            p.run_graph()  # replays
             p.sync()
+            diff = R.first_difference(plan, R.read_bytes(p, names), before)
+            assert diff is None, "the replayed launch graph differs from run(): " + diff
             for v in ("det", "boxes", scores_var):
                 assert p.get_var(v, F32).tobytes() == got[v].tobytes(), v + ": the replayed launch graph differs from run()"
             assert p.get_var("det/count", np.int32).tobytes() == got["det/count"].tobytes()
@@ -77,9 +86,9 @@ def _run(lite, wl, net, feeds, scores_var, replay=False, **kw):
 
 
 @pytest.mark.parametrize("batch", [2, 3])
-def test_yolov3_mini_net_against_the_oracle_and_between_the_programs(lite, wl, yolonet, oracle, batch):
+def test_yolov3_mini_net_against_the_oracle_and_between_the_programs(lite, wl, yolonet, oracle, gpu_ctx, batch):
     feeds, ref = oracle[batch]
-    on, plan_on, kernels_on, lod = _run(lite, wl, yolonet, feeds, "scores", replay=True, fuse=True, fuse_yolo_head=True)
+    on, plan_on, kernels_on, lod = _run(lite, wl, yolonet, feeds, "scores", replay=True, ctx=gpu_ctx, fuse=True, fuse_yolo_head=True)
     off, plan_off, kernels_off, _ = _run(lite, wl, yolonet, feeds, "scores_npc", fuse=True, fuse_yolo_head=False)
     un, plan_un, _, _ = _run(lite, wl, yolonet, feeds, "scores", fuse=False)
     un2, _, _, _ = _run(lite, wl, yolonet, feeds, "scores_npc", fuse=False)

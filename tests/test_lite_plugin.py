@@ -392,29 +392,50 @@ def test_device_timer_and_kernel_func_name(lite):
 
 
 @pytest.mark.gpu
-def test_launch_graph_replays_the_program_bit_for_bit(lite, wl, plref):
+def test_launch_graph_replays_the_program_bit_for_bit(lite, wl, plref, gpu_ctx):
     """HipPredictor::RunGraph: the device part of the program recorded once as a launch graph (plhip_graph_*) and replayed
     must produce exactly the bytes of the instruction-by-instruction run — also after the feed changed (the graph holds
-    device addresses, not data)."""
+    device addresses, not data).  Every variable the plan writes is filled with the poison byte in front of each compared
+    replay, and the second image reaches the predictor through its io_copy instruction alone: what is compared is what the
+    replay wrote, against the plain run of a second predictor."""
+    import replay_cases as R
     net = wl.mobilenet_v1_net(seed=11)
     rng = np.random.default_rng(12)
+    img = rng.uniform(-1, 1, (2, 3, 224, 224)).astype(np.float32)
+    img2 = rng.uniform(-1, 1, (2, 3, 224, 224)).astype(np.float32)
     p = lite.Predictor(0)
+    p2 = lite.Predictor(0)
     try:
         wl.emit_graph(p, net, 2)
+        plan = p.graph_plan()
         p.graph_lower()
-        img = rng.uniform(-1, 1, (2, 3, 224, 224)).astype(np.float32)
         p.set_input(net["input"], img)
         p.run()
         want = p.get_var(net["output"], np.float32).copy()
+        names, kept = R.to_poison(plan, p.kernel_names())
+        assert kept == ["image/target_trans"] and net["output"] in names and len(names) == 17
+        want_all = R.read_bytes(p, names)
         p.run_graph()   # records, then launches
+        R.poison(p, gpu_ctx, names)
         p.run_graph()   # replays
         assert np.array_equal(p.get_var(net["output"], np.float32), want)
-        img2 = rng.uniform(-1, 1, (2, 3, 224, 224)).astype(np.float32)
-        p.set_input(net["input"], img2)
-        p.run()         # uploads the new feed, runs kernel by kernel
-        want2 = p.get_var(net["output"], np.float32).copy()
+        assert R.first_difference(plan, R.read_bytes(p, names), want_all) is None
+        # the second image: a plain run of a second predictor is the reference; the first sees it in the replay only
+        wl.emit_graph(p2, net, 2)
+        p2.graph_lower()
+        p2.set_input(net["input"], img2)
+        p2.run()
+        p2.sync()
+        want2 = p2.get_var(net["output"], np.float32).copy()
+        want2_all = R.read_bytes(p2, names)
         assert not np.array_equal(want, want2)
+        R.upload_feed(p, net["input"], img2, R.feeds(plan)[1][0])
+        R.poison(p, gpu_ctx, names)
+        assert not np.array_equal(p.get_var(net["output"], np.float32), want2)
         p.run_graph()
         assert np.array_equal(p.get_var(net["output"], np.float32), want2)
+        diff = R.first_difference(plan, R.read_bytes(p, names), want2_all)
+        assert diff is None, diff
     finally:
         p.close()
+        p2.close()
