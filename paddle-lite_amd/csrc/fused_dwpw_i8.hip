@@ -15,6 +15,8 @@
 //   * produce task = 16 channels x 4 column quads x the 7-row strip on one wave: the rows-in-registers dot4 body of
 //     depthwise3x3_direct_kernel (9 unaligned 8-byte row windows per lane straight from global memory, v_alignbyte +
 //     v_dot4_i32_i8, the reference's requantisation), each requantised dword written straight into the activation image;
+//     with an int8 output the rows come as two 16-byte-per-lane loads of whole rows through a wave-private LDS stage (FW_RP
+//     below), and a lane reads its windows from there: 2 scattered loads per task instead of 9, no v_perm per row;
 //   * a ROUND = 8 tasks = 128 channels = 4 K-steps.  While round r is produced (VALU), the 4 K-steps of round r - 1 are
 //     multiplied (MFMA, weights global -> registers one round ahead, a wave owns 32 MTW output channels for all 4 n tiles):
 //     the two pipes of a SIMD work side by side, one barrier per ROUND (4 for K = 512), the next round's input rows and
@@ -36,6 +38,15 @@ namespace plhip {
 constexpr int FW_TR = 7;       // output rows per tile
 constexpr int FW_NT = 4;       // 32-pixel n tiles per tile (2 rows of pitch 16 each; the second half of the last one is empty)
 // (FW_SP, FW_KSTEP: dw_plan.h, which sizes the launch with them)
+// The row stage of the int8-output form: a wave's slice of the output staging region (idle until the epilogue) holds the input
+// rows of the task being produced, [channel 16][row slot 9][20 B]: a row is stored from column -1 on (bytes 0 and 15 .. 19 are
+// zero: the pad columns), so quad q's window is dwords q and q + 1 of its row.  Slot t is strip row t; the slot of the row outside
+// the image (0 in the upper half, 8 in the lower one) is never written and stays zero.  52 dwords per channel = 20 (mod 32): the 8
+// channels x 4 quads of a half wave read 32 different banks.
+constexpr int FW_RP = 20;      // stage: bytes per row slot
+constexpr int FW_CP = 208;     // stage: bytes per channel
+constexpr int FW_STAGE_AT = 5; // stage: the row chunk of a producing round at which the next task's two pieces are requested
+static_assert(16 * FW_CP <= 32 * FW_SP && 16 * FW_CP % 16 == 0, "the row stage lives in one wave's staging slice of the M = 256 form");
 
 // timeline stamps (EXPERIMENTS=1 builds, plhip_device.h): per wave of the first 1024 tiles at the phase boundaries, straight
 // into the "fw" stamp buffer [tile][wave 8][FW_STAMP_SLOTS] (tools/fused_timeline.py).  Slots: 0 realtime start, 1 entry,
@@ -52,8 +63,10 @@ __device__ __forceinline__ void fw_load_row(const int8_t* __restrict__ xs, uint3
 
 // MTW: 32-row m tiles per wave (M = 256 MTW).  OUT: output kind.  DWNN / PWNN: the depthwise / pointwise activation is
 // relu or relu6 (the packed non-negative requantisation); else none / leaky (leaky with slope 1 for none: exact).
-template <int MTW, int OUT, bool DWNN, bool PWNN>
-__global__ __launch_bounds__(512, 2) void fused_dwpw14_kernel(FusedArgs a) {
+// R: rounds of 128 input channels, a compile-time constant of the body (the kernel below dispatches on it): which round is the
+// first to multiply and which the last to produce is then known where the round is compiled, and every path is straight-line code.
+template <int MTW, int OUT, bool DWNN, bool PWNN, int R>
+__device__ __forceinline__ void fused_dwpw14_body(const FusedArgs& a) {
   const GemmArgs& g = a.pw;
   PLHIP_PRELOAD(a.x); PLHIP_PRELOAD(a.dw_w); PLHIP_PRELOAD(a.dw_scale); PLHIP_PRELOAD(a.dw_bias); PLHIP_PRELOAD(a.dw_act);
   PLHIP_PRELOAD(a.dw_alpha); PLHIP_PRELOAD(a.n); PLHIP_PRELOAD(a.C); PLHIP_PRELOAD(a.tiles); PLHIP_PRELOAD(a.ones); PLHIP_PRELOAD(g.wp); PLHIP_PRELOAD(g.y);
@@ -71,7 +84,8 @@ __global__ __launch_bounds__(512, 2) void fused_dwpw14_kernel(FusedArgs a) {
   unsigned long long* const lstamp = diag ? gstamp + ((size_t)vb * 8 + wave) * FW_STAMP_SLOTS : nullptr;
   PLHIP_STAMP_REAL(0);
   PLHIP_STAMP(1);
-  const int KS = g.KS, C = a.C, R = KS >> 2;  // rounds of 128 channels (K % 128 == 0: dwpw_launch_plan)
+  constexpr int KS = 4 * R;  // == g.KS (K % 128 == 0: dwpw_launch_plan)
+  const int C = a.C;
   const int c = lane & 31, h = lane >> 5;
 
   // ------------------------------------------------------------------ producer state
@@ -86,7 +100,23 @@ __global__ __launch_bounds__(512, 2) void fused_dwpw14_kernel(FusedArgs a) {
   // byte offset of (image b, channel 16 wave + chl, input row 7 hf, the window's fetch column); a round advances it by 128
   // planes.  Strip row t is input row 7 hf - 1 + t: distance 14 (t - 1), an immediate; the two rows that can lie outside
   // the image get their own scalar base (the neighbouring row's address).
-  uint32_t xoff = (uint32_t)(((b * C + 16 * wave + chl) * 14 + 7 * hf) * 14 + (q == 0 ? 0 : (q == 1 ? 3 : 6)));
+  //
+  // STAGED (int8 output: the plan has a staging region): the rows come through the wave's row stage instead.  A task's strip is 8
+  // rows of the image (0 .. 7 / 6 .. 13) x 16 channels = 128 rows = two wave loads of one 16-byte piece per lane: lane l of
+  // load i fetches row 6 hf + (l & 7) of the task's channel 8 i + (l >> 3) from ONE BYTE IN FRONT OF THE ROW, so that what it gets
+  // is the stage's row as it stands (column -1 .. 14) and only bytes 0 and 15, which belong to the neighbouring rows, are cleared.
+  // Kept inside the tensor: the piece of the tensor's first row would start one byte in front of it: that lane (image 0, channel 0,
+  // round 0: the prologue only) fetches from the row's first byte and shifts up; the piece of the tensor's last row would end
+  // one byte behind it: that lane (nb1 = 1) fetches from two bytes in front of the row and shifts down, in every round.  Every other
+  // row has a whole row on either side.  The row outside the image is not fetched at all: its slot of the stage stays zero.
+  constexpr bool STAGED = OUT == OUT_I8;
+  const uint32_t stage0 = (uint32_t)(KS * FW_KSTEP + wave * (32 * MTW * FW_SP));  // == stg of the epilogue
+  const uint32_t rdb = stage0 + (uint32_t)(chl * FW_CP + 4 * q);                                       // window reads
+  const uint32_t wst = stage0 + (uint32_t)((lane >> 3) * FW_CP + ((lane & 7) + 1 - hf) * FW_RP);      // row writes
+  const uint32_t xrow = (uint32_t)(((b * C + 16 * wave + (lane >> 3)) * 14 + 6 * hf + (lane & 7)) * 14);  // the loader lane's row, load 0
+  // the last byte any of this lane's pieces reaches (load 1 of round R - 1) against the tensor's size: at most one byte over
+  const uint32_t nb1 = STAGED && xrow + (uint32_t)(8 * 196 + (R - 1) * (128 * 196) + 15) > (uint32_t)(a.n * C * 196) ? 1u : 0u;
+  uint32_t xoff = STAGED ? xrow - 1u - nb1 : (uint32_t)(((b * C + 16 * wave + chl) * 14 + 7 * hf) * 14 + (q == 0 ? 0 : (q == 1 ? 3 : 6)));
   const uint32_t top = hf == 0 ? 0u : 0xffffffffu, bot = hf == 1 ? 0u : 0xffffffffu;  // scalar (block-uniform)
   const int8_t* const xs0 = a.x + (hf == 0 ? 0 : -14);   // strip row 0: input row 7 hf - 1, or row 0 again for the upper half
   const int8_t* const xs8 = a.x + (hf == 1 ? 84 : 98);   // strip row 8: input row 7 hf + 7, or row 13 again for the lower half
@@ -129,6 +159,37 @@ __global__ __launch_bounds__(512, 2) void fused_dwpw14_kernel(FusedArgs a) {
     load_row(std::integral_constant<int, 7>{}, off, in[7]);
     load_row(std::integral_constant<int, 8>{}, off, in[8]);
   };
+  // STAGED: the two pieces of the task being fetched (the registers are the stage's second buffer), its parameters
+  v4i nx[2];
+  auto load_rows = [&](uint32_t off) __attribute__((always_inline)) {
+    __builtin_memcpy(&nx[0], a.x + off, 16);
+    __builtin_memcpy(&nx[1], a.x + off + 8 * 196, 16);
+  };
+  auto fetch_params = [&](int ch, uint32_t (&w)[3], float& s, float& bb) __attribute__((always_inline)) {
+    const int8_t* wp = a.dw_w + (size_t)ch * 9;
+    uint32_t w0, w1, w2;
+    __builtin_memcpy(&w0, wp, 4);
+    __builtin_memcpy(&w1, wp + 3, 4);
+    __builtin_memcpy(&w2, wp + 5, 4);
+    w[0] = w0 & 0xffffffu;
+    w[1] = w1 & 0xffffffu;
+    w[2] = w2 >> 8;
+    s = a.dw_scale[ch];
+    bb = (a.dw_bias ? a.dw_bias : a.dw_scale)[ch];  // no branch inside a round
+    if (!a.dw_bias) bb = 0.f;
+  };
+  // the pieces into the stage: behind the last window read of the task it holds (the wave's own LDS order: no barrier)
+  auto stage_rows = [&]() __attribute__((always_inline)) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const uint32_t d0 = (uint32_t)nx[i][0], d1 = (uint32_t)nx[i][1], d2 = (uint32_t)nx[i][2], d3 = (uint32_t)nx[i][3];
+      uint32_t* p = reinterpret_cast<uint32_t*>(fw_lds + wst + i * (8 * FW_CP));
+      p[0] = __builtin_amdgcn_alignbyte(d1, d0, nb1) & 0xffffff00u;
+      p[1] = __builtin_amdgcn_alignbyte(d2, d1, nb1);
+      p[2] = __builtin_amdgcn_alignbyte(d3, d2, nb1);
+      p[3] = __builtin_amdgcn_alignbyte(0u, d3, nb1) & 0x00ffffffu;
+    }
+  };
 
   // ------------------------------------------------------------------ consumer state
   // transposed-read addresses (gemm_wide_kernel.h): tile t <-> chunk pair (2t, 2t+1); lane 2q'+p of a 16-lane group -> row
@@ -147,13 +208,8 @@ __global__ __launch_bounds__(512, 2) void fused_dwpw14_kernel(FusedArgs a) {
 #pragma unroll
     for (int m = 0; m < MTW; ++m) W[j][m] = *reinterpret_cast<const v4i*>(wpk + ((size_t)m * KS + ks) * 1024 + wlane);  // scalar base + lane offset
   };
-  v16i acc[FW_NT][MTW];
-#pragma unroll
-  for (int n = 0; n < FW_NT; ++n)
-#pragma unroll
-    for (int m = 0; m < MTW; ++m)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[n][m][r] = 0;
+  v16i acc[FW_NT][MTW];  // never zeroed: K-step 0 multiplies into the constant
+  const v16i zero16 = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 
   // ------------------------------------------------------------------ one round
   // PRODUCE: the task in (in, wr, dsc, dbi) -> K-steps 4 rp .. 4 rp + 3 of the image, and the next task's operands fetched
@@ -166,16 +222,21 @@ __global__ __launch_bounds__(512, 2) void fused_dwpw14_kernel(FusedArgs a) {
   // MFMA-only wave runs at 9.5 cycles per dot4), while cvt / fma / min / perm overlap with it.  (Dealing everything over the
   // row chunks instead made rounds take MFMA time + VALU time, profiles/r04_fused_timeline_order0.txt.)  The consume-only
   // last round deals its MFMAs over the 9 row chunks' proportions.
-  auto round = [&](auto produce_c, auto consume_c, int rp, int rc) __attribute__((always_inline)) {
+  // FIRST: the round multiplies K-steps 0 .. 3 (K-step 0 into the constant 0: the accumulators are never zeroed).  LAST: the
+  // last producing round requests no next task; the consume-only round behind it requests no weights.  Both are compile-time:
+  // there is no branch inside a round.
+  auto round = [&](auto produce_c, auto consume_c, auto first_c, auto last_c, int rp, int rc) __attribute__((always_inline)) {
     constexpr bool PRODUCE = decltype(produce_c)::value, CONSUME = decltype(consume_c)::value;
-    // next task (clamped: the last round fetches its own operands again, unused)
-    const int rn = rp + 1 < R ? rp + 1 : rp;
-    const int nch = 128 * rn + 16 * wave + chl;
-    const uint32_t noff = xoff + (uint32_t)(rn - rp) * (128 * 196);
+    constexpr bool FIRST = decltype(first_c)::value, LAST = decltype(last_c)::value;
+    constexpr bool NEXT_TASK = PRODUCE && !LAST;  // round rp + 1 produces
+    constexpr bool NEXT_W = PRODUCE;              // K-steps 4 (rc + 1) .. exist: only the consume-only round multiplies the last four
+    const int nch = 128 * (rp + 1) + 16 * wave + chl;
+    const uint32_t noff = xoff + (uint32_t)(128 * 196);
     const uint32_t wb = wbase + (uint32_t)rp * (4 * FW_KSTEP);
     const uint32_t rb = (uint32_t)rc * (4 * FW_KSTEP);
     int dacc[FW_TR][4];
-    const uint32_t wr0t = wr[0] & top, wr2b = wr[2] & bot;  // input row 0 / 8 of the strip lies outside the image in the upper / lower half
+    // input row 0 / 8 of the strip lies outside the image in the upper / lower half (STAGED: its slot of the stage is zero)
+    const uint32_t wr0t = STAGED ? wr[0] : wr[0] & top, wr2b = STAGED ? wr[2] : wr[2] & bot;
     uint32_t nwr[3];
     float ndsc = 0.f, ndbi = 0.f;
     v2i lo[FW_NT], hi[FW_NT];
@@ -198,11 +259,8 @@ __global__ __launch_bounds__(512, 2) void fused_dwpw14_kernel(FusedArgs a) {
         if constexpr (jn < 4) read_frag(jn, nn);
       }
       const v4i av = {lo[n][0], lo[n][1], hi[n][0], hi[n][1]};
-      acc[n][m] = __builtin_amdgcn_mfma_i32_32x32x32_i8(av, W[j][m], acc[n][m], 0, 0, 0);
-      if constexpr (n == FW_NT - 1 && m == MTW - 1) {  // K-step j done: its registers take K-step j of the next round
-        const int ksn = 4 * (rc + 1) + j;
-        fetch_w(j, ksn < KS ? ksn : KS - 1);
-      }
+      acc[n][m] = __builtin_amdgcn_mfma_i32_32x32x32_i8(av, W[j][m], FIRST && j == 0 ? zero16 : acc[n][m], 0, 0, 0);
+      if constexpr (NEXT_W && n == FW_NT - 1 && m == MTW - 1) fetch_w(j, 4 * (rc + 1) + j);  // K-step j done: its registers take K-step j of the next round
     };
     auto mfmas = [&](auto self, auto i_c, auto end_c) __attribute__((always_inline)) -> void {
       constexpr int i = decltype(i_c)::value, end = decltype(end_c)::value;
@@ -219,7 +277,15 @@ __global__ __launch_bounds__(512, 2) void fused_dwpw14_kernel(FusedArgs a) {
     };
     auto taps = [&](auto t_c) __attribute__((always_inline)) {
       constexpr int t = decltype(t_c)::value;
-      const uint32_t e0 = __builtin_amdgcn_perm(in[t][1], in[t][0], sel_lo), e1 = __builtin_amdgcn_perm(in[t][1], in[t][0], sel_hi);
+      uint32_t e0, e1;
+      if constexpr (STAGED) {  // dwords q, q + 1 of the row's slot: one 4-byte aligned two-dword read
+        const uint32_t* rp2 = reinterpret_cast<const uint32_t*>(fw_lds + rdb + t * FW_RP);
+        e0 = rp2[0];
+        e1 = rp2[1];
+      } else {
+        e0 = __builtin_amdgcn_perm(in[t][1], in[t][0], sel_lo);
+        e1 = __builtin_amdgcn_perm(in[t][1], in[t][0], sel_hi);
+      }
       uint32_t win[4];
       win[0] = e0;
       win[1] = __builtin_amdgcn_alignbyte(e1, e0, 1);
@@ -234,20 +300,11 @@ __global__ __launch_bounds__(512, 2) void fused_dwpw14_kernel(FusedArgs a) {
           dacc[o][jj] = r == 0 ? sdot4_first(win[jj], t == 0 ? wr0t : wr[0])
                                : __builtin_amdgcn_sdot4((int)win[jj], (int)(t == 8 ? wr2b : wr[r]), dacc[o][jj], false);
       }
-      // the next task's row t into the registers just consumed
-      load_row(integral_constant<int, t>{}, noff, in[t]);
-      if constexpr (t == 2) {
-        const int8_t* wp = a.dw_w + (size_t)nch * 9;
-        uint32_t w0, w1, w2;
-        __builtin_memcpy(&w0, wp, 4);
-        __builtin_memcpy(&w1, wp + 3, 4);
-        __builtin_memcpy(&w2, wp + 5, 4);
-        nwr[0] = w0 & 0xffffffu;
-        nwr[1] = w1 & 0xffffffu;
-        nwr[2] = w2 >> 8;
-        ndsc = a.dw_scale[nch];
-        ndbi = (a.dw_bias ? a.dw_bias : a.dw_scale)[nch];  // no branch inside the round
-        if (!a.dw_bias) ndbi = 0.f;
+      if constexpr (NEXT_TASK) {
+        // the next task's row t into the registers just consumed; STAGED: its two pieces, once
+        if constexpr (!STAGED) load_row(integral_constant<int, t>{}, noff, in[t]);
+        else if constexpr (t == FW_STAGE_AT) load_rows(noff);
+        if constexpr (t == 2) fetch_params(nch, nwr, ndsc, ndbi);
       }
     };
     auto finish = [&](auto o_c) __attribute__((always_inline)) {  // output row o is complete: requantise, into the image
@@ -298,9 +355,13 @@ __global__ __launch_bounds__(512, 2) void fused_dwpw14_kernel(FusedArgs a) {
       slice(integral_constant<int, 3>{});
       slice(integral_constant<int, 4>{});
       slice(integral_constant<int, 5>{});
+      if constexpr (STAGED && NEXT_TASK) {  // every window of this task has been read: the stage takes the next one
+        stage_rows();
+        __builtin_amdgcn_sched_barrier(0);
+      }
       slice(integral_constant<int, 6>{});
     }
-    if constexpr (PRODUCE) {
+    if constexpr (NEXT_TASK) {
       wr[0] = nwr[0];
       wr[1] = nwr[1];
       wr[2] = nwr[2];
@@ -309,22 +370,70 @@ __global__ __launch_bounds__(512, 2) void fused_dwpw14_kernel(FusedArgs a) {
     }
   };
 
-  fetch_task(ch0, xoff);
+  if constexpr (STAGED) {
+    // the stage zeroed once: the fifth dword of every row and the slot of the row outside the image stay zero
+    const v4i z4 = {0, 0, 0, 0};
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      if (64 * i + lane < 16 * FW_CP / 16) *reinterpret_cast<v4i*>(fw_lds + stage0 + (64 * i + lane) * 16) = z4;
+    const bool first = xoff == 0xffffffffu;  // the tensor's first row: fetched from its first byte, shifted up one
+    load_rows(first ? 0u : xoff);
+    float s, bb;
+    fetch_params(ch0, wr, s, bb);
+    dsc = s + s;
+    dbi = bb + bb;
+    if (first) {  // (both pieces: the lane's second one shares the offset register)
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        const uint32_t d0 = (uint32_t)nx[i][0], d1 = (uint32_t)nx[i][1], d2 = (uint32_t)nx[i][2], d3 = (uint32_t)nx[i][3];
+        nx[i][0] = (int)(d0 << 8);
+        nx[i][1] = (int)__builtin_amdgcn_alignbyte(d1, d0, 3);
+        nx[i][2] = (int)__builtin_amdgcn_alignbyte(d2, d1, 3);
+        nx[i][3] = (int)__builtin_amdgcn_alignbyte(d3, d2, 3);
+      }
+    }
+  } else {
+    fetch_task(ch0, xoff);
+  }
   fetch_w(0, 0);
-  fetch_w(1, 1 < KS ? 1 : KS - 1);
-  fetch_w(2, 2 < KS ? 2 : KS - 1);
-  fetch_w(3, 3 < KS ? 3 : KS - 1);
+  fetch_w(1, 1);  // (KS >= 4: whole rounds)
+  fetch_w(2, 2);
+  fetch_w(3, 3);
   PLHIP_STAMP(2);
-  round(std::true_type{}, std::false_type{}, 0, 0);
-  xoff += (R > 1 ? 1 : 0) * 128 * 196;
-  PLHIP_STAMP(3);
-  __syncthreads();
-  for (int r = 1; r < R; ++r) {
-    round(std::true_type{}, std::true_type{}, r, r - 1);
-    xoff += (r + 1 < R ? 1 : 0) * 128 * 196;
-    if (r < 5) PLHIP_STAMP(4 + 2 * (r - 1));
+  if constexpr (STAGED) stage_rows();
+  // the rounds: 0 produces only, 1 is the first to multiply, R - 1 the last to produce
+  using T = std::true_type;
+  using F = std::false_type;
+  auto behind = [&](int r) __attribute__((always_inline)) {  // round r is done: the stamps of the timeline, the barrier
+    // The rounds of a path are one basic block.  An MFMA has no side effect, and nothing but the epilogue reads an accumulator:
+    // without this empty statement the compiler moved whole accumulation chains behind the last round and kept every operand of
+    // theirs in scratch until then.  It costs no instruction: the accumulators of round r exist here, in their registers.
+    if (r >= 1) {
+#pragma unroll
+      for (int n = 0; n < FW_NT; ++n)
+#pragma unroll
+        for (int m = 0; m < MTW; ++m) asm volatile("" : "+v"(acc[n][m]));
+    }
+    xoff += 128 * 196;
+    if (r == 0) PLHIP_STAMP(3);
+    else if (r < 5) PLHIP_STAMP(4 + 2 * (r - 1));
     __syncthreads();
-    if (r < 5) PLHIP_STAMP(5 + 2 * (r - 1));
+    if (r >= 1 && r < 5) PLHIP_STAMP(5 + 2 * (r - 1));
+  };
+  round(T{}, F{}, F{}, std::bool_constant<R == 1>{}, 0, 0);
+  behind(0);
+  if constexpr (R >= 2) {
+    round(T{}, T{}, T{}, std::bool_constant<R == 2>{}, 1, 0);
+    behind(1);
+  }
+  if constexpr (R >= 3) {
+    round(T{}, T{}, F{}, std::bool_constant<R == 3>{}, 2, 1);
+    behind(2);
+  }
+  if constexpr (R >= 4) {
+    static_assert(R <= 4, "C <= 512: dwpw_launch_plan");
+    round(T{}, T{}, F{}, T{}, 3, 2);
+    behind(3);
   }
   float psc[MTW], pbi[MTW];  // pointwise scale / bias of this lane's channels: fetched under the last round's MFMAs
 #pragma unroll
@@ -357,13 +466,14 @@ __global__ __launch_bounds__(512, 2) void fused_dwpw14_kernel(FusedArgs a) {
         fhi[n & 1][j] = __builtin_amdgcn_ds_read_tr8_b64_v2i32((lds_v2i_ptr_t)(fw_lds + ta + j * FW_KSTEP + 1024));
       }
     };
-    auto mfma_tile = [&](auto n_c) __attribute__((always_inline)) {
+    auto mfma_tile = [&](auto n_c, auto first_c) __attribute__((always_inline)) {  // first_c: these are K-steps 0 .. 3 (R = 1)
       constexpr int n = decltype(n_c)::value;
+      constexpr bool FIRST = decltype(first_c)::value;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const v4i av = {flo[n & 1][j][0], flo[n & 1][j][1], fhi[n & 1][j][0], fhi[n & 1][j][1]};
 #pragma unroll
-        for (int m = 0; m < MTW; ++m) acc[n][m] = __builtin_amdgcn_mfma_i32_32x32x32_i8(av, W[j][m], acc[n][m], 0, 0, 0);
+        for (int m = 0; m < MTW; ++m) acc[n][m] = __builtin_amdgcn_mfma_i32_32x32x32_i8(av, W[j][m], FIRST && j == 0 ? zero16 : acc[n][m], 0, 0, 0);
       }
     };
     auto epi_tile = [&](auto n_c) __attribute__((always_inline)) {
@@ -396,21 +506,24 @@ __global__ __launch_bounds__(512, 2) void fused_dwpw14_kernel(FusedArgs a) {
     using I1 = integral_constant<int, 1>;
     using I2 = integral_constant<int, 2>;
     using I3 = integral_constant<int, 3>;
-    read_tile(I0{});
-    read_tile(I1{});
-    mfma_tile(I0{});
-    __builtin_amdgcn_sched_barrier(0);
-    read_tile(I2{});
-    mfma_tile(I1{});
-    epi_tile(I0{});
-    __builtin_amdgcn_sched_barrier(0);
-    read_tile(I3{});
-    mfma_tile(I2{});
-    epi_tile(I1{});
-    __builtin_amdgcn_sched_barrier(0);
-    mfma_tile(I3{});
-    epi_tile(I2{});
-    __builtin_amdgcn_sched_barrier(0);
+    auto last_k_steps = [&](auto first_c) __attribute__((always_inline)) {
+      read_tile(I0{});
+      read_tile(I1{});
+      mfma_tile(I0{}, first_c);
+      __builtin_amdgcn_sched_barrier(0);
+      read_tile(I2{});
+      mfma_tile(I1{}, first_c);
+      epi_tile(I0{});
+      __builtin_amdgcn_sched_barrier(0);
+      read_tile(I3{});
+      mfma_tile(I2{}, first_c);
+      epi_tile(I1{});
+      __builtin_amdgcn_sched_barrier(0);
+      mfma_tile(I3{}, first_c);
+      epi_tile(I2{});
+      __builtin_amdgcn_sched_barrier(0);
+    };
+    last_k_steps(std::bool_constant<R == 1>{});  // R = 1: the first consuming round is the last one
     PLHIP_STAMP(12);
     epi_tile(I3{});
     PLHIP_STAMP(13);
@@ -429,8 +542,13 @@ __global__ __launch_bounds__(512, 2) void fused_dwpw14_kernel(FusedArgs a) {
       }
     }
   } else {
-    round(std::false_type{}, std::true_type{}, R, R - 1);
+    round(F{}, T{}, std::bool_constant<R == 1>{}, T{}, R, R - 1);  // R = 1: the first consuming round is the last one
     PLHIP_STAMP(12);
+    // the lane's k half again from the thread index, which is in a register anyway (through an empty statement, or the compiler
+    // recognises `h`): `h` kept from the top of the kernel to here was the one register too many of the M = 512 forms
+    uint32_t tid = threadIdx.x;
+    asm volatile("" : "+v"(tid));
+    const int h = (int)(tid >> 5) & 1;
     const float fcap = g.act == ACT_RELU6 ? g.alpha : __builtin_huge_valf();
     const float flo = (g.act == ACT_RELU || g.act == ACT_RELU6) ? 0.f : -__builtin_huge_valf();
 #pragma unroll
@@ -478,6 +596,16 @@ __global__ __launch_bounds__(512, 2) void fused_dwpw14_kernel(FusedArgs a) {
   if (diag) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     PLHIP_STAMP(15);
+  }
+}
+
+template <int MTW, int OUT, bool DWNN, bool PWNN>
+__global__ __launch_bounds__(512, 2) void fused_dwpw14_kernel(FusedArgs a) {
+  switch (a.pw.KS >> 2) {  // block-uniform (128 | C <= 512: dwpw_launch_plan)
+    case 1: return fused_dwpw14_body<MTW, OUT, DWNN, PWNN, 1>(a);
+    case 2: return fused_dwpw14_body<MTW, OUT, DWNN, PWNN, 2>(a);
+    case 3: return fused_dwpw14_body<MTW, OUT, DWNN, PWNN, 3>(a);
+    default: return fused_dwpw14_body<MTW, OUT, DWNN, PWNN, 4>(a);
   }
 }
 
