@@ -64,24 +64,8 @@ __device__ __forceinline__ void ds2_store(const DirectS2Args& a, size_t off, int
       if (j < room) yp[j] = f;
     }
   } else {
-    const float hi2 = ACT == ACT_RELU6 ? fminf(a.alpha + a.alpha, 254.f) : 254.f;
-    const float lo2 = (ACT == ACT_RELU || ACT == ACT_RELU6) ? 0.f : -254.f;
-    const float s2 = s + s, b2 = bi + bi;
-    uint32_t pk;
-    if (ACT == ACT_RELU || ACT == ACT_RELU6) {
-      pk = pack4_nn_rtz(__fmaf_rn((float)acc[0], s2, b2), __fmaf_rn((float)acc[1], s2, b2), __fmaf_rn((float)acc[2], s2, b2),
-                        __fmaf_rn((float)acc[3], s2, b2), hi2);
-    } else {
-      int q[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        float y2 = __fmaf_rn((float)acc[j], s2, b2);
-        if (ACT == ACT_LEAKY) y2 = y2 > 0.f ? y2 : a.alpha * y2;
-        const int t = (int)__builtin_amdgcn_fmed3f(y2, lo2, hi2);
-        q[j] = (t + 1 + (t >> 31)) >> 1;
-      }
-      pk = pack4_i8(q[0], q[1], q[2], q[3]);
-    }
+    const RequantBounds qb = requant_bounds<ACT>(a.alpha);
+    const uint32_t pk = requant4<ACT>(acc, s + s, bi + bi, a.alpha, qb.lo2, qb.hi2);
     int8_t* yp = reinterpret_cast<int8_t*>(a.y) + off;
     if (room >= 4) {
       __builtin_memcpy(yp, &pk, 4);

@@ -252,6 +252,7 @@ __global__ __launch_bounds__(256 * NH, 2) void conv_patch_i8_kernel(PatchArgs a)
   v4i wr[KT];          // weight fragments of the step (ring mode)
 
   // ---- epilogue constants
+  // (requant_hi2 / requant_lo2 / requant_leak, plhip_device.h, written out: through the functions conv_patch_i8's ISA moves)
   const float hi2 = a.act == ACT_RELU6 ? fminf(a.alpha + a.alpha, 254.f) : 254.f;
   const float lo2 = NONNEG ? 0.f : -254.f;
   const float leak = a.act == ACT_LEAKY ? a.alpha : 1.f;  // int8, !NONNEG: none = leaky with slope 1

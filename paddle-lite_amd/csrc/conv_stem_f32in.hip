@@ -56,7 +56,7 @@ __global__ __launch_bounds__(256) void conv3x3s2_mfma_f32in_kernel(DirectS2Args 
 #pragma unroll
   for (int it = 0; it < NPIECE; ++it) {
     const v4f v = pv[it];
-    const uint32_t pk = pack4_i8(round_sat_i8(inv * v[0]), round_sat_i8(inv * v[1]), round_sat_i8(inv * v[2]), round_sat_i8(inv * v[3]));
+    const uint32_t pk = calib4_i8(v, inv);
     if (pdst[it] >= 0) *reinterpret_cast<uint32_t*>(img + pdst[it]) = pk;  // (a piece outside the image: +0.0 -> 0, the padding)
   }
   // (bytes 264 .. 271 of a row are read by the last quads' 16-byte windows and never used: no need to clear them)

@@ -246,8 +246,7 @@ __device__ __forceinline__ void dw_finish_row(const DwArgs& a, void* rowbase, ui
       if (j < room) yp[j] = f;
     }
   } else {
-    const float lo2 = (ACT == ACT_RELU || ACT == ACT_RELU6) ? 0.f : -254.f;
-    const uint32_t pk = dw_requant4<ACT>(acc, s + s, bi + bi, a.alpha, lo2, a.hi2, a.ones);
+    const uint32_t pk = requant4<ACT>(acc, s + s, bi + bi, a.alpha, requant_lo2(ACT), a.hi2, a.ones);
     int8_t* yp = reinterpret_cast<int8_t*>(rowbase) + off;
     if (room >= 4) {
       __builtin_memcpy(yp, &pk, 4);  // may be unaligned when OW % 4 != 0: fine for global memory
@@ -349,14 +348,7 @@ __device__ __forceinline__ void dw3x3_finish(const DwArgs& a, const uint32_t (&i
       wr4[r] = hi >> 24;
     }
   } else {
-    const int8_t* wp = a.wt + (size_t)ch * 9;
-    uint32_t w0, w1, w2;
-    __builtin_memcpy(&w0, wp, 4);
-    __builtin_memcpy(&w1, wp + 3, 4);
-    __builtin_memcpy(&w2, wp + 5, 4);
-    wr[0] = w0 & 0xffffffu;
-    wr[1] = w1 & 0xffffffu;
-    wr[2] = w2 >> 8;
+    dw_filter_rows3(a.wt + (size_t)ch * 9, wr);
   }
   const float sc = a.scale ? a.scale[ch] : 1.f;
   const float bi = a.bias ? a.bias[ch] : 0.f;
@@ -412,7 +404,7 @@ __device__ __forceinline__ void dw3x3_finish(const DwArgs& a, const uint32_t (&i
     const float s2 = sc + sc, b2 = bi + bi;
 #define DW_PK(ACTV)                                                                                                  \
   _Pragma("unroll") for (int o = 0; o < RS; ++o) pk[o] =                                                             \
-      dw_requant4<ACTV>(acc[o], s2, b2, a.alpha, (ACTV == ACT_RELU || ACTV == ACT_RELU6) ? 0.f : -254.f, a.hi2, a.ones);
+      requant4<ACTV>(acc[o], s2, b2, a.alpha, requant_lo2(ACTV), a.hi2, a.ones);
     switch (a.act) {
       case ACT_RELU: DW_PK(ACT_RELU) break;
       case ACT_RELU6: DW_PK(ACT_RELU6) break;
@@ -634,7 +626,7 @@ void launch_depthwise(const DwArgs& a_in, const DwPlan& p, int out, hipStream_t 
     a.stage_bytes = d.stage_bytes;
     a.lw = d.lw;
     a.nblocks = d.nblocks;
-    a.hi2 = a.act == ACT_RELU6 ? (a.alpha + a.alpha < 254.f ? a.alpha + a.alpha : 254.f) : 254.f;
+    a.hi2 = requant_hi2(a.act, a.alpha);
     with_const<1, 2>(p.S, [&](auto st) {
       with_const<4, 7, 8>(p.RS, [&](auto rs) {
         with_const<0, 1>(p.STAGE, [&](auto stage) {

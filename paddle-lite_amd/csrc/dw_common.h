@@ -1,5 +1,7 @@
-// dw_common.h — device helpers shared by the depthwise kernels (depthwise_i8.hip) and the fused depthwise -> pointwise
-// kernel (fused_dwpw_i8.hip): the unaligned row-window fetch and the 4-wide int8 requantisation.
+// dw_common.h — helpers of the kernels with a depthwise stage (depthwise_i8.hip, fused_dwconv_i8.hip, fused_dwpw_*.hip): the
+// packed 3x3 filter rows and the unaligned, masked row-window fetch (the stem convs fetch their rows with it too); and the
+// fast division by a host-prepared constant, which every kernel family uses.  The int8 requantisation these kernels share
+// with all others is requant4 (plhip_device.h).
 #pragma once
 #include <stdint.h>
 
@@ -31,29 +33,16 @@ __device__ __forceinline__ uint32_t fastdiv_u31(uint32_t n, uint32_t magic, int 
   return magic ? (__umulhi(n, magic) >> sh) : (n >> sh);
 }
 
-// ones: 0x01010101 (the byte-wise +1 of the packed rounding) — a parameter so that a caller can hand over a scalar kernel
-// argument instead of a constant the compiler moves into a VGPR again per use
-template <int ACT>
-__device__ __forceinline__ uint32_t dw_requant4(const int (&a)[4], float s2, float b2, float alpha, float lo2, float hi2,
-                                                uint32_t ones = 0x01010101u) {
-  if (ACT == ACT_RELU || ACT == ACT_RELU6)  // (lo2 == 0: the conversion saturates negative values to it)
-    return pack4_nn_rtz(__fmaf_rn((float)a[0], s2, b2), __fmaf_rn((float)a[1], s2, b2), __fmaf_rn((float)a[2], s2, b2),
-                        __fmaf_rn((float)a[3], s2, b2), hi2, ones);
-  int q[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    float y2 = __fmaf_rn((float)a[j], s2, b2);
-    if (ACT == ACT_LEAKY) y2 = y2 > 0.f ? y2 : alpha * y2;
-    const int t = (int)__builtin_amdgcn_fmed3f(y2, lo2, hi2);
-    q[j] = (t + 1 + (t >> 31)) >> 1;
-  }
-  return pack4_i8(q[0], q[1], q[2], q[3]);
-}
-
-// relu / relu6 requantisation of 4 accumulators on doubled values (pack4_nn_rtz, plhip_device.h)
-__device__ __forceinline__ uint32_t requant4_nn_rtz(const int (&a)[4], float s2, float b2, float hi2, uint32_t ones = 0x01010101u) {
-  return pack4_nn_rtz(__fmaf_rn((float)a[0], s2, b2), __fmaf_rn((float)a[1], s2, b2), __fmaf_rn((float)a[2], s2, b2),
-                      __fmaf_rn((float)a[3], s2, b2), hi2, ones);
+// The three packed filter rows (w0 w1 w2 0) of one channel's 3x3 depthwise filter, wp -> its 9 int8 weights: three unaligned
+// dword fetches that stay inside the 9 bytes (the last one starts at byte 5 and drops its first byte)
+__device__ __forceinline__ void dw_filter_rows3(const int8_t* wp, uint32_t (&w)[3]) {
+  uint32_t w0, w1, w2;
+  __builtin_memcpy(&w0, wp, 4);
+  __builtin_memcpy(&w1, wp + 3, 4);
+  __builtin_memcpy(&w2, wp + 5, 4);
+  w[0] = w0 & 0xffffffu;
+  w[1] = w1 & 0xffffffu;
+  w[2] = w2 >> 8;
 }
 
 // Byte-validity masks of a row window of ND dwords whose byte 0 is input column `start` (may be negative: left padding):

@@ -20,7 +20,7 @@
 //   * PRODUCE (the rows-in-registers body of the depthwise kernel): a lane = 4 consecutive outputs of one channel row; per
 //     filter row 3 (stride 1) or 4 (stride 2) aligned LDS dwords, the four windows cut by v_alignbyte_b32 and multiplied with
 //     the packed filter row by v_dot4_i32_i8; the depthwise kernel's requantisation on doubled values (requant4_nn_rtz /
-//     pack4_nn_rtz for relu / relu6, dw_requant4 otherwise); 4 bytes into the activation tile [pixel][32 ch + 16 pad].
+//     pack4_nn_rtz for relu / relu6, requant4 otherwise); 4 bytes into the activation tile [pixel][32 ch + 16 pad].
 //     Channels >= C are zeros, so the last K-step of C = 144 adds exactly 0 against the zero-padded weights;
 //   * CONSUME: v_mfma_i32_32x32x32_i8, A = the 1x1 conv's weight fragments straight from plhip_pack_conv_weights' order
 //     [MT32][KS][64][16] (global, L2-resident), B = 16 channels of one pixel per lane from the tile (ds_read_b128);
@@ -99,6 +99,7 @@ __global__ __launch_bounds__(DC_THREADS) void dw_conv1x1_fused_kernel(DwConvArgs
 
   // ---------------------------------------------------------------- produce: depthwise of K-step ks -> activation tile buf
   const bool dwnn = a.dw_act == ACT_RELU || a.dw_act == ACT_RELU6;
+  // (requant_hi2 / requant_leak, plhip_device.h, written out: through the functions this unit's ISA moves)
   const float dw_hi2 = a.dw_act == ACT_RELU6 ? fminf(a.dw_alpha + a.dw_alpha, 254.f) : 254.f;
   const float dw_leak = a.dw_act == ACT_LEAKY ? a.dw_alpha : 1.f;
   const int owq = (a.CW + 3) >> 2;
@@ -115,11 +116,8 @@ __global__ __launch_bounds__(DC_THREADS) void dw_conv1x1_fused_kernel(DwConvArgs
       uint32_t pk = 0;
       if (c < a.C) {
         const int8_t* const wp = a.dw_w + c * 9;
-        uint32_t w0, w1, w2;
-        __builtin_memcpy(&w0, wp, 4);
-        __builtin_memcpy(&w1, wp + 3, 4);
-        __builtin_memcpy(&w2, wp + 5, 4);
-        const uint32_t wr[3] = {w0 & 0xffffffu, w1 & 0xffffffu, w2 >> 8};
+        uint32_t wr[3];
+        dw_filter_rows3(wp, wr);
         int acc4[4] = {0, 0, 0, 0};
 #pragma unroll
         for (int r = 0; r < 3; ++r) {
@@ -133,7 +131,7 @@ __global__ __launch_bounds__(DC_THREADS) void dw_conv1x1_fused_kernel(DwConvArgs
           acc4[3] = __builtin_amdgcn_sdot4((int)dc_window<4 - PL + 3 * S, ND>(d), (int)wr[r], acc4[3], false);
         }
         const float s = a.dw_scale[c], bb = a.dw_bias ? a.dw_bias[c] : 0.f;
-        pk = dwnn ? requant4_nn_rtz(acc4, s + s, bb + bb, dw_hi2) : dw_requant4<ACT_LEAKY>(acc4, s + s, bb + bb, dw_leak, -254.f, 254.f);
+        pk = dwnn ? requant4_nn_rtz(acc4, s + s, bb + bb, dw_hi2) : requant4<ACT_LEAKY>(acc4, s + s, bb + bb, dw_leak, -254.f, 254.f);
       }
       uint8_t* const ap = act + (o * a.CW + x0) * DC_APITCH + cl;
 #pragma unroll
@@ -182,6 +180,8 @@ __global__ __launch_bounds__(DC_THREADS) void dw_conv1x1_fused_kernel(DwConvArgs
 
   // ---------------------------------------------------------------- epilogue
   // D layout: column (pixel) = lane & 31, row (output channel) = 8 (r >> 2) + 4 (lane >> 5) + (r & 3)
+  // (requant_hi2 / requant_lo2 and, below, requant4's arithmetic on one value, written out: through the shared functions
+  // this unit's ISA moves)
   const float hi2 = a.act == ACT_RELU6 ? fminf(a.alpha + a.alpha, 254.f) : 254.f;
   const float lo2 = (a.act == ACT_RELU || a.act == ACT_RELU6) ? 0.f : -254.f;
 #pragma unroll

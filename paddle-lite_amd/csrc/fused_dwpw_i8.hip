@@ -124,6 +124,7 @@ __device__ __forceinline__ void fused_dwpw14_body(const FusedArgs& a) {
   // chunk o in slot o ^ (2 ((k % 8) >> 1)) (the swizzle of gemm_wide_kernel.h), byte 4 q:  address = wbase ^ (o << 4)
   const int ch0 = 16 * wave + chl;
   uint32_t wbase = (uint32_t)((ch0 >> 5) * FW_KSTEP + ((ch0 >> 3) & 3) * 1024 + (ch0 & 7) * 128 + ((ch0 & 6) << 4) + 4 * q);
+  // (requant_hi2 / requant_leak, plhip_device.h, written out: through the functions this unit's ISA moves)
   const float dw_hi2 = a.dw_act == ACT_RELU6 ? fminf(a.dw_alpha + a.dw_alpha, 254.f) : 254.f;
   const float dw_leak = a.dw_act == ACT_LEAKY ? a.dw_alpha : 1.f;
 
@@ -138,14 +139,7 @@ __device__ __forceinline__ void fused_dwpw14_body(const FusedArgs& a) {
   };
   auto fetch_task = [&](int ch, uint32_t off) __attribute__((always_inline)) {
     // ch / off: this lane's channel and window offset of the task
-    const int8_t* wp = a.dw_w + (size_t)ch * 9;
-    uint32_t w0, w1, w2;
-    __builtin_memcpy(&w0, wp, 4);
-    __builtin_memcpy(&w1, wp + 3, 4);
-    __builtin_memcpy(&w2, wp + 5, 4);
-    wr[0] = w0 & 0xffffffu;
-    wr[1] = w1 & 0xffffffu;
-    wr[2] = w2 >> 8;
+    dw_filter_rows3(a.dw_w + (size_t)ch * 9, wr);
     const float s = a.dw_scale[ch], bb = a.dw_bias ? a.dw_bias[ch] : 0.f;
     dsc = s + s;
     dbi = bb + bb;
@@ -166,14 +160,7 @@ __device__ __forceinline__ void fused_dwpw14_body(const FusedArgs& a) {
     __builtin_memcpy(&nx[1], a.x + off + 8 * 196, 16);
   };
   auto fetch_params = [&](int ch, uint32_t (&w)[3], float& s, float& bb) __attribute__((always_inline)) {
-    const int8_t* wp = a.dw_w + (size_t)ch * 9;
-    uint32_t w0, w1, w2;
-    __builtin_memcpy(&w0, wp, 4);
-    __builtin_memcpy(&w1, wp + 3, 4);
-    __builtin_memcpy(&w2, wp + 5, 4);
-    w[0] = w0 & 0xffffffu;
-    w[1] = w1 & 0xffffffu;
-    w[2] = w2 >> 8;
+    dw_filter_rows3(a.dw_w + (size_t)ch * 9, w);
     s = a.dw_scale[ch];
     bb = (a.dw_bias ? a.dw_bias : a.dw_scale)[ch];  // no branch inside a round
     if (!a.dw_bias) bb = 0.f;
@@ -309,7 +296,7 @@ __device__ __forceinline__ void fused_dwpw14_body(const FusedArgs& a) {
     };
     auto finish = [&](auto o_c) __attribute__((always_inline)) {  // output row o is complete: requantise, into the image
       constexpr int o = decltype(o_c)::value;
-      const uint32_t pk = DWNN ? requant4_nn_rtz(dacc[o], dsc, dbi, dw_hi2, a.ones) : dw_requant4<ACT_LEAKY>(dacc[o], dsc, dbi, dw_leak, -254.f, 254.f);
+      const uint32_t pk = DWNN ? requant4_nn_rtz(dacc[o], dsc, dbi, dw_hi2, a.ones) : requant4<ACT_LEAKY>(dacc[o], dsc, dbi, dw_leak, -254.f, 254.f);
       *reinterpret_cast<uint32_t*>(fw_lds + (wb ^ (uint32_t)(o << 4))) = pk;
     };
     auto chunk = [&](auto t_c) __attribute__((always_inline)) {  // consume-only round: row chunk t's share of the MFMAs
@@ -452,6 +439,7 @@ __device__ __forceinline__ void fused_dwpw14_body(const FusedArgs& a) {
   if (OUT == OUT_I8) {
     // int8: the last round's 4 K-steps n-tile-major, so that tile n - 1 is requantised (fma / min / cvt: they overlap with the
     // matrix pipe) in the shadow of tile n's MFMAs; only the last tile's epilogue is exposed
+    // (requant_hi2 / requant_leak, plhip_device.h, written out: through the functions this unit's ISA moves)
     const float hi2 = g.act == ACT_RELU6 ? fminf(g.alpha + g.alpha, 254.f) : 254.f;
     const float leak = g.act == ACT_LEAKY ? g.alpha : 1.f;
     uint8_t* stg = fw_lds + (size_t)KS * FW_KSTEP + wave * (32 * MTW * FW_SP);
@@ -481,12 +469,12 @@ __device__ __forceinline__ void fused_dwpw14_body(const FusedArgs& a) {
 #pragma unroll
       for (int m = 0; m < MTW; ++m) {
         const float s2 = psc[m] + psc[m], b2 = pbi[m] + pbi[m];
-        uint32_t edw[4] = {0, 0, 0, 0};
+        uint32_t edw[4] = {0, 0, 0, 0};  // (tr_requant_chunk, gemm_tr_common.h, written out: the last tile skips its two dead groups)
 #pragma unroll
         for (int gq = 0; gq < 4; ++gq) {
           if (n == FW_NT - 1 && gq >= 2) continue;  // row 7 of the tile does not exist
           int v[4] = {acc[n][m][4 * gq], acc[n][m][4 * gq + 1], acc[n][m][4 * gq + 2], acc[n][m][4 * gq + 3]};
-          edw[gq] = PWNN ? requant4_nn_rtz(v, s2, b2, hi2, a.ones) : dw_requant4<ACT_LEAKY>(v, s2, b2, leak, -254.f, 254.f);
+          edw[gq] = PWNN ? requant4_nn_rtz(v, s2, b2, hi2, a.ones) : requant4<ACT_LEAKY>(v, s2, b2, leak, -254.f, 254.f);
         }
         // half exchange: every lane gets the 16 pixels of ONE output row of its channel (h = 0: row 2 n, h = 1: row 2 n + 1)
         auto s02 = __builtin_amdgcn_permlane32_swap(edw[0], edw[2], false, false);
@@ -549,8 +537,8 @@ __device__ __forceinline__ void fused_dwpw14_body(const FusedArgs& a) {
     uint32_t tid = threadIdx.x;
     asm volatile("" : "+v"(tid));
     const int h = (int)(tid >> 5) & 1;
-    const float fcap = g.act == ACT_RELU6 ? g.alpha : __builtin_huge_valf();
-    const float flo = (g.act == ACT_RELU || g.act == ACT_RELU6) ? 0.f : -__builtin_huge_valf();
+    const float fcap = f32_cap(g.act, g.alpha);
+    const float flo = f32_lo(g.act);
 #pragma unroll
     for (int m = 0; m < MTW; ++m) {
       const size_t chan = ((size_t)b * g.M + (mt0 + m) * 32 + c) * 196;
@@ -565,11 +553,7 @@ __device__ __forceinline__ void fused_dwpw14_body(const FusedArgs& a) {
           if (OUT == OUT_F32) {
             float f[4];
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              float y = __fmaf_rn((float)acc[n][m][4 * gq + e], psc[m], pbi[m]);
-              if (g.act == ACT_LEAKY) y = y > 0.f ? y : g.alpha * y;
-              f[e] = fminf(fmaxf(y, flo), fcap);
-            }
+            for (int e = 0; e < 4; ++e) f[e] = f32_clamped(acc[n][m][4 * gq + e], psc[m], pbi[m], g.act, g.alpha, flo, fcap);
             float* yp = reinterpret_cast<float*>(g.y) + off;
             if (col + 3 < 14) {
               const v4f v = {f[0], f[1], f[2], f[3]};

@@ -67,6 +67,7 @@ __global__ __launch_bounds__(512, K >= 1024 ? 1 : 2) void fused_dwpw7_kernel(Fus
   PLHIP_STAMP(1);
 
   // ------------------------------------------------------------------ produce
+  // (requant_hi2 / requant_leak, plhip_device.h, written out: through the functions this unit's ISA moves)
   const float dw_hi2 = a.dw_act == ACT_RELU6 ? fminf(a.dw_alpha + a.dw_alpha, 254.f) : 254.f;
   const float dw_leak = a.dw_act == ACT_LEAKY ? a.dw_alpha : 1.f;
   constexpr uint32_t plane_in = (uint32_t)(WI * WI);
@@ -155,7 +156,7 @@ __global__ __launch_bounds__(512, K >= 1024 ? 1 : 2) void fused_dwpw7_kernel(Fus
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
       const int v[4] = {dacc[4 * q], dacc[4 * q + 1], dacc[4 * q + 2], dacc[4 * q + 3]};
-      pk[q] = DWNN ? requant4_nn_rtz(v, dsc, dbi, dw_hi2, a.ones) : dw_requant4<ACT_LEAKY>(v, dsc, dbi, dw_leak, -254.f, 254.f);
+      pk[q] = DWNN ? requant4_nn_rtz(v, dsc, dbi, dw_hi2, a.ones) : requant4<ACT_LEAKY>(v, dsc, dbi, dw_leak, -254.f, 254.f);
     }
     const v2i pv2 = {(int)pk[0], (int)pk[1]};
     *reinterpret_cast<v2i*>(f7_lds + (uint32_t)ch * F7_PITCH + (uint32_t)o * 8) = pv2;
@@ -194,7 +195,7 @@ __global__ __launch_bounds__(512, K >= 1024 ? 1 : 2) void fused_dwpw7_kernel(Fus
   }
   // depthwise parameters of all K channels into LDS: (w0 w1 w2 0 | w3 w4 w5 0 | w6 w7 w8 0 | 2 scale | 2 bias)
   for (int i = tid; i < K; i += 512) {
-    const int8_t* wp = a.dw_w + (size_t)i * 9;
+    const int8_t* wp = a.dw_w + (size_t)i * 9;  // (dw_filter_rows3, dw_common.h, with the masks applied below: as a call this unit's ISA moves)
     uint32_t pw0, pw1, pw2;
     __builtin_memcpy(&pw0, wp, 4);
     __builtin_memcpy(&pw1, wp + 3, 4);
@@ -265,10 +266,11 @@ __global__ __launch_bounds__(512, K >= 1024 ? 1 : 2) void fused_dwpw7_kernel(Fus
   // ------------------------------------------------------------------ epilogue
   // accumulator register r of n tile n: slot 32 n + 8 (r >> 2) + 4 h + (r & 3) = (row slot >> 3, column slot & 7); lane (c, h)
   // owns channel 32 (mt0 + m) + c
+  // (requant_hi2 / requant_leak, plhip_device.h, written out: through the functions this unit's ISA moves)
   const float hi2 = g.act == ACT_RELU6 ? fminf(g.alpha + g.alpha, 254.f) : 254.f;
   const float leak = g.act == ACT_LEAKY ? g.alpha : 1.f;
-  const float fcap = g.act == ACT_RELU6 ? g.alpha : __builtin_huge_valf();
-  const float flo = (g.act == ACT_RELU || g.act == ACT_RELU6) ? 0.f : -__builtin_huge_valf();
+  const float fcap = f32_cap(g.act, g.alpha);
+  const float flo = f32_lo(g.act);
 #pragma unroll
   for (int m = 0; m < MW; ++m) {
     const int mch = (mt0 + m) * 32 + c;
@@ -286,9 +288,7 @@ __global__ __launch_bounds__(512, K >= 1024 ? 1 : 2) void fused_dwpw7_kernel(Fus
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
             if (e == 3 && (slot & 7) != 0) continue;  // (the junk slot of the row)
-            float y = __fmaf_rn((float)acc[n][m][4 * gq + e], sc, bi);
-            if (g.act == ACT_LEAKY) y = y > 0.f ? y : g.alpha * y;
-            part += fminf(fmaxf(y, flo), fcap);
+            part += f32_clamped(acc[n][m][4 * gq + e], sc, bi, g.act, g.alpha, flo, fcap);
           }
         }
       const float other = __shfl_xor(part, 32);
@@ -299,17 +299,11 @@ __global__ __launch_bounds__(512, K >= 1024 ? 1 : 2) void fused_dwpw7_kernel(Fus
     for (int n = 0; n < 2; ++n) {
       if (OUT == OUT_I8) {
         const float s2 = sc + sc, b2 = bi + bi;
-        uint32_t edw[4];
-#pragma unroll
-        for (int gq = 0; gq < 4; ++gq) {
-          int v[4] = {acc[n][m][4 * gq], acc[n][m][4 * gq + 1], acc[n][m][4 * gq + 2], acc[n][m][4 * gq + 3]};
-          edw[gq] = PWNN ? requant4_nn_rtz(v, s2, b2, hi2, a.ones) : dw_requant4<ACT_LEAKY>(v, s2, b2, leak, -254.f, 254.f);
-        }
-        // half exchange: every lane gets 16 consecutive slots = rows 4 n + 2 h, 4 n + 2 h + 1 of its channel
-        auto s02 = __builtin_amdgcn_permlane32_swap(edw[0], edw[2], false, false);
-        auto s13 = __builtin_amdgcn_permlane32_swap(edw[1], edw[3], false, false);
+        // every lane gets 16 consecutive slots = rows 4 n + 2 h, 4 n + 2 h + 1 of its channel
+        const v4i ch = PWNN ? tr_requant_chunk<ACT_RELU>(acc[n][m], s2, b2, leak, 0.f, hi2, a.ones)
+                            : tr_requant_chunk<ACT_LEAKY>(acc[n][m], s2, b2, leak, -254.f, 254.f);
         // (p0 .. p6 x | q0 .. q6 x) -> 14 contiguous bytes
-        const uint32_t A0 = s02[0], A1 = s02[1], A2 = s13[0], A3 = s13[1];
+        const uint32_t A0 = (uint32_t)ch[0], A1 = (uint32_t)ch[1], A2 = (uint32_t)ch[2], A3 = (uint32_t)ch[3];
         const uint32_t B1 = __builtin_amdgcn_perm(A2, A1, 0x04020100u);   // p4 p5 p6 q0
         const uint32_t B2 = __builtin_amdgcn_alignbyte(A3, A2, 1);        // q1 q2 q3 q4
         const uint32_t B3 = A3 >> 8;                                      // q5 q6
@@ -343,9 +337,7 @@ __global__ __launch_bounds__(512, K >= 1024 ? 1 : 2) void fused_dwpw7_kernel(Fus
           for (int e = 0; e < 4; ++e) {
             uint32_t v = (uint32_t)acc[n][m][4 * gq + e];
             if (OUT == OUT_F32) {
-              float y = __fmaf_rn((float)acc[n][m][4 * gq + e], sc, bi);
-              if (g.act == ACT_LEAKY) y = y > 0.f ? y : g.alpha * y;
-              v = __float_as_uint(fminf(fmaxf(y, flo), fcap));
+              v = __float_as_uint(f32_clamped(acc[n][m][4 * gq + e], sc, bi, g.act, g.alpha, flo, fcap));
             }
             if (e < 3 || col == 0) sp[e] = v;
           }

@@ -94,8 +94,8 @@ __global__ __launch_bounds__(256, M / MP >= 256 ? 2 : 3) void fused_dwpw_stream_
   const int colq = q == 0 ? 0 : (q == QW - 1 ? W - 8 : 4 * q - 1);
   const uint32_t sel_lo = q == 0 ? 0x0201000cu : (q == QW - 1 ? 0x06050403u : 0x03020100u);
   const uint32_t sel_hi = q == 0 ? 0x06050403u : (q == QW - 1 ? 0x0c0c0c07u : 0x07060504u);
-  const float dw_hi2 = a.dw_act == ACT_RELU6 ? fminf(a.dw_alpha + a.dw_alpha, 254.f) : 254.f;
-  const float dw_leak = a.dw_act == ACT_LEAKY ? a.dw_alpha : 1.f;
+  const float dw_hi2 = requant_hi2(a.dw_act, a.dw_alpha);
+  const float dw_leak = requant_leak(a.dw_act, a.dw_alpha);
   const uint32_t plane = (uint32_t)H * W, plane_in = (uint32_t)a.h * WI;
   // stride 2: a quad of 4 outputs reads input columns 8 q - 1 .. 8 q + 7.  The lane fetches the 12 aligned bytes from column
   // 8 q - 4 (d0 d1 d2): output j's window (columns 8 q + 2 j - 1 .. + 1) is bytes 3 + 2 j .. of them: three v_alignbyte and,
@@ -118,7 +118,7 @@ __global__ __launch_bounds__(256, M / MP >= 256 ? 2 : 3) void fused_dwpw_stream_
   uint32_t pw0 = 0, pw1 = 0, pw2 = 0;
   float psc0 = 0.f, pbi0 = 0.f;
   if ((int)threadIdx.x < K) {  // requested first; stored behind the row fetches below (nothing in front of them waits)
-    const int8_t* wp = a.dw_w + (size_t)threadIdx.x * 9;
+    const int8_t* wp = a.dw_w + (size_t)threadIdx.x * 9;  // (dw_filter_rows3, dw_common.h, with the masks applied at the store below)
     __builtin_memcpy(&pw0, wp, 4);
     __builtin_memcpy(&pw1, wp + 3, 4);
     __builtin_memcpy(&pw2, wp + 5, 4);
@@ -227,7 +227,7 @@ __global__ __launch_bounds__(256, M / MP >= 256 ? 2 : 3) void fused_dwpw_stream_
 #pragma unroll
     for (int o = 0; o < RS; ++o) {
       const uint32_t pk = DWNN ? requant4_nn_rtz(dacc[o], dsc, dbi, dw_hi2, a.ones)
-                               : dw_requant4<ACT_LEAKY>(dacc[o], dsc, dbi, dw_leak, -254.f, 254.f);
+                               : requant4<ACT_LEAKY>(dacc[o], dsc, dbi, dw_leak, -254.f, 254.f);
       if (SINK || active) *reinterpret_cast<uint32_t*>(fs_lds + ldsw + o * RP) = pk;
     }
   };
@@ -306,10 +306,10 @@ __global__ __launch_bounds__(256, M / MP >= 256 ? 2 : 3) void fused_dwpw_stream_
   // ------------------------------------------------------------------ consume, MP passes over the output channels
   const int vrows = H - tr0 < TR ? H - tr0 : TR;  // valid rows of this tile
   const int vpx = vrows * W;                      // (RP == W: valid pixels, a multiple of 16)
-  const float hi2 = g.act == ACT_RELU6 ? fminf(g.alpha + g.alpha, 254.f) : 254.f;
-  const float leak = g.act == ACT_LEAKY ? g.alpha : 1.f;
-  const float fcap = g.act == ACT_RELU6 ? g.alpha : __builtin_huge_valf();
-  const float flo = (g.act == ACT_RELU || g.act == ACT_RELU6) ? 0.f : -__builtin_huge_valf();
+  const float hi2 = requant_hi2(g.act, g.alpha);
+  const float leak = requant_leak(g.act, g.alpha);
+  const float fcap = f32_cap(g.act, g.alpha);
+  const float flo = f32_lo(g.act);
   auto pass = [&](auto self, auto mp_c) __attribute__((always_inline)) -> void {
     constexpr int mp = decltype(mp_c)::value;
     if constexpr (mp < MP) {
@@ -375,11 +375,11 @@ __global__ __launch_bounds__(256, M / MP >= 256 ? 2 : 3) void fused_dwpw_stream_
           const int px0 = (n0 + n) * 32;
           if (OUT == OUT_I8) {
             const float s2 = sc + sc, b2 = bi + bi;
-            uint32_t edw[4];
+            uint32_t edw[4];  // (tr_requant_chunk, gemm_tr_common.h, written out: as a call the control flow around the stores changes)
 #pragma unroll
             for (int gq = 0; gq < 4; ++gq) {
               int v[4] = {acc[n][m][4 * gq], acc[n][m][4 * gq + 1], acc[n][m][4 * gq + 2], acc[n][m][4 * gq + 3]};
-              edw[gq] = PWNN ? requant4_nn_rtz(v, s2, b2, hi2, a.ones) : dw_requant4<ACT_LEAKY>(v, s2, b2, leak, -254.f, 254.f);
+              edw[gq] = PWNN ? requant4_nn_rtz(v, s2, b2, hi2, a.ones) : requant4<ACT_LEAKY>(v, s2, b2, leak, -254.f, 254.f);
             }
             // half exchange: every lane gets 16 consecutive slots of its channel (h = 0: px0 + 0..15, h = 1: px0 + 16..31)
             auto s02 = __builtin_amdgcn_permlane32_swap(edw[0], edw[2], false, false);
@@ -418,7 +418,7 @@ __global__ __launch_bounds__(256, M / MP >= 256 ? 2 : 3) void fused_dwpw_stream_
               if (OUT == OUT_F32) {
                 float f[4];
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
+                for (int e = 0; e < 4; ++e) {  // (f32_clamped, gemm_tr_common.h, written out: as a call this unit's ISA moves)
                   float y = __fmaf_rn((float)acc[n][m][4 * gq + e], sc, bi);
                   if (g.act == ACT_LEAKY) y = y > 0.f ? y : g.alpha * y;
                   f[e] = fminf(fmaxf(y, flo), fcap);

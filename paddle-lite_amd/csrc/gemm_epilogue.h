@@ -40,8 +40,8 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, const v16i (&ac
   // address = per-lane part (image, column, the half's 4-row shift) + wave-uniform row offset: one 64-bit add per row
   // instead of a per-lane integer multiply (quarter rate) per row
   const size_t ylane = (size_t)b * g.y_bstride + hw + (size_t)(4 * h) * (uint32_t)g.HWY;
-  const float hi2 = ACT == ACT_RELU6 ? fminf(g.alpha + g.alpha, 254.f) : 254.f;
-  const float lo2 = (ACT == ACT_RELU || ACT == ACT_RELU6) ? 0.f : -254.f;
+  const float hi2 = requant_bounds<ACT>(g.alpha).hi2;
+  const float lo2 = requant_bounds<ACT>(g.alpha).lo2;
   // Fused residual operand: the 4 rows of group (a, gq) are fetched RD GROUPS AHEAD of their use.  Fetched where they are
   // used, every group's loads sit behind the previous group's stores in the in-order memory queue (the compiler may not
   // move a load above a store it cannot prove distinct) and the epilogue becomes one memory round trip per group:
@@ -151,8 +151,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, const v16i (&ac
               const float i2 = g.inv_scale2 + g.inv_scale2;
               packed = pack4_nn_rtz(i2 * f[0], i2 * f[1], i2 * f[2], i2 * f[3], 254.f);
             } else {
-              packed = pack4_i8(round_sat_i8(g.inv_scale2 * f[0]), round_sat_i8(g.inv_scale2 * f[1]),
-                                round_sat_i8(g.inv_scale2 * f[2]), round_sat_i8(g.inv_scale2 * f[3]));
+              packed = calib4_i8(v4f{f[0], f[1], f[2], f[3]}, g.inv_scale2);
             }
             int8_t* qp = g.y2 + yoff;
             if (VEC_STORE) {
@@ -169,7 +168,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, const v16i (&ac
         } else {
           const float s2 = sc[e], b2 = bi[e];  // staged already doubled for int8 output (store_scale_bias)
           const int vv[4] = {v0, v1, v2, v3};
-          uint32_t packed;
+          uint32_t packed;  // (requant4, plhip_device.h, written out: as a call gemm_i8's and the stem units' ISA moves)
           if (ACT == ACT_RELU || ACT == ACT_RELU6) {
             packed = pack4_nn_rtz(__fmaf_rn((float)vv[0], s2, b2), __fmaf_rn((float)vv[1], s2, b2), __fmaf_rn((float)vv[2], s2, b2),
                                   __fmaf_rn((float)vv[3], s2, b2), hi2);

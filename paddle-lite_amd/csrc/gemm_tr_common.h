@@ -48,38 +48,34 @@ __device__ __forceinline__ void store_chunk_i8(int8_t* p, uint32_t d0, uint32_t 
 
 // Requantise this wave's 128 (n) x 64 (m) accumulators and lay the int8 tile out in LDS as [64 m][144 B] rows.
 // Lane (c, h) owns channel rows 32u + c; register r of n tile t <-> n = 32t + 8(r>>2) + 4h + (r&3).  The requantisation
-// works on DOUBLED values (gemm_epilogue.h): y2 = fma(acc, 2s, 2b) = 2y exactly, t = trunc(clamp(y2)),
-// q = (t + 1 + (t >> 31)) >> 1; for relu / relu6 four results are packed first and (+1, >>1) finishes them at once.
-// Two v_permlane32_swap per tile then give every lane 16 consecutive columns of its row (h = 0: 32t + 0..15, h = 1:
-// 32t + 16..31): one ds_write_b128 per tile and row.  Pitch 144: the 8 lanes of a write group hit 8 distinct 16-byte
-// bank slots.
+// is requant4 (plhip_device.h) on each register group.  Two v_permlane32_swap per tile then give every lane 16 consecutive
+// columns of its row (h = 0: 32t + 0..15, h = 1: 32t + 16..31): one ds_write_b128 per tile and row.  Pitch 144: the 8 lanes
+// of a write group hit 8 distinct 16-byte bank slots.
 // one 32 (n) x 32 (m) accumulator tile -> this lane's 16 consecutive int8 columns of its channel row (chunk 2t + h)
 template <int ACT>
-__device__ __forceinline__ v4i tr_requant_chunk(const v16i& acc, float s2, float b2, float alpha, float lo2, float hi2) {
+__device__ __forceinline__ v4i tr_requant_chunk(const v16i& acc, float s2, float b2, float alpha, float lo2, float hi2,
+                                                uint32_t ones = 0x01010101u) {
   uint32_t dw[4];
 #pragma unroll
   for (int gq = 0; gq < 4; ++gq) {
-    if (ACT == ACT_RELU || ACT == ACT_RELU6) {
-      dw[gq] = pack4_nn_rtz(__fmaf_rn((float)acc[4 * gq], s2, b2), __fmaf_rn((float)acc[4 * gq + 1], s2, b2),
-                            __fmaf_rn((float)acc[4 * gq + 2], s2, b2), __fmaf_rn((float)acc[4 * gq + 3], s2, b2), hi2);
-    } else {
-      int qv[4];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        float y2 = __fmaf_rn((float)acc[4 * gq + e], s2, b2);
-        if (ACT == ACT_LEAKY) y2 = y2 > 0.f ? y2 : alpha * y2;
-        y2 = __builtin_amdgcn_fmed3f(y2, lo2, hi2);
-        const int tq = (int)y2;
-        qv[e] = (tq + 1 + (tq >> 31)) >> 1;
-      }
-      dw[gq] = pack4_i8(qv[0], qv[1], qv[2], qv[3]);
-    }
+    const int v[4] = {acc[4 * gq], acc[4 * gq + 1], acc[4 * gq + 2], acc[4 * gq + 3]};
+    dw[gq] = requant4<ACT>(v, s2, b2, alpha, lo2, hi2, ones);
   }
   // half exchange (lanes 32-63 of the first <-> lanes 0-31 of the second)
   auto s02 = __builtin_amdgcn_permlane32_swap(dw[0], dw[2], false, false);
   auto s13 = __builtin_amdgcn_permlane32_swap(dw[1], dw[3], false, false);
   const v4i v = {(int)s02[0], (int)s02[1], (int)s13[0], (int)s13[1]};
   return v;
+}
+
+// The fp32 output value of the fused depthwise -> 1x1 kernels, whose activation is a run-time argument: relu / relu6 are one
+// clamp to [lo, cap] (infinite where the activation has no bound), leaky is applied in front of it.
+__device__ __forceinline__ float f32_cap(int act, float alpha) { return act == ACT_RELU6 ? alpha : __builtin_huge_valf(); }
+__device__ __forceinline__ float f32_lo(int act) { return (act == ACT_RELU || act == ACT_RELU6) ? 0.f : -__builtin_huge_valf(); }
+__device__ __forceinline__ float f32_clamped(int acc, float s, float b, int act, float alpha, float lo, float cap) {
+  float y = __fmaf_rn((float)acc, s, b);
+  if (act == ACT_LEAKY) y = y > 0.f ? y : alpha * y;
+  return fminf(fmaxf(y, lo), cap);
 }
 
 // calib-only tail of an fp32-output conv (conv2d[fp32_out] -> calib with the fp32 value unused): the int8 value is
@@ -110,14 +106,13 @@ __device__ __forceinline__ void tr_stage_i8_calib(const v16i (&acc)[4][2], const
 template <int ACT>
 __device__ __forceinline__ void tr_stage_i8(const v16i (&acc)[4][2], const float (&sc)[2], const float (&bi)[2], float alpha,
                                             uint8_t* stg, int c, int h) {
-  const float hi2 = ACT == ACT_RELU6 ? fminf(alpha + alpha, 254.f) : 254.f;
-  const float lo2 = (ACT == ACT_RELU || ACT == ACT_RELU6) ? 0.f : -254.f;
+  const RequantBounds qb = requant_bounds<ACT>(alpha);
 #pragma unroll
   for (int u = 0; u < 2; ++u) {
     const float s2 = sc[u] + sc[u], b2 = bi[u] + bi[u];
 #pragma unroll
     for (int t = 0; t < 4; ++t)
-      *reinterpret_cast<v4i*>(stg + (32 * u + c) * 144 + (2 * t + h) * 16) = tr_requant_chunk<ACT>(acc[t][u], s2, b2, alpha, lo2, hi2);
+      *reinterpret_cast<v4i*>(stg + (32 * u + c) * 144 + (2 * t + h) * 16) = tr_requant_chunk<ACT>(acc[t][u], s2, b2, alpha, qb.lo2, qb.hi2);
   }
 }
 

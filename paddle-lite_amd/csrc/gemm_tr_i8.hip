@@ -396,8 +396,7 @@ __global__ __launch_bounds__(64 * WN * WM, 2) void gemm_i8_tr_kernel(GemmArgs g)
                 }
               }
               if (g.y2) {  // fused calib fp32 -> int8 of the value just produced (type_trans.cc:45,183-184)
-                const uint32_t packed = pack4_i8(round_sat_i8(g.inv_scale2 * f[0]), round_sat_i8(g.inv_scale2 * f[1]),
-                                                 round_sat_i8(g.inv_scale2 * f[2]), round_sat_i8(g.inv_scale2 * f[3]));
+                const uint32_t packed = calib4_i8(v4f{f[0], f[1], f[2], f[3]}, g.inv_scale2);
                 int8_t* qp = g.y2 + yoff;
                 if (whole) {
                   __builtin_memcpy(qp, &packed, 4);

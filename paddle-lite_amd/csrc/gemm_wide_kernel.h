@@ -265,10 +265,10 @@ __global__ __launch_bounds__(512, 2) void gemm_i8_wide_kernel(GemmArgs g) {
   // ---------------------------------------------------------------------------------------------------------------
   // phase 2: the flat MFMA sequence i = t * NG + j (tile t, K-step S1 + j); fragments two MFMAs ahead in a ring of 3 sets;
   // behind MFMA i the slices [j SPG, (j+1) SPG) of tile t-1's epilogue.
-  const float hi2 = g.act == ACT_RELU6 ? fminf(g.alpha + g.alpha, 254.f) : 254.f;
-  const float lo2 = NONNEG ? 0.f : -254.f;
+  const float hi2 = requant_hi2(g.act, g.alpha);
+  const float lo2 = NONNEG ? 0.f : -254.f;  // (requant_lo2, as the constant the template knows)
   const float s2 = sc + sc, b2 = bi + bi;
-  const float leak = g.act == ACT_LEAKY ? g.alpha : 1.f;                              // int8, !NONNEG: none = leaky with slope 1
+  const float leak = requant_leak(g.act, g.alpha);                                    // int8, !NONNEG: none = leaky with slope 1
   const float fcap = g.act == ACT_RELU6 ? g.alpha : __builtin_huge_valf();            // fp32: relu6 cap
   const float flo = (g.act == ACT_RELU || g.act == ACT_RELU6) ? 0.f : -__builtin_huge_valf();
   uint8_t* stg = ring + TILE_BYTES + wave * (32 * SP);

@@ -44,8 +44,7 @@ __device__ __forceinline__ float hard_act(float x, float p0, float p1, float p2)
 __device__ __forceinline__ void store4(float* __restrict__ yf, int8_t* __restrict__ yq, int64_t quad, const v4f& r, float inv) {
   if (yf) reinterpret_cast<v4f*>(yf)[quad] = r;
   if (yq)
-    reinterpret_cast<uint32_t*>(yq)[quad] =
-        pack4_i8(round_sat_i8(inv * r[0]), round_sat_i8(inv * r[1]), round_sat_i8(inv * r[2]), round_sat_i8(inv * r[3]));
+    reinterpret_cast<uint32_t*>(yq)[quad] = calib4_i8(r, inv);
 }
 
 __device__ __forceinline__ void store1(float* __restrict__ yf, int8_t* __restrict__ yq, int64_t i, float r, float inv) {

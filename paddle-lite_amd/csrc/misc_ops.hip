@@ -260,8 +260,7 @@ __global__ void calib_f32_to_i8_kernel(const float* __restrict__ x, int8_t* __re
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nq; i += stride) {
     const v4f v = reinterpret_cast<const v4f*>(x)[i];
-    reinterpret_cast<uint32_t*>(y)[i] = pack4_i8(round_sat_i8(inv_scale * v[0]), round_sat_i8(inv_scale * v[1]),
-                                                 round_sat_i8(inv_scale * v[2]), round_sat_i8(inv_scale * v[3]));
+    reinterpret_cast<uint32_t*>(y)[i] = calib4_i8(v, inv_scale);
   }
   for (int64_t t = (nq << 2) + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < count; t += stride)
     y[t] = (int8_t)round_sat_i8(inv_scale * x[t]);

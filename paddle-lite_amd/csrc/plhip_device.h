@@ -82,9 +82,57 @@ __device__ __forceinline__ uint32_t pack4_i8(int q0, int q1, int q2, int q3) {
   return lo | hi;
 }
 
-// calib_f32_to_i8_kernel's quantiser on a quad: four int8 in one dword (shuffle_ops.hip, interp_ops.hip)
+// calib_f32_to_i8_kernel's quantiser on a quad: four int8 in one dword
 __device__ __forceinline__ uint32_t calib4_i8(const v4f& v, float inv) {
   return pack4_i8(round_sat_i8(inv * v[0]), round_sat_i8(inv * v[1]), round_sat_i8(inv * v[2]), round_sat_i8(inv * v[3]));
+}
+
+// ---- THE int8 requantisation of the contract above, on DOUBLED values: with s2 = 2s, b2 = 2b, y2 = fma(acc, s2, b2) = 2y
+// exactly (power-of-two scaling commutes with rounding), t = trunc(clamp(act(y2), lo2, hi2)), q = (t + 1 + (t >> 31)) >> 1
+// as in round_sat_i8.  relu / relu6 are folded into the clamp; leaky on the doubled value is alpha * (2y) == 2 (alpha * y).
+//
+// Its clamp bounds: hi2 = min(2 alpha, 254) for relu6 (a half-integer alpha and 2 alpha > 254 both land where the reference's
+// clamp-then-round does: tests/edge_cases.py ACTS), lo2 = 0 for relu / relu6, and `leak`, the slope a kernel with a run-time
+// activation hands requant4<ACT_LEAKY> (none = leaky with slope 1).  Host (the depthwise launcher) and device compute them here.
+__host__ __device__ __forceinline__ float requant_hi2(int act, float alpha) {
+  return act == ACT_RELU6 ? fminf(alpha + alpha, 254.f) : 254.f;
+}
+__host__ __device__ __forceinline__ float requant_lo2(int act) { return (act == ACT_RELU || act == ACT_RELU6) ? 0.f : -254.f; }
+__host__ __device__ __forceinline__ float requant_leak(int act, float alpha) { return act == ACT_LEAKY ? alpha : 1.f; }
+struct RequantBounds {
+  float hi2, lo2, leak;
+};
+__host__ __device__ __forceinline__ RequantBounds requant_bounds(int act, float alpha) {
+  return {requant_hi2(act, alpha), requant_lo2(act), requant_leak(act, alpha)};
+}
+template <int ACT>
+__host__ __device__ __forceinline__ RequantBounds requant_bounds(float alpha) {
+  return requant_bounds(ACT, alpha);
+}
+
+// relu / relu6 requantisation of 4 accumulators (pack4_nn_rtz)
+__device__ __forceinline__ uint32_t requant4_nn_rtz(const int (&a)[4], float s2, float b2, float hi2, uint32_t ones = 0x01010101u) {
+  return pack4_nn_rtz(__fmaf_rn((float)a[0], s2, b2), __fmaf_rn((float)a[1], s2, b2), __fmaf_rn((float)a[2], s2, b2),
+                      __fmaf_rn((float)a[3], s2, b2), hi2, ones);
+}
+
+// 4 accumulators -> four int8 in one dword, for every activation.  ones: 0x01010101 (the byte-wise +1 of the packed rounding):
+// a parameter so that a caller can hand over a scalar kernel argument instead of a constant the compiler moves into a VGPR
+// again per use
+template <int ACT>
+__device__ __forceinline__ uint32_t requant4(const int (&a)[4], float s2, float b2, float alpha, float lo2, float hi2,
+                                             uint32_t ones = 0x01010101u) {
+  if (ACT == ACT_RELU || ACT == ACT_RELU6)  // (lo2 == 0: the conversion saturates negative values to it)
+    return requant4_nn_rtz(a, s2, b2, hi2, ones);
+  int q[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    float y2 = __fmaf_rn((float)a[j], s2, b2);
+    if (ACT == ACT_LEAKY) y2 = y2 > 0.f ? y2 : alpha * y2;
+    const int t = (int)__builtin_amdgcn_fmed3f(y2, lo2, hi2);
+    q[j] = (t + 1 + (t >> 31)) >> 1;
+  }
+  return pack4_i8(q[0], q[1], q[2], q[3]);
 }
 
 // 4x4 byte transpose: in r0..r3 (row j holds bytes for columns 0..3), out o[i] holds column i's

@@ -94,7 +94,8 @@ def test_descriptor_helpers(pkg):
 
 
 def test_round_half_away_integer_trick(plref):
-    """Device epilogue: q = (t + 1 + (t>>31)) >> 1, t = trunc(clamp(2y, -254, 254)) == clamp(roundf(y))."""
+    """Device epilogue (round_sat_i8 / requant4, csrc/plhip_device.h): q = (t + 1 + (t>>31)) >> 1, t = trunc(clamp(2y, -254, 254))
+    == clamp(roundf(y))."""
     rng = np.random.default_rng(5)
     y = np.concatenate([
         rng.uniform(-140, 140, 200000).astype(np.float32),
