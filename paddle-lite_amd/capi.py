@@ -193,13 +193,14 @@ KNOBS = ("STEM_MFMA", "CONV_PATCH", "CONV_PATCH_S2", "STEM7", "DW_STAGE", "DW_ST
 KNOBS_SET = {}
 
 
-TAIL_RESIDUAL, TAIL_INT8_COPY, TAIL_NO_F32, TAIL_UNALIGNED = 1, 2, 4, 8
+TAIL_RESIDUAL, TAIL_INT8_COPY, TAIL_NO_F32, TAIL_UNALIGNED, TAIL_X_UNALIGNED = 1, 2, 4, 8, 16
 
 
 def gemm_plan_text(d, out, tail=0):
     """The GEMM launch plan (csrc/gemm_plan.h) the library makes for conv descriptor d with output kind `out` and the fused tail
     `tail` (TAIL_* bits) under the knobs in force: 'name family=... grid=... lds=...'.  Pointers are assumed aligned unless
-    TAIL_UNALIGNED says that an output or the residual is off its vector alignment.  '' for a conv on a non-GEMM route.  Host
+    TAIL_UNALIGNED says that an output or the residual is off its vector alignment, TAIL_X_UNALIGNED that the input of a 1x1
+    conv is off a dword.  '' for a conv on a non-GEMM route.  Host
     only: launches nothing, needs no context."""
     buf = C.create_string_buffer(512)
     if load().plhip_debug_gemm_plan(C.byref(d), int(out), int(tail), buf, len(buf)) < 0:
@@ -564,19 +565,24 @@ class Context:
         wsb = self.L.plhip_conv_workspace_bytes(C.byref(d))
         return (s.alloc(wsb) if wsb else C.c_void_p()), wsb
 
-    def conv2d(self, d, x, w, scale, bias, out_kind, depthwise=False):
+    def conv2d(self, d, x, w, scale, bias, out_kind, depthwise=False, misalign=0, sentinel=None):
+        """plhip_conv2d_int8 / plhip_depthwise_conv_int8 on host arrays.  misalign: (x, y), as in conv2d_fused: x starts that
+        many BYTES past a 16-byte boundary, y that many ELEMENTS; one number stands for both.  sentinel: a byte value the output
+        allocation (MARGIN_GUARD more bytes on either side) is filled with first; the result is then (y, the bytes around y)."""
         oh, ow = out_hw(d)
+        xo, yo = (misalign,) * 2 if isinstance(misalign, int) else misalign
+        dtype = _OUT_DTYPE[out_kind]
         with self.scope() as s:
-            dx = s.put(x, np.int8)
+            dx = s.put(x, np.int8, off=xo)
             ds, db = s.put_opt(scale, np.float32), s.put_opt(bias, np.float32)
-            y = s.out((d.n, d.cout, oh, ow), _OUT_DTYPE[out_kind])
+            y = s.out((d.n, d.cout, oh, ow), dtype, np.dtype(dtype).itemsize * yo, sentinel, 0 if sentinel is None else MARGIN_GUARD)
             if depthwise:
                 self.check(self.L.plhip_depthwise_conv_int8(self.h, C.byref(d), dx, s.put(w, np.int8), ds, db, y.ptr, out_kind), "depthwise")
             else:
                 dwp = self._packed_conv(s, d, w)
                 dws, wsb = self._conv_workspace(s, d)
                 self.check(self.L.plhip_conv2d_int8(self.h, C.byref(d), dx, dwp, ds, db, y.ptr, out_kind, dws, wsb), "conv2d")
-            return y.get()
+            return y.get() if sentinel is None else (y.get(), y.margins())
 
     def conv2d_transpose(self, d, x, w, scale, bias, out_kind, misalign=0, sentinel=None):
         """plhip_conv2d_transpose_int8 on host arrays: x [n, cin, h, w], w [cin, cout / groups, kh, kw] (packed here).  misalign:

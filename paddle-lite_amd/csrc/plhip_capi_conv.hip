@@ -488,7 +488,8 @@ const char* plhip_conv_impl_name(const plhip_conv_desc* d) {
 // Diagnostics, host only (not in include/plhip.h; paddle-lite_amd/capi.py declares it): the GEMM launch plan (gemm_plan.h) of a
 // conv on one of the three GEMM routes, as text, from the route's own argument builder and the knobs in force, assuming aligned
 // pointers.  out: the output kind; tail: bit 0 a residual, bit 1 the int8 copy, bit 2 the fp32 output dropped, bit 3 an output or
-// residual pointer is off its vector alignment (what vec_store_ok answers for the call's pointers).  A non-GEMM route answers the
+// residual pointer is off its vector alignment (what vec_store_ok answers for the call's pointers), bit 4 the 1x1 route's x is
+// off a dword (what run_gemm_groups answers for its base).  A non-GEMM route answers the
 // empty string.  Returns the text's length, or -1 for a bad descriptor or buffer.
 int plhip_debug_gemm_plan(const plhip_conv_desc* d, int out, int tail, char* buf, size_t cap) {
   ConvGeom g;
@@ -500,7 +501,8 @@ int plhip_debug_gemm_plan(const plhip_conv_desc* d, int out, int tail, char* buf
   else if (r->impl == IMPL_IM2COL_GEMM) c = gemm_call(d, g, gemm_b_im2col(d, g), 0);
   else if (r->impl == IMPL_IMPLICIT_GEMM) c = implicit_call(d, g);
   else return 0;
-  plhip::GemmProblem p = plhip::gemm_problem(c.a, g.MA, out, c.vec_store && (tail & 8) == 0, c.aligned_loads);
+  const bool x_aligned = r->impl != IMPL_GEMM_1X1 || (tail & 16) == 0;  // (the other two routes read their own workspace copy)
+  plhip::GemmProblem p = plhip::gemm_problem(c.a, g.MA, out, c.vec_store && (tail & 8) == 0, c.aligned_loads && x_aligned);
   p.res = (tail & 1) != 0;
   p.y2 = (tail & 2) != 0;
   p.y = (tail & 4) == 0;

@@ -233,7 +233,7 @@ def kernel_for(route, out):
 
 # the value each knob has when nobody set it (the launchers' defaults)
 KNOB_DEFAULTS = {"GEMM_VARIANT": 0, "GEMM_AREG": 1, "GEMM_MA": 0, "WIDE_NTT": 0, "DW_STAGE": 1, "DW_FASTV": 1, "DW5_DIRECT": 1,
-                 "FC_MFMA": 0}
+                 "FC_MFMA": 0, "GEMM_TR": 1, "TR_CFG": 3, "GEMM_WIDE": 1}
 # the dw stage's activation of a fused pair, cycled against the pw stage's
 DW_ACTS = ((ACT_RELU6, 60.5), (ACT_LEAKY, 0.375), (ACT_NONE, 0.0), (ACT_RELU, 0.0), (ACT_RELU6, 200.5))
 

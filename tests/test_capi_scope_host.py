@@ -264,3 +264,32 @@ def test_helpers_keep_every_pointer_residue(pkg, monkeypatch):
     assert sorted(got) == sorted(PARENT_RESIDUES)
     for label in PARENT_RESIDUES:
         assert got[label] == PARENT_RESIDUES[label], label
+
+
+def test_conv2d_places_x_and_y_and_returns_the_margins(pkg, monkeypatch):
+    """Context.conv2d over the stub library, as conv2d_fused (test_tail_cases.py): x lies misalign[0] bytes and y misalign[1]
+    elements past a 16-byte boundary, every other operand on one; with a sentinel the allocation comes back filled around the
+    tensor, and without either argument the call is what it always was."""
+    capi = pkg.capi
+    d = capi.conv_desc(1, 16, 4, 4, 8, 1, 1)
+    x, w, sc = np.zeros((1, 16, 4, 4), np.int8), np.zeros((8, 16, 1, 1), np.int8), np.ones(8, F32)
+
+    def call(out_kind, **kw):
+        ctx, lib = stub_context(capi, monkeypatch)
+        r = ctx.conv2d(d, x, w, sc, None, out_kind, **kw)
+        assert ctx.outstanding() == 0 and not lib.live
+        return r, dict(lib.calls)["plhip_conv2d_int8"]
+    # x, packed weights, scale, bias, y, workspace
+    r, got = call(capi.OUT_F32)
+    assert got == [0, 0, 0, None, 0, 0] and r.shape == (1, 8, 4, 4) and r.dtype == F32
+    r, got = call(capi.OUT_F32, misalign=(3, 1), sentinel=0xA5)
+    assert got == [3, 0, 0, None, 4, 0]
+    y, m = r
+    assert y.shape == (1, 8, 4, 4) and y.dtype == F32 and (y.view(np.uint8) == 0xA5).all()
+    assert m.dtype == np.uint8 and m.size == 2 * capi.MARGIN_GUARD + 4 + capi.SCOPE_SLACK and (m == 0xA5).all()
+    r, got = call(capi.OUT_I8, misalign=(0, 3), sentinel=0x80)
+    assert got == [0, 0, 0, None, 3, 0] and r[0].dtype == np.int8 and (r[0] == -128).all() and r[1].size == 2 * capi.MARGIN_GUARD + 3 + capi.SCOPE_SLACK
+    r, got = call(capi.OUT_I32, misalign=2)
+    assert got == [2, 0, 0, None, 8, 0] and r.dtype == np.int32
+    r, got = call(capi.OUT_I8, sentinel=0)
+    assert got == [0, 0, 0, None, 0, 0] and (r[1] == 0).all() and r[1].size == 2 * capi.MARGIN_GUARD + capi.SCOPE_SLACK
