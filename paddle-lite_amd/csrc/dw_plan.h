@@ -190,15 +190,26 @@ inline bool direct_plan(const DwProblem& a, const DwKnobs& kn, DwPlan* out) {
 }
 
 // the streaming kernel's instances: MobileNetV1's pairs on the large planes
-struct StreamShape { int W, S, K, M, TP, RS, PD, MP; };  // W = output plane width
+// ROWS: the produce stage takes its input rows as 16-byte pieces through a wave-private LDS stage (stream_rows.h) instead of
+// row windows straight from global memory.  The stage is STATIC LDS of the kernel instance: no part of DwPlan::lds, not printed
+// by dw_plan_text.  On for the stride-1 pairs at 112 and 56 (46.7 / 43.1 -> 38.2 / 39.0 us and 38.4 / 38.6 -> 36.1 / 36.3 us in
+// the serial step).  Off where the stage does not fit (256 -> 256 @28: 80 KiB are half a CU), where the kernel is not
+// VALU-bound (14), and for the stride-2 pairs onto 56 and 28: staged they issue 33 / 60 fewer VALU and 20 / 33 fewer vector
+// loads per wave and ran 29.5 / 30.6 -> 31.7 / 33.6 us and 21.7 / 21.0 -> 23.7 / 23.3 us (DESIGN 8.2 "Rows staged").
+struct StreamShape { int W, S, K, M, TP, RS, PD, MP; bool ROWS; };  // W = output plane width
 constexpr StreamShape kStreamShapes[] = {
-    {112, 1, 32, 64, 448, 4, 2, 1},   // 4-row tiles of 448 pixels (2-row tiles fetched and cut every input row twice: 61 us, the two kernels 56)
-    {56, 1, 128, 128, 224, 4, 2, 1},
-    {28, 1, 256, 256, 224, 4, 2, 1},
-    {56, 2, 64, 128, 224, 4, 2, 1},
-    {28, 2, 128, 256, 224, 4, 2, 1},
-    {14, 2, 256, 512, 128, 7, 2, 2},  // half images, M in two passes
+    {112, 1, 32, 64, 448, 4, 2, 1, true},   // 4-row tiles of 448 pixels (2-row tiles fetched and cut every input row twice: 61 us, the two kernels 56)
+    {56, 1, 128, 128, 224, 4, 2, 1, true},
+    {28, 1, 256, 256, 224, 4, 2, 1, false},
+    {56, 2, 64, 128, 224, 4, 2, 1, false},
+    {28, 2, 128, 256, 224, 4, 2, 1, false},
+    {14, 2, 256, 512, 128, 7, 2, 2, false},  // half images, M in two passes
 };
+constexpr bool stream_rows_staged(int W, int S) {
+  for (const StreamShape& t : kStreamShapes)
+    if (t.W == W && t.S == S) return t.ROWS;
+  return false;
+}
 // the 7 x 7 kernel's: MobileNetV1's last two pairs
 struct SmallShape { int S, K, M; };
 constexpr SmallShape kSmallShapes[] = {{2, 512, 1024}, {1, 1024, 1024}};
@@ -247,7 +258,10 @@ inline DwPlan dwpw_launch_plan(const DwProblem& a, const DwKnobs& kn) {
       p.grid_x = round8(p.tiles);
       p.block = 256;
       // image, depthwise parameters, sink of the idle lanes (256 -> 256 @28 has none: its 80 KiB are exactly half a CU's LDS,
-      // and 512 bytes more made it one block per CU: 28.3 -> 34.0 us)
+      // and 512 bytes more made it one block per CU: 28.3 -> 34.0 us).
+      // The row stage of the ROWS shapes (4 waves x stream_rows::Rows::WB = 6.25 KiB at 112 and at 56 wide) is STATIC LDS of the
+      // kernel instance and no part of lds=: this is the dynamic size the launch asks for, the one dw_plan_text prints and
+      // tests/golden/dw_plans pins; the kernel asserts static + dynamic bytes x blocks per CU against the CU's 160 KiB.
       p.lds = (size_t)t.K * fs_pitch(t.TP) + (size_t)t.K * 32 + (t.M / t.MP < 256 ? 512 : 0);
       return p;
     }

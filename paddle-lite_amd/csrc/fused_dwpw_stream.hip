@@ -16,6 +16,16 @@
 //     windows placed by v_perm_b32, taps on v_dot4_i32_i8, the reference's requantisation) writes each requantised dword into
 //     the activation image in LDS: image[k][288 B]: pixel-linear rows, pitch 288 = 72 dwords = 8 (mod 64) so that the 8 rows x
 //     2 chunks a half-wave's ds_read_b64_tr_b8 touches fall into distinct banks without a swizzle;
+//   * ROWS (StreamShape::ROWS, dw_plan.h: on for 32 -> 64 @112 and 128 -> 128 @56; the stride-2 pairs onto 56 and 28 have
+//     the form too, measured slower and are switched off; geometry and its host walk: stream_rows.h,
+//     tests/test_stream_rows_host.py): a (channel, strip)'s input rows are ONE contiguous span of global memory: a wave
+//     fetches the spans of its groups as aligned 16-byte pieces, one per lane and load (2 loads instead of 6 row windows at
+//     stride 1, 4 | 5 instead of 9 at stride 2; address = wave-uniform base + one per-lane offset computed once).  The
+//     pieces of PD iterations wait in registers; once an iteration's windows have been read the next iteration's pieces go
+//     into a wave-private stage (wave-local order, no barrier) of padded rows: column -1 and column WI are zero bytes that
+//     are already there, a lane's window is three aligned dwords of LDS and three v_alignbyte_b32: no v_perm_b32, no border
+//     mask, no shifted fetch at the tensor's ends.  The stage is STATIC LDS of the instance (zero bytes in the register-path
+//     instances), not part of the launch plan's lds=, which stays the dynamic size;
 //   * one barrier; consume: a wave owns M / 4 output channels (m tiles) for all 7 n tiles (M = 64: 2 m x 2 n splits), its weight
 //     fragments straight from L2 (each byte of the weights once per block), K-outer; epilogue: requantise, two
 //     v_permlane32_swap give a lane 16 consecutive pixels of one channel = one aligned 16-byte store.
@@ -27,10 +37,26 @@
 #include "plhip_kernels.h"
 #include "dw_common.h"
 #include "gemm_tr_common.h"
+#include "stream_rows.h"
 
 namespace plhip {
 
 typedef float v2f __attribute__((ext_vector_type(2)));
+
+// the row stage of the ROWS forms: static LDS of the instance (4 waves x Rows::WB bytes), in front of the dynamic bytes the
+// launch plan asks for; the register-path instances never name it and have none
+template <int BYTES>
+__device__ __forceinline__ uint8_t* fs_row_stage() {
+  __shared__ __attribute__((aligned(16))) uint8_t stage[BYTES];
+  return stage;
+}
+// LDS of one wave, written and read by different lanes: the hardware runs a wave's LDS instructions in order; this keeps the
+// compiler from reordering them
+__device__ __forceinline__ void fs_wave_order() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
 
 // TP pixels per tile (224 or 448 = 7 or 14 n tiles); LDS bytes per channel row of the activation image: TP + pad with
 // pitch / 4 = 8 (mod 16): 160 / 288 / 544
@@ -67,6 +93,14 @@ __global__ __launch_bounds__(256, M / MP >= 256 ? 2 : 3) void fused_dwpw_stream_
   constexpr int WI = S * W;                                 // input plane width
   static_assert(S == 1 || S == 2, "stride");
   static_assert(TR * RP <= FS_TP && TR % RS == 0 && K % 32 == 0 && M % (32 * MP) == 0 && MT % MSPLIT == 0, "geometry");
+  // ROWS (dw_plan.h): the input rows come as 16-byte pieces through a wave-private LDS stage (geometry: stream_rows.h)
+  constexpr bool ROWS = dw_plan_detail::stream_rows_staged(W, S);
+  constexpr stream_rows::Rows RG = {W, S, K, RS, TP};
+  constexpr int NL = ROWS ? RG.NL() : 1, UPP = ROWS ? RG.UPP() : 1, STAGE_BYTES = ROWS ? 4 * RG.WB() : 0;
+  static_assert(!ROWS || (RG.ok() && RP == W && RG.G() == G && RG.NIN() == NIN && RG.NIT() == NIT && RG.NGRP() == NGRP && NGRP >= 4 * G), "row stage");
+  // static + dynamic LDS (dwpw_launch_plan's lds) of the blocks a CU holds: the launch bounds' 3 | 2, 4 at 112 wide (119 VGPRs)
+  constexpr int DYN_BYTES = K * FS_PITCH + K * 32 + (M / MP < 256 ? 512 : 0), BPC = W == 112 ? 4 : (M / MP >= 256 ? 2 : 3);
+  static_assert(!ROWS || (STAGE_BYTES + DYN_BYTES <= 64 * 1024 && (STAGE_BYTES + DYN_BYTES) * BPC <= 160 * 1024), "LDS of a CU");
   const GemmArgs& g = a.pw;
   PLHIP_PRELOAD(a.x); PLHIP_PRELOAD(a.dw_w); PLHIP_PRELOAD(a.dw_scale); PLHIP_PRELOAD(a.dw_bias); PLHIP_PRELOAD(a.dw_act);
   PLHIP_PRELOAD(a.dw_alpha); PLHIP_PRELOAD(a.n); PLHIP_PRELOAD(a.h); PLHIP_PRELOAD(a.tiles); PLHIP_PRELOAD(a.ones); PLHIP_PRELOAD(g.wp);
@@ -110,6 +144,41 @@ __global__ __launch_bounds__(256, M / MP >= 256 ? 2 : 3) void fused_dwpw_stream_
   // PD iterations of operands in flight (a ring of PD register sets): an iteration is ~100-150 VALU, a fetch from HBM under
   // load ~2 us: with one iteration ahead every wave waited for its rows (first form: 61 / 45 / 33 us for the three pairs)
   uint32_t in[PD][NIN][ND];  // row windows
+  // ROWS: a ring of PD iterations of pieces, NL loads of one 16-byte piece per lane: address = wave-uniform base of the
+  // iteration + a per-lane offset that does not change (Rows::lane_piece; the strips of a wave's lanes repeat every iteration).
+  // No load leaves the tensor: a piece lies inside the group's own plane, the pieces of a row outside the image (first / last
+  // strip of a plane; the filter row against them is zero) are fetched one row further in, and the 8 junk bytes around a
+  // 56-byte-row span belong to the neighbouring rows of the same plane (strips start on multiples of 4 rows).
+  v4i pc[PD][NL];
+  // load 0's per-lane byte offset and stage addresses (load l: a wave-uniform step and a constant more); where the last load
+  // has lanes without a group (RAGGED), its own
+  constexpr bool RAGGED = ROWS && RG.ragged();
+  uint32_t poff = 0, poff_r = 0;
+  uint8_t *pdst[UPP], *pdst_r[UPP];
+  const uint8_t* wsrc = nullptr;  // the lane's window of row 0
+  if constexpr (ROWS) {
+    uint8_t* const st = fs_row_stage<STAGE_BYTES>() + wave * RG.WB();
+    const stream_rows::LanePiece lp = RG.lane_piece(wave * G, lane, 0, tr0, H, false);
+    const stream_rows::LanePiece lr = RG.lane_piece(wave * G, lane, NL - 1, tr0, H, false);
+    poff = (uint32_t)lp.off;
+    poff_r = (uint32_t)lr.off;
+#pragma unroll
+    for (int e = 0; e < UPP; ++e) {
+      pdst[e] = st + lp.dst[e];
+      pdst_r[e] = st + lr.dst[e];
+    }
+    wsrc = st + RG.window_off(active ? gl : 0, 0, q);
+    // the pads (column -1 and column WI of every row): zeroed once, never written again; 16 lanes per group
+    static_assert(NIN + 1 <= 16, "pads of a group");
+#pragma unroll
+    for (int g0 = 0; g0 < G; g0 += 4) {
+      const int pg = g0 + (lane >> 4), pk = lane & 15;
+      if (pk <= NIN && pg < G) {
+        if constexpr (RG.U() == 16) *reinterpret_cast<v4i*>(st + RG.pad_off(pg, pk)) = v4i{0, 0, 0, 0};
+        else *reinterpret_cast<v2i*>(st + RG.pad_off(pg, pk)) = v2i{0, 0};
+      }
+    }
+  }
   // depthwise parameters of all K channels, once per block, into LDS: (w0 w1 w2 0 | w3 w4 w5 0 | w6 w7 w8 0 | 2 scale | 2 bias):
   // per iteration a lane then reads ONE 16-byte and one 4-byte LDS word instead of five global loads (the vector-memory
   // instructions were the startup cost of a block: 44 per wave, 6.7 k cycles to issue with four blocks per CU)
@@ -159,7 +228,38 @@ __global__ __launch_bounds__(256, M / MP >= 256 ? 2 : 3) void fused_dwpw_stream_
       }
     }
   };
-  auto compute = [&](auto it_c) __attribute__((always_inline)) {
+  auto fetch_rows = [&](auto it_c) __attribute__((always_inline)) {
+    constexpr int it = decltype(it_c)::value, s = it % PD;
+    constexpr bool SURPLUS = (it + 1) * 4 * G > NGRP;  // the last iteration repeats the last group: its own offsets
+    const int gi0 = (it * 4 + wave) * G;
+    // (wave-uniform; in front of the tensor for its very first strip, whose lanes all add at least that much)
+    const uint8_t* const base = reinterpret_cast<const uint8_t*>(a.x) + (ptrdiff_t)RG.wave_base(b, gi0, tr0, H);
+#pragma unroll
+    for (int l = 0; l < NL; ++l) {
+      const uint8_t* src;
+      if constexpr (SURPLUS) src = base + (uint32_t)RG.lane_piece(gi0, lane, l, tr0, H).off;
+      else if (RAGGED && l == NL - 1) src = base + poff_r;
+      else src = base + (size_t)((uint32_t)l * (uint32_t)RG.src_step(H)) + poff;
+      pc[s][l] = *reinterpret_cast<const v4i*>(src);
+    }
+  };
+  auto stage_rows = [&](auto it_c) __attribute__((always_inline)) {
+    constexpr int s = decltype(it_c)::value % PD;
+#pragma unroll
+    for (int l = 0; l < NL; ++l) {
+      const bool r = RAGGED && l == NL - 1;
+      uint8_t* const d0 = r ? pdst_r[0] : pdst[0] + l * RG.dst_step();
+      uint8_t* const d1 = r ? pdst_r[UPP - 1] : pdst[UPP - 1] + l * RG.dst_step();
+      if constexpr (UPP == 1) {
+        *reinterpret_cast<v4i*>(d0) = pc[s][l];
+      } else {
+        *reinterpret_cast<v2i*>(d0) = v2i{pc[s][l][0], pc[s][l][1]};
+        *reinterpret_cast<v2i*>(d1) = v2i{pc[s][l][2], pc[s][l][3]};
+      }
+    }
+  };
+  // mid(): runs between the taps and the requantisation (ROWS: every window has been read, the stage takes the next iteration)
+  auto compute = [&](auto it_c, auto mid) __attribute__((always_inline)) {
     constexpr int it = decltype(it_c)::value, s = it % PD;
     int ch, strip, r0;
     task(it, ch, strip, r0);
@@ -182,12 +282,23 @@ __global__ __launch_bounds__(256, M / MP >= 256 ? 2 : 3) void fused_dwpw_stream_
 #pragma unroll
     for (int t = 0; t < NIN; ++t) {
       uint32_t win[4];
+      // ROWS: the three aligned dwords around the quad from the stage: columns 4 S q - 4 .. 4 S q + 7, the padding columns are
+      // zero bytes that are already there
+      const uint32_t* const rw = ROWS ? reinterpret_cast<const uint32_t*>(wsrc + t * RG.P()) : nullptr;
       if constexpr (S == 1) {
-        const uint32_t e0 = __builtin_amdgcn_perm(in[s][t][1], in[s][t][0], sel_lo), e1 = __builtin_amdgcn_perm(in[s][t][1], in[s][t][0], sel_hi);
-        win[0] = e0;
-        win[1] = __builtin_amdgcn_alignbyte(e1, e0, 1);
-        win[2] = __builtin_amdgcn_alignbyte(e1, e0, 2);
-        win[3] = __builtin_amdgcn_alignbyte(e1, e0, 3);
+        if constexpr (ROWS) {
+          const uint32_t d0 = rw[0], d1 = rw[1], d2 = rw[2];
+          win[0] = __builtin_amdgcn_alignbyte(d1, d0, 3);
+          win[1] = d1;
+          win[2] = __builtin_amdgcn_alignbyte(d2, d1, 1);
+          win[3] = __builtin_amdgcn_alignbyte(d2, d1, 2);
+        } else {
+          const uint32_t e0 = __builtin_amdgcn_perm(in[s][t][1], in[s][t][0], sel_lo), e1 = __builtin_amdgcn_perm(in[s][t][1], in[s][t][0], sel_hi);
+          win[0] = e0;
+          win[1] = __builtin_amdgcn_alignbyte(e1, e0, 1);
+          win[2] = __builtin_amdgcn_alignbyte(e1, e0, 2);
+          win[3] = __builtin_amdgcn_alignbyte(e1, e0, 3);
+        }
 #pragma unroll
         for (int r = 0; r < 3; ++r) {
           const int o = t - r;
@@ -198,8 +309,8 @@ __global__ __launch_bounds__(256, M / MP >= 256 ? 2 : 3) void fused_dwpw_stream_
                                  : __builtin_amdgcn_sdot4((int)win[jj], (int)(t == NIN - 1 ? w2b : wr[r]), dacc[o][jj], false);
         }
       } else {
-        uint32_t d0 = in[s][t][0], d1 = in[s][t][1], d2 = in[s][t][2];
-        if (t < 2) {  // the lane that fetched from column 0
+        uint32_t d0 = ROWS ? rw[0] : in[s][t][0], d1 = ROWS ? rw[1] : in[s][t][1], d2 = ROWS ? rw[2] : in[s][t][2];
+        if (!ROWS && t < 2) {  // the lane that fetched from column 0
           d2 = fix ? d1 : d2;
           d1 = fix ? d0 : d1;
         }
@@ -207,7 +318,7 @@ __global__ __launch_bounds__(256, M / MP >= 256 ? 2 : 3) void fused_dwpw_stream_
           d0 = fixe ? d1 : d0;
           d1 = fixe ? d2 : d1;
         }
-        win[0] = __builtin_amdgcn_alignbyte(d1, d0, 3) & m0;
+        win[0] = __builtin_amdgcn_alignbyte(d1, d0, 3) & (ROWS ? 0xffffffffu : m0);  // (ROWS: column -1 is a zero byte of the stage)
         win[1] = __builtin_amdgcn_alignbyte(d2, d1, 1);
         win[2] = __builtin_amdgcn_alignbyte(d2, d1, 3);
         win[3] = d2;  // against the filter row moved up one byte
@@ -224,6 +335,7 @@ __global__ __launch_bounds__(256, M / MP >= 256 ? 2 : 3) void fused_dwpw_stream_
         }
       }
     }
+    mid();
 #pragma unroll
     for (int o = 0; o < RS; ++o) {
       const uint32_t pk = DWNN ? requant4_nn_rtz(dacc[o], dsc, dbi, dw_hi2, a.ones)
@@ -234,7 +346,8 @@ __global__ __launch_bounds__(256, M / MP >= 256 ? 2 : 3) void fused_dwpw_stream_
   auto prime = [&](auto self, auto it_c) __attribute__((always_inline)) -> void {
     constexpr int it = decltype(it_c)::value;
     if constexpr (it < PD && it < NIT) {
-      fetch(it_c);
+      if constexpr (ROWS) fetch_rows(it_c);
+      else fetch(it_c);
       self(self, integral_constant<int, it + 1>{});
     }
   };
@@ -290,11 +403,29 @@ __global__ __launch_bounds__(256, M / MP >= 256 ? 2 : 3) void fused_dwpw_stream_
     o[4] = a.dw_bias ? __float_as_uint(pbi0 + pbi0) : 0u;
   }
   __syncthreads();  // the parameters are in LDS (the row fetches above are in flight meanwhile)
+  // ROWS: iteration it + 1 goes from its registers into the stage once the windows of iteration it have been read (wave-local
+  // order, no barrier), the freed register set takes iteration it + 1 + PD, and the write's way through LDS lies under the
+  // requantisation of iteration it:
+  // PD iterations wait in registers while one is computed
+  auto stage_next = [&](auto it_c) __attribute__((always_inline)) {
+    constexpr int it = decltype(it_c)::value;
+    if constexpr (it < NIT) {
+      fs_wave_order();
+      stage_rows(it_c);
+      fs_wave_order();
+      if constexpr (it + PD < NIT) fetch_rows(integral_constant<int, it + PD>{});
+    }
+  };
+  if constexpr (ROWS) stage_next(integral_constant<int, 0>{});
   auto steps = [&](auto self, auto it_c) __attribute__((always_inline)) -> void {
     constexpr int it = decltype(it_c)::value;
     if constexpr (it < NIT) {
-      compute(it_c);
-      if constexpr (it + PD < NIT) fetch(integral_constant<int, it + PD>{});
+      if constexpr (ROWS) {
+        compute(it_c, [&]() __attribute__((always_inline)) { stage_next(integral_constant<int, it + 1>{}); });
+      } else {
+        compute(it_c, []() {});
+        if constexpr (it + PD < NIT) fetch(integral_constant<int, it + PD>{});
+      }
       self(self, integral_constant<int, it + 1>{});
     }
   };
